@@ -17,8 +17,13 @@ A step = clear + decode/rasterize every loaded batch + (merge) + resolve, inputs
 frame, the clear and the next frame's cull/LOD prepass share one launch, pcr_frame_turn).
 Before the W warm-up steps the frame loop runs for --preroll seconds (not counted as warm-up, not timed): the clocks of a
 fresh box settle in that time, so a 20-step run reports what a 200-step run reports.
-At N = 1 the line also carries `secondary`: the reference-default row (LOD 10 % + culling), the HQS method and
-4096x4096 with culling (configs[2], configs[4]'s one-GPU half), 20 steps each on the same resident stream.
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, `config`). --full adds everything else, as before: per-launch kernel events in the
+timed steps and the roofline built on them, the distribution of single steps, the measured HBM ceiling, the other stream
+layout (`variants`), the CPU oracle baseline with its full-size parity check, and at N = 1 `secondary`: the reference-default
+row (LOD 10 % + culling), the HQS method and 4096x4096 with culling (configs[2], configs[4]'s one-GPU half), 20 steps
+each on the same resident stream, the 10-10-10 method and the GPU encoder.
+--dump-outputs DIR writes what the last timed step computed, as rank 0's caller receives it (dump_outputs below).
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -67,9 +72,14 @@ def parse_args():
                          "collectives on torch-owned int64 frames; rccl = the C++ layer unchecked")
     ap.add_argument("--batches", type=int, default=0, help="experiments: load only the first N batches of this rank's shard")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED)
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: kernel events + roofline, step distribution, HBM ceiling, the other layout, "
+                         "CPU baseline + parity, secondary rows (the --no-* options below trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-variants", action="store_true", help="skip the second pass with the other stream layout")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary rows (LOD 10 % + cull, HQS, 4096x4096 + cull)")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary rows (LOD 10 %% + cull, HQS, 4096x4096 + cull)")
     ap.add_argument("--no-kernel-events", action="store_true",
                     help="keep the per-launch kernel events out of the timed steps (A/B of their overhead)")
     ap.add_argument("--cpu-sample-batches", type=int, default=0, help="0 = automatic (bounded)")
@@ -201,6 +211,28 @@ def scaling_base(P, total_points, args):
                 "kernel_version": d["roofline"]["kernel_version"], "this_kernel_version": P.kernel_version(), "source": SCALING_BASE_FILE}
     except Exception as e:
         return {"value": None, "why": "%s unreadable: %s" % (SCALING_BASE_FILE, e)}
+
+
+DUMP_IMAGE_BYTES = 48 << 20        # float32 image at most; above it a fixed sample of its pixels (1920x1080: whole, 33 MB)
+STATS_FIELDS = ("batches_total", "batches_culled", "points_iterated", "batches_double")
+
+
+def dump_outputs(dirname, rgba, width, height, stats):
+    """What the last timed step handed its caller: rgba.npy, the resolved RGBA8 image as float32 [height, width, 4] (bytes in
+    memory order), and stats.npy, the render counters (pcr_get_stats, STATS_FIELDS order) as float64. An image larger than
+    DUMP_IMAGE_BYTES goes out as rgba_sample.npy [k, 4] with the pixel indices in rgba_sample_index.npy: a seeded choice, the
+    same for every run of one image size."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    img = rgba.view(np.uint8).reshape(height, width, 4).astype(np.float32)
+    if img.nbytes <= DUMP_IMAGE_BYTES:
+        np.save(os.path.join(dirname, "rgba.npy"), img)
+    else:
+        k = DUMP_IMAGE_BYTES // 24          # 16 B of pixel + 8 B of index each
+        idx = np.sort(np.random.default_rng(0x5EED).choice(width * height, k, replace=False))
+        np.save(os.path.join(dirname, "rgba_sample.npy"), img.reshape(-1, 4)[idx])
+        np.save(os.path.join(dirname, "rgba_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(dirname, "stats.npy"), np.array([stats[n] for n in STATS_FIELDS], np.float64))
 
 
 def main():
@@ -366,7 +398,9 @@ def main():
             torch.cuda.synchronize()
 
     def timed_run(step, method, q, steps, warmup, preroll_s, kernel_events=True, prime=True):
-        """(elapsed seconds of `steps` steps between fences, average k_render ms, launches timed, first-frame ms)."""
+        """(elapsed seconds of `steps` steps between fences, average k_render ms, launches timed, first-frame ms).
+        kernel_events: True = HIP event pairs on k_render inside the timed steps, False = in a second, untimed pass,
+        None = no kernel timing at all (kernel ms None)."""
         launches_per_step = 1 if method == "basic" else 2
         if prime:
             ctx.frame_begin(q, hqs=method == "hqs")      # primes the turn-based loops (clear + prepass); untimed
@@ -398,6 +432,8 @@ def main():
             step()
         fence()
         elapsed = time.perf_counter() - t0
+        if kernel_events is None:
+            return elapsed, None, 0, first_ms
         if not kernel_events:       # A/B of the event overhead: time the kernel in a second, untimed pass instead
             ctx.kernel_timing(True)
             for _ in range(min(steps, 64)):
@@ -407,19 +443,24 @@ def main():
         ctx.kernel_timing(False)
         return elapsed, kernel_ms, launches, first_ms
 
+    # (a plain run keeps kernel events out of the timed steps: they serve only --full's roofline)
     elapsed, kernel_ms, kernel_launches, first_frame_ms = timed_run(step, args.method, p, args.steps, args.warmup, args.preroll,
-                                                                    not args.no_kernel_events, prime)
+                                                                    (not args.no_kernel_events) if args.full else None, prime)
+    st = ctx.stats()            # counters of the last render launch (per rank)
+    if args.dump_outputs and rank == 0:
+        rgba = frame.image().cpu().numpy()[:args.width * args.height].view("uint32") if isinstance(frame, pdist.SlicedFrame) else ctx.read_rgba()
+        dump_outputs(args.dump_outputs, rgba, args.width, args.height, st)
 
     # distribution of single steps (after the timed region, each step between its own event pair and a sync: launch gaps
     # included, pipelining across steps excluded)
     step_ms = []
-    for _ in range(48):
-        ctx.timing_begin()
-        step()
-        step_ms.append(ctx.timing_end())
-    fence()
+    if args.full:
+        for _ in range(48):
+            ctx.timing_begin()
+            step()
+            step_ms.append(ctx.timing_end())
+        fence()
 
-    st = ctx.stats()            # counters of the last render launch (per rank)
     pts = torch.tensor([st["points_iterated"]], dtype=torch.float64, device=dev)
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if use_dist:
@@ -430,42 +471,44 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     value = points_per_step / (elapsed / args.steps) / 1e6
 
-    # ---- dominant kernel: per-launch HIP event pairs recorded inside pcr_render_* on the context's stream, around
-    # k_render only, during the timed steps above (pcr_kernel_timing_*; a stride keeps it to <=64 pairs spread over the
-    # whole timed region, since an event pair costs ~5 us of stream time) ---------------------------------------------
-    # decode-pass bytes of what this rank's launch drew (SURVEY 8d B_dec x points): the whole shard at LOD 100 % without
-    # culling; with a level of detail or culling only the batches drawn, and of their words the share the LOD decodes
-    full_frame = args.lod >= 100 and not args.cull
-    alg_bytes = ctx.algorithmic_bytes if full_frame else ctx.last_frame_algorithmic_bytes
-    achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
-    traffic_by_variant, traffic_source = load_traffic(P, args) if world == 1 else ({}, "not quoted for N > 1")
-    resident_main = ctx.resident_bytes
-    hbm_read, hbm_copy = ctx.measure_hbm(2 << 30, 5) if rank == 0 else (0.0, 0.0)   # practical ceiling of this box
-    kernel_name = "k_render<%s, %s>" % ("basic" if args.method == "basic" else "hqs_depth + hqs_color",
-                                        "point windows" if args.layout == "point_windows" else "packed words")
-    roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic_by_variant.get(args.layout), "traffic_source": traffic_source,
-                "peak_measured": {"stream_read": round(hbm_read, 1), "stream_copy": round(hbm_copy, 1), "unit": "GB/s",
-                                  "frac_of_read": round(achieved / hbm_read, 5) if hbm_read else None},
-                "kernel": kernel_name, "kernel_version": P.kernel_version(),
-                "kernel_ms": round(kernel_ms, 4), "kernel_launches_timed": kernel_launches, "algorithmic_bytes": alg_bytes,
-                "algorithmic_bytes_how": "every byte of the compressed stream once (pcr_stream_algorithmic_bytes)" if full_frame else
-                                         "drawn batches only, words by the decoded share npr/64 of each chain (pcr_last_frame_algorithmic_bytes)",
-                "bytes_per_point": round(alg_bytes / max(1, st["points_iterated"]), 4)}
+    roofline, variants = None, None
+    if args.full:
+        # ---- dominant kernel: per-launch HIP event pairs recorded inside pcr_render_* on the context's stream, around
+        # k_render only, during the timed steps above (pcr_kernel_timing_*; a stride keeps it to <=64 pairs spread over the
+        # whole timed region, since an event pair costs ~5 us of stream time) ---------------------------------------------
+        # decode-pass bytes of what this rank's launch drew (SURVEY 8d B_dec x points): the whole shard at LOD 100 % without
+        # culling; with a level of detail or culling only the batches drawn, and of their words the share the LOD decodes
+        full_frame = args.lod >= 100 and not args.cull
+        alg_bytes = ctx.algorithmic_bytes if full_frame else ctx.last_frame_algorithmic_bytes
+        achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
+        traffic_by_variant, traffic_source = load_traffic(P, args) if world == 1 else ({}, "not quoted for N > 1")
+        resident_main = ctx.resident_bytes
+        hbm_read, hbm_copy = ctx.measure_hbm(2 << 30, 5) if rank == 0 else (0.0, 0.0)   # practical ceiling of this box
+        kernel_name = "k_render<%s, %s>" % ("basic" if args.method == "basic" else "hqs_depth + hqs_color",
+                                            "point windows" if args.layout == "point_windows" else "packed words")
+        roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic_by_variant.get(args.layout), "traffic_source": traffic_source,
+                    "peak_measured": {"stream_read": round(hbm_read, 1), "stream_copy": round(hbm_copy, 1), "unit": "GB/s",
+                                      "frac_of_read": round(achieved / hbm_read, 5) if hbm_read else None},
+                    "kernel": kernel_name, "kernel_version": P.kernel_version(),
+                    "kernel_ms": round(kernel_ms, 4), "kernel_launches_timed": kernel_launches, "algorithmic_bytes": alg_bytes,
+                    "algorithmic_bytes_how": "every byte of the compressed stream once (pcr_stream_algorithmic_bytes)" if full_frame else
+                                             "drawn batches only, words by the decoded share npr/64 of each chain (pcr_last_frame_algorithmic_bytes)",
+                    "bytes_per_point": round(alg_bytes / max(1, st["points_iterated"]), 4)}
 
-    def variant_record(layout, ms_step, k_ms, resident):
-        tr = traffic_by_variant.get(layout)
-        return {"ms_per_step": round(ms_step, 4), "kernel_ms": round(k_ms, 4),
-                "frac": round(alg_bytes / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                "Mpoints_per_s": round(points_per_step / (ms_step * 1e-3) / 1e6, 1),
-                "resident_bytes_per_point": round(resident / max(1, count_b * BATCH), 3),
-                "hbm_bytes_read_per_point": round(tr / max(1, st["points_iterated"]), 3) if tr else None}
+        def variant_record(layout, ms_step, k_ms, resident):
+            tr = traffic_by_variant.get(layout)
+            return {"ms_per_step": round(ms_step, 4), "kernel_ms": round(k_ms, 4),
+                    "frac": round(alg_bytes / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                    "Mpoints_per_s": round(points_per_step / (ms_step * 1e-3) / 1e6, 1),
+                    "resident_bytes_per_point": round(resident / max(1, count_b * BATCH), 3),
+                    "hbm_bytes_read_per_point": round(tr / max(1, st["points_iterated"]), 3) if tr else None}
 
-    variants = {args.layout: variant_record(args.layout, ms_per_step, kernel_ms, resident_main)}
+        variants = {args.layout: variant_record(args.layout, ms_per_step, kernel_ms, resident_main)}
 
     # ---- CPU baseline + full-size parity check (rank 0, N == 1 only) ----------------------------------------
     cpu_baseline, parity, ties = None, None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import numpy as np
         from tests import oracle
         of = oracle.OracleFile(hf.buf)
@@ -527,7 +570,7 @@ def main():
 
     # ---- secondary rows, same resident stream (N == 1 only): 20 steps each --------------------------------------------------
     secondary = None
-    if world == 1 and not use_dist and not args.no_secondary:
+    if args.full and world == 1 and not use_dist and not args.no_secondary:
         secondary = {}
         rows = (("lod10_cull1", "basic", args.width, args.height, 10, 1, args.camera, "LOD 10 % + frustum culling: the reference's defaults (include/Debug.h:21-23)"),
                 ("hqs", "hqs", args.width, args.height, 100, 0, args.camera, "HQS two-pass (BASELINE configs[2])"),
@@ -554,7 +597,7 @@ def main():
                 ctx.set_image_size(args.width, args.height)
 
     # ---- the other layout, same stream, same camera: a shorter second pass (N == 1 only) ---------------------------
-    if world == 1 and not use_dist and not args.no_variants:
+    if args.full and world == 1 and not use_dist and not args.no_variants:
         other = "words" if args.layout == "point_windows" else "point_windows"
         load(other)
         n2 = min(args.steps, 100)
@@ -563,7 +606,7 @@ def main():
 
     # ---- the rows SURVEY 8f built next, on contexts of their own (N == 1 only): the 10-10-10 method and the GPU encoder -------------
     # (a failure in one of these rows must not cost the line its headline: it is recorded in the row's place)
-    if world == 1 and not use_dist and not args.no_secondary and rank == 0:
+    if args.full and world == 1 and not use_dist and not args.no_secondary and rank == 0:
         for name, row in (("las", lambda: las_row(P, local_rank, args)), ("encoder", lambda: encoder_row(P, local_rank, args, nthreads))):
             try:
                 secondary[name] = row()
@@ -605,7 +648,7 @@ def main():
             "roofline": roofline,
             "variants": variants,
             "secondary": secondary,
-            "scaling_base": scaling_base(P, total_points, args) if fixed_total else None,
+            "scaling_base": scaling_base(P, total_points, args) if fixed_total and args.full else None,
             "cpu_baseline": cpu_baseline,
             "parity_full_size": parity,
             "depth_ties": ties,

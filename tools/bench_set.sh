@@ -2,14 +2,14 @@
 # usage (on the GPU box): tools/bench_set.sh OUTDIR   runs the round's standard bench configurations, one JSON line each
 OUT=${1:-gpurun_out/r03}; mkdir -p $OUT
 run() { name=$1; shift; timeout -k 10 500 "$@" 2>$OUT/b_$name.err | tail -1 > $OUT/b_$name.json || echo "$name FAILED"; }
-run basic   python bench.py
-run basic20 python bench.py --steps 20 --warmup 5
-run closeup python bench.py --camera closeup --no-cpu-baseline --no-variants --no-secondary
-PCR_FORCE_DIST=1 run dist1_torch python bench.py --no-cpu-baseline --no-variants --no-secondary
-PCR_FORCE_DIST=1 run dist1_rccl python bench.py --transport rccl --no-cpu-baseline --no-variants --no-secondary
-PCR_FORCE_DIST=1 run dist1_rccl_sliced python bench.py --transport rccl --merge sliced --no-cpu-baseline --no-variants --no-secondary
-PCR_FORCE_DIST=1 run dist1_auto python bench.py --transport auto --no-cpu-baseline --no-variants --no-secondary
-run 2e9 python bench.py --points 2000000000 --no-variants --no-secondary
+run basic   python bench.py --full
+run basic20 python bench.py --full --steps 20 --warmup 5
+run closeup python bench.py --full --camera closeup --no-cpu-baseline --no-variants --no-secondary
+PCR_FORCE_DIST=1 run dist1_torch python bench.py --full --no-cpu-baseline --no-variants --no-secondary
+PCR_FORCE_DIST=1 run dist1_rccl python bench.py --full --transport rccl --no-cpu-baseline --no-variants --no-secondary
+PCR_FORCE_DIST=1 run dist1_rccl_sliced python bench.py --full --transport rccl --merge sliced --no-cpu-baseline --no-variants --no-secondary
+PCR_FORCE_DIST=1 run dist1_auto python bench.py --full --transport auto --no-cpu-baseline --no-variants --no-secondary
+run 2e9 python bench.py --full --points 2000000000 --no-variants --no-secondary
 python3 - $OUT <<'PY'
 import json, sys, glob, os
 for n in ("basic", "basic20", "closeup", "dist1_torch", "dist1_rccl", "dist1_rccl_sliced", "dist1_auto", "2e9"):

@@ -2,7 +2,7 @@
 # usage: tools/exp/pmc.sh VARIANT "COUNTER COUNTER ..."   prints per-dispatch averages for k_render
 V=$1; PMC=$2; OUT=$PWD/gpurun_out/pmc_$V; ROOT=$PWD
 cd /tmp && export TMPDIR=/tmp
-PCR_HIP_LIB=$ROOT/tools/exp/libpcr_hip_$V.so rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d $OUT -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT.log 2>&1
+PCR_HIP_LIB=$ROOT/tools/exp/libpcr_hip_$V.so rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d $OUT -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT.log 2>&1
 cd $ROOT
 python3 - "$OUT" <<'PY'
 import csv,glob,sys

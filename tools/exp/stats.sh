@@ -2,7 +2,7 @@
 # usage: tools/exp/stats.sh VARIANT "bench args"   rocprofv3 kernel stats (average ns per kernel) of a short bench run with tools/exp/libpcr_hip_<VARIANT>.so
 V=$1; ARGS=$2; OUT=$PWD/gpurun_out/stats_$V; ROOT=$PWD
 cd /tmp && export TMPDIR=/tmp
-PCR_HIP_LIB=$ROOT/tools/exp/libpcr_hip_$V.so rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $ROOT/bench.py $ARGS --steps 100 --warmup 5 --no-cpu-baseline --no-variants --no-secondary > $OUT.log 2>&1
+PCR_HIP_LIB=$ROOT/tools/exp/libpcr_hip_$V.so rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $ROOT/bench.py --full $ARGS --steps 100 --warmup 5 --no-cpu-baseline --no-variants --no-secondary > $OUT.log 2>&1
 cd $ROOT
 python3 - "$OUT" "$V" <<'PY'
 import csv,glob,sys

@@ -11,8 +11,8 @@ if [ -n "$PROFILE_SCRIPT" ]; then
   BENCH="$PWD/$PROFILE_SCRIPT --steps 5 --warmup 2 --no-parity $*"
   BENCH_FULL="$PWD/$PROFILE_SCRIPT --steps 200 --warmup 5 --no-parity $*"
 else
-  BENCH="$PWD/bench.py --steps 5 --warmup 2 --preroll 0 --no-cpu-baseline --no-variants --no-secondary $*"
-  BENCH_FULL="$PWD/bench.py --no-cpu-baseline --no-variants --no-secondary $*"
+  BENCH="$PWD/bench.py --full --steps 5 --warmup 2 --preroll 0 --no-cpu-baseline --no-variants --no-secondary $*"
+  BENCH_FULL="$PWD/bench.py --full --no-cpu-baseline --no-variants --no-secondary $*"
 fi
 cd /tmp
 # the stats pass runs the bench at its default length so that its k_render average can be set beside roofline.kernel_ms
