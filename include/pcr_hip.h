@@ -107,13 +107,32 @@ int pcr_resolve_hqs(pcr_ctx *ctx, const pcr_render_params *p);
  * pcr_resolve_las <- the resolve launch (compute_loop_las_cuda.h:185-207; kernel resolve.cu): pixel <- colour of the
  *                    winning point index, background 0x00443322; all pixels (the reference skips partial 16x16 tiles).
  * pcr_las_algorithmic_bytes: HBM bytes the last pcr_render_las had to read at least once (4/8/12 B per point by
- *                    level + 64 B per drawn batch); synchronises. */
+ *                    level + 64 B per drawn batch, + 4 B per point of colour after pcr_render_las_hqs_color); synchronises.
+ *
+ * ---- the 10-10-10 HQS method: ComputeLoopLasHqs ("loop_las_hqs", modules/compute_loop_las_hqs) ---------------------
+ * A frame is pcr_clear -> pcr_render_las_hqs_depth -> pcr_render_las_hqs_color -> pcr_resolve_hqs (compute_loop_las_hqs.h:170-300).
+ * Both passes draw the batches pcr_render_las draws, at the same levels, with the same positions; errors, stats, kernel timing
+ * and the no-op on 0 batches are those of pcr_render_las.
+ * pcr_render_las_hqs_depth <- the DEPTH dispatch (compute_loop_las_hqs.h:170-196; shader depth.cs:335-355): key depth<<32 with
+ *                    payload 0, so fb >> 32 is the basic frame's depth half at every pixel, the low word 0 where a point landed.
+ * pcr_render_las_hqs_color <- the COLORS dispatch (compute_loop_las_hqs.h:198-223; shader color.cs:360-405): a point is averaged
+ *                    into its pixel iff w <= d * 1.01f, d the pixel's depth -- an f32 product as color.cs:370 (the Huffman HQS
+ *                    pass compares in f64); RG += R<<32 | G, BA += B<<32 | 1 (the Huffman HQS packing; color.cs:399-400 packs
+ *                    R | G<<32), so pcr_resolve_hqs, pcr_read_accum and pcr_merge_sum take these sums unchanged. The next
+ *                    pcr_clear zeroes RG / BA.
+ * pcr_resolve_hqs  <- the RESOLVE dispatch (compute_loop_las_hqs.h:225-245; shader resolve.cs). Its debug modes (show_num_points,
+ *                    colorize_chunks) read the depth word's payload, which is 0 here: out of scope for this method.
+ * Deviations from the GLSL method, each keeping the two 10-10-10 methods consistent: the CUDA method's level function
+ * (compute_loop_las_cuda/render.cu:157-197, not color.cs:180-205), 1024-thread workgroups (not 128), the last loaded batch
+ * is not drawn (render.cu:201-202), the accumulator packing above. */
 int     pcr_las_begin(pcr_ctx *ctx, int64_t num_points);
 int     pcr_las_upload(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_xyz_batch *batches,
                        const uint32_t *xyz12, const uint32_t *xyz8, const uint32_t *xyz4, const uint32_t *rgba);
 int     pcr_las_unload(pcr_ctx *ctx);
 int64_t pcr_las_batches_loaded(const pcr_ctx *ctx);
 int     pcr_render_las(pcr_ctx *ctx, const pcr_render_params *p);
+int     pcr_render_las_hqs_depth(pcr_ctx *ctx, const pcr_render_params *p);
+int     pcr_render_las_hqs_color(pcr_ctx *ctx, const pcr_render_params *p);
 int     pcr_resolve_las(pcr_ctx *ctx, const pcr_render_params *p);
 int64_t pcr_las_algorithmic_bytes(pcr_ctx *ctx);
 

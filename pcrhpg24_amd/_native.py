@@ -78,6 +78,7 @@ HIP_SYMBOLS = [
     "pcr_timing_end", "pcr_kernel_timing_enable", "pcr_kernel_timing_read", "pcr_measure_hbm",
     "pcr_frame_begin", "pcr_frame_turn", "pcr_set_stream_layout", "pcr_set_hbm_budget", "pcr_stream_layout", "pcr_set_render_variant", "pcr_set_workgroup_parts", "pcr_set_int64_mergeable", "pcr_fence_record", "pcr_fence_wait", "pcr_merge_min_slices", "pcr_resolve_basic_range", "pcr_set_async_upload", "pcr_batches_resident", "pcr_last_frame_batches", "pcr_stream_algorithmic_bytes", "pcr_last_frame_algorithmic_bytes", "pcr_stream_resident_bytes", "pcr_stream_color_format", "pcr_kernel_version", "pcr_get_stream", "pcr_get_device", "pcr_framebuffer_elems", "pcr_framebuffer_capacity", "pcr_device_rgba", "pcr_resolve_hqs_range",
     "pcr_las_begin", "pcr_las_upload", "pcr_las_unload", "pcr_las_batches_loaded", "pcr_render_las", "pcr_resolve_las",
+    "pcr_render_las_hqs_depth", "pcr_render_las_hqs_color",
     "pcr_las_algorithmic_bytes", "pcr_gpu_encode_points", "pcr_gpu_encode_free",
 ]
 
@@ -131,7 +132,7 @@ def hip_lib() -> C.CDLL:
         lib.pcr_clear.argtypes = [C.c_void_p]
         for n in ("pcr_render_basic", "pcr_render_hqs_depth", "pcr_render_hqs_color", "pcr_resolve_basic", "pcr_resolve_hqs"):
             getattr(lib, n).argtypes = [C.c_void_p, C.POINTER(RenderParams)]
-        for n in ("pcr_render_las", "pcr_resolve_las"):
+        for n in ("pcr_render_las", "pcr_resolve_las", "pcr_render_las_hqs_depth", "pcr_render_las_hqs_color"):
             getattr(lib, n).argtypes = [C.c_void_p, C.POINTER(RenderParams)]
         lib.pcr_gpu_encode_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i64, C.POINTER(LasInfo),
                                               C.c_int, c_i64, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(EncodeStats)]

@@ -127,7 +127,8 @@ struct pcr_ctx {
     pcr_xyz_batch *d_xyzb = nullptr;
     uint32_t *d_xyz12 = nullptr, *d_xyz8 = nullptr, *d_xyz4 = nullptr, *d_point_rgba = nullptr;
     int32_t *d_las_level = nullptr;
-    uint2 *d_las_win = nullptr;
+    uint2 *d_las_win = nullptr, *d_las_win_hqs = nullptr;      // LasArgs::win / win_hqs
+    bool las_last_color = false;                // the last LAS render call was loop_las_hqs's colour pass (pcr_las_algorithmic_bytes)
     uint32_t *d_las_order = nullptr, *d_las_chunk_count = nullptr;      // LasArgs::order / chunk_count
 
     // method (framebuffers)
@@ -225,7 +226,7 @@ void free_stream_buffers(pcr_ctx *c)
 void free_las_buffers(pcr_ctx *c)
 {
     dfree(c->d_xyzb); dfree(c->d_xyz12); dfree(c->d_xyz8); dfree(c->d_xyz4); dfree(c->d_point_rgba);
-    dfree(c->d_las_level); dfree(c->d_las_win); dfree(c->d_las_order); dfree(c->d_las_chunk_count);
+    dfree(c->d_las_level); dfree(c->d_las_win); dfree(c->d_las_win_hqs); dfree(c->d_las_order); dfree(c->d_las_chunk_count);
     c->las_open = false; c->las_capacity = c->las_loaded = 0;
 }
 
@@ -1196,7 +1197,7 @@ int pcr_las_begin(pcr_ctx *c, int64_t num_points)
     if ((rc = dalloc_zero(c, c->d_xyzb, (size_t)nB)) || (rc = dalloc_zero(c, c->d_xyz12, slots)) ||
         (rc = dalloc_zero(c, c->d_xyz8, slots)) || (rc = dalloc_zero(c, c->d_xyz4, slots)) ||
         (rc = dalloc_zero(c, c->d_point_rgba, slots)) || (rc = dalloc_zero(c, c->d_las_level, (size_t)nB)) ||
-        (rc = dalloc_zero(c, c->d_las_win, (size_t)nB)) ||
+        (rc = dalloc_zero(c, c->d_las_win, (size_t)nB)) || (rc = dalloc_zero(c, c->d_las_win_hqs, (size_t)nB)) ||
         (rc = dalloc_zero(c, c->d_las_order, (size_t)((nB + LAS_PREPASS_BATCHES - 1) / LAS_PREPASS_BATCHES) * LAS_PREPASS_BATCHES)) ||
         (rc = dalloc_zero(c, c->d_las_chunk_count, (size_t)LAS_CLASSES * (size_t)((nB + LAS_PREPASS_BATCHES - 1) / LAS_PREPASS_BATCHES)))) {
         free_las_buffers(c);
@@ -1254,7 +1255,11 @@ static int check_las(pcr_ctx *c, const pcr_render_params *p)
     return PCR_OK;
 }
 
-int pcr_render_las(pcr_ctx *c, const pcr_render_params *p)
+// The three 10-10-10 passes: prepass (cull, level, windows, draw list) + one workgroup per drawn batch. Every call runs its own
+// prepass (a few microseconds: one lane per batch), so each fills pcr_get_stats and none depends on the one before.
+enum LasPass { LAS_BASIC, LAS_HQS_DEPTH, LAS_HQS_COLOR };
+
+static int launch_las(pcr_ctx *c, const pcr_render_params *p, LasPass pass)
 {
     int rc = check_las(c, p);
     if (rc) return rc;
@@ -1270,15 +1275,29 @@ int pcr_render_las(pcr_ctx *c, const pcr_render_params *p)
     a.level = c->d_las_level; a.win = c->d_las_win; a.stats = c->d_stats; a.win_capacity = WIN_PIXELS;
     c->stats_partials = (int)((nB + PREPASS_THREADS - 1) / PREPASS_THREADS);
     a.order = c->d_las_order; a.chunk_count = c->d_las_chunk_count; a.chunks = (uint32_t)c->stats_partials;
+    a.win_hqs = pass == LAS_HQS_COLOR ? c->d_las_win_hqs : nullptr; a.win_capacity_hqs = LAS_WIN_PIXELS_HQS;
+    a.rgba_points = c->d_point_rgba;
     hipLaunchKernelGGL(k_las_prepass, dim3((unsigned)c->stats_partials), dim3(PREPASS_THREADS), 0, c->stream, a);
     const bool timed = c->kt_sample_now();
     const int slot = (int)(c->kt_samples % pcr_ctx::KT_PAIRS);
     if (timed) HIP_TRY(c, hipEventRecord(c->kt_begin[slot], c->stream));
-    hipLaunchKernelGGL(k_las_render, dim3((unsigned)nB), dim3(PCR_WORKGROUP_SIZE), 0, c->stream, a);
+    if (pass == LAS_BASIC)          hipLaunchKernelGGL(k_las_render<false>, dim3((unsigned)nB), dim3(PCR_WORKGROUP_SIZE), 0, c->stream, a);
+    else if (pass == LAS_HQS_DEPTH) hipLaunchKernelGGL(k_las_render<true>, dim3((unsigned)nB), dim3(PCR_WORKGROUP_SIZE), 0, c->stream, a);
+    else                            hipLaunchKernelGGL(k_las_render_color, dim3((unsigned)nB), dim3(PCR_WORKGROUP_SIZE), 0, c->stream, a);
     if (timed) { HIP_TRY(c, hipEventRecord(c->kt_end[slot], c->stream)); ++c->kt_samples; }
     if (c->kt_every > 0) ++c->kt_launches;
+    if (pass == LAS_HQS_COLOR) c->accum_dirty = true;           // RG / BA written: the next pcr_clear zeroes them
+    c->las_last_color = pass == LAS_HQS_COLOR;
     HIP_TRY(c, hipGetLastError());
     return PCR_OK;
+}
+
+int pcr_render_las(pcr_ctx *c, const pcr_render_params *p) { return launch_las(c, p, LAS_BASIC); }
+int pcr_render_las_hqs_depth(pcr_ctx *c, const pcr_render_params *p) { return launch_las(c, p, LAS_HQS_DEPTH); }
+int pcr_render_las_hqs_color(pcr_ctx *c, const pcr_render_params *p)
+{
+    if (c && (!c->rg || !c->ba)) return set_err(c, PCR_E_ARG, "no RG/BA accumulation buffers");
+    return launch_las(c, p, LAS_HQS_COLOR);
 }
 
 int pcr_resolve_las(pcr_ctx *c, const pcr_render_params *p)
@@ -1301,7 +1320,7 @@ int64_t pcr_las_algorithmic_bytes(pcr_ctx *c)
     for (int64_t b = 0; b + 1 < c->las_loaded; ++b) {         // the last workgroup does not run
         const int l = level[(size_t)b];
         if (l < 0) continue;
-        bytes += (int64_t)sizeof(pcr_xyz_batch) + (int64_t)PCR_POINTS_PER_BATCH * 4 * (l >= 2 ? 1 : l == 1 ? 2 : 3);
+        bytes += (int64_t)sizeof(pcr_xyz_batch) + (int64_t)PCR_POINTS_PER_BATCH * 4 * ((l >= 2 ? 1 : l == 1 ? 2 : 3) + (c->las_last_color ? 1 : 0));
     }
     return bytes;
 }

@@ -2055,6 +2055,11 @@ struct LasArgs {
     uint32_t *order;          // [chunks * LAS_PREPASS_BATCHES]
     uint32_t *chunk_count;    // [LAS_CLASSES][chunks]
     uint32_t chunks;
+    // loop_las_hqs (k_las_render_color): the prepass plans a second rectangle per batch for the colour window's 20-byte pixels
+    // (NULL: the basic method, nothing planned); the kernel reads the points' colours
+    uint2 *win_hqs;           // [nB]
+    int win_capacity_hqs;
+    const uint32_t *rgba_points;
 };
 constexpr int LAS_PREPASS_BATCHES = PREPASS_THREADS;     // one lane per batch
 // Heaviest first, as the Huffman lists' classes (RenderArgs::work_classes): class 0 = batches whose screen rectangle the LDS window does
@@ -2172,6 +2177,51 @@ __device__ __forceinline__ void las_prepass_batch(const LasArgs &a, int64_t b, p
     if (b != a.s.num_batches - 1)                                            // the last workgroup returns early (:201-202)
         st.points_iterated += PCR_POINTS_PER_BATCH;
     a.win[b] = window_rect(p, bmin, bmax, a.win_capacity, heavy);
+    if (a.win_hqs) a.win_hqs[b] = window_rect(p, bmin, bmax, a.win_capacity_hqs);
+}
+
+// Which batch is the blockIdx.x-th of the prepass's list (false: none)? Every wave for itself: a 64-lane inclusive prefix sum over
+// the chunk counts. k_las_render_color's; k_las_render keeps the same walk inline (called from there, this function reorders two of
+// the basic kernel's instructions).
+__device__ __forceinline__ bool las_list_batch(const LasArgs &a, uint32_t &b)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    // Heaviest class first only while it is a minority (a few stragglers among batches with windows: started first, they run beside
+    // everything else). A frame made of such batches (a close-up: every batch larger on screen than its window) is bound by its
+    // global atomics, and drawn class by class it was 18 % slower than in the file's order -- then the chunks are walked in order.
+    uint32_t heavy_total = 0, all_total = 0;
+    for (uint32_t c0 = 0; c0 < a.chunks; c0 += 64) {                    // (uniform)
+        uint32_t h = c0 + lane < a.chunks ? a.chunk_count[c0 + lane] : 0u, l = c0 + lane < a.chunks ? a.chunk_count[a.chunks + c0 + lane] : 0u;
+        h = wave_read_lane(wave_inclusive_sum(h), 63); l = wave_read_lane(wave_inclusive_sum(l), 63);
+        heavy_total += h; all_total += h + l;
+    }
+    const bool by_class = heavy_total * 4u < all_total;
+    static_assert(LAS_CLASSES == 2, "heavy / light");
+    uint32_t x = blockIdx.x, found = 0xFFFFFFFFu;
+    for (uint32_t cls = 0; cls < (by_class ? 2u : 1u) && found == 0xFFFFFFFFu; ++cls) {       // (uniform)
+        uint32_t before = 0;
+        for (uint32_t c0 = 0; c0 < a.chunks; c0 += 64) {                // (uniform)
+            const uint32_t c = c0 + lane;
+            // by class: the chunk's records of this class; in the file's order: all of the chunk's records (heavy ones first inside it)
+            const uint32_t cnt = c < a.chunks ? (by_class ? a.chunk_count[cls * a.chunks + c] : a.chunk_count[c] + a.chunk_count[a.chunks + c]) : 0u;
+            const uint32_t incl = wave_inclusive_sum(cnt);
+            const uint32_t total = wave_read_lane(incl, 63);
+            if (x < before + total) {
+                const uint64_t m = __ballot(before + incl > x);
+                const uint32_t first = (uint32_t)__ffsll((unsigned long long)m) - 1u;
+                const uint32_t excl = wave_read_lane(incl - cnt, first);
+                const uint32_t lighter = by_class && cls == 1u ? a.chunk_count[c0 + first] : 0u;      // the chunk's heavy records lie in front
+                found = (c0 + first) * LAS_PREPASS_BATCHES + lighter + (x - before - excl);
+                break;
+            }
+            before += total;
+        }
+        x -= before;                                                    // (not found: `before` is the class's total)
+    }
+    found = __builtin_amdgcn_readfirstlane(found);
+    if (found == 0xFFFFFFFFu) return false;                             // the grid is sized for "every batch drawn"
+    b = a.order[found];
+    return true;
 }
 
 // Round 4: brought to k_render's standard. The window starts EMPTY (round 1 copied the framebuffer's words into it: a global read
@@ -2183,6 +2233,10 @@ __device__ __forceinline__ void las_prepass_batch(const LasArgs &a, int64_t b, p
 // keep their pre-read of the global word (strip-ordered clouds put most points there: unfiltered 8 x the time in atomics), now
 // requested a point ahead like the window word. Reference: modules/compute_loop_las_cuda/render.cu:204-327 (USE_PREFETCH loop),
 // :108-128 (rasterize).
+//
+// DEPTH_ONLY: the depth pass of loop_las_hqs (modules/compute_loop_las_hqs/depth.cs:335-355): the same walk, tests and atomics
+// with the key depth<<32 and payload 0, so that fb >> 32 is the basic frame's depth half at every pixel.
+template <bool DEPTH_ONLY>
 __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE, 8) k_las_render(LasArgs a)
 {
     // which batch is the blockIdx.x-th of the list? (every wave for itself: a 64-lane inclusive prefix sum over the chunk counts)
@@ -2265,7 +2319,7 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE, 8) k_las_render(LasArgs a)
     auto scatter_pending = [&]() __attribute__((always_inline)) {
         // rasterize, second half (:119-126): the pre-read filter on the depth half, then the min (ties go to the atomic: min is idempotent)
         if (pend_depth <= pend_old_hi) {
-            const unsigned long long key = ((unsigned long long)pend_depth << 32) | pend_index;             // :119-120
+            const unsigned long long key = ((unsigned long long)pend_depth << 32) | (DEPTH_ONLY ? 0u : pend_index);  // :119-120, depth.cs:344-348
             // (either / or: in a strip-ordered cloud most lanes are outside the window, and 50 of them on the dummy slot's one
             // address would serialise the LDS atomic)
             if (__builtin_amdgcn_inverse_ballot_w64(pend_off_mask)) atomicMin((unsigned long long *)&g_fb[pend_pix], key);   // :123-126
@@ -2360,6 +2414,181 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE, 8) k_las_render(LasArgs a)
             window_row_col(i, ww, inv_ww, y, x);
             const unsigned long long v = s_win[i];
             if (v != ~0ull) atomicMin((unsigned long long *)&a.f.fb[(size_t)(wy0 + y) * W + wx0 + x], v);      // (a pixel no point reached issues nothing)
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// colour pass of "loop_las_hqs" (modules/compute_loop_las_hqs/color.cs:360-405): every point k_las_render<true> drew is averaged
+// into its pixel iff w <= d * 1.01f, d = the pixel's depth after the depth pass -- an f32 product (color.cs:370: `1.01` is a GLSL
+// float literal), where the Huffman HQS pass compares in f64 (huffman_hqs/render.cu:296). RG += R<<32 | G, BA += B<<32 | 1: the
+// Huffman HQS packing, so that k_resolve<true> and the merges take both methods' sums (color.cs:399-400 packs R | G<<32; the
+// resolved image is the same).
+//
+// Same list walk, levels, 16-byte quad-ahead loads and projection as k_las_render (so both passes see identical positions), plus
+// the points' colours, 16 bytes per quad. The LDS window holds {RG u64, BA u64, depth u32} per pixel: 4096 slots of 20 B
+// = 80 KiB, two workgroups per CU in the 160 KiB; the last slot is the dummy (depth all ones, a NaN: no point passes it). Its
+// depth half is preloaded from fb at workgroup start, row by row; the sums go through ds_add_u64 and leave with one global
+// 64-bit atomicAdd per word of every pixel that counted a point. A point outside the window, or in a batch without one, reads
+// its depth from fb and adds to RG / BA in global memory.
+// ------------------------------------------------------------------------------------------------
+constexpr int LAS_WIN_SLOTS_HQS = 4096;
+constexpr int LAS_WIN_PIXELS_HQS = LAS_WIN_SLOTS_HQS - 1;      // the prepass's capacity of the colour window
+
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE, 8) k_las_render_color(LasArgs a)
+{
+    uint32_t b;
+    if (!las_list_batch(a, b)) return;
+    const int level = a.level[b];
+    const uint32_t tid = threadIdx.x;
+    __shared__ __align__(16) unsigned long long s_rg[LAS_WIN_SLOTS_HQS], s_ba[LAS_WIN_SLOTS_HQS];
+    __shared__ uint32_t s_depth[LAS_WIN_SLOTS_HQS];
+
+    const uint2 wr = a.win_hqs[b];
+    const uint32_t wx0 = wr.x & 0xFFFFu, wy0 = wr.x >> 16, ww = wr.y & 0xFFFFu, wh = wr.y >> 16;
+    const uint32_t wpix = ww * wh;                                          // <= LAS_WIN_PIXELS_HQS (window_rect)
+    const uint32_t W = (uint32_t)a.p.width;
+    const float inv_ww = 1.0f / (float)max(ww, 1u);
+    const uint64_t *const g_fb = a.f.fb;
+    for (uint32_t i = tid; i < wpix; i += PCR_WORKGROUP_SIZE) {
+        uint32_t y, x;
+        window_row_col(i, ww, inv_ww, y, x);
+        s_rg[i] = 0ull; s_ba[i] = 0ull;
+        s_depth[i] = reinterpret_cast<const uint32_t *>(&g_fb[(size_t)(wy0 + y) * W + wx0 + x])[1];
+    }
+    if (tid == 0) { s_rg[wpix] = 0ull; s_ba[wpix] = 0ull; s_depth[wpix] = 0xFFFFFFFFu; }    // the dummy slot
+    const pcr_xyz_batch g = a.s.batches[b];
+    const float div = level >= 2 ? 1024.0f : 1073741824.0f;                  // STEPS_10BIT / STEPS_30BIT
+    const float sx = (g.max_x - g.min_x) / div, sy = (g.max_y - g.min_y) / div, sz = (g.max_z - g.min_z) / div;
+    auto in_vgpr = [](float v) { float r; asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "s"(v)); return r; };
+    const float *M = a.p.transform;
+    const float m00 = M[0], m01 = M[1], m02 = M[2], m03 = M[3];
+    const float m10 = M[4], m11 = M[5], m12 = M[6], m13 = M[7];
+    const float m30 = in_vgpr(M[12]), m31 = in_vgpr(M[13]), m32 = in_vgpr(M[14]), m33 = in_vgpr(M[15]);
+    const float vsx = sx, vsy = sy, vsz = sz, vox = g.min_x, voy = g.min_y, voz = g.min_z;
+    const float fw = (float)a.p.width, fh = (float)a.p.height;
+    const int img_w = a.p.width;
+    unsigned long long *const g_rg = reinterpret_cast<unsigned long long *>(a.f.rg), *const g_ba = reinterpret_cast<unsigned long long *>(a.f.ba);
+    const size_t base = (size_t)b * PCR_POINTS_PER_BATCH;
+    const uint4 *q4 = reinterpret_cast<const uint4 *>(a.s.xyz4 + base);
+    const uint4 *q8 = reinterpret_cast<const uint4 *>(a.s.xyz8 + base);
+    const uint4 *q12 = reinterpret_cast<const uint4 *>(a.s.xyz12 + base);
+    const uint4 *qc = reinterpret_cast<const uint4 *>(a.rgba_points + base);
+    typedef __attribute__((address_space(3))) unsigned long long lds_u64;
+    // the pending point: projected, its depth requested; accumulated while the next point is projected. pend_at: its window slot
+    // (the dummy slot wpix if it has none), or its pixel if it takes the global path (pend_off_mask)
+    uint32_t pend_at = wpix, pend_depth = 0xFFFFFFFFu, pend_w = 0, pend_color = 0;
+    uint64_t pend_off_mask = 0;                                              // lanes whose pending point is inside the frustum but outside the window
+    __syncthreads();
+
+    auto add_pending = [&]() __attribute__((always_inline)) {
+        if (__uint_as_float(pend_w) <= __uint_as_float(pend_depth) * 1.01f) {    // color.cs:370 (NaN depth: untouched pixel or dummy slot)
+            const uint64_t rg = ((uint64_t)(pend_color & 255u) << 32) | ((pend_color >> 8) & 255u);     // color.cs:387-400, repacked
+            const uint64_t ba = ((uint64_t)((pend_color >> 16) & 255u) << 32) | 1u;
+            if (__builtin_amdgcn_inverse_ballot_w64(pend_off_mask)) {
+                uint32_t pix = pend_at;
+                asm volatile("; pixel of a point outside its window %0" : "+v"(pix));     // (widened here, not carried as 64 bits)
+                atomicAdd(&g_rg[pix], (unsigned long long)rg);
+                atomicAdd(&g_ba[pix], (unsigned long long)ba);
+            } else {
+                __hip_atomic_fetch_add((lds_u64 *)s_rg + pend_at, (unsigned long long)rg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add((lds_u64 *)s_ba + pend_at, (unsigned long long)ba, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+    };
+    // projection and inside tests: k_las_render's point() (same arithmetic, same results)
+    auto point = [&](uint32_t X, uint32_t Y, uint32_t Z, uint32_t color) __attribute__((always_inline)) {
+        const float x = __fmaf_rn((float)X, vsx, vox), y = __fmaf_rn((float)Y, vsy, voy), z = __fmaf_rn((float)Z, vsz, voz);
+        const float qx = __fmaf_rn(m03, 1.0f, __fmaf_rn(m02, z, __fmaf_rn(m01, y, m00 * x)));
+        const float qy = __fmaf_rn(m13, 1.0f, __fmaf_rn(m12, z, __fmaf_rn(m11, y, m10 * x)));
+        const float qw = __fmaf_rn(m33, 1.0f, __fmaf_rn(m32, z, __fmaf_rn(m31, y, m30 * x)));
+        uint64_t cand_mask = __builtin_amdgcn_ballot_w64(fabsf(qx) <= qw) & __builtin_amdgcn_ballot_w64(fabsf(qy) <= qw);
+        int ix, iy;
+        {
+            const float r0 = __builtin_amdgcn_rcpf(qw);
+            const float r1 = __fmaf_rn(__fmaf_rn(-qw, r0, 1.0f), r0, r0);
+            const v2f xy = {qx, qy}, rr = {r1, r1}, nw = {-qw, -qw};
+            const v2f q0 = xy * rr;
+            const v2f q1 = __builtin_elementwise_fma(__builtin_elementwise_fma(nw, q0, xy), rr, q0);
+            const v2f q2 = __builtin_elementwise_fma(__builtin_elementwise_fma(nw, q1, xy), rr, q1);
+            const v2f half = {0.5f, 0.5f}, size = {fw, fh};
+            const v2f img = __builtin_elementwise_fma(q2, half, half) * size;
+            ix = (int)img.x; iy = (int)img.y;
+        }
+        const uint64_t w_ok_mask = __builtin_amdgcn_ballot_w64((__float_as_uint(qw) - 0x1F800000u) < 0x40000000u);   // 2^-64 <= w < 2^64
+        if (__builtin_expect((cand_mask & ~w_ok_mask) != 0, 0)) {
+            const float nx = qx / qw, ny = qy / qw;
+            ix = (int)(__fmaf_rn(nx, 0.5f, 0.5f) * fw);
+            iy = (int)(__fmaf_rn(ny, 0.5f, 0.5f) * fh);
+            cand_mask &= __builtin_amdgcn_ballot_w64(qw > 0.0f);
+        }
+        add_pending();                                                       // the point before this one: its depth has arrived by now
+        const uint32_t rx = (uint32_t)ix - wx0, ry = (uint32_t)iy - wy0;
+        const uint64_t in_mask = cand_mask & __builtin_amdgcn_ballot_w64(rx < ww) & __builtin_amdgcn_ballot_w64(ry < wh);
+        pend_off_mask = cand_mask & ~in_mask;
+        pend_w = __float_as_uint(qw);
+        pend_color = color;
+        pend_at = __builtin_amdgcn_inverse_ballot_w64(in_mask) ? (uint32_t)__umul24(ry, ww) + rx : wpix;
+        pend_depth = s_depth[pend_at];
+        if (__builtin_expect(pend_off_mask != 0, 0)) {                      // (uniform) some lane's point lies outside the window: the global word's depth
+            if (__builtin_amdgcn_inverse_ballot_w64(pend_off_mask)) {
+                pend_at = (uint32_t)(ix + iy * img_w);
+                uint32_t seen = reinterpret_cast<const uint32_t *>(&g_fb[pend_at])[1];
+                asm volatile("; framebuffer depth of a point outside its window %0" : "+v"(seen));
+                pend_depth = seen;
+            }
+        }
+    };
+
+    auto quads = [&](auto arrays_) __attribute__((always_inline)) {
+        constexpr int ARRAYS = decltype(arrays_)::value;
+        uint4 n4 = q4[tid], n8 = make_uint4(0, 0, 0, 0), n12 = make_uint4(0, 0, 0, 0);
+        if (ARRAYS >= 2) n8 = q8[tid];
+        if (ARRAYS >= 3) n12 = q12[tid];
+#pragma unroll 1
+        for (int i = 0; i < PCR_POINTS_PER_BATCH / 4 / PCR_WORKGROUP_SIZE; ++i) {
+            const uint4 c4 = n4, c8 = n8, c12 = n12;
+            const uint32_t quad = tid + (uint32_t)i * PCR_WORKGROUP_SIZE;
+            // the quad's colours: requested here, not a quad ahead (four more registers would not fit the 64 of two workgroups
+            // per CU: the three-array copy spilled), and in front of the next quad's words, so that waiting for them does not
+            // wait for those
+            uint32_t cq = quad;
+            asm volatile("; colour quad %0" : "+v"(cq));                    // (no 64-bit pointer induction variable: it spilled)
+            const uint4 cc = qc[cq];
+            {
+                const uint32_t nq = min(quad + PCR_WORKGROUP_SIZE, (uint32_t)(PCR_POINTS_PER_BATCH / 4 - 1));
+                n4 = q4[nq];
+                if (ARRAYS >= 2) n8 = q8[nq];
+                if (ARRAYS >= 3) n12 = q12[nq];
+            }
+            const uint32_t w4[4] = { c4.x, c4.y, c4.z, c4.w }, w8[4] = { c8.x, c8.y, c8.z, c8.w }, w12[4] = { c12.x, c12.y, c12.z, c12.w };
+            const uint32_t wc[4] = { cc.x, cc.y, cc.z, cc.w };
+            if (ARRAYS == 1) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) point(w4[j] & 1023u, (w4[j] >> 10) & 1023u, (w4[j] >> 20) & 1023u, wc[j]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    point(((w4[j] & 1023u) << 20) | ((w8[j] & 1023u) << 10) | (w12[j] & 1023u),
+                          (((w4[j] >> 10) & 1023u) << 20) | (((w8[j] >> 10) & 1023u) << 10) | ((w12[j] >> 10) & 1023u),
+                          (((w4[j] >> 20) & 1023u) << 20) | (((w8[j] >> 20) & 1023u) << 10) | ((w12[j] >> 20) & 1023u), wc[j]);
+            }
+        }
+    };
+    if (level >= 2)      quads(std::integral_constant<int, 1>{});
+    else if (level == 1) quads(std::integral_constant<int, 2>{});
+    else                 quads(std::integral_constant<int, 3>{});
+    add_pending();
+    if (wpix) {
+        __syncthreads();
+        for (uint32_t i = tid; i < wpix; i += PCR_WORKGROUP_SIZE) {
+            const unsigned long long vba = s_ba[i];
+            if ((uint32_t)vba == 0u) continue;                               // (a pixel no point was averaged into issues nothing)
+            uint32_t y, x;
+            window_row_col(i, ww, inv_ww, y, x);
+            const size_t gp = (size_t)(wy0 + y) * W + wx0 + x;
+            atomicAdd(&g_rg[gp], s_rg[i]);
+            atomicAdd(&g_ba[gp], vba);
         }
     }
 }

@@ -8,6 +8,7 @@
 //   HuffmanHQS     ("huffman_hqs")              modules/huffman_hqs/huffman_hqs.h
 //   ComputeLasData, ComputeLoopLasCUDA ("loop_las_cuda")   modules/compute/ComputeLasLoader.{h,cpp},
 //                                                          modules/compute_loop_las_cuda/compute_loop_las_cuda.h
+//   ComputeLoopLasHQS ("loop_las_hqs")                     modules/compute_loop_las_hqs/compute_loop_las_hqs.h
 // Headless: `Renderer` carries the window size and the orbit camera only (no GLFW/GL/ImGui); the resolve target is
 // a device RGBA8 buffer instead of a GL texture.
 #pragma once
@@ -453,6 +454,25 @@ struct ComputeLoopLasCUDA : Method {                                            
         r->check(pcr_clear(r->ctx), "pcr_clear");
         r->check(pcr_render_las(r->ctx, &lastParams), "pcr_render_las");
         r->check(pcr_resolve_las(r->ctx, &lastParams), "pcr_resolve_las");
+    }
+};
+
+struct ComputeLoopLasHQS : ComputeLoopLasCUDA {                                  // compute_loop_las_hqs.h:36-309
+    ComputeLoopLasHQS(Renderer *r, std::shared_ptr<ComputeLasData> l) : ComputeLoopLasCUDA(r, std::move(l))
+    {
+        name = "loop_las_hqs";
+        description = "Like compute las, but also \naverages overlapping points";
+        group = "10-10-10 bit encoded";
+    }
+    void render(Renderer *r) override                                            // compute_loop_las_hqs.h:126-300
+    {
+        las->process(r);
+        if (las->numPointsLoaded == 0) return;
+        lastParams = r->params();
+        r->check(pcr_clear(r->ctx), "pcr_clear");
+        r->check(pcr_render_las_hqs_depth(r->ctx, &lastParams), "pcr_render_las_hqs_depth");   // DEPTH   (:172-196)
+        r->check(pcr_render_las_hqs_color(r->ctx, &lastParams), "pcr_render_las_hqs_color");   // COLORS  (:199-223)
+        r->check(pcr_resolve_hqs(r->ctx, &lastParams), "pcr_resolve_hqs");                     // RESOLVE (:226-245)
     }
 };
 

@@ -2,7 +2,7 @@
 // the renderer, the resource and its methods, select one by name, then run update()/render() frames.
 //
 //   pcr_render <file.huffman> [--method huffman_mem_iter_cuda|huffman_hqs|huffman_cuda] [--size WxH]
-//   pcr_render <file.las>      --method loop_las_cuda                      [--size WxH]
+//   pcr_render <file.las>      --method loop_las_cuda|loop_las_hqs         [--size WxH]
 //              [--camera yaw pitch radius tx ty tz] [--lod 0.1] [--cull 0|1] [--frames N]
 //              [--async-load]   (.huffman: copies on the loader stream, frames draw what has arrived)
 //              [--dump-fb fb.u64] [--dump-rgba out.ppm] [--dump-depth depth.exr]   (depth: huffman_hqs only, huffman_hqs.h:217-237)
@@ -55,10 +55,12 @@ int main(int argc, char **argv)
         std::shared_ptr<HuffmanLasData> las_huffman;
         std::shared_ptr<ComputeLasData> las_compute;
         std::unique_ptr<Method> m0, m1, m2;
-        if (method == "loop_las_cuda") {
+        if (method == "loop_las_cuda" || method == "loop_las_hqs") {
             las_compute = ComputeLasData::create(path);                 // main.cpp:241 (commented out there)
             m0 = std::make_unique<ComputeLoopLasCUDA>(&renderer, las_compute);   // main.cpp:251 (commented out there)
+            m1 = std::make_unique<ComputeLoopLasHQS>(&renderer, las_compute);
             Runtime::addMethod(m0.get());
+            Runtime::addMethod(m1.get());
         } else {
             las_huffman = HuffmanLasData::create(path);                 // main.cpp:244
             las_huffman->asyncUpload = async_load;

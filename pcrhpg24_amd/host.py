@@ -10,6 +10,7 @@ of the reference viewer without a window:
     HuffmanHQS      ("huffman_hqs")                                              modules/huffman_hqs/huffman_hqs.h
     ComputeLasData.create(path) / ComputeLoopLasCUDA ("loop_las_cuda")           modules/compute/ComputeLasLoader.{h,cpp},
                                                                                  modules/compute_loop_las_cuda/compute_loop_las_cuda.h
+    ComputeLoopLasHQS ("loop_las_hqs")                                           modules/compute_loop_las_hqs/compute_loop_las_hqs.h
     Runtime.addMethod / setSelectedMethod / resource                             include/Runtime.h:15-55
     Debug.LOD / frustumCullingEnabled / colorizeChunks / showNumPoints           include/Debug.h:14-31
 
@@ -369,6 +370,12 @@ class Context:
 
     def resolve_las(self, p: RenderParams):
         self._chk(self.lib.pcr_resolve_las(self.h, C.byref(p)), "pcr_resolve_las")
+
+    def render_las_hqs_depth(self, p: RenderParams):
+        self._chk(self.lib.pcr_render_las_hqs_depth(self.h, C.byref(p)), "pcr_render_las_hqs_depth")
+
+    def render_las_hqs_color(self, p: RenderParams):
+        self._chk(self.lib.pcr_render_las_hqs_color(self.h, C.byref(p)), "pcr_render_las_hqs_color")
 
     def set_image_size(self, w: int, h: int):
         self._chk(self.lib.pcr_set_image_size(self.h, w, h), "pcr_set_image_size")
@@ -803,4 +810,24 @@ class ComputeLoopLasCUDA(Method):
         ctx.clear()
         ctx.render_las(p)
         ctx.resolve_las(p)
+        self.last_params = p
+
+
+class ComputeLoopLasHQS(ComputeLoopLasCUDA):
+    """modules/compute_loop_las_hqs/compute_loop_las_hqs.h:36-309: the batches and levels of loop_las_cuda, a depth pass, a
+    colour pass that averages the points within 1 % of the nearest (w <= d * 1.01f), the averaging resolve of the HQS method."""
+    name = "loop_las_hqs"
+    description = "Like compute las, but also \naverages overlapping points"
+    group = "10-10-10 bit encoded"
+
+    def render(self, renderer: Renderer):                             # compute_loop_las_hqs.h:126-300
+        self.las.process(renderer)
+        if self.las.numPointsLoaded == 0:
+            return
+        p = renderer.render_params()
+        ctx = renderer.ctx
+        ctx.clear()
+        ctx.render_las_hqs_depth(p)   # DEPTH   (:172-196)
+        ctx.render_las_hqs_color(p)   # COLORS  (:199-223)
+        ctx.resolve_hqs(p)            # RESOLVE (:226-245)
         self.last_params = p
