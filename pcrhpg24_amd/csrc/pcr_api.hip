@@ -150,11 +150,7 @@ struct pcr_ctx {
     // a raw pointer to one of the context's own buffers has been handed out (pcr_device_framebuffer / _rg / _ba): whoever holds it
     // may write anywhere at any time, so tiles are not used at all until pcr_framebuffer_private says the pointers are dead
     bool fb_exposed = false;
-#ifdef PCR_EXP_NO_TILES     /* experiment: the whole frame is resolved and cleared, nothing marks tiles */
-    bool tiles_usable() const { return false; }
-#else
     bool tiles_usable() const { return d_tiles && !fb_exposed && fb == own_fb && rg == own_rg && ba == own_ba; }
-#endif
     uint8_t *tiles_half(int which) const { return d_tiles + (size_t)which * tiles_stride; }
     uint32_t *tiles_all(int which) const { return reinterpret_cast<uint32_t *>(d_tiles + 3 * (size_t)tiles_stride) + which; }
 
@@ -267,11 +263,9 @@ int check_params(pcr_ctx *c, const pcr_render_params *p)
 }
 
 // Workgroups per batch of a frame's k_render launches (RenderArgs::parts): half-batch workgroups unless told otherwise
-// (pcr_set_workgroup_parts; PCR_PARTS in the environment for experiments).
+// (pcr_set_workgroup_parts).
 int frame_parts(const pcr_ctx *c)
 {
-    static const char *force = getenv("PCR_PARTS");
-    if (force && (force[0] == '1' || force[0] == '2')) return force[0] - '0';
     return c->parts_mode ? c->parts_mode : PCR_DEFAULT_PARTS;
 }
 
@@ -393,12 +387,8 @@ int enqueue_transcode(pcr_ctx *c, bool include_provisional, hipStream_t st)
 // bound by global pre-reads and atomics; one workgroup per CU with windows of ~17 000 pixels keeps them in LDS.
 uint32_t frame_dyn_lds(const pcr_ctx *c, int64_t nB)
 {
-    static const char *force = getenv("PCR_EXP_DYN_LDS");              // experiments: "small" / "big"
     const bool halves = frame_parts(c) == 2;
     const uint32_t small = halves ? (uint32_t)DYN_LDS_BYTES_HALF : (uint32_t)DYN_LDS_BYTES, big = halves ? (uint32_t)DYN_LDS_BYTES_HALF_BIG : (uint32_t)DYN_LDS_BYTES_BIG;
-    if (force && force[0] == 's') return small;
-    if (force && force[0] == 'b') return big;
-    if (force && force[0] >= '1' && force[0] <= '9') return (uint32_t)atoi(force) * 1024u;     // KiB (must not exceed `big`)
     return (int64_t)c->width * c->height > nB * (int64_t)WIN_PIXELS ? big : small;
 }
 
@@ -1594,33 +1584,6 @@ int pcr_kernel_timing_read(pcr_ctx *c, float *avg_ms, int *launches)
     *avg_ms = (float)(sum / n); *launches = n;
     return PCR_OK;
 }
-
-#ifdef PCR_EXP_FAR_STATS
-int pcr_exp_read_far(pcr_ctx *c, unsigned long long *out, int reset)
-{
-    if (!c || !out) return PCR_E_ARG;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpyFromSymbol(out, HIP_SYMBOL(pcr::g_far), 8 * sizeof(unsigned long long)));
-    if (reset) { unsigned long long z[8] = {0}; HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(pcr::g_far), z, sizeof z)); }
-    return PCR_OK;
-}
-#endif
-#ifdef PCR_EXP_TIMELINE
-int pcr_exp_read_timeline(pcr_ctx *c, unsigned long long *out, size_t n)
-{
-    if (!c || !out) return PCR_E_ARG;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpyFromSymbol(out, HIP_SYMBOL(pcr::g_timeline), n * sizeof(unsigned long long)));
-    return PCR_OK;
-}
-int pcr_exp_read_wave_ends(pcr_ctx *c, unsigned long long *out, size_t n)
-{
-    if (!c || !out) return PCR_E_ARG;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpyFromSymbol(out, HIP_SYMBOL(pcr::g_wave_end), n * sizeof(unsigned long long)));
-    return PCR_OK;
-}
-#endif
 
 } // extern "C"
 

@@ -241,13 +241,6 @@ struct RenderArgs {
     uint32_t dyn_lds_bytes;   // dynamic LDS of the following k_render launch: DYN_LDS_BYTES or DYN_LDS_BYTES_BIG
 };
 
-#ifdef PCR_EXP_TIMELINE   /* experiment: wall-clock stamps (100 MHz) of the prepass block's phases, rows 7000 + block of g_timeline */
-extern __device__ unsigned long long g_timeline[8192 * 8];
-#define PCR_PTL(slot) do { if (threadIdx.x == 0) g_timeline[(size_t)(7000 + block * 2 + (LISTS ? 0 : 1)) * 8 + (slot)] = wall_clock64(); } while (0)
-#else
-#define PCR_PTL(slot) do { } while (0)
-#endif
-
 // ------------------------------------------------------------------------------------------------
 // wave64 inclusive prefix sum in six DPP adds (row_shr 1 / 2 / 4 / 8 inside the rows of 16 lanes, then row_bcast 15 / 31 across
 // them): no LDS, no wait. (__shfl_up compiles to ds_bpermute_b32: the scans at the top of k_render -- one per class of the list,
@@ -287,10 +280,8 @@ __device__ __forceinline__ bool plane_accepts(float x, float y, float z, float w
 
 // Frame statistics: every prepass workgroup sums its batches in LDS and writes ONE partial record (no global atomics,
 // nothing to zero beforehand); pcr_get_stats adds the partials of the last launch. PCR_STATS_PARTIALS bounds the grid.
-#ifndef PCR_VOTE_NUM
-#define PCR_VOTE_NUM 9u      // the prepass workgroup's vote (WinPlan::mostly_outside): at least NUM / DEN of its drawn batches. (With 1 / 2 the
-#define PCR_VOTE_DEN 10u     // batches in front of a close-up camera, neighbours in the file, voted themselves in: +6 %, +20 % with culling.)
-#endif
+constexpr uint32_t PCR_VOTE_NUM = 9u;   // the prepass workgroup's vote (WinPlan::mostly_outside): at least NUM / DEN of its drawn batches. (With 1 / 2 the
+constexpr uint32_t PCR_VOTE_DEN = 10u;  // batches in front of a close-up camera, neighbours in the file, voted themselves in: +6 %, +20 % with culling.)
 constexpr int PREPASS_THREADS = 256;
 constexpr int PCR_MAX_PREPASS_WORKGROUPS = 2048;        // ceil(65535 batches / 32 batches per prepass workgroup)
 constexpr int WORK_CLASSES = 4;                         // of the ordinary list, by points per chain: 49..64, 33..48, 17..32, 1..16 (RenderArgs::work_classes;
@@ -356,14 +347,13 @@ __device__ __forceinline__ PlanIn plan_preload(const RenderArgs &a, int64_t b, i
 // k_render's scan reads (lod words, statistics, the compacted lists), the other the window plans, the dirty tiles and the vote. Both
 // work out the chunk's cull / LOD decisions for themselves (a microsecond of arithmetic on CUs that have nothing else to do): the
 // block is a chain of cold starts -- kernel arguments, instruction cache, one round of loads -- and sits on every frame's critical
-// path; as one workgroup it took 8.6-10.1 us from its start (phase stamps: tools/exp/prepass_timeline.py), of which the plans 2.8-4.5.
+// path; as one workgroup it took 8.6-10.1 us from its start (phase stamps, profiles/r04_experiments.md), of which the plans 2.8-4.5.
 template <bool LISTS>
 __device__ __forceinline__ void lod_prepass_chunk(const RenderArgs &a, uint32_t block)
 {
     const int64_t b = ((int64_t)block * PREPASS_THREADS + threadIdx.x) / PREPASS_LANES;
     const int lane = (int)(threadIdx.x % PREPASS_LANES);
     pcr_render_stats st = {0, 0, 0, 0};
-    PCR_PTL(0);
     // the group's lod word (LOD_*), handed to the compaction / to the window plan through LDS (LOD_CULLED: no such batch)
     __shared__ uint32_t s_lod[PREPASS_BATCHES];
     // ---- every load of the block that does not depend on a result of the block, requested before anything is computed ----
@@ -386,16 +376,13 @@ __device__ __forceinline__ void lod_prepass_chunk(const RenderArgs &a, uint32_t 
     PlanIn pin = {};
     if (plan_lane) pin = plan_preload(a, pb, (int)part, (int)(threadIdx.x % RUNS));
 
-    PCR_PTL(1);
     if (lane == 0) s_lod[threadIdx.x / PREPASS_LANES] = LOD_CULLED;
     if (b < a.s.num_batches) {
         const uint32_t lod = lod_prepass_batch(a, b, lane, st, LISTS);                          // uniform per 8-lane group
         if (lane == 0) s_lod[threadIdx.x / PREPASS_LANES] = lod;
     }
-    PCR_PTL(2);
     if (LISTS) {
         commit_stats(st, a.stats, block);                   // (barriers inside: s_lod is complete afterwards)
-        PCR_PTL(3);
         // first level of the compaction: one ballot and one prefix count per list, in the workgroup's first wave
         if (threadIdx.x < 64) {
             const uint32_t lod = threadIdx.x < PREPASS_BATCHES ? s_lod[threadIdx.x] : LOD_CULLED;
@@ -422,7 +409,6 @@ __device__ __forceinline__ void lod_prepass_chunk(const RenderArgs &a, uint32_t 
                 if (kind == 2u) a.order[(size_t)a.order_stride + block * PREPASS_BATCHES + (uint32_t)__popcll(m & below)] = r;
             }
         }
-        PCR_PTL(4);
         return;
     }
     // LDS framebuffer windows of the workgroups that draw
@@ -432,7 +418,6 @@ __device__ __forceinline__ void lod_prepass_chunk(const RenderArgs &a, uint32_t 
     __shared__ uint32_t s_vote[2];                          // plans drawn, of those mostly outside
     if (threadIdx.x < 2) s_vote[threadIdx.x] = 0;
     __syncthreads();                                        // (s_lod is complete)
-    PCR_PTL(5);
     bool mine_drawn = false, mine_outside = false;
     if (plan_lane) {
         const uint32_t lod = s_lod[slot];
@@ -445,9 +430,7 @@ __device__ __forceinline__ void lod_prepass_chunk(const RenderArgs &a, uint32_t 
             }
         }
     }
-    PCR_PTL(6);
     __syncthreads();
-    PCR_PTL(7);
     // (the plan was written with the batch's own verdict; the neighbourhood's vote takes it back)
     if (mine_drawn && mine_outside && s_vote[1] * PCR_VOTE_DEN < s_vote[0] * PCR_VOTE_NUM) {
         a.win[pb * parts + part].mostly_outside = 0;
@@ -1152,17 +1135,6 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_bounds(StreamView s, con
     }
 }
 
-#ifdef PCR_EXP_TIMELINE   /* experiment: per-workgroup time stamps of k_render's phases (100 MHz wall clock) + the hardware slot it ran on */
-__device__ unsigned long long g_timeline[8192 * 8];         // (rows 7000..: the prepass blocks' stamps, PCR_PTL)
-__device__ unsigned long long g_wave_end[8192 * 16];        // per wave: wall clock at the end of its point loop
-#define PCR_TL(slot) do { if (threadIdx.x == 0) g_timeline[(size_t)blockIdx.x * 8 + (slot)] = wall_clock64(); } while (0)
-#else
-#define PCR_TL(slot) do { } while (0)
-#endif
-
-#ifdef PCR_EXP_FAR_STATS   /* experiment: what happens to the points outside their windows (counters per launch sequence) */
-__device__ unsigned long long g_far[8];   // wave-iterations with such lanes, lanes, pre-read iterations, -, -, waves
-#endif
 constexpr uint32_t NO_PIXEL = 0xFFFFFFFFu;
 typedef float v2f __attribute__((ext_vector_type(2)));
 
@@ -1181,16 +1153,6 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
     constexpr uint32_t THREADS = PCR_WORKGROUP_SIZE / PARTS;
     static_assert(PARTS == 1 || PARTS == 2, "whole batches or halves");
     const uint32_t part = PARTS == 1 ? 0u : (blockIdx.x >> 3) & 1u;
-    PCR_TL(0);
-#ifdef PCR_EXP_TIMELINE
-    if (threadIdx.x == 0) {
-        uint32_t hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        uint32_t xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        g_timeline[(size_t)blockIdx.x * 8 + 7] = ((unsigned long long)xcc << 32) | hwid;
-    }
-#endif
     // second level of the compaction: which batch is the blockIdx.x-th of my list? Every wave works it out for itself (a
     // 64-lane inclusive prefix sum over the chunk counts, 64 chunks = 2048 batches per round): no barrier, no LDS.
     DrawRec rec;
@@ -1375,26 +1337,22 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
     if (LAYOUT == LAYOUT_WORDS) {
         const uint32_t wave = __builtin_amdgcn_readfirstlane(chain >> 6);
         const uint32_t *wr = a.s.lw_wave_row + (size_t)b * (LWC_WAVES + 1) + wave;
-        const uint32_t r0 = wr[0], r1 = wr[1];
-        lwb = (global_bytes)(reinterpret_cast<const char *>(a.s.lw_block[b]) + (size_t)r0 * LWC_ROW_BYTES);      // uniform per wave
-        (void)r1;
+        lwb = (global_bytes)(reinterpret_cast<const char *>(a.s.lw_block[b]) + (size_t)wr[0] * LWC_ROW_BYTES);   // uniform per wave
     }
     auto lw_load = [&](uint32_t byte_off) -> uint32_t { return *(const __attribute__((address_space(1))) uint32_t *)(lwb + byte_off); };
     const char *pwb = reinterpret_cast<const char *>(a.s.point_windows) + (size_t)b * PW_BATCH_BYTES;               // uniform
     // the 40-bit window of a point as the top of a 64-bit view: high plane u32, low plane u8 (the 24 bits below are zero).
     // Window rows come through buffer loads: the lane's column offset stays put in a vector register, the row advances in a scalar
     // one (buffer_load_dword v, voffset, s[rsrc], soffset offen) -- no vector add per row and plane (with plain pointers hipcc either
-    // advanced a per-lane offset or added the lane's offset to an advancing uniform pointer with a 64-bit vector add). Reads past the
-    // batch's block + guard return 0. (HQS -0.7 %, LOD 10 % -1.2 %, LOD 100 % within the noise: the two adds were of the cheap class.)
+    // advanced a per-lane offset or added the lane's offset to an advancing uniform pointer with a 64-bit vector add). (HQS -0.7 %,
+    // LOD 10 % -1.2 %, LOD 100 % within the noise: the two adds were of the cheap class.) The descriptor's range check does not
+    // cover the row reads: it looks at voffset alone (the column, always in range), not at the row in soffset. The rows read ahead
+    // past the batch's block land in real memory only because the allocation carries PW_GUARD_BYTES behind the last block.
     const __amdgpu_buffer_rsrc_t pw_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)const_cast<char *>(pwb), 0, (int)(PW_BATCH_BYTES + PW_GUARD_BYTES), 0x00020000);
     uint32_t pw_row_hi = 0, pw_row_lo = PW_HI_BYTES;        // (uniform) byte offsets of the current row in the two planes
     const uint32_t pw_col_hi = chain * 4, pw_col_lo = chain;
     auto pw_load_hi = [&]() -> uint32_t { return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(pw_rsrc, (int)pw_col_hi, (int)pw_row_hi, 0); };
-#ifdef PCR_EXP_NO_LO      // timing experiment only (wrong frames): what 32-bit windows would save -- the low plane is never read
-    auto pw_load_lo = [&]() -> uint32_t { return 0u; };
-#else
     auto pw_load_lo = [&]() -> uint32_t { return (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(pw_rsrc, (int)pw_col_lo, (int)pw_row_lo, 0); };
-#endif
 #define PCR_PW_NEXT_ROW() do { pw_row_hi += PW_HI_ROW_BYTES; pw_row_lo += PW_LO_ROW_BYTES; } while (0)
     uint32_t lwo = (tid & 63u) * 4;                         // packed words: byte offset of my column in the row of far0
     uint32_t w0 = 0, w1 = 0, w2 = 0, far0 = 0, far1 = 0, spare = 0;
@@ -1456,10 +1414,6 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
             atomicAdd((unsigned long long *)&g_ba[run_pix], run_ba);        // :311-312
         }
     };
-    // `valid`: the pending point is inside the frustum; `off`: ... but outside the batch's LDS window (then `pix` is its pixel
-    // and `old` came from global memory). Both are lane masks the compiler keeps in scalar registers, so choosing between the
-    // LDS and the global path costs no vector instruction. The window word of the pixel: `wp` (basic / depth pass) or the
-    // index `w` (colour pass: three planes).
     // colour pass: the contribution of a point that passed the 1 % test (hqs render.cu:297-313)
     auto accumulate = [&](bool off, uint32_t pix, uint32_t w, int point) __attribute__((always_inline)) {
         uint32_t vrg, vbc;                                                     // r << 16 | g,  b << 16 | 1
@@ -1480,24 +1434,16 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
             run_pix = pix; run_widx = off ? NO_PIXEL : w; run_rg16 = vrg; run_bc16 = vbc;
         }
     };
-    auto scatter = [&](bool valid, bool off, uint32_t pix, uint32_t w, unsigned long long *wp, uint32_t depth, uint64_t old, int point) __attribute__((always_inline)) {
-        if (COLOR_PASS) {
-            const float pw = __uint_as_float(depth);
-            const float old_depth = __uint_as_float((uint32_t)(old >> 32));
-            if (valid && (double)pw <= (double)old_depth * 1.01) {          // hqs render.cu:296
-                accumulate(off, pix, w, point);
-            }
-            return;
+    // colour pass: the 1 % test of the pending point, then its contribution. `valid`: the point is inside the frustum; `off`:
+    // ... but outside the batch's LDS window (then `pix` is its pixel and `old` came from global memory); `w`: its window index.
+    // Both flags come from lane masks the compiler keeps in scalar registers, so choosing between the LDS and the global path
+    // costs no vector instruction.
+    auto scatter = [&](bool valid, bool off, uint32_t pix, uint32_t w, uint32_t depth, uint64_t old, int point) __attribute__((always_inline)) {
+        const float pw = __uint_as_float(depth);
+        const float old_depth = __uint_as_float((uint32_t)(old >> 32));
+        if (valid && (double)pw <= (double)old_depth * 1.01) {              // hqs render.cu:296
+            accumulate(off, pix, w, point);
         }
-        // pre-read filter (:297-298) on the depth half only: the result is min(depth<<32|payload) over all inside points
-        // whatever passes it (min is idempotent), so ties go to the atomic instead of a 64-bit compare here
-        if (!valid || depth > (uint32_t)(old >> 32)) return;
-#ifdef PCR_EXP_KEY_FILTER
-        if (!((((unsigned long long)depth << 32) | (MODE == MODE_BASIC ? bc1_color(pal, (uint32_t)point & 15u) : payload)) < old)) return;
-#endif
-        const unsigned long long key = ((unsigned long long)depth << 32) | (MODE == MODE_BASIC ? bc1_color(pal, (uint32_t)point & 15u) : payload);   // :299 / depth.cu:139-145
-        if (!off) __hip_atomic_fetch_min(wp, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        else      atomicMin((unsigned long long *)&g_fb[pix], key);         // :300
     };
 
     // Basic / depth pass: the same for a pending point described without per-lane flags. Its window word `wp` is the dummy slot
@@ -1515,15 +1461,10 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
         if (__builtin_amdgcn_inverse_ballot_w64(off_mask)) atomicMin((unsigned long long *)&g_fb[pix], key);   // :300 (rare)
     };
 
-    // End of a point: SFT0 - sft bits were consumed. Retire the 0..2 words that ran dry, pull in far0/far1 (requested a
-    // whole point ago), request the next two, cut the next view. u = spare - consumed + 64 lies in [28, 95].
+    // Packed words, end of a point: SFT0 - sft bits were consumed. Retire the 0..2 words that ran dry, pull in far0/far1 (requested
+    // a whole point ago), request the next two, cut the next view. u = spare - consumed + 64 lies in [28, 95].
 #define PCR_ADVANCE_WORD_WINDOW()                                                          \
     do {                                                                                   \
-        if (LAYOUT == LAYOUT_POINT_WINDOWS) {                                              \
-            bits = ((uint64_t)nwin_hi << 32) | nwin_lo;                                    \
-            sft = SFT0;                                                                    \
-            break;                                                                         \
-        }                                                                                  \
         const uint32_t u_ = spare + (sft & 63u) + (64u - SFT0);                            \
         const uint32_t k_ = u_ >> 5;               /* 2: no word retired, 1: one, 0: two */ \
         spare = u_ & 31u;                                                                  \
@@ -1562,64 +1503,38 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
     // (tools/exp/instr_rate2.hip). The kernel has the registers to spare (<= 64 for eight waves per SIMD).
     // (only where there are registers to spare: not in the colour pass, which keeps its run of sums in registers, not with
     // the packed-words variant's five-word queue, not in the checked variant)
-#ifdef PCR_EXP_WORDS_VGPR_CONSTANTS
-    constexpr bool VGPR_CONSTANTS = !COLOR_PASS && !GENERIC;
-#else
     constexpr bool VGPR_CONSTANTS = !COLOR_PASS && LAYOUT == LAYOUT_POINT_WINDOWS && !GENERIC;
-#endif
     auto in_vgpr_f = [](float v) { if (!VGPR_CONSTANTS) return v; float r; asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "s"(v)); return r; };
-    auto in_vgpr_u = [](uint32_t v) { if (!VGPR_CONSTANTS) return v; uint32_t r; asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "s"(v)); return r; };
     const float m30 = in_vgpr_f(M[12]), m31 = in_vgpr_f(M[13]), m32 = in_vgpr_f(M[14]), m33 = in_vgpr_f(M[15]);   // the w row
     const uint32_t v_wx0 = wx0, v_wy0 = wy0;                // (per-lane values: in vector registers anyway)
 
-    PCR_TL(1);
     __syncthreads();        // table, escapes and window are visible
-    PCR_TL(2);
 
-#ifdef PCR_EXP_PROLOGUE_ONLY   /* experiment only: cost of the per-batch set-up and the window merge (results are wrong) */
-    const int npr_run = a.p.reserved == 12345 ? npr : 0;
-#else
-    const int npr_run = npr;
-#endif
-    uint32_t toff_ahead = (uint32_t)(bits >> (sft & 63u)) & 0x3FFCu;
-    uint32_t e_ahead = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(s_table) + toff_ahead);
-    // (point windows: the second symbol's entry of the point ahead as well, see the loop)
-    uint32_t sft_ahead = SFT0 - e_ahead;                    // :439 (the whole entry: byte 0 is the length)
-    uint32_t toff1_ahead = ((uint32_t)(bits >> 32) >> (sft_ahead & 31u)) & 0x3FFCu;
-    uint32_t e1_ahead = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(s_table) + toff1_ahead);
-    // DECODE_AHEAD (point windows, basic / depth pass): all three entries of a point are requested during the iteration before
-    // it, spread over that iteration (see the loop); these are the ones of point 0
+    // All three table entries of a point are requested during the iteration before it, spread over that iteration (see the
+    // loop); these are the ones of point 0.
     // Packed words (round 4): the same order. A point's view is cut from the chain's word queue once the lengths of the point before
     // it are known -- at the top of the iteration, where all three of its entries have arrived -- so the queue advances THERE,
     // the words it needs were requested a whole iteration earlier, and the three entries of point i+1 are requested from the new
-    // view during iteration i exactly as with the point windows (round 3's form, kept behind PCR_EXP_WORDS_SERIAL for A/B: every
-    // table read of a point hung on the one before it, two round trips per point exposed).
-#ifdef PCR_EXP_WORDS_SERIAL
-    constexpr bool DECODE_AHEAD = LAYOUT == LAYOUT_POINT_WINDOWS;
-#else
-    constexpr bool DECODE_AHEAD = true;
-#endif
-    uint32_t toff2_ahead = 0, e2_ahead = 0;
-    if (DECODE_AHEAD) {
-        toff2_ahead = (uint32_t)(bits >> ((sft_ahead - e1_ahead) & 63u)) & 0x3FFCu;
-        e2_ahead = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(s_table) + toff2_ahead);
-    }
+    // view during iteration i exactly as with the point windows. (Round 3 cut the view symbol by symbol: every table read of a
+    // point hung on the one before it, two round trips per point exposed.)
+    uint32_t toff_ahead = (uint32_t)(bits >> (sft & 63u)) & 0x3FFCu;
+    uint32_t e_ahead = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(s_table) + toff_ahead);
+    const uint32_t sft_ahead = SFT0 - e_ahead;              // :439 (the whole entry: byte 0 is the length)
+    uint32_t toff1_ahead = ((uint32_t)(bits >> 32) >> (sft_ahead & 31u)) & 0x3FFCu;
+    uint32_t e1_ahead = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(s_table) + toff1_ahead);
+    uint32_t toff2_ahead = (uint32_t)(bits >> ((sft_ahead - e1_ahead) & 63u)) & 0x3FFCu;
+    uint32_t e2_ahead = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(s_table) + toff2_ahead);
 
     // ---- the point loop ---------------------------------------------------------------------------------------------------------
     // A wave issues in order and the decode is a chain of LDS round trips (table entry -> length -> next key -> next
-    // entry). What can run inside those waits does: the table entry of a symbol is requested one step ahead, the scatter of
-    // the previous point runs under the read for this point's second symbol (-2.5 % kernel time for moving one call), the
-    // framebuffer word of a point is requested a whole point before it is used. A deeper software pipeline (decode k+2 |
-    // project k+1 | scatter k, the projection split over the second and third table read) was built and measured: +4 %,
-    // hipcc spends the 64 registers on copies between the stages (profiles/r02_experiments.md).
+    // entry). What can run inside those waits does: the table entries of a point are requested during the point before it, the
+    // scatter of the previous point runs under the reads of this point's escape words, the framebuffer word of a point is requested
+    // a whole point before it is used. A deeper software pipeline (decode k+2 | project k+1 | scatter k, the projection split over
+    // the second and third table read) was built and measured: +4 %, hipcc spends the 64 registers on copies between the stages
+    // (profiles/r02_experiments.md).
 
-    // One symbol step (:430-451) of the point being decoded. `e` is the table entry of this symbol, fetched one step ahead;
-    // (bits >> sft) & 0x3FFC is 4 x the 12-bit window of :431-433 (== ((L|R) & mask) >> 20) at the current position, i.e.
-    // the byte offset of an entry. Returns the decoded delta.
-    // esc_first (the third symbol's form): the escape word, if any, is requested BEFORE the next table entry. LDS results
-    // return in issue order, so its value can be waited for (lgkmcnt(1)) while the look-ahead entry of the next point's first
-    // symbol -- needed only at the top of the next iteration -- stays in flight.
-    // The delta a table entry stands for (:435-438): the entry's own value, or -- escape -- the chain's next escape word.
+    // The delta a table entry stands for (:435-438): the entry's own value, or -- escape -- the chain's next escape word. `toff`
+    // is the entry's byte offset in the table: 4 x the 12-bit window of :431-433 (== ((L|R) & mask) >> 20).
     auto entry_value = [&](uint32_t e, uint32_t toff) __attribute__((always_inline)) -> uint32_t {
         int32_t val = (int32_t)e >> TE_VALUE_SHIFT;                         // the delta itself (v_ashrrev_i32)
         if (val == TE_SLOW_VALUE) {                                         // escape or wide
@@ -1644,7 +1559,7 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
     auto table_entry = [&](uint32_t toff) __attribute__((always_inline)) -> uint32_t {
         return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(s_table) + toff);
     };
-    // DECODE_AHEAD, top of iteration i (the entries e0..e2 of point i have arrived): request the first entry of point i+1. Point
+    // Top of iteration i (the entries e0..e2 of point i have arrived): request the first entry of point i+1. Point
     // windows: its key is the top of the window that has been in registers for an iteration. Packed words: the queue advances by
     // what point i consumed (the three lengths: byte 0 of the entries, subtracted whole -- only the low six bits of `sft` count),
     // the view of point i+1 is cut, its top twelve bits are the key. (A macro, not a lambda: a closure that captures the word queue
@@ -1660,53 +1575,11 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
         }                                                                                   \
         e_ahead = table_entry(toff_ahead);                                                  \
     } while (0)
-    // LAYOUT_WORDS: the symbols of a point AND the first symbol of the next one are cut from one 64-bit view, so every
-    // table read hangs on the one before it. esc_first (the third symbol's form): the escape word, if any, is requested
-    // BEFORE the next table entry. LDS results return in issue order, so its value can be waited for (lgkmcnt(1)) while the
-    // look-ahead entry of the next point's first symbol -- needed only at the top of the next iteration -- stays in flight.
-    auto symbol_step = [&](auto esc_first) __attribute__((always_inline)) -> uint32_t {
-        constexpr bool ESC_FIRST = decltype(esc_first)::value;
-        const uint32_t e = e_ahead, toff = toff_ahead;                      // :435-436
-        // :439. The whole entry is subtracted: byte 0 is the length, and only the low six bits of `sft` are ever used (the
-        // 64-bit shift below takes its count modulo 64; 14 <= true sft <= 50) -- a plain v_sub_u32
-        sft -= e;
-        toff_ahead = (uint32_t)(bits >> (sft & 63u)) & 0x3FFCu;
-        if (!ESC_FIRST) e_ahead = table_entry(toff_ahead);
-        const uint32_t val = entry_value(e, toff);
-        if (ESC_FIRST) e_ahead = table_entry(toff_ahead);
-#ifdef PCR_EXP_PAD_VALU   /* experiment: PCR_EXP_PAD_VALU extra independent VALU instructions per symbol step */
-        {
-            uint32_t pad = tid;
-#pragma unroll
-            for (int k = 0; k < PCR_EXP_PAD_VALU; ++k) asm volatile("v_add_u32 %0, %0, %0" : "+v"(pad));
-        }
-#endif
-        return val;
-    };
 
-#if defined(PCR_EXP_PRIO_LAST)   /* experiment: the last workgroups to start share their CU with an older one that would starve them: raise them */
-    if (blockIdx.x + PCR_EXP_PRIO_LAST >= gridDim.x) __builtin_amdgcn_s_setprio(3);
-#endif
-#if defined(PCR_EXP_PRIO_WAVE)   /* experiment: the hardware issues oldest-first; give a workgroup's later waves the higher priority */
-    switch ((tid >> 8) & 3u) {
-        case 0: __builtin_amdgcn_s_setprio(0); break;
-        case 1: __builtin_amdgcn_s_setprio(1); break;
-        case 2: __builtin_amdgcn_s_setprio(2); break;
-        default: __builtin_amdgcn_s_setprio(3); break;
-    }
-#endif
-    for (int seg = 0; seg < npr_run; seg += 16) {
-#if defined(PCR_EXP_PRIO_SEG)    /* experiment: a wave that is behind (an earlier segment) goes first */
-      switch (seg >> 4) {
-          case 0: __builtin_amdgcn_s_setprio(3); break;
-          case 1: __builtin_amdgcn_s_setprio(2); break;
-          case 2: __builtin_amdgcn_s_setprio(1); break;
-          default: __builtin_amdgcn_s_setprio(0); break;
-      }
-#endif
+    for (int seg = 0; seg < npr; seg += 16) {
       // Segment boundary: the point still pending belongs to the previous BC1 block, so it is scattered before the
       // block registers rotate (its framebuffer word has been in flight for the whole decode of the last point).
-      if (COLOR_PASS) { scatter(__builtin_amdgcn_inverse_ballot_w64(pend_valid_mask), __builtin_amdgcn_inverse_ballot_w64(pend_off_mask), pend_pix, pend_w, nullptr, pend_depth, pend_old, seg - 1); pend_valid_mask = 0; pend_off_mask = 0; }
+      if (COLOR_PASS) { scatter(__builtin_amdgcn_inverse_ballot_w64(pend_valid_mask), __builtin_amdgcn_inverse_ballot_w64(pend_off_mask), pend_pix, pend_w, pend_depth, pend_old, seg - 1); pend_valid_mask = 0; pend_off_mask = 0; }
       else { scatter_min(pend_p, pend_depth, pend_old_hi, pend_off_mask, pend_pix, seg - 1); pend_p = s_dummy; pend_off_mask = 0;
              // (the dummy slot's zero, READ rather than set: with an LDS read behind the last table request on this way into the loop
              // as well as on the way round it, hipcc's wait for that entry at the top of an iteration leaves one result in flight)
@@ -1719,7 +1592,7 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
               cnext = cblocks[min((seg >> 4) + 1, 3) * PCR_WORKGROUP_SIZE];
           }
       }
-      const int seg_end = min(seg + 16, npr_run);
+      const int seg_end = min(seg + 16, npr);
 #pragma unroll 1
       for (int i = seg; i < seg_end; ++i) {                                 // :428
         uint32_t fetched_hi = 0, fetched_lo = 0;
@@ -1729,110 +1602,56 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
             PCR_PW_NEXT_ROW();
             fetched_hi = pw_load_hi(); fetched_lo = pw_load_lo();
         }
-#if defined(PCR_EXP_PAD_FAST) || defined(PCR_EXP_PAD_SLOW) || defined(PCR_EXP_PAD_SALU)   /* experiment: what one more instruction per point costs */
-        {
-            uint32_t pad = tid;
-            (void)pad;
-#ifdef PCR_EXP_PAD_FAST
-#pragma unroll
-            for (int k = 0; k < PCR_EXP_PAD_FAST; ++k) asm volatile("v_add_u32 %0, %0, %0" : "+v"(pad));
-#endif
-#ifdef PCR_EXP_PAD_SLOW
-#pragma unroll
-            for (int k = 0; k < PCR_EXP_PAD_SLOW; ++k) asm volatile("v_lshlrev_b32 %0, 1, %0" : "+v"(pad));
-#endif
-#ifdef PCR_EXP_PAD_SALU
-            uint32_t spad = (uint32_t)i;
-#pragma unroll
-            for (int k = 0; k < PCR_EXP_PAD_SALU; ++k) asm volatile("s_add_u32 %0, %0, 1" : "+s"(spad));
-#endif
-        }
-#endif
         uint32_t d0, d1, d2;
-        uint32_t sft1_next = 0;
-        if (DECODE_AHEAD) {
-            // All three table entries of point i were requested while point i-1 was projected: nothing of the decode's dependent
-            // chain (entry -> length -> key -> entry) is waited for here. The escape words of the three symbols, if any, are
-            // requested back to back; the scatter of point i-1 runs under them. The entries of point i+1 (its window has been in
-            // registers since the top of the last iteration) are requested in three places of this iteration, each a table
-            // round trip after the one before: here, in front of the dot products, behind the division.
-            const uint32_t e0 = e_ahead, toff0 = toff_ahead, e1 = e1_ahead, toff1 = toff1_ahead, e2 = e2_ahead, toff2 = toff2_ahead;
-            if (!GENERIC) {
-                // Everything that hangs on a result of the last iteration -- the three entries, the framebuffer word of point i-1 --
-                // is looked at BEFORE this iteration issues its first LDS instruction: results return in issue order and hipcc
-                // counts a read under a branch (an escape word's) as maybe not issued, so a wait placed behind such reads waits for
-                // them as well. What is tested becomes a lane mask in a scalar register pair.
-                int32_t v0 = (int32_t)e0 >> TE_VALUE_SHIFT, v1 = (int32_t)e1 >> TE_VALUE_SHIFT, v2 = (int32_t)e2 >> TE_VALUE_SHIFT;
-                const uint64_t esc0 = __builtin_amdgcn_ballot_w64(v0 == TE_SLOW_VALUE), esc1 = __builtin_amdgcn_ballot_w64(v1 == TE_SLOW_VALUE),
-                               esc2 = __builtin_amdgcn_ballot_w64(v2 == TE_SLOW_VALUE);
-                // the pre-read filter of scatter_min / the 1 % test of the colour pass (hqs render.cu:296)
-                const uint64_t draw = COLOR_PASS
-                    ? pend_valid_mask & __builtin_amdgcn_ballot_w64((double)__uint_as_float(pend_depth) <= (double)__uint_as_float((uint32_t)(pend_old >> 32)) * 1.01)
-                    : __builtin_amdgcn_ballot_w64(pend_depth <= pend_old_hi);
-                if (__builtin_expect(__builtin_amdgcn_inverse_ballot_w64(esc0), 1)) v0 = *esc_next++;               // :438 (every such entry is an escape whose word is in the pool)
-                if (__builtin_expect(__builtin_amdgcn_inverse_ballot_w64(esc1), 1)) v1 = *esc_next++;
-                if (__builtin_expect(__builtin_amdgcn_inverse_ballot_w64(esc2), 1)) v2 = *esc_next++;
-                PCR_NEXT_FIRST_ENTRY(e0, e1, e2);
-                if (COLOR_PASS) {
-                    if (__builtin_amdgcn_inverse_ballot_w64(draw)) accumulate(__builtin_amdgcn_inverse_ballot_w64(pend_off_mask), pend_pix, pend_w, i - 1);
-                } else if (__builtin_amdgcn_inverse_ballot_w64(draw)) {                         // second half of rasterize() for point i-1
-                    const unsigned long long key = ((unsigned long long)pend_depth << 32) | (MODE == MODE_BASIC ? bc1_color(pal, (uint32_t)(i - 1) & 15u) : payload);
-                    __hip_atomic_fetch_min(pend_p, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if (__builtin_amdgcn_inverse_ballot_w64(pend_off_mask)) atomicMin((unsigned long long *)&g_fb[pend_pix], key);   // :300 (rare)
-                }
-                d0 = (uint32_t)v0; d1 = (uint32_t)v1; d2 = (uint32_t)v2;
-            } else {
-                d0 = entry_value(e0, toff0);                                    // :430
-                d1 = entry_value(e1, toff1);
-                d2 = entry_value(e2, toff2);
-                PCR_NEXT_FIRST_ENTRY(e0, e1, e2);
-                if (COLOR_PASS) scatter(__builtin_amdgcn_inverse_ballot_w64(pend_valid_mask), __builtin_amdgcn_inverse_ballot_w64(pend_off_mask), pend_pix, pend_w, nullptr, pend_depth, pend_old, i - 1);
-                else scatter_min(pend_p, pend_depth, pend_old_hi, pend_off_mask, pend_pix, i - 1);
+        // All three table entries of point i were requested while point i-1 was projected: nothing of the decode's dependent
+        // chain (entry -> length -> key -> entry) is waited for here. The escape words of the three symbols, if any, are
+        // requested back to back; the scatter of point i-1 runs under them. The entries of point i+1 (its window has been in
+        // registers since the top of the last iteration) are requested in three places of this iteration, each a table
+        // round trip after the one before: here, in front of the dot products, behind the division.
+        const uint32_t e0 = e_ahead, toff0 = toff_ahead, e1 = e1_ahead, toff1 = toff1_ahead, e2 = e2_ahead, toff2 = toff2_ahead;
+        if (!GENERIC) {
+            // Everything that hangs on a result of the last iteration -- the three entries, the framebuffer word of point i-1 --
+            // is looked at BEFORE this iteration issues its first LDS instruction: results return in issue order and hipcc
+            // counts a read under a branch (an escape word's) as maybe not issued, so a wait placed behind such reads waits for
+            // them as well. What is tested becomes a lane mask in a scalar register pair.
+            int32_t v0 = (int32_t)e0 >> TE_VALUE_SHIFT, v1 = (int32_t)e1 >> TE_VALUE_SHIFT, v2 = (int32_t)e2 >> TE_VALUE_SHIFT;
+            const uint64_t esc0 = __builtin_amdgcn_ballot_w64(v0 == TE_SLOW_VALUE), esc1 = __builtin_amdgcn_ballot_w64(v1 == TE_SLOW_VALUE),
+                           esc2 = __builtin_amdgcn_ballot_w64(v2 == TE_SLOW_VALUE);
+            // the pre-read filter of scatter_min / the 1 % test of the colour pass (hqs render.cu:296)
+            const uint64_t draw = COLOR_PASS
+                ? pend_valid_mask & __builtin_amdgcn_ballot_w64((double)__uint_as_float(pend_depth) <= (double)__uint_as_float((uint32_t)(pend_old >> 32)) * 1.01)
+                : __builtin_amdgcn_ballot_w64(pend_depth <= pend_old_hi);
+            if (__builtin_expect(__builtin_amdgcn_inverse_ballot_w64(esc0), 1)) v0 = *esc_next++;               // :438 (every such entry is an escape whose word is in the pool)
+            if (__builtin_expect(__builtin_amdgcn_inverse_ballot_w64(esc1), 1)) v1 = *esc_next++;
+            if (__builtin_expect(__builtin_amdgcn_inverse_ballot_w64(esc2), 1)) v2 = *esc_next++;
+            PCR_NEXT_FIRST_ENTRY(e0, e1, e2);
+            if (COLOR_PASS) {
+                if (__builtin_amdgcn_inverse_ballot_w64(draw)) accumulate(__builtin_amdgcn_inverse_ballot_w64(pend_off_mask), pend_pix, pend_w, i - 1);
+            } else if (__builtin_amdgcn_inverse_ballot_w64(draw)) {                         // second half of rasterize() for point i-1
+                const unsigned long long key = ((unsigned long long)pend_depth << 32) | (MODE == MODE_BASIC ? bc1_color(pal, (uint32_t)(i - 1) & 15u) : payload);
+                __hip_atomic_fetch_min(pend_p, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (__builtin_amdgcn_inverse_ballot_w64(pend_off_mask)) atomicMin((unsigned long long *)&g_fb[pend_pix], key);   // :300 (rare)
             }
-        } else if (LAYOUT == LAYOUT_POINT_WINDOWS) {
-            // The first symbol's key is the top of the point's own window: its entry was requested a whole point ago (the one of
-            // point i+1, whose window is already in registers, is requested now). The second symbol's entry was requested before
-            // the point began as well: at the end of the iteration before, as soon as the first entry gave the second key (the
-            // second symbol starts and ends inside the window's first 32 bits: a 32-bit shift, the hardware takes the count
-            // modulo 32 and SFT0 - 32 = 18). Left on the dependent chain of a point: entry 1 -> length -> key 2 -> entry 2, one LDS
-            // round trip (the third symbol may reach into the low plane's byte).
-            const uint32_t e0 = e_ahead, toff0 = toff_ahead, e1 = e1_ahead, toff1 = toff1_ahead;
-            sft = sft_ahead;
-            toff_ahead = (nwin_hi >> (SFT0 & 31u)) & 0x3FFCu;
-            e_ahead = table_entry(toff_ahead);
+            d0 = (uint32_t)v0; d1 = (uint32_t)v1; d2 = (uint32_t)v2;
+        } else {
             d0 = entry_value(e0, toff0);                                    // :430
-            // second half of rasterize() for point i-1, under the table read of this point's second symbol: its framebuffer
-            // word has been in flight since the end of the last iteration
-            // (the colour pass, which carries a run of sums and has no register to spare, scatters after the third symbol)
-            if (!COLOR_PASS) scatter_min(pend_p, pend_depth, pend_old_hi, pend_off_mask, pend_pix, i - 1);
-            sft -= e1;
-            const uint32_t toff2 = (uint32_t)(bits >> (sft & 63u)) & 0x3FFCu;
-            const uint32_t e2 = table_entry(toff2);
             d1 = entry_value(e1, toff1);
             d2 = entry_value(e2, toff2);
-        } else {
-            constexpr std::integral_constant<bool, false> table_first{};
-            constexpr std::integral_constant<bool, true> escape_first{};
-            d0 = symbol_step(table_first);                                  // :430
-            if (!COLOR_PASS) scatter_min(pend_p, pend_depth, pend_old_hi, pend_off_mask, pend_pix, i - 1);
-            d1 = symbol_step(table_first);
-            d2 = symbol_step(escape_first);
+            PCR_NEXT_FIRST_ENTRY(e0, e1, e2);
+            if (COLOR_PASS) scatter(__builtin_amdgcn_inverse_ballot_w64(pend_valid_mask), __builtin_amdgcn_inverse_ballot_w64(pend_off_mask), pend_pix, pend_w, pend_depth, pend_old, i - 1);
+            else scatter_min(pend_p, pend_depth, pend_old_hi, pend_off_mask, pend_pix, i - 1);
         }
-        if (COLOR_PASS && !DECODE_AHEAD) scatter(__builtin_amdgcn_inverse_ballot_w64(pend_valid_mask), __builtin_amdgcn_inverse_ballot_w64(pend_off_mask), pend_pix, pend_w, nullptr, pend_depth, pend_old, i - 1);
         px = (int32_t)((uint32_t)px + d0);                                  // :454-456, :463
         py = (int32_t)((uint32_t)py + d1);
         pz = (int32_t)((uint32_t)pz + d2);
-        if (!(DECODE_AHEAD && LAYOUT == LAYOUT_WORDS)) PCR_ADVANCE_WORD_WINDOW();     // (packed words, decode ahead: the queue advanced at the top)
-#ifdef PCR_EXP_NO_RASTER   /* experiment only: decode cost alone (results are wrong) */
-        if ((px ^ py ^ pz) == 0x7fffffff && i == 63) g_fb[tid] = 0;
-        if (LAYOUT == LAYOUT_POINT_WINDOWS) { nwin_hi = fetched_hi; nwin_lo = fetched_lo << 24; }
-        continue;
-#endif
+        if (LAYOUT == LAYOUT_POINT_WINDOWS) {               // the view of point i+1 (packed words: cut at the top of the iteration)
+            bits = ((uint64_t)nwin_hi << 32) | nwin_lo;
+            sft = SFT0;
+        }
         // (per-point temporaries and the three parts of the projection live inside the loop body: nothing of a point's
         // projection is carried into the next iteration -- with ix / iy declared outside, every iteration copied them)
         float fx, fy, fz;
         float qx, qy, qw;
-        bool inside;
         uint64_t cand_mask;                 // lanes whose point is inside the frustum, as a 64-bit lane mask (a scalar register pair)
         int ix, iy;
         // first half of rasterize() (:278-287), part 1: the three dot products and the inside test without dividing. For finite
@@ -1877,7 +1696,6 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
                 // x == y == 0 -- a point exactly in the eye, or a degenerate matrix -- passes |x| <= w and is no candidate: :296 `w <= 0`)
                 cand_mask &= __builtin_amdgcn_ballot_w64(qw > 0.0f);
             }
-            inside = __builtin_amdgcn_inverse_ballot_w64(cand_mask);
         };
         // part 3: the point becomes the pending one; its framebuffer word is requested now and consumed an iteration later:
         // from the LDS window if the pixel lies in the batch's rectangle (nearly always), from global memory otherwise (:297)
@@ -1890,11 +1708,7 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
                 const uint32_t rx = (uint32_t)ix - v_wx0, ry = (uint32_t)iy - v_wy0;
                 // (bitwise: `&&` would put the two compares under a branch of their own)
                 const uint64_t in_mask = cand_mask & __builtin_amdgcn_ballot_w64(rx < ww) & __builtin_amdgcn_ballot_w64(ry < wh);
-#ifdef PCR_EXP_NO_OFFWIN   /* timing experiment only (wrong frames): what the points outside their LDS window cost */
-                pend_off_mask = 0;
-#else
                 pend_off_mask = cand_mask & ~in_mask;
-#endif
                 pend_depth = __float_as_uint(qw);                                       // :287
                 pend_p = s_win_mine + (__builtin_amdgcn_inverse_ballot_w64(in_mask) ? (uint32_t)__umul24(ry, ww) + rx : dummy_idx);
                 // (the depth half alone: the filter looks at nothing else, and a 64-bit read whose low half nobody wants had hipcc reuse
@@ -1908,9 +1722,6 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
                     const uint64_t stray_now = g_tiles ? pend_off_mask & (__builtin_amdgcn_ballot_w64((uint32_t)ix - whole_x0 >= whole_w) |
                                                                           __builtin_amdgcn_ballot_w64((uint32_t)iy - whole_y0 >= whole_h)) : 0;
                     const bool sample = mostly_outside;                             // (uniform) see below
-#ifdef PCR_EXP_FAR_STATS
-                    if ((threadIdx.x & 63u) == 0) { atomicAdd(&g_far[0], 1ull); atomicAdd(&g_far[1], (unsigned long long)__builtin_popcountll(pend_off_mask)); if (sample) atomicAdd(&g_far[2], 1ull); }
-#endif
                     if (__builtin_amdgcn_inverse_ballot_w64(pend_off_mask)) {
                         pend_pix = (uint32_t)(ix + iy * img_w);                         // :285
                         if (__builtin_amdgcn_inverse_ballot_w64(stray_now)) {
@@ -1920,7 +1731,7 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
                         }
                         // The pre-read of the global framebuffer word (:297) is a filter in front of the global atomic -- min is
                         // idempotent, the frame is the same without it -- that costs the wave a memory round trip per point. It stops
-                        // 70-85 % of the points it sees, whatever the frame (tools/exp/far_stats.py); what differs is how many there
+                        // 70-85 % of the points it sees, whatever the frame (profiles/r03_experiments.md); what differs is how many there
                         // are. In a Morton-sorted stream 0.2 % (1080p) to 5 % (close-up) of a frame's wave-iterations have such lanes,
                         // 9-31 of them, concentrated in a few waves that the round trips turn into the launch's stragglers: without
                         // the load 4096x4096 is 8 % faster, a close-up 7 %, the benchmark frame 2.6 %. In an unsorted stream (a batch
@@ -1965,49 +1776,26 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
             fy = (float)__fma_rn((double)py, sy, oy);
             fz = (float)__fma_rn((double)pz, sz, oz);
         }
-        if (DECODE_AHEAD) {                         // second entry of point i+1 (`bits` is its window by now; the first has arrived)
-            sft1_next = SFT0 - e_ahead;
-            toff1_ahead = ((uint32_t)(bits >> 32) >> (sft1_next & 31u)) & 0x3FFCu;
-            e1_ahead = table_entry(toff1_ahead);
-        }
+        // second entry of point i+1 (`bits` is its window by now; the first has arrived)
+        const uint32_t sft1_next = SFT0 - e_ahead;
+        toff1_ahead = ((uint32_t)(bits >> 32) >> (sft1_next & 31u)) & 0x3FFCu;
+        e1_ahead = table_entry(toff1_ahead);
         project_dots();                                                     // first half of rasterize() (:278-287) for point i
         project_divide();
-        if (DECODE_AHEAD) {                         // third entry of point i+1
-            toff2_ahead = (uint32_t)(bits >> ((sft1_next - e1_ahead) & 63u)) & 0x3FFCu;
-            e2_ahead = table_entry(toff2_ahead);
-        }
-#ifdef PCR_EXP_NO_FBLOAD   /* experiment only: decode + projection, no framebuffer traffic (results are wrong) */
-        if (inside && ix == 0x12345678) g_fb[tid] = __float_as_uint(qw);
-        pend_valid_mask = 0; pend_p = s_dummy; pend_old_hi = 0; pend_off_mask = 0;
-#else
+        // third entry of point i+1
+        toff2_ahead = (uint32_t)(bits >> ((sft1_next - e1_ahead) & 63u)) & 0x3FFCu;
+        e2_ahead = table_entry(toff2_ahead);
         project_request();
-#endif
-        if (LAYOUT == LAYOUT_POINT_WINDOWS && !DECODE_AHEAD) {       // `bits` is the next point's window by now, e_ahead its first entry (requested at the top)
-            sft_ahead = SFT0 - e_ahead;
-            toff1_ahead = ((uint32_t)(bits >> 32) >> (sft_ahead & 31u)) & 0x3FFCu;
-            e1_ahead = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(s_table) + toff1_ahead);
-        }
         if (LAYOUT == LAYOUT_POINT_WINDOWS) { nwin_hi = fetched_hi; nwin_lo = fetched_lo << 24; }
       }
     }
-    if (COLOR_PASS) { scatter(__builtin_amdgcn_inverse_ballot_w64(pend_valid_mask), __builtin_amdgcn_inverse_ballot_w64(pend_off_mask), pend_pix, pend_w, nullptr, pend_depth, pend_old, npr_run - 1); flush_run(); }
-    else scatter_min(pend_p, pend_depth, pend_old_hi, pend_off_mask, pend_pix, npr_run - 1);
+    if (COLOR_PASS) { scatter(__builtin_amdgcn_inverse_ballot_w64(pend_valid_mask), __builtin_amdgcn_inverse_ballot_w64(pend_off_mask), pend_pix, pend_w, pend_depth, pend_old, npr - 1); flush_run(); }
+    else scatter_min(pend_p, pend_depth, pend_old_hi, pend_off_mask, pend_pix, npr - 1);
 
     // merge the window into the global framebuffer: rows of the rectangle are contiguous, so the 64 lanes of a wave
     // hit a handful of cache lines; only pixels this batch improved issue an atomic
-#if defined(PCR_EXP_PRIO_WAVE) || defined(PCR_EXP_PRIO_SEG) || defined(PCR_EXP_PRIO_LAST)
-    __builtin_amdgcn_s_setprio(0);
-#endif
-#ifdef PCR_EXP_FAR_STATS
-    if ((threadIdx.x & 63u) == 0) atomicAdd(&g_far[5], 1ull);
-#endif
-#ifdef PCR_EXP_TIMELINE
-    if ((threadIdx.x & 63u) == 0) g_wave_end[(size_t)blockIdx.x * 16 + (threadIdx.x >> 6)] = wall_clock64();
-#endif
-    PCR_TL(3);
     if (wpix) {
         __syncthreads();
-        PCR_TL(4);
         for_window_pixels([&](uint32_t i, size_t gp) {
             if (COLOR_PASS) {
                 const unsigned long long vba = s_acc[2 * i + 1];
@@ -2024,7 +1812,6 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
             }
         });
     }
-    PCR_TL(5);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2051,7 +1838,8 @@ struct LasArgs {
     int win_capacity;
     // dense list of the batches k_las_render draws (not culled, not the last one), compacted by the prepass per workgroup of
     // LAS_PREPASS_BATCHES batches in the file's order, as the Huffman methods' lists are (RenderArgs::order): order[wg * 256 ..],
-    // chunk_count[wg]; k_las_render's workgroup x finds the x-th entry with a wave-wide prefix sum over the chunk counts
+    // chunk_count[wg]; workgroup x of k_las_render / k_las_render_color finds the x-th entry with a wave-wide prefix sum over the
+    // chunk counts (las_list_batch)
     uint32_t *order;          // [chunks * LAS_PREPASS_BATCHES]
     uint32_t *chunk_count;    // [LAS_CLASSES][chunks]
     uint32_t chunks;
@@ -2181,8 +1969,7 @@ __device__ __forceinline__ void las_prepass_batch(const LasArgs &a, int64_t b, p
 }
 
 // Which batch is the blockIdx.x-th of the prepass's list (false: none)? Every wave for itself: a 64-lane inclusive prefix sum over
-// the chunk counts. k_las_render_color's; k_las_render keeps the same walk inline (called from there, this function reorders two of
-// the basic kernel's instructions).
+// the chunk counts. The list walk of k_las_render and k_las_render_color.
 __device__ __forceinline__ bool las_list_batch(const LasArgs &a, uint32_t &b)
 {
     const uint32_t lane = threadIdx.x & 63u;
@@ -2224,6 +2011,128 @@ __device__ __forceinline__ bool las_list_batch(const LasArgs &a, uint32_t &b)
     return true;
 }
 
+// ------------------------------------------------------------------------------------------------
+// What the two 10-10-10 kernels share (k_las_render, k_las_render_color): the batch set-up, the walk over its points and their
+// projection, so that both passes of loop_las_hqs see identical positions.
+// ------------------------------------------------------------------------------------------------
+struct ProjRows { float m00, m01, m02, m03, m10, m11, m12, m13, m30, m31, m32, m33; };   // rows x, y and w of the matrix
+struct Projection {
+    uint64_t cand;      // lanes whose point is inside the frustum, as a 64-bit lane mask (a scalar register pair)
+    float w;            // the point's depth
+    int ix, iy;         // its pixel (computed by every lane: garbage for a lane that is not in `cand`)
+};
+
+// First half of rasterize() (render.cu:108-118), as in k_render: the three dot products and the inside test without dividing
+// (for finite w > 0 the correctly rounded quotient lies in [-1,1] exactly when |x| <= w), then the division: the IEEE sequence
+// hipcc emits for `/` with its range scaling removed, shared reciprocal, x and y packed -- bit-identical to `/` for w in
+// [2^-64, 2^64). A wave in which some candidate's w lies outside that range (or is 0) takes `/` for all lanes.
+__device__ __forceinline__ Projection project_point(const ProjRows &m, float fw, float fh, float x, float y, float z)
+{
+    Projection p;
+    const float qx = __fmaf_rn(m.m03, 1.0f, __fmaf_rn(m.m02, z, __fmaf_rn(m.m01, y, m.m00 * x)));
+    const float qy = __fmaf_rn(m.m13, 1.0f, __fmaf_rn(m.m12, z, __fmaf_rn(m.m11, y, m.m10 * x)));
+    const float qw = __fmaf_rn(m.m33, 1.0f, __fmaf_rn(m.m32, z, __fmaf_rn(m.m31, y, m.m30 * x)));
+    p.cand = __builtin_amdgcn_ballot_w64(fabsf(qx) <= qw) & __builtin_amdgcn_ballot_w64(fabsf(qy) <= qw);
+    {
+        const float r0 = __builtin_amdgcn_rcpf(qw);
+        const float r1 = __fmaf_rn(__fmaf_rn(-qw, r0, 1.0f), r0, r0);
+        const v2f xy = {qx, qy}, rr = {r1, r1}, nw = {-qw, -qw};
+        const v2f q0 = xy * rr;
+        const v2f q1 = __builtin_elementwise_fma(__builtin_elementwise_fma(nw, q0, xy), rr, q0);
+        const v2f q2 = __builtin_elementwise_fma(__builtin_elementwise_fma(nw, q1, xy), rr, q1);
+        const v2f half = {0.5f, 0.5f}, size = {fw, fh};
+        const v2f img = __builtin_elementwise_fma(q2, half, half) * size;
+        p.ix = (int)img.x; p.iy = (int)img.y;
+    }
+    const uint64_t w_ok_mask = __builtin_amdgcn_ballot_w64((__float_as_uint(qw) - 0x1F800000u) < 0x40000000u);   // 2^-64 <= w < 2^64
+    if (__builtin_expect((p.cand & ~w_ok_mask) != 0, 0)) {              // (uniform, practically never) the plain `/` for all lanes
+        const float nx = qx / qw, ny = qy / qw;
+        p.ix = (int)(__fmaf_rn(nx, 0.5f, 0.5f) * fw);
+        p.iy = (int)(__fmaf_rn(ny, 0.5f, 0.5f) * fh);
+        p.cand &= __builtin_amdgcn_ballot_w64(qw > 0.0f);               // (w == 0 with x == y == 0 passes |x| <= w: rasterize rejects w <= 0, :113)
+    }
+    p.w = qw;
+    return p;
+}
+
+struct LasBatch {
+    int level;                          // 0 / 1 / 2..4: 12 / 8 / 4 bytes per point
+    float sx, sy, sz, ox, oy, oz;       // dequantisation: x = X * sx + ox
+    ProjRows m;
+    float fw, fh;
+    size_t base;                        // the batch's first point
+    const uint4 *q4, *q8, *q12;         // its level arrays
+};
+
+// The set-up of batch b at level `level` (read by the kernel at its start)
+__device__ __forceinline__ LasBatch las_batch(const LasArgs &a, uint32_t b, int level)
+{
+    LasBatch L;
+    L.level = level;
+    const pcr_xyz_batch g = a.s.batches[b];
+    const float div = level >= 2 ? 1024.0f : 1073741824.0f;                  // STEPS_10BIT / STEPS_30BIT
+    L.sx = (g.max_x - g.min_x) / div; L.sy = (g.max_y - g.min_y) / div; L.sz = (g.max_z - g.min_z) / div;   // :145, :345
+    L.ox = g.min_x; L.oy = g.min_y; L.oz = g.min_z;
+    // (the w row of the matrix in vector registers, as in k_render: a v_fma_f32 whose operands are all VGPRs issues in ~2.3 cycles,
+    // with an SGPR operand in ~4.2; the x and y rows run as packed operations with scalar pairs)
+    auto in_vgpr = [](float v) { float r; asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "s"(v)); return r; };
+    const float *M = a.p.transform;
+    L.m = { M[0], M[1], M[2], M[3], M[4], M[5], M[6], M[7], in_vgpr(M[12]), in_vgpr(M[13]), in_vgpr(M[14]), in_vgpr(M[15]) };
+    L.fw = (float)a.p.width; L.fh = (float)a.p.height;
+    L.base = (size_t)b * PCR_POINTS_PER_BATCH;
+    L.q4 = reinterpret_cast<const uint4 *>(a.s.xyz4 + L.base);
+    L.q8 = reinterpret_cast<const uint4 *>(a.s.xyz8 + L.base);
+    L.q12 = reinterpret_cast<const uint4 *>(a.s.xyz12 + L.base);
+    return L;
+}
+
+// The batch's points: thread t takes the quads t, t + 1024, ..., read with 16-byte loads from the level's one to three arrays,
+// the next quad in flight while this one is projected. Per quad, quad_fn(quad) runs first -- in front of the next quad's loads --
+// and its result goes to point_fn(projection, result, j) for the quad's points j = 0..3 in turn.
+template <typename QuadFn, typename PointFn>
+__device__ __forceinline__ void las_points(const LasBatch &L, QuadFn quad_fn, PointFn point_fn)
+{
+    const uint32_t tid = threadIdx.x;
+    // One copy of the loop per number of level arrays read (4 / 8 / 12 bytes per point): the copy that reads one array does not
+    // carry the registers of the other two (with one loop for all three, the 64-register budget of eight waves per SIMD spilled).
+    auto quads = [&](auto arrays_) __attribute__((always_inline)) {
+        constexpr int ARRAYS = decltype(arrays_)::value;
+        uint4 n4 = L.q4[tid], n8 = make_uint4(0, 0, 0, 0), n12 = make_uint4(0, 0, 0, 0);
+        if (ARRAYS >= 2) n8 = L.q8[tid];
+        if (ARRAYS >= 3) n12 = L.q12[tid];
+#pragma unroll 1
+        for (int i = 0; i < PCR_POINTS_PER_BATCH / 4 / PCR_WORKGROUP_SIZE; ++i) {
+            const uint4 c4 = n4, c8 = n8, c12 = n12;
+            const uint32_t quad = tid + (uint32_t)i * PCR_WORKGROUP_SIZE;
+            const auto per_quad = quad_fn(quad);
+            {   // next quad in flight while this one is projected (the last iteration re-reads its own: no branch around the loads)
+                const uint32_t nq = min(quad + PCR_WORKGROUP_SIZE, (uint32_t)(PCR_POINTS_PER_BATCH / 4 - 1));
+                n4 = L.q4[nq];
+                if (ARRAYS >= 2) n8 = L.q8[nq];
+                if (ARRAYS >= 3) n12 = L.q12[nq];
+            }
+            const uint32_t w4[4] = { c4.x, c4.y, c4.z, c4.w }, w8[4] = { c8.x, c8.y, c8.z, c8.w }, w12[4] = { c12.x, c12.y, c12.z, c12.w };
+            auto point = [&](uint32_t X, uint32_t Y, uint32_t Z, int j) __attribute__((always_inline)) {
+                const float x = __fmaf_rn((float)X, L.sx, L.ox), y = __fmaf_rn((float)Y, L.sy, L.oy), z = __fmaf_rn((float)Z, L.sz, L.oz);
+                point_fn(project_point(L.m, L.fw, L.fh, x, y, z), per_quad, j);
+            };
+            if (ARRAYS == 1) {                                                   // :381-392 (levels 2..4)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) point(w4[j] & 1023u, (w4[j] >> 10) & 1023u, (w4[j] >> 20) & 1023u, j);
+            } else {                                                             // :333-378 (level 1: the 12-byte array's bits are zero)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    point(((w4[j] & 1023u) << 20) | ((w8[j] & 1023u) << 10) | (w12[j] & 1023u),
+                          (((w4[j] >> 10) & 1023u) << 20) | (((w8[j] >> 10) & 1023u) << 10) | ((w12[j] >> 10) & 1023u),
+                          (((w4[j] >> 20) & 1023u) << 20) | (((w8[j] >> 20) & 1023u) << 10) | ((w12[j] >> 20) & 1023u), j);
+            }
+        }
+    };
+    if (L.level >= 2)      quads(std::integral_constant<int, 1>{});
+    else if (L.level == 1) quads(std::integral_constant<int, 2>{});
+    else                   quads(std::integral_constant<int, 3>{});
+}
+
 // Round 4: brought to k_render's standard. The window starts EMPTY (round 1 copied the framebuffer's words into it: a global read
 // of every window pixel in front of the barrier); a point's depth is tested against the depth half of its window word, read a
 // whole point before it is used, and only then is the 64-bit key put together for the ds_min_u64 (round 1: a 64-bit LDS read and
@@ -2239,46 +2148,8 @@ __device__ __forceinline__ bool las_list_batch(const LasArgs &a, uint32_t &b)
 template <bool DEPTH_ONLY>
 __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE, 8) k_las_render(LasArgs a)
 {
-    // which batch is the blockIdx.x-th of the list? (every wave for itself: a 64-lane inclusive prefix sum over the chunk counts)
     uint32_t b;
-    {
-        const uint32_t lane = threadIdx.x & 63u;
-        // Heaviest class first only while it is a minority (a few stragglers among batches with windows: started first, they run beside
-        // everything else). A frame made of such batches (a close-up: every batch larger on screen than its window) is bound by its
-        // global atomics, and drawn class by class it was 18 % slower than in the file's order -- then the chunks are walked in order.
-        uint32_t heavy_total = 0, all_total = 0;
-        for (uint32_t c0 = 0; c0 < a.chunks; c0 += 64) {                    // (uniform)
-            uint32_t h = c0 + lane < a.chunks ? a.chunk_count[c0 + lane] : 0u, l = c0 + lane < a.chunks ? a.chunk_count[a.chunks + c0 + lane] : 0u;
-            h = wave_read_lane(wave_inclusive_sum(h), 63); l = wave_read_lane(wave_inclusive_sum(l), 63);
-            heavy_total += h; all_total += h + l;
-        }
-        const bool by_class = heavy_total * 4u < all_total;
-        static_assert(LAS_CLASSES == 2, "heavy / light");
-        uint32_t x = blockIdx.x, found = 0xFFFFFFFFu;
-        for (uint32_t cls = 0; cls < (by_class ? 2u : 1u) && found == 0xFFFFFFFFu; ++cls) {       // (uniform)
-            uint32_t before = 0;
-            for (uint32_t c0 = 0; c0 < a.chunks; c0 += 64) {                // (uniform)
-                const uint32_t c = c0 + lane;
-                // by class: the chunk's records of this class; in the file's order: all of the chunk's records (heavy ones first inside it)
-                const uint32_t cnt = c < a.chunks ? (by_class ? a.chunk_count[cls * a.chunks + c] : a.chunk_count[c] + a.chunk_count[a.chunks + c]) : 0u;
-                const uint32_t incl = wave_inclusive_sum(cnt);
-                const uint32_t total = wave_read_lane(incl, 63);
-                if (x < before + total) {
-                    const uint64_t m = __ballot(before + incl > x);
-                    const uint32_t first = (uint32_t)__ffsll((unsigned long long)m) - 1u;
-                    const uint32_t excl = wave_read_lane(incl - cnt, first);
-                    const uint32_t lighter = by_class && cls == 1u ? a.chunk_count[c0 + first] : 0u;      // the chunk's heavy records lie in front
-                    found = (c0 + first) * LAS_PREPASS_BATCHES + lighter + (x - before - excl);
-                    break;
-                }
-                before += total;
-            }
-            x -= before;                                                    // (not found: `before` is the class's total)
-        }
-        found = __builtin_amdgcn_readfirstlane(found);
-        if (found == 0xFFFFFFFFu) return;                                   // the grid is sized for "every batch drawn"
-        b = a.order[found];
-    }
+    if (!las_list_batch(a, b)) return;
     const int level = a.level[b];
     const uint32_t tid = threadIdx.x;
     __shared__ __align__(16) unsigned long long s_win[WIN_PIXELS + 1];
@@ -2290,24 +2161,9 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE, 8) k_las_render(LasArgs a)
     const float inv_ww = 1.0f / (float)max(ww, 1u);
     for (uint32_t i = tid; i < wpix; i += PCR_WORKGROUP_SIZE) s_win[i] = ~0ull;
     if (tid == 0) s_win[wpix] = 0ull;                                        // the dummy slot: depth 0, no point passes it
-    const pcr_xyz_batch g = a.s.batches[b];
-    const float div = level >= 2 ? 1024.0f : 1073741824.0f;                  // STEPS_10BIT / STEPS_30BIT
-    const float sx = (g.max_x - g.min_x) / div, sy = (g.max_y - g.min_y) / div, sz = (g.max_z - g.min_z) / div;   // :145, :345
-    // (the w row of the matrix in vector registers, as in k_render: a v_fma_f32 whose operands are all VGPRs issues in ~2.3 cycles,
-    // with an SGPR operand in ~4.2; the x and y rows run as packed operations with scalar pairs)
-    auto in_vgpr = [](float v) { float r; asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "s"(v)); return r; };
-    const float *M = a.p.transform;
-    const float m00 = M[0], m01 = M[1], m02 = M[2], m03 = M[3];
-    const float m10 = M[4], m11 = M[5], m12 = M[6], m13 = M[7];
-    const float m30 = in_vgpr(M[12]), m31 = in_vgpr(M[13]), m32 = in_vgpr(M[14]), m33 = in_vgpr(M[15]);
-    const float vsx = sx, vsy = sy, vsz = sz, vox = g.min_x, voy = g.min_y, voz = g.min_z;
-    const float fw = (float)a.p.width, fh = (float)a.p.height;
+    const LasBatch L = las_batch(a, b, level);
     const int img_w = a.p.width;
     uint64_t *const g_fb = a.f.fb;
-    const size_t base = (size_t)b * PCR_POINTS_PER_BATCH;
-    const uint4 *q4 = reinterpret_cast<const uint4 *>(a.s.xyz4 + base);
-    const uint4 *q8 = reinterpret_cast<const uint4 *>(a.s.xyz8 + base);
-    const uint4 *q12 = reinterpret_cast<const uint4 *>(a.s.xyz12 + base);
     typedef __attribute__((address_space(3))) unsigned long long lds_u64;
     lds_u64 *const s_w = (lds_u64 *)s_win;
     // the pending point: projected, its window word's depth half requested; scattered while the next point is projected
@@ -2326,38 +2182,17 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE, 8) k_las_render(LasArgs a)
             else __hip_atomic_fetch_min(pend_p, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     };
-    auto point = [&](uint32_t X, uint32_t Y, uint32_t Z, uint32_t index) __attribute__((always_inline)) {
-        const float x = __fmaf_rn((float)X, vsx, vox), y = __fmaf_rn((float)Y, vsy, voy), z = __fmaf_rn((float)Z, vsz, voz);
-        // rasterize, first half (:108-118); projection as in k_render (exact inside test without dividing, shared-reciprocal division)
-        const float qx = __fmaf_rn(m03, 1.0f, __fmaf_rn(m02, z, __fmaf_rn(m01, y, m00 * x)));
-        const float qy = __fmaf_rn(m13, 1.0f, __fmaf_rn(m12, z, __fmaf_rn(m11, y, m10 * x)));
-        const float qw = __fmaf_rn(m33, 1.0f, __fmaf_rn(m32, z, __fmaf_rn(m31, y, m30 * x)));
-        uint64_t cand_mask = __builtin_amdgcn_ballot_w64(fabsf(qx) <= qw) & __builtin_amdgcn_ballot_w64(fabsf(qy) <= qw);
-        int ix, iy;
-        {
-            const float r0 = __builtin_amdgcn_rcpf(qw);
-            const float r1 = __fmaf_rn(__fmaf_rn(-qw, r0, 1.0f), r0, r0);
-            const v2f xy = {qx, qy}, rr = {r1, r1}, nw = {-qw, -qw};
-            const v2f q0 = xy * rr;
-            const v2f q1 = __builtin_elementwise_fma(__builtin_elementwise_fma(nw, q0, xy), rr, q0);
-            const v2f q2 = __builtin_elementwise_fma(__builtin_elementwise_fma(nw, q1, xy), rr, q1);
-            const v2f half = {0.5f, 0.5f}, size = {fw, fh};
-            const v2f img = __builtin_elementwise_fma(q2, half, half) * size;
-            ix = (int)img.x; iy = (int)img.y;
-        }
-        const uint64_t w_ok_mask = __builtin_amdgcn_ballot_w64((__float_as_uint(qw) - 0x1F800000u) < 0x40000000u);   // 2^-64 <= w < 2^64
-        if (__builtin_expect((cand_mask & ~w_ok_mask) != 0, 0)) {           // (uniform, practically never) the plain `/` for all lanes
-            const float nx = qx / qw, ny = qy / qw;
-            ix = (int)(__fmaf_rn(nx, 0.5f, 0.5f) * fw);
-            iy = (int)(__fmaf_rn(ny, 0.5f, 0.5f) * fh);
-            cand_mask &= __builtin_amdgcn_ballot_w64(qw > 0.0f);            // (w == 0 with x == y == 0 passes |x| <= w: rasterize rejects w <= 0, :113)
-        }
+    // per quad: the index of its first point; per point: the pending one is scattered, this one becomes the pending one
+    auto quad_index = [&](uint32_t quad) __attribute__((always_inline)) { return (uint32_t)L.base + quad * 4; };
+    auto point = [&](const Projection &pr, uint32_t index0, int j) __attribute__((always_inline)) {
+        const uint64_t cand_mask = pr.cand;
+        const int ix = pr.ix, iy = pr.iy;
         scatter_pending();                                                   // the point before this one: its window word has arrived by now
         const uint32_t rx = (uint32_t)ix - wx0, ry = (uint32_t)iy - wy0;
         const uint64_t in_mask = cand_mask & __builtin_amdgcn_ballot_w64(rx < ww) & __builtin_amdgcn_ballot_w64(ry < wh);
         pend_off_mask = cand_mask & ~in_mask;
-        pend_depth = __float_as_uint(qw);
-        pend_index = index;
+        pend_depth = __float_as_uint(pr.w);
+        pend_index = index0 + j;
         pend_p = s_w + (__builtin_amdgcn_inverse_ballot_w64(in_mask) ? (uint32_t)__umul24(ry, ww) + rx : wpix);
         pend_old_hi = reinterpret_cast<__attribute__((address_space(3))) const uint32_t *>(pend_p)[1];
         if (__builtin_expect(pend_off_mask != 0, 0)) {                      // (uniform) some lane's point lies outside the window: the global word's depth (:123)
@@ -2372,40 +2207,7 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE, 8) k_las_render(LasArgs a)
         }
     };
 
-    // One copy of the loop per number of level arrays read (4 / 8 / 12 bytes per point): the copy that reads one array does not
-    // carry the registers of the other two (with one loop for all three, the 64-register budget of eight waves per SIMD spilled).
-    auto quads = [&](auto arrays_) __attribute__((always_inline)) {
-        constexpr int ARRAYS = decltype(arrays_)::value;
-        uint4 n4 = q4[tid], n8 = make_uint4(0, 0, 0, 0), n12 = make_uint4(0, 0, 0, 0);
-        if (ARRAYS >= 2) n8 = q8[tid];
-        if (ARRAYS >= 3) n12 = q12[tid];
-#pragma unroll 1
-        for (int i = 0; i < PCR_POINTS_PER_BATCH / 4 / PCR_WORKGROUP_SIZE; ++i) {
-            const uint4 c4 = n4, c8 = n8, c12 = n12;
-            const uint32_t quad = tid + (uint32_t)i * PCR_WORKGROUP_SIZE;
-            {   // next quad in flight while this one is projected (the last iteration re-reads its own: no branch around the loads)
-                const uint32_t nq = min(quad + PCR_WORKGROUP_SIZE, (uint32_t)(PCR_POINTS_PER_BATCH / 4 - 1));
-                n4 = q4[nq];
-                if (ARRAYS >= 2) n8 = q8[nq];
-                if (ARRAYS >= 3) n12 = q12[nq];
-            }
-            const uint32_t w4[4] = { c4.x, c4.y, c4.z, c4.w }, w8[4] = { c8.x, c8.y, c8.z, c8.w }, w12[4] = { c12.x, c12.y, c12.z, c12.w };
-            const uint32_t index0 = (uint32_t)base + quad * 4;
-            if (ARRAYS == 1) {                                                   // :381-392 (levels 2..4)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) point(w4[j] & 1023u, (w4[j] >> 10) & 1023u, (w4[j] >> 20) & 1023u, index0 + j);
-            } else {                                                             // :333-378 (level 1: the 12-byte array's bits are zero)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    point(((w4[j] & 1023u) << 20) | ((w8[j] & 1023u) << 10) | (w12[j] & 1023u),
-                          (((w4[j] >> 10) & 1023u) << 20) | (((w8[j] >> 10) & 1023u) << 10) | ((w12[j] >> 10) & 1023u),
-                          (((w4[j] >> 20) & 1023u) << 20) | (((w8[j] >> 20) & 1023u) << 10) | ((w12[j] >> 20) & 1023u), index0 + j);
-            }
-        }
-    };
-    if (level >= 2)      quads(std::integral_constant<int, 1>{});
-    else if (level == 1) quads(std::integral_constant<int, 2>{});
-    else                 quads(std::integral_constant<int, 3>{});
+    las_points(L, quad_index, point);
     scatter_pending();
     if (wpix) {
         __syncthreads();
@@ -2425,8 +2227,8 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE, 8) k_las_render(LasArgs a)
 // Huffman HQS packing, so that k_resolve<true> and the merges take both methods' sums (color.cs:399-400 packs R | G<<32; the
 // resolved image is the same).
 //
-// Same list walk, levels, 16-byte quad-ahead loads and projection as k_las_render (so both passes see identical positions), plus
-// the points' colours, 16 bytes per quad. The LDS window holds {RG u64, BA u64, depth u32} per pixel: 4096 slots of 20 B
+// It shares k_las_render's list walk, levels, 16-byte quad-ahead loads and projection (las_list_batch, las_batch, las_points),
+// and reads the points' colours as well, 16 bytes per quad. The LDS window holds {RG u64, BA u64, depth u32} per pixel: 4096 slots of 20 B
 // = 80 KiB, two workgroups per CU in the 160 KiB; the last slot is the dummy (depth all ones, a NaN: no point passes it). Its
 // depth half is preloaded from fb at workgroup start, row by row; the sums go through ds_add_u64 and leave with one global
 // 64-bit atomicAdd per word of every pixel that counted a point. A point outside the window, or in a batch without one, reads
@@ -2457,23 +2259,10 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE, 8) k_las_render_color(LasA
         s_depth[i] = reinterpret_cast<const uint32_t *>(&g_fb[(size_t)(wy0 + y) * W + wx0 + x])[1];
     }
     if (tid == 0) { s_rg[wpix] = 0ull; s_ba[wpix] = 0ull; s_depth[wpix] = 0xFFFFFFFFu; }    // the dummy slot
-    const pcr_xyz_batch g = a.s.batches[b];
-    const float div = level >= 2 ? 1024.0f : 1073741824.0f;                  // STEPS_10BIT / STEPS_30BIT
-    const float sx = (g.max_x - g.min_x) / div, sy = (g.max_y - g.min_y) / div, sz = (g.max_z - g.min_z) / div;
-    auto in_vgpr = [](float v) { float r; asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "s"(v)); return r; };
-    const float *M = a.p.transform;
-    const float m00 = M[0], m01 = M[1], m02 = M[2], m03 = M[3];
-    const float m10 = M[4], m11 = M[5], m12 = M[6], m13 = M[7];
-    const float m30 = in_vgpr(M[12]), m31 = in_vgpr(M[13]), m32 = in_vgpr(M[14]), m33 = in_vgpr(M[15]);
-    const float vsx = sx, vsy = sy, vsz = sz, vox = g.min_x, voy = g.min_y, voz = g.min_z;
-    const float fw = (float)a.p.width, fh = (float)a.p.height;
+    const LasBatch L = las_batch(a, b, level);
     const int img_w = a.p.width;
     unsigned long long *const g_rg = reinterpret_cast<unsigned long long *>(a.f.rg), *const g_ba = reinterpret_cast<unsigned long long *>(a.f.ba);
-    const size_t base = (size_t)b * PCR_POINTS_PER_BATCH;
-    const uint4 *q4 = reinterpret_cast<const uint4 *>(a.s.xyz4 + base);
-    const uint4 *q8 = reinterpret_cast<const uint4 *>(a.s.xyz8 + base);
-    const uint4 *q12 = reinterpret_cast<const uint4 *>(a.s.xyz12 + base);
-    const uint4 *qc = reinterpret_cast<const uint4 *>(a.rgba_points + base);
+    const uint4 *qc = reinterpret_cast<const uint4 *>(a.rgba_points + L.base);
     typedef __attribute__((address_space(3))) unsigned long long lds_u64;
     // the pending point: projected, its depth requested; accumulated while the next point is projected. pend_at: its window slot
     // (the dummy slot wpix if it has none), or its pixel if it takes the global path (pend_off_mask)
@@ -2496,38 +2285,23 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE, 8) k_las_render_color(LasA
             }
         }
     };
-    // projection and inside tests: k_las_render's point() (same arithmetic, same results)
-    auto point = [&](uint32_t X, uint32_t Y, uint32_t Z, uint32_t color) __attribute__((always_inline)) {
-        const float x = __fmaf_rn((float)X, vsx, vox), y = __fmaf_rn((float)Y, vsy, voy), z = __fmaf_rn((float)Z, vsz, voz);
-        const float qx = __fmaf_rn(m03, 1.0f, __fmaf_rn(m02, z, __fmaf_rn(m01, y, m00 * x)));
-        const float qy = __fmaf_rn(m13, 1.0f, __fmaf_rn(m12, z, __fmaf_rn(m11, y, m10 * x)));
-        const float qw = __fmaf_rn(m33, 1.0f, __fmaf_rn(m32, z, __fmaf_rn(m31, y, m30 * x)));
-        uint64_t cand_mask = __builtin_amdgcn_ballot_w64(fabsf(qx) <= qw) & __builtin_amdgcn_ballot_w64(fabsf(qy) <= qw);
-        int ix, iy;
-        {
-            const float r0 = __builtin_amdgcn_rcpf(qw);
-            const float r1 = __fmaf_rn(__fmaf_rn(-qw, r0, 1.0f), r0, r0);
-            const v2f xy = {qx, qy}, rr = {r1, r1}, nw = {-qw, -qw};
-            const v2f q0 = xy * rr;
-            const v2f q1 = __builtin_elementwise_fma(__builtin_elementwise_fma(nw, q0, xy), rr, q0);
-            const v2f q2 = __builtin_elementwise_fma(__builtin_elementwise_fma(nw, q1, xy), rr, q1);
-            const v2f half = {0.5f, 0.5f}, size = {fw, fh};
-            const v2f img = __builtin_elementwise_fma(q2, half, half) * size;
-            ix = (int)img.x; iy = (int)img.y;
-        }
-        const uint64_t w_ok_mask = __builtin_amdgcn_ballot_w64((__float_as_uint(qw) - 0x1F800000u) < 0x40000000u);   // 2^-64 <= w < 2^64
-        if (__builtin_expect((cand_mask & ~w_ok_mask) != 0, 0)) {
-            const float nx = qx / qw, ny = qy / qw;
-            ix = (int)(__fmaf_rn(nx, 0.5f, 0.5f) * fw);
-            iy = (int)(__fmaf_rn(ny, 0.5f, 0.5f) * fh);
-            cand_mask &= __builtin_amdgcn_ballot_w64(qw > 0.0f);
-        }
+    // the quad's colours: requested in front of the next quad's words, so that waiting for them does not wait for those (not a
+    // quad ahead: four more registers would not fit the 64 of two workgroups per CU -- the three-array copy spilled)
+    auto quad_colors = [&](uint32_t quad) __attribute__((always_inline)) {
+        uint32_t cq = quad;
+        asm volatile("; colour quad %0" : "+v"(cq));                        // (no 64-bit pointer induction variable: it spilled)
+        return qc[cq];
+    };
+    auto point = [&](const Projection &pr, const uint4 &cc, int j) __attribute__((always_inline)) {
+        const uint32_t wc[4] = { cc.x, cc.y, cc.z, cc.w };
+        const uint64_t cand_mask = pr.cand;
+        const int ix = pr.ix, iy = pr.iy;
         add_pending();                                                       // the point before this one: its depth has arrived by now
         const uint32_t rx = (uint32_t)ix - wx0, ry = (uint32_t)iy - wy0;
         const uint64_t in_mask = cand_mask & __builtin_amdgcn_ballot_w64(rx < ww) & __builtin_amdgcn_ballot_w64(ry < wh);
         pend_off_mask = cand_mask & ~in_mask;
-        pend_w = __float_as_uint(qw);
-        pend_color = color;
+        pend_w = __float_as_uint(pr.w);
+        pend_color = wc[j];
         pend_at = __builtin_amdgcn_inverse_ballot_w64(in_mask) ? (uint32_t)__umul24(ry, ww) + rx : wpix;
         pend_depth = s_depth[pend_at];
         if (__builtin_expect(pend_off_mask != 0, 0)) {                      // (uniform) some lane's point lies outside the window: the global word's depth
@@ -2540,44 +2314,7 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE, 8) k_las_render_color(LasA
         }
     };
 
-    auto quads = [&](auto arrays_) __attribute__((always_inline)) {
-        constexpr int ARRAYS = decltype(arrays_)::value;
-        uint4 n4 = q4[tid], n8 = make_uint4(0, 0, 0, 0), n12 = make_uint4(0, 0, 0, 0);
-        if (ARRAYS >= 2) n8 = q8[tid];
-        if (ARRAYS >= 3) n12 = q12[tid];
-#pragma unroll 1
-        for (int i = 0; i < PCR_POINTS_PER_BATCH / 4 / PCR_WORKGROUP_SIZE; ++i) {
-            const uint4 c4 = n4, c8 = n8, c12 = n12;
-            const uint32_t quad = tid + (uint32_t)i * PCR_WORKGROUP_SIZE;
-            // the quad's colours: requested here, not a quad ahead (four more registers would not fit the 64 of two workgroups
-            // per CU: the three-array copy spilled), and in front of the next quad's words, so that waiting for them does not
-            // wait for those
-            uint32_t cq = quad;
-            asm volatile("; colour quad %0" : "+v"(cq));                    // (no 64-bit pointer induction variable: it spilled)
-            const uint4 cc = qc[cq];
-            {
-                const uint32_t nq = min(quad + PCR_WORKGROUP_SIZE, (uint32_t)(PCR_POINTS_PER_BATCH / 4 - 1));
-                n4 = q4[nq];
-                if (ARRAYS >= 2) n8 = q8[nq];
-                if (ARRAYS >= 3) n12 = q12[nq];
-            }
-            const uint32_t w4[4] = { c4.x, c4.y, c4.z, c4.w }, w8[4] = { c8.x, c8.y, c8.z, c8.w }, w12[4] = { c12.x, c12.y, c12.z, c12.w };
-            const uint32_t wc[4] = { cc.x, cc.y, cc.z, cc.w };
-            if (ARRAYS == 1) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) point(w4[j] & 1023u, (w4[j] >> 10) & 1023u, (w4[j] >> 20) & 1023u, wc[j]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    point(((w4[j] & 1023u) << 20) | ((w8[j] & 1023u) << 10) | (w12[j] & 1023u),
-                          (((w4[j] >> 10) & 1023u) << 20) | (((w8[j] >> 10) & 1023u) << 10) | ((w12[j] >> 10) & 1023u),
-                          (((w4[j] >> 20) & 1023u) << 20) | (((w8[j] >> 20) & 1023u) << 10) | ((w12[j] >> 20) & 1023u), wc[j]);
-            }
-        }
-    };
-    if (level >= 2)      quads(std::integral_constant<int, 1>{});
-    else if (level == 1) quads(std::integral_constant<int, 2>{});
-    else                 quads(std::integral_constant<int, 3>{});
+    las_points(L, quad_colors, point);
     add_pending();
     if (wpix) {
         __syncthreads();
