@@ -69,6 +69,15 @@ int pcr_encode_points(const int32_t *x, const int32_t *y, const int32_t *z, cons
                       int64_t n, const pcr_las_info *las, int flags, int64_t chunk_points,
                       int nthreads, void **out_bytes, size_t *out_len, pcr_encode_stats *stats);
 
+/* Write n points (int32 LAS coordinates + 0x00BBGGRR colours) as a LAS 1.2 file of point format 2 (26-byte records) with the
+ * scale, offset, min and max of `las` in its header: what the reference's LasLoader (src/preprocess.cpp:74-171) and
+ * pcr_preprocess read back unchanged. Colour components are written as v << 8 (the readers divide what exceeds 255 by 256).
+ * The reference has no LAS writer. n <= 0 and n > 2^32 - 1 (the format's 32-bit point count) are refused.
+ * pcr_write_las_points: the same from the 16-byte records pcr_read_points fills. */
+int pcr_write_las(const char *path, const int32_t *x, const int32_t *y, const int32_t *z, const uint32_t *color, int64_t n,
+                  const pcr_las_info *las);
+int pcr_write_las_points(const char *path, const pcr_point *points, int64_t n, const pcr_las_info *las);
+
 /* Deterministic synthetic scene: a heightfield surface over a square tile with LAS scale
  * 0.001 and int32 coordinates in [0, 1e6], smooth colour field. The scene of `total_points` points is
  * a jittered grid; this call materialises points [first, first+count) of it (row-major grid order, so

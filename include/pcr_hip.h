@@ -147,6 +147,22 @@ int pcr_read_rgba(pcr_ctx *ctx, uint32_t *host, size_t n_pixels);               
 /* ---- multi-GPU plumbing (no reference counterpart) ------------------------------------
  * Device pointers of the context's buffers so a collective library (RCCL through torch.distributed)
  * can reduce them in place, or externally owned buffers to render into. */
+/* The loaded stream back to points. The reference has no counterpart: its only decoder outside the render kernels is the
+ * per-chain CPU one of include/huffman.h:433-477. Decodes batches [first_batch, first_batch + count) of the loaded stream into
+ * dev_points (device memory of the context's device, capacity_points records, 16-byte aligned): all 64 points of all 1024
+ * chains of every batch, no cull, no level of detail, the tail artefact of the reference's interleave
+ * included -- exactly the points the render kernels draw. Point i of chain c of batch b is record
+ * (b - first_batch) * 65536 + c * 64 + i, the stream's own order; the colour is 0x00BBGGRR (BC1 or BC7 by the stream's format)
+ * as pcr_encode_points takes it. count < 0: up to the last batch the next frame would draw (pcr_batches_resident); with
+ * pcr_set_async_upload on, only those batches may be decoded. count == 0 succeeds and does nothing. Works before and after the
+ * first frame (it reads what the render kernels read, from either layout; with PCR_LAYOUT_BOTH the one pcr_set_render_variant
+ * names, AUTO: the point windows). Enqueues on the context's stream; touches no framebuffer, no prepass state, no statistics.
+ * PCR_E_ARG: no stream loaded, a range outside the resident batches, capacity_points < count * 65536, a NULL or misaligned
+ * pointer. */
+int pcr_decode_points(pcr_ctx *ctx, int64_t first_batch, int64_t count, void *dev_points, size_t capacity_points);
+/* The same into host memory: staged through a device buffer of the context, 64 batches (64 MiB) at a time; synchronises. */
+int pcr_read_points(pcr_ctx *ctx, int64_t first_batch, int64_t count, pcr_point *host, size_t capacity_points);
+
 /* What a collective library needs to merge partial frames in place (include/pcr_dist.h does it with RCCL): the HIP stream
  * the context enqueues on, its device ordinal and the length of each framebuffer in 64-bit words. */
 void *pcr_get_stream(pcr_ctx *ctx);

@@ -111,6 +111,13 @@ typedef struct pcr_render_stats {
     int64_t batches_double;    /* batches that took the double-precision dequantisation path */
 } pcr_render_stats;
 
+/* One decoded point (pcr_decode_points / pcr_read_points, pcr_write_las_points): the int32 LAS coordinates of the stream and
+ * the colour as 0x00BBGGRR, 16 bytes. */
+typedef struct pcr_point {
+    int32_t  x, y, z;
+    uint32_t color;
+} pcr_point;
+
 /* Number of u64 elements a framebuffer of w x h must hold: ndc == 1.0 maps to column w / row h
  * (SURVEY Appendix C.2), so pixel ids reach w*(h+1). */
 static inline size_t pcr_fb_elems(int w, int h) { return (size_t)w * (size_t)(h + 1) + 1; }

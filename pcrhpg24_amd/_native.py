@@ -53,6 +53,10 @@ class LasInfo(C.Structure):                       # pcr_las_info
     _fields_ = [("scale", c_f64 * 3), ("offset", c_f64 * 3), ("min", c_f64 * 3), ("max", c_f64 * 3)]
 
 
+class Point(C.Structure):                         # pcr_point: one decoded point, 16 bytes (colour 0x00BBGGRR)
+    _fields_ = [("x", c_i32), ("y", c_i32), ("z", c_i32), ("color", c_u32)]
+
+
 class EncodeStats(C.Structure):                   # pcr_encode_stats
     _fields_ = [(n, c_i64) for n in ("num_points_in", "num_points", "num_batches", "encoded_bytes", "separate_bytes",
                                      "cluster_bytes", "escaped_symbols", "total_symbols", "file_bytes")]
@@ -61,6 +65,7 @@ class EncodeStats(C.Structure):                   # pcr_encode_stats
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+assert C.sizeof(Point) == 16
 assert C.sizeof(XyzBatch) == 64 and C.sizeof(GpuBatch) == 160 and C.sizeof(FileHeader) == 40 and C.sizeof(RenderParams) == 224
 
 
@@ -80,12 +85,14 @@ HIP_SYMBOLS = [
     "pcr_las_begin", "pcr_las_upload", "pcr_las_unload", "pcr_las_batches_loaded", "pcr_render_las", "pcr_resolve_las",
     "pcr_render_las_hqs_depth", "pcr_render_las_hqs_color",
     "pcr_las_algorithmic_bytes", "pcr_gpu_encode_points", "pcr_gpu_encode_free",
+    "pcr_decode_points", "pcr_read_points",
 ]
 
 HOST_SYMBOLS = [
     "pcr_host_last_error", "pcr_host_free", "pcr_encode_points", "pcr_synth_points", "pcr_synth_las_info",
     "pcr_synth_encode", "pcr_morton_key", "pcr_huffman_build", "pcr_pack_chain", "pcr_table_from_dict",
     "pcr_bc1_encode_block", "pcr_bc7_encode_block", "pcr_las_quantize", "pcr_camera_orbit",
+    "pcr_write_las", "pcr_write_las_points",
 ]
 
 _hip = None
@@ -185,6 +192,8 @@ def hip_lib() -> C.CDLL:
         lib.pcr_last_frame_batches.restype = C.c_int64
         lib.pcr_kernel_timing_enable.argtypes = [C.c_void_p, C.c_int]
         lib.pcr_kernel_timing_read.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+        lib.pcr_decode_points.argtypes = [C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_size_t]
+        lib.pcr_read_points.argtypes = [C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_size_t]
         _hip = lib
     return _hip
 
@@ -221,6 +230,8 @@ def host_lib() -> C.CDLL:
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         lib.pcr_camera_orbit.argtypes = [c_f64, c_f64, c_f64, C.POINTER(c_f64), C.c_int, C.c_int, c_f64, c_f64, c_f64,
                                          C.POINTER(RenderParams)]
+        lib.pcr_write_las.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i64, C.POINTER(LasInfo)]
+        lib.pcr_write_las_points.argtypes = [C.c_char_p, C.c_void_p, c_i64, C.POINTER(LasInfo)]
         _host = lib
     return _host
 

@@ -85,17 +85,23 @@ def build_dist(force: bool = False) -> str:
 
 RENDER_BIN = os.path.join(PKG_DIR, "pcr_render")
 PREPROCESS_BIN = os.path.join(PKG_DIR, "pcr_preprocess")
+DECODE_BIN = os.path.join(PKG_DIR, "pcr_decode")
 
 
 def build_tools(force: bool = False) -> None:
-    """C++ host adapters (csrc/pcr_methods.hpp) as headless executables: pcr_render (the reference's main.cpp flow)
-    and pcr_preprocess (the reference's preprocess CLI)."""
+    """C++ host adapters (csrc/pcr_methods.hpp) as headless executables: pcr_render (the reference's main.cpp flow),
+    pcr_preprocess (the reference's preprocess CLI) and pcr_decode (.huffman -> .las, decoded on the GPU)."""
     build_host(force)
     build_hip(force)
     rsrc = [os.path.join(CSRC, "pcr_render.cpp"), os.path.join(CSRC, "pcr_methods.hpp"), os.path.join(CSRC, "pcr_las_reader.hpp"),
             HIP_LIB, HOST_LIB]
     if force or _stale(RENDER_BIN, rsrc):
         _run([_hipcc(), "-O2", "-std=c++17", "-I", INCLUDE, "-I", CSRC, rsrc[0], "-o", RENDER_BIN,
+              "-L", PKG_DIR, "-lpcr_hip", "-lpcr_host", "-lpthread", "-Wl,-rpath,$ORIGIN"])
+    dsrc = [os.path.join(CSRC, "pcr_decode.cpp"), os.path.join(CSRC, "pcr_methods.hpp"), os.path.join(CSRC, "pcr_las_reader.hpp"),
+            HIP_LIB, HOST_LIB]
+    if force or _stale(DECODE_BIN, dsrc):
+        _run([_hipcc(), "-O2", "-std=c++17", "-I", INCLUDE, "-I", CSRC, dsrc[0], "-o", DECODE_BIN,
               "-L", PKG_DIR, "-lpcr_hip", "-lpcr_host", "-lpthread", "-Wl,-rpath,$ORIGIN"])
     psrc = [os.path.join(CSRC, "pcr_preprocess.cpp"), os.path.join(CSRC, "pcr_las_reader.hpp"), HOST_LIB, HIP_LIB]
     if force or _stale(PREPROCESS_BIN, psrc):

@@ -21,6 +21,7 @@ constexpr int PCR_STATS_PARTIALS = PCR_MAX_PREPASS_WORKGROUPS;   // one partial 
 #ifndef PCR_DEFAULT_PARTS
 #define PCR_DEFAULT_PARTS 2                     /* workgroups per batch of k_render unless pcr_set_workgroup_parts says otherwise */
 #endif
+constexpr int64_t DECODE_STAGE_BATCHES = 64;     // batches per piece of pcr_read_points: 64 MiB of records on the device
 constexpr int64_t TRANSCODE_CHUNK = 128;        // batches per k_transcode launch when the lane-major words are scratch (40 MB)
 
 struct pcr_ctx {
@@ -116,6 +117,9 @@ struct pcr_ctx {
     int prepass_parts = 0;
     int parts_mode = 0;                         // pcr_set_workgroup_parts: 0 = chosen per frame, 1 = whole batches, 2 = half-batches
     bool big_lds_ready = false;                 // hipFuncSetAttribute done for the 140 KiB launches
+    bool decode_lds_ready = false;              // ... and for k_decode_points' 128 KiB of staging
+    pcr_point *d_decode_stage = nullptr;        // pcr_read_points: device staging of at most DECODE_STAGE_BATCHES batches of points
+    int64_t decode_stage_batches = 0;
     int64_t prepass_batches = 0;
     static constexpr int FENCES = 8;
     hipEvent_t fence[FENCES] = {};              // pcr_fence_record / pcr_fence_wait: device-scope ordering between streams
@@ -564,6 +568,7 @@ void pcr_destroy(pcr_ctx *c)
     free_las_buffers(c);
     free_frame_buffers(c);
     dfree(c->d_stats);
+    dfree(c->d_decode_stage);
     for (int i = 0; i < 2; ++i) {
         if (c->arena[i]) (void)hipHostFree(c->arena[i]);
         if (c->arena_done[i]) (void)hipEventDestroy(c->arena_done[i]);
@@ -1373,6 +1378,91 @@ int pcr_read_rgba(pcr_ctx *c, uint32_t *host, size_t n)
     if (!c->d_rgba || n > (size_t)c->width * c->height) return set_err(c, PCR_E_ARG, "bad rgba read");
     HIP_TRY(c, hipMemcpyAsync(host, c->d_rgba, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+// ---- decode ------------------------------------------------------------------------------------
+// Range check shared by pcr_decode_points / pcr_read_points: [first, first + count) inside the batches the next frame would
+// draw; count < 0 = up to the last of them. Returns the count through *n.
+static int decode_range(pcr_ctx *c, int64_t first, int64_t count, const void *dst, size_t capacity, int64_t *n)
+{
+    if (!c->stream_open) return set_err(c, PCR_E_ARG, "no stream loaded (call pcr_stream_begin / pcr_upload_batch)");
+    if (c->async_upload) poll_loader(c, false);
+    const int64_t nB = c->visible_batches();
+    if (first < 0 || first > nB) return set_err(c, PCR_E_ARG, "first batch %lld outside the %lld resident batches", (long long)first, (long long)nB);
+    if (count < 0) count = nB - first;
+    if (count > nB - first)
+        return set_err(c, PCR_E_ARG, "batches [%lld, %lld) reach past the %lld resident batches", (long long)first, (long long)(first + count), (long long)nB);
+    *n = count;
+    if (count == 0) return PCR_OK;
+    if (!dst) return set_err(c, PCR_E_ARG, "the destination is NULL");
+    if (reinterpret_cast<uintptr_t>(dst) % alignof(pcr_point) != 0) return set_err(c, PCR_E_ARG, "the destination is misaligned");
+    if (capacity < (size_t)count * PCR_POINTS_PER_BATCH)
+        return set_err(c, PCR_E_ARG, "capacity of %zu points is below the %lld x %d of the range", capacity, (long long)count, PCR_POINTS_PER_BATCH);
+    return PCR_OK;
+}
+
+static int launch_decode(pcr_ctx *c, int64_t first, int64_t count, void *dev_points)
+{
+    int rc;
+    // (as a frame: the provisional last batch of a stream that is still loading is walked here if no frame has done so)
+    if (!c->async_upload && (rc = enqueue_transcode(c, true, c->stream))) return rc;
+    if (!c->decode_lds_ready) {
+        hipError_t e = hipSuccess;
+#define PCR_ALLOW(L, B) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode_points<L, B>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEC_LDS_BYTES)
+        PCR_ALLOW(LAYOUT_WORDS, false); PCR_ALLOW(LAYOUT_WORDS, true); PCR_ALLOW(LAYOUT_POINT_WINDOWS, false); PCR_ALLOW(LAYOUT_POINT_WINDOWS, true);
+#undef PCR_ALLOW
+        if (e != hipSuccess) return set_err(c, PCR_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
+        c->decode_lds_ready = true;
+    }
+    // either layout decodes to the same points; a stream that holds both follows pcr_set_render_variant (AUTO: point windows)
+    const bool have_windows = c->layout != PCR_LAYOUT_WORDS, have_words = c->layout != PCR_LAYOUT_POINT_WINDOWS;
+    const bool windows = have_windows && (c->variant != PCR_VARIANT_WORDS || !have_words);
+    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)count), block(PCR_WORKGROUP_SIZE);
+    uint4 *out = static_cast<uint4 *>(dev_points);
+#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_decode_points<L, B>), grid, block, DEC_LDS_BYTES, c->stream, s, out, (uint32_t)first)
+    if (windows) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
+    else         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+#undef PCR_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    return PCR_OK;
+}
+
+int pcr_decode_points(pcr_ctx *c, int64_t first_batch, int64_t count, void *dev_points, size_t capacity_points)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int64_t n = 0;
+    int rc = decode_range(c, first_batch, count, dev_points, capacity_points, &n);
+    if (rc || n == 0) return rc;
+    if (reinterpret_cast<uintptr_t>(dev_points) % 16 != 0) return set_err(c, PCR_E_ARG, "dev_points must be 16-byte aligned");
+    return launch_decode(c, first_batch, n, dev_points);
+}
+
+int pcr_read_points(pcr_ctx *c, int64_t first_batch, int64_t count, pcr_point *host, size_t capacity_points)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int64_t n = 0;
+    int rc = decode_range(c, first_batch, count, host, capacity_points, &n);
+    if (rc || n == 0) return rc;
+    // staged through a device buffer of bounded size, piece by piece (never 16 bytes x the whole stream on the device)
+    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
+    if (!c->d_decode_stage || c->decode_stage_batches < piece) {
+        dfree(c->d_decode_stage); c->decode_stage_batches = 0;
+        if (hipMalloc((void **)&c->d_decode_stage, (size_t)piece * PCR_POINTS_PER_BATCH * sizeof(pcr_point)) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of points", (long long)piece);
+        c->decode_stage_batches = piece;
+    }
+    for (int64_t done = 0; done < n; done += piece) {
+        const int64_t m = std::min(piece, n - done);
+        if ((rc = launch_decode(c, first_batch + done, m, c->d_decode_stage))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(host + (size_t)done * PCR_POINTS_PER_BATCH, c->d_decode_stage, (size_t)m * PCR_POINTS_PER_BATCH * sizeof(pcr_point),
+                                  hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
     return PCR_OK;
 }
 

@@ -497,6 +497,53 @@ FM fm_mul(const FM &a, const FM &b)   // glm::mat4 operator*: ((A0*b0 + A1*b1) +
 }
 void fm_rows(const FM &a, float *rows) { for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) rows[r * 4 + c] = a.m[c][r]; }
 
+// LAS 1.2, point format 2 (26-byte records): the header fields pcr_las_reader.hpp reads, at the offsets its comment lists.
+// get(i, X, Y, Z, C) hands out point i.
+template <class Get> int write_las_file(const char *path, int64_t n, const pcr_las_info *las, Get get)
+{
+    if (!path || !las) return fail("null argument");
+    if (n <= 0) return fail("no points");
+    if (n > (int64_t)0xFFFFFFFFll) return fail("LAS 1.2 holds at most 2^32 - 1 points");
+    std::FILE *f = std::fopen(path, "wb");
+    if (!f) { g_err = std::string("cannot open ") + path + " for writing"; return -1; }
+    constexpr size_t HEADER = 227, RECORD = 26;
+    unsigned char hdr[HEADER] = {0};
+    auto put = [&](size_t off, const auto &v) { std::memcpy(hdr + off, &v, sizeof v); };
+    std::memcpy(hdr, "LASF", 4);
+    hdr[24] = 1; hdr[25] = 2;
+    std::snprintf(reinterpret_cast<char *>(hdr) + 26, 32, "OTHER");
+    std::snprintf(reinterpret_cast<char *>(hdr) + 58, 32, "pcrhpg24_amd pcr_write_las");
+    put(90, (uint16_t)1); put(92, (uint16_t)2024);
+    put(94, (uint16_t)HEADER); put(96, (uint32_t)HEADER); put(100, (uint32_t)0);
+    hdr[104] = 2; put(105, (uint16_t)RECORD);
+    put(107, (uint32_t)n); put(111, (uint32_t)n);                   // every point is return 1 of 1
+    for (int k = 0; k < 3; ++k) {
+        put(131 + 8 * (size_t)k, las->scale[k]); put(155 + 8 * (size_t)k, las->offset[k]);
+        put(179 + 16 * (size_t)k, las->max[k]); put(187 + 16 * (size_t)k, las->min[k]);
+    }
+    bool ok = std::fwrite(hdr, 1, HEADER, f) == HEADER;
+    std::vector<unsigned char> rec(RECORD * 65536);
+    for (int64_t done = 0; ok && done < n;) {
+        const int64_t m = std::min<int64_t>(65536, n - done);
+        std::memset(rec.data(), 0, (size_t)m * RECORD);
+        for (int64_t i = 0; i < m; ++i) {
+            unsigned char *r = rec.data() + (size_t)i * RECORD;
+            int32_t X, Y, Z; uint32_t C;
+            get(done + i, X, Y, Z, C);
+            std::memcpy(r + 0, &X, 4); std::memcpy(r + 4, &Y, 4); std::memcpy(r + 8, &Z, 4);
+            r[14] = 0x09;                                           // return 1 of 1
+            // 8-bit components as v << 8: a reader that divides what exceeds 255 by 256 (preprocess.cpp:150-152) gets v back
+            const uint16_t R = (uint16_t)((C & 255u) << 8), G = (uint16_t)(((C >> 8) & 255u) << 8), B = (uint16_t)(((C >> 16) & 255u) << 8);
+            std::memcpy(r + 20, &R, 2); std::memcpy(r + 22, &G, 2); std::memcpy(r + 24, &B, 2);
+        }
+        ok = std::fwrite(rec.data(), RECORD, (size_t)m, f) == (size_t)m;
+        done += m;
+    }
+    if (std::fclose(f) != 0) ok = false;
+    if (!ok) { g_err = std::string("write to ") + path + " failed"; return -1; }
+    return 0;
+}
+
 } // namespace
 
 // =================================================================================================
@@ -533,6 +580,20 @@ int pcr_encode_points(const int32_t *x, const int32_t *y, const int32_t *z, cons
     });
     if (rc) return rc;
     return assemble(chunks, n, out_bytes, out_len, stats);
+}
+
+int pcr_write_las(const char *path, const int32_t *x, const int32_t *y, const int32_t *z, const uint32_t *color, int64_t n,
+                  const pcr_las_info *las)
+{
+    if (!x || !y || !z || !color) return fail("null argument");
+    return write_las_file(path, n, las, [&](int64_t i, int32_t &X, int32_t &Y, int32_t &Z, uint32_t &C) { X = x[i]; Y = y[i]; Z = z[i]; C = color[i]; });
+}
+
+int pcr_write_las_points(const char *path, const pcr_point *points, int64_t n, const pcr_las_info *las)
+{
+    if (!points) return fail("null argument");
+    return write_las_file(path, n, las, [&](int64_t i, int32_t &X, int32_t &Y, int32_t &Z, uint32_t &C) {
+        X = points[i].x; Y = points[i].y; Z = points[i].z; C = points[i].color; });
 }
 
 int pcr_synth_las_info(int64_t total_points, uint64_t seed, pcr_las_info *las)

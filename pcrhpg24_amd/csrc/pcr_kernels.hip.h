@@ -14,6 +14,7 @@
 //                   one of 1024 (PARTS = 1): decodes the chain of <= 64 points from its own bits with the batch's decoder table in
 //                   LDS, then projects and scatters every point (render.cu:383-540, huffman_hqs/depth.cu, huffman_hqs/render.cu;
 //                   MODE 3: the colour pass over BC7 mode-6 colours)
+//   k_decode_points on request: the same decode, every point of a range of batches written out as {x, y, z, colour} records
 //   k_las_*         the 10-10-10 method (modules/compute_loop_las_cuda)
 //   k_resolve_*     framebuffer -> RGBA8 (resolve.cu:149-191, huffman_hqs/resolve.cu:2-47)
 //   k_merge_* / k_flip_sign  multi-GPU partial-framebuffer merges
@@ -1811,6 +1812,188 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE / PARTS, 8) k_render(Render
                 if (v != ~0ull) atomicMin(g, v);                            // (a pixel no point of the batch reached issues nothing)
             }
         });
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_decode_points: the loaded stream back to points (pcr_decode_points). No counterpart in the reference, whose only decoder
+// outside its render kernels is the per-chain CPU one of include/huffman.h:433-477. One workgroup per batch, one lane per
+// chain, all 64 points of every chain -- no cull, no level of detail, the garbage tails as they are -- from what
+// k_render reads and maybe_finalize() keeps: the packed table, start values, escape words, the colour blocks in segment-major
+// order, and the chain's own bits in either resident layout (the same reads as k_render's at 64 points per chain: the
+// packed words' rows up to four behind the wave's last one, window rows clamped to the batch's 64).
+// Escapes and `wide` table values come from global memory as k_bounds reads them (index clamped into the guard): a flagged
+// batch (BF_GENERIC_SLOW_PATH*) needs no second kernel and no pool in LDS. Escape words are requested a point ahead, at the
+// top of every point and whether or not anybody reads them (three words per point: a point consumes at most three): the
+// loads are on every path (no wait under a branch) -- nearly every wave has an escape in every point (3 % of the symbols
+// x 192 per wave) -- and have a whole point to arrive in. (Measured against requesting them at the top of the same point:
+// no difference on the benchmark stream; kept for the escape-heavy ones.)
+// Output: record (b - first_batch) * 65536 + 64 chain + i = {x, y, z, 0x00BBGGRR}. A lane that stored its own records would
+// write 16 bytes every 1024: 64 cache lines per store instruction. Instead every wave collects DEC_STAGE_POINTS points of its
+// 64 chains in LDS (8 KiB; 16-byte slot j of chain c at c * 8 + (j ^ (c >> 1 & 7)): a 16-lane group of the ds_write_b128 --
+// sixteen chains, one j -- and of the ds_read_b128 -- two chains, eight j -- covers the sixteen slots of a 256-byte bank row
+// once) and writes them back eight lanes per chain: every global_store_dwordx4 writes eight whole 128-byte lines
+// (non-temporal: nobody on the device reads the records back soon; 4 % on the 1e8-point stream, profiles/decode_points.json).
+// The staging is per wave, so the point loop has no workgroup barrier. 16 KiB table + 128 KiB staging: one workgroup per CU,
+// four waves per SIMD.
+// ------------------------------------------------------------------------------------------------
+constexpr int DEC_STAGE_POINTS = 8;
+constexpr uint32_t DEC_STAGE_WAVE_SLOTS = 64 * DEC_STAGE_POINTS;                       // 16-byte records per wave
+constexpr uint32_t DEC_LDS_BYTES = LWC_WAVES * DEC_STAGE_WAVE_SLOTS * 16;              // dynamic LDS of a launch: 128 KiB
+static_assert(sizeof(pcr_point) == 16, "one dwordx4 store per record");
+
+template <int LAYOUT, bool BC7>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_decode_points(StreamView s, uint4 *out, uint32_t first_batch)
+{
+    static_assert(DEC_STAGE_POINTS == 8 && PCR_POINTS_PER_THREAD % 16 == 0, "eight lanes write a chain's 128 bytes; two flushes per colour block");
+    const uint32_t b = first_batch + blockIdx.x;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    extern __shared__ __align__(16) unsigned char s_dyn[];                  // DEC_LDS_BYTES
+    uint4 *const stage = reinterpret_cast<uint4 *>(s_dyn) + wave * DEC_STAGE_WAVE_SLOTS;
+    reinterpret_cast<uint4 *>(s_table)[tid] = reinterpret_cast<const uint4 *>(s.packed_table + (size_t)b * PCR_HUFFMAN_TABLE_SIZE)[tid];
+
+    const pcr_gpu_batch *gb = s.batches + b;
+    const int32_t *sep = s.separate + gb->separate_batch_offset;
+    const uint32_t sep_last = (uint32_t)min((int64_t)0x7FFFFFF0, s.separate_words + (PCR_GUARD_WORDS - 2) - gb->separate_batch_offset);
+    const int32_t *tvalues = s.table_values + (size_t)b * PCR_HUFFMAN_TABLE_SIZE;     // only for `wide` entries
+    uint32_t esc = tid ? (uint32_t)s.separate_sizes[(size_t)b * 1024 + tid - 1] : 0u;
+    const int32_t *sv = s.start_values + ((size_t)b * 1024 + tid) * 3;
+    int32_t px = sv[0], py = sv[1], pz = sv[2];
+
+    // my chain's bits. Packed words: three consecutive words w0..w2 of the chain's sequence, `spare` = 32 minus the bits of w0
+    // already consumed, far0 / far1 the two words behind w2, requested a point before they can move up (k_render's queue).
+    // Point windows: row i of the batch's two planes is the 40-bit view of point i, requested two points ahead.
+    // (the block's base as a global pointer in scalar registers + a per-lane byte offset, as in k_render: a pointer loaded from
+    // memory is a generic one to hipcc -- flat loads, which count on the LDS counter as well)
+    typedef const __attribute__((address_space(1))) char *global_bytes;
+    global_bytes lwb = nullptr;
+    uint32_t lwo = lane * 4;                                // byte offset of my column in the row of far0
+    auto lw_load = [&](uint32_t byte_off) -> uint32_t { return *(const __attribute__((address_space(1))) uint32_t *)(lwb + byte_off); };
+    uint32_t w0 = 0, w1 = 0, w2 = 0, far0 = 0, far1 = 0, spare = 0;
+    const uint32_t *pw_hi = nullptr;
+    const uint8_t *pw_lo = nullptr;
+    uint32_t win_hi[2] = {0, 0}, win_lo[2] = {0, 0};        // the views of points i and i + 1
+    if (LAYOUT == LAYOUT_WORDS) {
+        const uint32_t *wr = s.lw_wave_row + (size_t)b * (LWC_WAVES + 1) + wave;
+        lwb = (global_bytes)(reinterpret_cast<const char *>(s.lw_block[b]) + (size_t)wr[0] * LWC_ROW_BYTES);    // uniform per wave
+        w1 = lw_load(lwo); w2 = lw_load(lwo + LWC_ROW_BYTES);
+        far0 = lw_load(lwo + 2 * LWC_ROW_BYTES); far1 = lw_load(lwo + 3 * LWC_ROW_BYTES);
+        lwo += 2 * LWC_ROW_BYTES;
+    } else {
+        pw_hi = reinterpret_cast<const uint32_t *>(s.point_windows + (size_t)b * PW_BATCH_BYTES) + tid;
+        pw_lo = s.point_windows + (size_t)b * PW_BATCH_BYTES + PW_HI_BYTES + tid;
+        win_hi[0] = pw_hi[0]; win_lo[0] = pw_lo[0];
+        win_hi[1] = pw_hi[PCR_WORKGROUP_SIZE]; win_lo[1] = pw_lo[PCR_WORKGROUP_SIZE];
+    }
+
+    // colour blocks of my chain: [segment][chain], the next segment's requested a segment ahead
+    const uint2 *blocks1 = reinterpret_cast<const uint2 *>(s.colors_t) + ((size_t)b * 4096 + tid);
+    const uint4 *blocks7 = reinterpret_cast<const uint4 *>(s.colors_t) + ((size_t)b * 4096 + tid);
+    uint2 next1 = make_uint2(0, 0);
+    uint4 next7 = make_uint4(0, 0, 0, 0);
+    if (BC7) next7 = blocks7[0]; else next1 = blocks1[0];
+
+    // write-back: lane l stores record (l & 7) of chains (l >> 3) + 8 k of the wave
+    uint4 *const out_wave = out + ((size_t)blockIdx.x * PCR_POINTS_PER_BATCH + (size_t)wave * 64 * PCR_POINTS_PER_THREAD);
+    const uint32_t my_slot = lane * DEC_STAGE_POINTS, my_swz = (lane >> 1) & 7u;
+    const uint32_t rd_chain = lane >> 3, rd_j = lane & 7u;
+
+    // Escape words: qa0..2 = the three at the chain's position before the last point, qb0..2 = the three behind those (requested
+    // at the top of the last point), esc_prev = how many the last point consumed. A point's own three are cut out of those six
+    // AFTER its table walk, so a request has a whole point to arrive in.
+    int32_t qa0 = sep[min(esc, sep_last)], qa1 = sep[min(esc + 1u, sep_last)], qa2 = sep[min(esc + 2u, sep_last)];
+    int32_t qb0 = sep[min(esc + 3u, sep_last)], qb1 = sep[min(esc + 4u, sep_last)], qb2 = sep[min(esc + 5u, sep_last)];
+    uint32_t esc_prev = 0;
+
+    __syncthreads();        // the table is visible
+
+#pragma unroll 1
+    for (int seg = 0; seg < PCR_POINTS_PER_THREAD / 16; ++seg) {
+        Bc1Palette pal = {0, 0, 0, 0};
+        Bc7Block pal7 = {0, 0, 0, 0, 0};
+        const int seg_next = min(seg + 1, PCR_POINTS_PER_THREAD / 16 - 1);
+        if (BC7) { pal7 = bc7_block(next7); next7 = blocks7[(size_t)seg_next * PCR_WORKGROUP_SIZE]; }
+        else     { pal = bc1_palette(next1); next1 = blocks1[(size_t)seg_next * PCR_WORKGROUP_SIZE]; }
+#pragma unroll 1
+        for (int half = 0; half < 16 / DEC_STAGE_POINTS; ++half) {
+            const int i0 = seg * 16 + half * DEC_STAGE_POINTS;
+#pragma unroll
+            for (int j = 0; j < DEC_STAGE_POINTS; ++j) {
+                // the escape words three to five behind the chain's next one, whether any point reads them or not (see above)
+                const int32_t c0 = sep[min(esc + 3u, sep_last)], c1 = sep[min(esc + 4u, sep_last)], c2 = sep[min(esc + 5u, sep_last)];
+                uint64_t bits;
+                if (LAYOUT == LAYOUT_WORDS) {
+                    bits = ((uint64_t)__builtin_amdgcn_alignbit(w0, w1, spare) << 32) | __builtin_amdgcn_alignbit(w1, w2, spare);
+                } else {
+                    bits = ((uint64_t)win_hi[0] << 32) | (win_lo[0] << 24);
+                    win_hi[0] = win_hi[1]; win_lo[0] = win_lo[1];
+                    const uint32_t r = (uint32_t)min(i0 + j + 2, PW_ROWS - 1);          // (uniform)
+                    win_hi[1] = pw_hi[(size_t)r * PCR_WORKGROUP_SIZE]; win_lo[1] = pw_lo[(size_t)r * PCR_WORKGROUP_SIZE];
+                }
+                // the three symbols (:430-439): key = the twelve bits at the head of the view, byte 0 of the entry = length
+                const uint32_t hi = (uint32_t)(bits >> 32);
+                const uint32_t k0 = hi >> 20, e0 = s_table[k0];
+                const uint32_t l0 = e0 & 63u;
+                const uint32_t k1 = ((hi << (l0 & 31u)) >> 20), e1 = s_table[k1];
+                const uint32_t l01 = l0 + (e1 & 63u);
+                const uint32_t k2 = (uint32_t)((bits << (l01 & 63u)) >> 52), e2 = s_table[k2];
+                int32_t v0 = (int32_t)e0 >> TE_VALUE_SHIFT, v1 = (int32_t)e1 >> TE_VALUE_SHIFT, v2 = (int32_t)e2 >> TE_VALUE_SHIFT;
+                // this point's escape words: three of the six requested one and two points ago, by what the last point consumed
+                const int32_t q0 = esc_prev == 0u ? qa0 : esc_prev == 1u ? qa1 : esc_prev == 2u ? qa2 : qb0;
+                const int32_t q1 = esc_prev == 0u ? qa1 : esc_prev == 1u ? qa2 : esc_prev == 2u ? qb0 : qb1;
+                const int32_t q2 = esc_prev == 0u ? qa2 : esc_prev == 1u ? qb0 : esc_prev == 2u ? qb1 : qb2;
+                qa0 = q0; qa1 = q1; qa2 = q2; qb0 = c0; qb1 = c1; qb2 = c2;
+                uint32_t n = 0;
+                if (v0 == TE_SLOW_VALUE) {
+                    if (e0 & TE_ESCAPE) { v0 = q0; n = 1; }                                 // :438
+                    else { v0 = tvalues[k0]; asm volatile("; wide table value from global memory %0" : "+v"(v0)); }
+                }
+                if (v1 == TE_SLOW_VALUE) {
+                    if (e1 & TE_ESCAPE) { v1 = n ? q1 : q0; ++n; }
+                    else { v1 = tvalues[k1]; asm volatile("; wide table value from global memory %0" : "+v"(v1)); }
+                }
+                if (v2 == TE_SLOW_VALUE) {
+                    if (e2 & TE_ESCAPE) { v2 = n == 0 ? q0 : n == 1 ? q1 : q2; ++n; }
+                    else { v2 = tvalues[k2]; asm volatile("; wide table value from global memory %0" : "+v"(v2)); }
+                }
+                esc += n; esc_prev = n;
+                px = (int32_t)((uint32_t)px + (uint32_t)v0);                                // :454-456, :463
+                py = (int32_t)((uint32_t)py + (uint32_t)v1);
+                pz = (int32_t)((uint32_t)pz + (uint32_t)v2);
+                if (LAYOUT == LAYOUT_WORDS) {
+                    // retire the 0..2 words that ran dry, pull in far0 / far1, request the two behind the new w2 (k_render's
+                    // PCR_ADVANCE_WORD_WINDOW: u = spare - consumed + 64)
+                    const uint32_t u = spare + ((64u - l01 - (e2 & 63u)) & 127u);
+                    const uint32_t k = min(u >> 5, 2u);     // 2: no word retired, 1: one, 0: two
+                    spare = u & 31u;
+                    const uint32_t n0 = k == 2u ? w0 : k == 1u ? w1 : w2;
+                    const uint32_t n1 = k == 2u ? w1 : k == 1u ? w2 : far0;
+                    const uint32_t n2 = k == 2u ? w2 : k == 1u ? far0 : far1;
+                    w0 = n0; w1 = n1; w2 = n2;
+                    lwo += (2u - k) * LWC_ROW_BYTES;
+                    far0 = lw_load(lwo); far1 = lw_load(lwo + LWC_ROW_BYTES);
+                }
+                const uint32_t colour = BC7 ? bc7_color(pal7, (uint32_t)(half * DEC_STAGE_POINTS + j)) : bc1_color(pal, (uint32_t)(half * DEC_STAGE_POINTS + j));
+                stage[my_slot + ((uint32_t)j ^ my_swz)] = make_uint4((uint32_t)px, (uint32_t)py, (uint32_t)pz, colour);
+            }
+            // my wave's 64 x 8 records are in LDS (DS operations of a wave execute in order; the fences only stop the compiler)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+            for (int k = 0; k < 64 / 8; ++k) {
+                const uint32_t c = rd_chain + 8u * (uint32_t)k;
+                const uint4 rec = stage[c * DEC_STAGE_POINTS + (rd_j ^ ((c >> 1) & 7u))];
+                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                const u32x4 v = {rec.x, rec.y, rec.z, rec.w};
+                __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(&out_wave[(size_t)c * PCR_POINTS_PER_THREAD + (uint32_t)i0 + rd_j]));
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
     }
 }
 

@@ -164,6 +164,7 @@ struct HuffmanLasData : Resource {
     int64_t numBatchesLoaded = 0, numPointsLoaded = 0, offsetToBatchData = 0;
     int64_t numBatchesResident = 0;     // what the next frame draws; lags numBatchesLoaded only with asyncUpload
     bool asyncUpload = false;           // copies + transcode on the context's loader stream (pcr_set_async_upload)
+    Renderer *loadedOn = nullptr;       // the renderer whose context holds the stream (load() .. unload())
 
     std::shared_ptr<LoaderTask> task;
     std::mutex mtx_state, mtx_tasks;
@@ -217,6 +218,7 @@ struct HuffmanLasData : Resource {
             state = LOADING;
         }
         pcr_file_header hdr{numPoints, numBatches, encodedBytes, separateBytes, clusterBytes};
+        loadedOn = renderer;
         renderer->check(pcr_stream_begin(renderer->ctx, &hdr, 0), "pcr_stream_begin");
         renderer->check(pcr_set_async_upload(renderer->ctx, asyncUpload ? 1 : 0), "pcr_set_async_upload");
         numBatchesLoaded = numPointsLoaded = numBatchesResident = 0;
@@ -282,6 +284,7 @@ struct HuffmanLasData : Resource {
     {
         stopReader();
         numBatchesLoaded = 0;
+        loadedOn = nullptr;
         pcr_stream_unload(renderer->ctx);
         std::lock_guard<std::mutex> lock(mtx_state);
         state = UNLOADED;
@@ -292,6 +295,33 @@ struct HuffmanLasData : Resource {
     {
         numBatchesResident = pcr_batches_resident(renderer->ctx);
         return numBatchesResident == numBatches;
+    }
+
+    // Every point the context it was loaded on holds right now, decoded on the GPU (pcr_read_points: the stream's order, 65 536
+    // records per batch, padding and tail artefacts as the render kernels draw them). Not in the reference.
+    void decodePoints(std::vector<pcr_point> &out)
+    {
+        if (!loadedOn) throw std::runtime_error("decodePoints: the resource is not loaded");
+        const int64_t nB = pcr_batches_resident(loadedOn->ctx);
+        out.resize((size_t)nB * PCR_POINTS_PER_BATCH);
+        loadedOn->check(pcr_read_points(loadedOn->ctx, 0, nB, out.data(), out.size()), "pcr_read_points");
+    }
+
+    // Scale, offset and box of the LAS file the stream was made from, as the first batch record carries them
+    // (include/BatchDumpData.h:60-107: doubles at 20 and 44, the LAS box as floats at 92 and 104).
+    pcr_las_info lasInfo() const
+    {
+        std::ifstream f(path, std::ios::binary);
+        char r[PCR_BATCH_FIXED_HEADER];
+        f.seekg(offsetToBatchData);
+        f.read(r, sizeof r);
+        if (!f) throw std::runtime_error(path + ": short read on the first batch record");
+        pcr_las_info las;
+        float lmin[3], lmax[3];
+        std::memcpy(las.scale, r + 20, 24); std::memcpy(las.offset, r + 44, 24);
+        std::memcpy(lmin, r + 92, 12); std::memcpy(lmax, r + 104, 12);
+        for (int k = 0; k < 3; ++k) { las.min[k] = lmin[k]; las.max[k] = lmax[k]; }
+        return las;
     }
 
 private:

@@ -183,6 +183,29 @@ def read_las(path: str):
             color.astype(np.uint32), las)
 
 
+POINT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("color", "<u4")])     # pcr_point
+
+
+def write_las(path, x=None, y=None, z=None, color=None, las: Optional[LasInfo] = None, points=None) -> None:
+    """LAS 1.2 / point format 2 file of the given points (pcr_write_las): either four arrays (int32 coordinates, 0x00BBGGRR
+    colours) or `points`, a structured array of POINT_DTYPE as Context.read_points returns it. `las`: the header's scale,
+    offset, min and max. read_las gives the same values back."""
+    if las is None:
+        raise ValueError("write_las needs the LasInfo of the header")
+    lib = N.host_lib()
+    if points is not None:
+        pts = np.ascontiguousarray(points, POINT_DTYPE)
+        rc = lib.pcr_write_las_points(os.fsencode(path), pts.ctypes.data, len(pts), C.byref(las))
+    else:
+        x, y, z = (np.ascontiguousarray(a, np.int32) for a in (x, y, z))
+        color = np.ascontiguousarray(color, np.uint32)
+        if not (len(x) == len(y) == len(z) == len(color)):
+            raise ValueError("x, y, z, color must be of equal length")
+        rc = lib.pcr_write_las(os.fsencode(path), x.ctypes.data, y.ctypes.data, z.ctypes.data, color.ctypes.data, len(x), C.byref(las))
+    if rc:
+        raise PcrError(f"pcr_write_las: {N.host_error()}")
+
+
 class HuffmanFile:
     """Header + batch-record slicing of a .huffman image held in memory or memory-mapped from disk."""
 
@@ -240,6 +263,15 @@ class HuffmanFile:
         enc = np.frombuffer(self.buf, np.uint32, min(ne, ENCODED_PAD_WORDS), o)
         sep = np.frombuffer(self.buf, np.int32, min(ns, SEPARATE_PAD_WORDS), o + 4 * ne)
         return enc, sep
+
+    def batch_las_info(self, b: int) -> LasInfo:
+        """Scale, offset and the cloud's min / max as batch b's record carries them (include/BatchDumpData.h:60-107: doubles
+        at 20 and 44, the LAS box as floats at 92 and 104)."""
+        o = int(self.batch_offsets[b])
+        las = LasInfo()
+        las.scale[:] = struct.unpack_from("<3d", self.buf, o + 20); las.offset[:] = struct.unpack_from("<3d", self.buf, o + 44)
+        las.min[:] = struct.unpack_from("<3f", self.buf, o + 92); las.max[:] = struct.unpack_from("<3f", self.buf, o + 104)
+        return las
 
     def blobs(self, first: int = 0, count: Optional[int] = None) -> Iterator[memoryview]:
         if count is None:
@@ -409,6 +441,37 @@ class Context:
 
     def synchronize(self):
         self._chk(self.lib.pcr_synchronize(self.h), "pcr_synchronize")
+
+    # -- decode (pcr_decode_points / pcr_read_points) -------------------------------------------------
+    def _decode_count(self, first: int, count: Optional[int]) -> int:
+        return self.batches_resident - first if count is None or count < 0 else int(count)
+
+    def decode_points(self, first: int = 0, count: Optional[int] = None, out=None):
+        """Batches [first, first + count) of the loaded stream as a torch.int32 tensor [n, 4] on the context's device:
+        columns x, y, z and the colour 0x00BBGGRR (its bits, as int32: torch's uint32 has few operators). count None:
+        every resident batch from `first` on. `out`: a contiguous int32 CUDA tensor of at least n * 4 elements to fill
+        instead of a new one. The kernel runs on the context's own stream, which nothing orders against torch's: the
+        call synchronises torch's current stream before it (the tensor's memory may be in use there) and the context's
+        stream after it, so the tensor is ready on return."""
+        import torch
+        n = self._decode_count(first, count) * POINTS_PER_BATCH
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((max(n, 0), 4), dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev or out.numel() < 4 * n:
+            raise ValueError(f"out must be a contiguous int32 tensor of at least {4 * n} elements on {dev}")
+        torch.cuda.current_stream(dev).synchronize()
+        self._chk(self.lib.pcr_decode_points(self.h, first, -1 if count is None else count, C.c_void_p(out.data_ptr() if out.numel() else None),
+                                             out.numel() // 4), "pcr_decode_points")
+        self.synchronize()
+        return out.view(-1, 4)[:max(n, 0)]
+
+    def read_points(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The same on the host, without torch: a numpy structured array of POINT_DTYPE (pcr_read_points; synchronises)."""
+        n = max(self._decode_count(first, count), 0) * POINTS_PER_BATCH
+        out = np.empty(n, POINT_DTYPE)
+        self._chk(self.lib.pcr_read_points(self.h, first, -1 if count is None else count, out.ctypes.data if n else None, n), "pcr_read_points")
+        return out
 
     def stats(self) -> dict:
         st = RenderStats()
@@ -670,6 +733,29 @@ class HuffmanLasData(Resource):
         self.numBatchesLoaded = 0
         renderer.ctx.stream_unload()
         self.state = Resource.UNLOADED
+
+    def points(self, renderer: Renderer, world: bool = False):
+        """Every point of the loaded resource, decoded on the GPU (Context.decode_points): a torch.int32 tensor [n, 4] of
+        x, y, z, colour in the stream's order. world=True: (xyz, pts) with xyz a float64 tensor [n, 3] = x * scale + offset,
+        computed by torch on the device from every batch record's own scale and offset, and pts the int32 tensor (its
+        column 3 holds the colours)."""
+        import torch
+        pts = renderer.ctx.decode_points(0, None)
+        if not world:
+            return pts
+        nb = pts.shape[0] // POINTS_PER_BATCH
+        so = np.empty((nb, 2, 3), np.float64)
+        for i in range(nb):
+            g = self.file.batch_las_info(self.first_batch + i)
+            so[i, 0], so[i, 1] = tuple(g.scale), tuple(g.offset)
+        so = torch.from_numpy(so).to(pts.device)
+        xyz = pts[:, :3].view(nb, POINTS_PER_BATCH, 3).to(torch.float64) * so[:, None, 0, :] + so[:, None, 1, :]
+        return xyz.view(-1, 3), pts
+
+    def las_info(self) -> LasInfo:
+        """Scale, offset, min and max of the LAS file the stream was made from, as its first batch record carries them (the
+        box as floats)."""
+        return self.file.batch_las_info(self.first_batch)
 
 
 class _HuffmanMethod(Method):
