@@ -346,7 +346,7 @@ void pcr_oracle_decode_batch(const pcr_oracle_stream *s, int64_t batch, int npr,
 /* ------------------------------------------------------------------------------------------------
  * rasterize variants
  * ---------------------------------------------------------------------------------------------- */
-enum { MODE_BASIC, MODE_HQS_DEPTH, MODE_HQS_COLOR, MODE_TIE_COUNT };
+enum { MODE_BASIC, MODE_HQS_DEPTH, MODE_HQS_COLOR, MODE_TIE_COUNT, MODE_TRACE };
 
 typedef struct {
     const pcr_oracle_stream *s;
@@ -359,6 +359,8 @@ typedef struct {
     uint64_t *fb;                /* basic / hqs depth: written; hqs colour: read */
     uint64_t *rg, *ba;
     uint32_t *tie;               /* MODE_TIE_COUNT: per pixel, bits 30:0 = points at the winning depth, bit 31 = one of them has another colour */
+    int64_t *tr_pix; uint32_t *tr_depth, *tr_colour;   /* MODE_TRACE: one entry per inside point, in walk order */
+    int64_t tr_n, tr_cap;
     size_t fb_elems;
     int shared_fb;               /* several host threads draw into fb (the multi-threaded CPU baseline): atomic min */
 } raster_ctx;
@@ -407,6 +409,17 @@ static void sink_raster(void *vctx, int chain, int i, int32_t cx, int32_t cy, in
         return;
     }
 
+    if (c->mode == MODE_TRACE) {
+        if (c->tr_n < c->tr_cap) {
+            c->tr_pix[c->tr_n] = pix;
+            c->tr_depth[c->tr_n] = depth;
+            c->tr_colour[c->tr_n] = c->s->color_format == PCR_COLOR_BC7 ? pcr_oracle_decode_bc7(index, c->s->colors)
+                                                                        : pcr_oracle_decode_bc1(index, c->s->colors);
+        }
+        c->tr_n++;
+        return;
+    }
+
     if (c->mode == MODE_HQS_COLOR) {
         uint64_t old = c->fb[pix];
         float old_depth = bits_f32((uint32_t)(old >> 32));
@@ -444,6 +457,19 @@ static void sink_raster(void *vctx, int chain, int i, int32_t cx, int32_t cy, in
     }
 }
 
+/* All npr points per chain of batch bi through sink_raster, in the mode of *c. */
+static void raster_batch(raster_ctx *c, int64_t bi, int npr, int use_double)
+{
+    const pcr_gpu_batch *b = &c->s->batches[bi];
+    c->batch = bi; c->npr = npr; c->use_double = use_double;
+    c->scale[0] = b->scale_x; c->scale[1] = b->scale_y; c->scale[2] = b->scale_z;
+    c->offd[0] = b->offset_x - b->las_min_x;
+    c->offd[1] = b->offset_y - b->las_min_y;
+    c->offd[2] = b->offset_z - b->las_min_z;
+    for (int k = 0; k < 3; ++k) { c->scalef[k] = (float)c->scale[k]; c->offf[k] = (float)c->offd[k]; }
+    for (int cl = 0; cl < 32; ++cl) decode_cluster(c->s, bi, cl, npr, sink_raster, c);
+}
+
 static void render_range_ex(const pcr_oracle_stream *s, const pcr_render_params *p, int mode,
                             int64_t first, int64_t count, uint64_t *fb, uint64_t *rg, uint64_t *ba,
                             pcr_render_stats *stats, int shared_fb)
@@ -465,13 +491,7 @@ static void render_range_ex(const pcr_oracle_stream *s, const pcr_render_params 
             stats->points_iterated += (int64_t)PCR_WORKGROUP_SIZE * npr;
             stats->batches_double += use_double;
         }
-        c.batch = bi; c.npr = npr; c.use_double = use_double;
-        c.scale[0] = b->scale_x; c.scale[1] = b->scale_y; c.scale[2] = b->scale_z;
-        c.offd[0] = b->offset_x - b->las_min_x;
-        c.offd[1] = b->offset_y - b->las_min_y;
-        c.offd[2] = b->offset_z - b->las_min_z;
-        for (int k = 0; k < 3; ++k) { c.scalef[k] = (float)c.scale[k]; c.offf[k] = (float)c.offd[k]; }
-        for (int cl = 0; cl < 32; ++cl) decode_cluster(s, bi, cl, npr, sink_raster, &c);
+        raster_batch(&c, bi, npr, use_double);
     }
 }
 
@@ -518,13 +538,7 @@ int pcr_oracle_count_depth_ties(const pcr_oracle_stream *s, const pcr_render_par
             const pcr_gpu_batch *b = &s->batches[bi];
             int npr = 0, use_double = 0;
             if (!pcr_oracle_batch_lod(b, p, PCR_ORACLE_MEM_ITER, &npr, &use_double)) continue;
-            c.batch = bi; c.npr = npr; c.use_double = use_double;
-            c.scale[0] = b->scale_x; c.scale[1] = b->scale_y; c.scale[2] = b->scale_z;
-            c.offd[0] = b->offset_x - b->las_min_x;
-            c.offd[1] = b->offset_y - b->las_min_y;
-            c.offd[2] = b->offset_z - b->las_min_z;
-            for (int k = 0; k < 3; ++k) { c.scalef[k] = (float)c.scale[k]; c.offf[k] = (float)c.offd[k]; }
-            for (int cl = 0; cl < 32; ++cl) decode_cluster(s, bi, cl, npr, sink_raster, &c);
+            raster_batch(&c, bi, npr, use_double);
         }
     }
     int64_t any = 0, other = 0;
@@ -535,6 +549,24 @@ int pcr_oracle_count_depth_ties(const pcr_oracle_stream *s, const pcr_render_par
     free(tie);
     *tie_pixels = any; *tie_pixels_other_colour = other;
     return 0;
+}
+
+/* Every point of batches [first, first + count) that passes the inside test, in walk order: its pixel id, f32_bits(w) and
+ * decoded colour (BC1 or BC7 by the stream). `variant` picks the LOD expression as in pcr_oracle_batch_lod. Returns how
+ * many there are; at most `cap` are written. */
+int64_t pcr_oracle_trace_points(const pcr_oracle_stream *s, const pcr_render_params *p, int64_t first, int64_t count,
+                                int variant, int64_t *pix, uint32_t *depth_bits, uint32_t *colour, int64_t cap)
+{
+    raster_ctx c;
+    memset(&c, 0, sizeof c);
+    c.s = s; c.p = p; c.mode = MODE_TRACE; c.fb_elems = pcr_fb_elems(p->width, p->height);
+    c.tr_pix = pix; c.tr_depth = depth_bits; c.tr_colour = colour; c.tr_cap = cap;
+    for (int64_t bi = first; bi < first + count; ++bi) {
+        int npr = 0, use_double = 0;
+        if (!pcr_oracle_batch_lod(&s->batches[bi], p, variant, &npr, &use_double)) continue;
+        raster_batch(&c, bi, npr, use_double);
+    }
+    return c.tr_n;
 }
 
 /* Multi-threaded basic render for the CPU baseline: batches handed out one at a time (an atomic counter), ONE

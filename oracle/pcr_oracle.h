@@ -70,6 +70,12 @@ int pcr_oracle_render_basic_mt(const pcr_oracle_stream *s, const pcr_render_para
  * depth<<32|pointIndex) while this build and the oracle define "plain min of depth<<32|colour" (SURVEY Appendix C.5). */
 int pcr_oracle_count_depth_ties(const pcr_oracle_stream *s, const pcr_render_params *p, int64_t first, int64_t count,
                                 const uint64_t *fb, int64_t *tie_pixels, int64_t *tie_pixels_other_colour);
+/* The same walk as a list: for every point of the batches that passes the inside test, in walk order, its pixel id,
+ * f32_bits(w) and decoded colour (BC1 or BC7 by the stream; the basic frame always holds the BC1 decode). `variant` as in
+ * pcr_oracle_batch_lod. Returns the number of such points; at most `cap` entries are written. Tests rebuild the frames from
+ * it in numpy, independently of the frame code above. */
+int64_t pcr_oracle_trace_points(const pcr_oracle_stream *s, const pcr_render_params *p, int64_t first, int64_t count,
+                                int variant, int64_t *pix, uint32_t *depth_bits, uint32_t *colour, int64_t cap);
 /* huffman_hqs/depth.cu */
 void pcr_oracle_render_hqs_depth(const pcr_oracle_stream *s, const pcr_render_params *p,
                                  int64_t first, int64_t count, uint64_t *fb, pcr_render_stats *stats);

@@ -94,22 +94,21 @@ void las_hqs_ref_color(const pcr_xyz_batch *batches, int64_t num_batches, const 
     las_walk(batches, num_batches, xyz12, xyz8, xyz4, p, stats, color_point, &c);
 }
 
-/* Every point the two passes draw, as (pixel, w): for counting the 1 % test independently of las_hqs_ref_color. Returns how many
- * there are; at most `cap` are written. */
-typedef struct { int64_t n, cap; int64_t *pix; float *w; } las_points_ctx;
+/* Every point the two passes draw, as (pixel, w) and, if `index` is not NULL, its point index: for counting the 1 % test and
+ * depth ties independently of the frame code. Returns how many there are; at most `cap` are written. */
+typedef struct { int64_t n, cap; int64_t *pix; float *w; uint32_t *index; } las_points_ctx;
 
 static void list_point(void *vctx, size_t pix, float w, uint32_t index)
 {
     las_points_ctx *c = (las_points_ctx *)vctx;
-    (void)index;
-    if (c->n < c->cap) { c->pix[c->n] = (int64_t)pix; c->w[c->n] = w; }
+    if (c->n < c->cap) { c->pix[c->n] = (int64_t)pix; c->w[c->n] = w; if (c->index) c->index[c->n] = index; }
     c->n++;
 }
 
 int64_t las_hqs_ref_points(const pcr_xyz_batch *batches, int64_t num_batches, const uint32_t *xyz12, const uint32_t *xyz8,
-                           const uint32_t *xyz4, const pcr_render_params *p, int64_t *pix, float *w, int64_t cap)
+                           const uint32_t *xyz4, const pcr_render_params *p, int64_t *pix, float *w, uint32_t *index, int64_t cap)
 {
-    las_points_ctx c = { 0, cap, pix, w };
+    las_points_ctx c = { 0, cap, pix, w, index };
     las_walk(batches, num_batches, xyz12, xyz8, xyz4, p, NULL, list_point, &c);
     return c.n;
 }

@@ -37,7 +37,7 @@ def lib() -> C.CDLL:
                                         C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RenderStats)]
         L.las_hqs_ref_color.restype = None
         L.las_hqs_ref_points.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RenderParams),
-                                         C.c_void_p, C.c_void_p, C.c_int64]
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
         L.las_hqs_ref_points.restype = C.c_int64
         _lib = L
     return _lib
@@ -67,12 +67,13 @@ def render_color(batches, xyz12, xyz8, xyz4, rgba, p: RenderParams, fb, rg=None,
     return rg, ba, st.as_dict()
 
 
-def drawn_points(batches, xyz12, xyz8, xyz4, p: RenderParams, num_batches=None):
-    """(pixel int64, w float32) of every point the passes draw."""
+def drawn_points(batches, xyz12, xyz8, xyz4, p: RenderParams, num_batches=None, with_index=False):
+    """(pixel int64, w float32) of every point the passes draw; with_index: and its point index (uint32)."""
     nb = _nb(batches, num_batches)
     cap = max(nb - 1, 0) * 65536
     pix, w = np.zeros(cap, np.int64), np.zeros(cap, np.float32)
+    index = np.zeros(cap, np.uint32) if with_index else None
     n = lib().las_hqs_ref_points(C.addressof(batches), nb, xyz12.ctypes.data, xyz8.ctypes.data, xyz4.ctypes.data, C.byref(p),
-                                 pix.ctypes.data, w.ctypes.data, cap)
+                                 pix.ctypes.data, w.ctypes.data, index.ctypes.data if with_index else None, cap)
     assert n <= cap
-    return pix[:n], w[:n]
+    return (pix[:n], w[:n], index[:n]) if with_index else (pix[:n], w[:n])

@@ -53,6 +53,9 @@ def lib() -> C.CDLL:
         L.pcr_oracle_render_hqs_color.restype = None
         L.pcr_oracle_count_depth_ties.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_int64, C.c_int64, C.c_void_p,
                                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.pcr_oracle_trace_points.restype = C.c_int64
+        L.pcr_oracle_trace_points.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_int64]
         L.pcr_oracle_resolve_basic.argtypes = [C.POINTER(RenderParams), C.c_void_p, C.c_void_p]
         L.pcr_oracle_resolve_basic.restype = None
         L.pcr_oracle_resolve_hqs.argtypes = [C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -154,6 +157,17 @@ class OracleFile:
         rc = lib().pcr_oracle_count_depth_ties(self.stream, C.byref(p), first, count, fb.ctypes.data, C.byref(a), C.byref(b))
         assert rc == 0
         return a.value, b.value
+
+    def trace_points(self, p: RenderParams, variant: int = MEM_ITER, first=0, count=None):
+        """(pixel int64, f32_bits(w) uint32, decoded colour uint32) of every point of the batches that passes the inside test, in
+        walk order; `variant` picks the LOD expression (MEM_ITER: the basic pass, HQS: the two HQS passes)."""
+        count = self.num_batches - first if count is None else count
+        cap = count * 65536
+        pix, depth, colour = np.zeros(cap, np.int64), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        n = lib().pcr_oracle_trace_points(self.stream, C.byref(p), first, count, variant, pix.ctypes.data, depth.ctypes.data,
+                                          colour.ctypes.data, cap)
+        assert 0 <= n <= cap
+        return pix[:n], depth[:n], colour[:n]
 
     def render_hqs_depth(self, p: RenderParams, fb=None, first=0, count=None):
         fb = self.new_fb(p) if fb is None else fb
