@@ -163,6 +163,31 @@ int pcr_decode_points(pcr_ctx *ctx, int64_t first_batch, int64_t count, void *de
 /* The same into host memory: staged through a device buffer of the context, 64 batches (64 MiB) at a time; synchronises. */
 int pcr_read_points(pcr_ctx *ctx, int64_t first_batch, int64_t count, pcr_point *host, size_t capacity_points);
 
+/* ---- box selection: a spatial read on the decode path (no reference counterpart) -----------------------------------------
+ * CONTRACT: the output of pcr_select_box equals pcr_decode_points of the same range with the records outside the box removed,
+ * byte for byte -- the same 16-byte records in the same relative order, packed without gaps; padding duplicates and the tail
+ * artefact are points like any other; BC1 and BC7, either resident layout, before and after the first frame.
+ *
+ * pcr_batch_point_bounds: host_bounds[i * 6 ..] = min x, y, z, max x, y, z over all 65 536 records pcr_decode_points writes for
+ *   batch first_batch + i: exact integers, computed on the GPU (k_point_bounds, about one colourless decode pass) and cached in
+ *   the context per batch; the cache is dropped by pcr_stream_begin / pcr_stream_unload and grows as batches become resident.
+ *   (pcr_gpu_batch::min/max are single-precision hints and do not cover the tail artefact.) Synchronises.
+ * pcr_select_box: the records of batches [first_batch, first_batch + count) inside *box (bounds inclusive) to dev_points, their
+ *   number to *out_count. Range semantics, count < 0 and the restriction under pcr_set_async_upload are pcr_decode_points'.
+ *   Batches whose exact box misses the query are not decoded, those wholly inside go through the full-batch decode, the ones
+ *   that straddle it are counted (k_select_count) and then written (k_select_write). dev_points == NULL only counts. A
+ *   capacity_points below the result: PCR_E_ARG, *out_count = the count needed, nothing written. An empty box, or a range of
+ *   0 batches: 0 records, PCR_OK. Synchronises (the host has to learn the count). Touches no framebuffer, no prepass state, no
+ *   render statistics. stats may be NULL.
+ * pcr_read_box: the same into host memory, staged through the context's decode staging buffer 64 batches at a time.
+ * PCR_E_ARG with a message: no stream loaded, a range outside the resident batches, a NULL box, a NULL out_count, a misaligned
+ * pointer (16 bytes on the device, alignof(pcr_point) on the host). */
+int pcr_batch_point_bounds(pcr_ctx *ctx, int64_t first_batch, int64_t count, int32_t *host_bounds);
+int pcr_select_box(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_box *box, void *dev_points, size_t capacity_points,
+                   int64_t *out_count, pcr_select_stats *stats);
+int pcr_read_box(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_box *box, pcr_point *host, size_t capacity_points,
+                 int64_t *out_count, pcr_select_stats *stats);
+
 /* What a collective library needs to merge partial frames in place (include/pcr_dist.h does it with RCCL): the HIP stream
  * the context enqueues on, its device ordinal and the length of each framebuffer in 64-bit words. */
 void *pcr_get_stream(pcr_ctx *ctx);

@@ -118,6 +118,22 @@ typedef struct pcr_point {
     uint32_t color;
 } pcr_point;
 
+/* An axis-aligned box in the stream's int32 coordinates (pcr_select_box), bounds inclusive. min[k] > max[k] on any axis: the
+ * empty box. */
+typedef struct pcr_box {
+    int32_t min[3], max[3];
+} pcr_box;
+
+/* What a selection did (pcr_select_box / pcr_read_box): the batches of the range by their exact box against the query -- wholly
+ * outside (not decoded), wholly inside (decoded whole), straddling (decoded twice: counted, then written) -- and the records
+ * selected, which is the call's *out_count. */
+typedef struct pcr_select_stats {
+    int64_t batches_outside;
+    int64_t batches_inside;
+    int64_t batches_straddling;
+    int64_t points_selected;
+} pcr_select_stats;
+
 /* Number of u64 elements a framebuffer of w x h must hold: ndc == 1.0 maps to column w / row h
  * (SURVEY Appendix C.2), so pixel ids reach w*(h+1). */
 static inline size_t pcr_fb_elems(int w, int h) { return (size_t)w * (size_t)(h + 1) + 1; }

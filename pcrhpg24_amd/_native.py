@@ -57,6 +57,17 @@ class Point(C.Structure):                         # pcr_point: one decoded point
     _fields_ = [("x", c_i32), ("y", c_i32), ("z", c_i32), ("color", c_u32)]
 
 
+class Box(C.Structure):                           # pcr_box: int32 coordinates, bounds inclusive; min > max on an axis = empty
+    _fields_ = [("min", c_i32 * 3), ("max", c_i32 * 3)]
+
+
+class SelectStats(C.Structure):                   # pcr_select_stats
+    _fields_ = [(n, c_i64) for n in ("batches_outside", "batches_inside", "batches_straddling", "points_selected")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class EncodeStats(C.Structure):                   # pcr_encode_stats
     _fields_ = [(n, c_i64) for n in ("num_points_in", "num_points", "num_batches", "encoded_bytes", "separate_bytes",
                                      "cluster_bytes", "escaped_symbols", "total_symbols", "file_bytes")]
@@ -65,7 +76,7 @@ class EncodeStats(C.Structure):                   # pcr_encode_stats
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
-assert C.sizeof(Point) == 16
+assert C.sizeof(Point) == 16 and C.sizeof(Box) == 24 and C.sizeof(SelectStats) == 32
 assert C.sizeof(XyzBatch) == 64 and C.sizeof(GpuBatch) == 160 and C.sizeof(FileHeader) == 40 and C.sizeof(RenderParams) == 224
 
 
@@ -86,6 +97,7 @@ HIP_SYMBOLS = [
     "pcr_render_las_hqs_depth", "pcr_render_las_hqs_color",
     "pcr_las_algorithmic_bytes", "pcr_gpu_encode_points", "pcr_gpu_encode_free",
     "pcr_decode_points", "pcr_read_points",
+    "pcr_batch_point_bounds", "pcr_select_box", "pcr_read_box",
 ]
 
 HOST_SYMBOLS = [
@@ -194,6 +206,9 @@ def hip_lib() -> C.CDLL:
         lib.pcr_kernel_timing_read.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
         lib.pcr_decode_points.argtypes = [C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_size_t]
         lib.pcr_read_points.argtypes = [C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_size_t]
+        lib.pcr_batch_point_bounds.argtypes = [C.c_void_p, c_i64, c_i64, C.c_void_p]
+        for n in ("pcr_select_box", "pcr_read_box"):
+            getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Box), C.c_void_p, C.c_size_t, C.POINTER(c_i64), C.POINTER(SelectStats)]
         _hip = lib
     return _hip
 

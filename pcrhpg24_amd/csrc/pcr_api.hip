@@ -8,6 +8,7 @@
 #include "pcr_hip.h"
 #include "pcr_kernels.hip.h"
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -120,6 +121,18 @@ struct pcr_ctx {
     bool decode_lds_ready = false;              // ... and for k_decode_points' 128 KiB of staging
     pcr_point *d_decode_stage = nullptr;        // pcr_read_points: device staging of at most DECODE_STAGE_BATCHES batches of points
     int64_t decode_stage_batches = 0;
+    // box selection (pcr_batch_point_bounds / pcr_select_box): the exact integer box of every batch's decoded records, computed on
+    // request by k_point_bounds and kept per batch until the stream goes (only for batches whose transcode is final: the last
+    // batch of a stream that is still loading decodes differently once its follower's words arrive), and the scratch of a
+    // selection's straddling batches
+    std::vector<int32_t> h_point_bounds;        // [hdr.num_batches * 6]
+    std::vector<uint8_t> h_point_bounds_ok;     // [hdr.num_batches]
+    int32_t *d_point_bounds = nullptr;          // [hdr.num_batches * 6]
+    int64_t sel_capacity = 0;                   // straddling batches the four arrays below hold
+    uint32_t *d_sel_list = nullptr;             // [sel_capacity] their batch indices
+    uint32_t *d_sel_counts = nullptr;           // [sel_capacity * 1024] selected points per chain (k_select_count)
+    uint32_t *d_sel_totals = nullptr;           // [sel_capacity] ... and per batch
+    int64_t *d_sel_offsets = nullptr;           // [sel_capacity] first output record of each (k_select_write)
     int64_t prepass_batches = 0;
     static constexpr int FENCES = 8;
     hipEvent_t fence[FENCES] = {};              // pcr_fence_record / pcr_fence_wait: device-scope ordering between streams
@@ -213,6 +226,8 @@ void free_stream_buffers(pcr_ctx *c)
     c->lw_segments.clear(); dfree(c->d_lw_block); dfree(c->d_lw_wave_row); dfree(c->d_wave_rows); dfree(c->d_lw_prov); c->provisional_for = -1;
     dfree(c->d_lane_words); dfree(c->d_batch_flags); dfree(c->d_packed_table); dfree(c->d_point_windows); dfree(c->d_batch_runs); c->transcoded = 0;
     dfree(c->d_order); dfree(c->d_chunk_count); dfree(c->d_any_generic); c->order_stride = 0;
+    dfree(c->d_point_bounds); c->h_point_bounds.clear(); c->h_point_bounds_ok.clear();
+    dfree(c->d_sel_list); dfree(c->d_sel_counts); dfree(c->d_sel_totals); dfree(c->d_sel_offsets); c->sel_capacity = 0;
 
     if (c->any_generic_pending && c->any_generic_ev) (void)hipEventSynchronize(c->any_generic_ev);
     c->any_generic_pending = false;
@@ -861,6 +876,7 @@ int pcr_upload_tail(pcr_ctx *c, const uint32_t *enc, size_t n_enc, const int32_t
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->batches_loaded > 0 && c->transcoded >= c->batches_loaded) c->transcoded = c->batches_loaded - 1;   // its over-reads see these words
     c->provisional_for = -1;
+    if (c->batches_loaded > 0 && (size_t)c->batches_loaded <= c->h_point_bounds_ok.size()) c->h_point_bounds_ok[(size_t)c->batches_loaded - 1] = 0;   // (its cached box too)
     if (c->async_upload) {           // no render-time transcode in this mode: redo the last batch now
         { int trc = enqueue_transcode(c, true, c->stream); if (trc) return trc; }
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1462,6 +1478,232 @@ int pcr_read_points(pcr_ctx *c, int64_t first_batch, int64_t count, pcr_point *h
         HIP_TRY(c, hipMemcpyAsync(host + (size_t)done * PCR_POINTS_PER_BATCH, c->d_decode_stage, (size_t)m * PCR_POINTS_PER_BATCH * sizeof(pcr_point),
                                   hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return PCR_OK;
+}
+
+// ---- box selection -----------------------------------------------------------------------------
+// (as launch_decode: a stream that holds both layouts follows pcr_set_render_variant, AUTO: point windows)
+static bool select_reads_windows(const pcr_ctx *c)
+{
+    const bool have_windows = c->layout != PCR_LAYOUT_WORDS, have_words = c->layout != PCR_LAYOUT_POINT_WINDOWS;
+    return have_windows && (c->variant != PCR_VARIANT_WORDS || !have_words);
+}
+
+// Range check shared by the three entry points: decode_range's without the destination (it may be NULL here).
+static int select_range(pcr_ctx *c, int64_t first, int64_t count, int64_t *n)
+{
+    if (!c->stream_open) return set_err(c, PCR_E_ARG, "no stream loaded (call pcr_stream_begin / pcr_upload_batch)");
+    if (c->async_upload) poll_loader(c, false);
+    const int64_t nB = c->visible_batches();
+    if (first < 0 || first > nB) return set_err(c, PCR_E_ARG, "first batch %lld outside the %lld resident batches", (long long)first, (long long)nB);
+    if (count < 0) count = nB - first;
+    if (count > nB - first)
+        return set_err(c, PCR_E_ARG, "batches [%lld, %lld) reach past the %lld resident batches", (long long)first, (long long)(first + count), (long long)nB);
+    *n = count;
+    return PCR_OK;
+}
+
+// c->h_point_bounds holds the exact boxes of batches [first, first + n) on return: one k_point_bounds launch over the span of the
+// batches not cached yet, read back. Synchronises if it launches.
+static int ensure_point_bounds(pcr_ctx *c, int64_t first, int64_t n)
+{
+    int rc;
+    if (!c->async_upload && (rc = enqueue_transcode(c, true, c->stream))) return rc;
+    const size_t nB = (size_t)c->hdr.num_batches;
+    if (c->h_point_bounds_ok.size() != nB) { c->h_point_bounds.assign(nB * 6, 0); c->h_point_bounds_ok.assign(nB, 0); }
+    for (size_t b = (size_t)std::max<int64_t>(c->transcoded, 0); b < nB; ++b) c->h_point_bounds_ok[b] = 0;     // not final (yet, or any more: pcr_upload_tail)
+    int64_t lo = -1, hi = -1;
+    for (int64_t b = first; b < first + n; ++b)
+        if (!c->h_point_bounds_ok[(size_t)b]) { if (lo < 0) lo = b; hi = b + 1; }
+    if (lo < 0) return PCR_OK;
+    if (!c->d_point_bounds) HIP_TRY(c, hipMalloc((void **)&c->d_point_bounds, nB * 6 * sizeof(int32_t)));
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)(hi - lo)), block(PCR_WORKGROUP_SIZE);
+    if (select_reads_windows(c)) hipLaunchKernelGGL((k_point_bounds<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_point_bounds, (uint32_t)lo);
+    else                         hipLaunchKernelGGL((k_point_bounds<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_point_bounds, (uint32_t)lo);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->h_point_bounds.data() + lo * 6, c->d_point_bounds + lo * 6, (size_t)(hi - lo) * 6 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int64_t b = lo; b < hi && b < c->transcoded; ++b) c->h_point_bounds_ok[(size_t)b] = 1;
+    return PCR_OK;
+}
+
+int pcr_batch_point_bounds(pcr_ctx *c, int64_t first_batch, int64_t count, int32_t *host_bounds)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int64_t n = 0;
+    int rc = select_range(c, first_batch, count, &n);
+    if (rc || n == 0) return rc;
+    if (!host_bounds) return set_err(c, PCR_E_ARG, "the destination is NULL");
+    if ((rc = ensure_point_bounds(c, first_batch, n))) return rc;
+    std::memcpy(host_bounds, c->h_point_bounds.data() + first_batch * 6, (size_t)n * 6 * sizeof(int32_t));
+    return PCR_OK;
+}
+
+namespace {
+enum : int8_t { SEL_OUTSIDE = 0, SEL_INSIDE = 1, SEL_STRADDLING = 2 };
+
+// What a selection over batches [first, first + n) has to write: the class of every batch, its record count, and for the
+// straddling ones (slot = position among them; their per-chain counts sit in c->d_sel_counts) the batch index.
+struct SelectPlan {
+    std::vector<int8_t> cls;
+    std::vector<int64_t> cnt;
+    std::vector<uint32_t> strad;        // batch indices of the straddling batches, ascending
+    std::vector<int64_t> offsets;       // staging of k_select_write's offsets (alive until the stream has been synchronised)
+    pcr_select_stats st{};
+};
+
+bool box_empty(const pcr_box &q) { return q.min[0] > q.max[0] || q.min[1] > q.max[1] || q.min[2] > q.max[2]; }
+
+// Classify (host, from the cached exact boxes) and count the straddling batches (k_select_count). Synchronises.
+int select_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_box &q, SelectPlan &p)
+{
+    p.cls.assign((size_t)n, SEL_OUTSIDE); p.cnt.assign((size_t)n, 0); p.strad.clear();
+    p.st = pcr_select_stats{n, 0, 0, 0};
+    if (n == 0 || box_empty(q)) return PCR_OK;
+    int rc;
+    if ((rc = ensure_point_bounds(c, first, n))) return rc;
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t *bb = c->h_point_bounds.data() + (first + i) * 6;
+        bool disjoint = false, within = true;
+        for (int k = 0; k < 3; ++k) {
+            disjoint = disjoint || bb[3 + k] < q.min[k] || bb[k] > q.max[k];
+            within = within && bb[k] >= q.min[k] && bb[3 + k] <= q.max[k];
+        }
+        if (disjoint) continue;
+        --p.st.batches_outside;
+        if (within) { p.cls[(size_t)i] = SEL_INSIDE; p.cnt[(size_t)i] = PCR_POINTS_PER_BATCH; ++p.st.batches_inside; }
+        else { p.cls[(size_t)i] = SEL_STRADDLING; p.strad.push_back((uint32_t)(first + i)); ++p.st.batches_straddling; }
+    }
+    const int64_t nS = (int64_t)p.strad.size();
+    if (nS) {
+        if (c->sel_capacity < nS) {
+            dfree(c->d_sel_list); dfree(c->d_sel_counts); dfree(c->d_sel_totals); dfree(c->d_sel_offsets); c->sel_capacity = 0;
+            if (hipMalloc((void **)&c->d_sel_list, (size_t)nS * 4) != hipSuccess || hipMalloc((void **)&c->d_sel_totals, (size_t)nS * 4) != hipSuccess ||
+                hipMalloc((void **)&c->d_sel_offsets, (size_t)nS * 8) != hipSuccess ||
+                hipMalloc((void **)&c->d_sel_counts, (size_t)nS * PCR_WORKGROUP_SIZE * 4) != hipSuccess)
+                return set_err(c, PCR_E_NOMEM, "out of device memory for the counts of %lld straddling batches", (long long)nS);
+            c->sel_capacity = nS;
+        }
+        HIP_TRY(c, hipMemcpyAsync(c->d_sel_list, p.strad.data(), (size_t)nS * 4, hipMemcpyHostToDevice, c->stream));
+        const StreamView s = make_stream_view(c);
+        const dim3 grid((unsigned)nS), block(PCR_WORKGROUP_SIZE);
+        if (select_reads_windows(c)) hipLaunchKernelGGL((k_select_count<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_sel_list, q, c->d_sel_counts, c->d_sel_totals);
+        else                         hipLaunchKernelGGL((k_select_count<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_sel_list, q, c->d_sel_counts, c->d_sel_totals);
+        HIP_TRY(c, hipGetLastError());
+        std::vector<uint32_t> totals((size_t)nS);
+        HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_sel_totals, (size_t)nS * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (int64_t k = 0; k < nS; ++k) p.cnt[(size_t)(p.strad[(size_t)k] - first)] = totals[(size_t)k];
+    }
+    for (int64_t i = 0; i < n; ++i) p.st.points_selected += p.cnt[(size_t)i];
+    return PCR_OK;
+}
+
+// Enqueue the writes of batches [i0, i1) of the plan's range to `out` (device, holds their records): runs of inside batches
+// through k_decode_points, the straddling ones through one k_select_write launch. The caller synchronises.
+int select_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, const pcr_box &q, SelectPlan &p, uint4 *out)
+{
+    int rc;
+    const size_t s0 = (size_t)(std::lower_bound(p.strad.begin(), p.strad.end(), (uint32_t)(first + i0)) - p.strad.begin());
+    p.offsets.clear();
+    int64_t off = 0;
+    for (int64_t i = i0; i < i1; ) {
+        if (p.cls[(size_t)i] == SEL_INSIDE) {
+            int64_t e = i;
+            while (e < i1 && p.cls[(size_t)e] == SEL_INSIDE) ++e;
+            if ((rc = launch_decode(c, first + i, e - i, out + off))) return rc;
+            off += (e - i) * PCR_POINTS_PER_BATCH;
+            i = e;
+            continue;
+        }
+        if (p.cls[(size_t)i] == SEL_STRADDLING) { p.offsets.push_back(off); off += p.cnt[(size_t)i]; }
+        ++i;
+    }
+    const size_t nS = p.offsets.size();
+    if (nS) {
+        HIP_TRY(c, hipMemcpyAsync(c->d_sel_offsets + s0, p.offsets.data(), nS * 8, hipMemcpyHostToDevice, c->stream));
+        const StreamView s = make_stream_view(c);
+        const dim3 grid((unsigned)nS), block(PCR_WORKGROUP_SIZE);
+        const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
+#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_select_write<L, B>), grid, block, 0, c->stream, s, c->d_sel_list + s0, q, \
+                                            c->d_sel_counts + s0 * PCR_WORKGROUP_SIZE, c->d_sel_offsets + s0, out)
+        if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
+        else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+#undef PCR_LAUNCH
+        HIP_TRY(c, hipGetLastError());
+    }
+    return PCR_OK;
+}
+
+// The checks and the plan shared by pcr_select_box / pcr_read_box. *done: nothing left to write (an error, a count-only call,
+// no records).
+int select_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_box *box, const void *dst, size_t dst_align, size_t capacity,
+                   int64_t *out_count, pcr_select_stats *stats, int64_t *n, SelectPlan &p, bool *done)
+{
+    *done = true;
+    if (out_count) *out_count = 0;
+    int rc = select_range(c, first, count, n);
+    if (rc) return rc;
+    if (!box) return set_err(c, PCR_E_ARG, "the box is NULL");
+    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
+    if (dst && reinterpret_cast<uintptr_t>(dst) % dst_align != 0) return set_err(c, PCR_E_ARG, "the destination is misaligned (%zu bytes)", dst_align);
+    if ((rc = select_plan(c, first, *n, *box, p))) return rc;
+    *out_count = p.st.points_selected;
+    if (stats) *stats = p.st;
+    if (!dst || p.st.points_selected == 0) return PCR_OK;
+    if (capacity < (size_t)p.st.points_selected)
+        return set_err(c, PCR_E_ARG, "capacity of %zu points is below the %lld selected", capacity, (long long)p.st.points_selected);
+    *done = false;
+    return PCR_OK;
+}
+} // namespace
+
+int pcr_select_box(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_box *box, void *dev_points, size_t capacity_points,
+                   int64_t *out_count, pcr_select_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    SelectPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = select_prepare(c, first_batch, count, box, dev_points, 16, capacity_points, out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    if ((rc = select_emit(c, first_batch, 0, n, *box, p, static_cast<uint4 *>(dev_points)))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+int pcr_read_box(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_box *box, pcr_point *host, size_t capacity_points,
+                 int64_t *out_count, pcr_select_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    SelectPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = select_prepare(c, first_batch, count, box, host, alignof(pcr_point), capacity_points, out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    // pieces of at most DECODE_STAGE_BATCHES batches: a batch selects at most 65 536 records, so a piece fits the staging buffer
+    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
+    if (!c->d_decode_stage || c->decode_stage_batches < piece) {
+        dfree(c->d_decode_stage); c->decode_stage_batches = 0;
+        if (hipMalloc((void **)&c->d_decode_stage, (size_t)piece * PCR_POINTS_PER_BATCH * sizeof(pcr_point)) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of points", (long long)piece);
+        c->decode_stage_batches = piece;
+    }
+    int64_t written = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += piece) {
+        const int64_t i1 = std::min(n, i0 + piece);
+        int64_t m = 0;
+        for (int64_t i = i0; i < i1; ++i) m += p.cnt[(size_t)i];
+        if (m == 0) continue;
+        if ((rc = select_emit(c, first_batch, i0, i1, *box, p, reinterpret_cast<uint4 *>(c->d_decode_stage)))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(host + written, c->d_decode_stage, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        written += m;
     }
     return PCR_OK;
 }

@@ -1998,6 +1998,231 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_decode_points(StreamView
 }
 
 // ------------------------------------------------------------------------------------------------
+// Box selection (pcr_batch_point_bounds / pcr_select_box): the points of a range of batches that lie inside an axis-aligned
+// box of the stream's int32 coordinates, as k_decode_points would write them with the records outside the box removed.
+//   k_point_bounds  once per batch (cached by the context): the exact integer box of the 65 536 records k_decode_points writes
+//                   for it, garbage tails and padding included -- pcr_gpu_batch::min/max and the k_bounds boxes are float hints
+//   k_select_count  per batch that straddles the box: how many of each chain's 64 points are inside, and their sum
+//   k_select_write  per straddling batch: a workgroup prefix over those 1024 counts, then every chain writes its selected
+//                   records consecutively from its offset (batches wholly inside go through k_decode_points)
+// The three share decode_chain(): k_decode_points' point loop restated with a sink per point instead of the staged write-back
+// (k_decode_points itself is left as it is: its schedule was tuned around the staging). Without colours and staging a workgroup
+// needs the 16 KiB table and a few hundred bytes of LDS, so several fit a CU. No workgroup waits for another one: the offsets
+// between batches are a prefix sum on the host, which has to learn the count anyway.
+// ------------------------------------------------------------------------------------------------
+enum { SEL_NO_COLOUR = 0, SEL_BC1 = 1, SEL_BC7 = 2 };
+
+// All 64 points of chain `tid` of batch b, in order: sink(i, x, y, z, colour) (colour 0 with SEL_NO_COLOUR). s_table holds the
+// batch's packed table and is visible to the workgroup. The reads are k_decode_points' (see there).
+template <int LAYOUT, int COLOUR, class Sink>
+__device__ __forceinline__ void decode_chain(const StreamView &s, uint32_t b, const uint32_t *s_table, Sink &&sink)
+{
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const pcr_gpu_batch *gb = s.batches + b;
+    const int32_t *sep = s.separate + gb->separate_batch_offset;
+    const uint32_t sep_last = (uint32_t)min((int64_t)0x7FFFFFF0, s.separate_words + (PCR_GUARD_WORDS - 2) - gb->separate_batch_offset);
+    const int32_t *tvalues = s.table_values + (size_t)b * PCR_HUFFMAN_TABLE_SIZE;     // only for `wide` entries
+    uint32_t esc = tid ? (uint32_t)s.separate_sizes[(size_t)b * 1024 + tid - 1] : 0u;
+    const int32_t *sv = s.start_values + ((size_t)b * 1024 + tid) * 3;
+    int32_t px = sv[0], py = sv[1], pz = sv[2];
+
+    typedef const __attribute__((address_space(1))) char *global_bytes;
+    global_bytes lwb = nullptr;
+    uint32_t lwo = lane * 4;
+    auto lw_load = [&](uint32_t byte_off) -> uint32_t { return *(const __attribute__((address_space(1))) uint32_t *)(lwb + byte_off); };
+    uint32_t w0 = 0, w1 = 0, w2 = 0, far0 = 0, far1 = 0, spare = 0;
+    const uint32_t *pw_hi = nullptr;
+    const uint8_t *pw_lo = nullptr;
+    uint32_t win_hi[2] = {0, 0}, win_lo[2] = {0, 0};
+    if (LAYOUT == LAYOUT_WORDS) {
+        const uint32_t *wr = s.lw_wave_row + (size_t)b * (LWC_WAVES + 1) + wave;
+        lwb = (global_bytes)(reinterpret_cast<const char *>(s.lw_block[b]) + (size_t)wr[0] * LWC_ROW_BYTES);
+        w1 = lw_load(lwo); w2 = lw_load(lwo + LWC_ROW_BYTES);
+        far0 = lw_load(lwo + 2 * LWC_ROW_BYTES); far1 = lw_load(lwo + 3 * LWC_ROW_BYTES);
+        lwo += 2 * LWC_ROW_BYTES;
+    } else {
+        pw_hi = reinterpret_cast<const uint32_t *>(s.point_windows + (size_t)b * PW_BATCH_BYTES) + tid;
+        pw_lo = s.point_windows + (size_t)b * PW_BATCH_BYTES + PW_HI_BYTES + tid;
+        win_hi[0] = pw_hi[0]; win_lo[0] = pw_lo[0];
+        win_hi[1] = pw_hi[PCR_WORKGROUP_SIZE]; win_lo[1] = pw_lo[PCR_WORKGROUP_SIZE];
+    }
+
+    const uint2 *blocks1 = reinterpret_cast<const uint2 *>(s.colors_t) + ((size_t)b * 4096 + tid);
+    const uint4 *blocks7 = reinterpret_cast<const uint4 *>(s.colors_t) + ((size_t)b * 4096 + tid);
+    uint2 next1 = make_uint2(0, 0);
+    uint4 next7 = make_uint4(0, 0, 0, 0);
+    if (COLOUR == SEL_BC7) next7 = blocks7[0]; else if (COLOUR == SEL_BC1) next1 = blocks1[0];
+
+    int32_t qa0 = sep[min(esc, sep_last)], qa1 = sep[min(esc + 1u, sep_last)], qa2 = sep[min(esc + 2u, sep_last)];
+    int32_t qb0 = sep[min(esc + 3u, sep_last)], qb1 = sep[min(esc + 4u, sep_last)], qb2 = sep[min(esc + 5u, sep_last)];
+    uint32_t esc_prev = 0;
+
+#pragma unroll 1
+    for (int seg = 0; seg < PCR_POINTS_PER_THREAD / 16; ++seg) {
+        Bc1Palette pal = {0, 0, 0, 0};
+        Bc7Block pal7 = {0, 0, 0, 0, 0};
+        const int seg_next = min(seg + 1, PCR_POINTS_PER_THREAD / 16 - 1);
+        if (COLOUR == SEL_BC7) { pal7 = bc7_block(next7); next7 = blocks7[(size_t)seg_next * PCR_WORKGROUP_SIZE]; }
+        else if (COLOUR == SEL_BC1) { pal = bc1_palette(next1); next1 = blocks1[(size_t)seg_next * PCR_WORKGROUP_SIZE]; }
+#pragma unroll 1
+        for (int half = 0; half < 2; ++half) {
+            const int i0 = seg * 16 + half * 8;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int32_t c0 = sep[min(esc + 3u, sep_last)], c1 = sep[min(esc + 4u, sep_last)], c2 = sep[min(esc + 5u, sep_last)];
+                uint64_t bits;
+                if (LAYOUT == LAYOUT_WORDS) {
+                    bits = ((uint64_t)__builtin_amdgcn_alignbit(w0, w1, spare) << 32) | __builtin_amdgcn_alignbit(w1, w2, spare);
+                } else {
+                    bits = ((uint64_t)win_hi[0] << 32) | (win_lo[0] << 24);
+                    win_hi[0] = win_hi[1]; win_lo[0] = win_lo[1];
+                    const uint32_t r = (uint32_t)min(i0 + j + 2, PW_ROWS - 1);
+                    win_hi[1] = pw_hi[(size_t)r * PCR_WORKGROUP_SIZE]; win_lo[1] = pw_lo[(size_t)r * PCR_WORKGROUP_SIZE];
+                }
+                const uint32_t hi = (uint32_t)(bits >> 32);
+                const uint32_t k0 = hi >> 20, e0 = s_table[k0];
+                const uint32_t l0 = e0 & 63u;
+                const uint32_t k1 = ((hi << (l0 & 31u)) >> 20), e1 = s_table[k1];
+                const uint32_t l01 = l0 + (e1 & 63u);
+                const uint32_t k2 = (uint32_t)((bits << (l01 & 63u)) >> 52), e2 = s_table[k2];
+                int32_t v0 = (int32_t)e0 >> TE_VALUE_SHIFT, v1 = (int32_t)e1 >> TE_VALUE_SHIFT, v2 = (int32_t)e2 >> TE_VALUE_SHIFT;
+                const int32_t q0 = esc_prev == 0u ? qa0 : esc_prev == 1u ? qa1 : esc_prev == 2u ? qa2 : qb0;
+                const int32_t q1 = esc_prev == 0u ? qa1 : esc_prev == 1u ? qa2 : esc_prev == 2u ? qb0 : qb1;
+                const int32_t q2 = esc_prev == 0u ? qa2 : esc_prev == 1u ? qb0 : esc_prev == 2u ? qb1 : qb2;
+                qa0 = q0; qa1 = q1; qa2 = q2; qb0 = c0; qb1 = c1; qb2 = c2;
+                uint32_t n = 0;
+                if (v0 == TE_SLOW_VALUE) {
+                    if (e0 & TE_ESCAPE) { v0 = q0; n = 1; }
+                    else { v0 = tvalues[k0]; asm volatile("; wide table value from global memory %0" : "+v"(v0)); }
+                }
+                if (v1 == TE_SLOW_VALUE) {
+                    if (e1 & TE_ESCAPE) { v1 = n ? q1 : q0; ++n; }
+                    else { v1 = tvalues[k1]; asm volatile("; wide table value from global memory %0" : "+v"(v1)); }
+                }
+                if (v2 == TE_SLOW_VALUE) {
+                    if (e2 & TE_ESCAPE) { v2 = n == 0 ? q0 : n == 1 ? q1 : q2; ++n; }
+                    else { v2 = tvalues[k2]; asm volatile("; wide table value from global memory %0" : "+v"(v2)); }
+                }
+                esc += n; esc_prev = n;
+                px = (int32_t)((uint32_t)px + (uint32_t)v0);
+                py = (int32_t)((uint32_t)py + (uint32_t)v1);
+                pz = (int32_t)((uint32_t)pz + (uint32_t)v2);
+                if (LAYOUT == LAYOUT_WORDS) {
+                    const uint32_t u = spare + ((64u - l01 - (e2 & 63u)) & 127u);
+                    const uint32_t k = min(u >> 5, 2u);
+                    spare = u & 31u;
+                    const uint32_t n0 = k == 2u ? w0 : k == 1u ? w1 : w2;
+                    const uint32_t n1 = k == 2u ? w1 : k == 1u ? w2 : far0;
+                    const uint32_t n2 = k == 2u ? w2 : k == 1u ? far0 : far1;
+                    w0 = n0; w1 = n1; w2 = n2;
+                    lwo += (2u - k) * LWC_ROW_BYTES;
+                    far0 = lw_load(lwo); far1 = lw_load(lwo + LWC_ROW_BYTES);
+                }
+                const uint32_t colour = COLOUR == SEL_BC7 ? bc7_color(pal7, (uint32_t)(half * 8 + j))
+                                      : COLOUR == SEL_BC1 ? bc1_color(pal, (uint32_t)(half * 8 + j)) : 0u;
+                sink(i0 + j, px, py, pz, colour);
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ void load_packed_table(const StreamView &s, uint32_t b, uint32_t *s_table)
+{
+    reinterpret_cast<uint4 *>(s_table)[threadIdx.x] = reinterpret_cast<const uint4 *>(s.packed_table + (size_t)b * PCR_HUFFMAN_TABLE_SIZE)[threadIdx.x];
+    __syncthreads();
+}
+
+__device__ __forceinline__ bool in_box(const pcr_box &q, int32_t x, int32_t y, int32_t z)
+{
+    return x >= q.min[0] && x <= q.max[0] && y >= q.min[1] && y <= q.max[1] && z >= q.min[2] && z <= q.max[2];
+}
+
+// bounds[(first_batch + blockIdx.x) * 6 ..] = min x, y, z, max x, y, z of the batch's 65 536 decoded records
+template <int LAYOUT>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_point_bounds(StreamView s, int32_t *bounds, uint32_t first_batch)
+{
+    const uint32_t b = first_batch + blockIdx.x;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ int32_t s_part[LWC_WAVES][6];
+    load_packed_table(s, b, s_table);
+    int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t) {
+        lo[0] = min(lo[0], x); lo[1] = min(lo[1], y); lo[2] = min(lo[2], z);
+        hi[0] = max(hi[0], x); hi[1] = max(hi[1], y); hi[2] = max(hi[2], z);
+    });
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            lo[k] = min(lo[k], __shfl_xor(lo[k], d, 64));
+            hi[k] = max(hi[k], __shfl_xor(hi[k], d, 64));
+        }
+        if (lane == 0) { s_part[wave][k] = lo[k]; s_part[wave][3 + k] = hi[k]; }
+    }
+    __syncthreads();
+    if (tid < 6) {
+        int32_t v = s_part[0][tid];
+        for (int w = 1; w < LWC_WAVES; ++w) v = tid < 3 ? min(v, s_part[w][tid]) : max(v, s_part[w][tid]);
+        bounds[(size_t)b * 6 + tid] = v;
+    }
+}
+
+// Workgroup x takes the straddling batch list[x]: chain_counts[x * 1024 + chain] = its points inside q, totals[x] = their sum
+template <int LAYOUT>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_select_count(StreamView s, const uint32_t *list, pcr_box q, uint32_t *chain_counts, uint32_t *totals)
+{
+    const uint32_t b = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint32_t s_part[LWC_WAVES];
+    load_packed_table(s, b, s_table);
+    uint32_t cnt = 0;
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t) { cnt += in_box(q, x, y, z) ? 1u : 0u; });
+    chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid] = cnt;
+    uint32_t sum = cnt;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    if (lane == 0) s_part[wave] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < LWC_WAVES; ++w) t += s_part[w];
+        totals[blockIdx.x] = t;
+    }
+}
+
+// Workgroup x takes the straddling batch list[x]: its selected records go to out[offsets[x] ..], chain after chain, each chain's
+// in point order (k_decode_points' order with the gaps closed). chain_counts is k_select_count's, for the same list and box.
+// The simplest store path: a lane stores its own 16-byte records where they belong.
+template <int LAYOUT, bool BC7>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_select_write(StreamView s, const uint32_t *list, pcr_box q, const uint32_t *chain_counts,
+                                                                     const int64_t *offsets, uint4 *out)
+{
+    const uint32_t b = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint32_t s_part[LWC_WAVES];
+    const uint32_t mine = chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid];
+    uint32_t incl = mine;                                   // inclusive prefix inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += up;
+    }
+    if (lane == 63) s_part[wave] = incl;
+    load_packed_table(s, b, s_table);                       // (its barrier publishes s_part as well)
+    uint32_t before = incl - mine;
+    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    uint4 *dst = out + offsets[blockIdx.x] + before;
+    uint4 *const end = dst + mine;                          // never past what k_select_count counted for this chain
+    decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        if (in_box(q, x, y, z) && dst < end) *dst++ = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
 // 10-10-10 path ("loop_las_cuda", modules/compute_loop_las_cuda/render.cu:130-442)
 //
 // Streaming kernel: one workgroup per batch of 65 536 points, thread t takes the point quads t, t+1024, ... so every

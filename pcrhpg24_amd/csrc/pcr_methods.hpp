@@ -15,6 +15,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -307,6 +308,21 @@ struct HuffmanLasData : Resource {
         loadedOn->check(pcr_read_points(loadedOn->ctx, 0, nB, out.data(), out.size()), "pcr_read_points");
     }
 
+    // The points inside `box` (the stream's int32 coordinates, bounds inclusive) of every batch the context holds right now:
+    // decodePoints() with the records outside the box removed, selected on the GPU (pcr_read_box: batches the box misses are
+    // not decoded). Not in the reference.
+    pcr_select_stats selectBox(const pcr_box &box, std::vector<pcr_point> &out)
+    {
+        if (!loadedOn) throw std::runtime_error("selectBox: the resource is not loaded");
+        const int64_t nB = pcr_batches_resident(loadedOn->ctx);
+        int64_t n = 0;
+        pcr_select_stats st{};
+        loadedOn->check(pcr_read_box(loadedOn->ctx, 0, nB, &box, nullptr, 0, &n, &st), "pcr_read_box");
+        out.resize((size_t)n);
+        if (n) loadedOn->check(pcr_read_box(loadedOn->ctx, 0, nB, &box, out.data(), out.size(), &n, &st), "pcr_read_box");
+        return st;
+    }
+
     // Scale, offset and box of the LAS file the stream was made from, as the first batch record carries them
     // (include/BatchDumpData.h:60-107: doubles at 20 and 44, the LAS box as floats at 92 and 104).
     pcr_las_info lasInfo() const
@@ -373,6 +389,33 @@ struct HuffmanMemIter : HuffmanMethodBase {
         r->check(pcr_resolve_basic(r->ctx, &lastParams), "pcr_resolve_basic");
     }
 };
+
+// The largest int32 box whose points i satisfy lo <= i * scale + offset <= hi on every axis, the expression evaluated in double
+// as written (a product rounded, then a sum rounded: two statements, so no compiler contracts them). floor / ceil of the inverse
+// give a guess, which is then moved by evaluating the expression until the bound and its outer neighbour disagree. An axis no
+// int32 coordinate satisfies makes the box empty (min > max). The Python twin is host.box_from_world.
+inline pcr_box boxFromWorld(const pcr_las_info &las, const double lo[3], const double hi[3])
+{
+    pcr_box b{};
+    for (int k = 0; k < 3; ++k) {
+        const double s = las.scale[k], o = las.offset[k];
+        if (!(s > 0.0) || o != o || lo[k] != lo[k] || hi[k] != hi[k]) throw std::runtime_error("boxFromWorld: needs a positive scale and numbers for offset and bounds");
+        auto f = [&](int64_t i) { const double p = (double)i * s; return p + o; };
+        auto guess = [&](double v, bool up) -> int64_t {
+            const double g = (v - o) / s;
+            return g <= (double)INT32_MIN ? (int64_t)INT32_MIN : g >= (double)INT32_MAX ? (int64_t)INT32_MAX : (int64_t)(up ? std::ceil(g) : std::floor(g));
+        };
+        int64_t a = guess(lo[k], true);
+        while (a > INT32_MIN && f(a - 1) >= lo[k]) --a;
+        while (a <= INT32_MAX && f(a) < lo[k]) ++a;
+        int64_t z = guess(hi[k], false);
+        while (z < INT32_MAX && f(z + 1) <= hi[k]) ++z;
+        while (z >= INT32_MIN && f(z) > hi[k]) --z;
+        if (a > z) { a = 0; z = -1; }
+        b.min[k] = (int32_t)a; b.max[k] = (int32_t)z;
+    }
+    return b;
+}
 
 // modules/huffman_cuda/huffman_cuda.h:60-75: the reference's first Huffman method (class ComputeHuffman, registered as
 // "huffman_cuda"; commented out in its main.cpp:19, 265 in favour of huffman_mem_iter_cuda, whose kernels are the same

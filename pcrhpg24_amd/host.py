@@ -28,7 +28,7 @@ from typing import Iterator, Optional
 import numpy as np
 
 from . import _native as N
-from ._native import EncodeStats, FileHeader, LasInfo, RenderParams, RenderStats, XyzBatch, fb_elems
+from ._native import Box, EncodeStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, XyzBatch, c_i64, fb_elems
 
 POINTS_PER_BATCH = 65536
 ENCODED_PAD_WORDS = 1024
@@ -184,6 +184,56 @@ def read_las(path: str):
 
 
 POINT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("color", "<u4")])     # pcr_point
+
+INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
+
+
+def as_box(box) -> Box:
+    """A pcr_box from a Box, (min xyz, max xyz) or six numbers min x, y, z, max x, y, z (int32, bounds inclusive)."""
+    if isinstance(box, Box):
+        return box
+    v = [int(a) for a in np.asarray(box, dtype=np.int64).reshape(6)]
+    if any(a < INT32_MIN or a > INT32_MAX for a in v):
+        raise ValueError("box coordinates are int32")
+    b = Box()
+    b.min[:], b.max[:] = v[:3], v[3:]
+    return b
+
+
+def box_from_world(las: LasInfo, lo, hi) -> Box:
+    """The largest int32 box whose points i satisfy lo <= i * scale + offset <= hi on every axis, the expression evaluated in
+    float64 exactly as HuffmanLasData.points(world=True) evaluates it (a product rounded, then a sum rounded: monotone in i
+    for a positive scale). ceil / floor of the inverse give a guess; it is then moved by evaluating the expression itself
+    until the bound and its outer neighbour disagree, so no rounding of the inverse can leak a point in or out. An axis no
+    int32 coordinate satisfies makes the box empty (min > max)."""
+    import math
+    b = Box()
+    for k in range(3):
+        s, o, l, h = float(las.scale[k]), float(las.offset[k]), float(lo[k]), float(hi[k])
+        if not s > 0.0 or math.isnan(o) or math.isnan(l) or math.isnan(h):
+            raise ValueError("box_from_world needs a positive scale and numbers for offset and bounds")
+
+        def f(i):
+            return float(i) * s + o
+
+        def guess(v, rnd):
+            g = (v - o) / s
+            return INT32_MIN if g <= INT32_MIN else INT32_MAX if g >= INT32_MAX else int(rnd(g))
+
+        a = guess(l, math.ceil)                             # the smallest i with f(i) >= lo
+        while a > INT32_MIN and f(a - 1) >= l:
+            a -= 1
+        while a <= INT32_MAX and f(a) < l:
+            a += 1
+        z = guess(h, math.floor)                            # the largest i with f(i) <= hi
+        while z < INT32_MAX and f(z + 1) <= h:
+            z += 1
+        while z >= INT32_MIN and f(z) > h:
+            z -= 1
+        if a > z:
+            a, z = 0, -1
+        b.min[k], b.max[k] = a, z
+    return b
 
 
 def write_las(path, x=None, y=None, z=None, color=None, las: Optional[LasInfo] = None, points=None) -> None:
@@ -473,6 +523,51 @@ class Context:
         self._chk(self.lib.pcr_read_points(self.h, first, -1 if count is None else count, out.ctypes.data if n else None, n), "pcr_read_points")
         return out
 
+    # -- box selection (pcr_batch_point_bounds / pcr_select_box / pcr_read_box) ----------------------------
+    def batch_point_bounds(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The exact integer box of the 65 536 records decode_points writes for each batch of the range: int32 [n, 6], columns
+        min x, y, z, max x, y, z (computed on the GPU once per batch, then cached by the context; synchronises)."""
+        n = max(self._decode_count(first, count), 0)
+        out = np.empty((n, 6), np.int32)
+        self._chk(self.lib.pcr_batch_point_bounds(self.h, first, -1 if count is None else count, out.ctypes.data if n else None), "pcr_batch_point_bounds")
+        return out
+
+    def select_box(self, box, first: int = 0, count: Optional[int] = None, out=None):
+        """The points of batches [first, first + count) inside `box` (as_box: a Box or (min xyz, max xyz), int32, inclusive) as
+        a torch.int32 tensor [n, 4] on the context's device: decode_points of the range with the rows outside the box removed.
+        `out`: a contiguous int32 CUDA tensor to fill; it has to hold the result (PcrError if not; select_stats then tells
+        the count). Without it the call counts first and allocates exactly. Stream ordering as decode_points. The batch
+        classes and the count of the last call are in self.select_stats."""
+        import torch
+        box = as_box(box)
+        dev = torch.device("cuda", self.device)
+        cnt, st, nb = c_i64(), N.SelectStats(), -1 if count is None else count
+        if out is None:
+            self._chk(self.lib.pcr_select_box(self.h, first, nb, C.byref(box), None, 0, C.byref(cnt), C.byref(st)), "pcr_select_box")
+            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
+        torch.cuda.current_stream(dev).synchronize()
+        rc = self.lib.pcr_select_box(self.h, first, nb, C.byref(box), C.c_void_p(out.data_ptr() if out.numel() else None), out.numel() // 4,
+                                     C.byref(cnt), C.byref(st))
+        self.select_stats = st.as_dict()
+        if rc:
+            self.select_stats["points_selected"] = cnt.value
+        self._chk(rc, "pcr_select_box")
+        return out.view(-1, 4)[:cnt.value]
+
+    def read_box(self, box, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The same on the host, without torch: a numpy structured array of POINT_DTYPE (pcr_read_box: a counting call, then
+        the read; synchronises)."""
+        box = as_box(box)
+        cnt, st, nb = c_i64(), N.SelectStats(), -1 if count is None else count
+        self._chk(self.lib.pcr_read_box(self.h, first, nb, C.byref(box), None, 0, C.byref(cnt), C.byref(st)), "pcr_read_box")
+        out = np.empty(cnt.value, POINT_DTYPE)
+        if cnt.value:
+            self._chk(self.lib.pcr_read_box(self.h, first, nb, C.byref(box), out.ctypes.data, len(out), C.byref(cnt), C.byref(st)), "pcr_read_box")
+        self.select_stats = st.as_dict()
+        return out
+
     def stats(self) -> dict:
         st = RenderStats()
         self._chk(self.lib.pcr_get_stats(self.h, C.byref(st)), "pcr_get_stats")
@@ -751,6 +846,21 @@ class HuffmanLasData(Resource):
         so = torch.from_numpy(so).to(pts.device)
         xyz = pts[:, :3].view(nb, POINTS_PER_BATCH, 3).to(torch.float64) * so[:, None, 0, :] + so[:, None, 1, :]
         return xyz.view(-1, 3), pts
+
+    def points_in_box(self, renderer: Renderer, lo, hi, world: bool = True):
+        """The points of the loaded resource inside a box, selected on the GPU (Context.select_box): what points() returns with the
+        rows outside the box removed, without decoding the batches the box misses. world=True: lo / hi are world coordinates,
+        turned into the largest integer box by box_from_world with las_info()'s scale and offset (the stream's: the reference's
+        encoder writes the same into every batch record), and the result is (xyz, pts) as points(world=True) returns it.
+        world=False: lo / hi are the stream's int32 coordinates, the result the int32 tensor alone."""
+        import torch
+        info = self.las_info()
+        box = box_from_world(info, lo, hi) if world else as_box((lo, hi))
+        pts = renderer.ctx.select_box(box)
+        if not world:
+            return pts
+        so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
+        return pts[:, :3].to(torch.float64) * so[0] + so[1], pts
 
     def las_info(self) -> LasInfo:
         """Scale, offset, min and max of the LAS file the stream was made from, as its first batch record carries them (the
