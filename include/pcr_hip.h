@@ -188,6 +188,46 @@ int pcr_select_box(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_b
 int pcr_read_box(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_box *box, pcr_point *host, size_t capacity_points,
                  int64_t *out_count, pcr_select_stats *stats);
 
+/* ---- screen selection and picking: which points does a frame show, and where (no reference counterpart) -----------------------
+ * CONTRACT of pcr_select_screen: the selected points are exactly those pcr_render_basic(params) scatters -- the batches its
+ * cull/LOD prepass keeps, of each chain the first points by the prepass's level of detail, each batch dequantised in the
+ * precision (f32 / f64) the prepass chose, and of those the points that pass the kernel's inside test (w > 0, NaNs rejected,
+ * pixel index below pcr_fb_elems) -- whose pixel lies in *rect. (The basic method's LOD expression is used for every stream, a
+ * BC7 stream included, which pcr_render_basic itself refuses; the HQS passes round one division differently and agree except
+ * on a batch exactly at a level's edge.) hit.pixel and hit.depth_bits are bit-identical to what the render kernel computes for
+ * the point: for a BC1 stream, the minimum of depth_bits << 32 | colour over the hits of a pixel is the word pcr_render_basic
+ * leaves there. params are checked as a render call checks them (pcr_set_image_size first); show_num_points and
+ * colorize_chunks have no effect.
+ * rect: pixel bounds, inclusive, clipped to the image [0, width) x [0, height); NULL = the whole image. Column and row of a
+ * point are those of its pixel index (pixel % width, pixel / width), so the few points at ndc == 1.0, which the kernels
+ * scatter to column `width` = column 0 of the next row, are found there, and those in the framebuffer's extra row `height` are
+ * in no rect.
+ * dev_points gets the 16-byte records pcr_decode_points writes for the selected points, dev_hits the parallel pcr_screen_hit
+ * array; both in increasing hit.index order, packed without gaps; capacity counts records of each. Either may be NULL to skip
+ * that array, both NULL only counts. A capacity below the result: PCR_E_ARG, *out_count = the count needed, nothing written.
+ * An empty rect or no resident batches: 0 records, PCR_OK. BC1 and BC7, either resident layout (PCR_LAYOUT_BOTH follows
+ * pcr_set_render_variant, AUTO: the point windows), before and after the first frame; with pcr_set_async_upload on, the
+ * batches the next frame would draw. Synchronises. Touches no framebuffer and no render statistics, and leaves the prepass
+ * state of a pending pcr_frame_begin as it is (the cull/LOD decision is recomputed into an array of the selection's own).
+ * Batches are skipped by the prepass's cull alone: no exact screen box per batch is at hand (pcr_gpu_batch::min/max do not
+ * cover the tail artefact), so every kept batch is decoded whatever the rect.
+ * pcr_read_screen: the same into host memory (either pointer may be NULL), staged through the context's decode staging buffer.
+ * PCR_E_ARG with a message: what a render call refuses, a NULL out_count, a misaligned pointer (16 bytes on the device).
+ *
+ * pcr_pick: the window is the square of `radius` pixels around (px, py), clipped to the image; among the hits of
+ * pcr_select_screen in it the winner is the least by (depth_bits, colour, index). *out_found = 0: no point in the window (not
+ * an error; (px, py) outside the image with a window that misses it entirely is that case too). out_point / out_hit may be
+ * NULL. For a BC1 stream and radius 0, depth_bits << 32 | colour of the winner is the word pcr_render_basic leaves at the
+ * pixel. Scratch memory is a few words whatever the number of candidates: k_pick<key> takes the 64-bit minimum of
+ * depth << 32 | colour, k_pick<index> the minimum index among the points that hold it, k_pick_fetch returns the record.
+ * radius < 0: PCR_E_ARG. Synchronises; state as pcr_select_screen. */
+int pcr_select_screen(pcr_ctx *ctx, const pcr_render_params *params, const pcr_rect *rect, void *dev_points, void *dev_hits,
+                      size_t capacity, int64_t *out_count, pcr_screen_stats *stats);
+int pcr_read_screen(pcr_ctx *ctx, const pcr_render_params *params, const pcr_rect *rect, pcr_point *host_points,
+                    pcr_screen_hit *host_hits, size_t capacity, int64_t *out_count, pcr_screen_stats *stats);
+int pcr_pick(pcr_ctx *ctx, const pcr_render_params *params, int px, int py, int radius, pcr_point *out_point,
+             pcr_screen_hit *out_hit, int *out_found);
+
 /* What a collective library needs to merge partial frames in place (include/pcr_dist.h does it with RCCL): the HIP stream
  * the context enqueues on, its device ordinal and the length of each framebuffer in 64-bit words. */
 void *pcr_get_stream(pcr_ctx *ctx);

@@ -134,6 +134,30 @@ typedef struct pcr_select_stats {
     int64_t points_selected;
 } pcr_select_stats;
 
+/* A rectangle of pixels (pcr_select_screen), bounds inclusive, clipped to the image by the call. x0 > x1 or y0 > y1: the
+ * empty rect. */
+typedef struct pcr_rect {
+    int32_t x0, y0, x1, y1;
+} pcr_rect;
+
+/* Where a selected point lands in a frame of the given camera (pcr_select_screen / pcr_pick), 16 bytes. */
+typedef struct pcr_screen_hit {
+    uint32_t pixel;        /* x + y * width: exactly the index the render kernels scatter to */
+    uint32_t depth_bits;   /* f32 bits of w: the high half of the framebuffer key */
+    int64_t  index;        /* record index in pcr_decode_points order, relative to batch 0 of the context */
+} pcr_screen_hit;
+
+/* What a screen selection did (pcr_select_screen / pcr_read_screen / pcr_pick): the resident batches the cull/LOD prepass
+ * drops for this camera (culled, or no point to draw: not decoded), the batches decoded, the points projected and tested
+ * (1024 x the level of detail's points per chain, summed over the decoded batches) and the records selected, which is the
+ * call's *out_count. (pcr_select_stats' classes -- outside / inside / straddling a box -- do not describe this.) */
+typedef struct pcr_screen_stats {
+    int64_t batches_skipped;
+    int64_t batches_decoded;
+    int64_t points_tested;
+    int64_t points_selected;
+} pcr_screen_stats;
+
 /* Number of u64 elements a framebuffer of w x h must hold: ndc == 1.0 maps to column w / row h
  * (SURVEY Appendix C.2), so pixel ids reach w*(h+1). */
 static inline size_t pcr_fb_elems(int w, int h) { return (size_t)w * (size_t)(h + 1) + 1; }

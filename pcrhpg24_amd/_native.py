@@ -68,6 +68,21 @@ class SelectStats(C.Structure):                   # pcr_select_stats
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class Rect(C.Structure):                          # pcr_rect: pixel bounds, inclusive; x0 > x1 or y0 > y1 = empty
+    _fields_ = [(n, c_i32) for n in ("x0", "y0", "x1", "y1")]
+
+
+class ScreenHit(C.Structure):                     # pcr_screen_hit: where a selected point lands in the frame, 16 bytes
+    _fields_ = [("pixel", c_u32), ("depth_bits", c_u32), ("index", c_i64)]
+
+
+class ScreenStats(C.Structure):                   # pcr_screen_stats
+    _fields_ = [(n, c_i64) for n in ("batches_skipped", "batches_decoded", "points_tested", "points_selected")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class EncodeStats(C.Structure):                   # pcr_encode_stats
     _fields_ = [(n, c_i64) for n in ("num_points_in", "num_points", "num_batches", "encoded_bytes", "separate_bytes",
                                      "cluster_bytes", "escaped_symbols", "total_symbols", "file_bytes")]
@@ -77,6 +92,7 @@ class EncodeStats(C.Structure):                   # pcr_encode_stats
 
 
 assert C.sizeof(Point) == 16 and C.sizeof(Box) == 24 and C.sizeof(SelectStats) == 32
+assert C.sizeof(Rect) == 16 and C.sizeof(ScreenHit) == 16 and C.sizeof(ScreenStats) == 32
 assert C.sizeof(XyzBatch) == 64 and C.sizeof(GpuBatch) == 160 and C.sizeof(FileHeader) == 40 and C.sizeof(RenderParams) == 224
 
 
@@ -98,6 +114,7 @@ HIP_SYMBOLS = [
     "pcr_las_algorithmic_bytes", "pcr_gpu_encode_points", "pcr_gpu_encode_free",
     "pcr_decode_points", "pcr_read_points",
     "pcr_batch_point_bounds", "pcr_select_box", "pcr_read_box",
+    "pcr_select_screen", "pcr_read_screen", "pcr_pick",
 ]
 
 HOST_SYMBOLS = [
@@ -209,6 +226,10 @@ def hip_lib() -> C.CDLL:
         lib.pcr_batch_point_bounds.argtypes = [C.c_void_p, c_i64, c_i64, C.c_void_p]
         for n in ("pcr_select_box", "pcr_read_box"):
             getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Box), C.c_void_p, C.c_size_t, C.POINTER(c_i64), C.POINTER(SelectStats)]
+        for n in ("pcr_select_screen", "pcr_read_screen"):
+            getattr(lib, n).argtypes = [C.c_void_p, C.POINTER(RenderParams), C.POINTER(Rect), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(c_i64),
+                                        C.POINTER(ScreenStats)]
+        lib.pcr_pick.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_int, C.c_int, C.c_int, C.POINTER(Point), C.POINTER(ScreenHit), C.POINTER(C.c_int)]
         _hip = lib
     return _hip
 

@@ -133,6 +133,15 @@ struct pcr_ctx {
     uint32_t *d_sel_counts = nullptr;           // [sel_capacity * 1024] selected points per chain (k_select_count)
     uint32_t *d_sel_totals = nullptr;           // [sel_capacity] ... and per batch
     int64_t *d_sel_offsets = nullptr;           // [sel_capacity] first output record of each (k_select_write)
+    // screen selection and picking (pcr_select_screen / pcr_pick): the cull/LOD words of the call's camera in an array of their own
+    // (k_screen_lod; the frame's d_lod, lists and plans are not touched), and the scratch of the kept batches
+    uint32_t *d_screen_lod = nullptr;           // [hdr.num_batches]
+    int64_t scr_capacity = 0;                   // kept batches the four arrays below hold
+    ScreenEntry *d_scr_list = nullptr;          // [scr_capacity] batch and LOD word
+    uint32_t *d_scr_counts = nullptr;           // [scr_capacity * 1024] selected points per chain (k_screen_count)
+    uint32_t *d_scr_totals = nullptr;           // [scr_capacity] ... and per batch
+    int64_t *d_scr_offsets = nullptr;           // [scr_capacity] first output record of each (k_screen_write)
+    unsigned long long *d_pick = nullptr;       // [PICK_WORDS] pcr_pick: key, index, record, hit
     int64_t prepass_batches = 0;
     static constexpr int FENCES = 8;
     hipEvent_t fence[FENCES] = {};              // pcr_fence_record / pcr_fence_wait: device-scope ordering between streams
@@ -228,6 +237,8 @@ void free_stream_buffers(pcr_ctx *c)
     dfree(c->d_order); dfree(c->d_chunk_count); dfree(c->d_any_generic); c->order_stride = 0;
     dfree(c->d_point_bounds); c->h_point_bounds.clear(); c->h_point_bounds_ok.clear();
     dfree(c->d_sel_list); dfree(c->d_sel_counts); dfree(c->d_sel_totals); dfree(c->d_sel_offsets); c->sel_capacity = 0;
+    dfree(c->d_screen_lod); dfree(c->d_scr_list); dfree(c->d_scr_counts); dfree(c->d_scr_totals); dfree(c->d_scr_offsets); c->scr_capacity = 0;
+    dfree(c->d_pick);
 
     if (c->any_generic_pending && c->any_generic_ev) (void)hipEventSynchronize(c->any_generic_ev);
     c->any_generic_pending = false;
@@ -1705,6 +1716,220 @@ int pcr_read_box(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_box *
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         written += m;
     }
+    return PCR_OK;
+}
+
+// ---- screen selection and picking --------------------------------------------------------------
+namespace {
+// What a screen selection has to write: the batches the prepass keeps for the camera (ascending, with their LOD words; their
+// per-chain counts sit in c->d_scr_counts in the same order) and each one's record count.
+struct ScreenPlan {
+    std::vector<ScreenEntry> kept;
+    std::vector<int64_t> cnt;
+    std::vector<int64_t> offsets;       // staging of k_screen_write's offsets (alive until the stream has been synchronised)
+    ScreenArgs q{};
+    pcr_screen_stats st{};
+};
+
+// The rect clipped to the image into q; false: nothing is left of it.
+bool screen_clip(const pcr_render_params *p, int64_t x0, int64_t y0, int64_t x1, int64_t y1, ScreenArgs &q)
+{
+    x0 = std::max<int64_t>(x0, 0); y0 = std::max<int64_t>(y0, 0);
+    x1 = std::min<int64_t>(x1, p->width - 1); y1 = std::min<int64_t>(y1, p->height - 1);
+    if (x0 > x1 || y0 > y1) return false;
+    q.x0 = (int32_t)x0; q.y0 = (int32_t)y0; q.x1 = (int32_t)x1; q.y1 = (int32_t)y1;
+    return true;
+}
+
+// The kept batches of the camera (k_screen_lod, read back: synchronises) and the scratch for them. nB resident batches, > 0.
+int screen_list(pcr_ctx *c, const pcr_render_params *p, int64_t nB, ScreenPlan &pl)
+{
+    int rc;
+    // (as a frame: the provisional last batch of a stream that is still loading is walked here if no frame has done so)
+    if (!c->async_upload && (rc = enqueue_transcode(c, true, c->stream))) return rc;
+    std::memcpy(pl.q.m, p->transform, sizeof pl.q.m);
+    pl.q.width = p->width; pl.q.height = p->height; pl.q.fb_elems = (uint32_t)c->fb_elems;
+    if (!c->d_screen_lod) HIP_TRY(c, hipMalloc((void **)&c->d_screen_lod, (size_t)c->hdr.num_batches * sizeof(uint32_t)));
+    const RenderArgs a = make_args(c, p, 0);                // the basic method's LOD expression; only a.p and a.s.batches are read
+    hipLaunchKernelGGL(k_screen_lod, dim3((unsigned)((nB + PREPASS_BATCHES - 1) / PREPASS_BATCHES)), dim3(PREPASS_THREADS), 0, c->stream, a, c->d_screen_lod);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint32_t> lod((size_t)nB);
+    HIP_TRY(c, hipMemcpyAsync(lod.data(), c->d_screen_lod, (size_t)nB * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    pl.kept.clear();
+    for (int64_t b = 0; b < nB; ++b) {
+        const uint32_t w = lod[(size_t)b];
+        if ((w & LOD_CULLED) || !(w & LOD_NPR_MASK)) continue;
+        pl.kept.push_back(ScreenEntry{(uint32_t)b, w});
+        pl.st.points_tested += (int64_t)(w & LOD_NPR_MASK) * PCR_WORKGROUP_SIZE;
+    }
+    const int64_t nK = (int64_t)pl.kept.size();
+    pl.st.batches_decoded = nK; pl.st.batches_skipped = nB - nK;
+    if (nK == 0) return PCR_OK;
+    if (c->scr_capacity < nK) {
+        dfree(c->d_scr_list); dfree(c->d_scr_counts); dfree(c->d_scr_totals); dfree(c->d_scr_offsets); c->scr_capacity = 0;
+        if (hipMalloc((void **)&c->d_scr_list, (size_t)nK * sizeof(ScreenEntry)) != hipSuccess || hipMalloc((void **)&c->d_scr_totals, (size_t)nK * 4) != hipSuccess ||
+            hipMalloc((void **)&c->d_scr_offsets, (size_t)nK * 8) != hipSuccess ||
+            hipMalloc((void **)&c->d_scr_counts, (size_t)nK * PCR_WORKGROUP_SIZE * 4) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for the counts of %lld batches", (long long)nK);
+        c->scr_capacity = nK;
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->d_scr_list, pl.kept.data(), (size_t)nK * sizeof(ScreenEntry), hipMemcpyHostToDevice, c->stream));
+    return PCR_OK;
+}
+
+// Count the kept batches' selected points (k_screen_count). Synchronises.
+int screen_count(pcr_ctx *c, ScreenPlan &pl)
+{
+    const int64_t nK = (int64_t)pl.kept.size();
+    pl.cnt.assign((size_t)nK, 0);
+    if (nK == 0) return PCR_OK;
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)nK), block(PCR_WORKGROUP_SIZE);
+    if (select_reads_windows(c)) hipLaunchKernelGGL((k_screen_count<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_scr_list, pl.q, c->d_scr_counts, c->d_scr_totals);
+    else                         hipLaunchKernelGGL((k_screen_count<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_scr_list, pl.q, c->d_scr_counts, c->d_scr_totals);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint32_t> totals((size_t)nK);
+    HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_scr_totals, (size_t)nK * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int64_t k = 0; k < nK; ++k) { pl.cnt[(size_t)k] = totals[(size_t)k]; pl.st.points_selected += totals[(size_t)k]; }
+    return PCR_OK;
+}
+
+// Enqueue the writes of kept batches [k0, k1) to points / hits (device, either may be NULL; record 0 = the first of batch k0).
+// The caller synchronises.
+int screen_emit(pcr_ctx *c, ScreenPlan &pl, int64_t k0, int64_t k1, uint4 *points, uint4 *hits)
+{
+    pl.offsets.clear();
+    int64_t off = 0;
+    for (int64_t k = k0; k < k1; ++k) { pl.offsets.push_back(off); off += pl.cnt[(size_t)k]; }
+    if (off == 0) return PCR_OK;
+    HIP_TRY(c, hipMemcpyAsync(c->d_scr_offsets + k0, pl.offsets.data(), (size_t)(k1 - k0) * 8, hipMemcpyHostToDevice, c->stream));
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)(k1 - k0)), block(PCR_WORKGROUP_SIZE);
+    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
+#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_screen_write<L, B>), grid, block, 0, c->stream, s, c->d_scr_list + k0, pl.q, \
+                                            c->d_scr_counts + k0 * PCR_WORKGROUP_SIZE, c->d_scr_offsets + k0, points, hits)
+    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
+    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+#undef PCR_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    return PCR_OK;
+}
+
+// The checks and the plan shared by pcr_select_screen / pcr_read_screen. *done: nothing left to write (an error, a count-only
+// call, no records).
+int screen_prepare(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect, const void *points, const void *hits, size_t align_points,
+                   size_t align_hits, size_t capacity, int64_t *out_count, pcr_screen_stats *stats, ScreenPlan &pl, bool *done)
+{
+    *done = true;
+    if (out_count) *out_count = 0;
+    int rc = check_params(c, p);
+    if (rc) return rc;
+    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
+    if (points && reinterpret_cast<uintptr_t>(points) % align_points != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", align_points);
+    if (hits && reinterpret_cast<uintptr_t>(hits) % align_hits != 0) return set_err(c, PCR_E_ARG, "the destination of the hits is misaligned (%zu bytes)", align_hits);
+    if (c->async_upload) poll_loader(c, false);
+    const int64_t nB = c->visible_batches();
+    pl.st = pcr_screen_stats{nB, 0, 0, 0};
+    const bool some = rect ? screen_clip(p, rect->x0, rect->y0, rect->x1, rect->y1, pl.q) : screen_clip(p, 0, 0, p->width - 1, p->height - 1, pl.q);
+    if (some && nB > 0) {
+        if ((rc = screen_list(c, p, nB, pl)) || (rc = screen_count(c, pl))) return rc;
+    }
+    *out_count = pl.st.points_selected;
+    if (stats) *stats = pl.st;
+    if ((!points && !hits) || pl.st.points_selected == 0) return PCR_OK;
+    if (capacity < (size_t)pl.st.points_selected)
+        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld selected", capacity, (long long)pl.st.points_selected);
+    *done = false;
+    return PCR_OK;
+}
+} // namespace
+
+int pcr_select_screen(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect, void *dev_points, void *dev_hits, size_t capacity,
+                      int64_t *out_count, pcr_screen_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ScreenPlan pl;
+    bool done = true;
+    int rc = screen_prepare(c, p, rect, dev_points, dev_hits, 16, 16, capacity, out_count, stats, pl, &done);
+    if (rc || done) return rc;
+    if ((rc = screen_emit(c, pl, 0, (int64_t)pl.kept.size(), static_cast<uint4 *>(dev_points), static_cast<uint4 *>(dev_hits)))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+int pcr_read_screen(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect, pcr_point *host_points, pcr_screen_hit *host_hits,
+                    size_t capacity, int64_t *out_count, pcr_screen_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ScreenPlan pl;
+    bool done = true;
+    int rc = screen_prepare(c, p, rect, host_points, host_hits, alignof(pcr_point), alignof(pcr_screen_hit), capacity, out_count, stats, pl, &done);
+    if (rc || done) return rc;
+    // pieces of at most DECODE_STAGE_BATCHES / 2 kept batches: a batch selects at most 65 536 records, so a piece's points fit the
+    // first half of the staging buffer and its hits the second
+    const int64_t nK = (int64_t)pl.kept.size();
+    const int64_t piece = std::min<int64_t>(nK, DECODE_STAGE_BATCHES / 2);
+    if (!c->d_decode_stage || c->decode_stage_batches < 2 * piece) {
+        dfree(c->d_decode_stage); c->decode_stage_batches = 0;
+        if (hipMalloc((void **)&c->d_decode_stage, (size_t)(2 * piece) * PCR_POINTS_PER_BATCH * sizeof(pcr_point)) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of points", (long long)(2 * piece));
+        c->decode_stage_batches = 2 * piece;
+    }
+    uint4 *const d_points = reinterpret_cast<uint4 *>(c->d_decode_stage), *const d_hits = d_points + (size_t)piece * PCR_POINTS_PER_BATCH;
+    int64_t written = 0;
+    for (int64_t k0 = 0; k0 < nK; k0 += piece) {
+        const int64_t k1 = std::min(nK, k0 + piece);
+        int64_t m = 0;
+        for (int64_t k = k0; k < k1; ++k) m += pl.cnt[(size_t)k];
+        if (m == 0) continue;
+        if ((rc = screen_emit(c, pl, k0, k1, host_points ? d_points : nullptr, host_hits ? d_hits : nullptr))) return rc;
+        if (host_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
+        if (host_hits) HIP_TRY(c, hipMemcpyAsync(host_hits + written, d_hits, (size_t)m * sizeof(pcr_screen_hit), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        written += m;
+    }
+    return PCR_OK;
+}
+
+int pcr_pick(pcr_ctx *c, const pcr_render_params *p, int px, int py, int radius, pcr_point *out_point, pcr_screen_hit *out_hit, int *out_found)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (out_found) *out_found = 0;
+    int rc = check_params(c, p);
+    if (rc) return rc;
+    if (!out_found) return set_err(c, PCR_E_ARG, "out_found is NULL");
+    if (radius < 0) return set_err(c, PCR_E_ARG, "radius must be >= 0");
+    if (c->async_upload) poll_loader(c, false);
+    const int64_t nB = c->visible_batches();
+    ScreenPlan pl;
+    if (nB == 0 || !screen_clip(p, (int64_t)px - radius, (int64_t)py - radius, (int64_t)px + radius, (int64_t)py + radius, pl.q)) return PCR_OK;
+    if ((rc = screen_list(c, p, nB, pl))) return rc;
+    const int64_t nK = (int64_t)pl.kept.size();
+    if (nK == 0) return PCR_OK;
+    if (!c->d_pick) HIP_TRY(c, hipMalloc((void **)&c->d_pick, PICK_WORDS * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemsetAsync(c->d_pick, 0xFF, PICK_WORDS * sizeof(unsigned long long), c->stream));
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)nK), block(PCR_WORKGROUP_SIZE);
+    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
+#define PCR_LAUNCH(L, B) do { hipLaunchKernelGGL((k_pick<L, B, false>), grid, block, 0, c->stream, s, c->d_scr_list, pl.q, c->d_pick); \
+                              hipLaunchKernelGGL((k_pick<L, B, true>), grid, block, 0, c->stream, s, c->d_scr_list, pl.q, c->d_pick); \
+                              hipLaunchKernelGGL((k_pick_fetch<L, B>), dim3(1), block, 0, c->stream, s, c->d_screen_lod, pl.q, c->d_pick); } while (0)
+    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
+    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+#undef PCR_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long h[PICK_WORDS];
+    HIP_TRY(c, hipMemcpyAsync(h, c->d_pick, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (h[1] == PICK_NONE) return PCR_OK;
+    *out_found = 1;
+    if (out_point) std::memcpy(out_point, &h[2], sizeof *out_point);
+    if (out_hit) std::memcpy(out_hit, &h[4], sizeof *out_hit);
     return PCR_OK;
 }
 

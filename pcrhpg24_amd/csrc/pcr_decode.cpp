@@ -1,13 +1,17 @@
 // pcr_decode — a .huffman file back to a LAS file, decoded on the GPU (pcr_read_points). The reference has no such tool: its only
 // decoder outside the render kernels is the per-chain CPU one of include/huffman.h:433-477.
 //     pcr_decode <in.huffman> <out.las> [--box x0 y0 z0 x1 y1 z1]
+//     pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1] [--rect x0 y0 x1 y1]
 // Loads the file with the loader of the render tools (HuffmanLasData, csrc/pcr_methods.hpp), reads the points back in pieces of
 // 64 batches and writes LAS 1.2 / point format 2 (pcr_write_las_points). With --box only the points inside a box of world
-// coordinates are read back (pcr_read_box: batches the box misses are not decoded).
+// coordinates are read back (pcr_read_box: batches the box misses are not decoded). With --view only the points a frame of that
+// camera draws (pcr_render's camera arguments and defaults), and of those the ones inside --rect, a rectangle of pixels
+// (pcr_read_screen).
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstdint>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -18,6 +22,8 @@ using namespace pcr_host;
 
 static const char *USAGE =
     "usage: pcr_decode <in.huffman> <out.las> [--box x0 y0 z0 x1 y1 z1]\n"
+    "       pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1]\n"
+    "                                                [--rect x0 y0 x1 y1]\n"
     "  Decodes every point of the stream on the GPU and writes a LAS 1.2 file (point format 2, 26-byte records).\n"
     "  A .huffman header stores the point count after padding only (a multiple of 65536: the encoder repeats the last\n"
     "  point), so the LAS file holds the padded count. Points come in the stream's order (Morton-sorted per chunk if the\n"
@@ -25,7 +31,66 @@ static const char *USAGE =
     "  thousandth of the points are the tail artefact the render kernels draw as well. The header's scale and offset are\n"
     "  the first batch record's, its min / max the cloud's box as that record carries it (single precision).\n"
     "  --box: only the points p with x0 <= p.x <= x1, y0 <= p.y <= y1, z0 <= p.z <= z1 in world coordinates (integer * scale +\n"
-    "  offset, in double precision), selected on the GPU, in the stream's order. A box that holds no point is an error.\n";
+    "  offset, in double precision), selected on the GPU, in the stream's order. A box that holds no point is an error.\n"
+    "  --view: only the points a frame of that camera draws (the basic method's cull and level of detail; the options and their\n"
+    "  defaults are pcr_render's), in the stream's order; --rect: of those the ones whose pixel lies in the rectangle (pixels,\n"
+    "  bounds inclusive, x0 <= x1 and y0 <= y1). A view that shows no point is an error.\n";
+
+static bool parse_double(const char *a, double &v)
+{
+    char *end = nullptr;
+    errno = 0;
+    v = std::strtod(a, &end);
+    return end != a && *end == '\0' && errno != ERANGE && std::isfinite(v);
+}
+
+static bool parse_int(const char *a, long lo, long hi, int &v)
+{
+    char *end = nullptr;
+    errno = 0;
+    const long x = std::strtol(a, &end, 10);
+    if (end == a || *end != '\0' || errno == ERANGE || x < lo || x > hi) return false;
+    v = (int)x;
+    return true;
+}
+
+struct View {
+    int w = 1920, h = 1080;
+    double cam[6] = {-0.15, -0.57, 3166.32, 2239.05, 1713.63, -202.02};        // pcr_render's default
+    double lod = 0.1;
+    int cull = 1;
+    bool has_rect = false;
+    pcr_rect rect{};
+};
+
+// the options behind --view, every one well formed, or false
+static bool parse_view(int argc, char **argv, int at, View &v)
+{
+    if (argc <= at || std::strcmp(argv[at], "--view") != 0) return false;
+    for (int i = at + 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        auto have = [&](int n) { return i + n < argc; };
+        if (a == "--size" && have(1)) {
+            char tail = 0;
+            if (std::sscanf(argv[++i], "%dx%d%c", &v.w, &v.h, &tail) != 2 || v.w < 1 || v.h < 1 || v.w > 16384 || v.h > 16384) return false;
+        } else if (a == "--camera" && have(6)) {
+            for (int k = 0; k < 6; ++k) if (!parse_double(argv[++i], v.cam[k])) return false;
+        } else if (a == "--lod" && have(1)) {
+            if (!parse_double(argv[++i], v.lod) || v.lod < 0.0 || v.lod > 1.0) return false;
+        } else if (a == "--cull" && have(1)) {
+            if (!parse_int(argv[++i], 0, 1, v.cull)) return false;
+        } else if (a == "--rect" && have(4) && !v.has_rect) {
+            int r[4];
+            for (int k = 0; k < 4; ++k) if (!parse_int(argv[++i], INT32_MIN, INT32_MAX, r[k])) return false;
+            if (r[0] > r[2] || r[1] > r[3]) return false;
+            v.rect = pcr_rect{r[0], r[1], r[2], r[3]};
+            v.has_rect = true;
+        } else {
+            return false;
+        }
+    }
+    return true;
+}
 
 // six finite numbers behind --box, or false
 static bool parse_box(int argc, char **argv, int at, double lo[3], double hi[3])
@@ -46,11 +111,12 @@ int main(int argc, char **argv)
 {
     if (argc >= 2 && (std::strcmp(argv[1], "--help") == 0 || std::strcmp(argv[1], "-h") == 0)) { std::fputs(USAGE, stdout); return 0; }
     double lo[3], hi[3];
-    const bool boxed = argc > 3;
-    if (argc < 3 || (boxed && !parse_box(argc, argv, 3, lo, hi))) { std::fputs(USAGE, stderr); return 2; }
+    View view;
+    const bool viewed = argc > 3 && std::strcmp(argv[3], "--view") == 0, boxed = argc > 3 && !viewed;
+    if (argc < 3 || (boxed && !parse_box(argc, argv, 3, lo, hi)) || (viewed && !parse_view(argc, argv, 3, view))) { std::fputs(USAGE, stderr); return 2; }
     const std::string in = argv[1], out = argv[2];
     try {
-        Renderer renderer(64, 64, 0);
+        Renderer renderer(viewed ? view.w : 64, viewed ? view.h : 64, 0);
         auto las = HuffmanLasData::create(in);
         las->load(&renderer);
         // (process() hands the reader thread's tasks over, and throws the reader's error if it had to give up)
@@ -69,6 +135,15 @@ int main(int argc, char **argv)
             std::printf("box: batches outside %lld, inside %lld, straddling %lld\n", (long long)st.batches_outside, (long long)st.batches_inside,
                         (long long)st.batches_straddling);
             if (points.empty()) throw std::runtime_error("no points inside the box: nothing written");
+        } else if (viewed) {
+            renderer.yaw = view.cam[0]; renderer.pitch = view.cam[1]; renderer.radius = view.cam[2];
+            for (int k = 0; k < 3; ++k) renderer.target[k] = view.cam[3 + k];
+            Debug::LOD = (float)view.lod;
+            Debug::frustumCullingEnabled = view.cull != 0;
+            const pcr_screen_stats st = las->selectScreen(renderer.params(), view.has_rect ? &view.rect : nullptr, &points, nullptr);
+            std::printf("view: batches skipped %lld, decoded %lld, points tested %lld\n", (long long)st.batches_skipped, (long long)st.batches_decoded,
+                        (long long)st.points_tested);
+            if (points.empty()) throw std::runtime_error("no points in the view: nothing written");
         } else {
             las->decodePoints(points);
         }

@@ -15,6 +15,7 @@
 //                   LDS, then projects and scatters every point (render.cu:383-540, huffman_hqs/depth.cu, huffman_hqs/render.cu;
 //                   MODE 3: the colour pass over BC7 mode-6 colours)
 //   k_decode_points on request: the same decode, every point of a range of batches written out as {x, y, z, colour} records
+//   k_screen_* / k_pick*  on request: the points a frame draws, selected by pixel (projection restated in screen_project)
 //   k_las_*         the 10-10-10 method (modules/compute_loop_las_cuda)
 //   k_resolve_*     framebuffer -> RGBA8 (resolve.cu:149-191, huffman_hqs/resolve.cu:2-47)
 //   k_merge_* / k_flip_sign  multi-GPU partial-framebuffer merges
@@ -2013,9 +2014,11 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_decode_points(StreamView
 enum { SEL_NO_COLOUR = 0, SEL_BC1 = 1, SEL_BC7 = 2 };
 
 // All 64 points of chain `tid` of batch b, in order: sink(i, x, y, z, colour) (colour 0 with SEL_NO_COLOUR). s_table holds the
-// batch's packed table and is visible to the workgroup. The reads are k_decode_points' (see there).
+// batch's packed table and is visible to the workgroup. The reads are k_decode_points' (see there). npr < 64 (uniform over the
+// workgroup): the chain's first npr points only, as a level of detail draws them -- the walk stops at the end of the group of
+// eight that holds point npr - 1 (the reads of a group are those of the full walk), the sink sees no point beyond it.
 template <int LAYOUT, int COLOUR, class Sink>
-__device__ __forceinline__ void decode_chain(const StreamView &s, uint32_t b, const uint32_t *s_table, Sink &&sink)
+__device__ __forceinline__ void decode_chain(const StreamView &s, uint32_t b, const uint32_t *s_table, Sink &&sink, int npr = PCR_POINTS_PER_THREAD)
 {
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2059,14 +2062,14 @@ __device__ __forceinline__ void decode_chain(const StreamView &s, uint32_t b, co
     uint32_t esc_prev = 0;
 
 #pragma unroll 1
-    for (int seg = 0; seg < PCR_POINTS_PER_THREAD / 16; ++seg) {
+    for (int seg = 0; seg < PCR_POINTS_PER_THREAD / 16 && seg * 16 < npr; ++seg) {
         Bc1Palette pal = {0, 0, 0, 0};
         Bc7Block pal7 = {0, 0, 0, 0, 0};
         const int seg_next = min(seg + 1, PCR_POINTS_PER_THREAD / 16 - 1);
         if (COLOUR == SEL_BC7) { pal7 = bc7_block(next7); next7 = blocks7[(size_t)seg_next * PCR_WORKGROUP_SIZE]; }
         else if (COLOUR == SEL_BC1) { pal = bc1_palette(next1); next1 = blocks1[(size_t)seg_next * PCR_WORKGROUP_SIZE]; }
 #pragma unroll 1
-        for (int half = 0; half < 2; ++half) {
+        for (int half = 0; half < 2 && seg * 16 + half * 8 < npr; ++half) {
             const int i0 = seg * 16 + half * 8;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -2121,7 +2124,7 @@ __device__ __forceinline__ void decode_chain(const StreamView &s, uint32_t b, co
                 }
                 const uint32_t colour = COLOUR == SEL_BC7 ? bc7_color(pal7, (uint32_t)(half * 8 + j))
                                       : COLOUR == SEL_BC1 ? bc1_color(pal, (uint32_t)(half * 8 + j)) : 0u;
-                sink(i0 + j, px, py, pz, colour);
+                if (i0 + j < npr) sink(i0 + j, px, py, pz, colour);
             }
         }
     }
@@ -2220,6 +2223,220 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_select_write(StreamView 
     decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t colour) {
         if (in_box(q, x, y, z) && dst < end) *dst++ = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Screen selection and picking (pcr_select_screen / pcr_read_screen / pcr_pick): the points a frame of the given camera draws,
+// with the pixel and the depth bits k_render computes for them -- the identity the framebuffer word (depth << 32 | colour) does
+// not carry. All of it is on the decode path; k_render, k_transcode and the prepass are not touched.
+//   k_screen_lod    the prepass's decision per batch (lod_prepass_batch with publish = false: culled, points per chain, f64
+//                   dequantisation) into an array of the selection's own: a pending pcr_frame_begin keeps its lists, plans and
+//                   statistics. The host reads the array and lists the kept batches.
+//   k_screen_count  per kept batch: how many of each chain's first npr points pass the inside test and fall into the rect
+//   k_screen_write  per kept batch: a workgroup prefix over those 1024 counts, then every chain writes its records and / or
+//                   hits consecutively from its offset (k_select_write's scheme; offsets between batches from the host)
+//   k_pick_key      per kept batch: 64-bit min of depth << 32 | colour over the window (lane, LDS, then one global atomic)
+//   k_pick_index    per kept batch: min of the record index among the window's points that hold that key
+//   k_pick_fetch    one workgroup: the winner's record and hit
+// No workgroup waits for another; every result is written with vector stores and vector atomics.
+// ------------------------------------------------------------------------------------------------
+struct ScreenEntry { uint32_t b, lod; };    // a kept batch and its LOD_* word
+struct ScreenArgs {
+    float m[16];                            // pcr_render_params::transform
+    int32_t width, height;
+    uint32_t fb_elems;
+    int32_t x0, y0, x1, y1;                 // the rect, clipped to the image, never empty
+};
+
+// What k_render works out per batch before its point loop (:1378-1381 there): the dequantisation in both precisions.
+struct ScreenBatch {
+    double sx, sy, sz, ox, oy, oz;
+    float fsx, fsy, fsz, fox, foy, foz;
+    bool use_double;
+};
+__device__ __forceinline__ ScreenBatch screen_batch(const StreamView &s, uint32_t b, uint32_t lod)
+{
+    const pcr_gpu_batch *gb = s.batches + b;
+    ScreenBatch B;
+    B.sx = gb->scale_x; B.sy = gb->scale_y; B.sz = gb->scale_z;
+    B.ox = gb->offset_x - gb->las_min_x; B.oy = gb->offset_y - gb->las_min_y; B.oz = gb->offset_z - gb->las_min_z;
+    B.fsx = (float)B.sx; B.fsy = (float)B.sy; B.fsz = (float)B.sz;
+    B.fox = (float)B.ox; B.foy = (float)B.oy; B.foz = (float)B.oz;
+    B.use_double = (lod & LOD_DOUBLE) != 0;
+    return B;
+}
+
+// k_render's projection of one point, operation for operation in its plain form (oracle/pcr_oracle.c, sink_raster): the
+// dequantisation in the batch's precision, the three dot products in dot4's order, the correctly rounded division k_render's
+// reciprocal sequence is bit-identical to (see project_divide there), the inside test that rejects NaNs, the pixel by
+// truncation. Every fused operation is spelled out and nothing else may be fused. false: the point is not drawn.
+__device__ __forceinline__ bool screen_project(const ScreenArgs &q, const ScreenBatch &B, int32_t x, int32_t y, int32_t z,
+                                               int &ix, int &iy, uint32_t &pixel, uint32_t &depth_bits)
+{
+#pragma clang fp contract(off)
+    float fx, fy, fz;
+    if (B.use_double) {
+        fx = (float)__fma_rn((double)x, B.sx, B.ox);
+        fy = (float)__fma_rn((double)y, B.sy, B.oy);
+        fz = (float)__fma_rn((double)z, B.sz, B.oz);
+    } else {
+        fx = __fmaf_rn((float)x, B.fsx, B.fox);
+        fy = __fmaf_rn((float)y, B.fsy, B.foy);
+        fz = __fmaf_rn((float)z, B.fsz, B.foz);
+    }
+    const float qx = __fmaf_rn(q.m[3], 1.0f, __fmaf_rn(q.m[2], fz, __fmaf_rn(q.m[1], fy, q.m[0] * fx)));
+    const float qy = __fmaf_rn(q.m[7], 1.0f, __fmaf_rn(q.m[6], fz, __fmaf_rn(q.m[5], fy, q.m[4] * fx)));
+    const float qw = __fmaf_rn(q.m[15], 1.0f, __fmaf_rn(q.m[14], fz, __fmaf_rn(q.m[13], fy, q.m[12] * fx)));
+    const float nx = qx / qw, ny = qy / qw;               // (correctly rounded: no fast-math, see the top of the file)
+    if (!(qw > 0.0f && nx >= -1.0f && nx <= 1.0f && ny >= -1.0f && ny <= 1.0f)) return false;
+    ix = (int)(__fmaf_rn(nx, 0.5f, 0.5f) * (float)q.width);
+    iy = (int)(__fmaf_rn(ny, 0.5f, 0.5f) * (float)q.height);
+    const int64_t pix = (int64_t)ix + (int64_t)iy * q.width;
+    if (pix < 0 || pix >= (int64_t)q.fb_elems) return false;
+    pixel = (uint32_t)pix;
+    depth_bits = __float_as_uint(qw);
+    return true;
+}
+
+// Does the pixel lie in the rect? Column and row are those of the linear index: ndc == 1.0 maps to column `width`, which in
+// the framebuffer is column 0 of the next row.
+__device__ __forceinline__ bool screen_in_rect(const ScreenArgs &q, int ix, int iy)
+{
+    const int cx = ix >= q.width ? ix - q.width : ix, cy = ix >= q.width ? iy + 1 : iy;
+    return cx >= q.x0 && cx <= q.x1 && cy >= q.y0 && cy <= q.y1;
+}
+
+// lod[b] = the prepass's LOD_* word of batch b for the camera of `a` (a.variant_hqs picks the expression): nothing else is written
+__global__ void __launch_bounds__(PREPASS_THREADS) k_screen_lod(RenderArgs a, uint32_t *lod)
+{
+    const int64_t b = ((int64_t)blockIdx.x * PREPASS_THREADS + threadIdx.x) / PREPASS_LANES;
+    const int lane = (int)(threadIdx.x % PREPASS_LANES);
+    pcr_render_stats st = {0, 0, 0, 0};
+    if (b < a.s.num_batches) {                              // (uniform per group of PREPASS_LANES lanes)
+        const uint32_t w = lod_prepass_batch(a, b, lane, st, false);
+        if (lane == 0) lod[b] = w;
+    }
+}
+
+// Workgroup x takes list[x]: chain_counts[x * 1024 + chain] = the chain's selected points, totals[x] = their sum
+template <int LAYOUT>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_screen_count(StreamView s, const ScreenEntry *list, ScreenArgs q, uint32_t *chain_counts, uint32_t *totals)
+{
+    const ScreenEntry e = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint32_t s_part[LWC_WAVES];
+    load_packed_table(s, e.b, s_table);
+    const ScreenBatch B = screen_batch(s, e.b, e.lod);
+    uint32_t cnt = 0;
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, e.b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t) {
+        int ix, iy; uint32_t pixel, depth;
+        if (screen_project(q, B, x, y, z, ix, iy, pixel, depth) && screen_in_rect(q, ix, iy)) ++cnt;
+    }, (int)(e.lod & LOD_NPR_MASK));
+    chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid] = cnt;
+    uint32_t sum = cnt;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    if (lane == 0) s_part[wave] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < LWC_WAVES; ++w) t += s_part[w];
+        totals[blockIdx.x] = t;
+    }
+}
+
+// Workgroup x takes list[x]: its selected records go to points[offsets[x] ..] and their hits to hits[offsets[x] ..] (either may be
+// NULL), chain after chain, each chain's in point order. chain_counts is k_screen_count's for the same list and arguments. A hit
+// is {pixel, depth bits, index lo, index hi}: one 16-byte store.
+template <int LAYOUT, bool BC7>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_screen_write(StreamView s, const ScreenEntry *list, ScreenArgs q, const uint32_t *chain_counts,
+                                                                     const int64_t *offsets, uint4 *points, uint4 *hits)
+{
+    static_assert(sizeof(pcr_screen_hit) == 16, "one dwordx4 store per hit");
+    const ScreenEntry e = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint32_t s_part[LWC_WAVES];
+    const uint32_t mine = chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid];
+    uint32_t incl = mine;                                   // inclusive prefix inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += up;
+    }
+    if (lane == 63) s_part[wave] = incl;
+    load_packed_table(s, e.b, s_table);                     // (its barrier publishes s_part as well)
+    uint32_t before = incl - mine;
+    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    const ScreenBatch B = screen_batch(s, e.b, e.lod);
+    const int64_t first = offsets[blockIdx.x] + before;
+    const uint64_t index0 = (uint64_t)e.b * PCR_POINTS_PER_BATCH + (uint64_t)tid * PCR_POINTS_PER_THREAD;
+    uint32_t k = 0;                                         // never past what k_screen_count counted for this chain
+    decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, e.b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        int ix, iy; uint32_t pixel, depth;
+        if (screen_project(q, B, x, y, z, ix, iy, pixel, depth) && screen_in_rect(q, ix, iy) && k < mine) {
+            const uint64_t index = index0 + (uint64_t)i;
+            if (points) points[first + k] = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
+            if (hits) hits[first + k] = make_uint4(pixel, depth, (uint32_t)index, (uint32_t)(index >> 32));
+            ++k;
+        }
+    }, (int)(e.lod & LOD_NPR_MASK));
+}
+
+// pick[0]: min of depth << 32 | colour over the points of the list's batches in the window; pick[1]: min record index among
+// those that hold it (both start as all ones); pick[2..3], pick[4..5]: the winner's record and hit.
+constexpr int PICK_WORDS = 6;
+constexpr uint64_t PICK_NONE = ~0ull;
+
+template <int LAYOUT, bool BC7, bool INDEX_PASS>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_pick(StreamView s, const ScreenEntry *list, ScreenArgs q, unsigned long long *pick)
+{
+    const ScreenEntry e = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ unsigned long long s_best;
+    const uint64_t key_wanted = INDEX_PASS ? pick[0] : 0;
+    if (INDEX_PASS && key_wanted == PICK_NONE) return;      // (uniform) the window is empty
+    if (tid == 0) s_best = PICK_NONE;
+    load_packed_table(s, e.b, s_table);                     // (its barrier publishes s_best as well)
+    const ScreenBatch B = screen_batch(s, e.b, e.lod);
+    const uint64_t index0 = (uint64_t)e.b * PCR_POINTS_PER_BATCH + (uint64_t)tid * PCR_POINTS_PER_THREAD;
+    uint64_t best = PICK_NONE;
+    decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, e.b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        int ix, iy; uint32_t pixel, depth;
+        if (screen_project(q, B, x, y, z, ix, iy, pixel, depth) && screen_in_rect(q, ix, iy)) {
+            const uint64_t key = ((uint64_t)depth << 32) | colour;
+            if (!INDEX_PASS) best = min(best, key);
+            else if (key == key_wanted) best = min(best, index0 + (uint64_t)i);
+        }
+    }, (int)(e.lod & LOD_NPR_MASK));
+    if (best != PICK_NONE) atomicMin(&s_best, (unsigned long long)best);
+    __syncthreads();
+    if (tid == 0 && s_best != PICK_NONE) atomicMin(&pick[INDEX_PASS ? 1 : 0], s_best);
+}
+
+// One workgroup: the record and the hit of point pick[1] (nothing if there is none). lod: k_screen_lod's array.
+template <int LAYOUT, bool BC7>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_pick_fetch(StreamView s, const uint32_t *lod, ScreenArgs q, unsigned long long *pick)
+{
+    const uint64_t winner = pick[1];
+    if (winner == PICK_NONE) return;                        // (uniform)
+    const uint32_t b = (uint32_t)(winner / PCR_POINTS_PER_BATCH), tid = threadIdx.x;
+    if ((int64_t)b >= s.num_batches) return;
+    const uint32_t w = lod[b];
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    load_packed_table(s, b, s_table);
+    const ScreenBatch B = screen_batch(s, b, w);
+    const uint64_t index0 = (uint64_t)b * PCR_POINTS_PER_BATCH + (uint64_t)tid * PCR_POINTS_PER_THREAD;
+    uint4 *const out = reinterpret_cast<uint4 *>(pick + 2);
+    decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        int ix, iy; uint32_t pixel, depth;
+        if (index0 + (uint64_t)i == winner && screen_project(q, B, x, y, z, ix, iy, pixel, depth)) {
+            out[0] = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
+            out[1] = make_uint4(pixel, depth, (uint32_t)winner, (uint32_t)(winner >> 32));
+        }
+    }, (int)(w & LOD_NPR_MASK));
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -323,6 +323,31 @@ struct HuffmanLasData : Resource {
         return st;
     }
 
+    // The points a frame of camera `p` draws whose pixel lies in `rect` (NULL: the whole image), with where they land, selected on
+    // the GPU (pcr_read_screen: a counting call, then the read). Either vector may be NULL. Not in the reference.
+    pcr_screen_stats selectScreen(const pcr_render_params &p, const pcr_rect *rect, std::vector<pcr_point> *points, std::vector<pcr_screen_hit> *hits)
+    {
+        if (!loadedOn) throw std::runtime_error("selectScreen: the resource is not loaded");
+        int64_t n = 0;
+        pcr_screen_stats st{};
+        loadedOn->check(pcr_read_screen(loadedOn->ctx, &p, rect, nullptr, nullptr, 0, &n, &st), "pcr_read_screen");
+        if (points) points->resize((size_t)n);
+        if (hits) hits->resize((size_t)n);
+        if (n && (points || hits))
+            loadedOn->check(pcr_read_screen(loadedOn->ctx, &p, rect, points ? points->data() : nullptr, hits ? hits->data() : nullptr, (size_t)n, &n, &st),
+                            "pcr_read_screen");
+        return st;
+    }
+
+    // The point under pixel (px, py) of a frame of camera `p`, within `radius` pixels (pcr_pick); false: none. Not in the reference.
+    bool pick(const pcr_render_params &p, int px, int py, int radius, pcr_point &point, pcr_screen_hit &hit)
+    {
+        if (!loadedOn) throw std::runtime_error("pick: the resource is not loaded");
+        int found = 0;
+        loadedOn->check(pcr_pick(loadedOn->ctx, &p, px, py, radius, &point, &hit, &found), "pcr_pick");
+        return found != 0;
+    }
+
     // Scale, offset and box of the LAS file the stream was made from, as the first batch record carries them
     // (include/BatchDumpData.h:60-107: doubles at 20 and 44, the LAS box as floats at 92 and 104).
     pcr_las_info lasInfo() const

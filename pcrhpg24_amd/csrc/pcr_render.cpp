@@ -5,9 +5,13 @@
 //   pcr_render <file.las>      --method loop_las_cuda|loop_las_hqs         [--size WxH]
 //              [--camera yaw pitch radius tx ty tz] [--lod 0.1] [--cull 0|1] [--frames N]
 //              [--async-load]   (.huffman: copies on the loader stream, frames draw what has arrived)
+//              [--pick X Y [R]]   (.huffman: the point under pixel (X, Y) of the view, within R pixels, pcr_pick; one line
+//                                  "pick x= y= z= color= index= pixel= px= py= depth_bits=" or "pick none")
 //              [--dump-fb fb.u64] [--dump-rgba out.ppm] [--dump-depth depth.exr]   (depth: huffman_hqs only, huffman_hqs.h:217-237)
 // Prints one JSON line: batches, frames needed to load, ms of the last frame, FNV-1a of the u64 framebuffer.
+#include <cerrno>
 #include <chrono>
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -24,12 +28,23 @@ static uint64_t fnv1a(const void *p, size_t n)
     return h;
 }
 
+static bool parse_int(const char *a, long lo, long hi, int &v)
+{
+    char *end = nullptr;
+    errno = 0;
+    const long x = std::strtol(a, &end, 10);
+    if (end == a || *end != '\0' || errno == ERANGE || x < lo || x > hi) return false;
+    v = (int)x;
+    return true;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 2) { std::fprintf(stderr, "usage: pcr_render <file.huffman> [options]\n"); return 2; }
     std::string path = argv[1], method = "huffman_mem_iter_cuda", dump_fb, dump_rgba, dump_depth;
     int w = 1920, h = 1080, frames = 0;
-    bool async_load = false;
+    bool async_load = false, do_pick = false;
+    int pick[3] = {0, 0, 0};                    // X Y R
     // src/main.cpp:192-218 default setting ("morrobay" overview)
     double cam[6] = {-0.15, -0.57, 3166.32, 2239.05, 1713.63, -202.02};
     for (int i = 2; i < argc; ++i) {
@@ -42,11 +57,24 @@ int main(int argc, char **argv)
         else if (a == "--cull") { need(1); Debug::frustumCullingEnabled = std::atoi(argv[++i]) != 0; }
         else if (a == "--frames") { need(1); frames = std::atoi(argv[++i]); }
         else if (a == "--async-load") { async_load = true; }
+        else if (a == "--pick") {
+            // two integers, and a third if the next argument is not an option; anything else is refused here, before a context exists
+            need(2);
+            const bool third = i + 3 < argc && std::strncmp(argv[i + 3], "--", 2) != 0;
+            if (!parse_int(argv[i + 1], INT_MIN / 2, INT_MAX / 2, pick[0]) || !parse_int(argv[i + 2], INT_MIN / 2, INT_MAX / 2, pick[1]) ||
+                (third && !parse_int(argv[i + 3], 0, INT_MAX / 2, pick[2]))) {
+                std::fprintf(stderr, "usage: --pick X Y [R]: integers, R >= 0\n");
+                return 2;
+            }
+            i += third ? 3 : 2;
+            do_pick = true;
+        }
         else if (a == "--dump-fb") { need(1); dump_fb = argv[++i]; }
         else if (a == "--dump-rgba") { need(1); dump_rgba = argv[++i]; }
         else if (a == "--dump-depth") { need(1); dump_depth = argv[++i]; }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
+    if (do_pick && (method == "loop_las_cuda" || method == "loop_las_hqs")) { std::fprintf(stderr, "--pick needs a .huffman stream and one of its methods\n"); return 2; }
     try {
         Renderer renderer(w, h, 0);
         renderer.yaw = cam[0]; renderer.pitch = cam[1]; renderer.radius = cam[2];
@@ -105,6 +133,15 @@ int main(int argc, char **argv)
             o << "P6\n" << w << " " << h << "\n255\n";
             for (int y = h - 1; y >= 0; --y)          // GL convention: row 0 is the bottom
                 for (int x = 0; x < w; ++x) { uint32_t c = rgba[(size_t)y * w + x]; char px[3] = {(char)(c & 255), (char)((c >> 8) & 255), (char)((c >> 16) & 255)}; o.write(px, 3); }
+        }
+        if (do_pick) {
+            pcr_point pt{};
+            pcr_screen_hit hit{};
+            if (las_huffman->pick(renderer.params(), pick[0], pick[1], pick[2], pt, hit))
+                std::printf("pick x=%d y=%d z=%d color=0x%06x index=%lld pixel=%u px=%u py=%u depth_bits=0x%08x\n", pt.x, pt.y, pt.z, pt.color,
+                            (long long)hit.index, hit.pixel, hit.pixel % (unsigned)w, hit.pixel / (unsigned)w, hit.depth_bits);
+            else
+                std::printf("pick none\n");
         }
         std::printf("{\"method\": \"%s\", \"batches\": %lld, \"frames_to_load\": %d, \"last_frame_ms\": %.3f, \"points_iterated\": %lld, "
                     "\"batches_culled\": %lld, \"covered_pixels\": %zu, \"fb_fnv1a\": \"%016llx\", \"rgba_fnv1a\": \"%016llx\"}\n",

@@ -185,7 +185,19 @@ def read_las(path: str):
 
 POINT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("color", "<u4")])     # pcr_point
 
+HIT_DTYPE = np.dtype([("pixel", "<u4"), ("depth_bits", "<u4"), ("index", "<i8")])          # pcr_screen_hit
+
 INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
+
+
+def as_rect(rect):
+    """A pcr_rect from a Rect or four numbers x0, y0, x1, y1 (pixels, bounds inclusive); None stays None: the whole image."""
+    if rect is None or isinstance(rect, N.Rect):
+        return rect
+    v = [int(a) for a in np.asarray(rect, dtype=np.int64).reshape(4)]
+    if any(a < INT32_MIN or a > INT32_MAX for a in v):
+        raise ValueError("rect coordinates are int32")
+    return N.Rect(*v)
 
 
 def as_box(box) -> Box:
@@ -568,6 +580,52 @@ class Context:
         self.select_stats = st.as_dict()
         return out
 
+    # -- screen selection and picking (pcr_select_screen / pcr_read_screen / pcr_pick) ---------------------
+    def select_screen(self, p: RenderParams, rect=None):
+        """The points a frame of camera `p` draws (render_basic's cull, level of detail, precision and inside test) whose pixel lies
+        in `rect` (as_rect: a Rect or x0, y0, x1, y1, inclusive, clipped to the image; None: the whole image), on the context's
+        device: (points, hits). points is a torch.int32 tensor [n, 4], the rows decode_points gives for them (x, y, z, colour
+        0x00BBGGRR). hits is a torch.int64 tensor [n, 2], the bytes of n pcr_screen_hit records: column 0 = depth_bits << 32 |
+        pixel (pixel = x + y * width, depth_bits = the float32 bits of w: hits[:, 0] & 0xFFFFFFFF and hits[:, 0] >> 32), column 1 =
+        the point's row in decode_points(0, None). Rows are in increasing index order. The call counts first and allocates
+        exactly; stream ordering as decode_points. The counts of the last call are in self.screen_stats."""
+        import torch
+        rect = as_rect(rect)
+        dev = torch.device("cuda", self.device)
+        cnt, st = c_i64(), N.ScreenStats()
+        rp = C.byref(rect) if rect is not None else None
+        self._chk(self.lib.pcr_select_screen(self.h, C.byref(p), rp, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_select_screen")
+        pts = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
+        hits = torch.empty((cnt.value, 2), dtype=torch.int64, device=dev)
+        if cnt.value:
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self.lib.pcr_select_screen(self.h, C.byref(p), rp, C.c_void_p(pts.data_ptr()), C.c_void_p(hits.data_ptr()), cnt.value,
+                                                 C.byref(cnt), C.byref(st)), "pcr_select_screen")
+        self.screen_stats = st.as_dict()
+        return pts, hits
+
+    def read_screen(self, p: RenderParams, rect=None):
+        """The same on the host, without torch: (points, hits), numpy structured arrays of POINT_DTYPE and HIT_DTYPE
+        (pcr_read_screen: a counting call, then the read; synchronises)."""
+        rect = as_rect(rect)
+        cnt, st = c_i64(), N.ScreenStats()
+        rp = C.byref(rect) if rect is not None else None
+        self._chk(self.lib.pcr_read_screen(self.h, C.byref(p), rp, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_read_screen")
+        pts, hits = np.empty(cnt.value, POINT_DTYPE), np.empty(cnt.value, HIT_DTYPE)
+        if cnt.value:
+            self._chk(self.lib.pcr_read_screen(self.h, C.byref(p), rp, pts.ctypes.data, hits.ctypes.data, cnt.value, C.byref(cnt), C.byref(st)),
+                      "pcr_read_screen")
+        self.screen_stats = st.as_dict()
+        return pts, hits
+
+    def pick(self, p: RenderParams, px: int, py: int, radius: int = 0):
+        """The point under pixel (px, py) of a frame of camera `p`: among the select_screen hits within `radius` pixels (a square
+        window, clipped to the image) the least by (depth_bits, colour, index). None if the window holds no point, else
+        (point, hit): a Point (x, y, z, color) and a ScreenHit (pixel, depth_bits, index). Synchronises."""
+        pt, hit, found = N.Point(), N.ScreenHit(), C.c_int()
+        self._chk(self.lib.pcr_pick(self.h, C.byref(p), int(px), int(py), int(radius), C.byref(pt), C.byref(hit), C.byref(found)), "pcr_pick")
+        return (pt, hit) if found.value else None
+
     def stats(self) -> dict:
         st = RenderStats()
         self._chk(self.lib.pcr_get_stats(self.h, C.byref(st)), "pcr_get_stats")
@@ -861,6 +919,18 @@ class HuffmanLasData(Resource):
             return pts
         so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
         return pts[:, :3].to(torch.float64) * so[0] + so[1], pts
+
+    def points_on_screen(self, renderer: Renderer, params: Optional[RenderParams] = None, rect=None, world: bool = True):
+        """The points of the loaded resource a frame of `params` (None: renderer.render_params()) draws inside `rect` (pixels,
+        None: the whole image), selected on the GPU (Context.select_screen). world=True: (xyz, pts, hits) with xyz a float64
+        tensor [n, 3] = x * scale + offset from las_info()'s scale and offset, as points_in_box; world=False: (pts, hits)."""
+        import torch
+        pts, hits = renderer.ctx.select_screen(renderer.render_params() if params is None else params, rect)
+        if not world:
+            return pts, hits
+        info = self.las_info()
+        so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
+        return pts[:, :3].to(torch.float64) * so[0] + so[1], pts, hits
 
     def las_info(self) -> LasInfo:
         """Scale, offset, min and max of the LAS file the stream was made from, as its first batch record carries them (the
