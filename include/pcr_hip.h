@@ -136,6 +136,42 @@ int     pcr_render_las_hqs_color(pcr_ctx *ctx, const pcr_render_params *p);
 int     pcr_resolve_las(pcr_ctx *ctx, const pcr_render_params *p);
 int64_t pcr_las_algorithmic_bytes(pcr_ctx *ctx);
 
+/* ---- display resolves: n x n point size and eye-dome lighting -------------------------------------------
+ * pcr_resolve_basic_display / pcr_resolve_hqs_display / pcr_resolve_las_display <- the resolve of the reference's GLSL 10-10-10
+ * method (modules/compute_loop_las/resolve.cs: :98-128 the "n x n pixel" loop over `window`, :41-62 and :143-185 eye-dome
+ * lighting over `edlWindow`), which the reference never brought to its CUDA / Huffman methods. Each is called where its plain
+ * counterpart (pcr_resolve_basic / _hqs / _las) is, with the same preconditions, and only enqueues on the context's stream. It
+ * writes the context's RGBA8 image (pcr_read_rgba / pcr_device_rgba) and nothing else: the framebuffer, RG / BA, the prepass
+ * state, the tile flags and the statistics stay as they are. It reads whichever buffers the context uses (external ones, and
+ * either empty word: pcr_set_int64_mergeable). With window == 0 and edl_window == 0 the image is the plain resolve's, byte for byte.
+ *
+ * Pixel (x, y), 0 <= x < width, 0 <= y < height, has index x + y * width; a window is the square of the given radius around a
+ * pixel, CLIPPED to the image.
+ *  1. D(x, y) = the 64-bit unsigned minimum of the framebuffer's words over the window of radius opts->window. This is the frame
+ *     that drawing every point as a (2 * window + 1)^2 square with the 64-bit atomicMin would leave (for points whose own pixel is
+ *     in the image), at the cost of a stencil over the pixels instead of window^2 atomics per point.
+ *  2. colour: basic -- D through pcr_resolve_basic's arithmetic (background, show_num_points, colorize_chunks included); las -- D
+ *     through pcr_resolve_las's (the colour of point index D & 0xFFFFFFFF, background for an empty D); hqs -- background for an
+ *     empty D, the debug flags on D's low word as pcr_resolve_hqs, else the 64-bit sums of RG and BA over the window's pixels n
+ *     that are drawn and whose OWN depth d_n <= d * 1.01f (d = the depth half of D; one rounded f32 product, color.cs:370),
+ *     divided as pcr_resolve_hqs divides (count 0: colour 0).
+ *  3. eye-dome lighting, when opts->edl_window = e > 0, of every pixel with a non-empty D (background is never shaded), on the
+ *     DILATED depths d(.) = D >> 32 as f32: response = (sum over ox = -e..e (outer), oy = -e..e (inner) of max(0, d(c) - d(n)),
+ *     0 for n outside the image or with an empty D, accumulated in f32) / (2e+1)^2; shade = expf((-response * 300.0f) *
+ *     opts->edl_strength); bytes 0..2 <- (uint32_t)((float)byte * shade), byte 3 <- 0 (resolve.cs:169-182).
+ * Deviations from resolve.cs: windows are clipped to the image (the shader reads through the linear pixel index and so wraps
+ * into the neighbouring rows at the left and right edges); the dilated word is the minimum of the whole 64-bit word, this
+ * project's rule for depth ties (the shader compares depths only and breaks ties by loop order) -- that is what makes step 1
+ * equal to drawing squares; EDL of a frame with window > 0 runs on the dilated depths. The hqs colour APPROXIMATES square
+ * splats under the 1 % rule: a neighbour's RG / BA sums were filtered by the colour pass against that neighbour's own front
+ * depth, not against d.
+ * PCR_E_ARG, with a message and the image untouched: opts NULL; window outside [0, PCR_DISPLAY_MAX_WINDOW]; edl_window outside
+ * [0, PCR_DISPLAY_MAX_EDL_WINDOW]; edl_strength NaN, infinite or negative while edl_window > 0; reserved != 0; and whatever the
+ * plain resolve refuses. The whole frame is walked (the tile flags are not consulted). */
+int pcr_resolve_basic_display(pcr_ctx *ctx, const pcr_render_params *p, const pcr_display_opts *opts);
+int pcr_resolve_hqs_display(pcr_ctx *ctx, const pcr_render_params *p, const pcr_display_opts *opts);
+int pcr_resolve_las_display(pcr_ctx *ctx, const pcr_render_params *p, const pcr_display_opts *opts);
+
 /* Counters of the most recent render call (synchronises). */
 int pcr_get_stats(pcr_ctx *ctx, pcr_render_stats *out);
 

@@ -158,6 +158,17 @@ typedef struct pcr_screen_stats {
     int64_t points_selected;
 } pcr_screen_stats;
 
+/* How a display resolve (pcr_resolve_*_display) turns the framebuffer into the image: the point size and eye-dome lighting of
+ * the reference's GLSL 10-10-10 resolve (modules/compute_loop_las/resolve.cs:98-128 `window`, :41-62 and :143-185 `edlWindow`). */
+#define PCR_DISPLAY_MAX_WINDOW      4   /* point size 2*4+1 = 9 pixels */
+#define PCR_DISPLAY_MAX_EDL_WINDOW  2
+typedef struct pcr_display_opts {       /* 16 bytes */
+    int32_t window;        /* 0..PCR_DISPLAY_MAX_WINDOW: a point covers (2*window+1)^2 pixels; 0 = one pixel */
+    int32_t edl_window;    /* 0 = no eye-dome lighting; 1..PCR_DISPLAY_MAX_EDL_WINDOW */
+    float   edl_strength;  /* finite, >= 0; the reference's constant is 0.0005f (resolve.cs:169); ignored when edl_window == 0 */
+    int32_t reserved;      /* must be 0 */
+} pcr_display_opts;
+
 /* Number of u64 elements a framebuffer of w x h must hold: ndc == 1.0 maps to column w / row h
  * (SURVEY Appendix C.2), so pixel ids reach w*(h+1). */
 static inline size_t pcr_fb_elems(int w, int h) { return (size_t)w * (size_t)(h + 1) + 1; }

@@ -5,4 +5,4 @@ Layout:  csrc/ (HIP kernels, C ABI, CPU encoder)  ·  host.py (the reference's M
 """
 from .host import (ComputeHuffman, ComputeLasData, ComputeLoopLasCUDA, ComputeLoopLasHQS, Context, Debug, HuffmanFile, HuffmanHQS, HuffmanLasData, HuffmanMemIter, Method, PcrError,  # noqa: F401
                    Renderer, Resource, Runtime, camera_orbit, encode_points, kernel_version, synth_encode, synth_las_info, synth_points, las_quantize, read_las, write_las, POINT_DTYPE, HIT_DTYPE, as_box, as_rect, box_from_world)
-from ._native import Box, Rect, ScreenHit, ScreenStats, SelectStats, FileHeader, LasInfo, Point, RenderParams, RenderStats, XyzBatch, fb_elems  # noqa: F401
+from ._native import Box, DisplayOpts, Rect, ScreenHit, ScreenStats, SelectStats, FileHeader, LasInfo, Point, RenderParams, RenderStats, XyzBatch, fb_elems  # noqa: F401

@@ -83,6 +83,10 @@ class ScreenStats(C.Structure):                   # pcr_screen_stats
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class DisplayOpts(C.Structure):                   # pcr_display_opts: point size and eye-dome lighting of a display resolve, 16 bytes
+    _fields_ = [("window", c_i32), ("edl_window", c_i32), ("edl_strength", c_f32), ("reserved", c_i32)]
+
+
 class EncodeStats(C.Structure):                   # pcr_encode_stats
     _fields_ = [(n, c_i64) for n in ("num_points_in", "num_points", "num_batches", "encoded_bytes", "separate_bytes",
                                      "cluster_bytes", "escaped_symbols", "total_symbols", "file_bytes")]
@@ -93,6 +97,7 @@ class EncodeStats(C.Structure):                   # pcr_encode_stats
 
 assert C.sizeof(Point) == 16 and C.sizeof(Box) == 24 and C.sizeof(SelectStats) == 32
 assert C.sizeof(Rect) == 16 and C.sizeof(ScreenHit) == 16 and C.sizeof(ScreenStats) == 32
+assert C.sizeof(DisplayOpts) == 16
 assert C.sizeof(XyzBatch) == 64 and C.sizeof(GpuBatch) == 160 and C.sizeof(FileHeader) == 40 and C.sizeof(RenderParams) == 224
 
 
@@ -115,6 +120,7 @@ HIP_SYMBOLS = [
     "pcr_decode_points", "pcr_read_points",
     "pcr_batch_point_bounds", "pcr_select_box", "pcr_read_box",
     "pcr_select_screen", "pcr_read_screen", "pcr_pick",
+    "pcr_resolve_basic_display", "pcr_resolve_hqs_display", "pcr_resolve_las_display",
 ]
 
 HOST_SYMBOLS = [
@@ -230,6 +236,8 @@ def hip_lib() -> C.CDLL:
             getattr(lib, n).argtypes = [C.c_void_p, C.POINTER(RenderParams), C.POINTER(Rect), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(c_i64),
                                         C.POINTER(ScreenStats)]
         lib.pcr_pick.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_int, C.c_int, C.c_int, C.POINTER(Point), C.POINTER(ScreenHit), C.POINTER(C.c_int)]
+        for n in ("pcr_resolve_basic_display", "pcr_resolve_hqs_display", "pcr_resolve_las_display"):
+            getattr(lib, n).argtypes = [C.c_void_p, C.POINTER(RenderParams), C.POINTER(DisplayOpts)]
         _hip = lib
     return _hip
 

@@ -9,6 +9,7 @@
 #include "pcr_kernels.hip.h"
 
 #include <algorithm>
+#include <cfloat>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -1361,6 +1362,52 @@ static int launch_resolve(pcr_ctx *c, const pcr_render_params *p, bool hqs)
 }
 int pcr_resolve_basic(pcr_ctx *c, const pcr_render_params *p) { return launch_resolve(c, p, false); }
 int pcr_resolve_hqs(pcr_ctx *c, const pcr_render_params *p) { return launch_resolve(c, p, true); }
+
+// ---- display resolves (n x n point size, eye-dome lighting) ------------------------------------------------
+// The preconditions of the plain resolve of `method`, then the options; one launch of k_resolve_display over the whole frame.
+static int launch_resolve_display(pcr_ctx *c, const pcr_render_params *p, const pcr_display_opts *o, int method)
+{
+    if (method == DISPLAY_LAS) {
+        const int rc = check_las(c, p);
+        if (rc) return rc;
+    } else {
+        if (!c) return PCR_E_ARG;
+        if (!p) return set_err(c, PCR_E_ARG, "params are NULL");
+        if (!c->fb) return set_err(c, PCR_E_ARG, "no framebuffer");
+        if (p->width != c->width || p->height != c->height) return set_err(c, PCR_E_ARG, "params image size != framebuffer");
+        if (method == DISPLAY_HQS && (!c->rg || !c->ba)) return set_err(c, PCR_E_ARG, "no RG/BA accumulation buffers");
+    }
+    if (!o) return set_err(c, PCR_E_ARG, "display options are NULL");
+    if (o->window < 0 || o->window > PCR_DISPLAY_MAX_WINDOW)
+        return set_err(c, PCR_E_ARG, "display window %d outside [0, %d]", o->window, PCR_DISPLAY_MAX_WINDOW);
+    if (o->edl_window < 0 || o->edl_window > PCR_DISPLAY_MAX_EDL_WINDOW)
+        return set_err(c, PCR_E_ARG, "display edl_window %d outside [0, %d]", o->edl_window, PCR_DISPLAY_MAX_EDL_WINDOW);
+    if (o->edl_window > 0 && !(o->edl_strength >= 0.0f && o->edl_strength <= FLT_MAX))
+        return set_err(c, PCR_E_ARG, "display edl_strength must be finite and >= 0");
+    if (o->reserved != 0) return set_err(c, PCR_E_ARG, "display options: reserved must be 0");
+    DisplayArgs a{};
+    a.width = c->width; a.height = c->height;
+    a.window = o->window; a.edl_window = o->edl_window; a.edl_strength = o->edl_strength;
+    a.show_num_points = p->show_num_points; a.colorize_chunks = p->colorize_chunks;
+    a.empty = c->empty_key;
+    a.fb = c->fb; a.rg = c->rg; a.ba = c->ba;
+    a.rgba_points = c->d_point_rgba;
+    a.rgba = c->d_rgba;
+    const dim3 grid((unsigned)((c->width + DISPLAY_TW - 1) / DISPLAY_TW), (unsigned)((c->height + DISPLAY_TH - 1) / DISPLAY_TH));
+    const bool edl = o->edl_window > 0;
+#define PCR_DISPLAY_LAUNCH(M) \
+    do { if (edl) hipLaunchKernelGGL((k_resolve_display<M, true>), grid, dim3(DISPLAY_THREADS), 0, c->stream, a); \
+         else     hipLaunchKernelGGL((k_resolve_display<M, false>), grid, dim3(DISPLAY_THREADS), 0, c->stream, a); } while (0)
+    if (method == DISPLAY_BASIC)    PCR_DISPLAY_LAUNCH(DISPLAY_BASIC);
+    else if (method == DISPLAY_HQS) PCR_DISPLAY_LAUNCH(DISPLAY_HQS);
+    else                            PCR_DISPLAY_LAUNCH(DISPLAY_LAS);
+#undef PCR_DISPLAY_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    return PCR_OK;
+}
+int pcr_resolve_basic_display(pcr_ctx *c, const pcr_render_params *p, const pcr_display_opts *o) { return launch_resolve_display(c, p, o, DISPLAY_BASIC); }
+int pcr_resolve_hqs_display(pcr_ctx *c, const pcr_render_params *p, const pcr_display_opts *o) { return launch_resolve_display(c, p, o, DISPLAY_HQS); }
+int pcr_resolve_las_display(pcr_ctx *c, const pcr_render_params *p, const pcr_display_opts *o) { return launch_resolve_display(c, p, o, DISPLAY_LAS); }
 
 int pcr_get_stats(pcr_ctx *c, pcr_render_stats *out)
 {

@@ -3132,6 +3132,200 @@ __global__ void __launch_bounds__(256) k_resolve(int show_num_points, int colori
     rgba[pix] = color;
 }
 
+// ------------------------------------------------------------------------------------------------
+// display resolve (pcr_resolve_*_display): n x n point size and eye-dome lighting, after the resolve of the reference's GLSL
+// 10-10-10 method (compute_loop_las/resolve.cs:98-128 the window loop, :41-62 and :143-185 EDL). Not in its CUDA methods.
+// ------------------------------------------------------------------------------------------------
+// Point size is a stencil over the FINISHED framebuffer: the u64 minimum of the words of a pixel's (2w+1)^2 window is the word
+// the 64-bit atomicMin would have left there had every point been drawn as a square of that size, so the render kernels stay
+// as they are and the cost is O(pixels). One workgroup per 64 x 16 tile:
+//   1. the tile's words with a halo of R = window + edl_window pixels go to LDS, row by row, 16-byte loads where the pair is
+//      aligned and inside the row; slots outside the image hold the empty word (windows are clipped to the image)
+//   2. minimum over the row window into a second array, 3. over the column window (2 (2w+1) comparisons for (2w+1)^2)
+//   4. EDL: the dilated words of the tile and a halo of edl_window go to a third array; a pixel reads its neighbours' depths there
+// Lanes walk a row, so the 8-byte LDS reads of a wave are to consecutive addresses: conflict-free in both halves of the wave.
+// (The pair load's two stores per lane are 16 bytes apart: the 8 % of bank-conflict cycles profiles/README.md reports.)
+// The HQS colour of a pixel: the rg/ba sums of the window's pixels whose OWN front depth passes the 1 % test against the dilated
+// depth, gathered from global memory (neighbouring lanes read neighbouring words; the tile's rows are in L2 from step 1's pass).
+enum { DISPLAY_BASIC = 0, DISPLAY_HQS = 1, DISPLAY_LAS = 2 };
+enum { DISPLAY_TW = 64, DISPLAY_TH = 16, DISPLAY_THREADS = 256,
+       DISPLAY_MAX_HALO = PCR_DISPLAY_MAX_WINDOW + PCR_DISPLAY_MAX_EDL_WINDOW,
+       DISPLAY_PITCH = DISPLAY_TW + 2 * DISPLAY_MAX_HALO, DISPLAY_ROWS = DISPLAY_TH + 2 * DISPLAY_MAX_HALO };
+static_assert(DISPLAY_TW == 64 && DISPLAY_THREADS == 4 * 64 && DISPLAY_TH % 4 == 0, "a wave per row of the tile, four rows per wave");
+static_assert(DISPLAY_PITCH / 2 + 1 <= 64 && DISPLAY_ROWS % 4 == 0, "a row's pairs are loaded by one wave, the rows dealt out to four");
+
+struct DisplayArgs {
+    int width, height;
+    int window, edl_window;
+    float edl_strength;
+    int show_num_points, colorize_chunks;
+    uint64_t empty;
+    const uint64_t *fb, *rg, *ba;
+    const uint32_t *rgba_points;
+    uint32_t *rgba;
+};
+
+// Minimum of the 2 w + 1 words p[0], p[stride], ...: the loop unrolled per window, so that its LDS reads are all in flight at once
+// (w is uniform: a scalar branch).
+template <int WN>
+__device__ __forceinline__ uint64_t display_min_run(const uint64_t *p, int stride)
+{
+    uint64_t m = p[0];
+#pragma unroll
+    for (int k = 1; k <= 2 * WN; ++k) m = min(m, p[k * stride]);
+    return m;
+}
+__device__ __forceinline__ uint64_t display_min_run(const uint64_t *p, int stride, int w)
+{
+    static_assert(PCR_DISPLAY_MAX_WINDOW == 4, "one case per window");
+    switch (w) {
+    case 1: return display_min_run<1>(p, stride);
+    case 2: return display_min_run<2>(p, stride);
+    case 3: return display_min_run<3>(p, stride);
+    case 4: return display_min_run<4>(p, stride);
+    default: return p[0];
+    }
+}
+
+template <int METHOD, bool EDL>
+__global__ void __launch_bounds__(DISPLAY_THREADS) k_resolve_display(DisplayArgs a)
+{
+    __shared__ uint64_t s_fb[DISPLAY_ROWS * DISPLAY_PITCH];              // the undilated words
+    __shared__ uint64_t s_h[DISPLAY_ROWS * DISPLAY_PITCH];               // minimum over the row window
+    __shared__ uint64_t s_d[EDL ? DISPLAY_ROWS * DISPLAY_PITCH : 1];     // the dilated words (EDL reads its neighbours' here)
+    const int W = a.width, H = a.height, w = a.window, e = EDL ? a.edl_window : 0, R = w + e;
+    const int LW = DISPLAY_TW + 2 * R, LH = DISPLAY_TH + 2 * R;
+    const int x0 = (int)blockIdx.x * DISPLAY_TW - R, y0 = (int)blockIdx.y * DISPLAY_TH - R;    // image position of LDS slot (0, 0)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t empty = a.empty;
+
+    // 1. load: a wave per row, a lane per aligned pair of words; every load of the wave is issued before the first LDS store, so
+    // a wave waits for memory once, not once per row
+    uint64_t v0[DISPLAY_ROWS / 4], v1[DISPLAY_ROWS / 4];
+#pragma unroll
+    for (int i = 0; i < DISPLAY_ROWS / 4; ++i) {
+        const int ly = wave + 4 * i, gy = y0 + ly;
+        const long long g0 = (long long)gy * W + x0;                     // linear index of the row's slot 0 (may lie left of the row)
+        const int lx = (int)(((g0 >> 1) + lane) * 2 - g0);               // -1 or 0 for lane 0: the pair's first slot
+        const int gx = x0 + lx;
+        const bool row = ly < LH && gy >= 0 && gy < H;
+        const bool in0 = row && lx >= 0 && lx < LW && gx >= 0 && gx < W, in1 = row && lx + 1 < LW && gx + 1 >= 0 && gx + 1 < W;
+        v0[i] = empty; v1[i] = empty;
+        const uint64_t *src = a.fb + (g0 + lx);
+        if (in0 && in1) { const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(src); v0[i] = v.x; v1[i] = v.y; }
+        else if (in0) v0[i] = src[0];
+        else if (in1) v1[i] = src[1];
+    }
+#pragma unroll
+    for (int i = 0; i < DISPLAY_ROWS / 4; ++i) {
+        const int ly = wave + 4 * i;
+        const long long g0 = (long long)(y0 + ly) * W + x0;
+        const int lx = (int)(((g0 >> 1) + lane) * 2 - g0);
+        if (ly < LH && lx >= 0 && lx < LW) s_fb[ly * DISPLAY_PITCH + lx] = v0[i];
+        if (ly < LH && lx + 1 < LW) s_fb[ly * DISPLAY_PITCH + lx + 1] = v1[i];
+    }
+    __syncthreads();
+
+    // 2. minimum over the row window: every row, columns [w, LW - w)
+    const uint64_t *rows = s_fb;
+    if (w > 0) {
+        const uint32_t cw = (uint32_t)(LW - 2 * w), n = cw * (uint32_t)LH;
+        const float inv_cw = 1.0f / (float)cw;
+        for (uint32_t i = threadIdx.x; i < n; i += DISPLAY_THREADS) {
+            uint32_t y, x;
+            window_row_col(i, cw, inv_cw, y, x);
+            const uint64_t *p = s_fb + y * DISPLAY_PITCH + x;            // slot x of the window that is centred on column x + w
+            s_h[y * DISPLAY_PITCH + x + w] = display_min_run(p, 1, w);
+        }
+        __syncthreads();
+        rows = s_h;
+    }
+    // 3. minimum over the column window at slot (lx, ly), w <= lx < LW - w, w <= ly < LH - w: the dilated word
+    auto dilated = [&](int lx, int ly) {
+        return display_min_run(rows + (ly - w) * DISPLAY_PITCH + lx, DISPLAY_PITCH, w);
+    };
+    if (EDL) {
+        const uint32_t cw = (uint32_t)(DISPLAY_TW + 2 * e), n = cw * (uint32_t)(DISPLAY_TH + 2 * e);
+        const float inv_cw = 1.0f / (float)cw;
+        for (uint32_t i = threadIdx.x; i < n; i += DISPLAY_THREADS) {
+            uint32_t y, x;
+            window_row_col(i, cw, inv_cw, y, x);
+            const int lx = (int)x + w, ly = (int)y + w, gx = x0 + lx, gy = y0 + ly;
+            // (a slot outside the image is no pixel: its window reaches into the image, its word stays empty)
+            s_d[ly * DISPLAY_PITCH + lx] = gx >= 0 && gx < W && gy >= 0 && gy < H ? dilated(lx, ly) : empty;
+        }
+        __syncthreads();
+    }
+
+    // the pixels: a wave per row, four rows per wave
+    const int px = (int)blockIdx.x * DISPLAY_TW + lane;
+    if (px >= W) return;
+    for (int k = 0; k < DISPLAY_TH / 4; ++k) {
+        const int ty = wave * (DISPLAY_TH / 4) + k, py = (int)blockIdx.y * DISPLAY_TH + ty;
+        if (py >= H) break;
+        const int lx = lane + R, ly = ty + R;
+        const uint64_t D = EDL ? s_d[ly * DISPLAY_PITCH + lx] : dilated(lx, ly);
+        const uint32_t id = (uint32_t)D;
+        uint32_t color = PCR_BACKGROUND_COLOR;
+        if (METHOD == DISPLAY_LAS) {
+            if (id < 0x7FFFFFFFu) color = a.rgba_points[id];
+        } else if (id < 0xFFFFFFFFu) {
+            if (a.show_num_points) {
+                const double div = METHOD == DISPLAY_HQS ? 512.0 : 64.0;
+                const uint32_t shade = (uint32_t)(((double)(float)(int)id / div) * 255.0);
+                color = (shade << 24) | (shade << 16) | (shade << 8) | shade;
+            } else if (a.colorize_chunks) {
+                color = id * 1234567u;
+            } else if (METHOD == DISPLAY_HQS) {
+                // the sums of the window's pixels that are drawn and whose own depth is within 1 % of the dilated depth
+                // (w <= d * 1.01f, one rounded f32 product: color.cs:370); slots outside the image are empty
+                const float limit = __uint_as_float((uint32_t)(D >> 32)) * 1.01f;
+                uint64_t vrg = 0, vba = 0;
+                for (int oy = -w; oy <= w; ++oy) {
+                    const uint64_t *p = s_fb + (ly + oy) * DISPLAY_PITCH + lx;
+                    const size_t g = (size_t)(py + oy) * (size_t)W + (size_t)px;
+                    for (int ox = -w; ox <= w; ++ox) {
+                        const uint64_t own = p[ox];
+                        if (own != empty && __uint_as_float((uint32_t)(own >> 32)) <= limit) {
+                            vrg += a.rg[g + ox];
+                            vba += a.ba[g + ox];
+                        }
+                    }
+                }
+                const uint32_t cnt = (uint32_t)vba;
+                if (cnt == 0) color = 0;
+                else color = (((uint32_t)(vba >> 32) / cnt) << 16) | (((uint32_t)vrg / cnt) << 8) | ((uint32_t)(vrg >> 32) / cnt);
+            } else {
+                color = id;
+            }
+        }
+        if (EDL && D != empty) {
+            // resolve.cs:143-185 on the dilated depths: every f32 operation a statement of its own, none contracts
+            const float dc = __uint_as_float((uint32_t)(D >> 32));
+            float sum = 0.0f;
+            for (int ox = -e; ox <= e; ++ox)
+                for (int oy = -e; oy <= e; ++oy) {
+                    const uint64_t nb = s_d[(ly + oy) * DISPLAY_PITCH + lx + ox];      // outside the image: empty
+                    float t = 0.0f;
+                    if (nb != empty) {
+                        const float diff = __fsub_rn(dc, __uint_as_float((uint32_t)(nb >> 32)));
+                        t = fmaxf(0.0f, diff);
+                    }
+                    sum = __fadd_rn(sum, t);
+                }
+            const float cells = (float)((2 * e + 1) * (2 * e + 1));
+            const float response = __fdiv_rn(sum, cells);
+            const float scaled = __fmul_rn(-response, 300.0f);
+            const float shade = expf(__fmul_rn(scaled, a.edl_strength));
+            const uint32_t r = (uint32_t)__fmul_rn((float)(color & 255u), shade);
+            const uint32_t g = (uint32_t)__fmul_rn((float)((color >> 8) & 255u), shade);
+            const uint32_t b = (uint32_t)__fmul_rn((float)((color >> 16) & 255u), shade);
+            color = r | (g << 8) | (b << 16);
+        }
+        a.rgba[(size_t)py * (size_t)W + (size_t)px] = color;
+    }
+}
+
 // RESOLVE of the finished frame, CLEAR for the next one and the next frame's cull/LOD prepass in ONE launch (pcr_frame_turn):
 // the reference's frame ends with resolve + clear (huffman_hqs.h:240-270); done separately they are two passes over the
 // framebuffer and two launches (21 us of a 269 us frame at 1080p), fused one pass reads every word once, writes the pixel,

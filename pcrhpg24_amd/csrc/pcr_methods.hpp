@@ -22,6 +22,7 @@
 #include <fstream>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -134,6 +135,9 @@ struct Resource {
 
 struct Method {
     std::string name = "no name", description = "", group = "no group";
+    // Set: the frame's resolve is the display resolve (pcr_resolve_*_display) with these options; nothing else in the frame changes.
+    // Not in the reference's Method; read by the Huffman and the 10-10-10 methods below.
+    std::optional<pcr_display_opts> display;
     virtual ~Method() = default;
     virtual void update(Renderer *renderer) = 0;
     virtual void render(Renderer *renderer) = 0;
@@ -411,7 +415,8 @@ struct HuffmanMemIter : HuffmanMethodBase {
         lastParams = r->params();
         r->check(pcr_frame_begin(r->ctx, &lastParams, PCR_METHOD_BASIC), "pcr_frame_begin");   // CLEAR + cull/LOD prepass
         r->check(pcr_render_basic(r->ctx, &lastParams), "pcr_render_basic");
-        r->check(pcr_resolve_basic(r->ctx, &lastParams), "pcr_resolve_basic");
+        if (display) r->check(pcr_resolve_basic_display(r->ctx, &lastParams, &*display), "pcr_resolve_basic_display");
+        else r->check(pcr_resolve_basic(r->ctx, &lastParams), "pcr_resolve_basic");
     }
 };
 
@@ -468,7 +473,8 @@ struct HuffmanHQS : HuffmanMethodBase {
             dumpDepthMap(r, r->ctx, r->width, r->height, Debug::depthMapPath);
             Debug::saveDepthMap = false;
         }
-        r->check(pcr_resolve_hqs(r->ctx, &lastParams), "pcr_resolve_hqs");
+        if (display) r->check(pcr_resolve_hqs_display(r->ctx, &lastParams, &*display), "pcr_resolve_hqs_display");
+        else r->check(pcr_resolve_hqs(r->ctx, &lastParams), "pcr_resolve_hqs");
     }
 };
 
@@ -551,7 +557,8 @@ struct ComputeLoopLasCUDA : Method {                                            
         lastParams = r->params();
         r->check(pcr_clear(r->ctx), "pcr_clear");
         r->check(pcr_render_las(r->ctx, &lastParams), "pcr_render_las");
-        r->check(pcr_resolve_las(r->ctx, &lastParams), "pcr_resolve_las");
+        if (display) r->check(pcr_resolve_las_display(r->ctx, &lastParams, &*display), "pcr_resolve_las_display");
+        else r->check(pcr_resolve_las(r->ctx, &lastParams), "pcr_resolve_las");
     }
 };
 
@@ -570,7 +577,8 @@ struct ComputeLoopLasHQS : ComputeLoopLasCUDA {                                 
         r->check(pcr_clear(r->ctx), "pcr_clear");
         r->check(pcr_render_las_hqs_depth(r->ctx, &lastParams), "pcr_render_las_hqs_depth");   // DEPTH   (:172-196)
         r->check(pcr_render_las_hqs_color(r->ctx, &lastParams), "pcr_render_las_hqs_color");   // COLORS  (:199-223)
-        r->check(pcr_resolve_hqs(r->ctx, &lastParams), "pcr_resolve_hqs");                     // RESOLVE (:226-245)
+        if (display) r->check(pcr_resolve_hqs_display(r->ctx, &lastParams, &*display), "pcr_resolve_hqs_display");
+        else r->check(pcr_resolve_hqs(r->ctx, &lastParams), "pcr_resolve_hqs");                     // RESOLVE (:226-245)
     }
 };
 

@@ -7,6 +7,9 @@
 //              [--async-load]   (.huffman: copies on the loader stream, frames draw what has arrived)
 //              [--pick X Y [R]]   (.huffman: the point under pixel (X, Y) of the view, within R pixels, pcr_pick; one line
 //                                  "pick x= y= z= color= index= pixel= px= py= depth_bits=" or "pick none")
+//              [--window N] [--edl STRENGTH] [--edl-window N]   (display resolve, pcr_resolve_*_display: points of (2N+1)^2 pixels,
+//                                  N <= 4; eye-dome lighting of the given strength over a window of 1 (default) or 2 pixels;
+//                                  --dump-rgba then writes the display image)
 //              [--dump-fb fb.u64] [--dump-rgba out.ppm] [--dump-depth depth.exr]   (depth: huffman_hqs only, huffman_hqs.h:217-237)
 // Prints one JSON line: batches, frames needed to load, ms of the last frame, FNV-1a of the u64 framebuffer.
 #include <cerrno>
@@ -28,6 +31,16 @@ static uint64_t fnv1a(const void *p, size_t n)
     return h;
 }
 
+static bool parse_strength(const char *a, float &v)      // a finite float >= 0, the whole argument
+{
+    char *end = nullptr;
+    errno = 0;
+    const float x = std::strtof(a, &end);
+    if (end == a || *end != '\0' || errno == ERANGE || !(x >= 0.0f) || !std::isfinite(x)) return false;
+    v = x;
+    return true;
+}
+
 static bool parse_int(const char *a, long lo, long hi, int &v)
 {
     char *end = nullptr;
@@ -43,7 +56,8 @@ int main(int argc, char **argv)
     if (argc < 2) { std::fprintf(stderr, "usage: pcr_render <file.huffman> [options]\n"); return 2; }
     std::string path = argv[1], method = "huffman_mem_iter_cuda", dump_fb, dump_rgba, dump_depth;
     int w = 1920, h = 1080, frames = 0;
-    bool async_load = false, do_pick = false;
+    bool async_load = false, do_pick = false, have_edl = false, have_edl_window = false;
+    pcr_display_opts display{};                 // --window / --edl / --edl-window
     int pick[3] = {0, 0, 0};                    // X Y R
     // src/main.cpp:192-218 default setting ("morrobay" overview)
     double cam[6] = {-0.15, -0.57, 3166.32, 2239.05, 1713.63, -202.02};
@@ -69,11 +83,27 @@ int main(int argc, char **argv)
             i += third ? 3 : 2;
             do_pick = true;
         }
+        else if (a == "--window") {
+            need(1);
+            if (!parse_int(argv[++i], 0, PCR_DISPLAY_MAX_WINDOW, display.window)) { std::fprintf(stderr, "usage: --window N: an integer in [0, %d]\n", PCR_DISPLAY_MAX_WINDOW); return 2; }
+        }
+        else if (a == "--edl") {
+            need(1);
+            if (!parse_strength(argv[++i], display.edl_strength)) { std::fprintf(stderr, "usage: --edl STRENGTH: a finite number >= 0\n"); return 2; }
+            have_edl = true;
+        }
+        else if (a == "--edl-window") {
+            need(1);
+            if (!parse_int(argv[++i], 1, PCR_DISPLAY_MAX_EDL_WINDOW, display.edl_window)) { std::fprintf(stderr, "usage: --edl-window N: an integer in [1, %d]\n", PCR_DISPLAY_MAX_EDL_WINDOW); return 2; }
+            have_edl_window = true;
+        }
         else if (a == "--dump-fb") { need(1); dump_fb = argv[++i]; }
         else if (a == "--dump-rgba") { need(1); dump_rgba = argv[++i]; }
         else if (a == "--dump-depth") { need(1); dump_depth = argv[++i]; }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
+    if (have_edl_window && !have_edl) { std::fprintf(stderr, "--edl-window needs --edl STRENGTH\n"); return 2; }
+    if (have_edl && !have_edl_window) display.edl_window = 1;
     if (do_pick && (method == "loop_las_cuda" || method == "loop_las_hqs")) { std::fprintf(stderr, "--pick needs a .huffman stream and one of its methods\n"); return 2; }
     try {
         Renderer renderer(w, h, 0);
@@ -102,6 +132,7 @@ int main(int argc, char **argv)
         Runtime::setSelectedMethod(method);
         Method *selected = Runtime::getSelectedMethod();
         if (!selected) { std::fprintf(stderr, "no method named %s\n", method.c_str()); return 2; }
+        if (display.window > 0 || have_edl) selected->display = display;
 
         int n = 0;
         double ms = 0;

@@ -28,7 +28,7 @@ from typing import Iterator, Optional
 import numpy as np
 
 from . import _native as N
-from ._native import Box, EncodeStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, XyzBatch, c_i64, fb_elems
+from ._native import Box, DisplayOpts, EncodeStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, XyzBatch, c_i64, fb_elems
 
 POINTS_PER_BATCH = 65536
 ENCODED_PAD_WORDS = 1024
@@ -501,6 +501,20 @@ class Context:
     def resolve_hqs(self, p: RenderParams):
         self._chk(self.lib.pcr_resolve_hqs(self.h, C.byref(p)), "pcr_resolve_hqs")
 
+    # -- display resolves (pcr_resolve_*_display): n x n point size and eye-dome lighting ------------------
+    def resolve_basic_display(self, p: RenderParams, opts: DisplayOpts):
+        """resolve_basic with every point (2 * opts.window + 1)^2 pixels large and, with opts.edl_window > 0, eye-dome lighting
+        (pcr_hip.h states the arithmetic). Writes the image only; zero opts give resolve_basic's bytes."""
+        self._chk(self.lib.pcr_resolve_basic_display(self.h, C.byref(p), C.byref(opts) if opts is not None else None), "pcr_resolve_basic_display")
+
+    def resolve_hqs_display(self, p: RenderParams, opts: DisplayOpts):
+        """The same for resolve_hqs: the sums of the window's pixels within 1 % of the dilated depth are averaged."""
+        self._chk(self.lib.pcr_resolve_hqs_display(self.h, C.byref(p), C.byref(opts) if opts is not None else None), "pcr_resolve_hqs_display")
+
+    def resolve_las_display(self, p: RenderParams, opts: DisplayOpts):
+        """The same for resolve_las."""
+        self._chk(self.lib.pcr_resolve_las_display(self.h, C.byref(p), C.byref(opts) if opts is not None else None), "pcr_resolve_las_display")
+
     def synchronize(self):
         self._chk(self.lib.pcr_synchronize(self.h), "pcr_synchronize")
 
@@ -940,6 +954,7 @@ class HuffmanLasData(Resource):
 
 class _HuffmanMethod(Method):
     group = "none"
+    display: Optional[DisplayOpts] = None     # set: the frame's resolve is the display resolve with these options
 
     def __init__(self, renderer: Renderer, las: HuffmanLasData):
         self.renderer, self.las = renderer, las
@@ -967,7 +982,10 @@ class HuffmanMemIter(_HuffmanMethod):
         ctx = renderer.ctx
         ctx.frame_begin(p)            # CLEAR (of the previous frame) + the cull/LOD prepass, one launch
         ctx.render_basic(p)           # RENDER
-        ctx.resolve_basic(p)          # RESOLVE
+        if self.display is not None:  # RESOLVE
+            ctx.resolve_basic_display(p, self.display)
+        else:
+            ctx.resolve_basic(p)
         self.last_params = p
 
 
@@ -991,7 +1009,10 @@ class HuffmanHQS(_HuffmanMethod):
         ctx.frame_begin(p, hqs=True)
         ctx.render_hqs_depth(p)
         ctx.render_hqs_color(p)
-        ctx.resolve_hqs(p)
+        if self.display is not None:
+            ctx.resolve_hqs_display(p, self.display)
+        else:
+            ctx.resolve_hqs(p)
         self.last_params = p
 
 
@@ -1056,6 +1077,7 @@ class ComputeLoopLasCUDA(Method):
     name = "loop_las_cuda"
     description = "- Each thread renders X points.\n- Loads points from LAS file\n- encodes point coordinates in 10+10+10 bits"
     group = "10-10-10 bit encoded"
+    display: Optional[DisplayOpts] = None     # set: the frame's resolve is the display resolve with these options
 
     def __init__(self, renderer: Renderer, las: ComputeLasData):
         self.renderer, self.las = renderer, las
@@ -1075,7 +1097,10 @@ class ComputeLoopLasCUDA(Method):
         ctx = renderer.ctx
         ctx.clear()
         ctx.render_las(p)
-        ctx.resolve_las(p)
+        if self.display is not None:
+            ctx.resolve_las_display(p, self.display)
+        else:
+            ctx.resolve_las(p)
         self.last_params = p
 
 
@@ -1095,5 +1120,8 @@ class ComputeLoopLasHQS(ComputeLoopLasCUDA):
         ctx.clear()
         ctx.render_las_hqs_depth(p)   # DEPTH   (:172-196)
         ctx.render_las_hqs_color(p)   # COLORS  (:199-223)
-        ctx.resolve_hqs(p)            # RESOLVE (:226-245)
+        if self.display is not None:  # RESOLVE (:226-245)
+            ctx.resolve_hqs_display(p, self.display)
+        else:
+            ctx.resolve_hqs(p)
         self.last_params = p
