@@ -264,6 +264,42 @@ int pcr_read_screen(pcr_ctx *ctx, const pcr_render_params *params, const pcr_rec
 int pcr_pick(pcr_ctx *ctx, const pcr_render_params *params, int px, int py, int radius, pcr_point *out_point,
              pcr_screen_hit *out_hit, int *out_found);
 
+/* ---- top-down grid: the stream rasterized into height / colour / density planes (no reference counterpart) ------------------
+ * CONTRACT: after pcr_grid_clear and pcr_grid_accumulate over a range, every cell of a plane holds the max / min / count
+ * (pcr_grid in pcr_types.h) over exactly the records pcr_decode_points writes for that range that fall into the cell and into
+ * *clip -- padding duplicates and the tail artefact included; BC1 and BC7, either resident layout, before and after the first
+ * frame. Max, min and add do not depend on the order, so the planes are exact and the same from run to run. One pass over the
+ * compressed stream; no record is written anywhere.
+ *
+ * The planes are device arrays of width * height cells, row cy at cy * width: dev_top / dev_bottom uint64 (8-byte aligned),
+ * dev_count uint32 (4-byte aligned). Any of them may be NULL: that plane is left out (with neither top nor bottom the colours
+ * are not decoded).
+ * pcr_grid_clear: the empty values into the planes given. Only enqueues.
+ * pcr_grid_accumulate: the points of batches [first_batch, first_batch + count) into the planes, on top of what they hold, so
+ *   several ranges, shards, contexts or streams can fill one grid (order the calls of different contexts yourself). Range
+ *   semantics, count < 0 and the restriction under pcr_set_async_upload are pcr_decode_points'. Points outside *clip (NULL: no
+ *   clip) are ignored. The host puts every batch into a class from its exact box (pcr_batch_point_bounds' cache, filled on first
+ *   use: that call synchronises) against grid and clip: outside -- the box misses them on x, y or z, the batch is not decoded;
+ *   windowed -- the rectangle of cells the box covers inside them has at most PCR_GRID_WINDOW_CELLS cells: the workgroup
+ *   accumulates in LDS and merges with one global atomic per non-empty cell and plane; direct -- more cells than that: a global
+ *   atomic per point and plane. PCR_GRID_NO_WINDOW in flags makes every batch that is not outside direct. *stats (may be NULL)
+ *   tells the three counts. With the boxes cached the call only enqueues (a list of a few words per batch is uploaded). Touches
+ *   no framebuffer, no prepass state, no render statistics. All three planes NULL: PCR_OK, no work, *stats zero. An empty clip,
+ *   or a range of 0 batches: PCR_OK, every batch outside.
+ * pcr_grid_unpack: per cell of dev_words (a top or a bottom plane, `which` = PCR_GRID_TOP / PCR_GRID_BOTTOM tells the empty
+ *   value) dev_height[i] = z of the word, INT32_MIN for an empty cell; dev_rgba[i] = colour | 0xFF000000, 0 for an empty cell.
+ *   Either output may be NULL. Only enqueues.
+ * pcr_read_grid: clear + accumulate + copy to the host (any of the three may be NULL) through scratch memory of the context,
+ *   grown on demand and released with it. Synchronises.
+ * PCR_E_ARG with a message, nothing written: no stream loaded, a range outside the resident batches, a NULL grid, cell < 1,
+ * width or height < 1, more than PCR_GRID_MAX_CELLS cells, reserved != 0, unknown flag bits or `which`, a misaligned pointer. */
+int pcr_grid_clear(pcr_ctx *ctx, const pcr_grid *grid, void *dev_top, void *dev_bottom, void *dev_count);
+int pcr_grid_accumulate(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_grid *grid, const pcr_box *clip,
+                        void *dev_top, void *dev_bottom, void *dev_count, uint32_t flags, pcr_grid_stats *stats);
+int pcr_grid_unpack(pcr_ctx *ctx, const pcr_grid *grid, const void *dev_words, int which, void *dev_height, void *dev_rgba);
+int pcr_read_grid(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_grid *grid, const pcr_box *clip,
+                  uint64_t *host_top, uint64_t *host_bottom, uint32_t *host_count, uint32_t flags, pcr_grid_stats *stats);
+
 /* What a collective library needs to merge partial frames in place (include/pcr_dist.h does it with RCCL): the HIP stream
  * the context enqueues on, its device ordinal and the length of each framebuffer in 64-bit words. */
 void *pcr_get_stream(pcr_ctx *ctx);

@@ -134,6 +134,32 @@ typedef struct pcr_select_stats {
     int64_t points_selected;
 } pcr_select_stats;
 
+/* A top-down grid over the stream's int32 x and y (pcr_grid_accumulate), 24 bytes. A point (x, y, z, colour) belongs to cell
+ * (cx, cy) iff x >= origin_x, y >= origin_y, cx = (uint32)(x - origin_x) / cell < width and cy = (uint32)(y - origin_y) / cell
+ * < height (the differences fit 32 unsigned bits for every int32 input); the cell's index in a plane is cx + cy * width.
+ * A cell of a plane holds, with the key K = (uint64)((uint32)z ^ 0x80000000u) << 32 | colour (unsigned order of K = signed
+ * order of z, ties in z decided by the colour: the whole word, as at depth ties in a frame):
+ *   top     uint64  unsigned max of K over the cell's points   empty: 0
+ *   bottom  uint64  unsigned min of K                          empty: all ones
+ *   count   uint32  number of points, modulo 2^32              empty: 0 */
+#define PCR_GRID_MAX_CELLS     (1 << 26)  /* width * height */
+#define PCR_GRID_WINDOW_CELLS  4096       /* largest per-batch footprint accumulated in LDS */
+#define PCR_GRID_NO_WINDOW     1          /* flags bit: every batch straight to global atomics */
+#define PCR_GRID_TOP           0
+#define PCR_GRID_BOTTOM        1
+typedef struct pcr_grid {
+    int32_t origin_x, origin_y;  /* min corner of cell (0, 0) */
+    int32_t cell;                /* edge length, >= 1 */
+    int32_t width, height;       /* cells, >= 1; width * height <= PCR_GRID_MAX_CELLS */
+    int32_t reserved;            /* 0 */
+} pcr_grid;
+
+/* What pcr_grid_accumulate did with the batches of its range, by their exact box against grid and clip: outside (not decoded),
+ * windowed (accumulated in LDS, then merged), direct (global atomics per point). */
+typedef struct pcr_grid_stats {
+    int64_t batches_outside, batches_windowed, batches_direct;
+} pcr_grid_stats;
+
 /* A rectangle of pixels (pcr_select_screen), bounds inclusive, clipped to the image by the call. x0 > x1 or y0 > y1: the
  * empty rect. */
 typedef struct pcr_rect {

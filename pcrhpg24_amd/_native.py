@@ -68,6 +68,20 @@ class SelectStats(C.Structure):                   # pcr_select_stats
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class Grid(C.Structure):                          # pcr_grid: a top-down grid over the stream's int32 x and y, 24 bytes
+    _fields_ = [(n, c_i32) for n in ("origin_x", "origin_y", "cell", "width", "height", "reserved")]
+
+
+class GridStats(C.Structure):                     # pcr_grid_stats
+    _fields_ = [(n, c_i64) for n in ("batches_outside", "batches_windowed", "batches_direct")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+GRID_MAX_CELLS, GRID_WINDOW_CELLS, GRID_NO_WINDOW, GRID_TOP, GRID_BOTTOM = 1 << 26, 4096, 1, 0, 1      # pcr_types.h
+
+
 class Rect(C.Structure):                          # pcr_rect: pixel bounds, inclusive; x0 > x1 or y0 > y1 = empty
     _fields_ = [(n, c_i32) for n in ("x0", "y0", "x1", "y1")]
 
@@ -98,6 +112,7 @@ class EncodeStats(C.Structure):                   # pcr_encode_stats
 assert C.sizeof(Point) == 16 and C.sizeof(Box) == 24 and C.sizeof(SelectStats) == 32
 assert C.sizeof(Rect) == 16 and C.sizeof(ScreenHit) == 16 and C.sizeof(ScreenStats) == 32
 assert C.sizeof(DisplayOpts) == 16
+assert C.sizeof(Grid) == 24 and C.sizeof(GridStats) == 24
 assert C.sizeof(XyzBatch) == 64 and C.sizeof(GpuBatch) == 160 and C.sizeof(FileHeader) == 40 and C.sizeof(RenderParams) == 224
 
 
@@ -121,6 +136,7 @@ HIP_SYMBOLS = [
     "pcr_batch_point_bounds", "pcr_select_box", "pcr_read_box",
     "pcr_select_screen", "pcr_read_screen", "pcr_pick",
     "pcr_resolve_basic_display", "pcr_resolve_hqs_display", "pcr_resolve_las_display",
+    "pcr_grid_clear", "pcr_grid_accumulate", "pcr_grid_unpack", "pcr_read_grid",
 ]
 
 HOST_SYMBOLS = [
@@ -238,6 +254,11 @@ def hip_lib() -> C.CDLL:
         lib.pcr_pick.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_int, C.c_int, C.c_int, C.POINTER(Point), C.POINTER(ScreenHit), C.POINTER(C.c_int)]
         for n in ("pcr_resolve_basic_display", "pcr_resolve_hqs_display", "pcr_resolve_las_display"):
             getattr(lib, n).argtypes = [C.c_void_p, C.POINTER(RenderParams), C.POINTER(DisplayOpts)]
+        lib.pcr_grid_clear.argtypes = [C.c_void_p, C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p]
+        for n in ("pcr_grid_accumulate", "pcr_read_grid"):
+            getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Grid), C.POINTER(Box), C.c_void_p, C.c_void_p, C.c_void_p, c_u32,
+                                        C.POINTER(GridStats)]
+        lib.pcr_grid_unpack.argtypes = [C.c_void_p, C.POINTER(Grid), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _hip = lib
     return _hip
 

@@ -143,6 +143,13 @@ struct pcr_ctx {
     uint32_t *d_scr_totals = nullptr;           // [scr_capacity] ... and per batch
     int64_t *d_scr_offsets = nullptr;           // [scr_capacity] first output record of each (k_screen_write)
     unsigned long long *d_pick = nullptr;       // [PICK_WORDS] pcr_pick: key, index, record, hit
+    // top-down grid (pcr_grid_accumulate / pcr_read_grid): the list of a call's batches with their windows, and pcr_read_grid's planes
+    int64_t grid_capacity = 0;                  // entries d_grid_list holds
+    GridEntry *d_grid_list = nullptr;           // [grid_capacity] the windowed batches of a call, then the direct ones
+    std::vector<GridEntry> h_grid_list;         // what it holds (a call with the same list uploads nothing)
+    bool grid_lds_ready = false;                // hipFuncSetAttribute done for the windowed k_grid launches
+    unsigned char *d_grid_scratch = nullptr;    // pcr_read_grid: top, bottom, count planes back to back
+    size_t grid_scratch_bytes = 0;
     int64_t prepass_batches = 0;
     static constexpr int FENCES = 8;
     hipEvent_t fence[FENCES] = {};              // pcr_fence_record / pcr_fence_wait: device-scope ordering between streams
@@ -240,6 +247,7 @@ void free_stream_buffers(pcr_ctx *c)
     dfree(c->d_sel_list); dfree(c->d_sel_counts); dfree(c->d_sel_totals); dfree(c->d_sel_offsets); c->sel_capacity = 0;
     dfree(c->d_screen_lod); dfree(c->d_scr_list); dfree(c->d_scr_counts); dfree(c->d_scr_totals); dfree(c->d_scr_offsets); c->scr_capacity = 0;
     dfree(c->d_pick);
+    dfree(c->d_grid_list); c->grid_capacity = 0; c->h_grid_list.clear();
 
     if (c->any_generic_pending && c->any_generic_ev) (void)hipEventSynchronize(c->any_generic_ev);
     c->any_generic_pending = false;
@@ -596,6 +604,7 @@ void pcr_destroy(pcr_ctx *c)
     free_frame_buffers(c);
     dfree(c->d_stats);
     dfree(c->d_decode_stage);
+    dfree(c->d_grid_scratch);
     for (int i = 0; i < 2; ++i) {
         if (c->arena[i]) (void)hipHostFree(c->arena[i]);
         if (c->arena_done[i]) (void)hipEventDestroy(c->arena_done[i]);
@@ -1763,6 +1772,202 @@ int pcr_read_box(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_box *
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         written += m;
     }
+    return PCR_OK;
+}
+
+// ---- top-down grid -----------------------------------------------------------------------------
+namespace {
+constexpr size_t GRID_MAX_LDS_BYTES = GRID_TABLE_BYTES + (size_t)PCR_GRID_WINDOW_CELLS * (8 + 8 + 4);
+
+// The checks on a grid and its planes shared by the four entry points (dev: the planes are device pointers with an alignment to keep).
+int grid_check(pcr_ctx *c, const pcr_grid *g, const void *top, const void *bottom, const void *count)
+{
+    if (!g) return set_err(c, PCR_E_ARG, "the grid is NULL");
+    if (g->cell < 1) return set_err(c, PCR_E_ARG, "grid cell of %d: the edge length is at least 1", g->cell);
+    if (g->width < 1 || g->height < 1) return set_err(c, PCR_E_ARG, "grid of %d x %d cells: width and height are at least 1", g->width, g->height);
+    if ((int64_t)g->width * g->height > PCR_GRID_MAX_CELLS)
+        return set_err(c, PCR_E_ARG, "grid of %d x %d cells: more than the %d of PCR_GRID_MAX_CELLS", g->width, g->height, PCR_GRID_MAX_CELLS);
+    if (g->reserved != 0) return set_err(c, PCR_E_ARG, "pcr_grid::reserved is %d, not 0", g->reserved);
+    if (reinterpret_cast<uintptr_t>(top) % 8 != 0 || reinterpret_cast<uintptr_t>(bottom) % 8 != 0)
+        return set_err(c, PCR_E_ARG, "the top / bottom plane is misaligned (8 bytes)");
+    if (reinterpret_cast<uintptr_t>(count) % 4 != 0) return set_err(c, PCR_E_ARG, "the count plane is misaligned (4 bytes)");
+    return PCR_OK;
+}
+
+void grid_launch(pcr_ctx *c, bool windowed, int colour, unsigned nblocks, size_t lds, const GridEntry *list, const GridArgs &a)
+{
+    const StreamView s = make_stream_view(c);
+    const dim3 grid(nblocks), block(PCR_WORKGROUP_SIZE);
+#define PCR_LAUNCH(L, C, W) hipLaunchKernelGGL((k_grid<L, C, W>), grid, block, lds, c->stream, s, list, a)
+#define PCR_LAUNCH_COLOUR(L, W) do { if (colour == SEL_BC7) PCR_LAUNCH(L, SEL_BC7, W); else if (colour == SEL_BC1) PCR_LAUNCH(L, SEL_BC1, W); else PCR_LAUNCH(L, SEL_NO_COLOUR, W); } while (0)
+    if (select_reads_windows(c)) { if (windowed) PCR_LAUNCH_COLOUR(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH_COLOUR(LAYOUT_POINT_WINDOWS, false); }
+    else                         { if (windowed) PCR_LAUNCH_COLOUR(LAYOUT_WORDS, true); else PCR_LAUNCH_COLOUR(LAYOUT_WORDS, false); }
+#undef PCR_LAUNCH_COLOUR
+#undef PCR_LAUNCH
+}
+
+// pcr_grid_accumulate behind its range check: n batches from `first`, the planes checked.
+int grid_accumulate(pcr_ctx *c, int64_t first, int64_t n, const pcr_grid &g, const pcr_box *clip, void *top, void *bottom, void *count,
+                    uint32_t flags, pcr_grid_stats *stats)
+{
+    pcr_grid_stats st{0, 0, 0};
+    if (!top && !bottom && !count) { if (stats) *stats = st; return PCR_OK; }
+    st.batches_outside = n;
+    // grid and clip intersected: a point inside this box has a cell of the grid (the far edges in 64 bits: origin + cell * width
+    // may lie beyond every int32 coordinate)
+    GridArgs a{};
+    const int64_t org[2] = {g.origin_x, g.origin_y}, ext[2] = {g.width, g.height};
+    bool empty = false;
+    for (int k = 0; k < 3; ++k) {
+        int64_t lo = clip ? clip->min[k] : INT32_MIN, hi = clip ? clip->max[k] : INT32_MAX;
+        if (k < 2) { lo = std::max(lo, org[k]); hi = std::min(hi, org[k] + (int64_t)g.cell * ext[k] - 1); }
+        empty = empty || lo > hi;
+        a.q.min[k] = (int32_t)lo; a.q.max[k] = (int32_t)hi;
+    }
+    if (n == 0 || empty) { if (stats) *stats = st; return PCR_OK; }
+    int rc;
+    if ((rc = ensure_point_bounds(c, first, n))) return rc;
+    std::vector<GridEntry> win, dir;
+    uint32_t win_cells = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t *bb = c->h_point_bounds.data() + (first + i) * 6;
+        bool disjoint = false;
+        for (int k = 0; k < 3; ++k) disjoint = disjoint || bb[3 + k] < a.q.min[k] || bb[k] > a.q.max[k];
+        if (disjoint) continue;
+        --st.batches_outside;
+        uint32_t c0[2], c1[2];                              // the cells the batch's box reaches inside grid and clip
+        for (int k = 0; k < 2; ++k) {
+            c0[k] = (uint32_t)(((int64_t)std::max(bb[k], a.q.min[k]) - org[k]) / g.cell);
+            c1[k] = (uint32_t)(((int64_t)std::min(bb[3 + k], a.q.max[k]) - org[k]) / g.cell);
+        }
+        const GridEntry e{(uint32_t)(first + i), c0[0], c0[1], c1[0] - c0[0] + 1, c1[1] - c0[1] + 1};
+        const int64_t cells = (int64_t)e.ww * e.wh;
+        if (cells <= PCR_GRID_WINDOW_CELLS && !(flags & PCR_GRID_NO_WINDOW)) { win.push_back(e); win_cells = std::max(win_cells, (uint32_t)cells); ++st.batches_windowed; }
+        else { dir.push_back(e); ++st.batches_direct; }
+    }
+    if (stats) *stats = st;
+    const size_t nW = win.size(), nD = dir.size();
+    if (nW + nD == 0) return PCR_OK;
+    win.insert(win.end(), dir.begin(), dir.end());
+    if (c->grid_capacity < (int64_t)win.size()) {
+        dfree(c->d_grid_list); c->grid_capacity = 0; c->h_grid_list.clear();
+        const int64_t cap = std::max<int64_t>((int64_t)win.size(), c->hdr.num_batches);
+        if (hipMalloc((void **)&c->d_grid_list, (size_t)cap * sizeof(GridEntry)) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for a list of %lld batches", (long long)cap);
+        c->grid_capacity = cap;
+    }
+    // (a call that repeats the last one's list finds it on the device)
+    if (win.size() != c->h_grid_list.size() || std::memcmp(win.data(), c->h_grid_list.data(), win.size() * sizeof(GridEntry)) != 0) {
+        c->h_grid_list.clear();
+        HIP_TRY(c, hipMemcpyAsync(c->d_grid_list, win.data(), win.size() * sizeof(GridEntry), hipMemcpyHostToDevice, c->stream));
+        c->h_grid_list = win;
+    }
+    if (!c->grid_lds_ready) {
+        hipError_t e = hipSuccess;
+#define PCR_ALLOW(L, C) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_grid<L, C, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GRID_MAX_LDS_BYTES)
+        PCR_ALLOW(LAYOUT_WORDS, SEL_NO_COLOUR); PCR_ALLOW(LAYOUT_WORDS, SEL_BC1); PCR_ALLOW(LAYOUT_WORDS, SEL_BC7);
+        PCR_ALLOW(LAYOUT_POINT_WINDOWS, SEL_NO_COLOUR); PCR_ALLOW(LAYOUT_POINT_WINDOWS, SEL_BC1); PCR_ALLOW(LAYOUT_POINT_WINDOWS, SEL_BC7);
+#undef PCR_ALLOW
+        if (e != hipSuccess) return set_err(c, PCR_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
+        c->grid_lds_ready = true;
+    }
+    a.ox = g.origin_x; a.oy = g.origin_y; a.width = (uint32_t)g.width;
+    const uint32_t cell = (uint32_t)g.cell;
+    if ((cell & (cell - 1)) == 0) { a.shift = (uint32_t)__builtin_ctz(cell); a.magic = 0; }
+    else { a.shift = GRID_NO_SHIFT; a.magic = ~0ull / cell + 1; }         // ceil(2^64 / cell): cell does not divide 2^64
+    a.top = static_cast<unsigned long long *>(top); a.bottom = static_cast<unsigned long long *>(bottom); a.count = static_cast<uint32_t *>(count);
+    a.win_cells = win_cells;
+    const int colour = !top && !bottom ? SEL_NO_COLOUR : c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7 ? SEL_BC7 : SEL_BC1;
+    if (nW) {
+        const size_t lds = GRID_TABLE_BYTES + (size_t)win_cells * ((top ? 8 : 0) + (bottom ? 8 : 0) + (count ? 4 : 0));
+        grid_launch(c, true, colour, (unsigned)nW, lds, c->d_grid_list, a);
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (nD) {
+        grid_launch(c, false, colour, (unsigned)nD, GRID_TABLE_BYTES, c->d_grid_list + nW, a);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return PCR_OK;
+}
+
+void grid_clear(pcr_ctx *c, const pcr_grid &g, void *top, void *bottom, void *count)
+{
+    const uint32_t n = (uint32_t)g.width * (uint32_t)g.height;
+    hipLaunchKernelGGL(k_grid_clear, dim3(std::min<uint32_t>((n + 255) / 256, 2048)), dim3(256), 0, c->stream, static_cast<unsigned long long *>(top),
+                       static_cast<unsigned long long *>(bottom), static_cast<uint32_t *>(count), n);
+}
+} // namespace
+
+int pcr_grid_clear(pcr_ctx *c, const pcr_grid *grid, void *dev_top, void *dev_bottom, void *dev_count)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = grid_check(c, grid, dev_top, dev_bottom, dev_count))) return rc;
+    if (!dev_top && !dev_bottom && !dev_count) return PCR_OK;
+    grid_clear(c, *grid, dev_top, dev_bottom, dev_count);
+    HIP_TRY(c, hipGetLastError());
+    return PCR_OK;
+}
+
+int pcr_grid_accumulate(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_grid *grid, const pcr_box *clip,
+                        void *dev_top, void *dev_bottom, void *dev_count, uint32_t flags, pcr_grid_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int64_t n = 0;
+    int rc = select_range(c, first_batch, count, &n);
+    if (rc) return rc;
+    if ((rc = grid_check(c, grid, dev_top, dev_bottom, dev_count))) return rc;
+    if (flags & ~(uint32_t)PCR_GRID_NO_WINDOW) return set_err(c, PCR_E_ARG, "unknown flag bits 0x%x", flags & ~(uint32_t)PCR_GRID_NO_WINDOW);
+    return grid_accumulate(c, first_batch, n, *grid, clip, dev_top, dev_bottom, dev_count, flags, stats);
+}
+
+int pcr_grid_unpack(pcr_ctx *c, const pcr_grid *grid, const void *dev_words, int which, void *dev_height, void *dev_rgba)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = grid_check(c, grid, dev_words, nullptr, nullptr))) return rc;
+    if (which != PCR_GRID_TOP && which != PCR_GRID_BOTTOM) return set_err(c, PCR_E_ARG, "which is %d, not PCR_GRID_TOP or PCR_GRID_BOTTOM", which);
+    if (!dev_words) return set_err(c, PCR_E_ARG, "the plane to unpack is NULL");
+    if (reinterpret_cast<uintptr_t>(dev_height) % 4 != 0 || reinterpret_cast<uintptr_t>(dev_rgba) % 4 != 0)
+        return set_err(c, PCR_E_ARG, "the height / rgba output is misaligned (4 bytes)");
+    if (!dev_height && !dev_rgba) return PCR_OK;
+    const uint32_t n = (uint32_t)grid->width * (uint32_t)grid->height;
+    hipLaunchKernelGGL(k_grid_unpack, dim3(std::min<uint32_t>((n + 255) / 256, 2048)), dim3(256), 0, c->stream, static_cast<const unsigned long long *>(dev_words),
+                       which == PCR_GRID_TOP ? 0ull : ~0ull, static_cast<int32_t *>(dev_height), static_cast<uint32_t *>(dev_rgba), n);
+    HIP_TRY(c, hipGetLastError());
+    return PCR_OK;
+}
+
+int pcr_read_grid(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_grid *grid, const pcr_box *clip,
+                  uint64_t *host_top, uint64_t *host_bottom, uint32_t *host_count, uint32_t flags, pcr_grid_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int64_t n = 0;
+    int rc = select_range(c, first_batch, count, &n);
+    if (rc) return rc;
+    if ((rc = grid_check(c, grid, nullptr, nullptr, nullptr))) return rc;
+    if (flags & ~(uint32_t)PCR_GRID_NO_WINDOW) return set_err(c, PCR_E_ARG, "unknown flag bits 0x%x", flags & ~(uint32_t)PCR_GRID_NO_WINDOW);
+    const size_t cells = (size_t)grid->width * (size_t)grid->height;
+    if (c->grid_scratch_bytes < cells * 20) {
+        dfree(c->d_grid_scratch); c->grid_scratch_bytes = 0;
+        if (hipMalloc((void **)&c->d_grid_scratch, cells * 20) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for the planes of a grid of %zu cells", cells);
+        c->grid_scratch_bytes = cells * 20;
+    }
+    void *top = host_top ? c->d_grid_scratch : nullptr, *bottom = host_bottom ? c->d_grid_scratch + cells * 8 : nullptr;
+    void *cnt = host_count ? c->d_grid_scratch + cells * 16 : nullptr;
+    if (!top && !bottom && !cnt) return grid_accumulate(c, first_batch, n, *grid, clip, nullptr, nullptr, nullptr, flags, stats);
+    grid_clear(c, *grid, top, bottom, cnt);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = grid_accumulate(c, first_batch, n, *grid, clip, top, bottom, cnt, flags, stats))) return rc;
+    if (top) HIP_TRY(c, hipMemcpyAsync(host_top, top, cells * 8, hipMemcpyDeviceToHost, c->stream));
+    if (bottom) HIP_TRY(c, hipMemcpyAsync(host_bottom, bottom, cells * 8, hipMemcpyDeviceToHost, c->stream));
+    if (cnt) HIP_TRY(c, hipMemcpyAsync(host_count, cnt, cells * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return PCR_OK;
 }
 

@@ -2,11 +2,13 @@
 // decoder outside the render kernels is the per-chain CPU one of include/huffman.h:433-477.
 //     pcr_decode <in.huffman> <out.las> [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1] [--rect x0 y0 x1 y1]
+//     pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]
 // Loads the file with the loader of the render tools (HuffmanLasData, csrc/pcr_methods.hpp), reads the points back in pieces of
 // 64 batches and writes LAS 1.2 / point format 2 (pcr_write_las_points). With --box only the points inside a box of world
 // coordinates are read back (pcr_read_box: batches the box misses are not decoded). With --view only the points a frame of that
 // camera draws (pcr_render's camera arguments and defaults), and of those the ones inside --rect, a rectangle of pixels
-// (pcr_read_screen).
+// (pcr_read_screen). With --ortho no points are read back at all: the stream is rasterized top-down on the GPU (pcr_read_grid) into
+// an orthophoto and, with --dsm, a surface model.
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -24,6 +26,7 @@ static const char *USAGE =
     "usage: pcr_decode <in.huffman> <out.las> [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1]\n"
     "                                                [--rect x0 y0 x1 y1]\n"
+    "       pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]\n"
     "  Decodes every point of the stream on the GPU and writes a LAS 1.2 file (point format 2, 26-byte records).\n"
     "  A .huffman header stores the point count after padding only (a multiple of 65536: the encoder repeats the last\n"
     "  point), so the LAS file holds the padded count. Points come in the stream's order (Morton-sorted per chunk if the\n"
@@ -34,7 +37,12 @@ static const char *USAGE =
     "  offset, in double precision), selected on the GPU, in the stream's order. A box that holds no point is an error.\n"
     "  --view: only the points a frame of that camera draws (the basic method's cull and level of detail; the options and their\n"
     "  defaults are pcr_render's), in the stream's order; --rect: of those the ones whose pixel lies in the rectangle (pixels,\n"
-    "  bounds inclusive, x0 <= x1 and y0 <= y1). A view that shows no point is an error.\n";
+    "  bounds inclusive, x0 <= x1 and y0 <= y1). A view that shows no point is an error.\n"
+    "  --ortho CELL: no LAS file; the stream is rasterized top-down on the GPU into square cells of CELL world units (a whole\n"
+    "  number of the stream's x and y lattice steps) and the colour of the highest point of every cell is written as a binary\n"
+    "  PPM (empty cells black), rows from north to south. The cells cover the x and y range of --box, of which z0 and z1 clip the\n"
+    "  points, or the box of the file's header. --dsm: the height of that point as an ESRI ASCII grid (ncols, nrows, xllcorner,\n"
+    "  yllcorner, cellsize, NODATA_value -9999; world units, %.17g), the same rows. A grid no point falls into is an error.\n";
 
 static bool parse_double(const char *a, double &v)
 {
@@ -107,13 +115,93 @@ static bool parse_box(int argc, char **argv, int at, double lo[3], double hi[3])
     return true;
 }
 
+struct Ortho {
+    double cell = 0.0;
+    bool has_box = false;
+    double lo[3], hi[3];
+    std::string dsm;
+};
+
+// the options behind --ortho, every one well formed, or false
+static bool parse_ortho(int argc, char **argv, int at, Ortho &o)
+{
+    if (argc < at + 2 || std::strcmp(argv[at], "--ortho") != 0) return false;
+    if (!parse_double(argv[at + 1], o.cell) || !(o.cell > 0.0)) return false;
+    for (int i = at + 2; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--box" && i + 6 < argc && !o.has_box) {
+            for (int k = 0; k < 6; ++k) if (!parse_double(argv[++i], k < 3 ? o.lo[k] : o.hi[k - 3])) return false;
+            o.has_box = true;
+        } else if (a == "--dsm" && i + 1 < argc && o.dsm.empty() && argv[i + 1][0] != '\0') {
+            o.dsm = argv[++i];
+        } else {
+            return false;
+        }
+    }
+    return true;
+}
+
+// The orthophoto (binary PPM) and, with a path, the surface model (ESRI ASCII grid) of the loaded resource, rows from north to south.
+static void write_ortho(HuffmanLasData &las, const pcr_las_info &info, const Ortho &o, const std::string &ppm)
+{
+    const double lo[2] = {o.has_box ? o.lo[0] : info.min[0], o.has_box ? o.lo[1] : info.min[1]};
+    const double hi[2] = {o.has_box ? o.hi[0] : info.max[0], o.has_box ? o.hi[1] : info.max[1]};
+    const pcr_grid grid = gridFromWorld(info, lo, hi, o.cell);
+    pcr_box clip{};
+    if (o.has_box) {
+        const double inf = std::numeric_limits<double>::infinity();
+        const double l3[3] = {-inf, -inf, o.lo[2]}, h3[3] = {inf, inf, o.hi[2]};
+        clip = boxFromWorld(info, l3, h3);
+    }
+    std::vector<uint64_t> top;
+    const pcr_grid_stats st = las.readGrid(grid, o.has_box ? &clip : nullptr, &top, nullptr, nullptr);
+    std::printf("ortho: %d x %d cells of %d lattice steps, batches outside %lld, windowed %lld, direct %lld\n", grid.width, grid.height, grid.cell,
+                (long long)st.batches_outside, (long long)st.batches_windowed, (long long)st.batches_direct);
+    size_t filled = 0;
+    for (uint64_t w : top) filled += w != 0;
+    if (!filled) throw std::runtime_error("no points inside the grid: nothing written");
+    std::vector<unsigned char> rgb((size_t)grid.width * 3);
+    FILE *f = std::fopen(ppm.c_str(), "wb");
+    if (!f) throw std::runtime_error(ppm + ": cannot open for writing");
+    std::fprintf(f, "P6\n%d %d\n255\n", grid.width, grid.height);
+    for (int cy = grid.height - 1; cy >= 0; --cy) {
+        for (int cx = 0; cx < grid.width; ++cx) {
+            const uint64_t w = top[(size_t)cy * grid.width + cx];
+            for (int k = 0; k < 3; ++k) rgb[(size_t)cx * 3 + k] = (unsigned char)(w >> (8 * k));
+        }
+        std::fwrite(rgb.data(), 1, rgb.size(), f);
+    }
+    if (std::fclose(f) != 0) throw std::runtime_error(ppm + ": write failed");
+    if (!o.dsm.empty()) {
+        f = std::fopen(o.dsm.c_str(), "w");
+        if (!f) throw std::runtime_error(o.dsm + ": cannot open for writing");
+        const double px = (double)grid.origin_x * info.scale[0], py = (double)grid.origin_y * info.scale[1];
+        std::fprintf(f, "ncols %d\nnrows %d\nxllcorner %.17g\nyllcorner %.17g\ncellsize %.17g\nNODATA_value -9999\n", grid.width, grid.height,
+                     px + info.offset[0], py + info.offset[1], o.cell);
+        for (int cy = grid.height - 1; cy >= 0; --cy) {
+            for (int cx = 0; cx < grid.width; ++cx) {
+                const uint64_t w = top[(size_t)cy * grid.width + cx];
+                const double pz = (double)(int32_t)((uint32_t)(w >> 32) ^ 0x80000000u) * info.scale[2];
+                if (w) std::fprintf(f, cx ? " %.17g" : "%.17g", pz + info.offset[2]);
+                else std::fputs(cx ? " -9999" : "-9999", f);
+            }
+            std::fputc('\n', f);
+        }
+        if (std::fclose(f) != 0) throw std::runtime_error(o.dsm + ": write failed");
+    }
+    std::printf("cells %zu of %zu filled -> %s%s%s\n", filled, top.size(), ppm.c_str(), o.dsm.empty() ? "" : ", ", o.dsm.c_str());
+}
+
 int main(int argc, char **argv)
 {
     if (argc >= 2 && (std::strcmp(argv[1], "--help") == 0 || std::strcmp(argv[1], "-h") == 0)) { std::fputs(USAGE, stdout); return 0; }
     double lo[3], hi[3];
     View view;
-    const bool viewed = argc > 3 && std::strcmp(argv[3], "--view") == 0, boxed = argc > 3 && !viewed;
-    if (argc < 3 || (boxed && !parse_box(argc, argv, 3, lo, hi)) || (viewed && !parse_view(argc, argv, 3, view))) { std::fputs(USAGE, stderr); return 2; }
+    Ortho ortho;
+    const bool viewed = argc > 3 && std::strcmp(argv[3], "--view") == 0, orthoed = argc > 3 && std::strcmp(argv[3], "--ortho") == 0;
+    const bool boxed = argc > 3 && !viewed && !orthoed;
+    if (argc < 3 || (boxed && !parse_box(argc, argv, 3, lo, hi)) || (viewed && !parse_view(argc, argv, 3, view)) ||
+        (orthoed && !parse_ortho(argc, argv, 3, ortho))) { std::fputs(USAGE, stderr); return 2; }
     const std::string in = argv[1], out = argv[2];
     try {
         Renderer renderer(viewed ? view.w : 64, viewed ? view.h : 64, 0);
@@ -130,6 +218,11 @@ int main(int argc, char **argv)
         }
         std::vector<pcr_point> points;
         const pcr_las_info info = las->lasInfo();
+        if (orthoed) {
+            write_ortho(*las, info, ortho, out);
+            las->unload(&renderer);
+            return 0;
+        }
         if (boxed) {
             const pcr_select_stats st = las->selectBox(boxFromWorld(info, lo, hi), points);
             std::printf("box: batches outside %lld, inside %lld, straddling %lld\n", (long long)st.batches_outside, (long long)st.batches_inside,

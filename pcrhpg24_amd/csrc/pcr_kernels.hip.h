@@ -16,6 +16,7 @@
 //                   MODE 3: the colour pass over BC7 mode-6 colours)
 //   k_decode_points on request: the same decode, every point of a range of batches written out as {x, y, z, colour} records
 //   k_screen_* / k_pick*  on request: the points a frame draws, selected by pixel (projection restated in screen_project)
+//   k_grid*         on request: the stream rasterized top-down into max / min / count planes over its integer x and y
 //   k_las_*         the 10-10-10 method (modules/compute_loop_las_cuda)
 //   k_resolve_*     framebuffer -> RGBA8 (resolve.cu:149-191, huffman_hqs/resolve.cu:2-47)
 //   k_merge_* / k_flip_sign  multi-GPU partial-framebuffer merges
@@ -2223,6 +2224,113 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_select_write(StreamView 
     decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t colour) {
         if (in_box(q, x, y, z) && dst < end) *dst++ = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Top-down grid (pcr_grid_clear / pcr_grid_accumulate / pcr_grid_unpack): the stream rasterized into planes over its integer x
+// and y -- per cell the unsigned max and min of (z ^ sign bit) << 32 | colour and the number of points (pcr_grid in
+// pcr_types.h). k_render's window scheme with an integer orthographic projection: the host knows every batch's exact box, hence
+// the rectangle of cells the batch can reach, and lists the batch with it.
+//   k_grid<.., true>   windowed: the rectangle has at most PCR_GRID_WINDOW_CELLS cells. The workgroup keeps the planes asked for
+//                      in LDS beside the table (8 + 8 + 4 bytes per cell of the launch's largest window, so a top-only call
+//                      fits several workgroups per CU), accumulates with LDS atomics that return nothing, and after a barrier
+//                      merges: one global atomic per non-empty cell and plane, rows of the rectangle contiguous.
+//   k_grid<.., false>  direct: a global atomic per point and plane.
+// Max, min and add commute, so the planes do not depend on the order of points, workgroups or launches. No workgroup waits for
+// another one; every result goes out through vector atomics and stores.
+// ------------------------------------------------------------------------------------------------
+struct GridEntry { uint32_t b, wx0, wy0, ww, wh; };     // a listed batch and its window: first cell and size in cells
+struct GridArgs {
+    pcr_box q;                      // grid and clip intersected, in the stream's coordinates, not empty: a point inside has a cell
+    int32_t ox, oy;                 // pcr_grid::origin_x / origin_y
+    uint32_t shift;                 // cell == 1 << shift; GRID_NO_SHIFT: not a power of two, then
+    unsigned long long magic;       // ceil(2^64 / cell)
+    uint32_t width;
+    uint32_t win_cells;             // cells of each LDS plane of this launch (windowed): the largest window listed
+    unsigned long long *top, *bottom;
+    uint32_t *count;
+};
+constexpr uint32_t GRID_NO_SHIFT = 32;
+constexpr uint32_t GRID_TABLE_BYTES = PCR_HUFFMAN_TABLE_SIZE * 4;
+
+// d / cell, exact for every 32-bit d. With m = ceil(2^64 / c) and c no power of two, m * c = 2^64 + e with 0 < e < c, so
+// d * m / 2^64 = d / c + d * e / (c * 2^64), and the excess is below 2^32 * c / (c * 2^64) = 2^-32 <= 1 / c: too little to
+// carry the fraction of d / c (at most 1 - 1 / c) over the next integer.
+__device__ __forceinline__ uint32_t grid_div(const GridArgs &a, uint32_t d)
+{
+    return a.shift < GRID_NO_SHIFT ? d >> a.shift : (uint32_t)__umul64hi((unsigned long long)d, a.magic);
+}
+
+template <int LAYOUT, int COLOUR, bool WINDOWED>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_grid(StreamView s, const GridEntry *list, GridArgs a)
+{
+    typedef unsigned long long u64;
+    const GridEntry e = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x;
+    extern __shared__ __align__(16) unsigned char s_dyn[];                  // the table, then the planes asked for
+    uint32_t *s_table = reinterpret_cast<uint32_t *>(s_dyn);
+    u64 *s_top = reinterpret_cast<u64 *>(s_dyn + GRID_TABLE_BYTES);
+    u64 *s_bottom = s_top + (a.top ? a.win_cells : 0u);
+    uint32_t *s_count = reinterpret_cast<uint32_t *>(s_bottom + (a.bottom ? a.win_cells : 0u));
+    const uint32_t ncell = e.ww * e.wh;
+    if (WINDOWED) {
+        if (ncell > a.win_cells) return;                                    // (uniform; the host lists no such window)
+        for (uint32_t i = tid; i < ncell; i += PCR_WORKGROUP_SIZE) {
+            if (a.top) s_top[i] = 0ull;
+            if (a.bottom) s_bottom[i] = ~0ull;
+            if (a.count) s_count[i] = 0u;
+        }
+    }
+    load_packed_table(s, e.b, s_table);                                     // (its barrier publishes the window as well)
+    decode_chain<LAYOUT, COLOUR>(s, e.b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        if (!in_box(a.q, x, y, z)) return;
+        const uint32_t cx = grid_div(a, (uint32_t)x - (uint32_t)a.ox), cy = grid_div(a, (uint32_t)y - (uint32_t)a.oy);
+        const u64 key = ((u64)((uint32_t)z ^ 0x80000000u) << 32) | colour;
+        if (WINDOWED) {
+            const uint32_t lx = cx - e.wx0, ly = cy - e.wy0;
+            if (lx >= e.ww || ly >= e.wh) return;                           // (no point of the batch: the window is its exact box's)
+            const uint32_t i = ly * e.ww + lx;
+            if (a.top) __hip_atomic_fetch_max(&s_top[i], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (a.bottom) __hip_atomic_fetch_min(&s_bottom[i], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (a.count) __hip_atomic_fetch_add(&s_count[i], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        } else {
+            const size_t g = (size_t)cy * a.width + cx;
+            if (a.top) atomicMax(&a.top[g], key);
+            if (a.bottom) atomicMin(&a.bottom[g], key);
+            if (a.count) atomicAdd(&a.count[g], 1u);
+        }
+    });
+    if (WINDOWED) {
+        __syncthreads();
+        // row by row: consecutive lanes take consecutive cells of a row of the rectangle, a handful of cache lines per wave; the
+        // empty values are the identities of max and min, so a cell no point reached issues nothing
+        for (uint32_t i = tid; i < ncell; i += PCR_WORKGROUP_SIZE) {
+            const uint32_t ly = i / e.ww, lx = i - ly * e.ww;
+            const size_t g = (size_t)(e.wy0 + ly) * a.width + e.wx0 + lx;
+            if (a.top) { const u64 v = s_top[i]; if (v != 0ull) atomicMax(&a.top[g], v); }
+            if (a.bottom) { const u64 v = s_bottom[i]; if (v != ~0ull) atomicMin(&a.bottom[g], v); }
+            if (a.count) { const uint32_t v = s_count[i]; if (v) atomicAdd(&a.count[g], v); }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_grid_clear(unsigned long long *top, unsigned long long *bottom, uint32_t *count, uint32_t n)
+{
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        if (top) top[i] = 0ull;
+        if (bottom) bottom[i] = ~0ull;
+        if (count) count[i] = 0u;
+    }
+}
+
+// height / rgba of every cell of a top or bottom plane (`empty`: the plane's empty value; either output may be NULL)
+__global__ void __launch_bounds__(256) k_grid_unpack(const unsigned long long *words, unsigned long long empty, int32_t *height, uint32_t *rgba, uint32_t n)
+{
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const unsigned long long w = words[i];
+        if (height) height[i] = w == empty ? INT32_MIN : (int32_t)((uint32_t)(w >> 32) ^ 0x80000000u);
+        if (rgba) rgba[i] = w == empty ? 0u : ((uint32_t)w | 0xFF000000u);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

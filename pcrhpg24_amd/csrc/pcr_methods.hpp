@@ -13,6 +13,7 @@
 // a device RGBA8 buffer instead of a GL texture.
 #pragma once
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -20,6 +21,7 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <optional>
@@ -352,6 +354,21 @@ struct HuffmanLasData : Resource {
         return found != 0;
     }
 
+    // The three planes of `grid` (pcr_grid in pcr_types.h) over every batch the context holds right now, rasterized on the GPU in
+    // one pass over the compressed stream (pcr_read_grid); clip may be NULL, a vector NULL leaves its plane out. Not in the reference.
+    pcr_grid_stats readGrid(const pcr_grid &grid, const pcr_box *clip, std::vector<uint64_t> *top, std::vector<uint64_t> *bottom, std::vector<uint32_t> *count)
+    {
+        if (!loadedOn) throw std::runtime_error("readGrid: the resource is not loaded");
+        const size_t cells = (size_t)std::max(grid.width, 0) * (size_t)std::max(grid.height, 0);
+        if (top) top->resize(cells);
+        if (bottom) bottom->resize(cells);
+        if (count) count->resize(cells);
+        pcr_grid_stats st{};
+        loadedOn->check(pcr_read_grid(loadedOn->ctx, 0, pcr_batches_resident(loadedOn->ctx), &grid, clip, top ? top->data() : nullptr,
+                                      bottom ? bottom->data() : nullptr, count ? count->data() : nullptr, 0, &st), "pcr_read_grid");
+        return st;
+    }
+
     // Scale, offset and box of the LAS file the stream was made from, as the first batch record carries them
     // (include/BatchDumpData.h:60-107: doubles at 20 and 44, the LAS box as floats at 92 and 104).
     pcr_las_info lasInfo() const
@@ -445,6 +462,30 @@ inline pcr_box boxFromWorld(const pcr_las_info &las, const double lo[3], const d
         b.min[k] = (int32_t)a; b.max[k] = (int32_t)z;
     }
     return b;
+}
+
+// The grid of square cells of `cell_size` world units over lo <= x, y <= hi: the origin is the first lattice point at or above lo on
+// each axis (boxFromWorld's), the cell the whole number of lattice steps cell_size is on x and on y (it has to be one, the same
+// on both, at least 1), width and height reach the last lattice point at or below hi. The Python twin is host.grid_from_world.
+inline pcr_grid gridFromWorld(const pcr_las_info &las, const double lo[2], const double hi[2], double cell_size)
+{
+    int64_t cells[2];
+    for (int k = 0; k < 2; ++k) {
+        const double s = las.scale[k];
+        if (!(s > 0.0) || !(cell_size > 0.0)) throw std::runtime_error("gridFromWorld: needs positive scales and a positive cell size");
+        const double n = std::nearbyint(cell_size / s);
+        if (!(n >= 1.0) || n > (double)INT32_MAX || std::fabs(n * s - cell_size) > 1e-9 * cell_size)
+            throw std::runtime_error("gridFromWorld: the cell size is not a whole number of lattice steps");
+        cells[k] = (int64_t)n;
+    }
+    if (cells[0] != cells[1]) throw std::runtime_error("gridFromWorld: the cell size is a different number of lattice steps on x and on y");
+    const double inf = std::numeric_limits<double>::infinity();
+    const double l3[3] = {lo[0], lo[1], -inf}, h3[3] = {hi[0], hi[1], inf};
+    const pcr_box b = boxFromWorld(las, l3, h3);
+    if (b.min[0] > b.max[0] || b.min[1] > b.max[1]) throw std::runtime_error("gridFromWorld: the range holds no lattice point");
+    const int64_t w = ((int64_t)b.max[0] - b.min[0]) / cells[0] + 1, h = ((int64_t)b.max[1] - b.min[1]) / cells[0] + 1;
+    if (w * h > PCR_GRID_MAX_CELLS) throw std::runtime_error("gridFromWorld: more cells than PCR_GRID_MAX_CELLS");
+    return pcr_grid{b.min[0], b.min[1], (int32_t)cells[0], (int32_t)w, (int32_t)h, 0};
 }
 
 // modules/huffman_cuda/huffman_cuda.h:60-75: the reference's first Huffman method (class ComputeHuffman, registered as

@@ -28,7 +28,7 @@ from typing import Iterator, Optional
 import numpy as np
 
 from . import _native as N
-from ._native import Box, DisplayOpts, EncodeStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, XyzBatch, c_i64, fb_elems
+from ._native import Box, DisplayOpts, EncodeStats, Grid, GridStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, XyzBatch, c_i64, fb_elems
 
 POINTS_PER_BATCH = 65536
 ENCODED_PAD_WORDS = 1024
@@ -246,6 +246,43 @@ def box_from_world(las: LasInfo, lo, hi) -> Box:
             a, z = 0, -1
         b.min[k], b.max[k] = a, z
     return b
+
+
+def as_grid(grid) -> Grid:
+    """A pcr_grid from a Grid or five numbers origin_x, origin_y, cell, width, height (the stream's int32 coordinates, cells)."""
+    if isinstance(grid, Grid):
+        return grid
+    v = [int(a) for a in np.asarray(grid, dtype=np.int64).reshape(5)]
+    if any(a < INT32_MIN or a > INT32_MAX for a in v):
+        raise ValueError("grid fields are int32")
+    return Grid(*v, 0)
+
+
+def grid_from_world(las: LasInfo, lo_xy, hi_xy, cell_size: float) -> Grid:
+    """The grid of square cells of `cell_size` world units that covers lo <= x, y <= hi (world coordinates): the origin is the
+    first lattice point at or above lo on each axis (box_from_world's), the cell the whole number of lattice steps cell_size
+    is on x and on y, width and height reach the last lattice point at or below hi. ValueError for a cell_size that is not a
+    whole number (>= 1) of steps of both the x and the y lattice -- the cells are squares of integer coordinates, so scale_x
+    and scale_y have to agree on that number -- or for a range that holds no lattice point."""
+    inf = float("inf")
+    cells = []
+    for k in range(2):
+        s = float(las.scale[k])
+        if not s > 0.0 or not cell_size > 0.0:
+            raise ValueError("grid_from_world needs positive scales and a positive cell size")
+        n = round(cell_size / s)
+        if n < 1 or n > INT32_MAX or abs(n * s - cell_size) > 1e-9 * cell_size:
+            raise ValueError(f"a cell of {cell_size} is not a whole number of lattice steps of {s}")
+        cells.append(int(n))
+    if cells[0] != cells[1]:
+        raise ValueError(f"a cell of {cell_size} is {cells[0]} steps on x and {cells[1]} on y: the cells are squares of lattice steps")
+    box = box_from_world(las, (lo_xy[0], lo_xy[1], -inf), (hi_xy[0], hi_xy[1], inf))
+    if box.min[0] > box.max[0] or box.min[1] > box.max[1]:
+        raise ValueError("the range holds no lattice point")
+    w, h = ((int(box.max[k]) - int(box.min[k])) // cells[0] + 1 for k in range(2))
+    if w * h > N.GRID_MAX_CELLS:
+        raise ValueError(f"{w} x {h} cells: more than the {N.GRID_MAX_CELLS} a grid may have")
+    return Grid(int(box.min[0]), int(box.min[1]), cells[0], w, h, 0)
 
 
 def write_las(path, x=None, y=None, z=None, color=None, las: Optional[LasInfo] = None, points=None) -> None:
@@ -593,6 +630,78 @@ class Context:
             self._chk(self.lib.pcr_read_box(self.h, first, nb, C.byref(box), out.ctypes.data, len(out), C.byref(cnt), C.byref(st)), "pcr_read_box")
         self.select_stats = st.as_dict()
         return out
+
+    # -- top-down grid (pcr_grid_clear / pcr_grid_accumulate / pcr_grid_unpack / pcr_read_grid) --------------
+    def _grid_plane(self, t, bits: int, cells: int, what: str):
+        """The device pointer of a plane given as a torch tensor (None: the plane is left out)."""
+        import torch
+        if t is None:
+            return None
+        dev = torch.device("cuda", self.device)
+        ok = (torch.int64, torch.uint64) if bits == 64 else (torch.int32, torch.uint32)
+        if t.dtype not in ok or not t.is_contiguous() or t.device != dev or t.numel() < cells:
+            raise ValueError(f"{what} must be a contiguous {bits}-bit integer tensor of at least {cells} elements on {dev}")
+        return C.c_void_p(t.data_ptr())
+
+    def grid_clear(self, grid, top=None, bottom=None, counts=None) -> None:
+        """The empty values into the planes of `grid` (as_grid) given: torch tensors on the context's device, top / bottom of
+        64-bit integers (0 / all ones), counts of 32-bit integers (0), width * height elements each, row cy at cy * width.
+        Stream ordering as decode_points."""
+        import torch
+        grid = as_grid(grid)
+        cells = grid.width * grid.height
+        ptrs = [self._grid_plane(t, b, cells, w) for t, b, w in ((top, 64, "top"), (bottom, 64, "bottom"), (counts, 32, "counts"))]
+        torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()
+        self._chk(self.lib.pcr_grid_clear(self.h, C.byref(grid), *ptrs), "pcr_grid_clear")
+        self.synchronize()
+
+    def grid_accumulate(self, grid, top=None, bottom=None, counts=None, clip=None, first: int = 0, count: Optional[int] = None,
+                        flags: int = 0) -> dict:
+        """The points of batches [first, first + count) inside `clip` (as_box; None: everywhere) into the planes of `grid`, on top
+        of what they hold: per cell top = unsigned max and bottom = unsigned min of (z ^ 0x80000000) << 32 | colour (int64
+        tensors hold the bits), counts += the number of points. Any plane may be None. Returns the classes of the batches
+        (also in self.grid_stats). Stream ordering as decode_points."""
+        import torch
+        grid = as_grid(grid)
+        cells = grid.width * grid.height
+        ptrs = [self._grid_plane(t, b, cells, w) for t, b, w in ((top, 64, "top"), (bottom, 64, "bottom"), (counts, 32, "counts"))]
+        clip = None if clip is None else as_box(clip)
+        st = GridStats()
+        torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()
+        self._chk(self.lib.pcr_grid_accumulate(self.h, first, -1 if count is None else count, C.byref(grid), None if clip is None else C.byref(clip),
+                                               *ptrs, flags, C.byref(st)), "pcr_grid_accumulate")
+        self.synchronize()
+        self.grid_stats = st.as_dict()
+        return self.grid_stats
+
+    def grid_unpack(self, grid, words, which: int = N.GRID_TOP):
+        """(height, rgba) of a top or bottom plane (`which`: GRID_TOP / GRID_BOTTOM tells its empty value): torch.int32 tensors
+        [height, width], height = z of the cell's word (INT32_MIN for an empty cell), rgba = the bits of colour | 0xFF000000
+        (0 for an empty cell)."""
+        import torch
+        grid = as_grid(grid)
+        cells = grid.width * grid.height
+        ptr = self._grid_plane(words, 64, cells, "words")
+        height = torch.empty((grid.height, grid.width), dtype=torch.int32, device=words.device)
+        rgba = torch.empty_like(height)
+        torch.cuda.current_stream(words.device).synchronize()
+        self._chk(self.lib.pcr_grid_unpack(self.h, C.byref(grid), ptr, which, C.c_void_p(height.data_ptr()), C.c_void_p(rgba.data_ptr())), "pcr_grid_unpack")
+        self.synchronize()
+        return height, rgba
+
+    def read_grid(self, grid, clip=None, first: int = 0, count: Optional[int] = None, flags: int = 0):
+        """The three planes of `grid` over batches [first, first + count) on the host, without torch (pcr_read_grid: clear,
+        accumulate, copy; synchronises): numpy top and bottom (uint64) and count (uint32), shaped [height, width]. The classes
+        of the batches are in self.grid_stats."""
+        grid = as_grid(grid)
+        clip = None if clip is None else as_box(clip)
+        shape = (max(grid.height, 0), max(grid.width, 0))
+        top, bottom, cnt = np.empty(shape, np.uint64), np.empty(shape, np.uint64), np.empty(shape, np.uint32)
+        st = GridStats()
+        self._chk(self.lib.pcr_read_grid(self.h, first, -1 if count is None else count, C.byref(grid), None if clip is None else C.byref(clip),
+                                         top.ctypes.data, bottom.ctypes.data, cnt.ctypes.data, flags, C.byref(st)), "pcr_read_grid")
+        self.grid_stats = st.as_dict()
+        return top, bottom, cnt
 
     # -- screen selection and picking (pcr_select_screen / pcr_read_screen / pcr_pick) ---------------------
     def select_screen(self, p: RenderParams, rect=None):
@@ -945,6 +1054,35 @@ class HuffmanLasData(Resource):
         info = self.las_info()
         so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
         return pts[:, :3].to(torch.float64) * so[0] + so[1], pts, hits
+
+    def height_map(self, renderer: Renderer, cell_size: float, lo_xy=None, hi_xy=None, which: str = "top", clip_z=None):
+        """A top-down map of the loaded resource, rasterized on the GPU in one pass over the compressed stream (Context.
+        grid_accumulate): (height, rgba, count, grid) over the cells of grid_from_world(las_info(), lo_xy, hi_xy, cell_size) --
+        lo_xy / hi_xy None: las_info()'s min / max. which="top": per cell the highest point (the surface model and its
+        orthophoto), "bottom": the lowest. height is a float64 tensor [h, w] = z * scale + offset of that point, NaN for an
+        empty cell; rgba a uint8 tensor [h, w, 4] with its colour and alpha 255, zeros for an empty cell; count an int32
+        tensor [h, w] with the bits of the number of points per cell. Row 0 is the southern edge (the lowest y). clip_z:
+        (lo, hi) in world units, only the points with lo <= z <= hi count."""
+        import torch
+        if which not in ("top", "bottom"):
+            raise ValueError('which is "top" or "bottom"')
+        info = self.las_info()
+        lo_xy = (info.min[0], info.min[1]) if lo_xy is None else lo_xy
+        hi_xy = (info.max[0], info.max[1]) if hi_xy is None else hi_xy
+        grid = grid_from_world(info, lo_xy, hi_xy, cell_size)
+        inf = float("inf")
+        clip = None if clip_z is None else box_from_world(info, (-inf, -inf, clip_z[0]), (inf, inf, clip_z[1]))
+        ctx = renderer.ctx
+        dev = torch.device("cuda", ctx.device)
+        words = torch.empty((grid.height, grid.width), dtype=torch.int64, device=dev)
+        count = torch.empty((grid.height, grid.width), dtype=torch.int32, device=dev)
+        planes = dict(top=words) if which == "top" else dict(bottom=words)
+        ctx.grid_clear(grid, counts=count, **planes)
+        ctx.grid_accumulate(grid, counts=count, clip=clip, **planes)
+        z, rgba = ctx.grid_unpack(grid, words, N.GRID_TOP if which == "top" else N.GRID_BOTTOM)
+        height = z.to(torch.float64) * float(info.scale[2]) + float(info.offset[2])
+        height[rgba == 0] = float("nan")
+        return height, rgba.view(torch.uint8).view(grid.height, grid.width, 4), count, grid
 
     def las_info(self) -> LasInfo:
         """Scale, offset, min and max of the LAS file the stream was made from, as its first batch record carries them (the
