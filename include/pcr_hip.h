@@ -300,6 +300,45 @@ int pcr_grid_unpack(pcr_ctx *ctx, const pcr_grid *grid, const void *dev_words, i
 int pcr_read_grid(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_grid *grid, const pcr_box *clip,
                   uint64_t *host_top, uint64_t *host_bottom, uint32_t *host_count, uint32_t flags, pcr_grid_stats *stats);
 
+/* ---- voxel-grid thinning: one record per voxel, straight from the compressed stream (no reference counterpart) ----------------
+ * The *rows* of a range are the records pcr_decode_points writes for it: row r = (b - first_batch) * 65536 + chain * 64 + i,
+ * padding duplicates and the tail artefact included. A row inside *clip (bounds inclusive; NULL: every row) is a *candidate*;
+ * its voxel is v[k] = floor((p[k] - origin[k]) / cell) on every axis, in exact integer arithmetic (pcr_voxels in pcr_types.h).
+ * CONTRACT: pcr_thin keeps exactly one candidate of every non-empty voxel -- PCR_THIN_FIRST the one with the lowest row,
+ * PCR_THIN_CENTER the least by (d2, row) with d2 = sum over the axes of (2 * (p[k] - origin[k] - v[k] * cell) - (cell - 1))^2,
+ * four times the squared distance to the voxel's centre as an integer. The kept records go to dev_points, byte for byte the
+ * records pcr_decode_points writes (colour included), their rows to dev_rows (int64), both in increasing row order, packed
+ * without gaps. The result is exact and the same from run to run; BC1 and BC7, either resident layout, before and after the
+ * first frame. A voxel that spans two ranges is kept once per range: thin the whole range in one call.
+ *
+ * pcr_thin: either of dev_points (16-byte aligned) and dev_rows (8-byte aligned) may be NULL, with both NULL the call only
+ *   counts; capacity_points counts records of each. A capacity below the result: PCR_E_ARG, *out_count = the count needed,
+ *   nothing written. Range semantics, count < 0 and the restriction under pcr_set_async_upload are pcr_decode_points'. An empty
+ *   clip, a range of 0 batches or a clip that misses every batch (by pcr_batch_point_bounds' cached exact boxes; no kernel runs):
+ *   0 records, PCR_OK. Synchronises (the host sizes the voxel table and the output from counts). Touches no framebuffer, no
+ *   prepass state, no render statistics. stats may be NULL.
+ *   How: the batches the clip does not miss are decoded without colours twice -- k_thin_runs counts the runs of consecutive
+ *   candidates of a chain in one voxel (the stream is Morton-sorted, so a chain mostly stays in a voxel for a while), the host
+ *   sizes an open-addressing table of max(1024, the power of two >= 2 * runs) slots of 16 bytes, k_thin_mark inserts one
+ *   (voxel, best row) per run with a 64-bit compare-and-swap on the key and an atomic minimum on the value -- then k_thin_flag
+ *   turns the table into a bitmap of kept rows (a 64-bit word per chain) and k_thin_write decodes the batches that keep a
+ *   record once more, with colours, and stores the flagged records. Minimum commutes: the table, hence the result, does not
+ *   depend on the order of lanes or workgroups, and run compression is exact on an unsorted stream too. The table, the bitmap
+ *   and the lists are scratch memory of the context, grown on demand and released with it.
+ * pcr_read_thin: the same into host memory (alignof(pcr_point) / alignof(int64_t)), staged through the context's decode
+ *   staging buffer and a second one for the rows, 64 batches at a time.
+ * PCR_E_ARG with a message, nothing written: no stream loaded, a range outside the resident batches, a NULL vox, a NULL
+ * out_count, a misaligned pointer, cell < 1 or > PCR_THIN_MAX_CELL, PCR_THIN_CENTER with cell > PCR_THIN_MAX_CENTER_CELL, an
+ * unknown mode, a range of more than 2^40 rows, and a lattice too large for the 3 x 21-bit voxel key: with q = the union of
+ * the exact boxes of the batches the clip does not miss, intersected with the clip, the call is refused if on any axis
+ * q.max - q.min >= 2^31 or (q.max - q.min) / cell + 2 > 2^21 -- pass a clip or a larger cell (the tail artefact far outside
+ * the cloud is the usual cause). PCR_E_NOMEM: no device memory for the table ("voxel table overflow" cannot happen: the table
+ * has twice as many slots as insertions; the probe loop is bounded all the same). */
+int pcr_thin(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int mode,
+             void *dev_points, void *dev_rows, size_t capacity_points, int64_t *out_count, pcr_thin_stats *stats);
+int pcr_read_thin(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int mode,
+                  pcr_point *host_points, int64_t *host_rows, size_t capacity_points, int64_t *out_count, pcr_thin_stats *stats);
+
 /* What a collective library needs to merge partial frames in place (include/pcr_dist.h does it with RCCL): the HIP stream
  * the context enqueues on, its device ordinal and the length of each framebuffer in 64-bit words. */
 void *pcr_get_stream(pcr_ctx *ctx);

@@ -160,6 +160,31 @@ typedef struct pcr_grid_stats {
     int64_t batches_outside, batches_windowed, batches_direct;
 } pcr_grid_stats;
 
+/* A lattice of cubic voxels over the stream's int32 coordinates (pcr_thin), 16 bytes: a point (x, y, z) belongs to voxel
+ * v[k] = floor((p[k] - origin[k]) / cell) on every axis, the difference and the division taken exactly (as 64-bit integers;
+ * v may be negative). Every int32 point has a voxel: the lattice has no far edge. */
+#define PCR_THIN_FIRST            0          /* mode: of a voxel's points the one with the lowest row */
+#define PCR_THIN_CENTER           1          /* mode: the one nearest to the voxel's centre, ties to the lowest row */
+#define PCR_THIN_MAX_CELL         (1 << 30)
+#define PCR_THIN_MAX_CENTER_CELL  2048       /* PCR_THIN_CENTER: 3 * (cell - 1)^2 < 2^24 */
+typedef struct pcr_voxels {
+    int32_t origin[3];           /* min corner of voxel (0, 0, 0) */
+    int32_t cell;                /* edge length, 1 .. PCR_THIN_MAX_CELL */
+} pcr_voxels;
+
+/* What pcr_thin did: the batches of the range whose exact box misses the clip (not decoded) and the others (decoded three
+ * times: runs counted, voxels marked, records written; the last only for a batch that keeps a record), the rows inside the
+ * clip, the runs of equal voxel they form along their chains (= insertions into the voxel table), the records kept, which
+ * is the call's *out_count and the number of non-empty voxels, and the slots of the table. */
+typedef struct pcr_thin_stats {
+    int64_t batches_outside;
+    int64_t batches_decoded;
+    int64_t points_considered;
+    int64_t runs;
+    int64_t points_kept;
+    int64_t table_slots;
+} pcr_thin_stats;
+
 /* A rectangle of pixels (pcr_select_screen), bounds inclusive, clipped to the image by the call. x0 > x1 or y0 > y1: the
  * empty rect. */
 typedef struct pcr_rect {

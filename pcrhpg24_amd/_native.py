@@ -82,6 +82,20 @@ class GridStats(C.Structure):                     # pcr_grid_stats
 GRID_MAX_CELLS, GRID_WINDOW_CELLS, GRID_NO_WINDOW, GRID_TOP, GRID_BOTTOM = 1 << 26, 4096, 1, 0, 1      # pcr_types.h
 
 
+class Voxels(C.Structure):                        # pcr_voxels: a lattice of cubic voxels over the stream's int32 coordinates, 16 bytes
+    _fields_ = [("origin", c_i32 * 3), ("cell", c_i32)]
+
+
+class ThinStats(C.Structure):                     # pcr_thin_stats
+    _fields_ = [(n, c_i64) for n in ("batches_outside", "batches_decoded", "points_considered", "runs", "points_kept", "table_slots")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+THIN_FIRST, THIN_CENTER, THIN_MAX_CELL, THIN_MAX_CENTER_CELL = 0, 1, 1 << 30, 2048                      # pcr_types.h
+
+
 class Rect(C.Structure):                          # pcr_rect: pixel bounds, inclusive; x0 > x1 or y0 > y1 = empty
     _fields_ = [(n, c_i32) for n in ("x0", "y0", "x1", "y1")]
 
@@ -113,6 +127,7 @@ assert C.sizeof(Point) == 16 and C.sizeof(Box) == 24 and C.sizeof(SelectStats) =
 assert C.sizeof(Rect) == 16 and C.sizeof(ScreenHit) == 16 and C.sizeof(ScreenStats) == 32
 assert C.sizeof(DisplayOpts) == 16
 assert C.sizeof(Grid) == 24 and C.sizeof(GridStats) == 24
+assert C.sizeof(Voxels) == 16 and C.sizeof(ThinStats) == 48
 assert C.sizeof(XyzBatch) == 64 and C.sizeof(GpuBatch) == 160 and C.sizeof(FileHeader) == 40 and C.sizeof(RenderParams) == 224
 
 
@@ -137,6 +152,7 @@ HIP_SYMBOLS = [
     "pcr_select_screen", "pcr_read_screen", "pcr_pick",
     "pcr_resolve_basic_display", "pcr_resolve_hqs_display", "pcr_resolve_las_display",
     "pcr_grid_clear", "pcr_grid_accumulate", "pcr_grid_unpack", "pcr_read_grid",
+    "pcr_thin", "pcr_read_thin",
 ]
 
 HOST_SYMBOLS = [
@@ -259,6 +275,9 @@ def hip_lib() -> C.CDLL:
             getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Grid), C.POINTER(Box), C.c_void_p, C.c_void_p, C.c_void_p, c_u32,
                                         C.POINTER(GridStats)]
         lib.pcr_grid_unpack.argtypes = [C.c_void_p, C.POINTER(Grid), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        for n in ("pcr_thin", "pcr_read_thin"):
+            getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Voxels), C.POINTER(Box), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.POINTER(c_i64), C.POINTER(ThinStats)]
         _hip = lib
     return _hip
 

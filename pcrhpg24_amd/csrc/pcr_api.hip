@@ -150,6 +150,20 @@ struct pcr_ctx {
     bool grid_lds_ready = false;                // hipFuncSetAttribute done for the windowed k_grid launches
     unsigned char *d_grid_scratch = nullptr;    // pcr_read_grid: top, bottom, count planes back to back
     size_t grid_scratch_bytes = 0;
+    // voxel thinning (pcr_thin / pcr_read_thin): the lists of a call's batches, the voxel table, the keep bitmap, and
+    // pcr_read_thin's staging of the rows (the records go through d_decode_stage)
+    int64_t thin_capacity = 0;                  // batches the four arrays below hold
+    uint32_t *d_thin_list = nullptr;            // [thin_capacity] the batches the clip does not miss
+    uint32_t *d_thin_totals = nullptr;          // [thin_capacity * 2] runs and candidates (k_thin_runs), then kept records (k_thin_totals)
+    uint32_t *d_thin_wlist = nullptr;           // [thin_capacity] of those the batches that keep a record
+    int64_t *d_thin_offsets = nullptr;          // [thin_capacity] first output record of each (k_thin_write)
+    ThinSlot *d_thin_table = nullptr;           // [thin_slots]
+    int64_t thin_slots = 0;
+    unsigned long long *d_thin_keep = nullptr;  // [thin_keep_words] a word per chain of the call's range
+    int64_t thin_keep_words = 0;
+    uint32_t *d_thin_error = nullptr;           // [1] k_thin_mark found no slot
+    int64_t *d_thin_rows_stage = nullptr;       // [thin_rows_stage_batches * 65536]
+    int64_t thin_rows_stage_batches = 0;
     int64_t prepass_batches = 0;
     static constexpr int FENCES = 8;
     hipEvent_t fence[FENCES] = {};              // pcr_fence_record / pcr_fence_wait: device-scope ordering between streams
@@ -248,6 +262,9 @@ void free_stream_buffers(pcr_ctx *c)
     dfree(c->d_screen_lod); dfree(c->d_scr_list); dfree(c->d_scr_counts); dfree(c->d_scr_totals); dfree(c->d_scr_offsets); c->scr_capacity = 0;
     dfree(c->d_pick);
     dfree(c->d_grid_list); c->grid_capacity = 0; c->h_grid_list.clear();
+    dfree(c->d_thin_list); dfree(c->d_thin_totals); dfree(c->d_thin_wlist); dfree(c->d_thin_offsets); c->thin_capacity = 0;
+    dfree(c->d_thin_table); c->thin_slots = 0; dfree(c->d_thin_keep); c->thin_keep_words = 0; dfree(c->d_thin_error);
+    dfree(c->d_thin_rows_stage); c->thin_rows_stage_batches = 0;
 
     if (c->any_generic_pending && c->any_generic_ev) (void)hipEventSynchronize(c->any_generic_ev);
     c->any_generic_pending = false;
@@ -1872,9 +1889,7 @@ int grid_accumulate(pcr_ctx *c, int64_t first, int64_t n, const pcr_grid &g, con
         c->grid_lds_ready = true;
     }
     a.ox = g.origin_x; a.oy = g.origin_y; a.width = (uint32_t)g.width;
-    const uint32_t cell = (uint32_t)g.cell;
-    if ((cell & (cell - 1)) == 0) { a.shift = (uint32_t)__builtin_ctz(cell); a.magic = 0; }
-    else { a.shift = GRID_NO_SHIFT; a.magic = ~0ull / cell + 1; }         // ceil(2^64 / cell): cell does not divide 2^64
+    a.div = make_cell_div((uint32_t)g.cell);
     a.top = static_cast<unsigned long long *>(top); a.bottom = static_cast<unsigned long long *>(bottom); a.count = static_cast<uint32_t *>(count);
     a.win_cells = win_cells;
     const int colour = !top && !bottom ? SEL_NO_COLOUR : c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7 ? SEL_BC7 : SEL_BC1;
@@ -1968,6 +1983,225 @@ int pcr_read_grid(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_grid
     if (bottom) HIP_TRY(c, hipMemcpyAsync(host_bottom, bottom, cells * 8, hipMemcpyDeviceToHost, c->stream));
     if (cnt) HIP_TRY(c, hipMemcpyAsync(host_count, cnt, cells * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+// ---- voxel thinning ----------------------------------------------------------------------------
+namespace {
+// What a thinning call over batches [first, first + n) has to write: the batches the clip does not miss, of those the ones that
+// keep a record (their keep words sit in c->d_thin_keep) and each one's record count.
+struct ThinPlan {
+    std::vector<uint32_t> listed;       // ascending
+    std::vector<uint32_t> writers;      // ascending
+    std::vector<int64_t> cnt;           // [writers.size()]
+    std::vector<int64_t> offsets;       // staging of k_thin_write's offsets (alive until the stream has been synchronised)
+    pcr_thin_stats st{};
+};
+
+// *p holds at least `want` elements on return (a larger array replaces it, its content is not kept), or false
+bool thin_grow(void **p, int64_t &have, int64_t want, size_t elem_bytes)
+{
+    if (*p && have >= want) return true;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; have = 0;
+    if (hipMalloc(p, (size_t)want * elem_bytes) != hipSuccess) { *p = nullptr; return false; }
+    have = want;
+    return true;
+}
+
+// Phases one to three: classify (host, from the cached exact boxes), count the runs, fill the voxel table, flag the kept rows and
+// count them per batch. Synchronises.
+int thin_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const pcr_box *clip, int mode, ThinPlan &p)
+{
+    p.listed.clear(); p.writers.clear(); p.cnt.clear();
+    p.st = pcr_thin_stats{n, 0, 0, 0, 0, 0};
+    ThinArgs a{};
+    for (int k = 0; k < 3; ++k) { a.q.min[k] = clip ? clip->min[k] : INT32_MIN; a.q.max[k] = clip ? clip->max[k] : INT32_MAX; }
+    if (n == 0 || box_empty(a.q)) return PCR_OK;
+    int rc;
+    if ((rc = ensure_point_bounds(c, first, n))) return rc;
+    pcr_box q{{INT32_MAX, INT32_MAX, INT32_MAX}, {INT32_MIN, INT32_MIN, INT32_MIN}};      // the union of the listed batches' boxes
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t *bb = c->h_point_bounds.data() + (first + i) * 6;
+        bool disjoint = false;
+        for (int k = 0; k < 3; ++k) disjoint = disjoint || bb[3 + k] < a.q.min[k] || bb[k] > a.q.max[k];
+        if (disjoint) continue;
+        p.listed.push_back((uint32_t)(first + i));
+        for (int k = 0; k < 3; ++k) { q.min[k] = std::min(q.min[k], bb[k]); q.max[k] = std::max(q.max[k], bb[3 + k]); }
+    }
+    const int64_t nL = (int64_t)p.listed.size();
+    if (nL == 0) return PCR_OK;
+    for (int k = 0; k < 3; ++k) { q.min[k] = std::max(q.min[k], a.q.min[k]); q.max[k] = std::min(q.max[k], a.q.max[k]); }
+    int axis = 0;
+    switch (thin_lattice(vox.origin, vox.cell, q.min, q.max, &a.lat, &axis)) {
+    case THIN_LATTICE_EXTENT:
+        return set_err(c, PCR_E_ARG, "the points to thin span %lld on axis %d, 2^31 or more: pass a clip or a larger cell (a tail artefact far outside the cloud?)",
+                       (long long)q.max[axis] - (long long)q.min[axis], axis);
+    case THIN_LATTICE_VOXELS:
+        return set_err(c, PCR_E_ARG, "the points to thin span %lld on axis %d, more than 2^21 voxels of %d: pass a clip or a larger cell (a tail artefact far outside the cloud?)",
+                       (long long)q.max[axis] - (long long)q.min[axis], axis, vox.cell);
+    default: break;
+    }
+    p.st.batches_outside = n - nL; p.st.batches_decoded = nL;
+
+    if (c->thin_capacity < nL) {
+        dfree(c->d_thin_list); dfree(c->d_thin_totals); dfree(c->d_thin_wlist); dfree(c->d_thin_offsets); c->thin_capacity = 0;
+        if (hipMalloc((void **)&c->d_thin_list, (size_t)nL * 4) != hipSuccess || hipMalloc((void **)&c->d_thin_totals, (size_t)nL * 8) != hipSuccess ||
+            hipMalloc((void **)&c->d_thin_wlist, (size_t)nL * 4) != hipSuccess || hipMalloc((void **)&c->d_thin_offsets, (size_t)nL * 8) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for the lists of %lld batches", (long long)nL);
+        c->thin_capacity = nL;
+    }
+    if (!c->d_thin_error && hipMalloc((void **)&c->d_thin_error, 4) != hipSuccess) return set_err(c, PCR_E_NOMEM, "out of device memory for a word");
+    if (!thin_grow((void **)&c->d_thin_keep, c->thin_keep_words, n * PCR_WORKGROUP_SIZE, 8))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the keep bitmap of %lld batches", (long long)n);
+
+    a.first_batch = (uint32_t)first;
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)nL), block(PCR_WORKGROUP_SIZE);
+    const bool windows = select_reads_windows(c);
+    HIP_TRY(c, hipMemcpyAsync(c->d_thin_list, p.listed.data(), (size_t)nL * 4, hipMemcpyHostToDevice, c->stream));
+    if (windows) hipLaunchKernelGGL((k_thin_runs<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_thin_list, a, c->d_thin_totals);
+    else         hipLaunchKernelGGL((k_thin_runs<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_thin_list, a, c->d_thin_totals);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint32_t> totals((size_t)nL * 2 + 1);
+    HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_thin_totals, (size_t)nL * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int64_t k = 0; k < nL; ++k) { p.st.runs += totals[(size_t)k * 2]; p.st.points_considered += totals[(size_t)k * 2 + 1]; }
+    if (p.st.runs == 0) return PCR_OK;
+
+    uint32_t log2_slots = 10;
+    while (((int64_t)1 << log2_slots) < 2 * p.st.runs) ++log2_slots;
+    const int64_t slots = (int64_t)1 << log2_slots;
+    if (!thin_grow((void **)&c->d_thin_table, c->thin_slots, slots, sizeof(ThinSlot)))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for a voxel table of %lld slots (%lld runs): pass a clip or a larger cell", (long long)slots,
+                       (long long)p.st.runs);
+    p.st.table_slots = slots;
+    a.log2_slots = log2_slots; a.table = c->d_thin_table; a.error = c->d_thin_error;
+    HIP_TRY(c, hipMemsetAsync(c->d_thin_table, 0xFF, (size_t)slots * sizeof(ThinSlot), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_thin_keep, 0, (size_t)n * PCR_WORKGROUP_SIZE * 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_thin_error, 0, 4, c->stream));
+#define PCR_LAUNCH(L, M) hipLaunchKernelGGL((k_thin_mark<L, M>), grid, block, 0, c->stream, s, c->d_thin_list, a)
+    if (windows) { if (mode == PCR_THIN_CENTER) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, PCR_THIN_CENTER); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, PCR_THIN_FIRST); }
+    else         { if (mode == PCR_THIN_CENTER) PCR_LAUNCH(LAYOUT_WORDS, PCR_THIN_CENTER); else PCR_LAUNCH(LAYOUT_WORDS, PCR_THIN_FIRST); }
+#undef PCR_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(k_thin_flag, dim3((unsigned)std::min<int64_t>((slots + 255) / 256, 4096)), dim3(256), 0, c->stream, c->d_thin_table,
+                       (unsigned long long)slots, (unsigned long long)n * PCR_POINTS_PER_BATCH, c->d_thin_keep);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(k_thin_totals, grid, dim3(256), 0, c->stream, c->d_thin_list, (uint32_t)first, c->d_thin_keep, c->d_thin_totals);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_thin_totals, (size_t)nL * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(totals.data() + nL * 2, c->d_thin_error, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (totals[(size_t)nL * 2]) return set_err(c, PCR_E_NOMEM, "voxel table overflow: %lld slots for %lld runs", (long long)slots, (long long)p.st.runs);
+    for (int64_t k = 0; k < nL; ++k) {
+        if (!totals[(size_t)k]) continue;
+        p.writers.push_back(p.listed[(size_t)k]); p.cnt.push_back(totals[(size_t)k]);
+        p.st.points_kept += totals[(size_t)k];
+    }
+    return PCR_OK;
+}
+
+// Enqueue the writes of batches [i0, i1) of the plan's range: their kept records to `points`, the rows to `rows` (device, either
+// may be NULL, each holds the records of those batches). The caller synchronises.
+int thin_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, uint4 *points, int64_t *rows)
+{
+    const size_t w0 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i0)) - p.writers.begin());
+    const size_t w1 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i1)) - p.writers.begin());
+    if (w0 == w1) return PCR_OK;
+    p.offsets.clear();
+    int64_t off = 0;
+    for (size_t w = w0; w < w1; ++w) { p.offsets.push_back(off); off += p.cnt[w]; }
+    HIP_TRY(c, hipMemcpyAsync(c->d_thin_wlist + w0, p.writers.data() + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_thin_offsets + w0, p.offsets.data(), (w1 - w0) * 8, hipMemcpyHostToDevice, c->stream));
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)(w1 - w0)), block(PCR_WORKGROUP_SIZE);
+    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
+#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_thin_write<L, B>), grid, block, 0, c->stream, s, c->d_thin_wlist + w0, (uint32_t)first, c->d_thin_keep, \
+                                            c->d_thin_offsets + w0, points, rows)
+    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
+    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+#undef PCR_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    return PCR_OK;
+}
+
+// The checks and the plan shared by pcr_thin / pcr_read_thin. *done: nothing left to write (an error, a count-only call, no records).
+int thin_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int mode, const void *points, size_t points_align,
+                 const void *rows, size_t rows_align, size_t capacity, int64_t *out_count, pcr_thin_stats *stats, int64_t *n, ThinPlan &p, bool *done)
+{
+    *done = true;
+    if (out_count) *out_count = 0;
+    int rc = select_range(c, first, count, n);
+    if (rc) return rc;
+    if (!vox) return set_err(c, PCR_E_ARG, "the voxel lattice is NULL");
+    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
+    if (points && reinterpret_cast<uintptr_t>(points) % points_align != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
+    if (rows && reinterpret_cast<uintptr_t>(rows) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the rows is misaligned (%zu bytes)", rows_align);
+    if (vox->cell < 1 || vox->cell > PCR_THIN_MAX_CELL)
+        return set_err(c, PCR_E_ARG, "voxel cell of %d: the edge length is 1 .. %d (PCR_THIN_MAX_CELL)", vox->cell, PCR_THIN_MAX_CELL);
+    if (mode != PCR_THIN_FIRST && mode != PCR_THIN_CENTER) return set_err(c, PCR_E_ARG, "mode is %d, not PCR_THIN_FIRST or PCR_THIN_CENTER", mode);
+    if (mode == PCR_THIN_CENTER && vox->cell > PCR_THIN_MAX_CENTER_CELL)
+        return set_err(c, PCR_E_ARG, "voxel cell of %d with PCR_THIN_CENTER: at most %d (PCR_THIN_MAX_CENTER_CELL)", vox->cell, PCR_THIN_MAX_CENTER_CELL);
+    if (*n > ((int64_t)1 << 40) / PCR_POINTS_PER_BATCH) return set_err(c, PCR_E_ARG, "a range of %lld batches has more than 2^40 rows", (long long)*n);
+    if ((rc = thin_plan(c, first, *n, *vox, clip, mode, p))) return rc;
+    *out_count = p.st.points_kept;
+    if (stats) *stats = p.st;
+    if ((!points && !rows) || p.st.points_kept == 0) return PCR_OK;
+    if (capacity < (size_t)p.st.points_kept)
+        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld kept", capacity, (long long)p.st.points_kept);
+    *done = false;
+    return PCR_OK;
+}
+} // namespace
+
+int pcr_thin(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int mode, void *dev_points, void *dev_rows,
+             size_t capacity_points, int64_t *out_count, pcr_thin_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = thin_prepare(c, first_batch, count, vox, clip, mode, dev_points, 16, dev_rows, 8, capacity_points, out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    if ((rc = thin_emit(c, first_batch, 0, n, p, static_cast<uint4 *>(dev_points), static_cast<int64_t *>(dev_rows)))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+int pcr_read_thin(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int mode, pcr_point *host_points,
+                  int64_t *host_rows, size_t capacity_points, int64_t *out_count, pcr_thin_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = thin_prepare(c, first_batch, count, vox, clip, mode, host_points, alignof(pcr_point), host_rows, alignof(int64_t), capacity_points, out_count,
+                          stats, &n, p, &done);
+    if (rc || done) return rc;
+    // pieces of at most DECODE_STAGE_BATCHES batches: a batch keeps at most 65 536 records, so a piece fits the staging buffers
+    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
+    if (host_points && !thin_grow((void **)&c->d_decode_stage, c->decode_stage_batches, piece, (size_t)PCR_POINTS_PER_BATCH * sizeof(pcr_point)))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of points", (long long)piece);
+    if (host_rows && !thin_grow((void **)&c->d_thin_rows_stage, c->thin_rows_stage_batches, piece, (size_t)PCR_POINTS_PER_BATCH * sizeof(int64_t)))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of rows", (long long)piece);
+    uint4 *const d_points = host_points ? reinterpret_cast<uint4 *>(c->d_decode_stage) : nullptr;
+    int64_t *const d_rows = host_rows ? c->d_thin_rows_stage : nullptr;
+    int64_t written = 0;
+    size_t w = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += piece) {
+        const int64_t i1 = std::min(n, i0 + piece);
+        int64_t m = 0;
+        for (; w < p.writers.size() && p.writers[w] < (uint32_t)(first_batch + i1); ++w) m += p.cnt[w];
+        if (m == 0) continue;
+        if ((rc = thin_emit(c, first_batch, i0, i1, p, d_points, d_rows))) return rc;
+        if (d_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
+        if (d_rows) HIP_TRY(c, hipMemcpyAsync(host_rows + written, d_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        written += m;
+    }
     return PCR_OK;
 }
 

@@ -1,6 +1,7 @@
 // pcr_decode — a .huffman file back to a LAS file, decoded on the GPU (pcr_read_points). The reference has no such tool: its only
 // decoder outside the render kernels is the per-chain CPU one of include/huffman.h:433-477.
 //     pcr_decode <in.huffman> <out.las> [--box x0 y0 z0 x1 y1 z1]
+//     pcr_decode <in.huffman> <out.las> --thin CELL [--center] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1] [--rect x0 y0 x1 y1]
 //     pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]
 // Loads the file with the loader of the render tools (HuffmanLasData, csrc/pcr_methods.hpp), reads the points back in pieces of
@@ -8,7 +9,8 @@
 // coordinates are read back (pcr_read_box: batches the box misses are not decoded). With --view only the points a frame of that
 // camera draws (pcr_render's camera arguments and defaults), and of those the ones inside --rect, a rectangle of pixels
 // (pcr_read_screen). With --ortho no points are read back at all: the stream is rasterized top-down on the GPU (pcr_read_grid) into
-// an orthophoto and, with --dsm, a surface model.
+// an orthophoto and, with --dsm, a surface model. With --thin one point per cubic voxel is read back (pcr_read_thin): the cloud
+// decimated on the GPU without ever existing in full.
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -24,6 +26,7 @@ using namespace pcr_host;
 
 static const char *USAGE =
     "usage: pcr_decode <in.huffman> <out.las> [--box x0 y0 z0 x1 y1 z1]\n"
+    "       pcr_decode <in.huffman> <out.las> --thin CELL [--center] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1]\n"
     "                                                [--rect x0 y0 x1 y1]\n"
     "       pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]\n"
@@ -35,6 +38,10 @@ static const char *USAGE =
     "  the first batch record's, its min / max the cloud's box as that record carries it (single precision).\n"
     "  --box: only the points p with x0 <= p.x <= x1, y0 <= p.y <= y1, z0 <= p.z <= z1 in world coordinates (integer * scale +\n"
     "  offset, in double precision), selected on the GPU, in the stream's order. A box that holds no point is an error.\n"
+    "  --thin CELL: one point of every cubic voxel of CELL world units (a whole number of the stream's x, y and z lattice steps;\n"
+    "  the lattice starts at the min corner of the header's box), thinned on the GPU, in the stream's order: the voxel's first\n"
+    "  point in that order, with --center the one nearest to the voxel's centre. Only the points inside --box count, or inside\n"
+    "  the box of the file's header. No point there is an error.\n"
     "  --view: only the points a frame of that camera draws (the basic method's cull and level of detail; the options and their\n"
     "  defaults are pcr_render's), in the stream's order; --rect: of those the ones whose pixel lies in the rectangle (pixels,\n"
     "  bounds inclusive, x0 <= x1 and y0 <= y1). A view that shows no point is an error.\n"
@@ -111,6 +118,31 @@ static bool parse_box(int argc, char **argv, int at, double lo[3], double hi[3])
         const double v = std::strtod(a, &end);
         if (end == a || *end != '\0' || errno == ERANGE || !std::isfinite(v)) return false;
         (k < 3 ? lo[k] : hi[k - 3]) = v;
+    }
+    return true;
+}
+
+struct Thin {
+    double cell = 0.0;
+    bool center = false, has_box = false;
+    double lo[3], hi[3];
+};
+
+// the options behind --thin, every one well formed, or false
+static bool parse_thin(int argc, char **argv, int at, Thin &t)
+{
+    if (argc < at + 2 || std::strcmp(argv[at], "--thin") != 0) return false;
+    if (!parse_double(argv[at + 1], t.cell) || !(t.cell > 0.0)) return false;
+    for (int i = at + 2; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--box" && i + 6 < argc && !t.has_box) {
+            for (int k = 0; k < 6; ++k) if (!parse_double(argv[++i], k < 3 ? t.lo[k] : t.hi[k - 3])) return false;
+            t.has_box = true;
+        } else if (a == "--center" && !t.center) {
+            t.center = true;
+        } else {
+            return false;
+        }
     }
     return true;
 }
@@ -199,9 +231,11 @@ int main(int argc, char **argv)
     View view;
     Ortho ortho;
     const bool viewed = argc > 3 && std::strcmp(argv[3], "--view") == 0, orthoed = argc > 3 && std::strcmp(argv[3], "--ortho") == 0;
-    const bool boxed = argc > 3 && !viewed && !orthoed;
+    Thin thin;
+    const bool thinned = argc > 3 && std::strcmp(argv[3], "--thin") == 0;
+    const bool boxed = argc > 3 && !viewed && !orthoed && !thinned;
     if (argc < 3 || (boxed && !parse_box(argc, argv, 3, lo, hi)) || (viewed && !parse_view(argc, argv, 3, view)) ||
-        (orthoed && !parse_ortho(argc, argv, 3, ortho))) { std::fputs(USAGE, stderr); return 2; }
+        (orthoed && !parse_ortho(argc, argv, 3, ortho)) || (thinned && !parse_thin(argc, argv, 3, thin))) { std::fputs(USAGE, stderr); return 2; }
     const std::string in = argv[1], out = argv[2];
     try {
         Renderer renderer(viewed ? view.w : 64, viewed ? view.h : 64, 0);
@@ -227,6 +261,14 @@ int main(int argc, char **argv)
             const pcr_select_stats st = las->selectBox(boxFromWorld(info, lo, hi), points);
             std::printf("box: batches outside %lld, inside %lld, straddling %lld\n", (long long)st.batches_outside, (long long)st.batches_inside,
                         (long long)st.batches_straddling);
+            if (points.empty()) throw std::runtime_error("no points inside the box: nothing written");
+        } else if (thinned) {
+            const pcr_voxels vox = voxelsFromWorld(info, thin.cell, info.min);
+            const pcr_box clip = boxFromWorld(info, thin.has_box ? thin.lo : info.min, thin.has_box ? thin.hi : info.max);
+            const pcr_thin_stats st = las->thin(vox, &clip, thin.center ? PCR_THIN_CENTER : PCR_THIN_FIRST, points);
+            std::printf("thin: cell of %d lattice steps, batches outside %lld, decoded %lld, points considered %lld, runs %lld, kept %lld, table slots %lld\n",
+                        vox.cell, (long long)st.batches_outside, (long long)st.batches_decoded, (long long)st.points_considered, (long long)st.runs,
+                        (long long)st.points_kept, (long long)st.table_slots);
             if (points.empty()) throw std::runtime_error("no points inside the box: nothing written");
         } else if (viewed) {
             renderer.yaw = view.cam[0]; renderer.pitch = view.cam[1]; renderer.radius = view.cam[2];

@@ -17,6 +17,7 @@
 //   k_decode_points on request: the same decode, every point of a range of batches written out as {x, y, z, colour} records
 //   k_screen_* / k_pick*  on request: the points a frame draws, selected by pixel (projection restated in screen_project)
 //   k_grid*         on request: the stream rasterized top-down into max / min / count planes over its integer x and y
+//   k_thin_*        on request: one record per voxel of a cubic lattice, straight from the compressed stream
 //   k_las_*         the 10-10-10 method (modules/compute_loop_las_cuda)
 //   k_resolve_*     framebuffer -> RGBA8 (resolve.cu:149-191, huffman_hqs/resolve.cu:2-47)
 //   k_merge_* / k_flip_sign  multi-GPU partial-framebuffer merges
@@ -25,6 +26,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "pcr_types.h"
+#include "pcr_lattice.h"
 
 namespace pcr {
 
@@ -2243,22 +2245,20 @@ struct GridEntry { uint32_t b, wx0, wy0, ww, wh; };     // a listed batch and it
 struct GridArgs {
     pcr_box q;                      // grid and clip intersected, in the stream's coordinates, not empty: a point inside has a cell
     int32_t ox, oy;                 // pcr_grid::origin_x / origin_y
-    uint32_t shift;                 // cell == 1 << shift; GRID_NO_SHIFT: not a power of two, then
-    unsigned long long magic;       // ceil(2^64 / cell)
+    CellDiv div;                    // pcr_grid::cell as a divisor (pcr_lattice.h)
     uint32_t width;
     uint32_t win_cells;             // cells of each LDS plane of this launch (windowed): the largest window listed
     unsigned long long *top, *bottom;
     uint32_t *count;
 };
-constexpr uint32_t GRID_NO_SHIFT = 32;
 constexpr uint32_t GRID_TABLE_BYTES = PCR_HUFFMAN_TABLE_SIZE * 4;
 
 // d / cell, exact for every 32-bit d. With m = ceil(2^64 / c) and c no power of two, m * c = 2^64 + e with 0 < e < c, so
 // d * m / 2^64 = d / c + d * e / (c * 2^64), and the excess is below 2^32 * c / (c * 2^64) = 2^-32 <= 1 / c: too little to
 // carry the fraction of d / c (at most 1 - 1 / c) over the next integer.
-__device__ __forceinline__ uint32_t grid_div(const GridArgs &a, uint32_t d)
+__device__ __forceinline__ uint32_t grid_div(const CellDiv &c, uint32_t d)
 {
-    return a.shift < GRID_NO_SHIFT ? d >> a.shift : (uint32_t)__umul64hi((unsigned long long)d, a.magic);
+    return c.shift < CELL_NO_SHIFT ? d >> c.shift : (uint32_t)__umul64hi((unsigned long long)d, c.magic);
 }
 
 template <int LAYOUT, int COLOUR, bool WINDOWED>
@@ -2284,7 +2284,7 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_grid(StreamView s, const
     load_packed_table(s, e.b, s_table);                                     // (its barrier publishes the window as well)
     decode_chain<LAYOUT, COLOUR>(s, e.b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t colour) {
         if (!in_box(a.q, x, y, z)) return;
-        const uint32_t cx = grid_div(a, (uint32_t)x - (uint32_t)a.ox), cy = grid_div(a, (uint32_t)y - (uint32_t)a.oy);
+        const uint32_t cx = grid_div(a.div, (uint32_t)x - (uint32_t)a.ox), cy = grid_div(a.div, (uint32_t)y - (uint32_t)a.oy);
         const u64 key = ((u64)((uint32_t)z ^ 0x80000000u) << 32) | colour;
         if (WINDOWED) {
             const uint32_t lx = cx - e.wx0, ly = cy - e.wy0;
@@ -2331,6 +2331,176 @@ __global__ void __launch_bounds__(256) k_grid_unpack(const unsigned long long *w
         if (height) height[i] = w == empty ? INT32_MIN : (int32_t)((uint32_t)(w >> 32) ^ 0x80000000u);
         if (rgba) rgba[i] = w == empty ? 0u : ((uint32_t)w | 0xFF000000u);
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Voxel-grid thinning (pcr_thin / pcr_read_thin): of the rows of a range inside a clip box, one per voxel of a cubic lattice --
+// the lowest row (PCR_THIN_FIRST) or the least by (distance to the voxel's centre, row) (PCR_THIN_CENTER). Four phases, each a
+// launch of its own over the batches the clip does not miss (`list`), the sizes in between computed by the host:
+//   k_thin_runs    colourless decode: per batch the candidates and the runs -- maximal stretches of consecutive candidates of a
+//                  chain with one voxel key. The host sizes the table from their sum.
+//   k_thin_mark    colourless decode again: at the end of every run one insertion of (key, the run's best value) into an
+//                  open-addressing table in global memory: compare-and-swap on the key, unsigned minimum on the value.
+//   k_thin_flag    a thread per slot: the winning row's bit into the keep bitmap (a 64-bit word per chain);
+//   k_thin_totals  the kept records of every listed batch.
+//   k_thin_write   decode with colour of the batches that keep a record: k_select_write with the chain's keep word as the test.
+// The value is the row (FIRST) or d2 << 40 | row (CENTER; d2 < 2^24, row < 2^40), so the minimum decides both orders at once.
+// Minimum commutes: the table's content does not depend on the order of lanes, workgroups or launches, and a voxel whose
+// candidates are scattered over chains and batches (or come back later in one chain of an unsorted stream) still gets the one
+// least value. No workgroup waits for another one; the probe loop makes at most `slots` steps.
+// ------------------------------------------------------------------------------------------------
+typedef unsigned long long thin_u64;
+struct ThinSlot { thin_u64 key, val; };                     // empty: both all ones (a key has 63 bits)
+constexpr thin_u64 THIN_EMPTY = ~0ull;
+constexpr thin_u64 THIN_ROW_MASK = (1ull << 40) - 1;
+constexpr thin_u64 THIN_HASH_MUL = 0x9E3779B97F4A7C15ull;   // odd: key -> key * MUL is a bijection of the 64-bit words
+
+struct ThinArgs {
+    pcr_box q;                      // the clip (every int32 point if the call has none)
+    ThinLattice lat;                // pcr_lattice.h: for a point inside the call's q, (p - origin) mod 2^32 / cell < 2^21
+    uint32_t first_batch;           // row = (b - first_batch) * 65536 + chain * 64 + i
+    uint32_t log2_slots;            // >= 10
+    ThinSlot *table;
+    uint32_t *error;                // set to 1 by a lane that found no slot
+};
+
+__device__ __forceinline__ thin_u64 thin_key(const ThinArgs &a, int32_t x, int32_t y, int32_t z, uint32_t &d2)
+{
+    const uint32_t dx = (uint32_t)x - a.lat.origin[0], dy = (uint32_t)y - a.lat.origin[1], dz = (uint32_t)z - a.lat.origin[2];
+    const uint32_t vx = grid_div(a.lat.div, dx), vy = grid_div(a.lat.div, dy), vz = grid_div(a.lat.div, dz);
+    // 2 * (offset inside the voxel) - (cell - 1): twice the signed distance to the centre, |.| <= cell - 1
+    const int32_t ex = (int32_t)(2u * (dx - vx * a.lat.cell)) - (int32_t)(a.lat.cell - 1u);
+    const int32_t ey = (int32_t)(2u * (dy - vy * a.lat.cell)) - (int32_t)(a.lat.cell - 1u);
+    const int32_t ez = (int32_t)(2u * (dz - vz * a.lat.cell)) - (int32_t)(a.lat.cell - 1u);
+    d2 = (uint32_t)ex * (uint32_t)ex + (uint32_t)ey * (uint32_t)ey + (uint32_t)ez * (uint32_t)ez;   // (only read for cell <= PCR_THIN_MAX_CENTER_CELL)
+    return (thin_u64)vx | ((thin_u64)vy << THIN_KEY_BITS) | ((thin_u64)vz << (2 * THIN_KEY_BITS));
+}
+
+// Workgroup x takes list[x]: totals[2 x] = its runs, totals[2 x + 1] = its candidates
+template <int LAYOUT>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_thin_runs(StreamView s, const uint32_t *list, ThinArgs a, uint32_t *totals)
+{
+    const uint32_t b = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint32_t s_part[LWC_WAVES][2];
+    load_packed_table(s, b, s_table);
+    uint32_t runs = 0, cand = 0;
+    thin_u64 prev = THIN_EMPTY;
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t) {
+        uint32_t d2;
+        const thin_u64 key = in_box(a.q, x, y, z) ? thin_key(a, x, y, z, d2) : THIN_EMPTY;
+        cand += key != THIN_EMPTY ? 1u : 0u;
+        runs += key != THIN_EMPTY && key != prev ? 1u : 0u;
+        prev = key;
+    });
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { runs += __shfl_xor(runs, d, 64); cand += __shfl_xor(cand, d, 64); }
+    if (lane == 0) { s_part[wave][0] = runs; s_part[wave][1] = cand; }
+    __syncthreads();
+    if (tid < 2) {
+        uint32_t t = 0;
+        for (int w = 0; w < LWC_WAVES; ++w) t += s_part[w][tid];
+        totals[(size_t)blockIdx.x * 2 + tid] = t;
+    }
+}
+
+// (key, val) into the table: the slot of the key, or the first free one from the key's home on, keeps the least val
+__device__ __forceinline__ void thin_insert(const ThinArgs &a, thin_u64 key, thin_u64 val)
+{
+    const thin_u64 slots = 1ull << a.log2_slots, mask = slots - 1;
+    thin_u64 h = (key * THIN_HASH_MUL) >> (64u - a.log2_slots);
+    for (thin_u64 probe = 0; probe < slots; ++probe) {
+        ThinSlot *slot = a.table + h;
+        thin_u64 old = __hip_atomic_load(&slot->key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // (a taken slot never changes its key)
+        if (old == THIN_EMPTY) old = atomicCAS(&slot->key, THIN_EMPTY, key);
+        if (old == THIN_EMPTY || old == key) {
+            __hip_atomic_fetch_min(&slot->val, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // (the result is not used)
+            return;
+        }
+        h = (h + 1) & mask;
+    }
+    *a.error = 1u;                                          // every slot holds another key: the host sized the table wrongly
+}
+
+template <int LAYOUT, int MODE>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_thin_mark(StreamView s, const uint32_t *list, ThinArgs a)
+{
+    const uint32_t b = list[blockIdx.x];
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    load_packed_table(s, b, s_table);
+    const thin_u64 row0 = (thin_u64)(b - a.first_batch) * PCR_POINTS_PER_BATCH + (thin_u64)threadIdx.x * PCR_POINTS_PER_THREAD;
+    thin_u64 prev = THIN_EMPTY, best = THIN_EMPTY;
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t) {
+        uint32_t d2 = 0;
+        const thin_u64 key = in_box(a.q, x, y, z) ? thin_key(a, x, y, z, d2) : THIN_EMPTY;
+        const thin_u64 val = MODE == PCR_THIN_CENTER ? ((thin_u64)d2 << 40) | (row0 + (uint32_t)i) : row0 + (uint32_t)i;
+        if (key == prev) {
+            if (MODE == PCR_THIN_CENTER) best = min(best, val);         // (FIRST: the run's first row is its least)
+        } else {
+            if (prev != THIN_EMPTY) thin_insert(a, prev, best);
+            prev = key; best = val;
+        }
+    });
+    if (prev != THIN_EMPTY) thin_insert(a, prev, best);
+}
+
+// keep[row >> 6] |= 1 << (row & 63) for the row of every taken slot (rows: those below `rows`, which is every row of the call)
+__global__ void __launch_bounds__(256) k_thin_flag(const ThinSlot *table, thin_u64 slots, thin_u64 rows, thin_u64 *keep)
+{
+    for (thin_u64 i = (thin_u64)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (thin_u64)gridDim.x * blockDim.x) {
+        if (table[i].key == THIN_EMPTY) continue;
+        const thin_u64 row = table[i].val & THIN_ROW_MASK;
+        if (row < rows) atomicOr(&keep[row >> 6], 1ull << (row & 63u));
+    }
+}
+
+// Workgroup x: totals[x] = the bits set in the 1024 keep words of batch list[x]
+__global__ void __launch_bounds__(256) k_thin_totals(const uint32_t *list, uint32_t first_batch, const thin_u64 *keep, uint32_t *totals)
+{
+    const thin_u64 *words = keep + (size_t)(list[blockIdx.x] - first_batch) * PCR_WORKGROUP_SIZE;
+    __shared__ uint32_t s_part[4];
+    uint32_t sum = 0;
+    for (uint32_t i = threadIdx.x; i < PCR_WORKGROUP_SIZE; i += 256) sum += (uint32_t)__popcll(words[i]);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    if ((threadIdx.x & 63u) == 0) s_part[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) totals[blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+}
+
+// Workgroup x takes list[x], a batch that keeps a record: the flagged records go to points[offsets[x] ..] and their rows to
+// rows[offsets[x] ..] (either may be NULL), chain after chain, each chain's in point order. A lane's keep word is its chain's.
+template <int LAYOUT, bool BC7>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_thin_write(StreamView s, const uint32_t *list, uint32_t first_batch, const thin_u64 *keep,
+                                                                   const int64_t *offsets, uint4 *points, int64_t *rows)
+{
+    const uint32_t b = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint32_t s_part[LWC_WAVES];
+    const thin_u64 word = keep[(size_t)(b - first_batch) * PCR_WORKGROUP_SIZE + tid];
+    const uint32_t mine = (uint32_t)__popcll(word);
+    uint32_t incl = mine;                                   // inclusive prefix inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += up;
+    }
+    if (lane == 63) s_part[wave] = incl;
+    load_packed_table(s, b, s_table);                       // (its barrier publishes s_part as well)
+    uint32_t before = incl - mine;
+    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    int64_t dst = offsets[blockIdx.x] + before;
+    const int64_t end = dst + mine;                         // never past the bits of this chain's word
+    const int64_t row0 = (int64_t)(b - first_batch) * PCR_POINTS_PER_BATCH + (int64_t)tid * PCR_POINTS_PER_THREAD;
+    decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        if (((word >> (uint32_t)i) & 1ull) && dst < end) {
+            if (points) points[dst] = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
+            if (rows) rows[dst] = row0 + i;
+            ++dst;
+        }
+    });
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,0 +1,53 @@
+// Integer lattice arithmetic shared by the top-down grid and the voxel thinning: the exact division of a 32-bit difference by a
+// cell, and the lattice pcr_thin hands to its kernels. Plain C++ without a HIP dependency, so a host-only build can call it.
+#pragma once
+#include <cstdint>
+
+// d / cell for every 32-bit d: a shift for a power of two, else the high half of d * ceil(2^64 / cell) (see grid_div).
+struct CellDiv {
+    uint32_t shift;                 // cell == 1 << shift; CELL_NO_SHIFT: not a power of two, then
+    unsigned long long magic;       // ceil(2^64 / cell)
+};
+constexpr uint32_t CELL_NO_SHIFT = 32;
+
+inline CellDiv make_cell_div(uint32_t cell)                 // cell >= 1
+{
+    CellDiv d{};
+    if ((cell & (cell - 1)) == 0) { d.shift = (uint32_t)__builtin_ctz(cell); d.magic = 0; }
+    else { d.shift = CELL_NO_SHIFT; d.magic = ~0ull / cell + 1; }           // ceil(2^64 / cell): cell does not divide 2^64
+    return d;
+}
+
+inline int64_t floor_div64(int64_t a, int64_t b)            // b > 0
+{
+    const int64_t q = a / b;
+    return q * b > a ? q - 1 : q;
+}
+
+// The lattice of a thinning call, shifted by whole cells so that q.min lies in voxel 0 on every axis: origin' = origin +
+// floor((q.min - origin) / cell) * cell in 64 bits. For a point p inside q, d = p - origin' is in [0, q.max - q.min + cell), so
+// it fits 32 unsigned bits (the kernels take it modulo 2^32 from the low half of origin'), and v' = d / cell <= (q.max - q.min)
+// / cell + 1. Shifting by whole cells changes neither which points share a voxel nor a point's offset inside its voxel.
+struct ThinLattice {
+    uint32_t origin[3];             // the low 32 bits of origin'
+    uint32_t cell;
+    CellDiv div;
+};
+constexpr int THIN_KEY_BITS = 21;                           // per axis: the key is v'x | v'y << 21 | v'z << 42, 63 bits
+enum { THIN_LATTICE_OK = 0, THIN_LATTICE_EXTENT = 1, THIN_LATTICE_VOXELS = 2 };
+
+// THIN_LATTICE_EXTENT: q spans 2^31 or more on *axis; THIN_LATTICE_VOXELS: more than 2^21 voxels there. q is not empty.
+inline int thin_lattice(const int32_t origin[3], int32_t cell, const int32_t qmin[3], const int32_t qmax[3], ThinLattice *out, int *axis)
+{
+    for (int k = 0; k < 3; ++k) {
+        const int64_t extent = (int64_t)qmax[k] - (int64_t)qmin[k];
+        *axis = k;
+        if (extent >= (int64_t)1 << 31) return THIN_LATTICE_EXTENT;
+        if (extent / cell + 2 > (int64_t)1 << THIN_KEY_BITS) return THIN_LATTICE_VOXELS;
+        const int64_t shifted = (int64_t)origin[k] + floor_div64((int64_t)qmin[k] - (int64_t)origin[k], cell) * (int64_t)cell;
+        out->origin[k] = (uint32_t)(uint64_t)shifted;
+    }
+    out->cell = (uint32_t)cell;
+    out->div = make_cell_div((uint32_t)cell);
+    return THIN_LATTICE_OK;
+}

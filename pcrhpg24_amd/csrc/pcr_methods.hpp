@@ -329,6 +329,20 @@ struct HuffmanLasData : Resource {
         return st;
     }
 
+    // One point per voxel of `vox` among the points inside `clip` (NULL: everywhere), thinned on the GPU straight from the compressed
+    // stream (pcr_read_thin: a counting call, then the read). Not in the reference.
+    pcr_thin_stats thin(const pcr_voxels &vox, const pcr_box *clip, int mode, std::vector<pcr_point> &out)
+    {
+        if (!loadedOn) throw std::runtime_error("thin: the resource is not loaded");
+        const int64_t nB = pcr_batches_resident(loadedOn->ctx);
+        int64_t n = 0;
+        pcr_thin_stats st{};
+        loadedOn->check(pcr_read_thin(loadedOn->ctx, 0, nB, &vox, clip, mode, nullptr, nullptr, 0, &n, &st), "pcr_read_thin");
+        out.resize((size_t)n);
+        if (n) loadedOn->check(pcr_read_thin(loadedOn->ctx, 0, nB, &vox, clip, mode, out.data(), nullptr, out.size(), &n, &st), "pcr_read_thin");
+        return st;
+    }
+
     // The points a frame of camera `p` draws whose pixel lies in `rect` (NULL: the whole image), with where they land, selected on
     // the GPU (pcr_read_screen: a counting call, then the read). Either vector may be NULL. Not in the reference.
     pcr_screen_stats selectScreen(const pcr_render_params &p, const pcr_rect *rect, std::vector<pcr_point> *points, std::vector<pcr_screen_hit> *hits)
@@ -486,6 +500,28 @@ inline pcr_grid gridFromWorld(const pcr_las_info &las, const double lo[2], const
     const int64_t w = ((int64_t)b.max[0] - b.min[0]) / cells[0] + 1, h = ((int64_t)b.max[1] - b.min[1]) / cells[0] + 1;
     if (w * h > PCR_GRID_MAX_CELLS) throw std::runtime_error("gridFromWorld: more cells than PCR_GRID_MAX_CELLS");
     return pcr_grid{b.min[0], b.min[1], (int32_t)cells[0], (int32_t)w, (int32_t)h, 0};
+}
+
+// The lattice of cubic voxels of `cell_size` world units with the min corner of voxel (0, 0, 0) at the first lattice point at or above
+// `origin` on each axis (boxFromWorld's): cell_size has to be the same whole number (1 .. PCR_THIN_MAX_CELL) of steps of the x, the y
+// and the z lattice. The Python twin is host.voxels_from_world.
+inline pcr_voxels voxelsFromWorld(const pcr_las_info &las, double cell_size, const double origin[3])
+{
+    int64_t cells[3];
+    for (int k = 0; k < 3; ++k) {
+        const double s = las.scale[k];
+        if (!(s > 0.0) || !(cell_size > 0.0)) throw std::runtime_error("voxelsFromWorld: needs positive scales and a positive cell size");
+        const double n = std::nearbyint(cell_size / s);
+        if (!(n >= 1.0) || n > (double)PCR_THIN_MAX_CELL || std::fabs(n * s - cell_size) > 1e-9 * cell_size)
+            throw std::runtime_error("voxelsFromWorld: the cell size is not a whole number (1 .. 2^30) of lattice steps");
+        cells[k] = (int64_t)n;
+    }
+    if (cells[0] != cells[1] || cells[0] != cells[2]) throw std::runtime_error("voxelsFromWorld: the cell size is a different number of lattice steps on x, y and z");
+    const double inf = std::numeric_limits<double>::infinity();
+    const double h3[3] = {inf, inf, inf};
+    const pcr_box b = boxFromWorld(las, origin, h3);
+    for (int k = 0; k < 3; ++k) if (b.min[k] > b.max[k]) throw std::runtime_error("voxelsFromWorld: the origin lies beyond every int32 coordinate");
+    return pcr_voxels{{b.min[0], b.min[1], b.min[2]}, (int32_t)cells[0]};
 }
 
 // modules/huffman_cuda/huffman_cuda.h:60-75: the reference's first Huffman method (class ComputeHuffman, registered as

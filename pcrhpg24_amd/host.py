@@ -28,7 +28,7 @@ from typing import Iterator, Optional
 import numpy as np
 
 from . import _native as N
-from ._native import Box, DisplayOpts, EncodeStats, Grid, GridStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, XyzBatch, c_i64, fb_elems
+from ._native import Box, DisplayOpts, EncodeStats, Grid, GridStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, ThinStats, Voxels, XyzBatch, c_i64, fb_elems
 
 POINTS_PER_BATCH = 65536
 ENCODED_PAD_WORDS = 1024
@@ -186,6 +186,7 @@ def read_las(path: str):
 POINT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("color", "<u4")])     # pcr_point
 
 HIT_DTYPE = np.dtype([("pixel", "<u4"), ("depth_bits", "<u4"), ("index", "<i8")])          # pcr_screen_hit
+ROW_DTYPE = np.dtype("<i8")                                                                  # a row of pcr_thin
 
 INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
 
@@ -283,6 +284,51 @@ def grid_from_world(las: LasInfo, lo_xy, hi_xy, cell_size: float) -> Grid:
     if w * h > N.GRID_MAX_CELLS:
         raise ValueError(f"{w} x {h} cells: more than the {N.GRID_MAX_CELLS} a grid may have")
     return Grid(int(box.min[0]), int(box.min[1]), cells[0], w, h, 0)
+
+
+def as_voxels(vox) -> Voxels:
+    """A pcr_voxels from a Voxels or four numbers origin x, y, z, cell (the stream's int32 coordinates)."""
+    if isinstance(vox, Voxels):
+        return vox
+    v = [int(a) for a in np.asarray(vox, dtype=np.int64).reshape(4)]
+    if any(a < INT32_MIN or a > INT32_MAX for a in v):
+        raise ValueError("voxel fields are int32")
+    out = Voxels()
+    out.origin[:], out.cell = v[:3], v[3]
+    return out
+
+
+def thin_mode(mode) -> int:
+    """PCR_THIN_FIRST / PCR_THIN_CENTER from "first" / "center" (an integer passes through: the library checks it)."""
+    if isinstance(mode, str):
+        if mode not in ("first", "center"):
+            raise ValueError('mode is "first" or "center"')
+        return N.THIN_FIRST if mode == "first" else N.THIN_CENTER
+    return int(mode)
+
+
+def voxels_from_world(las: LasInfo, cell_size: float, origin=None) -> Voxels:
+    """The lattice of cubic voxels of `cell_size` world units whose voxel (0, 0, 0) has its min corner at the first lattice point
+    at or above `origin` (world x, y, z; None: las.min) on each axis (box_from_world's). ValueError for a cell_size that is not a
+    whole number (1 .. THIN_MAX_CELL) of steps of the x, the y and the z lattice -- the voxels are cubes of integer coordinates,
+    so the three scales have to agree on that number -- or for an origin beyond every int32 coordinate."""
+    inf = float("inf")
+    cells = []
+    for k in range(3):
+        s = float(las.scale[k])
+        if not s > 0.0 or not cell_size > 0.0:
+            raise ValueError("voxels_from_world needs positive scales and a positive cell size")
+        n = round(cell_size / s)
+        if n < 1 or n > N.THIN_MAX_CELL or abs(n * s - cell_size) > 1e-9 * cell_size:
+            raise ValueError(f"a cell of {cell_size} is not a whole number (1 .. {N.THIN_MAX_CELL}) of lattice steps of {s}")
+        cells.append(int(n))
+    if not cells[0] == cells[1] == cells[2]:
+        raise ValueError(f"a cell of {cell_size} is {cells[0]}, {cells[1]} and {cells[2]} steps on x, y and z: the voxels are cubes of lattice steps")
+    origin = tuple(las.min) if origin is None else origin
+    box = box_from_world(las, origin, (inf, inf, inf))
+    if any(box.min[k] > box.max[k] for k in range(3)):
+        raise ValueError("the origin lies beyond every int32 coordinate")
+    return as_voxels((box.min[0], box.min[1], box.min[2], cells[0]))
 
 
 def write_las(path, x=None, y=None, z=None, color=None, las: Optional[LasInfo] = None, points=None) -> None:
@@ -703,6 +749,51 @@ class Context:
         self.grid_stats = st.as_dict()
         return top, bottom, cnt
 
+    # -- voxel thinning (pcr_thin / pcr_read_thin) ----------------------------------------------------------
+    def thin(self, vox, clip=None, mode="first", first: int = 0, count: Optional[int] = None, out=None, rows: bool = False):
+        """One point per voxel of `vox` (as_voxels: a Voxels or origin x, y, z, cell) among the rows of batches [first, first + count)
+        inside `clip` (as_box; None: everywhere), straight from the compressed stream: mode "first" keeps a voxel's lowest row,
+        "center" the point nearest to its centre (ties to the lowest row). A torch.int32 tensor [n, 4] on the context's device,
+        rows of decode_points of the range in increasing row order; with rows=True (points, rows), rows a torch.int64 tensor [n]
+        of their row numbers there. `out`: a contiguous int32 CUDA tensor to fill; it has to hold the result (PcrError if not;
+        thin_stats then tells the count). Without it the call counts first and allocates exactly. Stream ordering as
+        decode_points. What the last call did is in self.thin_stats."""
+        import torch
+        vox, clip, mode = as_voxels(vox), None if clip is None else as_box(clip), thin_mode(mode)
+        cp = None if clip is None else C.byref(clip)
+        dev = torch.device("cuda", self.device)
+        cnt, st, nb = c_i64(), ThinStats(), -1 if count is None else count
+        if out is None:
+            self._chk(self.lib.pcr_thin(self.h, first, nb, C.byref(vox), cp, mode, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_thin")
+            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
+        cap = out.numel() // 4
+        r = torch.empty(cap, dtype=torch.int64, device=dev) if rows else None
+        torch.cuda.current_stream(dev).synchronize()
+        rc = self.lib.pcr_thin(self.h, first, nb, C.byref(vox), cp, mode, C.c_void_p(out.data_ptr() if cap else None),
+                               C.c_void_p(r.data_ptr() if cap else None) if rows else None, cap, C.byref(cnt), C.byref(st))
+        self.thin_stats = st.as_dict()
+        if rc:
+            self.thin_stats["points_kept"] = cnt.value
+        self._chk(rc, "pcr_thin")
+        pts = out.view(-1, 4)[:cnt.value]
+        return (pts, r[:cnt.value]) if rows else pts
+
+    def read_thin(self, vox, clip=None, mode="first", first: int = 0, count: Optional[int] = None, rows: bool = False):
+        """The same on the host, without torch: a numpy structured array of POINT_DTYPE, with rows=True (points, rows), rows an
+        int64 array (pcr_read_thin: a counting call, then the read; synchronises)."""
+        vox, clip, mode = as_voxels(vox), None if clip is None else as_box(clip), thin_mode(mode)
+        cp = None if clip is None else C.byref(clip)
+        cnt, st, nb = c_i64(), ThinStats(), -1 if count is None else count
+        self._chk(self.lib.pcr_read_thin(self.h, first, nb, C.byref(vox), cp, mode, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_read_thin")
+        pts, r = np.empty(cnt.value, POINT_DTYPE), np.empty(cnt.value if rows else 0, ROW_DTYPE)
+        if cnt.value:
+            self._chk(self.lib.pcr_read_thin(self.h, first, nb, C.byref(vox), cp, mode, pts.ctypes.data, r.ctypes.data if rows else None, len(pts),
+                                             C.byref(cnt), C.byref(st)), "pcr_read_thin")
+        self.thin_stats = st.as_dict()
+        return (pts, r) if rows else pts
+
     # -- screen selection and picking (pcr_select_screen / pcr_read_screen / pcr_pick) ---------------------
     def select_screen(self, p: RenderParams, rect=None):
         """The points a frame of camera `p` draws (render_basic's cull, level of detail, precision and inside test) whose pixel lies
@@ -1083,6 +1174,28 @@ class HuffmanLasData(Resource):
         height = z.to(torch.float64) * float(info.scale[2]) + float(info.offset[2])
         height[rgba == 0] = float("nan")
         return height, rgba.view(torch.uint8).view(grid.height, grid.width, 4), count, grid
+
+    def thinned(self, renderer: Renderer, cell_size: float, lo=None, hi=None, mode: str = "first", world: bool = True):
+        """The loaded resource thinned to one point per cubic voxel of `cell_size`, on the GPU and straight from the compressed
+        stream (Context.thin): mode "first" keeps a voxel's first point in the stream's order, "center" the one nearest to the
+        voxel's centre. world=True: cell_size, lo and hi are world units -- the lattice is voxels_from_world(las_info(), cell_size)
+        (its origin at the header's min corner), the clip box_from_world(las_info(), lo, hi) with lo / hi None: the header's min /
+        max, so the tail artefact of a stream written without padding neither lands in the output nor stretches the lattice --
+        and the result is (xyz, pts) as points_in_box returns it. world=False: cell_size is a whole number of lattice steps, lo / hi
+        are the stream's int32 coordinates (None: no clip), the lattice's origin is (0, 0, 0), the result the int32 tensor alone."""
+        import torch
+        info = self.las_info()
+        if world:
+            vox = voxels_from_world(info, cell_size)
+            clip = box_from_world(info, tuple(info.min) if lo is None else lo, tuple(info.max) if hi is None else hi)
+        else:
+            vox = as_voxels((0, 0, 0, cell_size))
+            clip = None if lo is None and hi is None else as_box(((INT32_MIN,) * 3 if lo is None else lo, (INT32_MAX,) * 3 if hi is None else hi))
+        pts = renderer.ctx.thin(vox, clip, mode)
+        if not world:
+            return pts
+        so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
+        return pts[:, :3].to(torch.float64) * so[0] + so[1], pts
 
     def las_info(self) -> LasInfo:
         """Scale, offset, min and max of the LAS file the stream was made from, as its first batch record carries them (the
