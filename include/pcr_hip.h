@@ -224,6 +224,34 @@ int pcr_select_box(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_b
 int pcr_read_box(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_box *box, pcr_point *host, size_t capacity_points,
                  int64_t *out_count, pcr_select_stats *stats);
 
+/* ---- polygon selection: the stream clipped to a polygon prism (no reference counterpart) --------------------------------------
+ * CONTRACT: pcr_select_polygon / pcr_read_polygon are pcr_select_box / pcr_read_box in every respect except the predicate: the
+ * output equals pcr_decode_points of the same range with the unselected records removed, byte for byte, in the same order,
+ * packed without gaps; padding duplicates and the tail artefact are points like any other; BC1 and BC7, either resident layout
+ * (PCR_LAYOUT_BOTH follows pcr_set_render_variant), before and after the first frame; dev_points == NULL only counts; a capacity
+ * below the result is PCR_E_ARG with *out_count = the count needed and nothing written; range semantics, count < 0 and the
+ * restriction under pcr_set_async_upload are pcr_decode_points'. Synchronises. Touches no framebuffer, no prepass state, no
+ * render statistics. stats may be NULL. The predicate is pcr_polygon's (pcr_types.h): all integer, all exact.
+ *
+ * How a batch is treated, from its exact box (pcr_batch_point_bounds): R is the closed xy rectangle of the box, [zb0, zb1] its z
+ * range. An edge, horizontal ones included, is near if its bounding rectangle overlaps R. With no near edge every point of R has
+ * the same in_poly, evaluated at R's min corner. The xy verdict is all in (no near edge, the corner value differs from the
+ * invert flag), all out (no near edge, it equals the flag) or mixed (a near edge); the z verdict is all in, all out or mixed
+ * from [zb0, zb1] against [z_min, z_max]. A batch is outside (not decoded) if either verdict is all out, inside (decoded whole
+ * by the full-batch decode) if both are all in, else straddling: counted (k_polygon_count), then written (k_polygon_write).
+ * A straddling batch tests its points against its own slice of one edge array (uploaded per call; scratch of the context,
+ * grown on demand, released with it): the non-horizontal edges whose [l.y, u.y) meets R's rows and whose max x is above R's min
+ * x, except those that lie wholly right of R with [l.y, u.y) covering all of R's rows, which every point of R counts and which
+ * are folded into one parity bit of the batch. The kernels test a point against the z range and the vertices' bounding
+ * rectangle before any edge, so every difference fits 32 bits and every product stays below 2^62.
+ * PCR_E_ARG with a message, nothing written: a NULL polygon, xy, ring_sizes or out_count; num_rings < 1 or a ring of fewer than
+ * 3 vertices; more than PCR_POLY_MAX_VERTICES vertices; unknown flag bits or reserved != 0; vertices that span more than
+ * 2^31 - 1 on x or y; a misaligned destination; whatever pcr_select_box refuses about the range. */
+int pcr_select_polygon(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_polygon *poly, void *dev_points, size_t capacity_points,
+                       int64_t *out_count, pcr_polygon_stats *stats);
+int pcr_read_polygon(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_polygon *poly, pcr_point *host, size_t capacity_points,
+                     int64_t *out_count, pcr_polygon_stats *stats);
+
 /* ---- screen selection and picking: which points does a frame show, and where (no reference counterpart) -----------------------
  * CONTRACT of pcr_select_screen: the selected points are exactly those pcr_render_basic(params) scatters -- the batches its
  * cull/LOD prepass keeps, of each chain the first points by the prepass's level of detail, each batch dequantised in the

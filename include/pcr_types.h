@@ -134,6 +134,38 @@ typedef struct pcr_select_stats {
     int64_t points_selected;
 } pcr_select_stats;
 
+/* A polygon prism in the stream's int32 coordinates (pcr_select_polygon), 40 bytes: rings of vertices in x and y, a z range.
+ * Ring vertices v0..v(m-1) give the edges (v_i, v_((i+1) mod m)): a ring is closed implicitly, a repeated closing vertex is
+ * harmless. in_poly(x, y): take every edge of every ring, ordered so that l.y < u.y (horizontal edges never count); an edge
+ * counts iff l.y <= y < u.y and (x - l.x) * (u.y - l.y) < (y - l.y) * (u.x - l.x), the products exact; in_poly is true iff the
+ * number of counting edges is odd -- the even-odd rule with a half-open boundary: further rings are holes or islands, the
+ * rectangle (x0,y0),(x1,y0),(x1,y1),(x0,y1) selects x0 <= x < x1, y0 <= y < y1, and of two polygons that share an edge exactly
+ * one takes a point on it. A record is selected iff z_min <= z <= z_max and in_poly(x, y) != (flags & PCR_POLY_INVERT).
+ * The bounding rectangle of all vertices spans at most 2^31 - 1 on x and on y. */
+#define PCR_POLY_MAX_VERTICES 4096
+#define PCR_POLY_INVERT 1u            /* flags: keep the points NOT inside the polygon (the z range still applies) */
+typedef struct pcr_polygon {
+    const int32_t *xy;           /* x0, y0, x1, y1, ...: the vertices of all rings, ring after ring, stream coordinates */
+    const int32_t *ring_sizes;   /* vertices of each ring, each >= 3 */
+    int32_t num_rings;           /* >= 1 */
+    int32_t z_min, z_max;        /* inclusive; z_min > z_max: the empty query */
+    uint32_t flags;
+    uint32_t reserved;           /* 0 */
+} pcr_polygon;
+
+/* What a polygon selection did (pcr_select_polygon / pcr_read_polygon): the batches of the range by their exact box against the
+ * prism (pcr_hip.h has the rule) -- outside (not decoded), inside (decoded whole), straddling (counted, then written, each point
+ * tested against the batch's own edge list) -- the records selected, which is the call's *out_count, and the sum and the
+ * largest of the straddling batches' edge lists. */
+typedef struct pcr_polygon_stats {
+    int64_t batches_outside;
+    int64_t batches_inside;
+    int64_t batches_straddling;
+    int64_t points_selected;
+    int64_t edges_listed;
+    int64_t edges_max;
+} pcr_polygon_stats;
+
 /* A top-down grid over the stream's int32 x and y (pcr_grid_accumulate), 24 bytes. A point (x, y, z, colour) belongs to cell
  * (cx, cy) iff x >= origin_x, y >= origin_y, cx = (uint32)(x - origin_x) / cell < width and cy = (uint32)(y - origin_y) / cell
  * < height (the differences fit 32 unsigned bits for every int32 input); the cell's index in a plane is cx + cy * width.

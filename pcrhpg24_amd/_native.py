@@ -68,6 +68,21 @@ class SelectStats(C.Structure):                   # pcr_select_stats
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class Polygon(C.Structure):                       # pcr_polygon: rings of int32 vertices and a z range, 40 bytes (host.Polygon fills one)
+    _fields_ = [("xy", C.POINTER(c_i32)), ("ring_sizes", C.POINTER(c_i32)), ("num_rings", c_i32), ("z_min", c_i32), ("z_max", c_i32),
+                ("flags", c_u32), ("reserved", c_u32)]
+
+
+class PolygonStats(C.Structure):                  # pcr_polygon_stats
+    _fields_ = [(n, c_i64) for n in ("batches_outside", "batches_inside", "batches_straddling", "points_selected", "edges_listed", "edges_max")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+POLY_MAX_VERTICES, POLY_INVERT = 4096, 1                                                                # pcr_types.h
+
+
 class Grid(C.Structure):                          # pcr_grid: a top-down grid over the stream's int32 x and y, 24 bytes
     _fields_ = [(n, c_i32) for n in ("origin_x", "origin_y", "cell", "width", "height", "reserved")]
 
@@ -124,6 +139,7 @@ class EncodeStats(C.Structure):                   # pcr_encode_stats
 
 
 assert C.sizeof(Point) == 16 and C.sizeof(Box) == 24 and C.sizeof(SelectStats) == 32
+assert C.sizeof(Polygon) == 40 and C.sizeof(PolygonStats) == 48
 assert C.sizeof(Rect) == 16 and C.sizeof(ScreenHit) == 16 and C.sizeof(ScreenStats) == 32
 assert C.sizeof(DisplayOpts) == 16
 assert C.sizeof(Grid) == 24 and C.sizeof(GridStats) == 24
@@ -149,6 +165,7 @@ HIP_SYMBOLS = [
     "pcr_las_algorithmic_bytes", "pcr_gpu_encode_points", "pcr_gpu_encode_free",
     "pcr_decode_points", "pcr_read_points",
     "pcr_batch_point_bounds", "pcr_select_box", "pcr_read_box",
+    "pcr_select_polygon", "pcr_read_polygon",
     "pcr_select_screen", "pcr_read_screen", "pcr_pick",
     "pcr_resolve_basic_display", "pcr_resolve_hqs_display", "pcr_resolve_las_display",
     "pcr_grid_clear", "pcr_grid_accumulate", "pcr_grid_unpack", "pcr_read_grid",
@@ -264,6 +281,8 @@ def hip_lib() -> C.CDLL:
         lib.pcr_batch_point_bounds.argtypes = [C.c_void_p, c_i64, c_i64, C.c_void_p]
         for n in ("pcr_select_box", "pcr_read_box"):
             getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Box), C.c_void_p, C.c_size_t, C.POINTER(c_i64), C.POINTER(SelectStats)]
+        for n in ("pcr_select_polygon", "pcr_read_polygon"):
+            getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Polygon), C.c_void_p, C.c_size_t, C.POINTER(c_i64), C.POINTER(PolygonStats)]
         for n in ("pcr_select_screen", "pcr_read_screen"):
             getattr(lib, n).argtypes = [C.c_void_p, C.POINTER(RenderParams), C.POINTER(Rect), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(c_i64),
                                         C.POINTER(ScreenStats)]

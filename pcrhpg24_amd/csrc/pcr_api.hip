@@ -134,6 +134,13 @@ struct pcr_ctx {
     uint32_t *d_sel_counts = nullptr;           // [sel_capacity * 1024] selected points per chain (k_select_count)
     uint32_t *d_sel_totals = nullptr;           // [sel_capacity] ... and per batch
     int64_t *d_sel_offsets = nullptr;           // [sel_capacity] first output record of each (k_select_write)
+    // polygon selection (pcr_select_polygon): the straddling batches of a call with their slices of the edge array, and the array
+    // (the per-chain counts, totals and offsets are the box selection's four arrays above)
+    int64_t poly_capacity = 0;                  // entries d_poly_batches holds
+    PolyBatch *d_poly_batches = nullptr;        // [poly_capacity]
+    int64_t poly_edge_capacity = 0;             // edges d_poly_edges holds
+    PolyEdge *d_poly_edges = nullptr;           // [poly_edge_capacity] the batches' edge lists, back to back
+    bool poly_lds_ready = false;                // hipFuncSetAttribute done for the k_polygon_* launches
     // screen selection and picking (pcr_select_screen / pcr_pick): the cull/LOD words of the call's camera in an array of their own
     // (k_screen_lod; the frame's d_lod, lists and plans are not touched), and the scratch of the kept batches
     uint32_t *d_screen_lod = nullptr;           // [hdr.num_batches]
@@ -259,6 +266,7 @@ void free_stream_buffers(pcr_ctx *c)
     dfree(c->d_order); dfree(c->d_chunk_count); dfree(c->d_any_generic); c->order_stride = 0;
     dfree(c->d_point_bounds); c->h_point_bounds.clear(); c->h_point_bounds_ok.clear();
     dfree(c->d_sel_list); dfree(c->d_sel_counts); dfree(c->d_sel_totals); dfree(c->d_sel_offsets); c->sel_capacity = 0;
+    dfree(c->d_poly_batches); c->poly_capacity = 0; dfree(c->d_poly_edges); c->poly_edge_capacity = 0;
     dfree(c->d_screen_lod); dfree(c->d_scr_list); dfree(c->d_scr_counts); dfree(c->d_scr_totals); dfree(c->d_scr_offsets); c->scr_capacity = 0;
     dfree(c->d_pick);
     dfree(c->d_grid_list); c->grid_capacity = 0; c->h_grid_list.clear();
@@ -1641,6 +1649,19 @@ struct SelectPlan {
 
 bool box_empty(const pcr_box &q) { return q.min[0] > q.max[0] || q.min[1] > q.max[1] || q.min[2] > q.max[2]; }
 
+// Room for the list, counts, totals and offsets of nS straddling batches.
+int select_reserve(pcr_ctx *c, int64_t nS)
+{
+    if (c->sel_capacity >= nS) return PCR_OK;
+    dfree(c->d_sel_list); dfree(c->d_sel_counts); dfree(c->d_sel_totals); dfree(c->d_sel_offsets); c->sel_capacity = 0;
+    if (hipMalloc((void **)&c->d_sel_list, (size_t)nS * 4) != hipSuccess || hipMalloc((void **)&c->d_sel_totals, (size_t)nS * 4) != hipSuccess ||
+        hipMalloc((void **)&c->d_sel_offsets, (size_t)nS * 8) != hipSuccess ||
+        hipMalloc((void **)&c->d_sel_counts, (size_t)nS * PCR_WORKGROUP_SIZE * 4) != hipSuccess)
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the counts of %lld straddling batches", (long long)nS);
+    c->sel_capacity = nS;
+    return PCR_OK;
+}
+
 // Classify (host, from the cached exact boxes) and count the straddling batches (k_select_count). Synchronises.
 int select_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_box &q, SelectPlan &p)
 {
@@ -1663,14 +1684,7 @@ int select_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_box &q, SelectPl
     }
     const int64_t nS = (int64_t)p.strad.size();
     if (nS) {
-        if (c->sel_capacity < nS) {
-            dfree(c->d_sel_list); dfree(c->d_sel_counts); dfree(c->d_sel_totals); dfree(c->d_sel_offsets); c->sel_capacity = 0;
-            if (hipMalloc((void **)&c->d_sel_list, (size_t)nS * 4) != hipSuccess || hipMalloc((void **)&c->d_sel_totals, (size_t)nS * 4) != hipSuccess ||
-                hipMalloc((void **)&c->d_sel_offsets, (size_t)nS * 8) != hipSuccess ||
-                hipMalloc((void **)&c->d_sel_counts, (size_t)nS * PCR_WORKGROUP_SIZE * 4) != hipSuccess)
-                return set_err(c, PCR_E_NOMEM, "out of device memory for the counts of %lld straddling batches", (long long)nS);
-            c->sel_capacity = nS;
-        }
+        if ((rc = select_reserve(c, nS))) return rc;
         HIP_TRY(c, hipMemcpyAsync(c->d_sel_list, p.strad.data(), (size_t)nS * 4, hipMemcpyHostToDevice, c->stream));
         const StreamView s = make_stream_view(c);
         const dim3 grid((unsigned)nS), block(PCR_WORKGROUP_SIZE);
@@ -1687,8 +1701,10 @@ int select_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_box &q, SelectPl
 }
 
 // Enqueue the writes of batches [i0, i1) of the plan's range to `out` (device, holds their records): runs of inside batches
-// through k_decode_points, the straddling ones through one k_select_write launch. The caller synchronises.
-int select_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, const pcr_box &q, SelectPlan &p, uint4 *out)
+// through k_decode_points, the straddling ones through one launch of write(s0, nS, out): the kernel that writes the straddling
+// batches [s0, s0 + nS) of the plan from d_sel_offsets + s0. The caller synchronises.
+extern "C++" template <class Write>
+int select_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, SelectPlan &p, uint4 *out, Write &&write)
 {
     int rc;
     const size_t s0 = (size_t)(std::lower_bound(p.strad.begin(), p.strad.end(), (uint32_t)(first + i0)) - p.strad.begin());
@@ -1709,15 +1725,48 @@ int select_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, const pcr_box
     const size_t nS = p.offsets.size();
     if (nS) {
         HIP_TRY(c, hipMemcpyAsync(c->d_sel_offsets + s0, p.offsets.data(), nS * 8, hipMemcpyHostToDevice, c->stream));
-        const StreamView s = make_stream_view(c);
-        const dim3 grid((unsigned)nS), block(PCR_WORKGROUP_SIZE);
-        const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
+        write(s0, nS, out);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return PCR_OK;
+}
+
+// k_select_write over the straddling batches [s0, s0 + nS) of a box selection's plan
+void box_write(pcr_ctx *c, const pcr_box &q, size_t s0, size_t nS, uint4 *out)
+{
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)nS), block(PCR_WORKGROUP_SIZE);
+    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
 #define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_select_write<L, B>), grid, block, 0, c->stream, s, c->d_sel_list + s0, q, \
                                             c->d_sel_counts + s0 * PCR_WORKGROUP_SIZE, c->d_sel_offsets + s0, out)
-        if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
-        else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
+    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
 #undef PCR_LAUNCH
-        HIP_TRY(c, hipGetLastError());
+}
+
+// The selected records of the plan's n batches into host memory, through the context's decode staging buffer in pieces of at
+// most DECODE_STAGE_BATCHES batches: a batch selects at most 65 536 records, so a piece fits the buffer. Synchronises.
+extern "C++" template <class Write>
+int select_read(pcr_ctx *c, int64_t first, int64_t n, SelectPlan &p, pcr_point *host, Write &&write)
+{
+    int rc;
+    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
+    if (!c->d_decode_stage || c->decode_stage_batches < piece) {
+        dfree(c->d_decode_stage); c->decode_stage_batches = 0;
+        if (hipMalloc((void **)&c->d_decode_stage, (size_t)piece * PCR_POINTS_PER_BATCH * sizeof(pcr_point)) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of points", (long long)piece);
+        c->decode_stage_batches = piece;
+    }
+    int64_t written = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += piece) {
+        const int64_t i1 = std::min(n, i0 + piece);
+        int64_t m = 0;
+        for (int64_t i = i0; i < i1; ++i) m += p.cnt[(size_t)i];
+        if (m == 0) continue;
+        if ((rc = select_emit(c, first, i0, i1, p, reinterpret_cast<uint4 *>(c->d_decode_stage), write))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(host + written, c->d_decode_stage, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        written += m;
     }
     return PCR_OK;
 }
@@ -1755,7 +1804,8 @@ int pcr_select_box(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_box
     bool done = true;
     int rc = select_prepare(c, first_batch, count, box, dev_points, 16, capacity_points, out_count, stats, &n, p, &done);
     if (rc || done) return rc;
-    if ((rc = select_emit(c, first_batch, 0, n, *box, p, static_cast<uint4 *>(dev_points)))) return rc;
+    if ((rc = select_emit(c, first_batch, 0, n, p, static_cast<uint4 *>(dev_points),
+                          [&](size_t s0, size_t nS, uint4 *out) { box_write(c, *box, s0, nS, out); }))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return PCR_OK;
 }
@@ -1770,26 +1820,154 @@ int pcr_read_box(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_box *
     bool done = true;
     int rc = select_prepare(c, first_batch, count, box, host, alignof(pcr_point), capacity_points, out_count, stats, &n, p, &done);
     if (rc || done) return rc;
-    // pieces of at most DECODE_STAGE_BATCHES batches: a batch selects at most 65 536 records, so a piece fits the staging buffer
-    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
-    if (!c->d_decode_stage || c->decode_stage_batches < piece) {
-        dfree(c->d_decode_stage); c->decode_stage_batches = 0;
-        if (hipMalloc((void **)&c->d_decode_stage, (size_t)piece * PCR_POINTS_PER_BATCH * sizeof(pcr_point)) != hipSuccess)
-            return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of points", (long long)piece);
-        c->decode_stage_batches = piece;
+    return select_read(c, first_batch, n, p, host, [&](size_t s0, size_t nS, uint4 *out) { box_write(c, *box, s0, nS, out); });
+}
+
+// ---- polygon selection -------------------------------------------------------------------------
+namespace {
+constexpr size_t POLY_MAX_LDS_BYTES = POLY_TABLE_BYTES + (size_t)PCR_POLY_MAX_VERTICES * sizeof(PolyEdge);
+
+// What a polygon selection adds to a SelectPlan: the checked polygon, the straddling batches with their slices, the edge array.
+struct PolygonPlan {
+    SelectPlan sel;
+    PolyShape shape;
+    std::vector<PolyBatch> batches;     // the straddling batches, ascending (alive until the stream has been synchronised)
+    std::vector<PolyEdge> edges;
+    PolyArgs args{};
+    size_t lds = 0;                     // dynamic LDS of the k_polygon_* launches
+    pcr_polygon_stats st{};
+};
+
+// Classify (host, pcr_polygon.h), upload the straddling batches' edge lists and count them (k_polygon_count). Synchronises.
+int polygon_plan(pcr_ctx *c, int64_t first, int64_t n, PolygonPlan &p)
+{
+    p.sel.cls.assign((size_t)n, SEL_OUTSIDE); p.sel.cnt.assign((size_t)n, 0); p.sel.strad.clear();
+    p.batches.clear(); p.edges.clear();
+    p.st = pcr_polygon_stats{n, 0, 0, 0, 0, 0};
+    if (n == 0 || p.shape.z_min > p.shape.z_max) return PCR_OK;
+    int rc;
+    if ((rc = ensure_point_bounds(c, first, n))) return rc;
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t e0 = p.edges.size();
+        uint32_t base = 0;
+        const int cls = poly_plan_batch(p.shape, c->h_point_bounds.data() + (first + i) * 6, p.edges, &base);
+        if (cls == POLY_OUTSIDE) continue;
+        --p.st.batches_outside;
+        if (cls == POLY_INSIDE) { p.sel.cls[(size_t)i] = SEL_INSIDE; p.sel.cnt[(size_t)i] = PCR_POINTS_PER_BATCH; ++p.st.batches_inside; continue; }
+        const size_t ne = p.edges.size() - e0;
+        p.sel.cls[(size_t)i] = SEL_STRADDLING; p.sel.strad.push_back((uint32_t)(first + i)); ++p.st.batches_straddling;
+        p.batches.push_back(PolyBatch{(uint32_t)(first + i), (uint32_t)e0, (uint32_t)ne, base});
+        p.st.edges_listed += (int64_t)ne;
+        p.st.edges_max = std::max(p.st.edges_max, (int64_t)ne);
     }
-    int64_t written = 0;
-    for (int64_t i0 = 0; i0 < n; i0 += piece) {
-        const int64_t i1 = std::min(n, i0 + piece);
-        int64_t m = 0;
-        for (int64_t i = i0; i < i1; ++i) m += p.cnt[(size_t)i];
-        if (m == 0) continue;
-        if ((rc = select_emit(c, first_batch, i0, i1, *box, p, reinterpret_cast<uint4 *>(c->d_decode_stage)))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(host + written, c->d_decode_stage, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
+    const int64_t nS = (int64_t)p.batches.size(), nE = (int64_t)p.edges.size();
+    if (nS) {
+        if ((rc = select_reserve(c, nS))) return rc;
+        if (c->poly_capacity < nS) {
+            dfree(c->d_poly_batches); c->poly_capacity = 0;
+            if (hipMalloc((void **)&c->d_poly_batches, (size_t)nS * sizeof(PolyBatch)) != hipSuccess)
+                return set_err(c, PCR_E_NOMEM, "out of device memory for a list of %lld straddling batches", (long long)nS);
+            c->poly_capacity = nS;
+        }
+        if (c->poly_edge_capacity < nE) {
+            dfree(c->d_poly_edges); c->poly_edge_capacity = 0;
+            if (hipMalloc((void **)&c->d_poly_edges, (size_t)nE * sizeof(PolyEdge)) != hipSuccess)
+                return set_err(c, PCR_E_NOMEM, "out of device memory for %lld polygon edges", (long long)nE);
+            c->poly_edge_capacity = nE;
+        }
+        if (!c->poly_lds_ready) {
+            hipError_t e = hipSuccess;
+#define PCR_ALLOW(K) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)POLY_MAX_LDS_BYTES)
+            PCR_ALLOW(k_polygon_count<LAYOUT_WORDS>); PCR_ALLOW(k_polygon_count<LAYOUT_POINT_WINDOWS>);
+            PCR_ALLOW((k_polygon_write<LAYOUT_WORDS, false>)); PCR_ALLOW((k_polygon_write<LAYOUT_WORDS, true>));
+            PCR_ALLOW((k_polygon_write<LAYOUT_POINT_WINDOWS, false>)); PCR_ALLOW((k_polygon_write<LAYOUT_POINT_WINDOWS, true>));
+#undef PCR_ALLOW
+            if (e != hipSuccess) return set_err(c, PCR_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
+            c->poly_lds_ready = true;
+        }
+        HIP_TRY(c, hipMemcpyAsync(c->d_poly_batches, p.batches.data(), (size_t)nS * sizeof(PolyBatch), hipMemcpyHostToDevice, c->stream));
+        if (nE) HIP_TRY(c, hipMemcpyAsync(c->d_poly_edges, p.edges.data(), (size_t)nE * sizeof(PolyEdge), hipMemcpyHostToDevice, c->stream));
+        p.args = PolyArgs{p.shape.x0, p.shape.y0, p.shape.x1, p.shape.y1, p.shape.z_min, p.shape.z_max, p.shape.invert ? 1u : 0u,
+                          (uint32_t)p.st.edges_max, c->d_poly_batches, c->d_poly_edges};
+        p.lds = POLY_TABLE_BYTES + (size_t)p.st.edges_max * sizeof(PolyEdge);
+        const StreamView s = make_stream_view(c);
+        const dim3 grid((unsigned)nS), block(PCR_WORKGROUP_SIZE);
+        if (select_reads_windows(c)) hipLaunchKernelGGL((k_polygon_count<LAYOUT_POINT_WINDOWS>), grid, block, p.lds, c->stream, s, p.args, c->d_sel_counts, c->d_sel_totals);
+        else                         hipLaunchKernelGGL((k_polygon_count<LAYOUT_WORDS>), grid, block, p.lds, c->stream, s, p.args, c->d_sel_counts, c->d_sel_totals);
+        HIP_TRY(c, hipGetLastError());
+        std::vector<uint32_t> totals((size_t)nS);
+        HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_sel_totals, (size_t)nS * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        written += m;
+        for (int64_t k = 0; k < nS; ++k) p.sel.cnt[(size_t)(p.batches[(size_t)k].b - first)] = totals[(size_t)k];
     }
+    for (int64_t i = 0; i < n; ++i) p.st.points_selected += p.sel.cnt[(size_t)i];
     return PCR_OK;
+}
+
+// k_polygon_write over the straddling batches [s0, s0 + nS) of the plan
+void polygon_write(pcr_ctx *c, const PolygonPlan &p, size_t s0, size_t nS, uint4 *out)
+{
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)nS), block(PCR_WORKGROUP_SIZE);
+    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
+    PolyArgs a = p.args;
+    a.batches += s0;
+#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_polygon_write<L, B>), grid, block, p.lds, c->stream, s, a, c->d_sel_counts + s0 * PCR_WORKGROUP_SIZE, \
+                                            c->d_sel_offsets + s0, out)
+    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
+    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+#undef PCR_LAUNCH
+}
+
+// The checks and the plan shared by pcr_select_polygon / pcr_read_polygon (select_prepare with the polygon's checks).
+int polygon_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_polygon *poly, const void *dst, size_t dst_align, size_t capacity,
+                    int64_t *out_count, pcr_polygon_stats *stats, int64_t *n, PolygonPlan &p, bool *done)
+{
+    *done = true;
+    if (out_count) *out_count = 0;
+    int rc = select_range(c, first, count, n);
+    if (rc) return rc;
+    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
+    if (const char *why = poly_shape(poly, &p.shape)) return set_err(c, PCR_E_ARG, "%s", why);
+    if (dst && reinterpret_cast<uintptr_t>(dst) % dst_align != 0) return set_err(c, PCR_E_ARG, "the destination is misaligned (%zu bytes)", dst_align);
+    if ((rc = polygon_plan(c, first, *n, p))) return rc;
+    *out_count = p.st.points_selected;
+    if (stats) *stats = p.st;
+    if (!dst || p.st.points_selected == 0) return PCR_OK;
+    if (capacity < (size_t)p.st.points_selected)
+        return set_err(c, PCR_E_ARG, "capacity of %zu points is below the %lld selected", capacity, (long long)p.st.points_selected);
+    *done = false;
+    return PCR_OK;
+}
+} // namespace
+
+int pcr_select_polygon(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_polygon *poly, void *dev_points, size_t capacity_points,
+                       int64_t *out_count, pcr_polygon_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    PolygonPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = polygon_prepare(c, first_batch, count, poly, dev_points, 16, capacity_points, out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    if ((rc = select_emit(c, first_batch, 0, n, p.sel, static_cast<uint4 *>(dev_points),
+                          [&](size_t s0, size_t nS, uint4 *out) { polygon_write(c, p, s0, nS, out); }))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+int pcr_read_polygon(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_polygon *poly, pcr_point *host, size_t capacity_points,
+                     int64_t *out_count, pcr_polygon_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    PolygonPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = polygon_prepare(c, first_batch, count, poly, host, alignof(pcr_point), capacity_points, out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    return select_read(c, first_batch, n, p.sel, host, [&](size_t s0, size_t nS, uint4 *out) { polygon_write(c, p, s0, nS, out); });
 }
 
 // ---- top-down grid -----------------------------------------------------------------------------

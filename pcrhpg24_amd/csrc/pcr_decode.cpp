@@ -2,6 +2,7 @@
 // decoder outside the render kernels is the per-chain CPU one of include/huffman.h:433-477.
 //     pcr_decode <in.huffman> <out.las> [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --thin CELL [--center] [--box x0 y0 z0 x1 y1 z1]
+//     pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]
 //     pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1] [--rect x0 y0 x1 y1]
 //     pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]
 // Loads the file with the loader of the render tools (HuffmanLasData, csrc/pcr_methods.hpp), reads the points back in pieces of
@@ -10,13 +11,16 @@
 // camera draws (pcr_render's camera arguments and defaults), and of those the ones inside --rect, a rectangle of pixels
 // (pcr_read_screen). With --ortho no points are read back at all: the stream is rasterized top-down on the GPU (pcr_read_grid) into
 // an orthophoto and, with --dsm, a surface model. With --thin one point per cubic voxel is read back (pcr_read_thin): the cloud
-// decimated on the GPU without ever existing in full.
+// decimated on the GPU without ever existing in full. With --polygon only the points inside a polygon prism of world coordinates are
+// read back (pcr_read_polygon).
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstdint>
 #include <cstring>
+#include <fstream>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -27,6 +31,7 @@ using namespace pcr_host;
 static const char *USAGE =
     "usage: pcr_decode <in.huffman> <out.las> [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --thin CELL [--center] [--box x0 y0 z0 x1 y1 z1]\n"
+    "       pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]\n"
     "       pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1]\n"
     "                                                [--rect x0 y0 x1 y1]\n"
     "       pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]\n"
@@ -42,6 +47,12 @@ static const char *USAGE =
     "  the lattice starts at the min corner of the header's box), thinned on the GPU, in the stream's order: the voxel's first\n"
     "  point in that order, with --center the one nearest to the voxel's centre. Only the points inside --box count, or inside\n"
     "  the box of the file's header. No point there is an error.\n"
+    "  --polygon FILE: only the points inside a polygon, selected on the GPU, in the stream's order. FILE is text in world\n"
+    "  coordinates: one vertex `x y` per line, a blank line starts the next ring (a ring inside another is a hole: the even-odd\n"
+    "  rule); a ring has at least 3 vertices and is closed implicitly, all rings together at most 4096. A vertex goes to the\n"
+    "  nearest lattice step of the stream. The boundary is half-open: of two polygons that share an edge exactly one takes a\n"
+    "  point on it. --z: of those the points with LO <= p.z <= HI; --outside: the points NOT inside the polygon (--z still\n"
+    "  applies). A polygon that holds no point is an error.\n"
     "  --view: only the points a frame of that camera draws (the basic method's cull and level of detail; the options and their\n"
     "  defaults are pcr_render's), in the stream's order; --rect: of those the ones whose pixel lies in the rectangle (pixels,\n"
     "  bounds inclusive, x0 <= x1 and y0 <= y1). A view that shows no point is an error.\n"
@@ -147,6 +158,58 @@ static bool parse_thin(int argc, char **argv, int at, Thin &t)
     return true;
 }
 
+struct Poly {
+    std::vector<double> xy;             // world coordinates, ring after ring
+    std::vector<int32_t> ring_sizes;
+    bool has_z = false, outside = false;
+    double z[2] = {0.0, 0.0};
+};
+
+// the options behind --polygon, every one well formed and the file read, or false with the reason on stderr
+static bool parse_polygon(int argc, char **argv, int at, Poly &p)
+{
+    if (argc < at + 2 || std::strcmp(argv[at], "--polygon") != 0) return false;
+    for (int i = at + 2; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--z" && i + 2 < argc && !p.has_z) {
+            for (int k = 0; k < 2; ++k) if (!parse_double(argv[++i], p.z[k])) return false;
+            p.has_z = true;
+        } else if (a == "--outside" && !p.outside) {
+            p.outside = true;
+        } else {
+            return false;
+        }
+    }
+    const char *path = argv[at + 1];
+    std::ifstream f(path);
+    if (!f) { std::fprintf(stderr, "pcr_decode: %s: cannot open the polygon file\n", path); return false; }
+    std::string line;
+    int32_t ring = 0;
+    auto close_ring = [&]() {
+        if (ring == 0) return true;
+        if (ring < 3) { std::fprintf(stderr, "pcr_decode: %s: a ring of %d vertices (at least 3)\n", path, ring); return false; }
+        p.ring_sizes.push_back(ring);
+        ring = 0;
+        return true;
+    };
+    for (int no = 1; std::getline(f, line); ++no) {
+        if (line.find_first_not_of(" \t\r") == std::string::npos) { if (!close_ring()) return false; continue; }
+        std::istringstream in(line);
+        std::string sx, sy, more;
+        double x = 0.0, y = 0.0;
+        if (!(in >> sx >> sy) || (in >> more) || !parse_double(sx.c_str(), x) || !parse_double(sy.c_str(), y)) {
+            std::fprintf(stderr, "pcr_decode: %s: line %d is not `x y`\n", path, no);
+            return false;
+        }
+        p.xy.push_back(x); p.xy.push_back(y);
+        ++ring;
+    }
+    if (!close_ring()) return false;
+    if (p.ring_sizes.empty()) { std::fprintf(stderr, "pcr_decode: %s: no ring\n", path); return false; }
+    if (p.xy.size() / 2 > PCR_POLY_MAX_VERTICES) { std::fprintf(stderr, "pcr_decode: %s: more than %d vertices\n", path, PCR_POLY_MAX_VERTICES); return false; }
+    return true;
+}
+
 struct Ortho {
     double cell = 0.0;
     bool has_box = false;
@@ -233,8 +296,10 @@ int main(int argc, char **argv)
     const bool viewed = argc > 3 && std::strcmp(argv[3], "--view") == 0, orthoed = argc > 3 && std::strcmp(argv[3], "--ortho") == 0;
     Thin thin;
     const bool thinned = argc > 3 && std::strcmp(argv[3], "--thin") == 0;
-    const bool boxed = argc > 3 && !viewed && !orthoed && !thinned;
-    if (argc < 3 || (boxed && !parse_box(argc, argv, 3, lo, hi)) || (viewed && !parse_view(argc, argv, 3, view)) ||
+    Poly poly;
+    const bool polygoned = argc > 3 && std::strcmp(argv[3], "--polygon") == 0;
+    const bool boxed = argc > 3 && !viewed && !orthoed && !thinned && !polygoned;
+    if (argc < 3 || (polygoned && !parse_polygon(argc, argv, 3, poly)) || (boxed && !parse_box(argc, argv, 3, lo, hi)) || (viewed && !parse_view(argc, argv, 3, view)) ||
         (orthoed && !parse_ortho(argc, argv, 3, ortho)) || (thinned && !parse_thin(argc, argv, 3, thin))) { std::fputs(USAGE, stderr); return 2; }
     const std::string in = argv[1], out = argv[2];
     try {
@@ -262,6 +327,13 @@ int main(int argc, char **argv)
             std::printf("box: batches outside %lld, inside %lld, straddling %lld\n", (long long)st.batches_outside, (long long)st.batches_inside,
                         (long long)st.batches_straddling);
             if (points.empty()) throw std::runtime_error("no points inside the box: nothing written");
+        } else if (polygoned) {
+            PolygonOwner owner;
+            polygonFromWorld(info, poly.xy, poly.ring_sizes, poly.has_z ? &poly.z[0] : nullptr, poly.has_z ? &poly.z[1] : nullptr, poly.outside, owner);
+            const pcr_polygon_stats st = las->pointsInPolygon(owner.poly, points);
+            std::printf("polygon: batches outside %lld, inside %lld, straddling %lld, edges listed %lld, largest list %lld\n", (long long)st.batches_outside,
+                        (long long)st.batches_inside, (long long)st.batches_straddling, (long long)st.edges_listed, (long long)st.edges_max);
+            if (points.empty()) throw std::runtime_error("no points inside the polygon: nothing written");
         } else if (thinned) {
             const pcr_voxels vox = voxelsFromWorld(info, thin.cell, info.min);
             const pcr_box clip = boxFromWorld(info, thin.has_box ? thin.lo : info.min, thin.has_box ? thin.hi : info.max);

@@ -17,6 +17,7 @@
 //   k_decode_points on request: the same decode, every point of a range of batches written out as {x, y, z, colour} records
 //   k_screen_* / k_pick*  on request: the points a frame draws, selected by pixel (projection restated in screen_project)
 //   k_grid*         on request: the stream rasterized top-down into max / min / count planes over its integer x and y
+//   k_polygon_*     on request: the records inside a polygon prism, each straddling batch against its own edge list in LDS
 //   k_thin_*        on request: one record per voxel of a cubic lattice, straight from the compressed stream
 //   k_las_*         the 10-10-10 method (modules/compute_loop_las_cuda)
 //   k_resolve_*     framebuffer -> RGBA8 (resolve.cu:149-191, huffman_hqs/resolve.cu:2-47)
@@ -27,6 +28,7 @@
 #include <type_traits>
 #include "pcr_types.h"
 #include "pcr_lattice.h"
+#include "pcr_polygon.h"
 
 namespace pcr {
 
@@ -2225,6 +2227,112 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_select_write(StreamView 
     uint4 *const end = dst + mine;                          // never past what k_select_count counted for this chain
     decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t colour) {
         if (in_box(q, x, y, z) && dst < end) *dst++ = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Polygon selection (pcr_select_polygon): k_select_count / k_select_write with a polygon prism as the test, for the batches
+// whose exact box the prism's boundary crosses. The host (pcr_polygon.h) gives every such batch a slice of one edge array --
+// only the edges a point of the batch's box can count -- and a base parity for the edges all its points count. The workgroup
+// copies its slice into LDS beside the table (16 bytes an edge, launch-sized to the largest slice listed, at most 64 KiB).
+// Per point: the z range and the bounding rectangle of the polygon's vertices first (outside it a point is not in the polygon;
+// inside it every difference below fits 32 bits and every product stays below 2^62), then a loop over the slice in which all
+// lanes read the same entry (one ds_read_b128 that broadcasts), an unsigned compare y - l.y < dy that covers both ends of the
+// half-open row range, two 32 x 32 -> 64 multiplies and a signed compare, XORed into the parity.
+// ------------------------------------------------------------------------------------------------
+struct PolyBatch { uint32_t b, edge_first, edge_count, base_parity; };      // a straddling batch and its slice of the edge array
+struct PolyArgs {
+    int32_t x0, y0, x1, y1;         // the bounding rectangle of all vertices
+    int32_t z_min, z_max;
+    uint32_t invert;                // 0 or 1
+    uint32_t lds_edges;             // edges the launch's dynamic LDS holds behind the table: the largest slice listed
+    const PolyBatch *batches;
+    const PolyEdge *edges;
+};
+constexpr uint32_t POLY_TABLE_BYTES = PCR_HUFFMAN_TABLE_SIZE * 4;
+
+// The batch's table and edge slice into LDS; returns false (uniformly) for a slice the launch has no room for, which the host
+// never lists. The barrier publishes both.
+__device__ __forceinline__ bool load_polygon_batch(const StreamView &s, const PolyArgs &a, const PolyBatch &pb, uint32_t *s_table, int4 *s_edges)
+{
+    if (pb.edge_count > a.lds_edges) return false;
+    const int4 *src = reinterpret_cast<const int4 *>(a.edges) + pb.edge_first;
+    for (uint32_t i = threadIdx.x; i < pb.edge_count; i += PCR_WORKGROUP_SIZE) s_edges[i] = src[i];
+    load_packed_table(s, pb.b, s_table);
+    return true;
+}
+
+__device__ __forceinline__ bool in_polygon(const PolyArgs &a, const int4 *s_edges, uint32_t edge_count, uint32_t base_parity, int32_t x, int32_t y, int32_t z)
+{
+    if (z < a.z_min || z > a.z_max) return false;
+    uint32_t parity = 0;
+    if (x >= a.x0 && x <= a.x1 && y >= a.y0 && y <= a.y1) {
+        parity = base_parity;
+        for (uint32_t k = 0; k < edge_count; ++k) {
+            const int4 e = s_edges[k];                                      // l.x, l.y, dx, dy
+            const uint32_t t = (uint32_t)y - (uint32_t)e.y;                 // y - l.y: below dy iff l.y <= y < u.y
+            const int64_t lhs = (int64_t)(int32_t)((uint32_t)x - (uint32_t)e.x) * (int64_t)e.w;
+            const int64_t rhs = (int64_t)(int32_t)t * (int64_t)e.z;
+            parity ^= (t < (uint32_t)e.w && lhs < rhs) ? 1u : 0u;
+        }
+    }
+    return parity != a.invert;
+}
+
+// Workgroup x takes the straddling batch a.batches[x]: chain_counts[x * 1024 + chain] = its points selected, totals[x] = their sum
+template <int LAYOUT>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_polygon_count(StreamView s, PolyArgs a, uint32_t *chain_counts, uint32_t *totals)
+{
+    const PolyBatch pb = a.batches[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    extern __shared__ __align__(16) unsigned char s_dyn[];                  // the table, then a.lds_edges edges
+    __shared__ uint32_t s_part[LWC_WAVES];
+    uint32_t *s_table = reinterpret_cast<uint32_t *>(s_dyn);
+    int4 *s_edges = reinterpret_cast<int4 *>(s_dyn + POLY_TABLE_BYTES);
+    if (!load_polygon_batch(s, a, pb, s_table, s_edges)) return;
+    uint32_t cnt = 0;
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, pb.b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t) {
+        cnt += in_polygon(a, s_edges, pb.edge_count, pb.base_parity, x, y, z) ? 1u : 0u;
+    });
+    chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid] = cnt;
+    uint32_t sum = cnt;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    if (lane == 0) s_part[wave] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < LWC_WAVES; ++w) t += s_part[w];
+        totals[blockIdx.x] = t;
+    }
+}
+
+// Workgroup x takes the straddling batch a.batches[x]: its selected records go to out[offsets[x] ..] as k_select_write's do.
+// chain_counts is k_polygon_count's, for the same batches, edges and arguments.
+template <int LAYOUT, bool BC7>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_polygon_write(StreamView s, PolyArgs a, const uint32_t *chain_counts, const int64_t *offsets, uint4 *out)
+{
+    const PolyBatch pb = a.batches[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    extern __shared__ __align__(16) unsigned char s_dyn[];                  // the table, then a.lds_edges edges
+    __shared__ uint32_t s_part[LWC_WAVES];
+    uint32_t *s_table = reinterpret_cast<uint32_t *>(s_dyn);
+    int4 *s_edges = reinterpret_cast<int4 *>(s_dyn + POLY_TABLE_BYTES);
+    const uint32_t mine = chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid];
+    uint32_t incl = mine;                                   // inclusive prefix inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += up;
+    }
+    if (lane == 63) s_part[wave] = incl;
+    if (!load_polygon_batch(s, a, pb, s_table, s_edges)) return;            // (its barrier publishes s_part as well)
+    uint32_t before = incl - mine;
+    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    uint4 *dst = out + offsets[blockIdx.x] + before;
+    uint4 *const end = dst + mine;                          // never past what k_polygon_count counted for this chain
+    decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, pb.b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        if (in_polygon(a, s_edges, pb.edge_count, pb.base_parity, x, y, z) && dst < end) *dst++ = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
     });
 }
 

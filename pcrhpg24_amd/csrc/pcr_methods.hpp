@@ -329,6 +329,21 @@ struct HuffmanLasData : Resource {
         return st;
     }
 
+    // The points inside the polygon prism `poly` (the stream's int32 coordinates; pcr_types.h has the rule) of every batch the context
+    // holds right now: decodePoints() with the unselected records removed, selected on the GPU (pcr_read_polygon: batches the prism
+    // misses are not decoded, the ones its boundary crosses test their points against their own few edges). Not in the reference.
+    pcr_polygon_stats pointsInPolygon(const pcr_polygon &poly, std::vector<pcr_point> &out)
+    {
+        if (!loadedOn) throw std::runtime_error("pointsInPolygon: the resource is not loaded");
+        const int64_t nB = pcr_batches_resident(loadedOn->ctx);
+        int64_t n = 0;
+        pcr_polygon_stats st{};
+        loadedOn->check(pcr_read_polygon(loadedOn->ctx, 0, nB, &poly, nullptr, 0, &n, &st), "pcr_read_polygon");
+        out.resize((size_t)n);
+        if (n) loadedOn->check(pcr_read_polygon(loadedOn->ctx, 0, nB, &poly, out.data(), out.size(), &n, &st), "pcr_read_polygon");
+        return st;
+    }
+
     // One point per voxel of `vox` among the points inside `clip` (NULL: everywhere), thinned on the GPU straight from the compressed
     // stream (pcr_read_thin: a counting call, then the read). Not in the reference.
     pcr_thin_stats thin(const pcr_voxels &vox, const pcr_box *clip, int mode, std::vector<pcr_point> &out)
@@ -476,6 +491,37 @@ inline pcr_box boxFromWorld(const pcr_las_info &las, const double lo[3], const d
         b.min[k] = (int32_t)a; b.max[k] = (int32_t)z;
     }
     return b;
+}
+
+// A pcr_polygon with the arrays it points to.
+struct PolygonOwner {
+    std::vector<int32_t> xy, ring_sizes;
+    pcr_polygon poly{};
+    PolygonOwner() = default;
+    PolygonOwner(const PolygonOwner &) = delete;
+    PolygonOwner &operator=(const PolygonOwner &) = delete;
+};
+
+// The polygon prism of rings given in world coordinates (xy: x0, y0, x1, y1, ... ring after ring): a vertex goes to the nearest
+// lattice step, nearbyint((v - offset) / scale) in double (round to nearest even, the default mode), which moves it by at most half
+// a step; z_lo / z_hi (NULL: unbounded) follow boxFromWorld's rule. A vertex beyond int32 is refused. The Python twin is
+// host.polygon_from_world.
+inline void polygonFromWorld(const pcr_las_info &las, const std::vector<double> &xy, const std::vector<int32_t> &ring_sizes, const double *z_lo,
+                             const double *z_hi, bool invert, PolygonOwner &out)
+{
+    out.xy.resize(xy.size());
+    for (size_t i = 0; i < xy.size(); ++i) {
+        const double s = las.scale[i & 1], o = las.offset[i & 1];
+        if (!(s > 0.0)) throw std::runtime_error("polygonFromWorld: needs a positive scale");
+        const double v = std::nearbyint((xy[i] - o) / s);
+        if (!(v >= (double)INT32_MIN && v <= (double)INT32_MAX)) throw std::runtime_error("polygonFromWorld: a vertex lies beyond the int32 lattice of the stream");
+        out.xy[i] = (int32_t)v;
+    }
+    out.ring_sizes = ring_sizes;
+    const double inf = std::numeric_limits<double>::infinity();
+    const double l3[3] = {-inf, -inf, z_lo ? *z_lo : -inf}, h3[3] = {inf, inf, z_hi ? *z_hi : inf};
+    const pcr_box b = boxFromWorld(las, l3, h3);
+    out.poly = pcr_polygon{out.xy.data(), out.ring_sizes.data(), (int32_t)out.ring_sizes.size(), b.min[2], b.max[2], invert ? PCR_POLY_INVERT : 0u, 0u};
 }
 
 // The grid of square cells of `cell_size` world units over lo <= x, y <= hi: the origin is the first lattice point at or above lo on

@@ -249,6 +249,81 @@ def box_from_world(las: LasInfo, lo, hi) -> Box:
     return b
 
 
+class Polygon:
+    """A polygon prism in the stream's int32 coordinates (pcr_polygon): `rings` is a sequence of rings, each a sequence of at
+    least 3 (x, y) vertices (a single ring may be given alone, as an [m, 2] array); the first ring and every further one
+    combine by the even-odd rule, so a ring inside another is a hole. A ring is closed implicitly. z_min..z_max is
+    inclusive; invert=True keeps the points NOT inside the polygon (the z range still applies). The boundary is half-open
+    (include/pcr_types.h): of two polygons that share an edge exactly one takes a point on it. ValueError for a ring of
+    fewer than 3 vertices, a coordinate that is not a whole number (nothing is rounded here: polygon_from_world does that) or
+    one beyond int32; the limits on the vertex count and the extent are the call's."""
+
+    @staticmethod
+    def _ring(r) -> np.ndarray:
+        try:
+            a = np.asarray(r)
+            if a.dtype.kind not in "iu":                    # floats, Python integers beyond int64 (object)
+                if a.dtype.kind not in "fO" or not all(float(v) == int(v) for v in a.ravel()):
+                    raise ValueError
+                a = np.array([int(v) for v in a.ravel()], dtype=object).reshape(a.shape)
+            if a.size and (a.min() < INT32_MIN or a.max() > INT32_MAX):
+                raise ValueError
+            return a.astype(np.int64)
+        except (ValueError, TypeError, OverflowError):
+            raise ValueError("polygon vertices are whole numbers within int32, (x, y) per vertex") from None
+
+    def __init__(self, rings, z_min: int = INT32_MIN, z_max: int = INT32_MAX, invert: bool = False):
+        try:
+            single = np.asarray(rings)
+        except ValueError:                                  # rings of different lengths
+            single = None
+        if single is not None and single.ndim == 2 and single.dtype.kind != "O":
+            rings = [single]
+        self.rings = [self._ring(r) for r in rings]
+        if not self.rings or any(r.ndim != 2 or r.shape[1] != 2 or len(r) < 3 for r in self.rings):
+            raise ValueError("a polygon is one or more rings of at least 3 (x, y) vertices")
+        zs = (int(z_min), int(z_max))
+        if zs != (z_min, z_max) or any(v < INT32_MIN or v > INT32_MAX for v in zs):
+            raise ValueError("z_min and z_max are whole numbers within int32")
+        self.z_min, self.z_max, self.invert = zs[0], zs[1], bool(invert)
+        self._xy = np.ascontiguousarray(np.concatenate(self.rings), dtype=np.int32)
+        self._sizes = np.array([len(r) for r in self.rings], np.int32)
+        self.c = N.Polygon(self._xy.ctypes.data_as(C.POINTER(N.c_i32)), self._sizes.ctypes.data_as(C.POINTER(N.c_i32)), len(self.rings),
+                           self.z_min, self.z_max, N.POLY_INVERT if invert else 0, 0)
+
+    def inverted(self) -> "Polygon":
+        return Polygon(self.rings, self.z_min, self.z_max, not self.invert)
+
+
+def polygon_from_world(las: LasInfo, rings, z_lo=None, z_hi=None, invert: bool = False) -> Polygon:
+    """The Polygon of rings given in world coordinates. A vertex goes to the nearest lattice step, rint((v - offset) / scale) in
+    float64, which moves it by at most half a step (and a few units in the last place of the division): unlike a box, a
+    polygon has no largest integer counterpart, since its edges pass between lattice points whichever vertices are chosen.
+    z_lo / z_hi (None: unbounded) follow box_from_world's rule: the largest integer range whose points satisfy
+    z_lo <= z * scale + offset <= z_hi in float64. ValueError for a vertex that is not a number or lands beyond int32."""
+    try:
+        single = np.asarray(rings, dtype=np.float64)
+    except ValueError:
+        single = None
+    if single is not None and single.ndim == 2:
+        rings = [single]
+    s, o = np.array(tuple(las.scale)[:2]), np.array(tuple(las.offset)[:2])
+    if not (s > 0.0).all():
+        raise ValueError("polygon_from_world needs a positive scale")
+    out = []
+    for r in rings:
+        r = np.asarray(r, dtype=np.float64)
+        if r.ndim != 2 or r.shape[1] != 2 or len(r) < 3:
+            raise ValueError("a polygon is one or more rings of at least 3 (x, y) vertices")
+        v = np.rint((r - o) / s)
+        if not np.isfinite(v).all() or (v < INT32_MIN).any() or (v > INT32_MAX).any():
+            raise ValueError("a polygon vertex lies beyond the int32 lattice of the stream")
+        out.append(v.astype(np.int64))
+    inf = float("inf")
+    zb = box_from_world(las, (-inf, -inf, -inf if z_lo is None else z_lo), (inf, inf, inf if z_hi is None else z_hi))
+    return Polygon(out, zb.min[2], zb.max[2], invert)
+
+
 def as_grid(grid) -> Grid:
     """A pcr_grid from a Grid or five numbers origin_x, origin_y, cell, width, height (the stream's int32 coordinates, cells)."""
     if isinstance(grid, Grid):
@@ -675,6 +750,39 @@ class Context:
         if cnt.value:
             self._chk(self.lib.pcr_read_box(self.h, first, nb, C.byref(box), out.ctypes.data, len(out), C.byref(cnt), C.byref(st)), "pcr_read_box")
         self.select_stats = st.as_dict()
+        return out
+
+    # -- polygon selection (pcr_select_polygon / pcr_read_polygon) ------------------------------------------
+    def select_polygon(self, poly: Polygon, first: int = 0, count: Optional[int] = None, out=None):
+        """The points of batches [first, first + count) inside the prism `poly` (a Polygon) as a torch.int32 tensor [n, 4] on the
+        context's device: select_box with the polygon's predicate, `out` and the stream ordering as there. The batch classes,
+        the count and the edge-list sizes of the last call are in self.polygon_stats."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        cnt, st, nb = c_i64(), N.PolygonStats(), -1 if count is None else count
+        if out is None:
+            self._chk(self.lib.pcr_select_polygon(self.h, first, nb, C.byref(poly.c), None, 0, C.byref(cnt), C.byref(st)), "pcr_select_polygon")
+            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
+        torch.cuda.current_stream(dev).synchronize()
+        rc = self.lib.pcr_select_polygon(self.h, first, nb, C.byref(poly.c), C.c_void_p(out.data_ptr() if out.numel() else None), out.numel() // 4,
+                                         C.byref(cnt), C.byref(st))
+        self.polygon_stats = st.as_dict()
+        if rc:
+            self.polygon_stats["points_selected"] = cnt.value
+        self._chk(rc, "pcr_select_polygon")
+        return out.view(-1, 4)[:cnt.value]
+
+    def read_polygon(self, poly: Polygon, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The same on the host, without torch: a numpy structured array of POINT_DTYPE (pcr_read_polygon: a counting call, then
+        the read; synchronises)."""
+        cnt, st, nb = c_i64(), N.PolygonStats(), -1 if count is None else count
+        self._chk(self.lib.pcr_read_polygon(self.h, first, nb, C.byref(poly.c), None, 0, C.byref(cnt), C.byref(st)), "pcr_read_polygon")
+        out = np.empty(cnt.value, POINT_DTYPE)
+        if cnt.value:
+            self._chk(self.lib.pcr_read_polygon(self.h, first, nb, C.byref(poly.c), out.ctypes.data, len(out), C.byref(cnt), C.byref(st)), "pcr_read_polygon")
+        self.polygon_stats = st.as_dict()
         return out
 
     # -- top-down grid (pcr_grid_clear / pcr_grid_accumulate / pcr_grid_unpack / pcr_read_grid) --------------
@@ -1129,6 +1237,23 @@ class HuffmanLasData(Resource):
         info = self.las_info()
         box = box_from_world(info, lo, hi) if world else as_box((lo, hi))
         pts = renderer.ctx.select_box(box)
+        if not world:
+            return pts
+        so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
+        return pts[:, :3].to(torch.float64) * so[0] + so[1], pts
+
+    def points_in_polygon(self, renderer: Renderer, rings, z_lo=None, z_hi=None, invert: bool = False, world: bool = True):
+        """The points of the loaded resource inside a polygon prism, selected on the GPU (Context.select_polygon). world=True:
+        rings, z_lo and z_hi are world coordinates, turned into a Polygon by polygon_from_world with las_info()'s scale and
+        offset, and the result is (xyz, pts) as points(world=True) returns it. world=False: they are the stream's int32
+        coordinates (z_lo / z_hi None: unbounded), the result the int32 tensor alone."""
+        import torch
+        info = self.las_info()
+        if world:
+            poly = polygon_from_world(info, rings, z_lo, z_hi, invert)
+        else:
+            poly = Polygon(rings, INT32_MIN if z_lo is None else z_lo, INT32_MAX if z_hi is None else z_hi, invert)
+        pts = renderer.ctx.select_polygon(poly)
         if not world:
             return pts
         so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
