@@ -367,6 +367,41 @@ int pcr_thin(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_voxels 
 int pcr_read_thin(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int mode,
                   pcr_point *host_points, int64_t *host_rows, size_t capacity_points, int64_t *out_count, pcr_thin_stats *stats);
 
+/* ---- voxel denoising: drop or extract isolated points by 3 x 3 x 3 voxel count (no reference counterpart) -------------------
+ * Rows, candidates and voxels are pcr_thin's: the records pcr_decode_points writes for the range that lie inside *clip (NULL:
+ * all of them), v[k] = floor((p[k] - origin[k]) / cell), exact. N27(p) is the number of candidates of the call in the 27 voxels
+ * v(p) + {-1, 0, 1}^3; it counts p itself, exact duplicates and padding duplicates.
+ * CONTRACT: a candidate is isolated iff N27(p) <= max_count. max_count == 0 isolates nothing, a huge one everything.
+ * PCR_DENOISE_KEEP writes the candidates that are not isolated, PCR_DENOISE_ISOLATED the isolated ones: byte for byte the
+ * records pcr_decode_points writes (colour included) to dev_points, their rows to dev_rows (int64), both in increasing row
+ * order, packed without gaps. The result is exact and the same from run to run; BC1 and BC7, either resident layout, before
+ * and after the first frame. Only candidates of this call's range and clip count: a neighbour in another range or outside the
+ * clip does not exist for the call, so a point next to the cut may come out isolated -- denoise the whole range in one call,
+ * with a clip a little larger than the region wanted. (lasnoise's -isolated k counts the OTHER points of the 27 cells, which
+ * would make max_count = k + 1 its equivalent; that reading of its documentation has not been checked against the tool.)
+ *
+ * pcr_denoise: dev_points (16-byte aligned), dev_rows (8-byte aligned), capacity_points, *out_count, the count-only call, a
+ *   capacity below the result (PCR_E_ARG, *out_count = the count needed, nothing written), range semantics, the empty clip /
+ *   empty range / clip that misses every batch (0 records, PCR_OK, no kernel runs) and the synchronisation are pcr_thin's, word
+ *   for word. Touches no framebuffer, no prepass state, no render statistics. stats may be NULL.
+ *   How: pcr_thin's frame with a sum in the table. The lattice is shifted by whole cells so that every voxel index of a
+ *   candidate lies in 1 .. 2^21 - 2 (a neighbour's key never leaves its 21-bit fields). k_thin_runs counts the runs, the host
+ *   sizes the table as pcr_thin does, k_denoise_count inserts one (voxel, run length) per run -- compare-and-swap on the key,
+ *   64-bit atomic add on the value -- k_denoise_verdict sums, per occupied slot, the 27 values around it (stopping once the sum
+ *   exceeds max_count) and puts the verdict into bit 63 of the slot's value, k_denoise_flag decodes once more and builds the
+ *   bitmap of rows to write from the verdict of each run's voxel, and k_thin_totals / k_thin_write size and write the output.
+ *   Addition commutes: the table, hence the result, does not depend on the order of lanes or workgroups. The 27 lookups are
+ *   paid per voxel, not per point. The scratch memory is pcr_thin's.
+ * pcr_read_denoise: the same into host memory (alignof(pcr_point) / alignof(int64_t)), staged as pcr_read_thin stages.
+ * PCR_E_ARG with a message, nothing written: pcr_thin's refusals (without the PCR_THIN_CENTER limit), max_count < 0, a mode
+ * that is neither PCR_DENOISE_KEEP nor PCR_DENOISE_ISOLATED, and a lattice too large for the key: with q as for pcr_thin the
+ * call is refused if on any axis q.max - q.min >= 2^31 or (q.max - q.min) / cell + 4 > 2^21 -- pass a clip or a larger cell. */
+int pcr_denoise(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int64_t max_count,
+                int mode, void *dev_points, void *dev_rows, size_t capacity_points, int64_t *out_count, pcr_denoise_stats *stats);
+int pcr_read_denoise(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip,
+                     int64_t max_count, int mode, pcr_point *host_points, int64_t *host_rows, size_t capacity_points,
+                     int64_t *out_count, pcr_denoise_stats *stats);
+
 /* What a collective library needs to merge partial frames in place (include/pcr_dist.h does it with RCCL): the HIP stream
  * the context enqueues on, its device ordinal and the length of each framebuffer in 64-bit words. */
 void *pcr_get_stream(pcr_ctx *ctx);

@@ -192,7 +192,7 @@ typedef struct pcr_grid_stats {
     int64_t batches_outside, batches_windowed, batches_direct;
 } pcr_grid_stats;
 
-/* A lattice of cubic voxels over the stream's int32 coordinates (pcr_thin), 16 bytes: a point (x, y, z) belongs to voxel
+/* A lattice of cubic voxels over the stream's int32 coordinates (pcr_thin, pcr_denoise), 16 bytes: a point (x, y, z) belongs to voxel
  * v[k] = floor((p[k] - origin[k]) / cell) on every axis, the difference and the division taken exactly (as 64-bit integers;
  * v may be negative). Every int32 point has a voxel: the lattice has no far edge. */
 #define PCR_THIN_FIRST            0          /* mode: of a voxel's points the one with the lowest row */
@@ -216,6 +216,27 @@ typedef struct pcr_thin_stats {
     int64_t points_kept;
     int64_t table_slots;
 } pcr_thin_stats;
+
+/* pcr_denoise: a candidate is isolated iff the 27 voxels around its own hold at most max_count candidates, itself included. */
+#define PCR_DENOISE_KEEP          0          /* mode: write the candidates that are not isolated */
+#define PCR_DENOISE_ISOLATED      1          /* mode: write the isolated ones */
+
+/* What pcr_denoise did: the batches of the range whose exact box misses the clip (not decoded) and the others (decoded four
+ * times: runs counted, voxels counted, rows flagged, records written; the last only for a batch that writes a record), the
+ * rows inside the clip, the runs of equal voxel they form along their chains (= insertions into the voxel table), the
+ * non-empty voxels (occupied slots), of those the ones whose points are isolated, the isolated points (whichever mode), the
+ * records written, which is the call's *out_count, and the slots of the table. */
+typedef struct pcr_denoise_stats {
+    int64_t batches_outside;
+    int64_t batches_decoded;
+    int64_t points_considered;
+    int64_t runs;
+    int64_t voxels;
+    int64_t voxels_isolated;
+    int64_t points_isolated;
+    int64_t points_written;
+    int64_t table_slots;
+} pcr_denoise_stats;
 
 /* A rectangle of pixels (pcr_select_screen), bounds inclusive, clipped to the image by the call. x0 > x1 or y0 > y1: the
  * empty rect. */

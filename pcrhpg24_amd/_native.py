@@ -111,6 +111,17 @@ class ThinStats(C.Structure):                     # pcr_thin_stats
 THIN_FIRST, THIN_CENTER, THIN_MAX_CELL, THIN_MAX_CENTER_CELL = 0, 1, 1 << 30, 2048                      # pcr_types.h
 
 
+class DenoiseStats(C.Structure):                  # pcr_denoise_stats
+    _fields_ = [(n, c_i64) for n in ("batches_outside", "batches_decoded", "points_considered", "runs", "voxels", "voxels_isolated",
+                                     "points_isolated", "points_written", "table_slots")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+DENOISE_KEEP, DENOISE_ISOLATED = 0, 1                                                                   # pcr_types.h
+
+
 class Rect(C.Structure):                          # pcr_rect: pixel bounds, inclusive; x0 > x1 or y0 > y1 = empty
     _fields_ = [(n, c_i32) for n in ("x0", "y0", "x1", "y1")]
 
@@ -143,7 +154,7 @@ assert C.sizeof(Polygon) == 40 and C.sizeof(PolygonStats) == 48
 assert C.sizeof(Rect) == 16 and C.sizeof(ScreenHit) == 16 and C.sizeof(ScreenStats) == 32
 assert C.sizeof(DisplayOpts) == 16
 assert C.sizeof(Grid) == 24 and C.sizeof(GridStats) == 24
-assert C.sizeof(Voxels) == 16 and C.sizeof(ThinStats) == 48
+assert C.sizeof(Voxels) == 16 and C.sizeof(ThinStats) == 48 and C.sizeof(DenoiseStats) == 72
 assert C.sizeof(XyzBatch) == 64 and C.sizeof(GpuBatch) == 160 and C.sizeof(FileHeader) == 40 and C.sizeof(RenderParams) == 224
 
 
@@ -170,6 +181,7 @@ HIP_SYMBOLS = [
     "pcr_resolve_basic_display", "pcr_resolve_hqs_display", "pcr_resolve_las_display",
     "pcr_grid_clear", "pcr_grid_accumulate", "pcr_grid_unpack", "pcr_read_grid",
     "pcr_thin", "pcr_read_thin",
+    "pcr_denoise", "pcr_read_denoise",
 ]
 
 HOST_SYMBOLS = [
@@ -297,6 +309,9 @@ def hip_lib() -> C.CDLL:
         for n in ("pcr_thin", "pcr_read_thin"):
             getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Voxels), C.POINTER(Box), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.POINTER(c_i64), C.POINTER(ThinStats)]
+        for n in ("pcr_denoise", "pcr_read_denoise"):
+            getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Voxels), C.POINTER(Box), c_i64, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.POINTER(c_i64), C.POINTER(DenoiseStats)]
         _hip = lib
     return _hip
 

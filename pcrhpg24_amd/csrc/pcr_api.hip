@@ -171,6 +171,8 @@ struct pcr_ctx {
     uint32_t *d_thin_error = nullptr;           // [1] k_thin_mark found no slot
     int64_t *d_thin_rows_stage = nullptr;       // [thin_rows_stage_batches * 65536]
     int64_t thin_rows_stage_batches = 0;
+    // voxel denoising (pcr_denoise / pcr_read_denoise) shares all of the above; its own: the voxel counters of k_denoise_verdict
+    unsigned long long *d_denoise_counters = nullptr;   // [2] occupied slots, isolated ones
     int64_t prepass_batches = 0;
     static constexpr int FENCES = 8;
     hipEvent_t fence[FENCES] = {};              // pcr_fence_record / pcr_fence_wait: device-scope ordering between streams
@@ -273,6 +275,7 @@ void free_stream_buffers(pcr_ctx *c)
     dfree(c->d_thin_list); dfree(c->d_thin_totals); dfree(c->d_thin_wlist); dfree(c->d_thin_offsets); c->thin_capacity = 0;
     dfree(c->d_thin_table); c->thin_slots = 0; dfree(c->d_thin_keep); c->thin_keep_words = 0; dfree(c->d_thin_error);
     dfree(c->d_thin_rows_stage); c->thin_rows_stage_batches = 0;
+    dfree(c->d_denoise_counters);
 
     if (c->any_generic_pending && c->any_generic_ev) (void)hipEventSynchronize(c->any_generic_ev);
     c->any_generic_pending = false;
@@ -2187,6 +2190,41 @@ bool thin_grow(void **p, int64_t &have, int64_t want, size_t elem_bytes)
     return true;
 }
 
+// The batches of [first, first + n) whose exact box the clip a.q does not miss into `listed` (ascending), and into q the union of
+// their boxes intersected with the clip. a.q is not empty.
+int thin_list_batches(pcr_ctx *c, int64_t first, int64_t n, const ThinArgs &a, std::vector<uint32_t> &listed, pcr_box &q)
+{
+    int rc;
+    if ((rc = ensure_point_bounds(c, first, n))) return rc;
+    q = pcr_box{{INT32_MAX, INT32_MAX, INT32_MAX}, {INT32_MIN, INT32_MIN, INT32_MIN}};
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t *bb = c->h_point_bounds.data() + (first + i) * 6;
+        bool disjoint = false;
+        for (int k = 0; k < 3; ++k) disjoint = disjoint || bb[3 + k] < a.q.min[k] || bb[k] > a.q.max[k];
+        if (disjoint) continue;
+        listed.push_back((uint32_t)(first + i));
+        for (int k = 0; k < 3; ++k) { q.min[k] = std::min(q.min[k], bb[k]); q.max[k] = std::max(q.max[k], bb[3 + k]); }
+    }
+    for (int k = 0; k < 3; ++k) { q.min[k] = std::max(q.min[k], a.q.min[k]); q.max[k] = std::min(q.max[k], a.q.max[k]); }
+    return PCR_OK;
+}
+
+// The lists of nL batches, the error word and the keep bitmap of n batches
+int thin_reserve(pcr_ctx *c, int64_t nL, int64_t n)
+{
+    if (c->thin_capacity < nL) {
+        dfree(c->d_thin_list); dfree(c->d_thin_totals); dfree(c->d_thin_wlist); dfree(c->d_thin_offsets); c->thin_capacity = 0;
+        if (hipMalloc((void **)&c->d_thin_list, (size_t)nL * 4) != hipSuccess || hipMalloc((void **)&c->d_thin_totals, (size_t)nL * 8) != hipSuccess ||
+            hipMalloc((void **)&c->d_thin_wlist, (size_t)nL * 4) != hipSuccess || hipMalloc((void **)&c->d_thin_offsets, (size_t)nL * 8) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for the lists of %lld batches", (long long)nL);
+        c->thin_capacity = nL;
+    }
+    if (!c->d_thin_error && hipMalloc((void **)&c->d_thin_error, 4) != hipSuccess) return set_err(c, PCR_E_NOMEM, "out of device memory for a word");
+    if (!thin_grow((void **)&c->d_thin_keep, c->thin_keep_words, n * PCR_WORKGROUP_SIZE, 8))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the keep bitmap of %lld batches", (long long)n);
+    return PCR_OK;
+}
+
 // Phases one to three: classify (host, from the cached exact boxes), count the runs, fill the voxel table, flag the kept rows and
 // count them per batch. Synchronises.
 int thin_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const pcr_box *clip, int mode, ThinPlan &p)
@@ -2197,19 +2235,10 @@ int thin_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const
     for (int k = 0; k < 3; ++k) { a.q.min[k] = clip ? clip->min[k] : INT32_MIN; a.q.max[k] = clip ? clip->max[k] : INT32_MAX; }
     if (n == 0 || box_empty(a.q)) return PCR_OK;
     int rc;
-    if ((rc = ensure_point_bounds(c, first, n))) return rc;
-    pcr_box q{{INT32_MAX, INT32_MAX, INT32_MAX}, {INT32_MIN, INT32_MIN, INT32_MIN}};      // the union of the listed batches' boxes
-    for (int64_t i = 0; i < n; ++i) {
-        const int32_t *bb = c->h_point_bounds.data() + (first + i) * 6;
-        bool disjoint = false;
-        for (int k = 0; k < 3; ++k) disjoint = disjoint || bb[3 + k] < a.q.min[k] || bb[k] > a.q.max[k];
-        if (disjoint) continue;
-        p.listed.push_back((uint32_t)(first + i));
-        for (int k = 0; k < 3; ++k) { q.min[k] = std::min(q.min[k], bb[k]); q.max[k] = std::max(q.max[k], bb[3 + k]); }
-    }
+    pcr_box q{};                                    // the union of the listed batches' boxes, inside the clip
+    if ((rc = thin_list_batches(c, first, n, a, p.listed, q))) return rc;
     const int64_t nL = (int64_t)p.listed.size();
     if (nL == 0) return PCR_OK;
-    for (int k = 0; k < 3; ++k) { q.min[k] = std::max(q.min[k], a.q.min[k]); q.max[k] = std::min(q.max[k], a.q.max[k]); }
     int axis = 0;
     switch (thin_lattice(vox.origin, vox.cell, q.min, q.max, &a.lat, &axis)) {
     case THIN_LATTICE_EXTENT:
@@ -2221,17 +2250,7 @@ int thin_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const
     default: break;
     }
     p.st.batches_outside = n - nL; p.st.batches_decoded = nL;
-
-    if (c->thin_capacity < nL) {
-        dfree(c->d_thin_list); dfree(c->d_thin_totals); dfree(c->d_thin_wlist); dfree(c->d_thin_offsets); c->thin_capacity = 0;
-        if (hipMalloc((void **)&c->d_thin_list, (size_t)nL * 4) != hipSuccess || hipMalloc((void **)&c->d_thin_totals, (size_t)nL * 8) != hipSuccess ||
-            hipMalloc((void **)&c->d_thin_wlist, (size_t)nL * 4) != hipSuccess || hipMalloc((void **)&c->d_thin_offsets, (size_t)nL * 8) != hipSuccess)
-            return set_err(c, PCR_E_NOMEM, "out of device memory for the lists of %lld batches", (long long)nL);
-        c->thin_capacity = nL;
-    }
-    if (!c->d_thin_error && hipMalloc((void **)&c->d_thin_error, 4) != hipSuccess) return set_err(c, PCR_E_NOMEM, "out of device memory for a word");
-    if (!thin_grow((void **)&c->d_thin_keep, c->thin_keep_words, n * PCR_WORKGROUP_SIZE, 8))
-        return set_err(c, PCR_E_NOMEM, "out of device memory for the keep bitmap of %lld batches", (long long)n);
+    if ((rc = thin_reserve(c, nL, n))) return rc;
 
     a.first_batch = (uint32_t)first;
     const StreamView s = make_stream_view(c);
@@ -2331,6 +2350,34 @@ int thin_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_voxels *vox
     *done = false;
     return PCR_OK;
 }
+
+// The plan's records and / or rows (either may be NULL) into host memory through the staging buffers. Synchronises.
+int thin_read_pieces(pcr_ctx *c, int64_t first_batch, int64_t n, ThinPlan &p, pcr_point *host_points, int64_t *host_rows)
+{
+    int rc;
+    // pieces of at most DECODE_STAGE_BATCHES batches: a batch keeps at most 65 536 records, so a piece fits the staging buffers
+    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
+    if (host_points && !thin_grow((void **)&c->d_decode_stage, c->decode_stage_batches, piece, (size_t)PCR_POINTS_PER_BATCH * sizeof(pcr_point)))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of points", (long long)piece);
+    if (host_rows && !thin_grow((void **)&c->d_thin_rows_stage, c->thin_rows_stage_batches, piece, (size_t)PCR_POINTS_PER_BATCH * sizeof(int64_t)))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of rows", (long long)piece);
+    uint4 *const d_points = host_points ? reinterpret_cast<uint4 *>(c->d_decode_stage) : nullptr;
+    int64_t *const d_rows = host_rows ? c->d_thin_rows_stage : nullptr;
+    int64_t written = 0;
+    size_t w = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += piece) {
+        const int64_t i1 = std::min(n, i0 + piece);
+        int64_t m = 0;
+        for (; w < p.writers.size() && p.writers[w] < (uint32_t)(first_batch + i1); ++w) m += p.cnt[w];
+        if (m == 0) continue;
+        if ((rc = thin_emit(c, first_batch, i0, i1, p, d_points, d_rows))) return rc;
+        if (d_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
+        if (d_rows) HIP_TRY(c, hipMemcpyAsync(host_rows + written, d_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        written += m;
+    }
+    return PCR_OK;
+}
 } // namespace
 
 int pcr_thin(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int mode, void *dev_points, void *dev_rows,
@@ -2359,28 +2406,157 @@ int pcr_read_thin(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxe
     int rc = thin_prepare(c, first_batch, count, vox, clip, mode, host_points, alignof(pcr_point), host_rows, alignof(int64_t), capacity_points, out_count,
                           stats, &n, p, &done);
     if (rc || done) return rc;
-    // pieces of at most DECODE_STAGE_BATCHES batches: a batch keeps at most 65 536 records, so a piece fits the staging buffers
-    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
-    if (host_points && !thin_grow((void **)&c->d_decode_stage, c->decode_stage_batches, piece, (size_t)PCR_POINTS_PER_BATCH * sizeof(pcr_point)))
-        return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of points", (long long)piece);
-    if (host_rows && !thin_grow((void **)&c->d_thin_rows_stage, c->thin_rows_stage_batches, piece, (size_t)PCR_POINTS_PER_BATCH * sizeof(int64_t)))
-        return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of rows", (long long)piece);
-    uint4 *const d_points = host_points ? reinterpret_cast<uint4 *>(c->d_decode_stage) : nullptr;
-    int64_t *const d_rows = host_rows ? c->d_thin_rows_stage : nullptr;
-    int64_t written = 0;
-    size_t w = 0;
-    for (int64_t i0 = 0; i0 < n; i0 += piece) {
-        const int64_t i1 = std::min(n, i0 + piece);
-        int64_t m = 0;
-        for (; w < p.writers.size() && p.writers[w] < (uint32_t)(first_batch + i1); ++w) m += p.cnt[w];
-        if (m == 0) continue;
-        if ((rc = thin_emit(c, first_batch, i0, i1, p, d_points, d_rows))) return rc;
-        if (d_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
-        if (d_rows) HIP_TRY(c, hipMemcpyAsync(host_rows + written, d_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        written += m;
+    return thin_read_pieces(c, first_batch, n, p, host_points, host_rows);
+}
+
+// ---- voxel denoising ---------------------------------------------------------------------------
+namespace {
+// pcr_thin's phases with a sum in the table: classify, count the runs, count the candidates per voxel, decide per voxel, flag the
+// rows to write and count them per batch. Fills the plan thin_emit takes (p.st is not used) and st. Synchronises.
+int denoise_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const pcr_box *clip, int64_t max_count, int mode, ThinPlan &p,
+                 pcr_denoise_stats &st)
+{
+    p.listed.clear(); p.writers.clear(); p.cnt.clear();
+    st = pcr_denoise_stats{};
+    st.batches_outside = n;
+    DenoiseArgs d{};
+    ThinArgs &a = d.t;
+    for (int k = 0; k < 3; ++k) { a.q.min[k] = clip ? clip->min[k] : INT32_MIN; a.q.max[k] = clip ? clip->max[k] : INT32_MAX; }
+    if (n == 0 || box_empty(a.q)) return PCR_OK;
+    int rc;
+    pcr_box q{};                                    // the union of the listed batches' boxes, inside the clip
+    if ((rc = thin_list_batches(c, first, n, a, p.listed, q))) return rc;
+    const int64_t nL = (int64_t)p.listed.size();
+    if (nL == 0) return PCR_OK;
+    int axis = 0;
+    switch (noise_lattice(vox.origin, vox.cell, q.min, q.max, &a.lat, &axis)) {
+    case THIN_LATTICE_EXTENT:
+        return set_err(c, PCR_E_ARG, "the points to denoise span %lld on axis %d, 2^31 or more: pass a clip or a larger cell (a tail artefact far outside the cloud?)",
+                       (long long)q.max[axis] - (long long)q.min[axis], axis);
+    case THIN_LATTICE_VOXELS:
+        return set_err(c, PCR_E_ARG, "the points to denoise span %lld on axis %d, more than 2^21 - 2 voxels of %d: pass a clip or a larger cell (a tail artefact far outside the cloud?)",
+                       (long long)q.max[axis] - (long long)q.min[axis], axis, vox.cell);
+    default: break;
     }
+    st.batches_outside = n - nL; st.batches_decoded = nL;
+    if ((rc = thin_reserve(c, nL, n))) return rc;
+    if (!c->d_denoise_counters && hipMalloc((void **)&c->d_denoise_counters, 16) != hipSuccess)
+        return set_err(c, PCR_E_NOMEM, "out of device memory for two words");
+
+    a.first_batch = (uint32_t)first;
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)nL), block(PCR_WORKGROUP_SIZE);
+    const bool windows = select_reads_windows(c);
+    HIP_TRY(c, hipMemcpyAsync(c->d_thin_list, p.listed.data(), (size_t)nL * 4, hipMemcpyHostToDevice, c->stream));
+    if (windows) hipLaunchKernelGGL((k_thin_runs<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_thin_list, a, c->d_thin_totals);
+    else         hipLaunchKernelGGL((k_thin_runs<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_thin_list, a, c->d_thin_totals);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint32_t> totals((size_t)nL * 2 + 1);
+    unsigned long long counters[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_thin_totals, (size_t)nL * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int64_t k = 0; k < nL; ++k) { st.runs += totals[(size_t)k * 2]; st.points_considered += totals[(size_t)k * 2 + 1]; }
+    if (st.runs == 0) return PCR_OK;
+
+    uint32_t log2_slots = 10;
+    while (((int64_t)1 << log2_slots) < 2 * st.runs) ++log2_slots;
+    const int64_t slots = (int64_t)1 << log2_slots;
+    if (!thin_grow((void **)&c->d_thin_table, c->thin_slots, slots, sizeof(ThinSlot)))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for a voxel table of %lld slots (%lld runs): pass a clip or a larger cell", (long long)slots,
+                       (long long)st.runs);
+    st.table_slots = slots;
+    a.log2_slots = log2_slots; a.table = c->d_thin_table; a.error = c->d_thin_error;
+    d.max_count = (unsigned long long)max_count; d.counters = c->d_denoise_counters;
+    const dim3 per_slot((unsigned)std::min<int64_t>((slots + 255) / 256, 4096));
+    hipLaunchKernelGGL(k_denoise_clear, per_slot, dim3(256), 0, c->stream, c->d_thin_table, (unsigned long long)slots);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemsetAsync(c->d_thin_error, 0, 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_denoise_counters, 0, 16, c->stream));
+    if (windows) hipLaunchKernelGGL((k_denoise_count<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_thin_list, a);
+    else         hipLaunchKernelGGL((k_denoise_count<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_thin_list, a);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(k_denoise_verdict, per_slot, dim3(256), 0, c->stream, d);
+    HIP_TRY(c, hipGetLastError());
+    // (every lane of a listed batch stores its keep word, and only listed batches are read: the bitmap needs no clearing)
+#define PCR_LAUNCH(L, M) hipLaunchKernelGGL((k_denoise_flag<L, M>), grid, block, 0, c->stream, s, c->d_thin_list, a, c->d_thin_keep)
+    if (windows) { if (mode == PCR_DENOISE_ISOLATED) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, PCR_DENOISE_ISOLATED); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, PCR_DENOISE_KEEP); }
+    else         { if (mode == PCR_DENOISE_ISOLATED) PCR_LAUNCH(LAYOUT_WORDS, PCR_DENOISE_ISOLATED); else PCR_LAUNCH(LAYOUT_WORDS, PCR_DENOISE_KEEP); }
+#undef PCR_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(k_thin_totals, grid, dim3(256), 0, c->stream, c->d_thin_list, (uint32_t)first, c->d_thin_keep, c->d_thin_totals);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_thin_totals, (size_t)nL * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(totals.data() + nL * 2, c->d_thin_error, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(counters, c->d_denoise_counters, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (totals[(size_t)nL * 2]) return set_err(c, PCR_E_NOMEM, "voxel table overflow: %lld slots for %lld runs", (long long)slots, (long long)st.runs);
+    for (int64_t k = 0; k < nL; ++k) {
+        if (!totals[(size_t)k]) continue;
+        p.writers.push_back(p.listed[(size_t)k]); p.cnt.push_back(totals[(size_t)k]);
+        st.points_written += totals[(size_t)k];
+    }
+    st.voxels = (int64_t)counters[0]; st.voxels_isolated = (int64_t)counters[1];
+    st.points_isolated = mode == PCR_DENOISE_ISOLATED ? st.points_written : st.points_considered - st.points_written;
     return PCR_OK;
+}
+
+// The checks and the plan shared by pcr_denoise / pcr_read_denoise. *done: nothing left to write (an error, a count-only call, no records).
+int denoise_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int64_t max_count, int mode, const void *points,
+                    size_t points_align, const void *rows, size_t rows_align, size_t capacity, int64_t *out_count, pcr_denoise_stats *stats, int64_t *n,
+                    ThinPlan &p, bool *done)
+{
+    *done = true;
+    if (out_count) *out_count = 0;
+    int rc = select_range(c, first, count, n);
+    if (rc) return rc;
+    if (!vox) return set_err(c, PCR_E_ARG, "the voxel lattice is NULL");
+    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
+    if (points && reinterpret_cast<uintptr_t>(points) % points_align != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
+    if (rows && reinterpret_cast<uintptr_t>(rows) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the rows is misaligned (%zu bytes)", rows_align);
+    if (vox->cell < 1 || vox->cell > PCR_THIN_MAX_CELL)
+        return set_err(c, PCR_E_ARG, "voxel cell of %d: the edge length is 1 .. %d (PCR_THIN_MAX_CELL)", vox->cell, PCR_THIN_MAX_CELL);
+    if (max_count < 0) return set_err(c, PCR_E_ARG, "max_count is %lld: 0 or more", (long long)max_count);
+    if (mode != PCR_DENOISE_KEEP && mode != PCR_DENOISE_ISOLATED) return set_err(c, PCR_E_ARG, "mode is %d, not PCR_DENOISE_KEEP or PCR_DENOISE_ISOLATED", mode);
+    if (*n > ((int64_t)1 << 40) / PCR_POINTS_PER_BATCH) return set_err(c, PCR_E_ARG, "a range of %lld batches has more than 2^40 rows", (long long)*n);
+    pcr_denoise_stats st{};
+    if ((rc = denoise_plan(c, first, *n, *vox, clip, max_count, mode, p, st))) return rc;
+    *out_count = st.points_written;
+    if (stats) *stats = st;
+    if ((!points && !rows) || st.points_written == 0) return PCR_OK;
+    if (capacity < (size_t)st.points_written)
+        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld to write", capacity, (long long)st.points_written);
+    *done = false;
+    return PCR_OK;
+}
+} // namespace
+
+int pcr_denoise(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int64_t max_count, int mode, void *dev_points,
+                void *dev_rows, size_t capacity_points, int64_t *out_count, pcr_denoise_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = denoise_prepare(c, first_batch, count, vox, clip, max_count, mode, dev_points, 16, dev_rows, 8, capacity_points, out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    if ((rc = thin_emit(c, first_batch, 0, n, p, static_cast<uint4 *>(dev_points), static_cast<int64_t *>(dev_rows)))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+int pcr_read_denoise(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int64_t max_count, int mode,
+                     pcr_point *host_points, int64_t *host_rows, size_t capacity_points, int64_t *out_count, pcr_denoise_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = denoise_prepare(c, first_batch, count, vox, clip, max_count, mode, host_points, alignof(pcr_point), host_rows, alignof(int64_t), capacity_points,
+                             out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    return thin_read_pieces(c, first_batch, n, p, host_points, host_rows);
 }
 
 // ---- screen selection and picking --------------------------------------------------------------

@@ -2,6 +2,7 @@
 // decoder outside the render kernels is the per-chain CPU one of include/huffman.h:433-477.
 //     pcr_decode <in.huffman> <out.las> [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --thin CELL [--center] [--box x0 y0 z0 x1 y1 z1]
+//     pcr_decode <in.huffman> <out.las> --denoise CELL MAXCOUNT [--isolated] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]
 //     pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1] [--rect x0 y0 x1 y1]
 //     pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]
@@ -12,7 +13,7 @@
 // (pcr_read_screen). With --ortho no points are read back at all: the stream is rasterized top-down on the GPU (pcr_read_grid) into
 // an orthophoto and, with --dsm, a surface model. With --thin one point per cubic voxel is read back (pcr_read_thin): the cloud
 // decimated on the GPU without ever existing in full. With --polygon only the points inside a polygon prism of world coordinates are
-// read back (pcr_read_polygon).
+// read back (pcr_read_polygon). With --denoise the points come back without the isolated ones, or those alone (pcr_read_denoise).
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -31,6 +32,7 @@ using namespace pcr_host;
 static const char *USAGE =
     "usage: pcr_decode <in.huffman> <out.las> [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --thin CELL [--center] [--box x0 y0 z0 x1 y1 z1]\n"
+    "       pcr_decode <in.huffman> <out.las> --denoise CELL MAXCOUNT [--isolated] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]\n"
     "       pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1]\n"
     "                                                [--rect x0 y0 x1 y1]\n"
@@ -47,6 +49,10 @@ static const char *USAGE =
     "  the lattice starts at the min corner of the header's box), thinned on the GPU, in the stream's order: the voxel's first\n"
     "  point in that order, with --center the one nearest to the voxel's centre. Only the points inside --box count, or inside\n"
     "  the box of the file's header. No point there is an error.\n"
+    "  --denoise CELL MAXCOUNT: the points without the isolated ones, in the stream's order. A point is isolated if the 3 x 3 x 3\n"
+    "  cubic voxels of CELL world units around its own (the lattice of --thin) hold at most MAXCOUNT points (a whole number >= 0),\n"
+    "  the point itself and exact duplicates included. --isolated: the isolated points instead. Only the points inside --box\n"
+    "  count, as neighbours too, or inside the box of the file's header. No point to write is an error.\n"
     "  --polygon FILE: only the points inside a polygon, selected on the GPU, in the stream's order. FILE is text in world\n"
     "  coordinates: one vertex `x y` per line, a blank line starts the next ring (a ring inside another is a hole: the even-odd\n"
     "  rule); a ring has at least 3 vertices and is closed implicitly, all rings together at most 4096. A vertex goes to the\n"
@@ -151,6 +157,36 @@ static bool parse_thin(int argc, char **argv, int at, Thin &t)
             t.has_box = true;
         } else if (a == "--center" && !t.center) {
             t.center = true;
+        } else {
+            return false;
+        }
+    }
+    return true;
+}
+
+struct Denoise {
+    double cell = 0.0;
+    long long max_count = 0;
+    bool isolated = false, has_box = false;
+    double lo[3], hi[3];
+};
+
+// the options behind --denoise, every one well formed, or false
+static bool parse_denoise(int argc, char **argv, int at, Denoise &d)
+{
+    if (argc < at + 3 || std::strcmp(argv[at], "--denoise") != 0) return false;
+    if (!parse_double(argv[at + 1], d.cell) || !(d.cell > 0.0)) return false;
+    char *end = nullptr;
+    errno = 0;
+    d.max_count = std::strtoll(argv[at + 2], &end, 10);
+    if (end == argv[at + 2] || *end != '\0' || errno == ERANGE || d.max_count < 0) return false;
+    for (int i = at + 3; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--box" && i + 6 < argc && !d.has_box) {
+            for (int k = 0; k < 6; ++k) if (!parse_double(argv[++i], k < 3 ? d.lo[k] : d.hi[k - 3])) return false;
+            d.has_box = true;
+        } else if (a == "--isolated" && !d.isolated) {
+            d.isolated = true;
         } else {
             return false;
         }
@@ -298,9 +334,11 @@ int main(int argc, char **argv)
     const bool thinned = argc > 3 && std::strcmp(argv[3], "--thin") == 0;
     Poly poly;
     const bool polygoned = argc > 3 && std::strcmp(argv[3], "--polygon") == 0;
-    const bool boxed = argc > 3 && !viewed && !orthoed && !thinned && !polygoned;
+    Denoise noise;
+    const bool denoised = argc > 3 && std::strcmp(argv[3], "--denoise") == 0;
+    const bool boxed = argc > 3 && !viewed && !orthoed && !thinned && !polygoned && !denoised;
     if (argc < 3 || (polygoned && !parse_polygon(argc, argv, 3, poly)) || (boxed && !parse_box(argc, argv, 3, lo, hi)) || (viewed && !parse_view(argc, argv, 3, view)) ||
-        (orthoed && !parse_ortho(argc, argv, 3, ortho)) || (thinned && !parse_thin(argc, argv, 3, thin))) { std::fputs(USAGE, stderr); return 2; }
+        (orthoed && !parse_ortho(argc, argv, 3, ortho)) || (thinned && !parse_thin(argc, argv, 3, thin)) || (denoised && !parse_denoise(argc, argv, 3, noise))) { std::fputs(USAGE, stderr); return 2; }
     const std::string in = argv[1], out = argv[2];
     try {
         Renderer renderer(viewed ? view.w : 64, viewed ? view.h : 64, 0);
@@ -342,6 +380,16 @@ int main(int argc, char **argv)
                         vox.cell, (long long)st.batches_outside, (long long)st.batches_decoded, (long long)st.points_considered, (long long)st.runs,
                         (long long)st.points_kept, (long long)st.table_slots);
             if (points.empty()) throw std::runtime_error("no points inside the box: nothing written");
+        } else if (denoised) {
+            const pcr_voxels vox = voxelsFromWorld(info, noise.cell, info.min);
+            const pcr_box clip = boxFromWorld(info, noise.has_box ? noise.lo : info.min, noise.has_box ? noise.hi : info.max);
+            const pcr_denoise_stats st = las->denoised(vox, &clip, noise.max_count, noise.isolated ? PCR_DENOISE_ISOLATED : PCR_DENOISE_KEEP, points);
+            std::printf("denoise: cell of %d lattice steps, batches outside %lld, decoded %lld, points considered %lld, runs %lld, voxels %lld, "
+                        "isolated voxels %lld, isolated points %lld, written %lld, table slots %lld\n",
+                        vox.cell, (long long)st.batches_outside, (long long)st.batches_decoded, (long long)st.points_considered, (long long)st.runs,
+                        (long long)st.voxels, (long long)st.voxels_isolated, (long long)st.points_isolated, (long long)st.points_written,
+                        (long long)st.table_slots);
+            if (points.empty()) throw std::runtime_error("no points to write: nothing written");
         } else if (viewed) {
             renderer.yaw = view.cam[0]; renderer.pitch = view.cam[1]; renderer.radius = view.cam[2];
             for (int k = 0; k < 3; ++k) renderer.target[k] = view.cam[3 + k];

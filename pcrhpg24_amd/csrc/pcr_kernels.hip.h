@@ -19,6 +19,7 @@
 //   k_grid*         on request: the stream rasterized top-down into max / min / count planes over its integer x and y
 //   k_polygon_*     on request: the records inside a polygon prism, each straddling batch against its own edge list in LDS
 //   k_thin_*        on request: one record per voxel of a cubic lattice, straight from the compressed stream
+//   k_denoise_*     on request: the records whose 3 x 3 x 3 voxels hold few points (or the others), on k_thin_*'s frame
 //   k_las_*         the 10-10-10 method (modules/compute_loop_las_cuda)
 //   k_resolve_*     framebuffer -> RGBA8 (resolve.cu:149-191, huffman_hqs/resolve.cu:2-47)
 //   k_merge_* / k_flip_sign  multi-GPU partial-framebuffer merges
@@ -2609,6 +2610,153 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_thin_write(StreamView s,
             ++dst;
         }
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Voxel denoising (pcr_denoise / pcr_read_denoise): a candidate is isolated iff the 27 voxels around its own hold at most
+// max_count candidates of the call (itself included). pcr_thin's frame with a sum in the table instead of a minimum, on the
+// lattice of noise_lattice (pcr_lattice.h: every voxel index in 1 .. 2^21 - 2, so a neighbour's key is the voxel's key plus or
+// minus 1, 2^21, 2^42 and never leaves its fields). One launch each:
+//   k_thin_runs        (above) runs and candidates per batch; the host sizes the table from the runs.
+//   k_denoise_clear    key = all ones, value = 0 in every slot.
+//   k_denoise_count    colourless decode: at the end of every run one insertion, compare-and-swap on the key as thin_insert,
+//                      then a 64-bit atomic add of the run's length. Addition commutes: the table is exact and the same from run
+//                      to run.
+//   k_denoise_verdict  a thread per slot: the values of the 27 keys around an occupied slot's summed (each looked up from its
+//                      home to the key or an empty slot), early out once the sum exceeds max_count; "isolated" goes into bit 63
+//                      of the slot's own value with an atomic OR (counts are below 2^40: readers mask the bit out). The 27
+//                      lookups are paid per voxel, not per point.
+//   k_denoise_flag     colourless decode a third time: at every run start the run's own slot is looked up, the bits of the run's
+//                      rows go into the lane's keep word by verdict and mode; the lane stores its chain's word once.
+//   k_thin_totals / k_thin_write (above) size and write the output.
+// No workgroup waits for another one; every probe loop makes at most `slots` steps.
+// ------------------------------------------------------------------------------------------------
+constexpr thin_u64 DENOISE_ISOLATED_BIT = 1ull << 63;
+
+struct DenoiseArgs {
+    ThinArgs t;                     // the clip, the shifted lattice, the first batch, the table and the error word
+    thin_u64 max_count;             // isolated: N27 <= max_count
+    thin_u64 *counters;             // [2] occupied slots, and of those the isolated ones (k_denoise_verdict adds)
+};
+
+__global__ void __launch_bounds__(256) k_denoise_clear(ThinSlot *table, thin_u64 slots)
+{
+    for (thin_u64 i = (thin_u64)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (thin_u64)gridDim.x * blockDim.x) {
+        table[i].key = THIN_EMPTY;
+        table[i].val = 0ull;
+    }
+}
+
+// thin_insert with a sum: the slot of the key, or the first free one from the key's home on, gets `count` added
+__device__ __forceinline__ void denoise_insert(const ThinArgs &a, thin_u64 key, thin_u64 count)
+{
+    const thin_u64 slots = 1ull << a.log2_slots, mask = slots - 1;
+    thin_u64 h = (key * THIN_HASH_MUL) >> (64u - a.log2_slots);
+    for (thin_u64 probe = 0; probe < slots; ++probe) {
+        ThinSlot *slot = a.table + h;
+        thin_u64 old = __hip_atomic_load(&slot->key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // (a taken slot never changes its key)
+        if (old == THIN_EMPTY) old = atomicCAS(&slot->key, THIN_EMPTY, key);
+        if (old == THIN_EMPTY || old == key) {
+            __hip_atomic_fetch_add(&slot->val, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (the result is not used)
+            return;
+        }
+        h = (h + 1) & mask;
+    }
+    *a.error = 1u;                                          // every slot holds another key: the host sized the table wrongly
+}
+
+// The value of `key` in a table nobody inserts into any more (bit 63 included): from the key's home on to the key or an empty
+// slot. found: the key has a slot.
+__device__ __forceinline__ thin_u64 denoise_lookup(const ThinSlot *table, uint32_t log2_slots, thin_u64 key, bool &found)
+{
+    const thin_u64 slots = 1ull << log2_slots, mask = slots - 1;
+    thin_u64 h = (key * THIN_HASH_MUL) >> (64u - log2_slots);
+    found = false;
+    for (thin_u64 probe = 0; probe < slots; ++probe) {
+        const thin_u64 k = table[h].key;
+        if (k == key) { found = true; return __hip_atomic_load(&table[h].val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+        if (k == THIN_EMPTY) return 0ull;
+        h = (h + 1) & mask;
+    }
+    return 0ull;
+}
+
+template <int LAYOUT>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_denoise_count(StreamView s, const uint32_t *list, ThinArgs a)
+{
+    const uint32_t b = list[blockIdx.x];
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    load_packed_table(s, b, s_table);
+    thin_u64 prev = THIN_EMPTY;
+    uint32_t len = 0;
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t) {
+        uint32_t d2;
+        const thin_u64 key = in_box(a.q, x, y, z) ? thin_key(a, x, y, z, d2) : THIN_EMPTY;
+        if (key == prev) {
+            ++len;
+        } else {
+            if (prev != THIN_EMPTY) denoise_insert(a, prev, len);
+            prev = key; len = 1;
+        }
+    });
+    if (prev != THIN_EMPTY) denoise_insert(a, prev, len);
+}
+
+__global__ void __launch_bounds__(256) k_denoise_verdict(DenoiseArgs a)
+{
+    ThinSlot *table = a.t.table;
+    const thin_u64 slots = 1ull << a.t.log2_slots;
+    uint32_t occupied = 0, isolated = 0;
+    for (thin_u64 i = (thin_u64)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (thin_u64)gridDim.x * blockDim.x) {
+        const thin_u64 key = table[i].key;
+        if (key == THIN_EMPTY) continue;
+        // the voxel's own count first (no lookup), then the 26 around it; every index is in 1 .. 2^21 - 2 (noise_lattice)
+        thin_u64 sum = __hip_atomic_load(&table[i].val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ~DENOISE_ISOLATED_BIT;
+        for (int n = 0; n < 27 && sum <= a.max_count; ++n) {
+            if (n == 13) continue;
+            const thin_u64 dx = (thin_u64)(n % 3), dy = (thin_u64)(n / 3 % 3), dz = (thin_u64)(n / 9);
+            const thin_u64 other = key + dx + (dy << THIN_KEY_BITS) + (dz << (2 * THIN_KEY_BITS)) - (1ull + (1ull << THIN_KEY_BITS) + (1ull << (2 * THIN_KEY_BITS)));
+            bool found;
+            sum += denoise_lookup(table, a.t.log2_slots, other, found) & ~DENOISE_ISOLATED_BIT;
+        }
+        ++occupied;
+        if (sum <= a.max_count) {
+            ++isolated;
+            atomicOr(&table[i].val, DENOISE_ISOLATED_BIT);
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { occupied += __shfl_xor(occupied, d, 64); isolated += __shfl_xor(isolated, d, 64); }
+    if ((threadIdx.x & 63u) == 0) {
+        if (occupied) atomicAdd(&a.counters[0], (thin_u64)occupied);
+        if (isolated) atomicAdd(&a.counters[1], (thin_u64)isolated);
+    }
+}
+
+// Workgroup x takes list[x]: keep[(b - first_batch) * 1024 + chain] = the chain's rows to write, MODE's side of the verdict
+template <int LAYOUT, int MODE>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_denoise_flag(StreamView s, const uint32_t *list, ThinArgs a, thin_u64 *keep)
+{
+    const uint32_t b = list[blockIdx.x];
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    load_packed_table(s, b, s_table);
+    thin_u64 prev = THIN_EMPTY, word = 0;
+    bool write = false;
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t) {
+        uint32_t d2;
+        const thin_u64 key = in_box(a.q, x, y, z) ? thin_key(a, x, y, z, d2) : THIN_EMPTY;
+        if (key != prev) {
+            prev = key; write = false;
+            if (key != THIN_EMPTY) {
+                bool found;
+                const thin_u64 val = denoise_lookup(a.table, a.log2_slots, key, found);
+                if (!found) *a.error = 1u;                                  // (k_denoise_count inserted every run's key)
+                write = found && ((val & DENOISE_ISOLATED_BIT) != 0) == (MODE == PCR_DENOISE_ISOLATED);
+            }
+        }
+        word |= write ? 1ull << (uint32_t)i : 0ull;
+    });
+    keep[(size_t)(b - a.first_batch) * PCR_WORKGROUP_SIZE + threadIdx.x] = word;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
-// Integer lattice arithmetic shared by the top-down grid and the voxel thinning: the exact division of a 32-bit difference by a
-// cell, and the lattice pcr_thin hands to its kernels. Plain C++ without a HIP dependency, so a host-only build can call it.
+// Integer lattice arithmetic shared by the top-down grid, the voxel thinning and the voxel denoising: the exact division of a
+// 32-bit difference by a cell, and the lattices pcr_thin and pcr_denoise hand to their kernels. Plain C++ without a HIP dependency, so a host-only build can call it.
 #pragma once
 #include <cstdint>
 
@@ -45,6 +45,27 @@ inline int thin_lattice(const int32_t origin[3], int32_t cell, const int32_t qmi
         if (extent >= (int64_t)1 << 31) return THIN_LATTICE_EXTENT;
         if (extent / cell + 2 > (int64_t)1 << THIN_KEY_BITS) return THIN_LATTICE_VOXELS;
         const int64_t shifted = (int64_t)origin[k] + floor_div64((int64_t)qmin[k] - (int64_t)origin[k], cell) * (int64_t)cell;
+        out->origin[k] = (uint32_t)(uint64_t)shifted;
+    }
+    out->cell = (uint32_t)cell;
+    out->div = make_cell_div((uint32_t)cell);
+    return THIN_LATTICE_OK;
+}
+
+// The lattice of a denoising call: thin_lattice shifted by one whole cell more, origin'' = origin + (floor((q.min - origin) /
+// cell) - 1) * cell, so that q.min lies in voxel 1 on every axis. For a point p inside q, d = p - origin'' is in [cell, q.max -
+// q.min + 2 * cell) -- at most 2^32 - 1 for an extent below 2^31 and a cell of at most 2^30, so it still fits 32 unsigned bits --
+// and v'' = d / cell is in [1, (q.max - q.min) / cell + 2]: every index of the 27 voxels v'' + {-1, 0, 1}^3 lies in [0, (q.max -
+// q.min) / cell + 3]. The call is refused when (q.max - q.min) / cell + 4 > 2^21, so no neighbour index leaves its 21-bit field
+// of the key and the kernels need no range test. Same result codes as thin_lattice.
+inline int noise_lattice(const int32_t origin[3], int32_t cell, const int32_t qmin[3], const int32_t qmax[3], ThinLattice *out, int *axis)
+{
+    for (int k = 0; k < 3; ++k) {
+        const int64_t extent = (int64_t)qmax[k] - (int64_t)qmin[k];
+        *axis = k;
+        if (extent >= (int64_t)1 << 31) return THIN_LATTICE_EXTENT;
+        if (extent / cell + 4 > (int64_t)1 << THIN_KEY_BITS) return THIN_LATTICE_VOXELS;
+        const int64_t shifted = (int64_t)origin[k] + (floor_div64((int64_t)qmin[k] - (int64_t)origin[k], cell) - 1) * (int64_t)cell;
         out->origin[k] = (uint32_t)(uint64_t)shifted;
     }
     out->cell = (uint32_t)cell;

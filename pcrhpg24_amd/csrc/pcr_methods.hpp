@@ -358,6 +358,21 @@ struct HuffmanLasData : Resource {
         return st;
     }
 
+    // The points inside `clip` (NULL: everywhere) without the isolated ones -- those whose 3 x 3 x 3 voxels of `vox` hold at most
+    // max_count of them, the point itself included -- or with PCR_DENOISE_ISOLATED those alone, on the GPU straight from the
+    // compressed stream (pcr_read_denoise: a counting call, then the read). Not in the reference.
+    pcr_denoise_stats denoised(const pcr_voxels &vox, const pcr_box *clip, int64_t max_count, int mode, std::vector<pcr_point> &out)
+    {
+        if (!loadedOn) throw std::runtime_error("denoised: the resource is not loaded");
+        const int64_t nB = pcr_batches_resident(loadedOn->ctx);
+        int64_t n = 0;
+        pcr_denoise_stats st{};
+        loadedOn->check(pcr_read_denoise(loadedOn->ctx, 0, nB, &vox, clip, max_count, mode, nullptr, nullptr, 0, &n, &st), "pcr_read_denoise");
+        out.resize((size_t)n);
+        if (n) loadedOn->check(pcr_read_denoise(loadedOn->ctx, 0, nB, &vox, clip, max_count, mode, out.data(), nullptr, out.size(), &n, &st), "pcr_read_denoise");
+        return st;
+    }
+
     // The points a frame of camera `p` draws whose pixel lies in `rect` (NULL: the whole image), with where they land, selected on
     // the GPU (pcr_read_screen: a counting call, then the read). Either vector may be NULL. Not in the reference.
     pcr_screen_stats selectScreen(const pcr_render_params &p, const pcr_rect *rect, std::vector<pcr_point> *points, std::vector<pcr_screen_hit> *hits)

@@ -28,7 +28,7 @@ from typing import Iterator, Optional
 import numpy as np
 
 from . import _native as N
-from ._native import Box, DisplayOpts, EncodeStats, Grid, GridStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, ThinStats, Voxels, XyzBatch, c_i64, fb_elems
+from ._native import Box, DisplayOpts, EncodeStats, Grid, GridStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, DenoiseStats, ThinStats, Voxels, XyzBatch, c_i64, fb_elems
 
 POINTS_PER_BATCH = 65536
 ENCODED_PAD_WORDS = 1024
@@ -379,6 +379,15 @@ def thin_mode(mode) -> int:
         if mode not in ("first", "center"):
             raise ValueError('mode is "first" or "center"')
         return N.THIN_FIRST if mode == "first" else N.THIN_CENTER
+    return int(mode)
+
+
+def denoise_mode(mode) -> int:
+    """PCR_DENOISE_KEEP / PCR_DENOISE_ISOLATED from "keep" / "isolated" (an integer passes through: the library checks it)."""
+    if isinstance(mode, str):
+        if mode not in ("keep", "isolated"):
+            raise ValueError(f'mode is "keep" or "isolated", not {mode!r}')
+        return N.DENOISE_KEEP if mode == "keep" else N.DENOISE_ISOLATED
     return int(mode)
 
 
@@ -902,6 +911,48 @@ class Context:
         self.thin_stats = st.as_dict()
         return (pts, r) if rows else pts
 
+    # -- voxel denoising (pcr_denoise / pcr_read_denoise) ----------------------------------------------------
+    def denoise(self, vox, max_count: int, clip=None, mode="keep", first: int = 0, count: Optional[int] = None, out=None, rows: bool = False):
+        """The rows of batches [first, first + count) inside `clip` (as_box; None: everywhere) without the isolated ones (mode
+        "keep") or the isolated ones alone (mode "isolated"), straight from the compressed stream. A row is isolated iff the 27
+        voxels of `vox` (as_voxels) around its own hold at most `max_count` rows of the range inside the clip, itself included.
+        Results, `out`, rows=True and stream ordering as Context.thin. What the last call did is in self.denoise_stats."""
+        import torch
+        vox, clip, mode = as_voxels(vox), None if clip is None else as_box(clip), denoise_mode(mode)
+        cp = None if clip is None else C.byref(clip)
+        dev = torch.device("cuda", self.device)
+        cnt, st, nb = c_i64(), DenoiseStats(), -1 if count is None else count
+        if out is None:
+            self._chk(self.lib.pcr_denoise(self.h, first, nb, C.byref(vox), cp, max_count, mode, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_denoise")
+            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
+        cap = out.numel() // 4
+        r = torch.empty(cap, dtype=torch.int64, device=dev) if rows else None
+        torch.cuda.current_stream(dev).synchronize()
+        rc = self.lib.pcr_denoise(self.h, first, nb, C.byref(vox), cp, max_count, mode, C.c_void_p(out.data_ptr() if cap else None),
+                                  C.c_void_p(r.data_ptr() if cap else None) if rows else None, cap, C.byref(cnt), C.byref(st))
+        self.denoise_stats = st.as_dict()
+        if rc:
+            self.denoise_stats["points_written"] = cnt.value
+        self._chk(rc, "pcr_denoise")
+        pts = out.view(-1, 4)[:cnt.value]
+        return (pts, r[:cnt.value]) if rows else pts
+
+    def read_denoise(self, vox, max_count: int, clip=None, mode="keep", first: int = 0, count: Optional[int] = None, rows: bool = False):
+        """The same on the host, without torch: a numpy structured array of POINT_DTYPE, with rows=True (points, rows), rows an
+        int64 array (pcr_read_denoise: a counting call, then the read; synchronises)."""
+        vox, clip, mode = as_voxels(vox), None if clip is None else as_box(clip), denoise_mode(mode)
+        cp = None if clip is None else C.byref(clip)
+        cnt, st, nb = c_i64(), DenoiseStats(), -1 if count is None else count
+        self._chk(self.lib.pcr_read_denoise(self.h, first, nb, C.byref(vox), cp, max_count, mode, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_read_denoise")
+        pts, r = np.empty(cnt.value, POINT_DTYPE), np.empty(cnt.value if rows else 0, ROW_DTYPE)
+        if cnt.value:
+            self._chk(self.lib.pcr_read_denoise(self.h, first, nb, C.byref(vox), cp, max_count, mode, pts.ctypes.data, r.ctypes.data if rows else None,
+                                                len(pts), C.byref(cnt), C.byref(st)), "pcr_read_denoise")
+        self.denoise_stats = st.as_dict()
+        return (pts, r) if rows else pts
+
     # -- screen selection and picking (pcr_select_screen / pcr_read_screen / pcr_pick) ---------------------
     def select_screen(self, p: RenderParams, rect=None):
         """The points a frame of camera `p` draws (render_basic's cull, level of detail, precision and inside test) whose pixel lies
@@ -1317,6 +1368,26 @@ class HuffmanLasData(Resource):
             vox = as_voxels((0, 0, 0, cell_size))
             clip = None if lo is None and hi is None else as_box(((INT32_MIN,) * 3 if lo is None else lo, (INT32_MAX,) * 3 if hi is None else hi))
         pts = renderer.ctx.thin(vox, clip, mode)
+        if not world:
+            return pts
+        so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
+        return pts[:, :3].to(torch.float64) * so[0] + so[1], pts
+
+    def denoised(self, renderer: Renderer, cell_size: float, max_count: int, lo=None, hi=None, isolated: bool = False, world: bool = True):
+        """The loaded resource without its isolated points -- those whose 3 x 3 x 3 cubic voxels of `cell_size` hold at most
+        `max_count` points, the point itself included -- or, with isolated=True, those points alone; on the GPU and straight from
+        the compressed stream (Context.denoise). cell_size, lo, hi, world and the result are as for thinned(): with world=True the
+        clip defaults to the header's box, so the tail artefact of a stream written without padding neither counts as a
+        neighbour nor lands in the output."""
+        import torch
+        info = self.las_info()
+        if world:
+            vox = voxels_from_world(info, cell_size)
+            clip = box_from_world(info, tuple(info.min) if lo is None else lo, tuple(info.max) if hi is None else hi)
+        else:
+            vox = as_voxels((0, 0, 0, cell_size))
+            clip = None if lo is None and hi is None else as_box(((INT32_MIN,) * 3 if lo is None else lo, (INT32_MAX,) * 3 if hi is None else hi))
+        pts = renderer.ctx.denoise(vox, max_count, clip, "isolated" if isolated else "keep")
         if not world:
             return pts
         so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
