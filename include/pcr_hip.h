@@ -402,6 +402,44 @@ int pcr_read_denoise(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr
                      int64_t max_count, int mode, pcr_point *host_points, int64_t *host_rows, size_t capacity_points,
                      int64_t *out_count, pcr_denoise_stats *stats);
 
+/* ---- connected components of the occupied voxels: split the cloud, or drop every blob below a size (no reference counterpart) ---
+ * Rows, candidates, voxels and the lattice are pcr_denoise's, word for word: the records pcr_decode_points writes for the range
+ * that lie inside *clip (NULL: all of them), padding duplicates and tail garbage included; v[k] = floor((p[k] - origin[k]) /
+ * cell), exact. Two occupied voxels are adjacent if they differ by at most 1 on every axis (connectivity == 26) or by exactly 1
+ * on exactly one axis (connectivity == 6). A component is a class of the transitive closure of adjacency; its size is the number
+ * of candidates in its voxels, duplicates counted. Only candidates of this call's range and clip exist for the call.
+ * CONTRACT: the label of a component is the least row (pcr_decode_points order, counted from first_batch) of any candidate in it.
+ * It is canonical: it does not depend on the hash function, the table size, the resident layout or the order of lanes,
+ * workgroups or launches, and it is itself a row of the output when the component is written. A component is small iff its size
+ * is < min_points: min_points <= 1 makes nothing small, a huge one everything. PCR_COMPONENTS_KEEP writes the candidates of the
+ * components that are not small, PCR_COMPONENTS_SMALL those of the small ones: byte for byte the records pcr_decode_points
+ * writes to dev_points, their rows to dev_rows (int64), the labels of their components to dev_labels (int64), all three in
+ * increasing row order, packed without gaps. Exact and the same from run to run; BC1 and BC7, either resident layout, before and
+ * after the first frame.
+ *
+ * pcr_components: dev_points (16-byte aligned), dev_rows and dev_labels (8-byte aligned); any of them may be NULL, all three NULL
+ *   only counts. capacity_points, *out_count, a capacity below the result (PCR_E_ARG, *out_count = the count needed, nothing
+ *   written), range semantics, the empty clip / empty range / clip that misses every batch (0 records, PCR_OK, no kernel runs) and
+ *   the synchronisation are pcr_denoise's. Touches no framebuffer, no prepass state, no render statistics. stats may be NULL.
+ *   How: pcr_denoise's frame. k_components_count is k_denoise_count that also keeps the least row of every voxel; k_components_link
+ *   looks up, per occupied slot, the forward half of the neighbourhood (13 keys of 26, 3 of 6) and unites the slot with every
+ *   neighbour found in a lock-free union-find over the slot indices (Rem's algorithm with splicing: every step a compare-and-swap
+ *   that lowers a parent word, a parent always the lesser index); k_components_flatten points every slot at its root and takes
+ *   the sum of the sizes and the minimum of the least rows there; k_components_verdict marks the slots of small components and
+ *   hands every slot its label; k_denoise_flag, k_thin_totals and k_thin_write flag, size and write as for pcr_denoise, k_components_labels writes the
+ *   labels in a colourless decode of its own. Every loop is bounded by the number of slots. The scratch memory is pcr_thin's
+ *   plus 20 bytes per slot of the table.
+ * pcr_read_components: the same into host memory (alignof(pcr_point) / alignof(int64_t)), staged as pcr_read_thin stages.
+ * PCR_E_ARG with a message, nothing written: pcr_denoise's refusals (the lattice too large for the key included: pass a clip or a
+ * larger cell), a connectivity that is neither 6 nor 26, min_points < 0, a mode that is neither PCR_COMPONENTS_KEEP nor
+ * PCR_COMPONENTS_SMALL. PCR_E_NOMEM: a table of more than 2^32 slots (the forest's parent words are 32-bit). */
+int pcr_components(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int connectivity,
+                   int64_t min_points, int mode, void *dev_points, void *dev_rows, void *dev_labels, size_t capacity_points,
+                   int64_t *out_count, pcr_components_stats *stats);
+int pcr_read_components(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int connectivity,
+                        int64_t min_points, int mode, pcr_point *host_points, int64_t *host_rows, int64_t *host_labels,
+                        size_t capacity_points, int64_t *out_count, pcr_components_stats *stats);
+
 /* What a collective library needs to merge partial frames in place (include/pcr_dist.h does it with RCCL): the HIP stream
  * the context enqueues on, its device ordinal and the length of each framebuffer in 64-bit words. */
 void *pcr_get_stream(pcr_ctx *ctx);

@@ -192,7 +192,7 @@ typedef struct pcr_grid_stats {
     int64_t batches_outside, batches_windowed, batches_direct;
 } pcr_grid_stats;
 
-/* A lattice of cubic voxels over the stream's int32 coordinates (pcr_thin, pcr_denoise), 16 bytes: a point (x, y, z) belongs to voxel
+/* A lattice of cubic voxels over the stream's int32 coordinates (pcr_thin, pcr_denoise, pcr_components), 16 bytes: a point (x, y, z) belongs to voxel
  * v[k] = floor((p[k] - origin[k]) / cell) on every axis, the difference and the division taken exactly (as 64-bit integers;
  * v may be negative). Every int32 point has a voxel: the lattice has no far edge. */
 #define PCR_THIN_FIRST            0          /* mode: of a voxel's points the one with the lowest row */
@@ -237,6 +237,28 @@ typedef struct pcr_denoise_stats {
     int64_t points_written;
     int64_t table_slots;
 } pcr_denoise_stats;
+
+/* pcr_components: the occupied voxels form a graph; a component is small iff its voxels hold fewer than min_points candidates. */
+#define PCR_COMPONENTS_KEEP       0          /* mode: write the candidates of the components that are not small */
+#define PCR_COMPONENTS_SMALL      1          /* mode: write the candidates of the small ones */
+
+/* What pcr_components did: the first four as in pcr_denoise_stats (a listed batch is decoded three times for the plan, a fourth
+ * time if it writes a record, a fifth for its labels), the non-empty voxels, the components they form, of those the small ones
+ * and the candidates they hold (whichever mode), the candidates of the largest component, the records written, which is the
+ * call's *out_count, and the slots of the table. */
+typedef struct pcr_components_stats {
+    int64_t batches_outside;
+    int64_t batches_decoded;
+    int64_t points_considered;
+    int64_t runs;
+    int64_t voxels;
+    int64_t components;
+    int64_t components_small;
+    int64_t points_small;
+    int64_t largest_points;
+    int64_t points_written;
+    int64_t table_slots;
+} pcr_components_stats;
 
 /* A rectangle of pixels (pcr_select_screen), bounds inclusive, clipped to the image by the call. x0 > x1 or y0 > y1: the
  * empty rect. */

@@ -122,6 +122,17 @@ class DenoiseStats(C.Structure):                  # pcr_denoise_stats
 DENOISE_KEEP, DENOISE_ISOLATED = 0, 1                                                                   # pcr_types.h
 
 
+class ComponentsStats(C.Structure):               # pcr_components_stats
+    _fields_ = [(n, c_i64) for n in ("batches_outside", "batches_decoded", "points_considered", "runs", "voxels", "components", "components_small",
+                                     "points_small", "largest_points", "points_written", "table_slots")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+COMPONENTS_KEEP, COMPONENTS_SMALL = 0, 1                                                                # pcr_types.h
+
+
 class Rect(C.Structure):                          # pcr_rect: pixel bounds, inclusive; x0 > x1 or y0 > y1 = empty
     _fields_ = [(n, c_i32) for n in ("x0", "y0", "x1", "y1")]
 
@@ -154,7 +165,7 @@ assert C.sizeof(Polygon) == 40 and C.sizeof(PolygonStats) == 48
 assert C.sizeof(Rect) == 16 and C.sizeof(ScreenHit) == 16 and C.sizeof(ScreenStats) == 32
 assert C.sizeof(DisplayOpts) == 16
 assert C.sizeof(Grid) == 24 and C.sizeof(GridStats) == 24
-assert C.sizeof(Voxels) == 16 and C.sizeof(ThinStats) == 48 and C.sizeof(DenoiseStats) == 72
+assert C.sizeof(Voxels) == 16 and C.sizeof(ThinStats) == 48 and C.sizeof(DenoiseStats) == 72 and C.sizeof(ComponentsStats) == 88
 assert C.sizeof(XyzBatch) == 64 and C.sizeof(GpuBatch) == 160 and C.sizeof(FileHeader) == 40 and C.sizeof(RenderParams) == 224
 
 
@@ -182,6 +193,7 @@ HIP_SYMBOLS = [
     "pcr_grid_clear", "pcr_grid_accumulate", "pcr_grid_unpack", "pcr_read_grid",
     "pcr_thin", "pcr_read_thin",
     "pcr_denoise", "pcr_read_denoise",
+    "pcr_components", "pcr_read_components",
 ]
 
 HOST_SYMBOLS = [
@@ -312,6 +324,9 @@ def hip_lib() -> C.CDLL:
         for n in ("pcr_denoise", "pcr_read_denoise"):
             getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Voxels), C.POINTER(Box), c_i64, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.POINTER(c_i64), C.POINTER(DenoiseStats)]
+        for n in ("pcr_components", "pcr_read_components"):
+            getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Voxels), C.POINTER(Box), C.c_int, c_i64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.POINTER(c_i64), C.POINTER(ComponentsStats)]
         _hip = lib
     return _hip
 

@@ -173,6 +173,13 @@ struct pcr_ctx {
     int64_t thin_rows_stage_batches = 0;
     // voxel denoising (pcr_denoise / pcr_read_denoise) shares all of the above; its own: the voxel counters of k_denoise_verdict
     unsigned long long *d_denoise_counters = nullptr;   // [2] occupied slots, isolated ones
+    // connected components (pcr_components / pcr_read_components) share all of the above; their own: per slot of the table the
+    // least row / label (8 bytes), the component's total (8) and the parent word of the union-find (4), in this order
+    unsigned char *d_components_scratch = nullptr;      // [components_slots * 20]
+    int64_t components_slots = 0;
+    unsigned long long *d_components_counters = nullptr; // [5] occupied slots, components, small ones, their candidates, the largest
+    int64_t *d_components_labels_stage = nullptr;       // [components_labels_stage_batches * 65536]
+    int64_t components_labels_stage_batches = 0;
     int64_t prepass_batches = 0;
     static constexpr int FENCES = 8;
     hipEvent_t fence[FENCES] = {};              // pcr_fence_record / pcr_fence_wait: device-scope ordering between streams
@@ -276,6 +283,8 @@ void free_stream_buffers(pcr_ctx *c)
     dfree(c->d_thin_table); c->thin_slots = 0; dfree(c->d_thin_keep); c->thin_keep_words = 0; dfree(c->d_thin_error);
     dfree(c->d_thin_rows_stage); c->thin_rows_stage_batches = 0;
     dfree(c->d_denoise_counters);
+    dfree(c->d_components_scratch); c->components_slots = 0; dfree(c->d_components_counters);
+    dfree(c->d_components_labels_stage); c->components_labels_stage_batches = 0;
 
     if (c->any_generic_pending && c->any_generic_ev) (void)hipEventSynchronize(c->any_generic_ev);
     c->any_generic_pending = false;
@@ -2177,6 +2186,8 @@ struct ThinPlan {
     std::vector<int64_t> cnt;           // [writers.size()]
     std::vector<int64_t> offsets;       // staging of k_thin_write's offsets (alive until the stream has been synchronised)
     pcr_thin_stats st{};
+    ThinArgs args{};                    // pcr_components only: the lattice and the table of the plan, for k_components_labels,
+    const thin_u64 *label = nullptr;    // and the label of every slot
 };
 
 // *p holds at least `want` elements on return (a larger array replaces it, its content is not kept), or false
@@ -2300,8 +2311,9 @@ int thin_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const
 }
 
 // Enqueue the writes of batches [i0, i1) of the plan's range: their kept records to `points`, the rows to `rows` (device, either
-// may be NULL, each holds the records of those batches). The caller synchronises.
-int thin_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, uint4 *points, int64_t *rows)
+// may be NULL, each holds the records of those batches); for a plan of pcr_components the labels of the rows to `labels` as well
+// (NULL: not). The caller synchronises.
+int thin_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, uint4 *points, int64_t *rows, int64_t *labels = nullptr)
 {
     const size_t w0 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i0)) - p.writers.begin());
     const size_t w1 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i1)) - p.writers.begin());
@@ -2316,10 +2328,21 @@ int thin_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, ui
     const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
 #define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_thin_write<L, B>), grid, block, 0, c->stream, s, c->d_thin_wlist + w0, (uint32_t)first, c->d_thin_keep, \
                                             c->d_thin_offsets + w0, points, rows)
-    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
-    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+    if (points || rows) {
+        if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
+        else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+        HIP_TRY(c, hipGetLastError());
+    }
 #undef PCR_LAUNCH
-    HIP_TRY(c, hipGetLastError());
+    if (labels) {
+        if (select_reads_windows(c))
+            hipLaunchKernelGGL((k_components_labels<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_thin_wlist + w0, p.args, c->d_thin_keep,
+                               c->d_thin_offsets + w0, p.label, labels);
+        else
+            hipLaunchKernelGGL((k_components_labels<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_thin_wlist + w0, p.args, c->d_thin_keep,
+                               c->d_thin_offsets + w0, p.label, labels);
+        HIP_TRY(c, hipGetLastError());
+    }
     return PCR_OK;
 }
 
@@ -2351,8 +2374,9 @@ int thin_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_voxels *vox
     return PCR_OK;
 }
 
-// The plan's records and / or rows (either may be NULL) into host memory through the staging buffers. Synchronises.
-int thin_read_pieces(pcr_ctx *c, int64_t first_batch, int64_t n, ThinPlan &p, pcr_point *host_points, int64_t *host_rows)
+// The plan's records and / or rows (either may be NULL), for a plan of pcr_components the labels too (NULL: not), into host memory
+// through the staging buffers. Synchronises.
+int thin_read_pieces(pcr_ctx *c, int64_t first_batch, int64_t n, ThinPlan &p, pcr_point *host_points, int64_t *host_rows, int64_t *host_labels = nullptr)
 {
     int rc;
     // pieces of at most DECODE_STAGE_BATCHES batches: a batch keeps at most 65 536 records, so a piece fits the staging buffers
@@ -2361,8 +2385,11 @@ int thin_read_pieces(pcr_ctx *c, int64_t first_batch, int64_t n, ThinPlan &p, pc
         return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of points", (long long)piece);
     if (host_rows && !thin_grow((void **)&c->d_thin_rows_stage, c->thin_rows_stage_batches, piece, (size_t)PCR_POINTS_PER_BATCH * sizeof(int64_t)))
         return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of rows", (long long)piece);
+    if (host_labels && !thin_grow((void **)&c->d_components_labels_stage, c->components_labels_stage_batches, piece, (size_t)PCR_POINTS_PER_BATCH * sizeof(int64_t)))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of labels", (long long)piece);
     uint4 *const d_points = host_points ? reinterpret_cast<uint4 *>(c->d_decode_stage) : nullptr;
     int64_t *const d_rows = host_rows ? c->d_thin_rows_stage : nullptr;
+    int64_t *const d_labels = host_labels ? c->d_components_labels_stage : nullptr;
     int64_t written = 0;
     size_t w = 0;
     for (int64_t i0 = 0; i0 < n; i0 += piece) {
@@ -2370,9 +2397,10 @@ int thin_read_pieces(pcr_ctx *c, int64_t first_batch, int64_t n, ThinPlan &p, pc
         int64_t m = 0;
         for (; w < p.writers.size() && p.writers[w] < (uint32_t)(first_batch + i1); ++w) m += p.cnt[w];
         if (m == 0) continue;
-        if ((rc = thin_emit(c, first_batch, i0, i1, p, d_points, d_rows))) return rc;
+        if ((rc = thin_emit(c, first_batch, i0, i1, p, d_points, d_rows, d_labels))) return rc;
         if (d_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
         if (d_rows) HIP_TRY(c, hipMemcpyAsync(host_rows + written, d_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        if (d_labels) HIP_TRY(c, hipMemcpyAsync(host_labels + written, d_labels, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         written += m;
     }
@@ -2411,16 +2439,27 @@ int pcr_read_thin(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxe
 
 // ---- voxel denoising ---------------------------------------------------------------------------
 namespace {
-// pcr_thin's phases with a sum in the table: classify, count the runs, count the candidates per voxel, decide per voxel, flag the
-// rows to write and count them per batch. Fills the plan thin_emit takes (p.st is not used) and st. Synchronises.
-int denoise_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const pcr_box *clip, int64_t max_count, int mode, ThinPlan &p,
-                 pcr_denoise_stats &st)
+// What the calls on pcr_denoise's frame (pcr_denoise, pcr_components) share: the statistics common to both, and what the first half
+// of the plan hands to the call's own kernels and to the second half.
+struct VoxelPlan {
+    int64_t batches_outside = 0, batches_decoded = 0, points_considered = 0, runs = 0, table_slots = 0, points_written = 0;
+    int64_t nL = 0;                     // the listed batches
+    bool windows = false;               // the layout the kernels read
+    ThinArgs a{};                       // the clip, the lattice of noise_lattice, the first batch, the table and the error word
+    std::vector<uint32_t> totals;       // staging of d_thin_totals and the error word
+};
+
+// The first half: classify (host, from the cached exact boxes), the lattice, the scratch, the runs (k_thin_runs), the table sized
+// from them, key = all ones and value = 0 in every slot, the error word cleared. v.runs == 0 on return: nothing to do, no kernel
+// has touched the table. `verb` names the call in the messages; a table of more than 2^max_log2_slots slots is refused.
+// Synchronises.
+int voxel_plan_begin(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const pcr_box *clip, const char *verb, uint32_t max_log2_slots, ThinPlan &p,
+                     VoxelPlan &v)
 {
     p.listed.clear(); p.writers.clear(); p.cnt.clear();
-    st = pcr_denoise_stats{};
-    st.batches_outside = n;
-    DenoiseArgs d{};
-    ThinArgs &a = d.t;
+    v = VoxelPlan{};
+    v.batches_outside = n;
+    ThinArgs &a = v.a;
     for (int k = 0; k < 3; ++k) { a.q.min[k] = clip ? clip->min[k] : INT32_MIN; a.q.max[k] = clip ? clip->max[k] : INT32_MAX; }
     if (n == 0 || box_empty(a.q)) return PCR_OK;
     int rc;
@@ -2431,70 +2470,105 @@ int denoise_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, co
     int axis = 0;
     switch (noise_lattice(vox.origin, vox.cell, q.min, q.max, &a.lat, &axis)) {
     case THIN_LATTICE_EXTENT:
-        return set_err(c, PCR_E_ARG, "the points to denoise span %lld on axis %d, 2^31 or more: pass a clip or a larger cell (a tail artefact far outside the cloud?)",
-                       (long long)q.max[axis] - (long long)q.min[axis], axis);
+        return set_err(c, PCR_E_ARG, "the points to %s span %lld on axis %d, 2^31 or more: pass a clip or a larger cell (a tail artefact far outside the cloud?)",
+                       verb, (long long)q.max[axis] - (long long)q.min[axis], axis);
     case THIN_LATTICE_VOXELS:
-        return set_err(c, PCR_E_ARG, "the points to denoise span %lld on axis %d, more than 2^21 - 2 voxels of %d: pass a clip or a larger cell (a tail artefact far outside the cloud?)",
-                       (long long)q.max[axis] - (long long)q.min[axis], axis, vox.cell);
+        return set_err(c, PCR_E_ARG, "the points to %s span %lld on axis %d, more than 2^21 - 2 voxels of %d: pass a clip or a larger cell (a tail artefact far outside the cloud?)",
+                       verb, (long long)q.max[axis] - (long long)q.min[axis], axis, vox.cell);
     default: break;
     }
-    st.batches_outside = n - nL; st.batches_decoded = nL;
+    v.batches_outside = n - nL; v.batches_decoded = nL; v.nL = nL;
     if ((rc = thin_reserve(c, nL, n))) return rc;
-    if (!c->d_denoise_counters && hipMalloc((void **)&c->d_denoise_counters, 16) != hipSuccess)
-        return set_err(c, PCR_E_NOMEM, "out of device memory for two words");
 
     a.first_batch = (uint32_t)first;
     const StreamView s = make_stream_view(c);
     const dim3 grid((unsigned)nL), block(PCR_WORKGROUP_SIZE);
-    const bool windows = select_reads_windows(c);
+    v.windows = select_reads_windows(c);
     HIP_TRY(c, hipMemcpyAsync(c->d_thin_list, p.listed.data(), (size_t)nL * 4, hipMemcpyHostToDevice, c->stream));
-    if (windows) hipLaunchKernelGGL((k_thin_runs<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_thin_list, a, c->d_thin_totals);
-    else         hipLaunchKernelGGL((k_thin_runs<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_thin_list, a, c->d_thin_totals);
+    if (v.windows) hipLaunchKernelGGL((k_thin_runs<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_thin_list, a, c->d_thin_totals);
+    else           hipLaunchKernelGGL((k_thin_runs<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_thin_list, a, c->d_thin_totals);
     HIP_TRY(c, hipGetLastError());
-    std::vector<uint32_t> totals((size_t)nL * 2 + 1);
-    unsigned long long counters[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_thin_totals, (size_t)nL * 8, hipMemcpyDeviceToHost, c->stream));
+    v.totals.assign((size_t)nL * 2 + 1, 0u);
+    HIP_TRY(c, hipMemcpyAsync(v.totals.data(), c->d_thin_totals, (size_t)nL * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (int64_t k = 0; k < nL; ++k) { st.runs += totals[(size_t)k * 2]; st.points_considered += totals[(size_t)k * 2 + 1]; }
-    if (st.runs == 0) return PCR_OK;
+    for (int64_t k = 0; k < nL; ++k) { v.runs += v.totals[(size_t)k * 2]; v.points_considered += v.totals[(size_t)k * 2 + 1]; }
+    if (v.runs == 0) return PCR_OK;
 
     uint32_t log2_slots = 10;
-    while (((int64_t)1 << log2_slots) < 2 * st.runs) ++log2_slots;
+    while (((int64_t)1 << log2_slots) < 2 * v.runs) ++log2_slots;
     const int64_t slots = (int64_t)1 << log2_slots;
+    if (log2_slots > max_log2_slots)
+        return set_err(c, PCR_E_NOMEM, "a voxel table of %lld slots (%lld runs) is more than the 2^%u this call can index: pass a clip or a larger cell",
+                       (long long)slots, (long long)v.runs, max_log2_slots);
     if (!thin_grow((void **)&c->d_thin_table, c->thin_slots, slots, sizeof(ThinSlot)))
         return set_err(c, PCR_E_NOMEM, "out of device memory for a voxel table of %lld slots (%lld runs): pass a clip or a larger cell", (long long)slots,
-                       (long long)st.runs);
-    st.table_slots = slots;
+                       (long long)v.runs);
+    v.table_slots = slots;
     a.log2_slots = log2_slots; a.table = c->d_thin_table; a.error = c->d_thin_error;
-    d.max_count = (unsigned long long)max_count; d.counters = c->d_denoise_counters;
-    const dim3 per_slot((unsigned)std::min<int64_t>((slots + 255) / 256, 4096));
-    hipLaunchKernelGGL(k_denoise_clear, per_slot, dim3(256), 0, c->stream, c->d_thin_table, (unsigned long long)slots);
+    hipLaunchKernelGGL(k_denoise_clear, dim3((unsigned)std::min<int64_t>((slots + 255) / 256, 4096)), dim3(256), 0, c->stream, c->d_thin_table,
+                       (unsigned long long)slots);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemsetAsync(c->d_thin_error, 0, 4, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_denoise_counters, 0, 16, c->stream));
-    if (windows) hipLaunchKernelGGL((k_denoise_count<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_thin_list, a);
-    else         hipLaunchKernelGGL((k_denoise_count<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_thin_list, a);
-    HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(k_denoise_verdict, per_slot, dim3(256), 0, c->stream, d);
-    HIP_TRY(c, hipGetLastError());
+    return PCR_OK;
+}
+
+// The second half, after the call's own kernels have left their verdict in bit 63 of every occupied slot's value: flag the rows
+// on `mode`'s side of it (PCR_DENOISE_KEEP: bit clear), count them per batch, fill the plan thin_emit takes (p.st is not used) and
+// v.points_written, and copy `bytes` of the call's device counters `src` to `dst` on the way. Synchronises.
+int voxel_plan_finish(pcr_ctx *c, int64_t first, int mode, ThinPlan &p, VoxelPlan &v, void *dst, const void *src, size_t bytes)
+{
+    const int64_t nL = v.nL;
+    const ThinArgs &a = v.a;
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)nL), block(PCR_WORKGROUP_SIZE);
     // (every lane of a listed batch stores its keep word, and only listed batches are read: the bitmap needs no clearing)
 #define PCR_LAUNCH(L, M) hipLaunchKernelGGL((k_denoise_flag<L, M>), grid, block, 0, c->stream, s, c->d_thin_list, a, c->d_thin_keep)
-    if (windows) { if (mode == PCR_DENOISE_ISOLATED) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, PCR_DENOISE_ISOLATED); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, PCR_DENOISE_KEEP); }
-    else         { if (mode == PCR_DENOISE_ISOLATED) PCR_LAUNCH(LAYOUT_WORDS, PCR_DENOISE_ISOLATED); else PCR_LAUNCH(LAYOUT_WORDS, PCR_DENOISE_KEEP); }
+    if (v.windows) { if (mode == PCR_DENOISE_ISOLATED) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, PCR_DENOISE_ISOLATED); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, PCR_DENOISE_KEEP); }
+    else           { if (mode == PCR_DENOISE_ISOLATED) PCR_LAUNCH(LAYOUT_WORDS, PCR_DENOISE_ISOLATED); else PCR_LAUNCH(LAYOUT_WORDS, PCR_DENOISE_KEEP); }
 #undef PCR_LAUNCH
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(k_thin_totals, grid, dim3(256), 0, c->stream, c->d_thin_list, (uint32_t)first, c->d_thin_keep, c->d_thin_totals);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_thin_totals, (size_t)nL * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(totals.data() + nL * 2, c->d_thin_error, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(counters, c->d_denoise_counters, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(v.totals.data(), c->d_thin_totals, (size_t)nL * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(v.totals.data() + nL * 2, c->d_thin_error, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (totals[(size_t)nL * 2]) return set_err(c, PCR_E_NOMEM, "voxel table overflow: %lld slots for %lld runs", (long long)slots, (long long)st.runs);
+    if (v.totals[(size_t)nL * 2]) return set_err(c, PCR_E_NOMEM, "voxel table overflow: %lld slots for %lld runs", (long long)v.table_slots, (long long)v.runs);
     for (int64_t k = 0; k < nL; ++k) {
-        if (!totals[(size_t)k]) continue;
-        p.writers.push_back(p.listed[(size_t)k]); p.cnt.push_back(totals[(size_t)k]);
-        st.points_written += totals[(size_t)k];
+        if (!v.totals[(size_t)k]) continue;
+        p.writers.push_back(p.listed[(size_t)k]); p.cnt.push_back(v.totals[(size_t)k]);
+        v.points_written += v.totals[(size_t)k];
     }
+    return PCR_OK;
+}
+
+// pcr_thin's phases with a sum in the table: classify, count the runs, count the candidates per voxel, decide per voxel, flag the
+// rows to write and count them per batch. Fills the plan thin_emit takes (p.st is not used) and st. Synchronises.
+int denoise_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const pcr_box *clip, int64_t max_count, int mode, ThinPlan &p,
+                 pcr_denoise_stats &st)
+{
+    st = pcr_denoise_stats{};
+    VoxelPlan v;
+    int rc = voxel_plan_begin(c, first, n, vox, clip, "denoise", 62, p, v);
+    st.batches_outside = v.batches_outside; st.batches_decoded = v.batches_decoded; st.points_considered = v.points_considered; st.runs = v.runs;
+    if (rc || v.runs == 0) return rc;
+    if (!c->d_denoise_counters && hipMalloc((void **)&c->d_denoise_counters, 16) != hipSuccess)
+        return set_err(c, PCR_E_NOMEM, "out of device memory for two words");
+    st.table_slots = v.table_slots;
+    DenoiseArgs d{};
+    d.t = v.a; d.max_count = (unsigned long long)max_count; d.counters = c->d_denoise_counters;
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)v.nL), block(PCR_WORKGROUP_SIZE);
+    const dim3 per_slot((unsigned)std::min<int64_t>((v.table_slots + 255) / 256, 4096));
+    unsigned long long counters[2] = {0, 0};
+    HIP_TRY(c, hipMemsetAsync(c->d_denoise_counters, 0, 16, c->stream));
+    if (v.windows) hipLaunchKernelGGL((k_denoise_count<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_thin_list, v.a);
+    else           hipLaunchKernelGGL((k_denoise_count<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_thin_list, v.a);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(k_denoise_verdict, per_slot, dim3(256), 0, c->stream, d);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = voxel_plan_finish(c, first, mode, p, v, counters, c->d_denoise_counters, 16))) return rc;
+    st.points_written = v.points_written;
     st.voxels = (int64_t)counters[0]; st.voxels_isolated = (int64_t)counters[1];
     st.points_isolated = mode == PCR_DENOISE_ISOLATED ? st.points_written : st.points_considered - st.points_written;
     return PCR_OK;
@@ -2557,6 +2631,121 @@ int pcr_read_denoise(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_v
                              out_count, stats, &n, p, &done);
     if (rc || done) return rc;
     return thin_read_pieces(c, first_batch, n, p, host_points, host_rows);
+}
+
+// ---- connected components -----------------------------------------------------------------------
+namespace {
+// pcr_denoise's plan with a union-find between the counting and the flagging: count the candidates and the least row per voxel,
+// unite adjacent voxels, point every slot at its root and sum the sizes there, mark the slots of small components. Fills the plan
+// thin_emit takes, labels included, and st. Synchronises.
+int components_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const pcr_box *clip, int connectivity, int64_t min_points, int mode,
+                    ThinPlan &p, pcr_components_stats &st)
+{
+    st = pcr_components_stats{};
+    VoxelPlan v;
+    int rc = voxel_plan_begin(c, first, n, vox, clip, "label", 32, p, v);       // (the parent words are 32-bit)
+    st.batches_outside = v.batches_outside; st.batches_decoded = v.batches_decoded; st.points_considered = v.points_considered; st.runs = v.runs;
+    if (rc || v.runs == 0) return rc;
+    const int64_t slots = v.table_slots;
+    if (!thin_grow((void **)&c->d_components_scratch, c->components_slots, slots, 20))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the union-find over %lld slots (%lld runs): pass a clip or a larger cell", (long long)slots,
+                       (long long)v.runs);
+    if (!c->d_components_counters && hipMalloc((void **)&c->d_components_counters, 40) != hipSuccess)
+        return set_err(c, PCR_E_NOMEM, "out of device memory for five words");
+    st.table_slots = slots;
+    ComponentsArgs g{};
+    g.t = v.a;
+    g.min_row = reinterpret_cast<thin_u64 *>(c->d_components_scratch);
+    g.total = g.min_row + slots;
+    g.parent = reinterpret_cast<uint32_t *>(g.total + slots);
+    g.min_points = (unsigned long long)min_points; g.counters = c->d_components_counters; g.connectivity = connectivity;
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)v.nL), block(PCR_WORKGROUP_SIZE);
+    const dim3 per_slot((unsigned)std::min<int64_t>((slots + 255) / 256, 4096));
+    unsigned long long counters[5] = {0, 0, 0, 0, 0};
+    HIP_TRY(c, hipMemsetAsync(c->d_components_counters, 0, 40, c->stream));
+    hipLaunchKernelGGL(k_components_clear, per_slot, dim3(256), 0, c->stream, g);
+    HIP_TRY(c, hipGetLastError());
+    if (v.windows) hipLaunchKernelGGL((k_components_count<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_thin_list, v.a, g.min_row);
+    else           hipLaunchKernelGGL((k_components_count<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_thin_list, v.a, g.min_row);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(k_components_link, per_slot, dim3(256), 0, c->stream, g);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(k_components_flatten, per_slot, dim3(256), 0, c->stream, g);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(k_components_verdict, per_slot, dim3(256), 0, c->stream, g);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = voxel_plan_finish(c, first, mode == PCR_COMPONENTS_SMALL ? PCR_DENOISE_ISOLATED : PCR_DENOISE_KEEP, p, v, counters, c->d_components_counters, 40)))
+        return rc;
+    st.points_written = v.points_written;
+    st.voxels = (int64_t)counters[0]; st.components = (int64_t)counters[1]; st.components_small = (int64_t)counters[2];
+    st.points_small = (int64_t)counters[3]; st.largest_points = (int64_t)counters[4];
+    p.args = v.a; p.label = g.min_row;
+    return PCR_OK;
+}
+
+// The checks and the plan shared by pcr_components / pcr_read_components. *done: nothing left to write (an error, a count-only call, no records).
+int components_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int connectivity, int64_t min_points, int mode,
+                       const void *points, size_t points_align, const void *rows, const void *labels, size_t rows_align, size_t capacity, int64_t *out_count,
+                       pcr_components_stats *stats, int64_t *n, ThinPlan &p, bool *done)
+{
+    *done = true;
+    if (out_count) *out_count = 0;
+    int rc = select_range(c, first, count, n);
+    if (rc) return rc;
+    if (!vox) return set_err(c, PCR_E_ARG, "the voxel lattice is NULL");
+    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
+    if (points && reinterpret_cast<uintptr_t>(points) % points_align != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
+    if (rows && reinterpret_cast<uintptr_t>(rows) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the rows is misaligned (%zu bytes)", rows_align);
+    if (labels && reinterpret_cast<uintptr_t>(labels) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the labels is misaligned (%zu bytes)", rows_align);
+    if (vox->cell < 1 || vox->cell > PCR_THIN_MAX_CELL)
+        return set_err(c, PCR_E_ARG, "voxel cell of %d: the edge length is 1 .. %d (PCR_THIN_MAX_CELL)", vox->cell, PCR_THIN_MAX_CELL);
+    if (connectivity != 6 && connectivity != 26) return set_err(c, PCR_E_ARG, "connectivity is %d, not 6 or 26", connectivity);
+    if (min_points < 0) return set_err(c, PCR_E_ARG, "min_points is %lld: 0 or more", (long long)min_points);
+    if (mode != PCR_COMPONENTS_KEEP && mode != PCR_COMPONENTS_SMALL) return set_err(c, PCR_E_ARG, "mode is %d, not PCR_COMPONENTS_KEEP or PCR_COMPONENTS_SMALL", mode);
+    if (*n > ((int64_t)1 << 40) / PCR_POINTS_PER_BATCH) return set_err(c, PCR_E_ARG, "a range of %lld batches has more than 2^40 rows", (long long)*n);
+    pcr_components_stats st{};
+    if ((rc = components_plan(c, first, *n, *vox, clip, connectivity, min_points, mode, p, st))) return rc;
+    *out_count = st.points_written;
+    if (stats) *stats = st;
+    if ((!points && !rows && !labels) || st.points_written == 0) return PCR_OK;
+    if (capacity < (size_t)st.points_written)
+        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld to write", capacity, (long long)st.points_written);
+    *done = false;
+    return PCR_OK;
+}
+} // namespace
+
+int pcr_components(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int connectivity, int64_t min_points, int mode,
+                   void *dev_points, void *dev_rows, void *dev_labels, size_t capacity_points, int64_t *out_count, pcr_components_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = components_prepare(c, first_batch, count, vox, clip, connectivity, min_points, mode, dev_points, 16, dev_rows, dev_labels, 8, capacity_points,
+                                out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    if ((rc = thin_emit(c, first_batch, 0, n, p, static_cast<uint4 *>(dev_points), static_cast<int64_t *>(dev_rows), static_cast<int64_t *>(dev_labels))))
+        return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+int pcr_read_components(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int connectivity, int64_t min_points,
+                        int mode, pcr_point *host_points, int64_t *host_rows, int64_t *host_labels, size_t capacity_points, int64_t *out_count,
+                        pcr_components_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = components_prepare(c, first_batch, count, vox, clip, connectivity, min_points, mode, host_points, alignof(pcr_point), host_rows, host_labels,
+                                alignof(int64_t), capacity_points, out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    return thin_read_pieces(c, first_batch, n, p, host_points, host_rows, host_labels);
 }
 
 // ---- screen selection and picking --------------------------------------------------------------

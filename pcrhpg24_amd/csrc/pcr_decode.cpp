@@ -3,6 +3,7 @@
 //     pcr_decode <in.huffman> <out.las> [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --thin CELL [--center] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --denoise CELL MAXCOUNT [--isolated] [--box x0 y0 z0 x1 y1 z1]
+//     pcr_decode <in.huffman> <out.las> --components CELL MINPOINTS [--conn 6|26] [--small] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]
 //     pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1] [--rect x0 y0 x1 y1]
 //     pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]
@@ -14,6 +15,7 @@
 // an orthophoto and, with --dsm, a surface model. With --thin one point per cubic voxel is read back (pcr_read_thin): the cloud
 // decimated on the GPU without ever existing in full. With --polygon only the points inside a polygon prism of world coordinates are
 // read back (pcr_read_polygon). With --denoise the points come back without the isolated ones, or those alone (pcr_read_denoise).
+// With --components they come back without the connected components of voxels below a size, or those alone (pcr_read_components).
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -33,6 +35,7 @@ static const char *USAGE =
     "usage: pcr_decode <in.huffman> <out.las> [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --thin CELL [--center] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --denoise CELL MAXCOUNT [--isolated] [--box x0 y0 z0 x1 y1 z1]\n"
+    "       pcr_decode <in.huffman> <out.las> --components CELL MINPOINTS [--conn 6|26] [--small] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]\n"
     "       pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1]\n"
     "                                                [--rect x0 y0 x1 y1]\n"
@@ -53,6 +56,11 @@ static const char *USAGE =
     "  cubic voxels of CELL world units around its own (the lattice of --thin) hold at most MAXCOUNT points (a whole number >= 0),\n"
     "  the point itself and exact duplicates included. --isolated: the isolated points instead. Only the points inside --box\n"
     "  count, as neighbours too, or inside the box of the file's header. No point to write is an error.\n"
+    "  --components CELL MINPOINTS: the points without the small blobs, in the stream's order. The occupied cubic voxels of CELL\n"
+    "  world units (the lattice of --thin) that touch -- by a face, an edge or a corner, with --conn 6 by a face only -- form a\n"
+    "  connected component; it is small if it holds fewer than MINPOINTS points (a whole number >= 0), exact duplicates\n"
+    "  counted. --small: the points of the small components instead. Only the points inside --box count, or inside the box of\n"
+    "  the file's header. No point to write is an error.\n"
     "  --polygon FILE: only the points inside a polygon, selected on the GPU, in the stream's order. FILE is text in world\n"
     "  coordinates: one vertex `x y` per line, a blank line starts the next ring (a ring inside another is a hole: the even-odd\n"
     "  rule); a ring has at least 3 vertices and is closed implicitly, all rings together at most 4096. A vertex goes to the\n"
@@ -187,6 +195,42 @@ static bool parse_denoise(int argc, char **argv, int at, Denoise &d)
             d.has_box = true;
         } else if (a == "--isolated" && !d.isolated) {
             d.isolated = true;
+        } else {
+            return false;
+        }
+    }
+    return true;
+}
+
+struct Components {
+    double cell = 0.0;
+    long long min_points = 0;
+    int conn = 26;
+    bool small = false, has_box = false, has_conn = false;
+    double lo[3], hi[3];
+};
+
+// the options behind --components, every one well formed, or false
+static bool parse_components(int argc, char **argv, int at, Components &d)
+{
+    if (argc < at + 3 || std::strcmp(argv[at], "--components") != 0) return false;
+    if (!parse_double(argv[at + 1], d.cell) || !(d.cell > 0.0)) return false;
+    char *end = nullptr;
+    errno = 0;
+    d.min_points = std::strtoll(argv[at + 2], &end, 10);
+    if (end == argv[at + 2] || *end != '\0' || errno == ERANGE || d.min_points < 0) return false;
+    for (int i = at + 3; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--box" && i + 6 < argc && !d.has_box) {
+            for (int k = 0; k < 6; ++k) if (!parse_double(argv[++i], k < 3 ? d.lo[k] : d.hi[k - 3])) return false;
+            d.has_box = true;
+        } else if (a == "--conn" && i + 1 < argc && !d.has_conn) {
+            const std::string v = argv[++i];
+            if (v != "6" && v != "26") return false;
+            d.conn = v == "6" ? 6 : 26;
+            d.has_conn = true;
+        } else if (a == "--small" && !d.small) {
+            d.small = true;
         } else {
             return false;
         }
@@ -336,9 +380,12 @@ int main(int argc, char **argv)
     const bool polygoned = argc > 3 && std::strcmp(argv[3], "--polygon") == 0;
     Denoise noise;
     const bool denoised = argc > 3 && std::strcmp(argv[3], "--denoise") == 0;
-    const bool boxed = argc > 3 && !viewed && !orthoed && !thinned && !polygoned && !denoised;
+    Components comps;
+    const bool componented = argc > 3 && std::strcmp(argv[3], "--components") == 0;
+    const bool boxed = argc > 3 && !viewed && !orthoed && !thinned && !polygoned && !denoised && !componented;
     if (argc < 3 || (polygoned && !parse_polygon(argc, argv, 3, poly)) || (boxed && !parse_box(argc, argv, 3, lo, hi)) || (viewed && !parse_view(argc, argv, 3, view)) ||
-        (orthoed && !parse_ortho(argc, argv, 3, ortho)) || (thinned && !parse_thin(argc, argv, 3, thin)) || (denoised && !parse_denoise(argc, argv, 3, noise))) { std::fputs(USAGE, stderr); return 2; }
+        (orthoed && !parse_ortho(argc, argv, 3, ortho)) || (thinned && !parse_thin(argc, argv, 3, thin)) || (denoised && !parse_denoise(argc, argv, 3, noise)) ||
+        (componented && !parse_components(argc, argv, 3, comps))) { std::fputs(USAGE, stderr); return 2; }
     const std::string in = argv[1], out = argv[2];
     try {
         Renderer renderer(viewed ? view.w : 64, viewed ? view.h : 64, 0);
@@ -389,6 +436,16 @@ int main(int argc, char **argv)
                         vox.cell, (long long)st.batches_outside, (long long)st.batches_decoded, (long long)st.points_considered, (long long)st.runs,
                         (long long)st.voxels, (long long)st.voxels_isolated, (long long)st.points_isolated, (long long)st.points_written,
                         (long long)st.table_slots);
+            if (points.empty()) throw std::runtime_error("no points to write: nothing written");
+        } else if (componented) {
+            const pcr_voxels vox = voxelsFromWorld(info, comps.cell, info.min);
+            const pcr_box clip = boxFromWorld(info, comps.has_box ? comps.lo : info.min, comps.has_box ? comps.hi : info.max);
+            const pcr_components_stats st = las->components(vox, &clip, comps.conn, comps.min_points, comps.small ? PCR_COMPONENTS_SMALL : PCR_COMPONENTS_KEEP, points);
+            std::printf("components: cell of %d lattice steps, connectivity %d, batches outside %lld, decoded %lld, points considered %lld, runs %lld, "
+                        "voxels %lld, components %lld, small components %lld, small points %lld, largest %lld, written %lld, table slots %lld\n",
+                        vox.cell, comps.conn, (long long)st.batches_outside, (long long)st.batches_decoded, (long long)st.points_considered, (long long)st.runs,
+                        (long long)st.voxels, (long long)st.components, (long long)st.components_small, (long long)st.points_small,
+                        (long long)st.largest_points, (long long)st.points_written, (long long)st.table_slots);
             if (points.empty()) throw std::runtime_error("no points to write: nothing written");
         } else if (viewed) {
             renderer.yaw = view.cam[0]; renderer.pitch = view.cam[1]; renderer.radius = view.cam[2];

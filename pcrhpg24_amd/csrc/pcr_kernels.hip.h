@@ -20,6 +20,7 @@
 //   k_polygon_*     on request: the records inside a polygon prism, each straddling batch against its own edge list in LDS
 //   k_thin_*        on request: one record per voxel of a cubic lattice, straight from the compressed stream
 //   k_denoise_*     on request: the records whose 3 x 3 x 3 voxels hold few points (or the others), on k_thin_*'s frame
+//   k_components_*  on request: the connected components of the occupied voxels, the small ones dropped or extracted
 //   k_las_*         the 10-10-10 method (modules/compute_loop_las_cuda)
 //   k_resolve_*     framebuffer -> RGBA8 (resolve.cu:149-191, huffman_hqs/resolve.cu:2-47)
 //   k_merge_* / k_flip_sign  multi-GPU partial-framebuffer merges
@@ -2647,8 +2648,9 @@ __global__ void __launch_bounds__(256) k_denoise_clear(ThinSlot *table, thin_u64
     }
 }
 
-// thin_insert with a sum: the slot of the key, or the first free one from the key's home on, gets `count` added
-__device__ __forceinline__ void denoise_insert(const ThinArgs &a, thin_u64 key, thin_u64 count)
+// thin_insert with a sum: the slot of the key, or the first free one from the key's home on, gets `count` added. Returns the
+// slot's index, or THIN_EMPTY with the error word set.
+__device__ __forceinline__ thin_u64 denoise_insert_slot(const ThinArgs &a, thin_u64 key, thin_u64 count)
 {
     const thin_u64 slots = 1ull << a.log2_slots, mask = slots - 1;
     thin_u64 h = (key * THIN_HASH_MUL) >> (64u - a.log2_slots);
@@ -2658,11 +2660,17 @@ __device__ __forceinline__ void denoise_insert(const ThinArgs &a, thin_u64 key, 
         if (old == THIN_EMPTY) old = atomicCAS(&slot->key, THIN_EMPTY, key);
         if (old == THIN_EMPTY || old == key) {
             __hip_atomic_fetch_add(&slot->val, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (the result is not used)
-            return;
+            return h;
         }
         h = (h + 1) & mask;
     }
     *a.error = 1u;                                          // every slot holds another key: the host sized the table wrongly
+    return THIN_EMPTY;
+}
+
+__device__ __forceinline__ void denoise_insert(const ThinArgs &a, thin_u64 key, thin_u64 count)
+{
+    (void)denoise_insert_slot(a, key, count);
 }
 
 // The value of `key` in a table nobody inserts into any more (bit 63 included): from the key's home on to the key or an empty
@@ -2757,6 +2765,259 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_denoise_flag(StreamView 
         word |= write ? 1ull << (uint32_t)i : 0ull;
     });
     keep[(size_t)(b - a.first_batch) * PCR_WORKGROUP_SIZE + threadIdx.x] = word;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Connected components (pcr_components / pcr_read_components): the occupied voxels of pcr_denoise's table are the nodes of a
+// graph, two of them adjacent if they differ by at most 1 on every axis (26) or by exactly 1 on one axis (6); a component whose
+// voxels hold fewer than min_points candidates is small. pcr_denoise's frame and lattice with a union-find over the slots of the
+// table between the counting and the flagging. One launch each:
+//   k_thin_runs / k_denoise_clear (above), k_components_clear (min_row = all ones, total = 0, parent[i] = i).
+//   k_components_count    k_denoise_count that also takes the minimum of the run's first row into min_row[slot].
+//   k_components_link     a thread per slot: the forward half of the neighbourhood (13 of 26 keys, 3 of 6) looked up, every
+//                         neighbour found united with the slot (components_unite). The total order of the forest is the slot
+//                         index: a parent is always a lesser index than its child, so no cycle can form.
+//   k_components_flatten  a thread per slot: parent[i] = the root, the slot's count added to total[root], its least row taken
+//                         into min_row[root] by minimum: the root then holds the component's size and its label.
+//   k_components_verdict  a thread per slot: DENOISE_ISOLATED_BIT into the slot's value iff total[root] < min_points, min_row[i]
+//                         = min_row[root] (the label of every slot), and the counters of the statistics.
+//   k_denoise_flag / k_thin_totals / k_thin_write (above) flag, size and write; k_components_labels writes the labels of the
+//                         flagged rows in a colourless decode of its own (run -> slot -> label).
+// While a kernel changes parent[], every read of it is a relaxed atomic load at agent scope and every write an atomic (another
+// CU's L1 is never refreshed by a store: a plain re-read after a failed compare-and-swap could see "I am a root" forever).
+// Kernel boundaries on the one stream are the only other synchronisation; no workgroup waits for another one. Every loop is
+// bounded: a climb goes to a strictly lesser index with every step, at most `slots` of them; a union makes fewer than 4 * slots
+// rounds. A lane that runs out sets the error word and leaves. The result is exact and canonical: which slot is a root depends on
+// the table, but labels and sizes are minima and sums over the component, functions of the partition alone.
+// ------------------------------------------------------------------------------------------------
+struct ComponentsArgs {
+    ThinArgs t;                     // the clip, the shifted lattice, the first batch, the table and the error word
+    thin_u64 *min_row;              // [slots] the least row of the slot's voxel; at a root after k_components_flatten, everywhere after
+                                    // k_components_verdict: of its component
+    thin_u64 *total;                // [slots] at a root: the candidates of its component
+    uint32_t *parent;               // [slots] the forest over slot indices
+    thin_u64 min_points;            // small: total < min_points
+    thin_u64 *counters;             // [5] occupied slots, components, small ones, their candidates, the largest total
+    int32_t connectivity;           // 6 or 26
+};
+
+__global__ void __launch_bounds__(256) k_components_clear(ComponentsArgs a)
+{
+    const thin_u64 slots = 1ull << a.t.log2_slots;
+    for (thin_u64 i = (thin_u64)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (thin_u64)gridDim.x * blockDim.x) {
+        a.min_row[i] = THIN_EMPTY;
+        a.total[i] = 0ull;
+        a.parent[i] = (uint32_t)i;
+    }
+}
+
+template <int LAYOUT>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_components_count(StreamView s, const uint32_t *list, ThinArgs a, thin_u64 *min_row)
+{
+    const uint32_t b = list[blockIdx.x];
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    load_packed_table(s, b, s_table);
+    const thin_u64 row0 = (thin_u64)(b - a.first_batch) * PCR_POINTS_PER_BATCH + (thin_u64)threadIdx.x * PCR_POINTS_PER_THREAD;
+    thin_u64 prev = THIN_EMPTY, start = 0;
+    uint32_t len = 0;
+    auto insert = [&]() {
+        const thin_u64 slot = denoise_insert_slot(a, prev, len);
+        if (slot != THIN_EMPTY) __hip_atomic_fetch_min(&min_row[slot], start, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t) {
+        uint32_t d2;
+        const thin_u64 key = in_box(a.q, x, y, z) ? thin_key(a, x, y, z, d2) : THIN_EMPTY;
+        if (key == prev) {
+            ++len;
+        } else {
+            if (prev != THIN_EMPTY) insert();
+            prev = key; len = 1; start = row0 + (uint32_t)i;
+        }
+    });
+    if (prev != THIN_EMPTY) insert();
+}
+
+// The slot of `key` in a table nobody inserts into any more: from the key's home on to the key or an empty slot
+__device__ __forceinline__ bool components_lookup(const ThinSlot *table, uint32_t log2_slots, thin_u64 key, uint32_t &at)
+{
+    const thin_u64 slots = 1ull << log2_slots, mask = slots - 1;
+    thin_u64 h = (key * THIN_HASH_MUL) >> (64u - log2_slots);
+    for (thin_u64 probe = 0; probe < slots; ++probe) {
+        const thin_u64 k = table[h].key;
+        if (k == key) { at = (uint32_t)h; return true; }
+        if (k == THIN_EMPTY) return false;
+        h = (h + 1) & mask;
+    }
+    return false;
+}
+
+__device__ __forceinline__ uint32_t components_parent(const uint32_t *parent, uint32_t x)
+{
+    return __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// One tree out of the trees of x and y (Rem's algorithm with splicing, every step a compare-and-swap): of the two walkers the
+// one whose parent is the greater moves. If it stands on a root, the root goes under the other walker's parent and the union is
+// done; else its parent word is lowered to the other walker's parent -- a slot of the component this union forms, and a lesser
+// index than the old parent -- and it steps to the old parent. Both walkers under one parent: done, without a look at the root.
+// So lanes that unite inside a component that already hangs under one root read two parent words and leave the root's word
+// alone: a cloud that is one large component does not turn that word into the one address every lane waits for.
+// Every move takes a walker to a lesser index and a failed compare-and-swap on a root is followed by a move: fewer than
+// 4 * slots rounds.
+__device__ __forceinline__ void components_unite(const ComponentsArgs &a, uint32_t x, uint32_t y)
+{
+    const thin_u64 rounds = 4ull << a.t.log2_slots;
+    for (thin_u64 round = 0; round < rounds; ++round) {
+        uint32_t px = components_parent(a.parent, x), py = components_parent(a.parent, y);
+        if (px == py) return;
+        if (px < py) { uint32_t t = x; x = y; y = t; t = px; px = py; py = t; }     // x is the walker with the greater parent
+        if (px == x) {
+            if (atomicCAS(&a.parent[x], x, py) == x) return;
+            // x has been hooked by another lane in between: it is no root any more, the next round moves on from it
+        } else {
+            (void)atomicCAS(&a.parent[x], px, py);          // (whoever changed it first lowered it as well)
+            x = px;
+        }
+    }
+    *a.t.error = 1u;
+}
+
+__global__ void __launch_bounds__(256) k_components_link(ComponentsArgs a)
+{
+    const ThinSlot *table = a.t.table;
+    const thin_u64 slots = 1ull << a.t.log2_slots;
+    for (thin_u64 i = (thin_u64)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (thin_u64)gridDim.x * blockDim.x) {
+        const thin_u64 key = table[i].key;
+        if (key == THIN_EMPTY) continue;
+        // n = (dx + 1) + 3 (dy + 1) + 9 (dz + 1) above the centre's 13: every undirected edge once; with 6 the three axes only.
+        // Every index is in 1 .. 2^21 - 2 (noise_lattice), so no neighbour's key leaves its fields.
+        for (int n = 14; n < 27; ++n) {
+            if (a.connectivity == 6 && n != 14 && n != 16 && n != 22) continue;
+            const thin_u64 dx = (thin_u64)(n % 3), dy = (thin_u64)(n / 3 % 3), dz = (thin_u64)(n / 9);
+            const thin_u64 other = key + dx + (dy << THIN_KEY_BITS) + (dz << (2 * THIN_KEY_BITS)) - (1ull + (1ull << THIN_KEY_BITS) + (1ull << (2 * THIN_KEY_BITS)));
+            uint32_t at;
+            if (components_lookup(table, a.t.log2_slots, other, at)) components_unite(a, (uint32_t)i, at);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_components_flatten(ComponentsArgs a)
+{
+    const ThinSlot *table = a.t.table;
+    const thin_u64 slots = 1ull << a.t.log2_slots;
+    const thin_u64 stride = (thin_u64)gridDim.x * blockDim.x;
+    // (slots is a multiple of the stride or below it and the stride a multiple of 64: the lanes of a wave leave the loop together)
+    for (thin_u64 i = (thin_u64)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += stride) {
+        bool root = table[i].key != THIN_EMPTY;
+        const bool occupied = root;
+        // (the only store to parent[i] in this kernel is this lane's, so it is the root when the kernel ends; a lane that climbs
+        // through i meanwhile sees the old parent or the root, an ancestor either way)
+        uint32_t x = (uint32_t)i;
+        if (occupied) {
+            root = false;
+            for (thin_u64 step = 0; step < slots && !root; ++step) {
+                const uint32_t p = components_parent(a.parent, x);
+                root = p == x;
+                x = p;
+            }
+            if (!root) *a.t.error = 1u;
+        }
+        thin_u64 count = root ? table[i].val : 0ull, least = root ? a.min_row[i] : THIN_EMPTY;
+        if (root) __hip_atomic_store(&a.parent[i], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // the lanes of the wave that share the first such lane's root hand it their sums in one pair of atomics: in a cloud that
+        // is one large component every lane would queue at the same two words otherwise
+        const thin_u64 have = __ballot(root);
+        if (have == 0ull) continue;
+        const int lead = __ffsll((long long)have) - 1;
+        const bool shared = root && x == (uint32_t)__shfl((int)x, lead, 64);
+        thin_u64 sum = shared ? count : 0ull, low = shared ? least : THIN_EMPTY;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            sum += (thin_u64)__shfl_xor((long long)sum, d, 64);
+            low = min(low, (thin_u64)__shfl_xor((long long)low, d, 64));
+        }
+        if (shared ? (int)(threadIdx.x & 63u) == lead : root) {
+            __hip_atomic_fetch_add(&a.total[x], shared ? sum : count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_min(&a.min_row[x], shared ? low : least, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_components_verdict(ComponentsArgs a)
+{
+    ThinSlot *table = a.t.table;
+    const thin_u64 slots = 1ull << a.t.log2_slots;
+    uint32_t occupied = 0, roots = 0, small_roots = 0;
+    thin_u64 small_points = 0, largest = 0;
+    for (thin_u64 i = (thin_u64)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (thin_u64)gridDim.x * blockDim.x) {
+        if (table[i].key == THIN_EMPTY) continue;
+        const uint32_t r = a.parent[i];
+        const thin_u64 total = a.total[r];
+        const bool small = total < a.min_points;
+        ++occupied;
+        if (small) atomicOr(&table[i].val, DENOISE_ISOLATED_BIT);
+        if (r == (uint32_t)i) {
+            ++roots;
+            largest = max(largest, total);
+            if (small) { ++small_roots; small_points += total; }
+        } else {
+            a.min_row[i] = a.min_row[r];                    // (a root's own min_row is written by nobody)
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        occupied += __shfl_xor(occupied, d, 64); roots += __shfl_xor(roots, d, 64); small_roots += __shfl_xor(small_roots, d, 64);
+        small_points += __shfl_xor(small_points, d, 64);
+        largest = max(largest, (thin_u64)__shfl_xor(largest, d, 64));
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        if (occupied) atomicAdd(&a.counters[0], (thin_u64)occupied);
+        if (roots) atomicAdd(&a.counters[1], (thin_u64)roots);
+        if (small_roots) atomicAdd(&a.counters[2], (thin_u64)small_roots);
+        if (small_points) atomicAdd(&a.counters[3], small_points);
+        if (largest) atomicMax(&a.counters[4], largest);
+    }
+}
+
+// k_thin_write's placement without the records: workgroup x takes list[x], a batch that writes a record; the label of every
+// flagged row goes to labels[offsets[x] ..], chain after chain. label[] is min_row after k_components_verdict.
+template <int LAYOUT>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_components_labels(StreamView s, const uint32_t *list, ThinArgs a, const thin_u64 *keep,
+                                                                          const int64_t *offsets, const thin_u64 *label, int64_t *labels)
+{
+    const uint32_t b = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint32_t s_part[LWC_WAVES];
+    const thin_u64 word = keep[(size_t)(b - a.first_batch) * PCR_WORKGROUP_SIZE + tid];
+    const uint32_t mine = (uint32_t)__popcll(word);
+    uint32_t incl = mine;                                   // inclusive prefix inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += up;
+    }
+    if (lane == 63) s_part[wave] = incl;
+    load_packed_table(s, b, s_table);                       // (its barrier publishes s_part as well)
+    uint32_t before = incl - mine;
+    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    int64_t dst = offsets[blockIdx.x] + before;
+    const int64_t end = dst + mine;                         // never past the bits of this chain's word
+    thin_u64 prev = THIN_EMPTY;
+    int64_t mark = -1;
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t) {
+        if (((word >> (uint32_t)i) & 1ull) && dst < end) {  // (a flagged row is a candidate: it has a key)
+            uint32_t d2, at;
+            const thin_u64 key = thin_key(a, x, y, z, d2);
+            if (key != prev) {
+                prev = key;
+                if (components_lookup(a.table, a.log2_slots, key, at)) mark = (int64_t)label[at];
+                else mark = -1;                             // (cannot happen: k_components_count inserted every run's key)
+            }
+            labels[dst] = mark;
+            ++dst;
+        }
+    });
 }
 
 // ------------------------------------------------------------------------------------------------

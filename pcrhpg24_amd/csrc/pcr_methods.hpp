@@ -373,6 +373,26 @@ struct HuffmanLasData : Resource {
         return st;
     }
 
+    // The points inside `clip` (NULL: everywhere) of the connected components of the occupied voxels of `vox` (adjacent: at most 1
+    // apart on every axis with connectivity 26, exactly 1 on one axis with 6) that hold at least min_points of them, or with
+    // PCR_COMPONENTS_SMALL those of the others, on the GPU straight from the compressed stream (pcr_read_components: a counting
+    // call, then the read). labels (may be NULL): per point the least row of its component. Not in the reference.
+    pcr_components_stats components(const pcr_voxels &vox, const pcr_box *clip, int connectivity, int64_t min_points, int mode, std::vector<pcr_point> &out,
+                                    std::vector<int64_t> *labels = nullptr)
+    {
+        if (!loadedOn) throw std::runtime_error("components: the resource is not loaded");
+        const int64_t nB = pcr_batches_resident(loadedOn->ctx);
+        int64_t n = 0;
+        pcr_components_stats st{};
+        loadedOn->check(pcr_read_components(loadedOn->ctx, 0, nB, &vox, clip, connectivity, min_points, mode, nullptr, nullptr, nullptr, 0, &n, &st),
+                        "pcr_read_components");
+        out.resize((size_t)n);
+        if (labels) labels->resize((size_t)n);
+        if (n) loadedOn->check(pcr_read_components(loadedOn->ctx, 0, nB, &vox, clip, connectivity, min_points, mode, out.data(), nullptr,
+                                                   labels ? labels->data() : nullptr, out.size(), &n, &st), "pcr_read_components");
+        return st;
+    }
+
     // The points a frame of camera `p` draws whose pixel lies in `rect` (NULL: the whole image), with where they land, selected on
     // the GPU (pcr_read_screen: a counting call, then the read). Either vector may be NULL. Not in the reference.
     pcr_screen_stats selectScreen(const pcr_render_params &p, const pcr_rect *rect, std::vector<pcr_point> *points, std::vector<pcr_screen_hit> *hits)

@@ -28,7 +28,7 @@ from typing import Iterator, Optional
 import numpy as np
 
 from . import _native as N
-from ._native import Box, DisplayOpts, EncodeStats, Grid, GridStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, DenoiseStats, ThinStats, Voxels, XyzBatch, c_i64, fb_elems
+from ._native import Box, DisplayOpts, EncodeStats, Grid, GridStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, ComponentsStats, DenoiseStats, ThinStats, Voxels, XyzBatch, c_i64, fb_elems
 
 POINTS_PER_BATCH = 65536
 ENCODED_PAD_WORDS = 1024
@@ -388,6 +388,15 @@ def denoise_mode(mode) -> int:
         if mode not in ("keep", "isolated"):
             raise ValueError(f'mode is "keep" or "isolated", not {mode!r}')
         return N.DENOISE_KEEP if mode == "keep" else N.DENOISE_ISOLATED
+    return int(mode)
+
+
+def components_mode(mode) -> int:
+    """PCR_COMPONENTS_KEEP / PCR_COMPONENTS_SMALL from "keep" / "small" (an integer passes through: the library checks it)."""
+    if isinstance(mode, str):
+        if mode not in ("keep", "small"):
+            raise ValueError(f'mode is "keep" or "small", not {mode!r}')
+        return N.COMPONENTS_KEEP if mode == "keep" else N.COMPONENTS_SMALL
     return int(mode)
 
 
@@ -953,6 +962,59 @@ class Context:
         self.denoise_stats = st.as_dict()
         return (pts, r) if rows else pts
 
+    # -- connected components (pcr_components / pcr_read_components) -----------------------------------------
+    def components(self, vox, min_points: int = 1, connectivity: int = 26, clip=None, mode="keep", first: int = 0, count: Optional[int] = None, out=None,
+                   rows: bool = False, labels: bool = False):
+        """The rows of batches [first, first + count) inside `clip` (as_box; None: everywhere) without those of the small connected
+        components (mode "keep") or those alone (mode "small"), straight from the compressed stream. The occupied voxels of `vox`
+        (as_voxels) are adjacent if they differ by at most 1 on every axis (connectivity 26) or by exactly 1 on one axis (6); a
+        component is small iff its voxels hold fewer than `min_points` rows of the range inside the clip. The label of a component
+        is the least of its rows. Results, `out`, rows=True and stream ordering as Context.denoise; labels=True appends an int64
+        tensor of the labels: points, (points, rows), (points, labels) or (points, rows, labels). What the last call did is in
+        self.components_stats."""
+        import torch
+        vox, clip, mode = as_voxels(vox), None if clip is None else as_box(clip), components_mode(mode)
+        cp = None if clip is None else C.byref(clip)
+        dev = torch.device("cuda", self.device)
+        cnt, st, nb = c_i64(), ComponentsStats(), -1 if count is None else count
+        if out is None:
+            self._chk(self.lib.pcr_components(self.h, first, nb, C.byref(vox), cp, connectivity, min_points, mode, None, None, None, 0, C.byref(cnt),
+                                              C.byref(st)), "pcr_components")
+            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
+        cap = out.numel() // 4
+        r = torch.empty(cap, dtype=torch.int64, device=dev) if rows else None
+        lab = torch.empty(cap, dtype=torch.int64, device=dev) if labels else None
+        torch.cuda.current_stream(dev).synchronize()
+        rc = self.lib.pcr_components(self.h, first, nb, C.byref(vox), cp, connectivity, min_points, mode, C.c_void_p(out.data_ptr() if cap else None),
+                                     C.c_void_p(r.data_ptr() if cap else None) if rows else None,
+                                     C.c_void_p(lab.data_ptr() if cap else None) if labels else None, cap, C.byref(cnt), C.byref(st))
+        self.components_stats = st.as_dict()
+        if rc:
+            self.components_stats["points_written"] = cnt.value
+        self._chk(rc, "pcr_components")
+        res = (out.view(-1, 4)[:cnt.value],) + ((r[:cnt.value],) if rows else ()) + ((lab[:cnt.value],) if labels else ())
+        return res if len(res) > 1 else res[0]
+
+    def read_components(self, vox, min_points: int = 1, connectivity: int = 26, clip=None, mode="keep", first: int = 0, count: Optional[int] = None,
+                        rows: bool = False, labels: bool = False):
+        """The same on the host, without torch: a numpy structured array of POINT_DTYPE, with rows=True / labels=True followed by
+        int64 arrays of the rows / the labels (pcr_read_components: a counting call, then the read; synchronises)."""
+        vox, clip, mode = as_voxels(vox), None if clip is None else as_box(clip), components_mode(mode)
+        cp = None if clip is None else C.byref(clip)
+        cnt, st, nb = c_i64(), ComponentsStats(), -1 if count is None else count
+        self._chk(self.lib.pcr_read_components(self.h, first, nb, C.byref(vox), cp, connectivity, min_points, mode, None, None, None, 0, C.byref(cnt),
+                                               C.byref(st)), "pcr_read_components")
+        pts, r, lab = np.empty(cnt.value, POINT_DTYPE), np.empty(cnt.value if rows else 0, ROW_DTYPE), np.empty(cnt.value if labels else 0, ROW_DTYPE)
+        if cnt.value:
+            self._chk(self.lib.pcr_read_components(self.h, first, nb, C.byref(vox), cp, connectivity, min_points, mode, pts.ctypes.data,
+                                                   r.ctypes.data if rows else None, lab.ctypes.data if labels else None, len(pts), C.byref(cnt),
+                                                   C.byref(st)), "pcr_read_components")
+        self.components_stats = st.as_dict()
+        res = (pts,) + ((r,) if rows else ()) + ((lab,) if labels else ())
+        return res if len(res) > 1 else res[0]
+
     # -- screen selection and picking (pcr_select_screen / pcr_read_screen / pcr_pick) ---------------------
     def select_screen(self, p: RenderParams, rect=None):
         """The points a frame of camera `p` draws (render_basic's cull, level of detail, precision and inside test) whose pixel lies
@@ -1392,6 +1454,28 @@ class HuffmanLasData(Resource):
             return pts
         so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
         return pts[:, :3].to(torch.float64) * so[0] + so[1], pts
+
+    def components(self, renderer: Renderer, cell_size: float, min_points: int = 1, connectivity: int = 26, lo=None, hi=None, small: bool = False,
+                   world: bool = True):
+        """The loaded resource split into the connected components of its occupied cubic voxels of `cell_size` (adjacent: at most 1
+        apart on every axis with connectivity 26, exactly 1 on one axis with 6), without the components of fewer than `min_points`
+        points or, with small=True, those alone; on the GPU and straight from the compressed stream (Context.components). Returns
+        what denoised() returns with the labels appended -- (xyz, points, labels), with world=False (points, labels) -- labels an
+        int64 tensor: per point the least row of its component, rows counted over the whole stream. cell_size, lo, hi and world
+        are as for denoised(): with world=True the clip defaults to the header's box."""
+        import torch
+        info = self.las_info()
+        if world:
+            vox = voxels_from_world(info, cell_size)
+            clip = box_from_world(info, tuple(info.min) if lo is None else lo, tuple(info.max) if hi is None else hi)
+        else:
+            vox = as_voxels((0, 0, 0, cell_size))
+            clip = None if lo is None and hi is None else as_box(((INT32_MIN,) * 3 if lo is None else lo, (INT32_MAX,) * 3 if hi is None else hi))
+        pts, lab = renderer.ctx.components(vox, min_points, connectivity, clip, "small" if small else "keep", labels=True)
+        if not world:
+            return pts, lab
+        so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
+        return pts[:, :3].to(torch.float64) * so[0] + so[1], pts, lab
 
     def las_info(self) -> LasInfo:
         """Scale, offset, min and max of the LAS file the stream was made from, as its first batch record carries them (the
