@@ -328,6 +328,62 @@ int pcr_grid_unpack(pcr_ctx *ctx, const pcr_grid *grid, const void *dev_words, i
 int pcr_read_grid(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_grid *grid, const pcr_box *clip,
                   uint64_t *host_top, uint64_t *host_bottom, uint32_t *host_count, uint32_t flags, pcr_grid_stats *stats);
 
+/* ---- ground model and heights above it: lasground + lasheight on the grid (no reference counterpart) ---------------------------
+ * pcr_ground_filter turns a lowest-point height plane (pcr_grid's bottom plane through pcr_grid_unpack) into a ground plane;
+ * pcr_select_height is pcr_select_box with a predicate that looks the record's cell up in such a plane. All integer, all exact.
+ *
+ * pcr_ground_filter: dev_lowest and dev_ground are int32[height * width] (4-byte aligned, index cx + cy * width as in
+ *   pcr_grid), dev_class uint8[height * width] or NULL. dev_ground must not be dev_lowest. Of *grid only width and height play
+ *   a part. With Z0 the input plane and EMPTY = PCR_GROUND_EMPTY:
+ *   1. A cell is empty iff Z0[c] == EMPTY (a real z == INT32_MIN cannot be told from an empty cell, as after pcr_grid_unpack).
+ *   2. A = Z0, F = 0. W_r(c) = the cells within r of c on both axes that lie inside the grid.
+ *   3. For k = 0 .. num_steps - 1, r = radius[k], t = threshold[k]: E[c] = the minimum of A over the non-empty cells of W_r(c)
+ *      (EMPTY if there is none), O[c] = the maximum of E over the non-EMPTY cells of W_r(c) (likewise); for every non-empty c
+ *      (O[c] <= A[c] holds): F[c] = 1 if (int64)A[c] - O[c] > t; then A[c] = O[c]. Empty cells stay EMPTY in A.
+ *   4. Classes: empty -> PCR_CELL_EMPTY, F[c] -> PCR_CELL_NONGROUND, else PCR_CELL_GROUND. H[c] = Z0[c] for ground cells, EMPTY
+ *      for the others.
+ *   5. Fill, in Jacobi rounds that read the previous round's plane: every EMPTY cell with m >= 1 non-EMPTY cells among its 8
+ *      neighbours inside the grid takes floor(sum / m), the sum in 64 bits, the floor toward minus infinity. Rounds end when
+ *      fill_rounds have run, no cell is EMPTY, or a round fills nothing. dev_ground = H; unfilled cells stay EMPTY.
+ *   Heights from INT32_MIN + 1 to INT32_MAX are legal beside empties: the kernels carry "empty" as a flag in a wider word.
+ *   How: k_ground_morph is one separable pass (row or column, minimum or maximum, any radius up to 64) over a tile and its halo
+ *   in LDS, four launches a step; k_ground_flag compares and flags; k_ground_class writes classes, H and the class counts;
+ *   k_ground_fill is one round between two planes and counts what it filled and what stayed EMPTY; the host reads the two
+ *   counters back after every round, so the result does not depend on when it looks. Scratch: three int32 planes and a byte
+ *   plane in the scratch memory pcr_read_grid uses, grown on demand and released with the context. Synchronises. Needs no
+ *   stream loaded; touches no framebuffer, no prepass state, no render statistics. stats may be NULL.
+ *   PCR_E_ARG with a message, nothing written: a NULL grid, params, dev_lowest or dev_ground; width or height < 1 or more than
+ *   PCR_GRID_MAX_CELLS cells; num_steps outside 0 .. 16; fill_rounds outside 0 .. 4096; a radius outside 1 .. 64 or a negative
+ *   threshold for k < num_steps; dev_ground == dev_lowest; a misaligned plane.
+ * pcr_read_ground: pcr_grid_clear + pcr_grid_accumulate (bottom plane only) + pcr_grid_unpack + pcr_ground_filter + copies to
+ *   the host, through the same scratch memory. host_lowest / host_ground int32[height * width], host_class uint8; any may be
+ *   NULL. Range semantics and grid / clip checks are pcr_read_grid's.
+ *
+ * pcr_select_height: of the records pcr_decode_points would write for the range, a record is selected iff it lies inside *clip
+ *   (NULL: all), in a cell of *grid (pcr_grid's cell rule exactly), g = dev_ground[cell] != PCR_GROUND_EMPTY and
+ *   h_min <= h <= h_max with h = (int64)z - g compared in 64 bits, so a selected h fits int32. The records go to dev_points
+ *   (16-byte aligned), byte for byte, with PCR_HEIGHT_REPLACE_Z in flags the z field holding h; h goes to dev_heights (int32,
+ *   4-byte aligned); both in increasing row order, packed; either may be NULL, both NULL only counts. capacity counts records
+ *   of each; a capacity below the result: PCR_E_ARG, *out_count = the count needed, nothing written. h_min > h_max, an empty
+ *   clip or a range of 0 batches: 0 records, PCR_OK. BC1 and BC7, either layout, before and after the first frame.
+ *   A batch whose exact box (pcr_batch_point_bounds' cache) misses grid and clip intersected is outside and not decoded; every
+ *   other one is counted (k_height_count, colourless) and then written (k_height_write, with colours only when dev_points is
+ *   given). There is no "inside" class: the height test needs every record's cell. Synchronises. stats may be NULL.
+ *   PCR_E_ARG: pcr_select_box's refusals about range and destination, pcr_grid_accumulate's about the grid, a NULL dev_ground
+ *   or a misaligned one, unknown flag bits.
+ * pcr_read_height: the same into host memory (either pointer may be NULL); dev_ground is still a device plane. */
+int pcr_ground_filter(pcr_ctx *ctx, const pcr_grid *grid, const pcr_ground_params *gp, const void *dev_lowest, void *dev_ground,
+                      void *dev_class, pcr_ground_stats *stats);
+int pcr_read_ground(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_grid *grid, const pcr_box *clip,
+                    const pcr_ground_params *gp, int32_t *host_lowest, int32_t *host_ground, uint8_t *host_class,
+                    pcr_ground_stats *stats);
+int pcr_select_height(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_grid *grid, const void *dev_ground,
+                      const pcr_box *clip, int32_t h_min, int32_t h_max, uint32_t flags, void *dev_points, void *dev_heights,
+                      size_t capacity, int64_t *out_count, pcr_height_stats *stats);
+int pcr_read_height(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_grid *grid, const void *dev_ground,
+                    const pcr_box *clip, int32_t h_min, int32_t h_max, uint32_t flags, pcr_point *host_points, int32_t *host_heights,
+                    size_t capacity, int64_t *out_count, pcr_height_stats *stats);
+
 /* ---- voxel-grid thinning: one record per voxel, straight from the compressed stream (no reference counterpart) ----------------
  * The *rows* of a range are the records pcr_decode_points writes for it: row r = (b - first_batch) * 65536 + chain * 64 + i,
  * padding duplicates and the tail artefact included. A row inside *clip (bounds inclusive; NULL: every row) is a *candidate*;

@@ -192,6 +192,44 @@ typedef struct pcr_grid_stats {
     int64_t batches_outside, batches_windowed, batches_direct;
 } pcr_grid_stats;
 
+/* The ground filter over a lowest-point height plane of a grid (pcr_ground_filter): Zhang et al.'s progressive morphological
+ * filter, step k an opening (minimum, then maximum) of the running surface over the square window of radius[k] cells around
+ * each cell; a cell whose surface drops by more than threshold[k] in a step is not ground. pcr_hip.h has the exact definition.
+ * A cell is empty iff its height is PCR_GROUND_EMPTY, the value pcr_grid_unpack writes for a cell without points: a real
+ * z == INT32_MIN cannot be told from it. */
+#define PCR_GROUND_MAX_STEPS   16
+#define PCR_GROUND_MAX_RADIUS  64
+#define PCR_GROUND_MAX_FILL    4096
+#define PCR_GROUND_EMPTY       INT32_MIN
+#define PCR_CELL_EMPTY         0          /* classes of the input plane's cells */
+#define PCR_CELL_GROUND        1
+#define PCR_CELL_NONGROUND     2
+typedef struct pcr_ground_params {       /* 136 bytes */
+    int32_t num_steps;           /* 0 .. PCR_GROUND_MAX_STEPS; 0: no cell is flagged, the call only fills */
+    int32_t fill_rounds;         /* 0 .. PCR_GROUND_MAX_FILL: the most rounds of the hole fill */
+    int32_t radius[16];          /* cells, 1 .. PCR_GROUND_MAX_RADIUS for k < num_steps; the rest 0 */
+    int32_t threshold[16];       /* the stream's z units, >= 0 */
+} pcr_ground_params;
+
+/* What pcr_ground_filter found: the cells of the input plane by class, of the empty and non-ground ones those the fill gave a
+ * height and those it left PCR_GROUND_EMPTY, and the rounds of the fill that filled at least one cell. */
+typedef struct pcr_ground_stats {
+    int64_t cells_empty, cells_ground, cells_nonground;
+    int64_t cells_filled, cells_unfilled;
+    int64_t fill_rounds;
+} pcr_ground_stats;
+
+/* pcr_select_height: flags bit -- the z field of a written record holds its height above the ground plane instead of z. */
+#define PCR_HEIGHT_REPLACE_Z 1
+/* What pcr_select_height did: the batches of the range whose exact box misses grid and clip (not decoded) and the others (decoded
+ * twice: counted, then written), the records inside grid and clip whose cell has no ground (never selected), and the records
+ * selected, which is the call's *out_count. */
+typedef struct pcr_height_stats {
+    int64_t batches_outside, batches_decoded;
+    int64_t points_no_ground;
+    int64_t points_selected;
+} pcr_height_stats;
+
 /* A lattice of cubic voxels over the stream's int32 coordinates (pcr_thin, pcr_denoise, pcr_components), 16 bytes: a point (x, y, z) belongs to voxel
  * v[k] = floor((p[k] - origin[k]) / cell) on every axis, the difference and the division taken exactly (as 64-bit integers;
  * v may be negative). Every int32 point has a voxel: the lattice has no far edge. */

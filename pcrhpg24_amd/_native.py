@@ -97,6 +97,28 @@ class GridStats(C.Structure):                     # pcr_grid_stats
 GRID_MAX_CELLS, GRID_WINDOW_CELLS, GRID_NO_WINDOW, GRID_TOP, GRID_BOTTOM = 1 << 26, 4096, 1, 0, 1      # pcr_types.h
 
 
+class GroundParams(C.Structure):                  # pcr_ground_params: the steps of the ground filter and the rounds of its fill, 136 bytes
+    _fields_ = [("num_steps", c_i32), ("fill_rounds", c_i32), ("radius", c_i32 * 16), ("threshold", c_i32 * 16)]
+
+
+class GroundStats(C.Structure):                   # pcr_ground_stats
+    _fields_ = [(n, c_i64) for n in ("cells_empty", "cells_ground", "cells_nonground", "cells_filled", "cells_unfilled", "fill_rounds")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class HeightStats(C.Structure):                   # pcr_height_stats
+    _fields_ = [(n, c_i64) for n in ("batches_outside", "batches_decoded", "points_no_ground", "points_selected")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+GROUND_MAX_STEPS, GROUND_MAX_RADIUS, GROUND_MAX_FILL, GROUND_EMPTY = 16, 64, 4096, -(1 << 31)          # pcr_types.h
+CELL_EMPTY, CELL_GROUND, CELL_NONGROUND, HEIGHT_REPLACE_Z = 0, 1, 2, 1
+
+
 class Voxels(C.Structure):                        # pcr_voxels: a lattice of cubic voxels over the stream's int32 coordinates, 16 bytes
     _fields_ = [("origin", c_i32 * 3), ("cell", c_i32)]
 
@@ -165,6 +187,7 @@ assert C.sizeof(Polygon) == 40 and C.sizeof(PolygonStats) == 48
 assert C.sizeof(Rect) == 16 and C.sizeof(ScreenHit) == 16 and C.sizeof(ScreenStats) == 32
 assert C.sizeof(DisplayOpts) == 16
 assert C.sizeof(Grid) == 24 and C.sizeof(GridStats) == 24
+assert C.sizeof(GroundParams) == 136 and C.sizeof(GroundStats) == 48 and C.sizeof(HeightStats) == 32
 assert C.sizeof(Voxels) == 16 and C.sizeof(ThinStats) == 48 and C.sizeof(DenoiseStats) == 72 and C.sizeof(ComponentsStats) == 88
 assert C.sizeof(XyzBatch) == 64 and C.sizeof(GpuBatch) == 160 and C.sizeof(FileHeader) == 40 and C.sizeof(RenderParams) == 224
 
@@ -191,6 +214,7 @@ HIP_SYMBOLS = [
     "pcr_select_screen", "pcr_read_screen", "pcr_pick",
     "pcr_resolve_basic_display", "pcr_resolve_hqs_display", "pcr_resolve_las_display",
     "pcr_grid_clear", "pcr_grid_accumulate", "pcr_grid_unpack", "pcr_read_grid",
+    "pcr_ground_filter", "pcr_read_ground", "pcr_select_height", "pcr_read_height",
     "pcr_thin", "pcr_read_thin",
     "pcr_denoise", "pcr_read_denoise",
     "pcr_components", "pcr_read_components",
@@ -318,6 +342,12 @@ def hip_lib() -> C.CDLL:
             getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Grid), C.POINTER(Box), C.c_void_p, C.c_void_p, C.c_void_p, c_u32,
                                         C.POINTER(GridStats)]
         lib.pcr_grid_unpack.argtypes = [C.c_void_p, C.POINTER(Grid), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.pcr_ground_filter.argtypes = [C.c_void_p, C.POINTER(Grid), C.POINTER(GroundParams), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GroundStats)]
+        lib.pcr_read_ground.argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Grid), C.POINTER(Box), C.POINTER(GroundParams), C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.POINTER(GroundStats)]
+        for n in ("pcr_select_height", "pcr_read_height"):
+            getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Grid), C.c_void_p, C.POINTER(Box), c_i32, c_i32, c_u32, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.POINTER(c_i64), C.POINTER(HeightStats)]
         for n in ("pcr_thin", "pcr_read_thin"):
             getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Voxels), C.POINTER(Box), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.POINTER(c_i64), C.POINTER(ThinStats)]

@@ -2176,6 +2176,306 @@ int pcr_read_grid(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_grid
     return PCR_OK;
 }
 
+// ---- ground filter and heights -----------------------------------------------------------------
+namespace {
+constexpr size_t GROUND_COUNTER_WORDS = 4 + 2 * (size_t)PCR_GROUND_MAX_FILL;    // class counts, then two words per fill round
+
+size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// The filter's scratch for a grid of `cells` cells: three int32 planes, the counters, a byte plane.
+size_t ground_scratch_bytes(size_t cells) { return round_up(cells * 12, 8) + GROUND_COUNTER_WORDS * 8 + round_up(cells, 16); }
+
+// At least `bytes` of the scratch memory pcr_read_grid uses.
+int grid_scratch_reserve(pcr_ctx *c, size_t bytes)
+{
+    if (c->grid_scratch_bytes >= bytes) return PCR_OK;
+    dfree(c->d_grid_scratch); c->grid_scratch_bytes = 0;
+    if (hipMalloc((void **)&c->d_grid_scratch, bytes) != hipSuccess)
+        return set_err(c, PCR_E_NOMEM, "out of device memory for %zu bytes of grid planes", bytes);
+    c->grid_scratch_bytes = bytes;
+    return PCR_OK;
+}
+
+int ground_check(pcr_ctx *c, const pcr_grid *g, const pcr_ground_params *gp)
+{
+    if (!g) return set_err(c, PCR_E_ARG, "the grid is NULL");
+    if (g->width < 1 || g->height < 1) return set_err(c, PCR_E_ARG, "grid of %d x %d cells: width and height are at least 1", g->width, g->height);
+    if ((int64_t)g->width * g->height > PCR_GRID_MAX_CELLS)
+        return set_err(c, PCR_E_ARG, "grid of %d x %d cells: more than the %d of PCR_GRID_MAX_CELLS", g->width, g->height, PCR_GRID_MAX_CELLS);
+    if (!gp) return set_err(c, PCR_E_ARG, "the ground parameters are NULL");
+    if (gp->num_steps < 0 || gp->num_steps > PCR_GROUND_MAX_STEPS) return set_err(c, PCR_E_ARG, "num_steps is %d, not 0 .. %d", gp->num_steps, PCR_GROUND_MAX_STEPS);
+    if (gp->fill_rounds < 0 || gp->fill_rounds > PCR_GROUND_MAX_FILL) return set_err(c, PCR_E_ARG, "fill_rounds is %d, not 0 .. %d", gp->fill_rounds, PCR_GROUND_MAX_FILL);
+    for (int k = 0; k < gp->num_steps; ++k) {
+        if (gp->radius[k] < 1 || gp->radius[k] > PCR_GROUND_MAX_RADIUS)
+            return set_err(c, PCR_E_ARG, "radius[%d] is %d, not 1 .. %d", k, gp->radius[k], PCR_GROUND_MAX_RADIUS);
+        if (gp->threshold[k] < 0) return set_err(c, PCR_E_ARG, "threshold[%d] is %d: negative", k, gp->threshold[k]);
+    }
+    return PCR_OK;
+}
+
+// pcr_ground_filter behind its checks. `scratch` holds ground_scratch_bytes(cells). Synchronises.
+int ground_filter(pcr_ctx *c, const pcr_grid &g, const pcr_ground_params &gp, const int32_t *lowest, int32_t *ground, uint8_t *cls,
+                  unsigned char *scratch, pcr_ground_stats *stats)
+{
+    typedef unsigned long long u64;
+    const uint32_t W = (uint32_t)g.width, H = (uint32_t)g.height, n = W * H;
+    int32_t *A = reinterpret_cast<int32_t *>(scratch), *T1 = A + n, *T2 = T1 + n;
+    u64 *counters = reinterpret_cast<u64 *>(scratch + round_up((size_t)n * 12, 8));
+    uint8_t *flag = reinterpret_cast<uint8_t *>(counters + GROUND_COUNTER_WORDS);
+    const dim3 flat((n + 255) / 256), block(256);
+    HIP_TRY(c, hipMemsetAsync(counters, 0, GROUND_COUNTER_WORDS * 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(flag, 0, n, c->stream));
+    auto morph = [&](const int32_t *src, int32_t *dst, int r, bool column, bool is_max) {
+        const uint32_t na = column ? H : W, nc = column ? W : H;
+        const uint32_t ta = (na + GM_SPAN - 1) / GM_SPAN, tc = (nc + GM_LINES - 1) / GM_LINES;
+        const GroundMorphArgs a{src, dst, W, H, (uint32_t)r, column ? 1u : 0u, is_max ? 1u : 0u, ta};
+        hipLaunchKernelGGL(k_ground_morph, dim3(ta * tc), dim3(GM_THREADS), 0, c->stream, a);
+    };
+    for (int k = 0; k < gp.num_steps; ++k) {
+        const int32_t *a_in = k == 0 ? lowest : A;
+        const int r = gp.radius[k];
+        morph(a_in, T1, r, false, false); morph(T1, T2, r, true, false);        // E: the minimum over the square
+        morph(T2, T1, r, false, true); morph(T1, T2, r, true, true);            // O: the maximum of E over the square
+        hipLaunchKernelGGL(k_ground_flag, flat, block, 0, c->stream, lowest, a_in, T2, A, flag, gp.threshold[k], n);
+        HIP_TRY(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_ground_class, flat, block, 0, c->stream, lowest, flag, ground, cls, counters, n);
+    HIP_TRY(c, hipGetLastError());
+    u64 classes[3] = {0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(classes, counters, sizeof classes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    pcr_ground_stats st{(int64_t)classes[0], (int64_t)classes[1], (int64_t)classes[2], 0, (int64_t)(classes[0] + classes[2]), 0};
+    // the fill: rounds between `ground` and T1; the host learns after every round what it did, so nothing depends on when it looks
+    int32_t *cur = ground, *other = T1;
+    for (int round = 0; round < gp.fill_rounds && st.cells_unfilled > 0; ++round) {
+        u64 *rc = counters + 4 + 2 * (size_t)round, did[2] = {0, 0};
+        hipLaunchKernelGGL(k_ground_fill, flat, block, 0, c->stream, cur, other, W, H, rc);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(did, rc, sizeof did, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (did[0] == 0) break;                                                 // (`other` equals `cur`: the round changed nothing)
+        st.cells_filled += (int64_t)did[0]; st.cells_unfilled = (int64_t)did[1]; ++st.fill_rounds;
+        std::swap(cur, other);
+    }
+    if (cur != ground) {
+        HIP_TRY(c, hipMemcpyAsync(ground, cur, (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    if (stats) *stats = st;
+    return PCR_OK;
+}
+
+// grid and clip intersected into q (the far edges in 64 bits, as grid_accumulate); false: nothing is left
+bool grid_clip_box(const pcr_grid &g, const pcr_box *clip, pcr_box &q)
+{
+    const int64_t org[2] = {g.origin_x, g.origin_y}, ext[2] = {g.width, g.height};
+    bool empty = false;
+    for (int k = 0; k < 3; ++k) {
+        int64_t lo = clip ? clip->min[k] : INT32_MIN, hi = clip ? clip->max[k] : INT32_MAX;
+        if (k < 2) { lo = std::max(lo, org[k]); hi = std::min(hi, org[k] + (int64_t)g.cell * ext[k] - 1); }
+        empty = empty || lo > hi;
+        q.min[k] = (int32_t)lo; q.max[k] = (int32_t)hi;
+    }
+    return !empty;
+}
+
+// What a height selection over batches [first, first + n) has to write: the batches that are not outside (ascending; their
+// per-chain counts sit in c->d_sel_counts in the same order) and each one's record count.
+struct HeightPlan {
+    std::vector<uint32_t> listed;
+    std::vector<int64_t> cnt;
+    std::vector<int64_t> offsets;       // staging of k_height_write's offsets (alive until the stream has been synchronised)
+    HeightArgs a{};
+    pcr_height_stats st{};
+};
+
+// Classify (host, from the cached exact boxes) and count (k_height_count). Synchronises.
+int height_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_grid &g, const pcr_box *clip, HeightPlan &p)
+{
+    p.listed.clear(); p.cnt.clear();
+    p.st = pcr_height_stats{n, 0, 0, 0};
+    if (n == 0 || p.a.h_min > p.a.h_max || !grid_clip_box(g, clip, p.a.q)) return PCR_OK;
+    int rc;
+    if ((rc = ensure_point_bounds(c, first, n))) return rc;
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t *bb = c->h_point_bounds.data() + (first + i) * 6;
+        bool disjoint = false;
+        for (int k = 0; k < 3; ++k) disjoint = disjoint || bb[3 + k] < p.a.q.min[k] || bb[k] > p.a.q.max[k];
+        if (!disjoint) p.listed.push_back((uint32_t)(first + i));
+    }
+    const int64_t nL = (int64_t)p.listed.size();
+    p.st.batches_outside = n - nL; p.st.batches_decoded = nL;
+    p.cnt.assign((size_t)nL, 0);
+    if (nL == 0) return PCR_OK;
+    if ((rc = select_reserve(c, 2 * nL))) return rc;                            // (two totals per batch)
+    HIP_TRY(c, hipMemcpyAsync(c->d_sel_list, p.listed.data(), (size_t)nL * 4, hipMemcpyHostToDevice, c->stream));
+    p.a.ox = g.origin_x; p.a.oy = g.origin_y; p.a.width = (uint32_t)g.width;
+    p.a.div = make_cell_div((uint32_t)g.cell);
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)nL), block(PCR_WORKGROUP_SIZE);
+    if (select_reads_windows(c)) hipLaunchKernelGGL((k_height_count<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_sel_list, p.a, c->d_sel_counts, c->d_sel_totals);
+    else                         hipLaunchKernelGGL((k_height_count<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_sel_list, p.a, c->d_sel_counts, c->d_sel_totals);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint32_t> totals((size_t)nL * 2);
+    HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_sel_totals, (size_t)nL * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int64_t k = 0; k < nL; ++k) {
+        p.cnt[(size_t)k] = totals[(size_t)k * 2];
+        p.st.points_selected += totals[(size_t)k * 2]; p.st.points_no_ground += totals[(size_t)k * 2 + 1];
+    }
+    return PCR_OK;
+}
+
+// Enqueue the writes of listed batches [k0, k1) to points / heights (device, either may be NULL; record 0 = the first of batch k0).
+// The caller synchronises.
+int height_emit(pcr_ctx *c, HeightPlan &p, int64_t k0, int64_t k1, uint4 *points, int32_t *heights)
+{
+    p.offsets.clear();
+    int64_t off = 0;
+    for (int64_t k = k0; k < k1; ++k) { p.offsets.push_back(off); off += p.cnt[(size_t)k]; }
+    if (off == 0) return PCR_OK;
+    HIP_TRY(c, hipMemcpyAsync(c->d_sel_offsets + k0, p.offsets.data(), (size_t)(k1 - k0) * 8, hipMemcpyHostToDevice, c->stream));
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)(k1 - k0)), block(PCR_WORKGROUP_SIZE);
+    const int colour = !points ? SEL_NO_COLOUR : c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7 ? SEL_BC7 : SEL_BC1;
+#define PCR_LAUNCH(L, C) hipLaunchKernelGGL((k_height_write<L, C>), grid, block, 0, c->stream, s, c->d_sel_list + k0, p.a, \
+                                            c->d_sel_counts + k0 * PCR_WORKGROUP_SIZE, c->d_sel_offsets + k0, points, heights)
+#define PCR_LAUNCH_COLOUR(L) do { if (colour == SEL_BC7) PCR_LAUNCH(L, SEL_BC7); else if (colour == SEL_BC1) PCR_LAUNCH(L, SEL_BC1); else PCR_LAUNCH(L, SEL_NO_COLOUR); } while (0)
+    if (select_reads_windows(c)) PCR_LAUNCH_COLOUR(LAYOUT_POINT_WINDOWS); else PCR_LAUNCH_COLOUR(LAYOUT_WORDS);
+#undef PCR_LAUNCH_COLOUR
+#undef PCR_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    return PCR_OK;
+}
+
+// The checks and the plan shared by pcr_select_height / pcr_read_height. *done: nothing left to write.
+int height_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_grid *grid, const void *dev_ground, const pcr_box *clip, int32_t h_min,
+                   int32_t h_max, uint32_t flags, const void *points, const void *heights, size_t align_points, size_t capacity,
+                   int64_t *out_count, pcr_height_stats *stats, HeightPlan &p, bool *done)
+{
+    *done = true;
+    if (out_count) *out_count = 0;
+    int64_t n = 0;
+    int rc = select_range(c, first, count, &n);
+    if (rc) return rc;
+    if ((rc = grid_check(c, grid, nullptr, nullptr, nullptr))) return rc;
+    if (!dev_ground) return set_err(c, PCR_E_ARG, "the ground plane is NULL");
+    if (reinterpret_cast<uintptr_t>(dev_ground) % 4 != 0) return set_err(c, PCR_E_ARG, "the ground plane is misaligned (4 bytes)");
+    if (flags & ~(uint32_t)PCR_HEIGHT_REPLACE_Z) return set_err(c, PCR_E_ARG, "unknown flag bits 0x%x", flags & ~(uint32_t)PCR_HEIGHT_REPLACE_Z);
+    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
+    if (points && reinterpret_cast<uintptr_t>(points) % align_points != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", align_points);
+    if (heights && reinterpret_cast<uintptr_t>(heights) % 4 != 0) return set_err(c, PCR_E_ARG, "the destination of the heights is misaligned (4 bytes)");
+    p.a.ground = static_cast<const int32_t *>(dev_ground); p.a.h_min = h_min; p.a.h_max = h_max; p.a.replace_z = flags & PCR_HEIGHT_REPLACE_Z;
+    if ((rc = height_plan(c, first, n, *grid, clip, p))) return rc;
+    *out_count = p.st.points_selected;
+    if (stats) *stats = p.st;
+    if ((!points && !heights) || p.st.points_selected == 0) return PCR_OK;
+    if (capacity < (size_t)p.st.points_selected)
+        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld selected", capacity, (long long)p.st.points_selected);
+    *done = false;
+    return PCR_OK;
+}
+} // namespace
+
+int pcr_ground_filter(pcr_ctx *c, const pcr_grid *grid, const pcr_ground_params *gp, const void *dev_lowest, void *dev_ground, void *dev_class,
+                      pcr_ground_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ground_check(c, grid, gp))) return rc;
+    if (!dev_lowest || !dev_ground) return set_err(c, PCR_E_ARG, "the lowest / ground plane is NULL");
+    if (dev_lowest == dev_ground) return set_err(c, PCR_E_ARG, "dev_ground must not be dev_lowest");
+    if (reinterpret_cast<uintptr_t>(dev_lowest) % 4 != 0 || reinterpret_cast<uintptr_t>(dev_ground) % 4 != 0)
+        return set_err(c, PCR_E_ARG, "the lowest / ground plane is misaligned (4 bytes)");
+    const size_t cells = (size_t)grid->width * (size_t)grid->height;
+    if ((rc = grid_scratch_reserve(c, ground_scratch_bytes(cells)))) return rc;
+    return ground_filter(c, *grid, *gp, static_cast<const int32_t *>(dev_lowest), static_cast<int32_t *>(dev_ground), static_cast<uint8_t *>(dev_class),
+                         c->d_grid_scratch, stats);
+}
+
+int pcr_read_ground(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_grid *grid, const pcr_box *clip, const pcr_ground_params *gp,
+                    int32_t *host_lowest, int32_t *host_ground, uint8_t *host_class, pcr_ground_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int64_t n = 0;
+    int rc = select_range(c, first_batch, count, &n);
+    if (rc) return rc;
+    if ((rc = grid_check(c, grid, nullptr, nullptr, nullptr)) || (rc = ground_check(c, grid, gp))) return rc;
+    // the filter's scratch, then the bottom plane, the lowest and ground planes and the classes
+    const size_t cells = (size_t)grid->width * (size_t)grid->height, own = round_up(ground_scratch_bytes(cells), 16);
+    if ((rc = grid_scratch_reserve(c, own + cells * 8 + cells * 4 + cells * 4 + cells))) return rc;
+    unsigned char *const bottom = c->d_grid_scratch + own;
+    int32_t *const lowest = reinterpret_cast<int32_t *>(bottom + cells * 8), *const ground = lowest + cells;
+    uint8_t *const cls = reinterpret_cast<uint8_t *>(ground + cells);
+    grid_clear(c, *grid, nullptr, bottom, nullptr);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = grid_accumulate(c, first_batch, n, *grid, clip, nullptr, bottom, nullptr, 0, nullptr))) return rc;
+    hipLaunchKernelGGL(k_grid_unpack, dim3(std::min<uint32_t>(((uint32_t)cells + 255) / 256, 2048)), dim3(256), 0, c->stream,
+                       reinterpret_cast<const unsigned long long *>(bottom), ~0ull, lowest, static_cast<uint32_t *>(nullptr), (uint32_t)cells);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = ground_filter(c, *grid, *gp, lowest, ground, cls, c->d_grid_scratch, stats))) return rc;
+    if (host_lowest) HIP_TRY(c, hipMemcpyAsync(host_lowest, lowest, cells * 4, hipMemcpyDeviceToHost, c->stream));
+    if (host_ground) HIP_TRY(c, hipMemcpyAsync(host_ground, ground, cells * 4, hipMemcpyDeviceToHost, c->stream));
+    if (host_class) HIP_TRY(c, hipMemcpyAsync(host_class, cls, cells, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+int pcr_select_height(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_grid *grid, const void *dev_ground, const pcr_box *clip,
+                      int32_t h_min, int32_t h_max, uint32_t flags, void *dev_points, void *dev_heights, size_t capacity, int64_t *out_count,
+                      pcr_height_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HeightPlan p;
+    bool done = true;
+    int rc = height_prepare(c, first_batch, count, grid, dev_ground, clip, h_min, h_max, flags, dev_points, dev_heights, 16, capacity, out_count, stats, p, &done);
+    if (rc || done) return rc;
+    if ((rc = height_emit(c, p, 0, (int64_t)p.listed.size(), static_cast<uint4 *>(dev_points), static_cast<int32_t *>(dev_heights)))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+int pcr_read_height(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_grid *grid, const void *dev_ground, const pcr_box *clip,
+                    int32_t h_min, int32_t h_max, uint32_t flags, pcr_point *host_points, int32_t *host_heights, size_t capacity,
+                    int64_t *out_count, pcr_height_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HeightPlan p;
+    bool done = true;
+    int rc = height_prepare(c, first_batch, count, grid, dev_ground, clip, h_min, h_max, flags, host_points, host_heights, alignof(pcr_point), capacity,
+                            out_count, stats, p, &done);
+    if (rc || done) return rc;
+    // pieces of at most DECODE_STAGE_BATCHES / 2 listed batches: a piece's points fit the first half of the staging buffer, its
+    // heights the second (pcr_read_screen's scheme)
+    const int64_t nL = (int64_t)p.listed.size();
+    const int64_t piece = std::min<int64_t>(nL, DECODE_STAGE_BATCHES / 2);
+    if (!c->d_decode_stage || c->decode_stage_batches < 2 * piece) {
+        dfree(c->d_decode_stage); c->decode_stage_batches = 0;
+        if (hipMalloc((void **)&c->d_decode_stage, (size_t)(2 * piece) * PCR_POINTS_PER_BATCH * sizeof(pcr_point)) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of points", (long long)(2 * piece));
+        c->decode_stage_batches = 2 * piece;
+    }
+    uint4 *const d_points = reinterpret_cast<uint4 *>(c->d_decode_stage);
+    int32_t *const d_heights = reinterpret_cast<int32_t *>(d_points + (size_t)piece * PCR_POINTS_PER_BATCH);
+    int64_t written = 0;
+    for (int64_t k0 = 0; k0 < nL; k0 += piece) {
+        const int64_t k1 = std::min(nL, k0 + piece);
+        int64_t m = 0;
+        for (int64_t k = k0; k < k1; ++k) m += p.cnt[(size_t)k];
+        if (m == 0) continue;
+        if ((rc = height_emit(c, p, k0, k1, host_points ? d_points : nullptr, host_heights ? d_heights : nullptr))) return rc;
+        if (host_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
+        if (host_heights) HIP_TRY(c, hipMemcpyAsync(host_heights + written, d_heights, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        written += m;
+    }
+    return PCR_OK;
+}
+
 // ---- voxel thinning ----------------------------------------------------------------------------
 namespace {
 // What a thinning call over batches [first, first + n) has to write: the batches the clip does not miss, of those the ones that

@@ -7,6 +7,8 @@
 //     pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]
 //     pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1] [--rect x0 y0 x1 y1]
 //     pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]
+//     pcr_decode <in.huffman> <out.asc> --dtm CELL [--slope S] [--max-window W] [--initial D] [--max-distance D] [--box x0 y0 z0 x1 y1 z1]
+//     pcr_decode <in.huffman> <out.las> --height CELL LO HI [--normalize] [--slope S] [--max-window W] [--initial D] [--max-distance D] [--box ...]
 // Loads the file with the loader of the render tools (HuffmanLasData, csrc/pcr_methods.hpp), reads the points back in pieces of
 // 64 batches and writes LAS 1.2 / point format 2 (pcr_write_las_points). With --box only the points inside a box of world
 // coordinates are read back (pcr_read_box: batches the box misses are not decoded). With --view only the points a frame of that
@@ -16,6 +18,8 @@
 // decimated on the GPU without ever existing in full. With --polygon only the points inside a polygon prism of world coordinates are
 // read back (pcr_read_polygon). With --denoise the points come back without the isolated ones, or those alone (pcr_read_denoise).
 // With --components they come back without the connected components of voxels below a size, or those alone (pcr_read_components).
+// With --dtm the lowest-point grid goes through the ground filter on the GPU (pcr_read_ground) and the terrain model is written;
+// with --height the points whose height above that model lies in a range are read back (pcr_read_height).
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -40,6 +44,10 @@ static const char *USAGE =
     "       pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1]\n"
     "                                                [--rect x0 y0 x1 y1]\n"
     "       pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]\n"
+    "       pcr_decode <in.huffman> <out.asc> --dtm CELL [--slope S] [--max-window W] [--initial D] [--max-distance D]\n"
+    "                                                [--box x0 y0 z0 x1 y1 z1]\n"
+    "       pcr_decode <in.huffman> <out.las> --height CELL LO HI [--normalize] [--slope S] [--max-window W] [--initial D]\n"
+    "                                                [--max-distance D] [--box x0 y0 z0 x1 y1 z1]\n"
     "  Decodes every point of the stream on the GPU and writes a LAS 1.2 file (point format 2, 26-byte records).\n"
     "  A .huffman header stores the point count after padding only (a multiple of 65536: the encoder repeats the last\n"
     "  point), so the LAS file holds the padded count. Points come in the stream's order (Morton-sorted per chunk if the\n"
@@ -74,7 +82,16 @@ static const char *USAGE =
     "  number of the stream's x and y lattice steps) and the colour of the highest point of every cell is written as a binary\n"
     "  PPM (empty cells black), rows from north to south. The cells cover the x and y range of --box, of which z0 and z1 clip the\n"
     "  points, or the box of the file's header. --dsm: the height of that point as an ESRI ASCII grid (ncols, nrows, xllcorner,\n"
-    "  yllcorner, cellsize, NODATA_value -9999; world units, %.17g), the same rows. A grid no point falls into is an error.\n";
+    "  yllcorner, cellsize, NODATA_value -9999; world units, %.17g), the same rows. A grid no point falls into is an error.\n"
+    "  --dtm CELL: no LAS file; a terrain model as an ESRI ASCII grid like --dsm's. The lowest point of every cell of CELL world\n"
+    "  units goes through a progressive morphological filter on the GPU: windows of 3, 5, 9, ... cells up to --max-window world\n"
+    "  units (33), a cell being ground unless an opening lowers it by more than --initial (0.15) at the first window and\n"
+    "  min(--max-distance (2.5), --slope (1.0) * the growth of the window + --initial) at the others; the other cells and the\n"
+    "  empty ones take the mean of their 8 neighbours, round after round. The cells cover the x and y range of --box, of which\n"
+    "  z0 and z1 clip the points, or the box of the file's header. A grid without a ground cell is an error.\n"
+    "  --height CELL LO HI: the points whose height above that terrain model lies in LO .. HI world units (multiples of the z\n"
+    "  scale), in the stream's order; --normalize: their z is the height. Only the points inside --box count, or inside the box\n"
+    "  of the file's header. No point to write is an error.\n";
 
 static bool parse_double(const char *a, double &v)
 {
@@ -316,6 +333,93 @@ static bool parse_ortho(int argc, char **argv, int at, Ortho &o)
     return true;
 }
 
+struct Ground {
+    double cell = 0.0, h_lo = 0.0, h_hi = 0.0;
+    double slope = 1.0, max_window = 33.0, initial = 0.15, max_distance = 2.5;
+    bool heights = false, normalize = false, has_box = false;
+    bool seen[4] = {false, false, false, false};
+    double lo[3], hi[3];
+};
+
+// the options behind --dtm / --height, every one well formed, or false
+static bool parse_ground(int argc, char **argv, int at, Ground &g)
+{
+    if (argc < at + 2) return false;
+    g.heights = std::strcmp(argv[at], "--height") == 0;
+    if (!g.heights && std::strcmp(argv[at], "--dtm") != 0) return false;
+    if (!parse_double(argv[at + 1], g.cell) || !(g.cell > 0.0)) return false;
+    int i = at + 2;
+    if (g.heights) {
+        if (argc < at + 4 || !parse_double(argv[at + 2], g.h_lo) || !parse_double(argv[at + 3], g.h_hi)) return false;
+        i = at + 4;
+    }
+    static const char *names[4] = {"--slope", "--max-window", "--initial", "--max-distance"};
+    double *values[4] = {&g.slope, &g.max_window, &g.initial, &g.max_distance};
+    for (; i < argc; ++i) {
+        const std::string a = argv[i];
+        int k = 0;
+        while (k < 4 && a != names[k]) ++k;
+        if (k < 4 && i + 1 < argc && !g.seen[k]) {
+            if (!parse_double(argv[++i], *values[k]) || *values[k] < 0.0) return false;
+            g.seen[k] = true;
+        } else if (a == "--box" && i + 6 < argc && !g.has_box) {
+            for (int j = 0; j < 6; ++j) if (!parse_double(argv[++i], j < 3 ? g.lo[j] : g.hi[j - 3])) return false;
+            g.has_box = true;
+        } else if (a == "--normalize" && g.heights && !g.normalize) {
+            g.normalize = true;
+        } else {
+            return false;
+        }
+    }
+    return true;
+}
+
+// The ground model of the loaded resource over the x and y range of the box: the grid, the parameters and the ground plane.
+static pcr_ground_stats ground_model(HuffmanLasData &las, const pcr_las_info &info, const Ground &g, pcr_grid &grid, std::vector<int32_t> &ground)
+{
+    const double lo[2] = {g.has_box ? g.lo[0] : info.min[0], g.has_box ? g.lo[1] : info.min[1]};
+    const double hi[2] = {g.has_box ? g.hi[0] : info.max[0], g.has_box ? g.hi[1] : info.max[1]};
+    grid = gridFromWorld(info, lo, hi, g.cell);
+    const pcr_ground_params gp = groundParamsFromWorld(info, g.cell, g.slope, g.initial, g.max_distance, g.max_window);
+    pcr_box clip{};
+    if (g.has_box && !g.heights) {                          // (--height: the box clips the selection, the model sees every point over its cells)
+        const double inf = std::numeric_limits<double>::infinity();
+        const double l3[3] = {-inf, -inf, g.lo[2]}, h3[3] = {inf, inf, g.hi[2]};
+        clip = boxFromWorld(info, l3, h3);
+    }
+    const pcr_ground_stats st = las.groundModel(grid, g.has_box && !g.heights ? &clip : nullptr, gp, nullptr, &ground, nullptr);
+    std::printf("ground: %d x %d cells of %d lattice steps, %d steps up to radius %d, cells empty %lld, ground %lld, non-ground %lld, filled %lld in %lld rounds, "
+                "unfilled %lld\n", grid.width, grid.height, grid.cell, gp.num_steps, gp.radius[gp.num_steps - 1], (long long)st.cells_empty,
+                (long long)st.cells_ground, (long long)st.cells_nonground, (long long)st.cells_filled, (long long)st.fill_rounds, (long long)st.cells_unfilled);
+    if (!st.cells_ground) throw std::runtime_error("no ground cell inside the grid: nothing written");
+    return st;
+}
+
+// The terrain model (ESRI ASCII grid) of the loaded resource, rows from north to south, as write_ortho writes the surface model.
+static void write_dtm(HuffmanLasData &las, const pcr_las_info &info, const Ground &g, const std::string &asc)
+{
+    pcr_grid grid{};
+    std::vector<int32_t> ground;
+    ground_model(las, info, g, grid, ground);
+    FILE *f = std::fopen(asc.c_str(), "w");
+    if (!f) throw std::runtime_error(asc + ": cannot open for writing");
+    const double px = (double)grid.origin_x * info.scale[0], py = (double)grid.origin_y * info.scale[1];
+    std::fprintf(f, "ncols %d\nnrows %d\nxllcorner %.17g\nyllcorner %.17g\ncellsize %.17g\nNODATA_value -9999\n", grid.width, grid.height,
+                 px + info.offset[0], py + info.offset[1], g.cell);
+    size_t filled = 0;
+    for (int cy = grid.height - 1; cy >= 0; --cy) {
+        for (int cx = 0; cx < grid.width; ++cx) {
+            const int32_t z = ground[(size_t)cy * grid.width + cx];
+            const double pz = (double)z * info.scale[2];
+            if (z != PCR_GROUND_EMPTY) { std::fprintf(f, cx ? " %.17g" : "%.17g", pz + info.offset[2]); ++filled; }
+            else std::fputs(cx ? " -9999" : "-9999", f);
+        }
+        std::fputc('\n', f);
+    }
+    if (std::fclose(f) != 0) throw std::runtime_error(asc + ": write failed");
+    std::printf("cells %zu of %zu with a height -> %s\n", filled, ground.size(), asc.c_str());
+}
+
 // The orthophoto (binary PPM) and, with a path, the surface model (ESRI ASCII grid) of the loaded resource, rows from north to south.
 static void write_ortho(HuffmanLasData &las, const pcr_las_info &info, const Ortho &o, const std::string &ppm)
 {
@@ -382,10 +486,12 @@ int main(int argc, char **argv)
     const bool denoised = argc > 3 && std::strcmp(argv[3], "--denoise") == 0;
     Components comps;
     const bool componented = argc > 3 && std::strcmp(argv[3], "--components") == 0;
-    const bool boxed = argc > 3 && !viewed && !orthoed && !thinned && !polygoned && !denoised && !componented;
+    Ground ground;
+    const bool grounded = argc > 3 && (std::strcmp(argv[3], "--dtm") == 0 || std::strcmp(argv[3], "--height") == 0);
+    const bool boxed = argc > 3 && !viewed && !orthoed && !thinned && !polygoned && !denoised && !componented && !grounded;
     if (argc < 3 || (polygoned && !parse_polygon(argc, argv, 3, poly)) || (boxed && !parse_box(argc, argv, 3, lo, hi)) || (viewed && !parse_view(argc, argv, 3, view)) ||
         (orthoed && !parse_ortho(argc, argv, 3, ortho)) || (thinned && !parse_thin(argc, argv, 3, thin)) || (denoised && !parse_denoise(argc, argv, 3, noise)) ||
-        (componented && !parse_components(argc, argv, 3, comps))) { std::fputs(USAGE, stderr); return 2; }
+        (componented && !parse_components(argc, argv, 3, comps)) || (grounded && !parse_ground(argc, argv, 3, ground))) { std::fputs(USAGE, stderr); return 2; }
     const std::string in = argv[1], out = argv[2];
     try {
         Renderer renderer(viewed ? view.w : 64, viewed ? view.h : 64, 0);
@@ -407,7 +513,25 @@ int main(int argc, char **argv)
             las->unload(&renderer);
             return 0;
         }
-        if (boxed) {
+        if (grounded && !ground.heights) {
+            write_dtm(*las, info, ground, out);
+            las->unload(&renderer);
+            return 0;
+        }
+        if (grounded) {
+            pcr_grid grid{};
+            std::vector<int32_t> plane;
+            ground_model(*las, info, ground, grid, plane);
+            const pcr_box clip = boxFromWorld(info, ground.has_box ? ground.lo : info.min, ground.has_box ? ground.hi : info.max);
+            // heights are multiples of the z scale: the offset cancels
+            const double a = std::ceil(ground.h_lo / info.scale[2] - 1e-9), b = std::floor(ground.h_hi / info.scale[2] + 1e-9);
+            const int32_t h_min = (int32_t)std::max((double)INT32_MIN, std::min((double)INT32_MAX, a));
+            const int32_t h_max = (int32_t)std::max((double)INT32_MIN, std::min((double)INT32_MAX, b));
+            const pcr_height_stats st = las->pointsByHeight(grid, plane, &clip, h_min, h_max, ground.normalize ? PCR_HEIGHT_REPLACE_Z : 0u, points);
+            std::printf("height: %d .. %d z steps, batches outside %lld, decoded %lld, points without ground %lld, selected %lld\n", h_min, h_max,
+                        (long long)st.batches_outside, (long long)st.batches_decoded, (long long)st.points_no_ground, (long long)st.points_selected);
+            if (points.empty()) throw std::runtime_error("no points in the height range: nothing written");
+        } else if (boxed) {
             const pcr_select_stats st = las->selectBox(boxFromWorld(info, lo, hi), points);
             std::printf("box: batches outside %lld, inside %lld, straddling %lld\n", (long long)st.batches_outside, (long long)st.batches_inside,
                         (long long)st.batches_straddling);

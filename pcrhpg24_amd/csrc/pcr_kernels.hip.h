@@ -2444,6 +2444,271 @@ __global__ void __launch_bounds__(256) k_grid_unpack(const unsigned long long *w
 }
 
 // ------------------------------------------------------------------------------------------------
+// Ground filter (pcr_ground_filter): a progressive morphological filter over an int32 height plane, then a hole fill. The planes
+// in global memory are int32 with INT32_MIN for "empty"; no legal height has that value, and a minimum or maximum over non-empty
+// heights never produces it. Inside a kernel an empty cell is never compared as a height: k_ground_morph widens every cell to
+// 64 bits and gives the empty ones the identity of the pass (beyond every int32), k_ground_fill tests the flag value first.
+//   k_ground_morph  one separable pass of one step: minimum or maximum over 2 * r + 1 cells along a row or a column. A workgroup
+//                   takes a tile of GM_LINES lines x GM_SPAN outputs, loads it with r cells of halo at both ends into LDS
+//                   (8 bytes a cell), and widens the window by doubling: m_2c[i] = op(m_c[i], m_c[i + c]) while 2c <= w, then
+//                   out[i] = op(m_c[i], m_c[i + w - c]) -- about log2(w) rounds whatever the radius, each a read of every cell
+//                   into registers, a barrier, the write, a barrier. Rows: consecutive lanes along the row. Columns: consecutive
+//                   lanes across GM_LINES neighbouring columns, the LDS index transposed to match (no bank conflicts either way).
+//   k_ground_flag   per non-empty cell: the drop A - O of the step in 64 bits against the threshold, the flag, A = O.
+//   k_ground_class  classes, H (the input height of ground cells, empty otherwise) and the three class counts.
+//   k_ground_fill   one Jacobi round from one plane into another: an empty cell with m >= 1 non-empty neighbours of 8 takes
+//                   floor(sum / m); counts the cells it filled and the cells still empty.
+// Every loop is bounded by the tile; counters go out through one vector atomic per wave.
+// ------------------------------------------------------------------------------------------------
+constexpr int GM_THREADS = 256;
+constexpr int GM_LINES = 16;                                // lines of a tile (rows of a row pass, columns of a column pass)
+constexpr int GM_SPAN = 64;                                 // outputs per line of a tile
+constexpr int GM_MAX_LL = GM_SPAN + 2 * PCR_GROUND_MAX_RADIUS;      // a line with its halo
+constexpr int GM_EPT = GM_LINES * GM_MAX_LL / GM_THREADS;   // cells of the tile per thread
+static_assert(GM_LINES * GM_MAX_LL % GM_THREADS == 0, "whole cells per thread");
+constexpr long long GM_IDENTITY = 1ll << 40;                // beyond every int32: +GM_IDENTITY for a minimum, -GM_IDENTITY for a maximum
+
+struct GroundMorphArgs {
+    const int32_t *src;
+    int32_t *dst;
+    uint32_t width, height;
+    uint32_t radius;                // 1 .. PCR_GROUND_MAX_RADIUS
+    uint32_t column;                // 0: along rows, 1: along columns
+    uint32_t is_max;                // 0: minimum, 1: maximum
+    uint32_t tiles_along;           // tiles along the axis of the pass; blockIdx.x = tile across * tiles_along + tile along
+};
+
+__global__ void __launch_bounds__(GM_THREADS) k_ground_morph(GroundMorphArgs a)
+{
+    __shared__ long long s_m[GM_LINES * GM_MAX_LL];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t na = a.column ? a.height : a.width, nc = a.column ? a.width : a.height;      // cells along a line, lines
+    const size_t sa = a.column ? a.width : 1u, sc = a.column ? 1u : a.width;                    // strides in the plane
+    const uint32_t t_along = blockIdx.x % a.tiles_along, t_across = blockIdx.x / a.tiles_along;
+    const uint32_t r = min(a.radius, (uint32_t)PCR_GROUND_MAX_RADIUS), w = 2u * r + 1u;
+    const uint32_t ll = GM_SPAN + 2u * r, cells = GM_LINES * ll;                                // cells of the tile, <= GM_LINES * GM_MAX_LL
+    const uint32_t step = a.column ? GM_LINES : 1u;                                             // LDS distance of neighbours along the line
+    const long long identity = a.is_max ? -GM_IDENTITY : GM_IDENTITY;
+    const long long a0 = (long long)t_along * GM_SPAN - (long long)r;                           // position along the line of tile cell 0
+    const uint32_t c0 = t_across * GM_LINES;
+
+    uint32_t line[GM_EPT], pos[GM_EPT];
+#pragma unroll
+    for (int j = 0; j < GM_EPT; ++j) {
+        const uint32_t e = tid + (uint32_t)j * GM_THREADS;
+        line[j] = a.column ? e % GM_LINES : e / ll;
+        pos[j] = a.column ? e / GM_LINES : e % ll;
+        if (e < cells) {
+            const long long p = a0 + pos[j];
+            const uint32_t l = c0 + line[j];
+            long long v = identity;
+            if (p >= 0 && p < (long long)na && l < nc) {
+                const int32_t z = a.src[(size_t)p * sa + (size_t)l * sc];
+                if (z != INT32_MIN) v = z;
+            }
+            s_m[e] = v;
+        }
+    }
+    __syncthreads();
+    long long v[GM_EPT];
+    uint32_t c = 1;
+#pragma unroll 1
+    for (int round = 0; round < 8 && 2u * c <= w; ++round, c *= 2u) {          // w <= 129: at most 7 doublings
+#pragma unroll
+        for (int j = 0; j < GM_EPT; ++j) {
+            const uint32_t e = tid + (uint32_t)j * GM_THREADS;
+            if (e < cells) {
+                v[j] = s_m[e];
+                if (pos[j] + c < ll) { const long long o = s_m[e + c * step]; v[j] = a.is_max ? max(v[j], o) : min(v[j], o); }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < GM_EPT; ++j) {
+            const uint32_t e = tid + (uint32_t)j * GM_THREADS;
+            if (e < cells) s_m[e] = v[j];
+        }
+        __syncthreads();
+    }
+    const uint32_t d = w - c;                                                  // 0 <= d < c: the two windows of c cells cover w
+#pragma unroll
+    for (int j = 0; j < GM_EPT; ++j) {
+        const uint32_t e = tid + (uint32_t)j * GM_THREADS;
+        if (e >= cells || pos[j] >= (uint32_t)GM_SPAN) continue;
+        const long long p = (long long)t_along * GM_SPAN + pos[j];
+        const uint32_t l = c0 + line[j];
+        if (p >= (long long)na || l >= nc) continue;
+        const long long x = s_m[e], y = s_m[e + d * step];                     // pos + d <= GM_SPAN - 1 + 2r - ... < ll
+        const long long m = a.is_max ? max(x, y) : min(x, y);
+        a.dst[(size_t)p * sa + (size_t)l * sc] = m == identity ? INT32_MIN : (int32_t)m;
+    }
+}
+
+// One 64-bit add per wave of the sum of v over the workgroup's lanes that hold one
+__device__ __forceinline__ void ground_count(unsigned long long *counter, uint32_t v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    if ((threadIdx.x & 63u) == 0 && v) atomicAdd(counter, (unsigned long long)v);
+}
+
+// a_in: the surface before the step (the input plane at step 0), o: its opening, a_out: the surface after it
+__global__ void __launch_bounds__(256) k_ground_flag(const int32_t *z0, const int32_t *a_in, const int32_t *o, int32_t *a_out, uint8_t *flag,
+                                                     int32_t threshold, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    if (z0[i] == INT32_MIN) { a_out[i] = INT32_MIN; return; }
+    const int32_t av = a_in[i], ov = o[i];
+    if ((long long)av - (long long)ov > (long long)threshold) flag[i] = 1;
+    a_out[i] = ov;
+}
+
+// counters[0..2] += empty, ground, non-ground cells
+__global__ void __launch_bounds__(256) k_ground_class(const int32_t *z0, const uint8_t *flag, int32_t *h, uint8_t *cls, unsigned long long *counters, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    uint32_t k = 3;                                                            // past the grid: no class
+    if (i < n) {
+        const int32_t z = z0[i];
+        k = z == INT32_MIN ? PCR_CELL_EMPTY : flag[i] ? PCR_CELL_NONGROUND : PCR_CELL_GROUND;
+        h[i] = k == PCR_CELL_GROUND ? z : INT32_MIN;
+        if (cls) cls[i] = (uint8_t)k;
+    }
+    ground_count(counters + 0, k == PCR_CELL_EMPTY ? 1u : 0u);
+    ground_count(counters + 1, k == PCR_CELL_GROUND ? 1u : 0u);
+    ground_count(counters + 2, k == PCR_CELL_NONGROUND ? 1u : 0u);
+}
+
+// counters[0] += cells filled by this round, counters[1] += cells still empty after it
+__global__ void __launch_bounds__(256) k_ground_fill(const int32_t *src, int32_t *dst, uint32_t width, uint32_t height, unsigned long long *counters)
+{
+    const uint32_t n = width * height;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    uint32_t filled = 0, left = 0;
+    if (i < n) {
+        int32_t v = src[i];
+        if (v == INT32_MIN) {
+            const uint32_t cy = i / width, cx = i - cy * width;
+            long long sum = 0;
+            int m = 0;
+#pragma unroll
+            for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+                for (int dx = -1; dx <= 1; ++dx) {
+                    if (dx == 0 && dy == 0) continue;
+                    const long long x = (long long)cx + dx, y = (long long)cy + dy;
+                    if (x < 0 || y < 0 || x >= (long long)width || y >= (long long)height) continue;
+                    const int32_t g = src[(size_t)y * width + (size_t)x];
+                    if (g != INT32_MIN) { sum += g; ++m; }
+                }
+            }
+            if (m) {
+                long long q = sum / m;
+                if (sum % m != 0 && sum < 0) --q;                              // floor: toward minus infinity
+                v = (int32_t)q;                                                // a mean of int32 heights above INT32_MIN is one
+                filled = 1;
+            } else left = 1;
+        }
+        dst[i] = v;
+    }
+    ground_count(counters + 0, filled);
+    ground_count(counters + 1, left);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Heights above a ground plane (pcr_select_height): k_select_count / k_select_write with a gather as the predicate. A record
+// inside grid and clip intersected (a.q) has a cell -- k_grid's division -- whose ground height g is read from the plane; the
+// record is selected iff g is not empty and h_min <= z - g <= h_max in 64 bits. The count pass decodes no colours; the write pass
+// decodes them only when records are asked for.
+// ------------------------------------------------------------------------------------------------
+struct HeightArgs {
+    pcr_box q;                      // grid and clip intersected, not empty: a point inside has a cell
+    int32_t ox, oy;
+    CellDiv div;
+    uint32_t width;
+    const int32_t *ground;
+    int32_t h_min, h_max;
+    uint32_t replace_z;
+};
+
+// 0: not selected, 1: selected (h set), 2: inside grid and clip on a cell without ground
+__device__ __forceinline__ int height_test(const HeightArgs &a, int32_t x, int32_t y, int32_t z, int32_t &h)
+{
+    if (!in_box(a.q, x, y, z)) return 0;
+    const uint32_t cx = grid_div(a.div, (uint32_t)x - (uint32_t)a.ox), cy = grid_div(a.div, (uint32_t)y - (uint32_t)a.oy);
+    const int32_t g = a.ground[(size_t)cy * a.width + cx];
+    if (g == INT32_MIN) return 2;
+    const long long d = (long long)z - (long long)g;
+    if (d < (long long)a.h_min || d > (long long)a.h_max) return 0;
+    h = (int32_t)d;
+    return 1;
+}
+
+// Workgroup x takes list[x]: chain_counts[x * 1024 + chain] = the chain's selected points, totals[2x] = their sum, totals[2x + 1] =
+// the batch's points on cells without ground
+template <int LAYOUT>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_height_count(StreamView s, const uint32_t *list, HeightArgs a, uint32_t *chain_counts, uint32_t *totals)
+{
+    const uint32_t b = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint32_t s_part[LWC_WAVES][2];
+    load_packed_table(s, b, s_table);
+    uint32_t cnt = 0, bare = 0;
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t) {
+        int32_t h;
+        const int t = height_test(a, x, y, z, h);
+        cnt += t == 1 ? 1u : 0u; bare += t == 2 ? 1u : 0u;
+    });
+    chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid] = cnt;
+    uint32_t sum = cnt, sum2 = bare;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { sum += __shfl_xor(sum, d, 64); sum2 += __shfl_xor(sum2, d, 64); }
+    if (lane == 0) { s_part[wave][0] = sum; s_part[wave][1] = sum2; }
+    __syncthreads();
+    if (tid < 2) {
+        uint32_t t = 0;
+        for (int w = 0; w < LWC_WAVES; ++w) t += s_part[w][tid];
+        totals[(size_t)blockIdx.x * 2 + tid] = t;
+    }
+}
+
+// Workgroup x takes list[x]: its selected records go to points[offsets[x] ..] and their heights to heights[offsets[x] ..] (either
+// may be NULL; COLOUR is SEL_NO_COLOUR when points is), chain after chain, each chain's in point order. chain_counts is
+// k_height_count's for the same list and arguments.
+template <int LAYOUT, int COLOUR>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_height_write(StreamView s, const uint32_t *list, HeightArgs a, const uint32_t *chain_counts,
+                                                                     const int64_t *offsets, uint4 *points, int32_t *heights)
+{
+    const uint32_t b = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint32_t s_part[LWC_WAVES];
+    const uint32_t mine = chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid];
+    uint32_t incl = mine;                                   // inclusive prefix inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += up;
+    }
+    if (lane == 63) s_part[wave] = incl;
+    load_packed_table(s, b, s_table);                       // (its barrier publishes s_part as well)
+    uint32_t before = incl - mine;
+    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    const int64_t first = offsets[blockIdx.x] + before;
+    uint32_t k = 0;                                         // never past what k_height_count counted for this chain
+    decode_chain<LAYOUT, COLOUR>(s, b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        int32_t h;
+        if (height_test(a, x, y, z, h) == 1 && k < mine) {
+            if (COLOUR != SEL_NO_COLOUR && points) points[first + k] = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)(a.replace_z ? h : z), colour);
+            if (heights) heights[first + k] = h;
+            ++k;
+        }
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
 // Voxel-grid thinning (pcr_thin / pcr_read_thin): of the rows of a range inside a clip box, one per voxel of a cubic lattice --
 // the lowest row (PCR_THIN_FIRST) or the least by (distance to the voxel's centre, row) (PCR_THIN_CENTER). Four phases, each a
 // launch of its own over the batches the clip does not miss (`list`), the sizes in between computed by the host:

@@ -30,6 +30,8 @@
 #include <thread>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>
+
 #include "pcr_encode.h"
 #include "pcr_hip.h"
 #include "pcr_las_reader.hpp"
@@ -433,6 +435,50 @@ struct HuffmanLasData : Resource {
         return st;
     }
 
+    // The lowest-point plane of `grid` over every batch the context holds right now, its ground plane (the progressive morphological
+    // filter and hole fill of pcr_ground_filter) and the classes of its cells, on the GPU in one call (pcr_read_ground); clip may be
+    // NULL, a vector NULL leaves its plane out. Not in the reference.
+    pcr_ground_stats groundModel(const pcr_grid &grid, const pcr_box *clip, const pcr_ground_params &gp, std::vector<int32_t> *lowest,
+                                 std::vector<int32_t> *ground, std::vector<uint8_t> *classes)
+    {
+        if (!loadedOn) throw std::runtime_error("groundModel: the resource is not loaded");
+        const size_t cells = (size_t)std::max(grid.width, 0) * (size_t)std::max(grid.height, 0);
+        if (lowest) lowest->resize(cells);
+        if (ground) ground->resize(cells);
+        if (classes) classes->resize(cells);
+        pcr_ground_stats st{};
+        loadedOn->check(pcr_read_ground(loadedOn->ctx, 0, pcr_batches_resident(loadedOn->ctx), &grid, clip, &gp, lowest ? lowest->data() : nullptr,
+                                        ground ? ground->data() : nullptr, classes ? classes->data() : nullptr, &st), "pcr_read_ground");
+        return st;
+    }
+
+    // The points inside `clip` (NULL: everywhere) and the cells of `grid` whose height above `ground` (a plane of the grid's cells as
+    // groundModel returns it, PCR_GROUND_EMPTY: no ground) lies in h_min .. h_max, with PCR_HEIGHT_REPLACE_Z in flags their z
+    // replaced by the height, selected on the GPU (pcr_read_height: a counting call, then the read; the plane goes to the device for
+    // the call). heights may be NULL. Not in the reference.
+    pcr_height_stats pointsByHeight(const pcr_grid &grid, const std::vector<int32_t> &ground, const pcr_box *clip, int32_t h_min, int32_t h_max,
+                                    uint32_t flags, std::vector<pcr_point> &out, std::vector<int32_t> *heights = nullptr)
+    {
+        if (!loadedOn) throw std::runtime_error("pointsByHeight: the resource is not loaded");
+        const size_t cells = (size_t)std::max(grid.width, 0) * (size_t)std::max(grid.height, 0);
+        if (ground.size() < cells || cells == 0) throw std::runtime_error("pointsByHeight: the ground plane is smaller than the grid");
+        struct DevicePlane {
+            void *p = nullptr;
+            ~DevicePlane() { if (p) (void)hipFree(p); }
+        } d;
+        if (hipMalloc(&d.p, cells * sizeof(int32_t)) != hipSuccess || hipMemcpy(d.p, ground.data(), cells * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
+            throw std::runtime_error("pointsByHeight: no device memory for the ground plane");
+        const int64_t nB = pcr_batches_resident(loadedOn->ctx);
+        int64_t n = 0;
+        pcr_height_stats st{};
+        loadedOn->check(pcr_read_height(loadedOn->ctx, 0, nB, &grid, d.p, clip, h_min, h_max, flags, nullptr, nullptr, 0, &n, &st), "pcr_read_height");
+        out.resize((size_t)n);
+        if (heights) heights->resize((size_t)n);
+        if (n) loadedOn->check(pcr_read_height(loadedOn->ctx, 0, nB, &grid, d.p, clip, h_min, h_max, flags, out.data(), heights ? heights->data() : nullptr,
+                                               out.size(), &n, &st), "pcr_read_height");
+        return st;
+    }
+
     // Scale, offset and box of the LAS file the stream was made from, as the first batch record carries them
     // (include/BatchDumpData.h:60-107: doubles at 20 and 44, the LAS box as floats at 92 and 104).
     pcr_las_info lasInfo() const
@@ -581,6 +627,29 @@ inline pcr_grid gridFromWorld(const pcr_las_info &las, const double lo[2], const
     const int64_t w = ((int64_t)b.max[0] - b.min[0]) / cells[0] + 1, h = ((int64_t)b.max[1] - b.min[1]) / cells[0] + 1;
     if (w * h > PCR_GRID_MAX_CELLS) throw std::runtime_error("gridFromWorld: more cells than PCR_GRID_MAX_CELLS");
     return pcr_grid{b.min[0], b.min[1], (int32_t)cells[0], (int32_t)w, (int32_t)h, 0};
+}
+
+// Zhang et al.'s schedule for a ground filter over cells of `cell_size` world units: radii 1, 2, 4, ... cells while the window
+// (2 r + 1) * cell_size is at most max_window (at least one step, at most PCR_GROUND_MAX_STEPS, r <= PCR_GROUND_MAX_RADIUS); with w_k
+// the window of step k the thresholds are dh_0 = initial_distance, dh_k = min(max_distance, slope * (w_k - w_(k-1)) + initial_distance),
+// in the stream's z units nearbyint(dh_k / scale_z). The Python twin is host.ground_params_from_world.
+inline pcr_ground_params groundParamsFromWorld(const pcr_las_info &las, double cell_size, double slope = 1.0, double initial_distance = 0.15,
+                                               double max_distance = 2.5, double max_window = 33.0, int fill_rounds = PCR_GROUND_MAX_FILL)
+{
+    if (!(las.scale[2] > 0.0) || !(cell_size > 0.0)) throw std::runtime_error("groundParamsFromWorld: needs a positive z scale and a positive cell size");
+    pcr_ground_params gp{};
+    gp.fill_rounds = fill_rounds;
+    double prev = 0.0;
+    for (int r = 1; gp.num_steps < PCR_GROUND_MAX_STEPS && r <= PCR_GROUND_MAX_RADIUS; r *= 2) {
+        const double w = (2.0 * r + 1.0) * cell_size;
+        if (gp.num_steps > 0 && w > max_window) break;
+        const double dh = gp.num_steps == 0 ? initial_distance : std::min(max_distance, slope * (w - prev) + initial_distance);
+        gp.radius[gp.num_steps] = r;
+        gp.threshold[gp.num_steps] = (int32_t)std::min((double)INT32_MAX, std::max(0.0, std::nearbyint(dh / las.scale[2])));
+        ++gp.num_steps;
+        prev = w;
+    }
+    return gp;
 }
 
 // The lattice of cubic voxels of `cell_size` world units with the min corner of voxel (0, 0, 0) at the first lattice point at or above

@@ -28,7 +28,7 @@ from typing import Iterator, Optional
 import numpy as np
 
 from . import _native as N
-from ._native import Box, DisplayOpts, EncodeStats, Grid, GridStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, ComponentsStats, DenoiseStats, ThinStats, Voxels, XyzBatch, c_i64, fb_elems
+from ._native import Box, DisplayOpts, EncodeStats, Grid, GridStats, GroundStats, HeightStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, ComponentsStats, DenoiseStats, ThinStats, Voxels, XyzBatch, c_i64, fb_elems
 
 POINTS_PER_BATCH = 65536
 ENCODED_PAD_WORDS = 1024
@@ -359,6 +359,52 @@ def grid_from_world(las: LasInfo, lo_xy, hi_xy, cell_size: float) -> Grid:
     if w * h > N.GRID_MAX_CELLS:
         raise ValueError(f"{w} x {h} cells: more than the {N.GRID_MAX_CELLS} a grid may have")
     return Grid(int(box.min[0]), int(box.min[1]), cells[0], w, h, 0)
+
+
+class GroundParams(N.GroundParams):
+    """pcr_ground_params: step k of the ground filter opens the surface over the square window of radii[k] cells (1 .. 64) and
+    flags the cells it lowers by more than thresholds[k] (the stream's z units, >= 0); at most 16 steps, none: the call only
+    fills. fill_rounds (0 .. 4096): the most rounds of the hole fill. The native call checks the ranges."""
+
+    def __init__(self, radii=(), thresholds=(), fill_rounds: int = 4096):
+        super().__init__()
+        radii, thresholds = [int(r) for r in radii], [int(t) for t in thresholds]
+        if len(radii) != len(thresholds):
+            raise ValueError("one threshold per radius")
+        if any(v < INT32_MIN or v > INT32_MAX for v in radii + thresholds + [int(fill_rounds)]):
+            raise ValueError("ground parameters are int32")
+        self.num_steps, self.fill_rounds = len(radii), int(fill_rounds)
+        for k in range(min(len(radii), N.GROUND_MAX_STEPS)):    # (more than 16 steps: num_steps says so and the call refuses)
+            self.radius[k], self.threshold[k] = radii[k], thresholds[k]
+
+    @property
+    def radii(self):
+        return tuple(self.radius[:min(self.num_steps, N.GROUND_MAX_STEPS)])
+
+    @property
+    def thresholds(self):
+        return tuple(self.threshold[:min(self.num_steps, N.GROUND_MAX_STEPS)])
+
+
+def ground_params_from_world(las: LasInfo, cell_size: float, slope: float = 1.0, initial_distance: float = 0.15, max_distance: float = 2.5,
+                             max_window: float = 33.0, fill_rounds: int = 4096) -> GroundParams:
+    """Zhang et al.'s schedule for a grid of `cell_size` world units: radii 1, 2, 4, ... cells while the window (2 r + 1) *
+    cell_size is at most max_window (at least one step, at most 16, r <= 64); with w_k the window of step k in world units the
+    elevation thresholds are dh_0 = initial_distance and dh_k = min(max_distance, slope * (w_k - w_(k-1)) + initial_distance),
+    turned into the stream's z units by threshold_k = round(dh_k / scale_z)."""
+    sz = float(las.scale[2])
+    if not sz > 0.0 or not cell_size > 0.0:
+        raise ValueError("ground_params_from_world needs a positive z scale and a positive cell size")
+    radii = [1]
+    while len(radii) < N.GROUND_MAX_STEPS and 2 * radii[-1] <= N.GROUND_MAX_RADIUS and (4 * radii[-1] + 1) * cell_size <= max_window:
+        radii.append(2 * radii[-1])
+    thresholds, prev = [], None
+    for r in radii:
+        w = (2 * r + 1) * cell_size
+        dh = initial_distance if prev is None else min(max_distance, slope * (w - prev) + initial_distance)
+        thresholds.append(min(INT32_MAX, max(0, int(round(dh / sz)))))
+        prev = w
+    return GroundParams(radii, thresholds, fill_rounds)
 
 
 def as_voxels(vox) -> Voxels:
@@ -874,6 +920,106 @@ class Context:
                                          top.ctypes.data, bottom.ctypes.data, cnt.ctypes.data, flags, C.byref(st)), "pcr_read_grid")
         self.grid_stats = st.as_dict()
         return top, bottom, cnt
+
+    # -- ground model and heights (pcr_ground_filter / pcr_read_ground / pcr_select_height / pcr_read_height) ----------
+    def _int32_plane(self, t, cells: int, what: str, dtype=None):
+        import torch
+        dev = torch.device("cuda", self.device)
+        dtype = torch.int32 if dtype is None else dtype
+        if t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() < cells:
+            raise ValueError(f"{what} must be a contiguous {dtype} tensor of at least {cells} elements on {dev}")
+        return C.c_void_p(t.data_ptr())
+
+    def ground_filter(self, grid, params, lowest, ground=None, classes=None):
+        """The ground plane of a lowest-point height plane (pcr_ground_filter): `lowest` is a torch.int32 tensor of the cells of
+        `grid` (as_grid; only width and height matter), INT32_MIN = empty, as grid_unpack gives it for a bottom plane; `params`
+        a GroundParams. Returns (ground, classes): torch.int32 heights [height, width] -- the input height on ground cells, the
+        8-neighbour fill elsewhere, INT32_MIN where the fill did not reach -- and torch.uint8 classes (CELL_EMPTY / CELL_GROUND /
+        CELL_NONGROUND of the input). `ground` / `classes`: tensors to fill instead of new ones; classes=False: no classes
+        (None is returned for them). The counts of the call are in self.ground_stats. Stream ordering as decode_points."""
+        import torch
+        grid = as_grid(grid)
+        cells = grid.width * grid.height
+        dev = torch.device("cuda", self.device)
+        shape = (max(grid.height, 0), max(grid.width, 0))
+        if ground is None:
+            ground = torch.empty(shape, dtype=torch.int32, device=dev)
+        if classes is None:
+            classes = torch.empty(shape, dtype=torch.uint8, device=dev)
+        ptrs = [self._int32_plane(lowest, cells, "lowest"), self._int32_plane(ground, cells, "ground"),
+                None if classes is False else self._int32_plane(classes, cells, "classes", torch.uint8)]
+        st = GroundStats()
+        torch.cuda.current_stream(dev).synchronize()
+        self._chk(self.lib.pcr_ground_filter(self.h, C.byref(grid), C.byref(params), *ptrs, C.byref(st)), "pcr_ground_filter")
+        self.ground_stats = st.as_dict()
+        return ground, (None if classes is False else classes)
+
+    def read_ground(self, grid, params, clip=None, first: int = 0, count: Optional[int] = None):
+        """The lowest-point plane of `grid` over batches [first, first + count) inside `clip`, its ground plane and the classes on
+        the host, without torch (pcr_read_ground: clear, accumulate the bottom plane, unpack, filter, copy; synchronises): numpy
+        lowest and ground (int32) and classes (uint8), shaped [height, width]. The counts are in self.ground_stats."""
+        grid = as_grid(grid)
+        clip = None if clip is None else as_box(clip)
+        shape = (max(grid.height, 0), max(grid.width, 0))
+        lowest, ground, classes = np.empty(shape, np.int32), np.empty(shape, np.int32), np.empty(shape, np.uint8)
+        st = GroundStats()
+        self._chk(self.lib.pcr_read_ground(self.h, first, -1 if count is None else count, C.byref(grid), None if clip is None else C.byref(clip),
+                                           C.byref(params), lowest.ctypes.data, ground.ctypes.data, classes.ctypes.data, C.byref(st)), "pcr_read_ground")
+        self.ground_stats = st.as_dict()
+        return lowest, ground, classes
+
+    def select_height(self, grid, ground, h_min: int, h_max: int, clip=None, replace_z: bool = False, heights: bool = False, first: int = 0,
+                      count: Optional[int] = None, out=None, points: bool = True):
+        """The points of batches [first, first + count) inside `clip` and the cells of `grid` whose height h = z - ground[cell]
+        above the ground plane (a torch.int32 tensor of the grid's cells, INT32_MIN = no ground: never selected) lies in
+        h_min .. h_max, as a torch.int32 tensor [n, 4] as select_box gives it; replace_z: column 2 holds h. heights=True: (points,
+        h) with h a torch.int32 tensor [n]; points=False: h alone, or with neither the count. `out`: a tensor for the records,
+        as select_box takes it. The counts of the call are in self.height_stats. Stream ordering as decode_points."""
+        import torch
+        grid = as_grid(grid)
+        clip = None if clip is None else as_box(clip)
+        dev = torch.device("cuda", self.device)
+        gptr = self._int32_plane(ground, grid.width * grid.height, "ground")
+        cnt, st, nb = c_i64(), HeightStats(), -1 if count is None else count
+        flags = N.HEIGHT_REPLACE_Z if replace_z else 0
+        args = (self.h, first, nb, C.byref(grid), gptr, None if clip is None else C.byref(clip), int(h_min), int(h_max), flags)
+        torch.cuda.current_stream(dev).synchronize()
+        if out is None or not points:
+            self._chk(self.lib.pcr_select_height(*args, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_select_height")
+            self.height_stats = st.as_dict()
+            if not points and not heights:
+                return cnt.value
+            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev) if points else None
+        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
+        cap = out.numel() // 4 if points else cnt.value
+        hts = torch.empty((cap,), dtype=torch.int32, device=dev) if heights else None
+        rc = self.lib.pcr_select_height(*args, C.c_void_p(out.data_ptr() if out.numel() else None) if points else None,
+                                        C.c_void_p(hts.data_ptr() if hts.numel() else None) if heights else None, cap, C.byref(cnt), C.byref(st))
+        self.height_stats = st.as_dict()
+        if rc:
+            self.height_stats["points_selected"] = cnt.value
+        self._chk(rc, "pcr_select_height")
+        res = ((out.view(-1, 4)[:cnt.value],) if points else ()) + ((hts[:cnt.value],) if heights else ())
+        return res[0] if len(res) == 1 else res
+
+    def read_height(self, grid, ground, h_min: int, h_max: int, clip=None, replace_z: bool = False, heights: bool = False, first: int = 0,
+                    count: Optional[int] = None):
+        """The same on the host: a numpy structured array of POINT_DTYPE, with heights=True (points, h) with h an int32 array
+        (pcr_read_height: a counting call, then the read; synchronises). `ground` is a device plane: a torch.int32 tensor, or
+        the integer address of one."""
+        grid = as_grid(grid)
+        clip = None if clip is None else as_box(clip)
+        gptr = C.c_void_p(int(ground)) if isinstance(ground, int) else self._int32_plane(ground, grid.width * grid.height, "ground")
+        cnt, st, nb = c_i64(), HeightStats(), -1 if count is None else count
+        args = (self.h, first, nb, C.byref(grid), gptr, None if clip is None else C.byref(clip), int(h_min), int(h_max), N.HEIGHT_REPLACE_Z if replace_z else 0)
+        self._chk(self.lib.pcr_read_height(*args, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_read_height")
+        pts, hts = np.empty(cnt.value, POINT_DTYPE), np.empty(cnt.value if heights else 0, np.int32)
+        if cnt.value:
+            self._chk(self.lib.pcr_read_height(*args, pts.ctypes.data, hts.ctypes.data if heights else None, cnt.value, C.byref(cnt), C.byref(st)),
+                      "pcr_read_height")
+        self.height_stats = st.as_dict()
+        return (pts, hts) if heights else pts
 
     # -- voxel thinning (pcr_thin / pcr_read_thin) ----------------------------------------------------------
     def thin(self, vox, clip=None, mode="first", first: int = 0, count: Optional[int] = None, out=None, rows: bool = False):
@@ -1412,6 +1558,70 @@ class HuffmanLasData(Resource):
         height = z.to(torch.float64) * float(info.scale[2]) + float(info.offset[2])
         height[rgba == 0] = float("nan")
         return height, rgba.view(torch.uint8).view(grid.height, grid.width, 4), count, grid
+
+    def _ground_planes(self, renderer: Renderer, cell_size: float, lo_xy, hi_xy, pmf: dict):
+        """(grid, ground, classes): the ground filter over the lowest-point grid of the resource, int32 / uint8 tensors."""
+        import torch
+        info = self.las_info()
+        lo_xy = (info.min[0], info.min[1]) if lo_xy is None else lo_xy
+        hi_xy = (info.max[0], info.max[1]) if hi_xy is None else hi_xy
+        grid = grid_from_world(info, lo_xy, hi_xy, cell_size)
+        params = pmf.pop("params", None) or ground_params_from_world(info, cell_size, **pmf)
+        ctx = renderer.ctx
+        words = torch.empty((grid.height, grid.width), dtype=torch.int64, device=torch.device("cuda", ctx.device))
+        ctx.grid_clear(grid, bottom=words)
+        ctx.grid_accumulate(grid, bottom=words)
+        lowest, _ = ctx.grid_unpack(grid, words, N.GRID_BOTTOM)
+        ground, classes = ctx.ground_filter(grid, params, lowest)
+        return grid, ground, classes
+
+    def ground_model(self, renderer: Renderer, cell_size: float, lo_xy=None, hi_xy=None, **pmf):
+        """A terrain model of the loaded resource (Context.grid_accumulate's lowest-point grid through Context.ground_filter):
+        (height, classes, grid) over the cells of grid_from_world(las_info(), lo_xy, hi_xy, cell_size), lo_xy / hi_xy None:
+        las_info()'s min / max. height is a float64 tensor [h, w] = ground * scale + offset in world units, NaN where the fill
+        did not reach; classes a uint8 tensor [h, w] of CELL_EMPTY / CELL_GROUND / CELL_NONGROUND. Row 0 is the southern edge.
+        **pmf: ground_params_from_world's arguments (slope, initial_distance, max_distance, max_window, fill_rounds), or
+        params=GroundParams(...) in the stream's units."""
+        import torch
+        info = self.las_info()
+        grid, ground, classes = self._ground_planes(renderer, cell_size, lo_xy, hi_xy, dict(pmf))
+        height = ground.to(torch.float64) * float(info.scale[2]) + float(info.offset[2])
+        height[ground == INT32_MIN] = float("nan")
+        return height, classes, grid
+
+    def points_by_height(self, renderer: Renderer, cell_size: float, h_lo: float, h_hi: float, lo=None, hi=None, normalize: bool = False,
+                         world: bool = True, **pmf):
+        """The points of the loaded resource whose height above the ground model of `cell_size` cells lies in h_lo .. h_hi
+        (Context.select_height over ground_model's plane). lo / hi: a box to stay inside (None: las_info()'s min / max); the
+        ground model covers its x and y range. normalize: the z of the result is the height. world=True: h_lo / h_hi, lo / hi are
+        world units (heights are multiples of scale_z; the offset cancels) and the result is (xyz, pts, h) with xyz and h float64
+        tensors; world=False: h_lo / h_hi and lo / hi are the stream's integers, cell_size stays in world units, the result
+        (pts, h) with int32 tensors."""
+        import math
+        import torch
+        info = self.las_info()
+        sz = float(info.scale[2])
+        if world:
+            lo_w, hi_w = (tuple(info.min) if lo is None else lo), (tuple(info.max) if hi is None else hi)
+            clip = box_from_world(info, lo_w, hi_w)
+            lo_xy, hi_xy = lo_w[:2], hi_w[:2]
+            h_min = max(INT32_MIN, min(INT32_MAX, math.ceil(h_lo / sz - 1e-9)))
+            h_max = max(INT32_MIN, min(INT32_MAX, math.floor(h_hi / sz + 1e-9)))
+        else:
+            clip = None if lo is None and hi is None else as_box(((INT32_MIN,) * 3 if lo is None else lo, (INT32_MAX,) * 3 if hi is None else hi))
+            lo_xy = None if lo is None else tuple(float(lo[k]) * float(info.scale[k]) + float(info.offset[k]) for k in range(2))
+            hi_xy = None if hi is None else tuple(float(hi[k]) * float(info.scale[k]) + float(info.offset[k]) for k in range(2))
+            h_min, h_max = int(h_lo), int(h_hi)
+        grid, ground, _ = self._ground_planes(renderer, cell_size, lo_xy, hi_xy, dict(pmf))
+        pts, h = renderer.ctx.select_height(grid, ground, h_min, h_max, clip=clip, replace_z=normalize, heights=True)
+        if not world:
+            return pts, h
+        so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
+        xyz = pts[:, :3].to(torch.float64) * so[0] + so[1]
+        hw = h.to(torch.float64) * sz
+        if normalize:
+            xyz[:, 2] = hw
+        return xyz, pts, hw
 
     def thinned(self, renderer: Renderer, cell_size: float, lo=None, hi=None, mode: str = "first", world: bool = True):
         """The loaded resource thinned to one point per cubic voxel of `cell_size`, on the GPU and straight from the compressed
