@@ -496,6 +496,55 @@ int pcr_read_components(pcr_ctx *ctx, int64_t first_batch, int64_t count, const 
                         int64_t min_points, int mode, pcr_point *host_points, int64_t *host_rows, int64_t *host_labels,
                         size_t capacity_points, int64_t *out_count, pcr_components_stats *stats);
 
+/* ---- radius neighbourhoods: exact counts within a radius and nearest distances per point (no reference counterpart) -----------
+ * Rows and candidates are pcr_thin's: the records pcr_decode_points writes for the range that lie inside *clip (bounds inclusive;
+ * NULL: all of them), padding duplicates and the tail artefact included. For an integer radius r, 1 <= r <=
+ * PCR_NEIGHBORS_MAX_RADIUS stream units, and d2(p, q) the squared Euclidean distance of the integer coordinates in exact 64-bit
+ * arithmetic:
+ *   N(p)   = the number of candidates q of the call with d2(p, q) <= r * r. It counts p itself (N >= 1), exact duplicates and a
+ *            point at exactly distance r.
+ *   nn2(p) = the least d2(p, q) over the candidates q of another row with d2 <= r * r: 0 if an exact duplicate exists,
+ *            PCR_NN2_NONE (all ones) if there is no such q.
+ * CONTRACT: a candidate is sparse iff N(p) < min_count. min_count <= 1 makes nothing sparse, a huge one everything.
+ * PCR_NEIGHBORS_ALL writes every candidate, PCR_NEIGHBORS_KEEP those that are not sparse, PCR_NEIGHBORS_SPARSE the sparse ones:
+ * byte for byte the records pcr_decode_points writes to dev_points (16-byte aligned), their rows to dev_rows (int64), N to
+ * dev_counts (int64) and nn2 to dev_nn2 (uint64; each 8-byte aligned), all in increasing row order, packed without gaps. Any of
+ * the four may be NULL; with all four NULL the call only counts. The result is exact and the same from run to run: it depends on
+ * no lattice, hash, table size, bucket order or order of lanes, workgroups and launches. BC1 and BC7, either resident layout,
+ * before and after the first frame. Only candidates of this call's range and clip exist for the call: as with pcr_denoise, filter
+ * with a clip a little larger than the region wanted.
+ * (PDAL's filters.outlier with method=radius counts the OTHER points within the radius and drops a point with fewer than min_k of
+ * them, which would make min_count = min_k + 1 its equivalent; that reading of its documentation has not been checked against the
+ * tool. CloudCompare's noise filter and a statistical outlier filter start from the same N and nn2.)
+ *
+ * pcr_neighbors: capacity_points, *out_count, the count-only call, a capacity below the result (PCR_E_ARG, *out_count = the count
+ *   needed, nothing written), range semantics, the empty clip / empty range / clip that misses every batch (0 records, PCR_OK, no
+ *   kernel runs) and the synchronisation are pcr_denoise's, word for word. Touches no framebuffer, no prepass state, no render
+ *   statistics. stats may be NULL.
+ *   How: pcr_denoise's frame on the lattice with origin (0, 0, 0) and cell = r, whose 27 voxels around a point's own cover its
+ *   sphere, with the counts of the table turned into an index. k_thin_runs counts the runs, the host sizes the table,
+ *   k_neighbors_count sums the candidates per voxel and notes where every chain's runs start, k_neighbors_alloc hands every
+ *   occupied voxel a bucket and ceil(count / 64) work items, k_neighbors_fill copies the candidates into their buckets as {x, y,
+ *   z, row} (one atomic per run), k_neighbors_pairs gives every work item a wave -- a lane per centre, the 27 neighbour buckets
+ *   looked up once per chunk, laid end to end and broadcast through the wave in tiles of 64 -- and k_thin_totals / k_neighbors_write size and write
+ *   the output. With PCR_NEIGHBORS_KEEP / _SPARSE and dev_counts == dev_nn2 == NULL a wave stops once all its centres have
+ *   min_count neighbours; the outputs are the same either way.
+ *   Scratch, grown on demand and released with the context: pcr_thin's, 8 bytes per slot, 8 per chain, 16 per candidate, the work
+ *   list, and 8 bytes per row of the range for each of N and nn2 that is asked for.
+ *   COST: a voxel of m candidates costs m * m tests, and a stream's padding duplicates are such a voxel (tens of thousands of
+ *   copies of the last point: some 1e9 tests). stats.pairs_bound is the number of tests the call makes at most.
+ * pcr_read_neighbors: the same into host memory (alignof(pcr_point) / alignof(int64_t)), staged as pcr_read_thin stages.
+ * PCR_E_ARG with a message, nothing written: pcr_denoise's refusals, a radius outside 1 .. PCR_NEIGHBORS_MAX_RADIUS, min_count
+ * < 0, an unknown mode, a range of more than 2^32 rows (the index stores a 32-bit row), and a lattice too large for the key: with
+ * q as for pcr_thin the call is refused if on any axis q.max - q.min >= 2^31 or (q.max - q.min) / r + 4 > 2^21 -- pass a clip or
+ * a larger radius. PCR_E_NOMEM: a table of more than 2^32 slots. */
+int pcr_neighbors(pcr_ctx *ctx, int64_t first_batch, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count, int mode,
+                  void *dev_points, void *dev_rows, void *dev_counts, void *dev_nn2, size_t capacity_points, int64_t *out_count,
+                  pcr_neighbors_stats *stats);
+int pcr_read_neighbors(pcr_ctx *ctx, int64_t first_batch, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count,
+                       int mode, pcr_point *host_points, int64_t *host_rows, int64_t *host_counts, uint64_t *host_nn2,
+                       size_t capacity_points, int64_t *out_count, pcr_neighbors_stats *stats);
+
 /* What a collective library needs to merge partial frames in place (include/pcr_dist.h does it with RCCL): the HIP stream
  * the context enqueues on, its device ordinal and the length of each framebuffer in 64-bit words. */
 void *pcr_get_stream(pcr_ctx *ctx);

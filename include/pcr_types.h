@@ -298,6 +298,31 @@ typedef struct pcr_components_stats {
     int64_t table_slots;
 } pcr_components_stats;
 
+/* pcr_neighbors: N(p) = the candidates within `radius` of p, itself included; a candidate is sparse iff N(p) < min_count. */
+#define PCR_NEIGHBORS_ALL         0          /* mode: write every candidate; min_count only feeds the statistics */
+#define PCR_NEIGHBORS_KEEP        1          /* mode: write the candidates that are not sparse */
+#define PCR_NEIGHBORS_SPARSE      2          /* mode: write the sparse ones */
+#define PCR_NEIGHBORS_MAX_RADIUS  (1 << 20)  /* stream units: coordinates of adjacent voxels then differ by less than 2^21 */
+#define PCR_NN2_NONE              UINT64_MAX /* nn2 of a candidate with no other candidate within the radius */
+
+/* What pcr_neighbors did: the first four as in pcr_denoise_stats (a listed batch is decoded three times for the index, a fourth
+ * time if it writes a record), the non-empty voxels of the lattice with cell = radius, the slots of the table, the candidates of
+ * the fullest voxel, pairs_bound = the sum over the candidates of the candidates in the 27 voxels around their own -- what the
+ * pair kernel tests at most; computed from the table, so an early exit does not change it --, the sparse candidates (whichever
+ * mode) and the records written, which is the call's *out_count. */
+typedef struct pcr_neighbors_stats {
+    int64_t batches_outside;
+    int64_t batches_decoded;
+    int64_t points_considered;
+    int64_t runs;
+    int64_t voxels;
+    int64_t table_slots;
+    int64_t max_voxel_points;
+    int64_t pairs_bound;
+    int64_t points_sparse;
+    int64_t points_written;
+} pcr_neighbors_stats;
+
 /* A rectangle of pixels (pcr_select_screen), bounds inclusive, clipped to the image by the call. x0 > x1 or y0 > y1: the
  * empty rect. */
 typedef struct pcr_rect {

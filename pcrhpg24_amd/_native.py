@@ -155,6 +155,17 @@ class ComponentsStats(C.Structure):               # pcr_components_stats
 COMPONENTS_KEEP, COMPONENTS_SMALL = 0, 1                                                                # pcr_types.h
 
 
+class NeighborsStats(C.Structure):                # pcr_neighbors_stats
+    _fields_ = [(n, c_i64) for n in ("batches_outside", "batches_decoded", "points_considered", "runs", "voxels", "table_slots", "max_voxel_points",
+                                     "pairs_bound", "points_sparse", "points_written")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+NEIGHBORS_ALL, NEIGHBORS_KEEP, NEIGHBORS_SPARSE, NEIGHBORS_MAX_RADIUS, NN2_NONE = 0, 1, 2, 1 << 20, (1 << 64) - 1   # pcr_types.h
+
+
 class Rect(C.Structure):                          # pcr_rect: pixel bounds, inclusive; x0 > x1 or y0 > y1 = empty
     _fields_ = [(n, c_i32) for n in ("x0", "y0", "x1", "y1")]
 
@@ -189,6 +200,7 @@ assert C.sizeof(DisplayOpts) == 16
 assert C.sizeof(Grid) == 24 and C.sizeof(GridStats) == 24
 assert C.sizeof(GroundParams) == 136 and C.sizeof(GroundStats) == 48 and C.sizeof(HeightStats) == 32
 assert C.sizeof(Voxels) == 16 and C.sizeof(ThinStats) == 48 and C.sizeof(DenoiseStats) == 72 and C.sizeof(ComponentsStats) == 88
+assert C.sizeof(NeighborsStats) == 80
 assert C.sizeof(XyzBatch) == 64 and C.sizeof(GpuBatch) == 160 and C.sizeof(FileHeader) == 40 and C.sizeof(RenderParams) == 224
 
 
@@ -218,6 +230,7 @@ HIP_SYMBOLS = [
     "pcr_thin", "pcr_read_thin",
     "pcr_denoise", "pcr_read_denoise",
     "pcr_components", "pcr_read_components",
+    "pcr_neighbors", "pcr_read_neighbors",
 ]
 
 HOST_SYMBOLS = [
@@ -357,6 +370,9 @@ def hip_lib() -> C.CDLL:
         for n in ("pcr_components", "pcr_read_components"):
             getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Voxels), C.POINTER(Box), C.c_int, c_i64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_size_t, C.POINTER(c_i64), C.POINTER(ComponentsStats)]
+        for n in ("pcr_neighbors", "pcr_read_neighbors"):
+            getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, c_i32, C.POINTER(Box), c_i64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.POINTER(c_i64), C.POINTER(NeighborsStats)]
         _hip = lib
     return _hip
 

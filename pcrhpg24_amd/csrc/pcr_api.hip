@@ -179,6 +179,22 @@ struct pcr_ctx {
     int64_t components_slots = 0;
     unsigned long long *d_components_counters = nullptr; // [5] occupied slots, components, small ones, their candidates, the largest
     int64_t *d_components_labels_stage = nullptr;       // [components_labels_stage_batches * 65536]
+    // radius neighbourhoods (pcr_neighbors / pcr_read_neighbors) share pcr_thin's scratch; their own: the index and the dense results
+    uint2 *d_neighbors_cursor = nullptr;                // [neighbors_slots] per slot of the table: bucket start, entries filled
+    int64_t neighbors_slots = 0;
+    unsigned long long *d_neighbors_starts = nullptr;   // [neighbors_chains] the run-start word of every chain
+    int64_t neighbors_chains = 0;
+    uint4 *d_neighbors_bucket = nullptr;                // [neighbors_candidates] x, y, z, row, bucketed by voxel
+    int64_t neighbors_candidates = 0;
+    unsigned long long *d_neighbors_work = nullptr;     // [neighbors_work] slot << 32 | chunk
+    int64_t neighbors_work = 0;
+    unsigned long long *d_neighbors_n = nullptr, *d_neighbors_nn2 = nullptr;    // [.._rows] N and nn2 by row, each only once asked for
+    int64_t neighbors_n_rows = 0, neighbors_nn2_rows = 0;
+    unsigned long long *d_neighbors_counters = nullptr; // [NEIGHBORS_COUNTERS]
+    int64_t *d_neighbors_counts_stage = nullptr;        // [neighbors_counts_stage_batches * 65536]
+    int64_t neighbors_counts_stage_batches = 0;
+    uint64_t *d_neighbors_nn2_stage = nullptr;          // [neighbors_nn2_stage_batches * 65536]
+    int64_t neighbors_nn2_stage_batches = 0;
     int64_t components_labels_stage_batches = 0;
     int64_t prepass_batches = 0;
     static constexpr int FENCES = 8;
@@ -285,6 +301,10 @@ void free_stream_buffers(pcr_ctx *c)
     dfree(c->d_denoise_counters);
     dfree(c->d_components_scratch); c->components_slots = 0; dfree(c->d_components_counters);
     dfree(c->d_components_labels_stage); c->components_labels_stage_batches = 0;
+    dfree(c->d_neighbors_cursor); c->neighbors_slots = 0; dfree(c->d_neighbors_starts); c->neighbors_chains = 0;
+    dfree(c->d_neighbors_bucket); c->neighbors_candidates = 0; dfree(c->d_neighbors_work); c->neighbors_work = 0;
+    dfree(c->d_neighbors_n); c->neighbors_n_rows = 0; dfree(c->d_neighbors_nn2); c->neighbors_nn2_rows = 0; dfree(c->d_neighbors_counters);
+    dfree(c->d_neighbors_counts_stage); c->neighbors_counts_stage_batches = 0; dfree(c->d_neighbors_nn2_stage); c->neighbors_nn2_stage_batches = 0;
 
     if (c->any_generic_pending && c->any_generic_ev) (void)hipEventSynchronize(c->any_generic_ev);
     c->any_generic_pending = false;
@@ -2754,7 +2774,7 @@ struct VoxelPlan {
 // has touched the table. `verb` names the call in the messages; a table of more than 2^max_log2_slots slots is refused.
 // Synchronises.
 int voxel_plan_begin(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const pcr_box *clip, const char *verb, uint32_t max_log2_slots, ThinPlan &p,
-                     VoxelPlan &v)
+                     VoxelPlan &v, const char *cell = "cell")
 {
     p.listed.clear(); p.writers.clear(); p.cnt.clear();
     v = VoxelPlan{};
@@ -2770,11 +2790,11 @@ int voxel_plan_begin(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox
     int axis = 0;
     switch (noise_lattice(vox.origin, vox.cell, q.min, q.max, &a.lat, &axis)) {
     case THIN_LATTICE_EXTENT:
-        return set_err(c, PCR_E_ARG, "the points to %s span %lld on axis %d, 2^31 or more: pass a clip or a larger cell (a tail artefact far outside the cloud?)",
-                       verb, (long long)q.max[axis] - (long long)q.min[axis], axis);
+        return set_err(c, PCR_E_ARG, "the points to %s span %lld on axis %d, 2^31 or more: pass a clip or a larger %s (a tail artefact far outside the cloud?)",
+                       verb, (long long)q.max[axis] - (long long)q.min[axis], axis, cell);
     case THIN_LATTICE_VOXELS:
-        return set_err(c, PCR_E_ARG, "the points to %s span %lld on axis %d, more than 2^21 - 2 voxels of %d: pass a clip or a larger cell (a tail artefact far outside the cloud?)",
-                       verb, (long long)q.max[axis] - (long long)q.min[axis], axis, vox.cell);
+        return set_err(c, PCR_E_ARG, "the points to %s span %lld on axis %d, more than 2^21 - 2 voxels of %d: pass a clip or a larger %s (a tail artefact far outside the cloud?)",
+                       verb, (long long)q.max[axis] - (long long)q.min[axis], axis, vox.cell, cell);
     default: break;
     }
     v.batches_outside = n - nL; v.batches_decoded = nL; v.nL = nL;
@@ -2798,11 +2818,11 @@ int voxel_plan_begin(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox
     while (((int64_t)1 << log2_slots) < 2 * v.runs) ++log2_slots;
     const int64_t slots = (int64_t)1 << log2_slots;
     if (log2_slots > max_log2_slots)
-        return set_err(c, PCR_E_NOMEM, "a voxel table of %lld slots (%lld runs) is more than the 2^%u this call can index: pass a clip or a larger cell",
-                       (long long)slots, (long long)v.runs, max_log2_slots);
+        return set_err(c, PCR_E_NOMEM, "a voxel table of %lld slots (%lld runs) is more than the 2^%u this call can index: pass a clip or a larger %s",
+                       (long long)slots, (long long)v.runs, max_log2_slots, cell);
     if (!thin_grow((void **)&c->d_thin_table, c->thin_slots, slots, sizeof(ThinSlot)))
-        return set_err(c, PCR_E_NOMEM, "out of device memory for a voxel table of %lld slots (%lld runs): pass a clip or a larger cell", (long long)slots,
-                       (long long)v.runs);
+        return set_err(c, PCR_E_NOMEM, "out of device memory for a voxel table of %lld slots (%lld runs): pass a clip or a larger %s", (long long)slots,
+                       (long long)v.runs, cell);
     v.table_slots = slots;
     a.log2_slots = log2_slots; a.table = c->d_thin_table; a.error = c->d_thin_error;
     hipLaunchKernelGGL(k_denoise_clear, dim3((unsigned)std::min<int64_t>((slots + 255) / 256, 4096)), dim3(256), 0, c->stream, c->d_thin_table,
@@ -3046,6 +3066,199 @@ int pcr_read_components(pcr_ctx *c, int64_t first_batch, int64_t count, const pc
                                 alignof(int64_t), capacity_points, out_count, stats, &n, p, &done);
     if (rc || done) return rc;
     return thin_read_pieces(c, first_batch, n, p, host_points, host_rows, host_labels);
+}
+
+// ---- radius neighbourhoods ----------------------------------------------------------------------
+namespace {
+// pcr_denoise's plan with the counts of the table turned into buckets: count the candidates per voxel and note the run starts,
+// hand out buckets and work items, fill the buckets, test the pairs, count the rows to write per batch. want_n / want_nn2: the
+// dense arrays a later neighbors_emit gathers from. Fills the plan neighbors_emit takes (p.st is not used) and st. Synchronises.
+int neighbors_plan(pcr_ctx *c, int64_t first, int64_t n, int32_t radius, const pcr_box *clip, int64_t min_count, int mode, bool want_n, bool want_nn2,
+                   ThinPlan &p, pcr_neighbors_stats &st)
+{
+    st = pcr_neighbors_stats{};
+    VoxelPlan v;
+    const pcr_voxels vox{{0, 0, 0}, radius};
+    int rc = voxel_plan_begin(c, first, n, vox, clip, "search", 32, p, v, "radius");      // (a work item holds a 32-bit slot)
+    st.batches_outside = v.batches_outside; st.batches_decoded = v.batches_decoded; st.points_considered = v.points_considered; st.runs = v.runs;
+    if (rc || v.runs == 0) return rc;
+    const int64_t slots = v.table_slots, nL = v.nL;
+    const int64_t work_capacity = v.runs + v.points_considered / 64 + 1;      // the sum of ceil(count / 64) over at most `runs` voxels
+    if (!thin_grow((void **)&c->d_neighbors_cursor, c->neighbors_slots, slots, sizeof(uint2)) ||
+        !thin_grow((void **)&c->d_neighbors_starts, c->neighbors_chains, n * PCR_WORKGROUP_SIZE, 8) ||
+        !thin_grow((void **)&c->d_neighbors_bucket, c->neighbors_candidates, v.points_considered, sizeof(uint4)) ||
+        !thin_grow((void **)&c->d_neighbors_work, c->neighbors_work, work_capacity, 8) ||
+        (want_n && !thin_grow((void **)&c->d_neighbors_n, c->neighbors_n_rows, n * PCR_POINTS_PER_BATCH, 8)) ||
+        (want_nn2 && !thin_grow((void **)&c->d_neighbors_nn2, c->neighbors_nn2_rows, n * PCR_POINTS_PER_BATCH, 8)))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the index of %lld candidates in %lld slots: pass a clip or a larger radius",
+                       (long long)v.points_considered, (long long)slots);
+    if (!c->d_neighbors_counters && hipMalloc((void **)&c->d_neighbors_counters, NEIGHBORS_COUNTERS * 8) != hipSuccess)
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the counters");
+    st.table_slots = slots;
+    NeighborsArgs g{};
+    g.t = v.a;
+    g.cursor = c->d_neighbors_cursor; g.starts = c->d_neighbors_starts; g.bucket = c->d_neighbors_bucket; g.work = c->d_neighbors_work;
+    g.counters = c->d_neighbors_counters;
+    g.candidates = (unsigned long long)v.points_considered; g.work_capacity = (unsigned long long)work_capacity;
+    g.rows = (unsigned long long)n * PCR_POINTS_PER_BATCH;
+    g.r2 = (unsigned long long)radius * (unsigned long long)radius; g.min_count = (unsigned long long)min_count;
+    g.mode = mode; g.early = mode != PCR_NEIGHBORS_ALL && !want_n && !want_nn2;
+    g.keep = c->d_thin_keep; g.out_n = want_n ? c->d_neighbors_n : nullptr; g.out_nn2 = want_nn2 ? c->d_neighbors_nn2 : nullptr;
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)nL), block(PCR_WORKGROUP_SIZE);
+    const dim3 per_slot((unsigned)std::min<int64_t>((slots + 255) / 256, 4096));      // (slots and 4096 * 256 are powers of two)
+    unsigned long long counters[NEIGHBORS_COUNTERS] = {};
+    HIP_TRY(c, hipMemsetAsync(c->d_neighbors_counters, 0, sizeof counters, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_thin_keep, 0, (size_t)n * PCR_WORKGROUP_SIZE * 8, c->stream));
+    if (v.windows) hipLaunchKernelGGL((k_neighbors_count<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_thin_list, v.a, g.starts);
+    else           hipLaunchKernelGGL((k_neighbors_count<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_thin_list, v.a, g.starts);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(k_neighbors_alloc, per_slot, dim3(256), 0, c->stream, g);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(counters, c->d_neighbors_counters, sizeof counters, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(v.totals.data() + nL * 2, c->d_thin_error, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const int64_t items = (int64_t)counters[NEIGHBORS_WORK_CURSOR];
+    if (v.totals[(size_t)nL * 2] || (int64_t)counters[NEIGHBORS_BUCKET_CURSOR] != v.points_considered || items > work_capacity)
+        return set_err(c, PCR_E_NOMEM, "voxel table overflow: %lld slots for %lld runs", (long long)slots, (long long)v.runs);
+    if (v.windows) hipLaunchKernelGGL((k_neighbors_fill<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_thin_list, g);
+    else           hipLaunchKernelGGL((k_neighbors_fill<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_thin_list, g);
+    HIP_TRY(c, hipGetLastError());
+    // (at most 16 384 workgroups: a wave walks the work list with the grid's stride and adds its statistics up in registers)
+    hipLaunchKernelGGL(k_neighbors_pairs, dim3((unsigned)std::min<int64_t>((items + 3) / 4, 16384)), dim3(256), 0, c->stream, g, (unsigned long long)items);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(k_thin_totals, grid, dim3(256), 0, c->stream, c->d_thin_list, (uint32_t)first, c->d_thin_keep, c->d_thin_totals);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(v.totals.data(), c->d_thin_totals, (size_t)nL * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(v.totals.data() + nL * 2, c->d_thin_error, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(counters, c->d_neighbors_counters, sizeof counters, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (v.totals[(size_t)nL * 2]) return set_err(c, PCR_E_NOMEM, "voxel table overflow: %lld slots for %lld runs", (long long)slots, (long long)v.runs);
+    for (int64_t k = 0; k < nL; ++k) {
+        if (!v.totals[(size_t)k]) continue;
+        p.writers.push_back(p.listed[(size_t)k]); p.cnt.push_back(v.totals[(size_t)k]);
+        st.points_written += v.totals[(size_t)k];
+    }
+    st.voxels = (int64_t)counters[NEIGHBORS_VOXELS]; st.max_voxel_points = (int64_t)counters[NEIGHBORS_MAX_VOXEL];
+    for (int k = 0; k < 64; ++k) { st.pairs_bound += (int64_t)counters[NEIGHBORS_PAIRS_BOUND + k]; st.points_sparse += (int64_t)counters[NEIGHBORS_SPARSE + k]; }
+    return PCR_OK;
+}
+
+// thin_emit with two more outputs: the writes of batches [i0, i1) of the plan's range, any of the four NULL. The caller synchronises.
+int neighbors_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, uint4 *points, int64_t *rows, int64_t *counts, uint64_t *nn2)
+{
+    const size_t w0 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i0)) - p.writers.begin());
+    const size_t w1 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i1)) - p.writers.begin());
+    if (w0 == w1) return PCR_OK;
+    p.offsets.clear();
+    int64_t off = 0;
+    for (size_t w = w0; w < w1; ++w) { p.offsets.push_back(off); off += p.cnt[w]; }
+    HIP_TRY(c, hipMemcpyAsync(c->d_thin_wlist + w0, p.writers.data() + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_thin_offsets + w0, p.offsets.data(), (w1 - w0) * 8, hipMemcpyHostToDevice, c->stream));
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)(w1 - w0)), block(PCR_WORKGROUP_SIZE);
+    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
+#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_neighbors_write<L, B>), grid, block, 0, c->stream, s, c->d_thin_wlist + w0, (uint32_t)first, c->d_thin_keep, \
+                                            c->d_thin_offsets + w0, c->d_neighbors_n, c->d_neighbors_nn2, points, rows, counts,                          \
+                                            reinterpret_cast<unsigned long long *>(nn2))
+    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
+    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+#undef PCR_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    return PCR_OK;
+}
+
+// The checks and the plan shared by pcr_neighbors / pcr_read_neighbors. *done: nothing left to write (an error, a count-only call, no records).
+int neighbors_prepare(pcr_ctx *c, int64_t first, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count, int mode, const void *points,
+                      size_t points_align, const void *rows, const void *counts, const void *nn2, size_t rows_align, size_t capacity, int64_t *out_count,
+                      pcr_neighbors_stats *stats, int64_t *n, ThinPlan &p, bool *done)
+{
+    *done = true;
+    if (out_count) *out_count = 0;
+    int rc = select_range(c, first, count, n);
+    if (rc) return rc;
+    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
+    if (points && reinterpret_cast<uintptr_t>(points) % points_align != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
+    if (rows && reinterpret_cast<uintptr_t>(rows) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the rows is misaligned (%zu bytes)", rows_align);
+    if (counts && reinterpret_cast<uintptr_t>(counts) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the counts is misaligned (%zu bytes)", rows_align);
+    if (nn2 && reinterpret_cast<uintptr_t>(nn2) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the nearest distances is misaligned (%zu bytes)", rows_align);
+    if (radius < 1 || radius > PCR_NEIGHBORS_MAX_RADIUS)
+        return set_err(c, PCR_E_ARG, "radius of %d: 1 .. %d stream units (PCR_NEIGHBORS_MAX_RADIUS)", radius, PCR_NEIGHBORS_MAX_RADIUS);
+    if (min_count < 0) return set_err(c, PCR_E_ARG, "min_count is %lld: 0 or more", (long long)min_count);
+    if (mode != PCR_NEIGHBORS_ALL && mode != PCR_NEIGHBORS_KEEP && mode != PCR_NEIGHBORS_SPARSE)
+        return set_err(c, PCR_E_ARG, "mode is %d, not PCR_NEIGHBORS_ALL, PCR_NEIGHBORS_KEEP or PCR_NEIGHBORS_SPARSE", mode);
+    if (*n > ((int64_t)1 << 32) / PCR_POINTS_PER_BATCH)
+        return set_err(c, PCR_E_ARG, "a range of %lld batches has more than 2^32 rows (the index stores a 32-bit row)", (long long)*n);
+    pcr_neighbors_stats st{};
+    if ((rc = neighbors_plan(c, first, *n, radius, clip, min_count, mode, counts != nullptr, nn2 != nullptr, p, st))) return rc;
+    *out_count = st.points_written;
+    if (stats) *stats = st;
+    if ((!points && !rows && !counts && !nn2) || st.points_written == 0) return PCR_OK;
+    if (capacity < (size_t)st.points_written)
+        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld to write", capacity, (long long)st.points_written);
+    *done = false;
+    return PCR_OK;
+}
+} // namespace
+
+int pcr_neighbors(pcr_ctx *c, int64_t first_batch, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count, int mode, void *dev_points,
+                  void *dev_rows, void *dev_counts, void *dev_nn2, size_t capacity_points, int64_t *out_count, pcr_neighbors_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = neighbors_prepare(c, first_batch, count, radius, clip, min_count, mode, dev_points, 16, dev_rows, dev_counts, dev_nn2, 8, capacity_points,
+                               out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    if ((rc = neighbors_emit(c, first_batch, 0, n, p, static_cast<uint4 *>(dev_points), static_cast<int64_t *>(dev_rows), static_cast<int64_t *>(dev_counts),
+                             static_cast<uint64_t *>(dev_nn2))))
+        return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+int pcr_read_neighbors(pcr_ctx *c, int64_t first_batch, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count, int mode,
+                       pcr_point *host_points, int64_t *host_rows, int64_t *host_counts, uint64_t *host_nn2, size_t capacity_points, int64_t *out_count,
+                       pcr_neighbors_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = neighbors_prepare(c, first_batch, count, radius, clip, min_count, mode, host_points, alignof(pcr_point), host_rows, host_counts, host_nn2,
+                               alignof(int64_t), capacity_points, out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    // thin_read_pieces with two more outputs: pieces of at most DECODE_STAGE_BATCHES batches through the staging buffers
+    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
+    const size_t per_batch = (size_t)PCR_POINTS_PER_BATCH;
+    if ((host_points && !thin_grow((void **)&c->d_decode_stage, c->decode_stage_batches, piece, per_batch * sizeof(pcr_point))) ||
+        (host_rows && !thin_grow((void **)&c->d_thin_rows_stage, c->thin_rows_stage_batches, piece, per_batch * sizeof(int64_t))) ||
+        (host_counts && !thin_grow((void **)&c->d_neighbors_counts_stage, c->neighbors_counts_stage_batches, piece, per_batch * sizeof(int64_t))) ||
+        (host_nn2 && !thin_grow((void **)&c->d_neighbors_nn2_stage, c->neighbors_nn2_stage_batches, piece, per_batch * sizeof(uint64_t))))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the staging buffers of %lld batches", (long long)piece);
+    uint4 *const d_points = host_points ? reinterpret_cast<uint4 *>(c->d_decode_stage) : nullptr;
+    int64_t *const d_rows = host_rows ? c->d_thin_rows_stage : nullptr;
+    int64_t *const d_counts = host_counts ? c->d_neighbors_counts_stage : nullptr;
+    uint64_t *const d_nn2 = host_nn2 ? c->d_neighbors_nn2_stage : nullptr;
+    int64_t written = 0;
+    size_t w = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += piece) {
+        const int64_t i1 = std::min(n, i0 + piece);
+        int64_t m = 0;
+        for (; w < p.writers.size() && p.writers[w] < (uint32_t)(first_batch + i1); ++w) m += p.cnt[w];
+        if (m == 0) continue;
+        if ((rc = neighbors_emit(c, first_batch, i0, i1, p, d_points, d_rows, d_counts, d_nn2))) return rc;
+        if (d_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
+        if (d_rows) HIP_TRY(c, hipMemcpyAsync(host_rows + written, d_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        if (d_counts) HIP_TRY(c, hipMemcpyAsync(host_counts + written, d_counts, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        if (d_nn2) HIP_TRY(c, hipMemcpyAsync(host_nn2 + written, d_nn2, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        written += m;
+    }
+    return PCR_OK;
 }
 
 // ---- screen selection and picking --------------------------------------------------------------

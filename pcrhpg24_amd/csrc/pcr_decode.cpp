@@ -4,6 +4,7 @@
 //     pcr_decode <in.huffman> <out.las> --thin CELL [--center] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --denoise CELL MAXCOUNT [--isolated] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --components CELL MINPOINTS [--conn 6|26] [--small] [--box x0 y0 z0 x1 y1 z1]
+//     pcr_decode <in.huffman> <out.las> --radius R MINCOUNT [--sparse] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]
 //     pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1] [--rect x0 y0 x1 y1]
 //     pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]
@@ -18,6 +19,8 @@
 // decimated on the GPU without ever existing in full. With --polygon only the points inside a polygon prism of world coordinates are
 // read back (pcr_read_polygon). With --denoise the points come back without the isolated ones, or those alone (pcr_read_denoise).
 // With --components they come back without the connected components of voxels below a size, or those alone (pcr_read_components).
+// With --radius they come back without those that have fewer than a number of points within a radius, or those alone: the radius
+// outlier filter on actual point pairs (pcr_read_neighbors).
 // With --dtm the lowest-point grid goes through the ground filter on the GPU (pcr_read_ground) and the terrain model is written;
 // with --height the points whose height above that model lies in a range are read back (pcr_read_height).
 #include <cerrno>
@@ -40,6 +43,7 @@ static const char *USAGE =
     "       pcr_decode <in.huffman> <out.las> --thin CELL [--center] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --denoise CELL MAXCOUNT [--isolated] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --components CELL MINPOINTS [--conn 6|26] [--small] [--box x0 y0 z0 x1 y1 z1]\n"
+    "       pcr_decode <in.huffman> <out.las> --radius R MINCOUNT [--sparse] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]\n"
     "       pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1]\n"
     "                                                [--rect x0 y0 x1 y1]\n"
@@ -69,6 +73,10 @@ static const char *USAGE =
     "  connected component; it is small if it holds fewer than MINPOINTS points (a whole number >= 0), exact duplicates\n"
     "  counted. --small: the points of the small components instead. Only the points inside --box count, or inside the box of\n"
     "  the file's header. No point to write is an error.\n"
+    "  --radius R MINCOUNT: the radius outlier filter, exact: the points that have at least MINCOUNT points (a whole number >= 0)\n"
+    "  within R world units, the point itself and exact duplicates included, in the stream's order. --sparse: the other points\n"
+    "  instead. Only the points inside --box count, as neighbours too, or inside the box of the file's header. No point to write\n"
+    "  is an error.\n"
     "  --polygon FILE: only the points inside a polygon, selected on the GPU, in the stream's order. FILE is text in world\n"
     "  coordinates: one vertex `x y` per line, a blank line starts the next ring (a ring inside another is a hole: the even-odd\n"
     "  rule); a ring has at least 3 vertices and is closed implicitly, all rings together at most 4096. A vertex goes to the\n"
@@ -212,6 +220,36 @@ static bool parse_denoise(int argc, char **argv, int at, Denoise &d)
             d.has_box = true;
         } else if (a == "--isolated" && !d.isolated) {
             d.isolated = true;
+        } else {
+            return false;
+        }
+    }
+    return true;
+}
+
+struct Radius {
+    double radius = 0.0;
+    long long min_count = 0;
+    bool sparse = false, has_box = false;
+    double lo[3], hi[3];
+};
+
+// the options behind --radius, every one well formed, or false
+static bool parse_radius(int argc, char **argv, int at, Radius &r)
+{
+    if (argc < at + 3 || std::strcmp(argv[at], "--radius") != 0) return false;
+    if (!parse_double(argv[at + 1], r.radius) || !(r.radius > 0.0)) return false;
+    char *end = nullptr;
+    errno = 0;
+    r.min_count = std::strtoll(argv[at + 2], &end, 10);
+    if (end == argv[at + 2] || *end != '\0' || errno == ERANGE || r.min_count < 0) return false;
+    for (int i = at + 3; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--box" && i + 6 < argc && !r.has_box) {
+            for (int k = 0; k < 6; ++k) if (!parse_double(argv[++i], k < 3 ? r.lo[k] : r.hi[k - 3])) return false;
+            r.has_box = true;
+        } else if (a == "--sparse" && !r.sparse) {
+            r.sparse = true;
         } else {
             return false;
         }
@@ -488,10 +526,13 @@ int main(int argc, char **argv)
     const bool componented = argc > 3 && std::strcmp(argv[3], "--components") == 0;
     Ground ground;
     const bool grounded = argc > 3 && (std::strcmp(argv[3], "--dtm") == 0 || std::strcmp(argv[3], "--height") == 0);
-    const bool boxed = argc > 3 && !viewed && !orthoed && !thinned && !polygoned && !denoised && !componented && !grounded;
+    Radius rad;
+    const bool radiused = argc > 3 && std::strcmp(argv[3], "--radius") == 0;
+    const bool boxed = argc > 3 && !viewed && !orthoed && !thinned && !polygoned && !denoised && !componented && !grounded && !radiused;
     if (argc < 3 || (polygoned && !parse_polygon(argc, argv, 3, poly)) || (boxed && !parse_box(argc, argv, 3, lo, hi)) || (viewed && !parse_view(argc, argv, 3, view)) ||
         (orthoed && !parse_ortho(argc, argv, 3, ortho)) || (thinned && !parse_thin(argc, argv, 3, thin)) || (denoised && !parse_denoise(argc, argv, 3, noise)) ||
-        (componented && !parse_components(argc, argv, 3, comps)) || (grounded && !parse_ground(argc, argv, 3, ground))) { std::fputs(USAGE, stderr); return 2; }
+        (componented && !parse_components(argc, argv, 3, comps)) || (grounded && !parse_ground(argc, argv, 3, ground)) ||
+        (radiused && !parse_radius(argc, argv, 3, rad))) { std::fputs(USAGE, stderr); return 2; }
     const std::string in = argv[1], out = argv[2];
     try {
         Renderer renderer(viewed ? view.w : 64, viewed ? view.h : 64, 0);
@@ -560,6 +601,14 @@ int main(int argc, char **argv)
                         vox.cell, (long long)st.batches_outside, (long long)st.batches_decoded, (long long)st.points_considered, (long long)st.runs,
                         (long long)st.voxels, (long long)st.voxels_isolated, (long long)st.points_isolated, (long long)st.points_written,
                         (long long)st.table_slots);
+            if (points.empty()) throw std::runtime_error("no points to write: nothing written");
+        } else if (radiused) {
+            const int32_t r = radiusFromWorld(info, rad.radius);
+            const pcr_box clip = boxFromWorld(info, rad.has_box ? rad.lo : info.min, rad.has_box ? rad.hi : info.max);
+            const pcr_neighbors_stats st = las->radiusFiltered(r, &clip, rad.min_count, rad.sparse ? PCR_NEIGHBORS_SPARSE : PCR_NEIGHBORS_KEEP, points);
+            std::printf("radius: %d lattice steps, written %lld, considered %lld, sparse %lld, voxels %lld, table slots %lld, pairs bound %lld\n", r,
+                        (long long)st.points_written, (long long)st.points_considered, (long long)st.points_sparse, (long long)st.voxels,
+                        (long long)st.table_slots, (long long)st.pairs_bound);
             if (points.empty()) throw std::runtime_error("no points to write: nothing written");
         } else if (componented) {
             const pcr_voxels vox = voxelsFromWorld(info, comps.cell, info.min);

@@ -21,6 +21,7 @@
 //   k_thin_*        on request: one record per voxel of a cubic lattice, straight from the compressed stream
 //   k_denoise_*     on request: the records whose 3 x 3 x 3 voxels hold few points (or the others), on k_thin_*'s frame
 //   k_components_*  on request: the connected components of the occupied voxels, the small ones dropped or extracted
+//   k_neighbors_*   on request: per point the points within a radius and the nearest one, from a copy bucketed by voxel
 //   k_las_*         the 10-10-10 method (modules/compute_loop_las_cuda)
 //   k_resolve_*     framebuffer -> RGBA8 (resolve.cu:149-191, huffman_hqs/resolve.cu:2-47)
 //   k_merge_* / k_flip_sign  multi-GPU partial-framebuffer merges
@@ -3280,6 +3281,283 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_components_labels(Stream
                 else mark = -1;                             // (cannot happen: k_components_count inserted every run's key)
             }
             labels[dst] = mark;
+            ++dst;
+        }
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Radius neighbourhoods (pcr_neighbors / pcr_read_neighbors): per candidate N = the candidates within `radius` (itself included)
+// and nn2 = the least squared distance to a candidate of another row within the radius. pcr_denoise's frame and lattice with
+// cell = radius, so the 27 voxels around a point's own cover its sphere, and the counts of the table turned into an index: a copy
+// of the candidates bucketed by voxel. One launch each:
+//   k_thin_runs / k_denoise_clear (above).
+//   k_neighbors_count   k_denoise_count that also stores, per chain, a word with a bit wherever the key differs from the previous
+//                       point's: the starts of the runs (and of the stretches outside the clip).
+//   k_neighbors_alloc   a thread per slot: an occupied slot takes its bucket [start, start + count) from one cursor and its
+//                       ceil(count / 64) work items (slot, chunk) from another, both aggregated per wave (a prefix over the wave,
+//                       one atomic by lane 63). Which bucket lies where depends on the order of the atomics; nothing observable
+//                       does. The slot's value becomes (count - 1) | start << 32 (both fit 32 bits: at most 2^32 candidates), so
+//                       that whoever finds a key has its bucket from the same 16 bytes. It also reduces the occupied slots and
+//                       the largest count.
+//   k_neighbors_fill    colourless decode: at every run start the run's length is read from the chain's word (the distance to
+//                       the next set bit), the slot looked up and `length` entries reserved in its bucket with one atomic; the
+//                       run's points then stream there as {x, y, z, row} with plain 16-byte stores.
+//   k_neighbors_pairs   a wave per work item at a time, four waves to a workgroup, the work list walked with the grid's stride: lane j holds centre j of the chunk, lanes 0 .. 26 look up one
+//                       neighbour voxel each (once per chunk, not per point), the 27 buckets laid end to end are read in tiles of
+//                       64 entries (one 16-byte load per lane, whatever bucket the entry lies in: one load per 64 entries, not
+//                       one per voxel) and broadcast entry by entry with a wave-uniform lane read -- no LDS, no barrier. Coordinates of adjacent voxels differ by less than 2 * radius <= 2^21, so the
+//                       32-bit difference is exact and each square is one 32 x 32 -> 64 multiply-add. N and nn2 go by row into
+//                       dense arrays (only those asked for), the row's bit into pcr_thin's keep bitmap by mode.
+//   k_thin_totals (above) / k_neighbors_write   k_thin_write that also gathers N and nn2 of the written rows.
+// Sums, minima and bit-ors commute: the result does not depend on the hash, the table size, the order of the buckets or of
+// lanes, workgroups and launches. No workgroup waits for another one; every probe loop makes at most `slots` steps, and a store
+// into the buckets or the work list is tested against the array's end (a miss sets the error word).
+// ------------------------------------------------------------------------------------------------
+struct NeighborsArgs {
+    ThinArgs t;                     // the clip, the lattice (cell = radius), the first batch, the table and the error word
+    uint2 *cursor;                  // [slots] x: the bucket's first entry, y: entries filled (k_neighbors_fill reserves from it)
+    thin_u64 *starts;               // [batches of the range * 1024] the run-start word of every chain of a listed batch
+    uint4 *bucket;                  // [candidates] x, y, z, row
+    thin_u64 *work;                 // [work_capacity] slot << 32 | chunk
+    thin_u64 *counters;             // [NEIGHBORS_COUNTERS]
+    thin_u64 candidates, work_capacity, rows;   // the lengths of bucket and work, and the rows of the range (the dense arrays' length)
+    thin_u64 r2, min_count;         // radius squared; sparse: N < min_count
+    int mode, early;                // early: nobody reads N or nn2, a wave may stop once every centre has min_count
+    thin_u64 *keep, *out_n, *out_nn2;   // the keep bitmap; dense by row, or NULL
+};
+// (pairs_bound and the sparse candidates are summed by every wave of k_neighbors_pairs over the work items it takes, in registers,
+// and added to one of 64 partial sums each, picked by workgroup; the host adds them up. One atomic per work item into 64 adjacent
+// words measured 16 ms for 1e7 work items.)
+enum { NEIGHBORS_BUCKET_CURSOR = 0, NEIGHBORS_WORK_CURSOR, NEIGHBORS_VOXELS, NEIGHBORS_MAX_VOXEL, NEIGHBORS_PAIRS_BOUND, NEIGHBORS_SPARSE = NEIGHBORS_PAIRS_BOUND + 64,
+       NEIGHBORS_COUNTERS = NEIGHBORS_SPARSE + 64 };
+
+template <int LAYOUT>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_neighbors_count(StreamView s, const uint32_t *list, ThinArgs a, thin_u64 *starts)
+{
+    const uint32_t b = list[blockIdx.x];
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    load_packed_table(s, b, s_table);
+    thin_u64 prev = THIN_EMPTY, word = 0;
+    uint32_t len = 0;
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t) {
+        uint32_t d2;
+        const thin_u64 key = in_box(a.q, x, y, z) ? thin_key(a, x, y, z, d2) : THIN_EMPTY;
+        if (key == prev) {
+            ++len;
+        } else {
+            if (prev != THIN_EMPTY) denoise_insert(a, prev, len);
+            prev = key; len = 1;
+            word |= 1ull << (uint32_t)i;
+        }
+    });
+    if (prev != THIN_EMPTY) denoise_insert(a, prev, len);
+    starts[(size_t)(b - a.first_batch) * PCR_WORKGROUP_SIZE + threadIdx.x] = word;
+}
+
+__device__ __forceinline__ thin_u64 neighbors_key(thin_u64 key, int n)
+{
+    const thin_u64 dx = (thin_u64)(n % 3), dy = (thin_u64)(n / 3 % 3), dz = (thin_u64)(n / 9);
+    return key + dx + (dy << THIN_KEY_BITS) + (dz << (2 * THIN_KEY_BITS)) - (1ull + (1ull << THIN_KEY_BITS) + (1ull << (2 * THIN_KEY_BITS)));
+}
+
+// (launched with a power of two of threads that divides the slots: every lane of a wave makes the same number of rounds)
+__global__ void __launch_bounds__(256) k_neighbors_alloc(NeighborsArgs a)
+{
+    ThinSlot *table = a.t.table;
+    const thin_u64 slots = 1ull << a.t.log2_slots;
+    const uint32_t lane = threadIdx.x & 63u;
+    thin_u64 voxels = 0, largest = 0;
+    for (thin_u64 i = (thin_u64)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (thin_u64)gridDim.x * blockDim.x) {
+        const thin_u64 key = table[i].key;
+        const thin_u64 cnt = key == THIN_EMPTY ? 0ull : table[i].val;
+        const thin_u64 chunks = (cnt + 63u) >> 6;
+        thin_u64 cnt_incl = cnt, chunks_incl = chunks;       // inclusive prefixes over the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const thin_u64 u0 = __shfl_up(cnt_incl, d, 64), u1 = __shfl_up(chunks_incl, d, 64);
+            if (lane >= (uint32_t)d) { cnt_incl += u0; chunks_incl += u1; }
+        }
+        thin_u64 base0 = 0, base1 = 0;
+        if (lane == 63 && cnt_incl) {
+            base0 = atomicAdd(&a.counters[NEIGHBORS_BUCKET_CURSOR], cnt_incl);
+            base1 = atomicAdd(&a.counters[NEIGHBORS_WORK_CURSOR], chunks_incl);
+        }
+        base0 = __shfl(base0, 63, 64); base1 = __shfl(base1, 63, 64);
+        if (cnt == 0) continue;                             // (the next round's shuffles run with the wave whole again: the loop has one latch)
+        const thin_u64 start = base0 + cnt_incl - cnt;
+        a.cursor[i] = make_uint2((uint32_t)start, 0u);
+        thin_u64 w = base1 + chunks_incl - chunks;
+        for (thin_u64 k = 0; k < chunks; ++k, ++w) {
+            if (w < a.work_capacity) a.work[w] = (i << 32) | k;
+            else *a.t.error = 1u;
+        }
+        table[i].val = (cnt - 1ull) | (start << 32);        // (only this thread reads or writes this slot's value in this kernel)
+        ++voxels;
+        largest = max(largest, cnt);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        voxels += __shfl_xor(voxels, d, 64);
+        largest = max(largest, (thin_u64)__shfl_xor(largest, d, 64));
+    }
+    if (lane == 0 && voxels) {
+        atomicAdd(&a.counters[NEIGHBORS_VOXELS], voxels);
+        atomicMax(&a.counters[NEIGHBORS_MAX_VOXEL], largest);
+    }
+}
+
+template <int LAYOUT>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_neighbors_fill(StreamView s, const uint32_t *list, NeighborsArgs a)
+{
+    const uint32_t b = list[blockIdx.x];
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    load_packed_table(s, b, s_table);
+    const thin_u64 word = a.starts[(size_t)(b - a.t.first_batch) * PCR_WORKGROUP_SIZE + threadIdx.x];
+    const uint32_t row0 = (b - a.t.first_batch) * (uint32_t)PCR_POINTS_PER_BATCH + threadIdx.x * (uint32_t)PCR_POINTS_PER_THREAD;
+    thin_u64 prev = THIN_EMPTY, pos = 0, end = 0;
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t) {
+        uint32_t d2;
+        const thin_u64 key = in_box(a.t.q, x, y, z) ? thin_key(a.t, x, y, z, d2) : THIN_EMPTY;
+        if (key != prev) {
+            prev = key; pos = end = 0;
+            if (key != THIN_EMPTY) {
+                const thin_u64 rest = i < 63 ? word >> (uint32_t)(i + 1) : 0ull;
+                const uint32_t len = rest ? (uint32_t)__builtin_ctzll(rest) + 1u : 64u - (uint32_t)i;
+                uint32_t at;
+                if (components_lookup(a.t.table, a.t.log2_slots, key, at)) {
+                    pos = (thin_u64)a.cursor[at].x + atomicAdd(&a.cursor[at].y, len);
+                    end = min(pos + len, a.candidates);
+                    if (end != pos + len) *a.t.error = 1u;
+                } else {
+                    *a.t.error = 1u;                        // (cannot happen: k_neighbors_count inserted every run's key)
+                }
+            }
+        }
+        if (pos < end) a.bucket[pos++] = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, row0 + (uint32_t)i);
+    });
+}
+
+__device__ __forceinline__ thin_u64 neighbors_uniform(thin_u64 v)
+{
+    return ((thin_u64)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+}
+
+__global__ void __launch_bounds__(256) k_neighbors_pairs(NeighborsArgs a, thin_u64 items)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    thin_u64 bound = 0, sparse_total = 0;                   // this wave's share of pairs_bound and of the sparse candidates
+    // (no barrier below: a wave is on its own; it takes every (waves of the grid)-th work item)
+    for (thin_u64 wi = neighbors_uniform((thin_u64)blockIdx.x * 4u + (threadIdx.x >> 6)); wi < items; wi += (thin_u64)gridDim.x * 4u) {
+    const thin_u64 item = neighbors_uniform(a.work[wi]);
+    const uint32_t slot = (uint32_t)(item >> 32), chunk = (uint32_t)item;
+    const ThinSlot *table = a.t.table;
+    const thin_u64 key = neighbors_uniform(table[slot].key), own = neighbors_uniform(table[slot].val);     // (k_neighbors_alloc's value)
+    const thin_u64 count = (own & 0xFFFFFFFFull) + 1ull, own_start = own >> 32;
+    const thin_u64 idx = (thin_u64)chunk * 64u + lane;
+    const bool valid = idx < count && own_start + idx < a.candidates;
+    const uint4 centre = valid ? a.bucket[own_start + idx] : make_uint4(0, 0, 0, 0);
+
+    // lane n < 27: the bucket of neighbour voxel n (13 is the chunk's own); lanes 27 .. 63 hold empty ones
+    uint32_t nb_start = 0;
+    thin_u64 nb_count = 0;
+    if (lane < 27u) {
+        uint32_t at = slot;
+        if (lane == 13u || components_lookup(table, a.t.log2_slots, neighbors_key(key, (int)lane), at)) {
+            const thin_u64 v = table[at].val;
+            nb_start = (uint32_t)(v >> 32);
+            nb_count = (v & 0xFFFFFFFFull) + 1ull;
+        }
+    }
+    // The 27 buckets laid end to end: bucket n covers [excl(n), excl(n) + count(n)) of `total` entries, which the wave reads in
+    // tiles of 64 whatever bucket they lie in -- one load per 64 entries, not one per neighbour voxel.
+    thin_u64 nb_excl = nb_count;
+#pragma unroll
+    for (int d = 1; d < 32; d <<= 1) {
+        const thin_u64 up = __shfl_up(nb_excl, d, 64);
+        if (lane >= (uint32_t)d) nb_excl += up;
+    }
+    const thin_u64 total = neighbors_uniform(__shfl(nb_excl, 26, 64));
+    nb_excl -= nb_count;
+    const uint32_t excl_lo = (uint32_t)nb_excl, excl_hi = (uint32_t)(nb_excl >> 32), count_lo = (uint32_t)nb_count, count_hi = (uint32_t)(nb_count >> 32);
+
+    // pairs_bound: what this chunk tests at most -- from the table, so the early exit below does not change it
+    bound += (thin_u64)__popcll(__ballot(valid)) * total;
+
+    thin_u64 n_in = 0, zeros = 0, least = ~0ull;            // least: the minimum of d2 - 1, so that d2 == 0 wraps out of the way
+    for (thin_u64 t0 = 0; t0 < total; t0 += 64u) {
+        const int m = (int)min((thin_u64)64u, total - t0);
+        const thin_u64 g = t0 + lane;                       // this lane's entry of the tile
+        thin_u64 at = ~0ull;
+        for (int nb = 0; nb < 27; ++nb) {                   // (every value read here is wave-uniform)
+            const thin_u64 e = ((thin_u64)(uint32_t)__builtin_amdgcn_readlane((int)excl_hi, nb) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)excl_lo, nb);
+            const thin_u64 c = ((thin_u64)(uint32_t)__builtin_amdgcn_readlane((int)count_hi, nb) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)count_lo, nb);
+            if (c == 0ull || e >= t0 + 64u || e + c <= t0) continue;
+            const thin_u64 first = (uint32_t)__builtin_amdgcn_readlane((int)nb_start, nb);
+            if (g >= e && g - e < c) at = first + (g - e);
+        }
+        const bool have = lane < (uint32_t)m && at < a.candidates;
+        const uint4 tile = have ? a.bucket[at] : make_uint4(0, 0, 0, 0);
+        uint32_t in32 = 0, zero32 = 0;
+#pragma unroll 4
+        for (int k = 0; k < m; ++k) {
+            const int32_t dx = (int32_t)(centre.x - (uint32_t)__builtin_amdgcn_readlane((int)tile.x, k));
+            const int32_t dy = (int32_t)(centre.y - (uint32_t)__builtin_amdgcn_readlane((int)tile.y, k));
+            const int32_t dz = (int32_t)(centre.z - (uint32_t)__builtin_amdgcn_readlane((int)tile.z, k));
+            const thin_u64 d2 = (thin_u64)((int64_t)dx * dx) + (thin_u64)((int64_t)dy * dy) + (thin_u64)((int64_t)dz * dz);
+            in32 += d2 <= a.r2 ? 1u : 0u;
+            zero32 += d2 == 0ull ? 1u : 0u;
+            least = min(least, d2 - 1ull);
+        }
+        n_in += in32; zeros += zero32;
+        if (a.early && __ballot(valid && n_in < a.min_count) == 0ull) break;
+    }
+    const bool sparse = valid && n_in < a.min_count;
+    if (valid && centre.w < a.rows) {                       // (k_neighbors_fill wrote every entry: the row is one of the range)
+        const thin_u64 row = centre.w;
+        if (a.out_n) a.out_n[row] = n_in;
+        if (a.out_nn2) a.out_nn2[row] = zeros >= 2ull ? 0ull : (least != ~0ull && least + 1ull <= a.r2 ? least + 1ull : ~0ull);
+        if (a.mode == PCR_NEIGHBORS_ALL || (a.mode == PCR_NEIGHBORS_SPARSE) == sparse) atomicOr(&a.keep[row >> 6], 1ull << (row & 63u));
+    }
+    sparse_total += (thin_u64)__popcll(__ballot(sparse));
+    }
+    if (lane == 0) {
+        if (bound) atomicAdd(&a.counters[NEIGHBORS_PAIRS_BOUND + (blockIdx.x & 63u)], bound);
+        if (sparse_total) atomicAdd(&a.counters[NEIGHBORS_SPARSE + (blockIdx.x & 63u)], sparse_total);
+    }
+}
+
+// k_thin_write that also gathers N and nn2 of the written rows from the dense arrays (any of the four outputs may be NULL)
+template <int LAYOUT, bool BC7>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_neighbors_write(StreamView s, const uint32_t *list, uint32_t first_batch, const thin_u64 *keep,
+                                                                        const int64_t *offsets, const thin_u64 *dense_n, const thin_u64 *dense_nn2,
+                                                                        uint4 *points, int64_t *rows, int64_t *counts, thin_u64 *nn2)
+{
+    const uint32_t b = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint32_t s_part[LWC_WAVES];
+    const thin_u64 word = keep[(size_t)(b - first_batch) * PCR_WORKGROUP_SIZE + tid];
+    const uint32_t mine = (uint32_t)__popcll(word);
+    uint32_t incl = mine;                                   // inclusive prefix inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += up;
+    }
+    if (lane == 63) s_part[wave] = incl;
+    load_packed_table(s, b, s_table);                       // (its barrier publishes s_part as well)
+    uint32_t before = incl - mine;
+    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    int64_t dst = offsets[blockIdx.x] + before;
+    const int64_t end = dst + mine;                         // never past the bits of this chain's word
+    const int64_t row0 = (int64_t)(b - first_batch) * PCR_POINTS_PER_BATCH + (int64_t)tid * PCR_POINTS_PER_THREAD;
+    decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        if (((word >> (uint32_t)i) & 1ull) && dst < end) {
+            if (points) points[dst] = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
+            if (rows) rows[dst] = row0 + i;
+            if (counts) counts[dst] = (int64_t)dense_n[row0 + i];
+            if (nn2) nn2[dst] = dense_nn2[row0 + i];
             ++dst;
         }
     });

@@ -395,6 +395,27 @@ struct HuffmanLasData : Resource {
         return st;
     }
 
+    // The points inside `clip` (NULL: everywhere) that have at least min_count of them within `radius` lattice steps, the point
+    // itself and exact duplicates included, or with PCR_NEIGHBORS_SPARSE the others (PCR_NEIGHBORS_ALL: all of them), on the GPU
+    // straight from the compressed stream (pcr_read_neighbors: a counting call, then the read). counts / nn2 (may be NULL): per
+    // point the points within the radius and the squared distance to the nearest other one (PCR_NN2_NONE: none). Not in the reference.
+    pcr_neighbors_stats radiusFiltered(int32_t radius, const pcr_box *clip, int64_t min_count, int mode, std::vector<pcr_point> &out,
+                                       std::vector<int64_t> *counts = nullptr, std::vector<uint64_t> *nn2 = nullptr)
+    {
+        if (!loadedOn) throw std::runtime_error("radiusFiltered: the resource is not loaded");
+        const int64_t nB = pcr_batches_resident(loadedOn->ctx);
+        int64_t n = 0;
+        pcr_neighbors_stats st{};
+        loadedOn->check(pcr_read_neighbors(loadedOn->ctx, 0, nB, radius, clip, min_count, mode, nullptr, nullptr, nullptr, nullptr, 0, &n, &st),
+                        "pcr_read_neighbors");
+        out.resize((size_t)n);
+        if (counts) counts->resize((size_t)n);
+        if (nn2) nn2->resize((size_t)n);
+        if (n) loadedOn->check(pcr_read_neighbors(loadedOn->ctx, 0, nB, radius, clip, min_count, mode, out.data(), nullptr, counts ? counts->data() : nullptr,
+                                                  nn2 ? nn2->data() : nullptr, out.size(), &n, &st), "pcr_read_neighbors");
+        return st;
+    }
+
     // The points a frame of camera `p` draws whose pixel lies in `rect` (NULL: the whole image), with where they land, selected on
     // the GPU (pcr_read_screen: a counting call, then the read). Either vector may be NULL. Not in the reference.
     pcr_screen_stats selectScreen(const pcr_render_params &p, const pcr_rect *rect, std::vector<pcr_point> *points, std::vector<pcr_screen_hit> *hits)
@@ -672,6 +693,20 @@ inline pcr_voxels voxelsFromWorld(const pcr_las_info &las, double cell_size, con
     const pcr_box b = boxFromWorld(las, origin, h3);
     for (int k = 0; k < 3; ++k) if (b.min[k] > b.max[k]) throw std::runtime_error("voxelsFromWorld: the origin lies beyond every int32 coordinate");
     return pcr_voxels{{b.min[0], b.min[1], b.min[2]}, (int32_t)cells[0]};
+}
+
+// The largest whole number r of lattice steps with r * scale <= radius (as doubles): the radius pcr_neighbors takes for `radius`
+// world units. The three scales have to be equal and r in 1 .. PCR_NEIGHBORS_MAX_RADIUS. The Python twin is host.radius_from_world.
+inline int32_t radiusFromWorld(const pcr_las_info &las, double radius)
+{
+    const double s = las.scale[0];
+    if (las.scale[1] != s || las.scale[2] != s) throw std::runtime_error("radiusFromWorld: the scales of x, y and z differ");
+    if (!(s > 0.0) || !(radius > 0.0) || radius == std::numeric_limits<double>::infinity()) throw std::runtime_error("radiusFromWorld: needs a positive scale and a positive finite radius");
+    int64_t r = (int64_t)std::min(radius / s, (double)PCR_NEIGHBORS_MAX_RADIUS + 1.0);
+    while ((double)r * s > radius) --r;
+    while (r <= PCR_NEIGHBORS_MAX_RADIUS && (double)(r + 1) * s <= radius) ++r;
+    if (r < 1 || r > PCR_NEIGHBORS_MAX_RADIUS) throw std::runtime_error("radiusFromWorld: the radius is not 1 .. 2^20 lattice steps");
+    return (int32_t)r;
 }
 
 // modules/huffman_cuda/huffman_cuda.h:60-75: the reference's first Huffman method (class ComputeHuffman, registered as

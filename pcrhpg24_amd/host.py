@@ -28,7 +28,7 @@ from typing import Iterator, Optional
 import numpy as np
 
 from . import _native as N
-from ._native import Box, DisplayOpts, EncodeStats, Grid, GridStats, GroundStats, HeightStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, ComponentsStats, DenoiseStats, ThinStats, Voxels, XyzBatch, c_i64, fb_elems
+from ._native import Box, DisplayOpts, EncodeStats, Grid, GridStats, GroundStats, HeightStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, ComponentsStats, DenoiseStats, NeighborsStats, ThinStats, Voxels, XyzBatch, c_i64, fb_elems
 
 POINTS_PER_BATCH = 65536
 ENCODED_PAD_WORDS = 1024
@@ -444,6 +444,35 @@ def components_mode(mode) -> int:
             raise ValueError(f'mode is "keep" or "small", not {mode!r}')
         return N.COMPONENTS_KEEP if mode == "keep" else N.COMPONENTS_SMALL
     return int(mode)
+
+
+def neighbors_mode(mode) -> int:
+    """PCR_NEIGHBORS_ALL / _KEEP / _SPARSE from "all" / "keep" / "sparse" (an integer passes through: the library checks it)."""
+    if isinstance(mode, str):
+        if mode not in ("all", "keep", "sparse"):
+            raise ValueError(f'mode is "all", "keep" or "sparse", not {mode!r}')
+        return {"all": N.NEIGHBORS_ALL, "keep": N.NEIGHBORS_KEEP, "sparse": N.NEIGHBORS_SPARSE}[mode]
+    return int(mode)
+
+
+def radius_from_world(las: LasInfo, radius: float) -> int:
+    """The largest whole number r of lattice steps with r * scale <= radius as float64 evaluates the product: the radius
+    Context.neighbors takes for `radius` world units. ValueError for a header whose three scales differ (the sphere is one of
+    integer coordinates), and for a result below 1 or above NEIGHBORS_MAX_RADIUS."""
+    sx, sy, sz = (float(las.scale[k]) for k in range(3))
+    if not (sx == sy == sz):
+        raise ValueError(f"the scales {sx}, {sy} and {sz} differ: a radius in world units is no sphere of lattice steps")
+    radius = float(radius)
+    if not sx > 0.0 or not radius > 0.0 or radius == float("inf"):
+        raise ValueError("radius_from_world needs a positive scale and a positive finite radius")
+    r = min(int(radius / sx), N.NEIGHBORS_MAX_RADIUS + 1)
+    while r * sx > radius:                       # (the quotient may be one step off either way: the product decides)
+        r -= 1
+    while r <= N.NEIGHBORS_MAX_RADIUS and (r + 1) * sx <= radius:
+        r += 1
+    if r < 1 or r > N.NEIGHBORS_MAX_RADIUS:
+        raise ValueError(f"a radius of {radius} is {r} lattice steps of {sx}: 1 .. {N.NEIGHBORS_MAX_RADIUS}")
+    return r
 
 
 def voxels_from_world(las: LasInfo, cell_size: float, origin=None) -> Voxels:
@@ -1161,6 +1190,59 @@ class Context:
         res = (pts,) + ((r,) if rows else ()) + ((lab,) if labels else ())
         return res if len(res) > 1 else res[0]
 
+    # -- radius neighbourhoods (pcr_neighbors / pcr_read_neighbors) ------------------------------------------
+    def neighbors(self, radius: int, min_count: int = 1, clip=None, mode="all", first: int = 0, count: Optional[int] = None, out=None,
+                  rows: bool = False, counts: bool = False, nn2: bool = False):
+        """The rows of batches [first, first + count) inside `clip` (as_box; None: everywhere), straight from the compressed stream:
+        all of them (mode "all"), those with at least `min_count` rows of the range and clip within `radius` lattice steps, the row
+        itself included (mode "keep"), or the others (mode "sparse"). Results, `out`, rows=True and stream ordering as
+        Context.denoise; counts=True appends an int64 tensor of N (the rows within the radius), nn2=True an int64 tensor holding
+        the squared distance to the nearest other row within the radius (-1, the bits of NN2_NONE, for none): points, then rows,
+        counts, nn2 as asked for. What the last call did is in self.neighbors_stats."""
+        import torch
+        clip, mode = None if clip is None else as_box(clip), neighbors_mode(mode)
+        cp = None if clip is None else C.byref(clip)
+        dev = torch.device("cuda", self.device)
+        cnt, st, nb = c_i64(), NeighborsStats(), -1 if count is None else count
+        if out is None:
+            self._chk(self.lib.pcr_neighbors(self.h, first, nb, radius, cp, min_count, mode, None, None, None, None, 0, C.byref(cnt), C.byref(st)),
+                      "pcr_neighbors")
+            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
+        cap = out.numel() // 4
+        extra = [torch.empty(cap, dtype=torch.int64, device=dev) if want else None for want in (rows, counts, nn2)]
+        torch.cuda.current_stream(dev).synchronize()
+        ptrs = [C.c_void_p(t.data_ptr() if cap else None) if t is not None else None for t in extra]
+        rc = self.lib.pcr_neighbors(self.h, first, nb, radius, cp, min_count, mode, C.c_void_p(out.data_ptr() if cap else None), ptrs[0], ptrs[1], ptrs[2],
+                                    cap, C.byref(cnt), C.byref(st))
+        self.neighbors_stats = st.as_dict()
+        if rc:
+            self.neighbors_stats["points_written"] = cnt.value
+        self._chk(rc, "pcr_neighbors")
+        res = (out.view(-1, 4)[:cnt.value],) + tuple(t[:cnt.value] for t in extra if t is not None)
+        return res if len(res) > 1 else res[0]
+
+    def read_neighbors(self, radius: int, min_count: int = 1, clip=None, mode="all", first: int = 0, count: Optional[int] = None, rows: bool = False,
+                       counts: bool = False, nn2: bool = False):
+        """The same on the host, without torch: a numpy structured array of POINT_DTYPE, followed as asked for by int64 arrays of
+        the rows and of N and a uint64 array of nn2 (NN2_NONE for none) (pcr_read_neighbors: a counting call, then the read;
+        synchronises)."""
+        clip, mode = None if clip is None else as_box(clip), neighbors_mode(mode)
+        cp = None if clip is None else C.byref(clip)
+        cnt, st, nb = c_i64(), NeighborsStats(), -1 if count is None else count
+        self._chk(self.lib.pcr_read_neighbors(self.h, first, nb, radius, cp, min_count, mode, None, None, None, None, 0, C.byref(cnt), C.byref(st)),
+                  "pcr_read_neighbors")
+        pts = np.empty(cnt.value, POINT_DTYPE)
+        extra = [np.empty(cnt.value, dt) if want else None for want, dt in ((rows, ROW_DTYPE), (counts, np.int64), (nn2, np.uint64))]
+        if cnt.value:
+            self._chk(self.lib.pcr_read_neighbors(self.h, first, nb, radius, cp, min_count, mode, pts.ctypes.data,
+                                                  *[None if a is None else a.ctypes.data for a in extra], len(pts), C.byref(cnt), C.byref(st)),
+                      "pcr_read_neighbors")
+        self.neighbors_stats = st.as_dict()
+        res = (pts,) + tuple(a for a in extra if a is not None)
+        return res if len(res) > 1 else res[0]
+
     # -- screen selection and picking (pcr_select_screen / pcr_read_screen / pcr_pick) ---------------------
     def select_screen(self, p: RenderParams, rect=None):
         """The points a frame of camera `p` draws (render_basic's cull, level of detail, precision and inside test) whose pixel lies
@@ -1686,6 +1768,39 @@ class HuffmanLasData(Resource):
             return pts, lab
         so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
         return pts[:, :3].to(torch.float64) * so[0] + so[1], pts, lab
+
+    def _neighbors_clip(self, info, radius, lo, hi, world):
+        if world:
+            return radius_from_world(info, radius), box_from_world(info, tuple(info.min) if lo is None else lo, tuple(info.max) if hi is None else hi)
+        clip = None if lo is None and hi is None else as_box(((INT32_MIN,) * 3 if lo is None else lo, (INT32_MAX,) * 3 if hi is None else hi))
+        return int(radius), clip
+
+    def radius_filtered(self, renderer: Renderer, radius: float, min_count: int, lo=None, hi=None, sparse: bool = False, world: bool = True):
+        """The loaded resource without the points that have fewer than `min_count` points within `radius` (the point itself and
+        exact duplicates included) or, with sparse=True, those points alone: the radius outlier filter, exact, on the GPU and
+        straight from the compressed stream (Context.neighbors). radius is in world units (radius_from_world), with world=False in
+        lattice steps; lo, hi, world and the result are as for denoised(): with world=True the clip defaults to the header's box."""
+        import torch
+        info = self.las_info()
+        r, clip = self._neighbors_clip(info, radius, lo, hi, world)
+        pts = renderer.ctx.neighbors(r, min_count, clip, "sparse" if sparse else "keep")
+        if not world:
+            return pts
+        so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
+        return pts[:, :3].to(torch.float64) * so[0] + so[1], pts
+
+    def point_spacing(self, renderer: Renderer, radius: float, lo=None, hi=None, world: bool = True):
+        """Per point of the loaded resource inside the clip: (points, N, spacing) -- the int32 records, N = the points within
+        `radius` (itself included, int64) and the distance to the nearest other point within the radius (float64: sqrt(nn2) *
+        scale in world units, with world=False sqrt(nn2) in lattice steps; inf for none). radius, lo, hi and world as for
+        radius_filtered()."""
+        import torch
+        info = self.las_info()
+        r, clip = self._neighbors_clip(info, radius, lo, hi, world)
+        pts, n, nn2 = renderer.ctx.neighbors(r, 1, clip, "all", counts=True, nn2=True)
+        scale = float(info.scale[0]) if world else 1.0
+        spacing = torch.where(nn2 < 0, torch.full_like(nn2, float("inf"), dtype=torch.float64), torch.sqrt(nn2.to(torch.float64)) * scale)
+        return pts, n, spacing
 
     def las_info(self) -> LasInfo:
         """Scale, offset, min and max of the LAS file the stream was made from, as its first batch record carries them (the
