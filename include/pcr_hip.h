@@ -545,6 +545,49 @@ int pcr_read_neighbors(pcr_ctx *ctx, int64_t first_batch, int64_t count, int32_t
                        int mode, pcr_point *host_points, int64_t *host_rows, int64_t *host_counts, uint64_t *host_nn2,
                        size_t capacity_points, int64_t *out_count, pcr_neighbors_stats *stats);
 
+/* ---- local moments: exact neighbourhood covariance and normals per point (no reference counterpart) -----------------------------
+ * Candidates are pcr_neighbors' own. For a candidate p and an integer radius r, 1 <= r <= PCR_MOMENTS_MAX_RADIUS, B(p) is the set
+ * of candidates q with d2(p, q) <= r * r in exact 64-bit integers: p itself, exact duplicates and points at exactly distance r
+ * included. With d = q - p (offsets from the centre, not the origin: every term stays below r, and the later floating-point
+ * covariance is free of cancellation against large coordinates) a pcr_moments record holds n = |B(p)| (pcr_neighbors' N), s[a] =
+ * the sum of d_a over B(p) and q = the sums of d_a * d_b for xx, xy, xz, yy, yz, zz. EXACT: with r <= 32767 every |d_a| <= r and
+ * every product is below 2^30; a call has at most 2^32 rows, so every sum stays below 2^62 -- the reason for the radius limit.
+ * Sums commute: the result does not depend on the hash, the table size, the bucket order or the lane order and is the same from
+ * run to run.
+ * A candidate is written iff n >= min_count (min_count <= 1: all of them): its 16-byte record to dev_points (16-byte aligned),
+ * its row to dev_rows (int64), its pcr_moments to dev_moments and its pcr_eigen to dev_eigen (each 8-byte aligned), all in
+ * increasing row order, packed. Any pointer may be NULL; all four NULL only counts. A capacity below the result is PCR_E_ARG with
+ * *out_count = the count needed and nothing written. stats are pcr_neighbors': points_sparse = the candidates with n < min_count,
+ * pairs_bound as there. PCR_E_ARG with a message, nothing written: pcr_neighbors' refusals word for word (range, alignment,
+ * min_count < 0, more than 2^32 rows, the lattice rule with cell = radius and its advice), and a radius outside 1 ..
+ * PCR_MOMENTS_MAX_RADIUS. The call synchronises, touches no framebuffer, no prepass state, no render statistics; BC1 and BC7,
+ * either resident layout, before and after the first frame.
+ *   How: pcr_neighbors' plan up to the filled buckets; k_moments_pairs has k_neighbors_pairs' work distribution and accumulates the
+ *   ten sums per lane (no early exit: every pair contributes), stores the 80-byte record by row and runs the eigen function
+ *   in-lane; k_moments_write gathers the records of the kept rows. Scratch: pcr_neighbors' plus 80 and 48 bytes per row of the
+ *   range for the moments and the eigen records, each only when asked for (PCR_E_NOMEM: pass a clip or a shorter range).
+ * pcr_read_local_moments: the same into host memory (alignof(pcr_point) / alignof(int64_t) / alignof(double)), in pieces through
+ * staging buffers as pcr_read_neighbors.
+ * pcr_moments_eigen: the eigen record of each of n pcr_moments records at dev_moments (8-byte aligned) into dev_eigen, one
+ * thread each; needs no stream loaded; synchronises; n == 0 does nothing; a NULL or misaligned pointer with n > 0 and n < 0 are
+ * PCR_E_ARG. The eigen record is a function of the moments record alone, and pcr_local_moments calls the same function: for the
+ * same moments the two are byte-identical. In f64, each operation rounded once:
+ *     nf = (double)n,  m_a = (double)s[a] / nf,  C_ab = (double)q[ab] / nf - m_a * m_b
+ * n <= 0: all six doubles are 0. Otherwise cyclic Jacobi on C: pivots (0,1), (0,2), (1,2); a zero off-diagonal is skipped; it
+ * stops when all three are zero or after 12 sweeps; theta = (C_qq - C_pp) / (2 C_pq), t = sgn(theta) / (|theta| + sqrt(theta^2 +
+ * 1)) (an overflowing theta^2 ends in t = 0), c = 1 / sqrt(t^2 + 1), s = t c, tau = s / (1 + c); only + - * / and sqrt. The
+ * eigenvalues are sorted ascending, ties keep the lower axis first; normal is the eigenvector of value[0] with the sign rule of
+ * pcr_eigen. A decoupled axis a (C_ab == 0 for both b != a) keeps exactly (C_aa, e_a): a flat roof has value[0] == 0.0 and
+ * normal == (0, 0, 1) to the bit, the zero matrix (n == 1) values 0 and normal (1, 0, 0). No output is NaN or Inf for any
+ * finite input. */
+int pcr_local_moments(pcr_ctx *ctx, int64_t first_batch, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count,
+                      void *dev_points, void *dev_rows, void *dev_moments, void *dev_eigen, size_t capacity_points, int64_t *out_count,
+                      pcr_neighbors_stats *stats);
+int pcr_read_local_moments(pcr_ctx *ctx, int64_t first_batch, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count,
+                           pcr_point *host_points, int64_t *host_rows, pcr_moments *host_moments, pcr_eigen *host_eigen,
+                           size_t capacity_points, int64_t *out_count, pcr_neighbors_stats *stats);
+int pcr_moments_eigen(pcr_ctx *ctx, const void *dev_moments, int64_t n, void *dev_eigen);
+
 /* What a collective library needs to merge partial frames in place (include/pcr_dist.h does it with RCCL): the HIP stream
  * the context enqueues on, its device ordinal and the length of each framebuffer in 64-bit words. */
 void *pcr_get_stream(pcr_ctx *ctx);

@@ -323,6 +323,25 @@ typedef struct pcr_neighbors_stats {
     int64_t points_written;
 } pcr_neighbors_stats;
 
+/* pcr_local_moments: the moments of a candidate's neighbourhood B(p) = the candidates q with d2(p, q) <= radius * radius, p itself
+ * included, over the offsets d = q - p. With radius <= PCR_MOMENTS_MAX_RADIUS every |d_a| <= 32767 and every product is below
+ * 2^30; a call has at most 2^32 rows, so every sum stays below 2^62 and the int64 fields are exact: that is the reason for the
+ * limit. n = |B(p)| (pcr_neighbors' N), s[a] = the sum of d_a, q = the sums of d_a * d_b in the order xx, xy, xz, yy, yz, zz. */
+#define PCR_MOMENTS_MAX_RADIUS 32767
+typedef struct pcr_moments {
+    int64_t n;
+    int64_t s[3];
+    int64_t q[6];
+} pcr_moments;
+
+/* What pcr_moments_eigen makes of a pcr_moments record: the eigenvalues of its covariance matrix, ascending, and a unit
+ * eigenvector of value[0] (the surface normal), its sign fixed: the first non-zero of normal[2], normal[1], normal[0] is
+ * positive. All zero for n <= 0. */
+typedef struct pcr_eigen {
+    double value[3];
+    double normal[3];
+} pcr_eigen;
+
 /* A rectangle of pixels (pcr_select_screen), bounds inclusive, clipped to the image by the call. x0 > x1 or y0 > y1: the
  * empty rect. */
 typedef struct pcr_rect {

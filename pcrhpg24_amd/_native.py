@@ -166,6 +166,17 @@ class NeighborsStats(C.Structure):                # pcr_neighbors_stats
 NEIGHBORS_ALL, NEIGHBORS_KEEP, NEIGHBORS_SPARSE, NEIGHBORS_MAX_RADIUS, NN2_NONE = 0, 1, 2, 1 << 20, (1 << 64) - 1   # pcr_types.h
 
 
+class Moments(C.Structure):                       # pcr_moments: n, the sums of the offsets, the sums of their products xx xy xz yy yz zz
+    _fields_ = [("n", c_i64), ("s", c_i64 * 3), ("q", c_i64 * 6)]
+
+
+class Eigen(C.Structure):                         # pcr_eigen: the eigenvalues of the covariance, ascending; the unit normal
+    _fields_ = [("value", C.c_double * 3), ("normal", C.c_double * 3)]
+
+
+MOMENTS_MAX_RADIUS = 32767                                                                              # pcr_types.h
+
+
 class Rect(C.Structure):                          # pcr_rect: pixel bounds, inclusive; x0 > x1 or y0 > y1 = empty
     _fields_ = [(n, c_i32) for n in ("x0", "y0", "x1", "y1")]
 
@@ -200,7 +211,7 @@ assert C.sizeof(DisplayOpts) == 16
 assert C.sizeof(Grid) == 24 and C.sizeof(GridStats) == 24
 assert C.sizeof(GroundParams) == 136 and C.sizeof(GroundStats) == 48 and C.sizeof(HeightStats) == 32
 assert C.sizeof(Voxels) == 16 and C.sizeof(ThinStats) == 48 and C.sizeof(DenoiseStats) == 72 and C.sizeof(ComponentsStats) == 88
-assert C.sizeof(NeighborsStats) == 80
+assert C.sizeof(NeighborsStats) == 80 and C.sizeof(Moments) == 80 and C.sizeof(Eigen) == 48
 assert C.sizeof(XyzBatch) == 64 and C.sizeof(GpuBatch) == 160 and C.sizeof(FileHeader) == 40 and C.sizeof(RenderParams) == 224
 
 
@@ -231,6 +242,7 @@ HIP_SYMBOLS = [
     "pcr_denoise", "pcr_read_denoise",
     "pcr_components", "pcr_read_components",
     "pcr_neighbors", "pcr_read_neighbors",
+    "pcr_local_moments", "pcr_read_local_moments", "pcr_moments_eigen",
 ]
 
 HOST_SYMBOLS = [
@@ -373,6 +385,10 @@ def hip_lib() -> C.CDLL:
         for n in ("pcr_neighbors", "pcr_read_neighbors"):
             getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, c_i32, C.POINTER(Box), c_i64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_size_t, C.POINTER(c_i64), C.POINTER(NeighborsStats)]
+        for n in ("pcr_local_moments", "pcr_read_local_moments"):
+            getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, c_i32, C.POINTER(Box), c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.POINTER(c_i64), C.POINTER(NeighborsStats)]
+        lib.pcr_moments_eigen.argtypes = [C.c_void_p, C.c_void_p, c_i64, C.c_void_p]
         _hip = lib
     return _hip
 

@@ -195,6 +195,13 @@ struct pcr_ctx {
     int64_t neighbors_counts_stage_batches = 0;
     uint64_t *d_neighbors_nn2_stage = nullptr;          // [neighbors_nn2_stage_batches * 65536]
     int64_t neighbors_nn2_stage_batches = 0;
+    // local moments (pcr_local_moments / pcr_read_local_moments) share pcr_neighbors' index; their own: the dense records and the stages
+    uint4 *d_moments_dense = nullptr, *d_moments_eigen = nullptr;   // [.._rows * 5] pcr_moments and [.._rows * 3] pcr_eigen by row, each only once asked for
+    int64_t moments_dense_rows = 0, moments_eigen_rows = 0;
+    pcr_moments *d_moments_stage = nullptr;             // [moments_stage_batches * 65536]
+    int64_t moments_stage_batches = 0;
+    pcr_eigen *d_moments_eigen_stage = nullptr;         // [moments_eigen_stage_batches * 65536]
+    int64_t moments_eigen_stage_batches = 0;
     int64_t components_labels_stage_batches = 0;
     int64_t prepass_batches = 0;
     static constexpr int FENCES = 8;
@@ -305,6 +312,8 @@ void free_stream_buffers(pcr_ctx *c)
     dfree(c->d_neighbors_bucket); c->neighbors_candidates = 0; dfree(c->d_neighbors_work); c->neighbors_work = 0;
     dfree(c->d_neighbors_n); c->neighbors_n_rows = 0; dfree(c->d_neighbors_nn2); c->neighbors_nn2_rows = 0; dfree(c->d_neighbors_counters);
     dfree(c->d_neighbors_counts_stage); c->neighbors_counts_stage_batches = 0; dfree(c->d_neighbors_nn2_stage); c->neighbors_nn2_stage_batches = 0;
+    dfree(c->d_moments_dense); c->moments_dense_rows = 0; dfree(c->d_moments_eigen); c->moments_eigen_rows = 0;
+    dfree(c->d_moments_stage); c->moments_stage_batches = 0; dfree(c->d_moments_eigen_stage); c->moments_eigen_stage_batches = 0;
 
     if (c->any_generic_pending && c->any_generic_ev) (void)hipEventSynchronize(c->any_generic_ev);
     c->any_generic_pending = false;
@@ -3073,8 +3082,11 @@ namespace {
 // pcr_denoise's plan with the counts of the table turned into buckets: count the candidates per voxel and note the run starts,
 // hand out buckets and work items, fill the buckets, test the pairs, count the rows to write per batch. want_n / want_nn2: the
 // dense arrays a later neighbors_emit gathers from. Fills the plan neighbors_emit takes (p.st is not used) and st. Synchronises.
+// mom (pcr_local_moments): the same sequence with k_moments_pairs in k_neighbors_pairs' place, which keeps the rows with N >=
+// min_count and fills the dense pcr_moments / pcr_eigen records asked for; mode, want_n and want_nn2 are not used then.
+struct MomentsWant { bool moments, eigen; };
 int neighbors_plan(pcr_ctx *c, int64_t first, int64_t n, int32_t radius, const pcr_box *clip, int64_t min_count, int mode, bool want_n, bool want_nn2,
-                   ThinPlan &p, pcr_neighbors_stats &st)
+                   ThinPlan &p, pcr_neighbors_stats &st, const MomentsWant *mom = nullptr)
 {
     st = pcr_neighbors_stats{};
     VoxelPlan v;
@@ -3092,6 +3104,10 @@ int neighbors_plan(pcr_ctx *c, int64_t first, int64_t n, int32_t radius, const p
         (want_nn2 && !thin_grow((void **)&c->d_neighbors_nn2, c->neighbors_nn2_rows, n * PCR_POINTS_PER_BATCH, 8)))
         return set_err(c, PCR_E_NOMEM, "out of device memory for the index of %lld candidates in %lld slots: pass a clip or a larger radius",
                        (long long)v.points_considered, (long long)slots);
+    if (mom && ((mom->moments && !thin_grow((void **)&c->d_moments_dense, c->moments_dense_rows, n * PCR_POINTS_PER_BATCH, sizeof(pcr_moments))) ||
+                (mom->eigen && !thin_grow((void **)&c->d_moments_eigen, c->moments_eigen_rows, n * PCR_POINTS_PER_BATCH, sizeof(pcr_eigen)))))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the moments of %lld rows (%d bytes each): pass a clip or a shorter range",
+                       (long long)(n * PCR_POINTS_PER_BATCH), (int)((mom->moments ? sizeof(pcr_moments) : 0) + (mom->eigen ? sizeof(pcr_eigen) : 0)));
     if (!c->d_neighbors_counters && hipMalloc((void **)&c->d_neighbors_counters, NEIGHBORS_COUNTERS * 8) != hipSuccess)
         return set_err(c, PCR_E_NOMEM, "out of device memory for the counters");
     st.table_slots = slots;
@@ -3125,7 +3141,10 @@ int neighbors_plan(pcr_ctx *c, int64_t first, int64_t n, int32_t radius, const p
     else           hipLaunchKernelGGL((k_neighbors_fill<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_thin_list, g);
     HIP_TRY(c, hipGetLastError());
     // (at most 16 384 workgroups: a wave walks the work list with the grid's stride and adds its statistics up in registers)
-    hipLaunchKernelGGL(k_neighbors_pairs, dim3((unsigned)std::min<int64_t>((items + 3) / 4, 16384)), dim3(256), 0, c->stream, g, (unsigned long long)items);
+    const dim3 per_item((unsigned)std::min<int64_t>((items + 3) / 4, 16384));
+    if (mom) hipLaunchKernelGGL(k_moments_pairs, per_item, dim3(256), 0, c->stream, g, (unsigned long long)items, mom->moments ? c->d_moments_dense : nullptr,
+                                mom->eigen ? c->d_moments_eigen : nullptr);
+    else     hipLaunchKernelGGL(k_neighbors_pairs, per_item, dim3(256), 0, c->stream, g, (unsigned long long)items);
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(k_thin_totals, grid, dim3(256), 0, c->stream, c->d_thin_list, (uint32_t)first, c->d_thin_keep, c->d_thin_totals);
     HIP_TRY(c, hipGetLastError());
@@ -3258,6 +3277,145 @@ int pcr_read_neighbors(pcr_ctx *c, int64_t first_batch, int64_t count, int32_t r
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         written += m;
     }
+    return PCR_OK;
+}
+
+// ---- local moments ------------------------------------------------------------------------------
+namespace {
+// neighbors_emit with the 80- and 48-byte records: the writes of batches [i0, i1) of the plan's range, any of the four NULL. The
+// caller synchronises.
+int moments_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, uint4 *points, int64_t *rows, void *moments, void *eigen)
+{
+    const size_t w0 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i0)) - p.writers.begin());
+    const size_t w1 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i1)) - p.writers.begin());
+    if (w0 == w1) return PCR_OK;
+    p.offsets.clear();
+    int64_t off = 0;
+    for (size_t w = w0; w < w1; ++w) { p.offsets.push_back(off); off += p.cnt[w]; }
+    HIP_TRY(c, hipMemcpyAsync(c->d_thin_wlist + w0, p.writers.data() + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_thin_offsets + w0, p.offsets.data(), (w1 - w0) * 8, hipMemcpyHostToDevice, c->stream));
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)(w1 - w0)), block(PCR_WORKGROUP_SIZE);
+    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
+#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_moments_write<L, B>), grid, block, 0, c->stream, s, c->d_thin_wlist + w0, (uint32_t)first, c->d_thin_keep, \
+                                            c->d_thin_offsets + w0, reinterpret_cast<const unsigned long long *>(c->d_moments_dense),                     \
+                                            reinterpret_cast<const unsigned long long *>(c->d_moments_eigen), points, rows,                               \
+                                            static_cast<unsigned long long *>(moments), static_cast<unsigned long long *>(eigen))
+    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
+    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+#undef PCR_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    return PCR_OK;
+}
+
+// The checks and the plan shared by pcr_local_moments / pcr_read_local_moments: neighbors_prepare's, with the radius limit of the
+// exact sums. *done: nothing left to write (an error, a count-only call, no records).
+int moments_prepare(pcr_ctx *c, int64_t first, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count, const void *points,
+                    size_t points_align, const void *rows, const void *moments, const void *eigen, size_t rows_align, size_t capacity, int64_t *out_count,
+                    pcr_neighbors_stats *stats, int64_t *n, ThinPlan &p, bool *done)
+{
+    *done = true;
+    if (out_count) *out_count = 0;
+    int rc = select_range(c, first, count, n);
+    if (rc) return rc;
+    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
+    if (points && reinterpret_cast<uintptr_t>(points) % points_align != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
+    if (rows && reinterpret_cast<uintptr_t>(rows) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the rows is misaligned (%zu bytes)", rows_align);
+    if (moments && reinterpret_cast<uintptr_t>(moments) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the moments is misaligned (%zu bytes)", rows_align);
+    if (eigen && reinterpret_cast<uintptr_t>(eigen) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the eigen records is misaligned (%zu bytes)", rows_align);
+    if (radius < 1 || radius > PCR_MOMENTS_MAX_RADIUS)
+        return set_err(c, PCR_E_ARG, "radius of %d: 1 .. %d stream units (PCR_MOMENTS_MAX_RADIUS: the sums stay exact in 64 bits)", radius, PCR_MOMENTS_MAX_RADIUS);
+    if (min_count < 0) return set_err(c, PCR_E_ARG, "min_count is %lld: 0 or more", (long long)min_count);
+    if (*n > ((int64_t)1 << 32) / PCR_POINTS_PER_BATCH)
+        return set_err(c, PCR_E_ARG, "a range of %lld batches has more than 2^32 rows (the index stores a 32-bit row)", (long long)*n);
+    pcr_neighbors_stats st{};
+    const MomentsWant want{moments != nullptr, eigen != nullptr};
+    if ((rc = neighbors_plan(c, first, *n, radius, clip, min_count, PCR_NEIGHBORS_ALL, false, false, p, st, &want))) return rc;
+    *out_count = st.points_written;
+    if (stats) *stats = st;
+    if ((!points && !rows && !moments && !eigen) || st.points_written == 0) return PCR_OK;
+    if (capacity < (size_t)st.points_written)
+        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld to write", capacity, (long long)st.points_written);
+    *done = false;
+    return PCR_OK;
+}
+} // namespace
+
+int pcr_local_moments(pcr_ctx *c, int64_t first_batch, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count, void *dev_points,
+                      void *dev_rows, void *dev_moments, void *dev_eigen, size_t capacity_points, int64_t *out_count, pcr_neighbors_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = moments_prepare(c, first_batch, count, radius, clip, min_count, dev_points, 16, dev_rows, dev_moments, dev_eigen, 8, capacity_points, out_count,
+                             stats, &n, p, &done);
+    if (rc || done) return rc;
+    if ((rc = moments_emit(c, first_batch, 0, n, p, static_cast<uint4 *>(dev_points), static_cast<int64_t *>(dev_rows), dev_moments, dev_eigen))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+int pcr_read_local_moments(pcr_ctx *c, int64_t first_batch, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count, pcr_point *host_points,
+                           int64_t *host_rows, pcr_moments *host_moments, pcr_eigen *host_eigen, size_t capacity_points, int64_t *out_count,
+                           pcr_neighbors_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = moments_prepare(c, first_batch, count, radius, clip, min_count, host_points, alignof(pcr_point), host_rows, host_moments, host_eigen,
+                             alignof(int64_t), capacity_points, out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    // pcr_read_neighbors' pieces: at most DECODE_STAGE_BATCHES batches at a time through the staging buffers
+    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
+    const size_t per_batch = (size_t)PCR_POINTS_PER_BATCH;
+    if ((host_points && !thin_grow((void **)&c->d_decode_stage, c->decode_stage_batches, piece, per_batch * sizeof(pcr_point))) ||
+        (host_rows && !thin_grow((void **)&c->d_thin_rows_stage, c->thin_rows_stage_batches, piece, per_batch * sizeof(int64_t))) ||
+        (host_moments && !thin_grow((void **)&c->d_moments_stage, c->moments_stage_batches, piece, per_batch * sizeof(pcr_moments))) ||
+        (host_eigen && !thin_grow((void **)&c->d_moments_eigen_stage, c->moments_eigen_stage_batches, piece, per_batch * sizeof(pcr_eigen))))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the staging buffers of %lld batches", (long long)piece);
+    uint4 *const d_points = host_points ? reinterpret_cast<uint4 *>(c->d_decode_stage) : nullptr;
+    int64_t *const d_rows = host_rows ? c->d_thin_rows_stage : nullptr;
+    pcr_moments *const d_moments = host_moments ? c->d_moments_stage : nullptr;
+    pcr_eigen *const d_eigen = host_eigen ? c->d_moments_eigen_stage : nullptr;
+    int64_t written = 0;
+    size_t w = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += piece) {
+        const int64_t i1 = std::min(n, i0 + piece);
+        int64_t m = 0;
+        for (; w < p.writers.size() && p.writers[w] < (uint32_t)(first_batch + i1); ++w) m += p.cnt[w];
+        if (m == 0) continue;
+        if ((rc = moments_emit(c, first_batch, i0, i1, p, d_points, d_rows, d_moments, d_eigen))) return rc;
+        if (d_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
+        if (d_rows) HIP_TRY(c, hipMemcpyAsync(host_rows + written, d_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        if (d_moments) HIP_TRY(c, hipMemcpyAsync(host_moments + written, d_moments, (size_t)m * sizeof(pcr_moments), hipMemcpyDeviceToHost, c->stream));
+        if (d_eigen) HIP_TRY(c, hipMemcpyAsync(host_eigen + written, d_eigen, (size_t)m * sizeof(pcr_eigen), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        written += m;
+    }
+    return PCR_OK;
+}
+
+int pcr_moments_eigen(pcr_ctx *c, const void *dev_moments, int64_t n, void *dev_eigen)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n < 0) return set_err(c, PCR_E_ARG, "n is %lld: 0 or more records", (long long)n);
+    if (n == 0) return PCR_OK;
+    if (!dev_moments || !dev_eigen) return set_err(c, PCR_E_ARG, "the moments / eigen records are NULL");
+    if (reinterpret_cast<uintptr_t>(dev_moments) % 8 != 0 || reinterpret_cast<uintptr_t>(dev_eigen) % 8 != 0)
+        return set_err(c, PCR_E_ARG, "the moments / eigen records are misaligned (8 bytes)");
+    const int64_t per_launch = (int64_t)1 << 30;        // (a grid of at most 2^22 workgroups)
+    for (int64_t i0 = 0; i0 < n; i0 += per_launch) {
+        const int64_t m = std::min(per_launch, n - i0);
+        hipLaunchKernelGGL(k_moments_eigen, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, static_cast<const int64_t *>(dev_moments) + i0 * 10,
+                           (unsigned long long)m, static_cast<double *>(dev_eigen) + i0 * 6);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return PCR_OK;
 }
 

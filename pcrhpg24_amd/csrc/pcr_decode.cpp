@@ -5,6 +5,7 @@
 //     pcr_decode <in.huffman> <out.las> --denoise CELL MAXCOUNT [--isolated] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --components CELL MINPOINTS [--conn 6|26] [--small] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --radius R MINCOUNT [--sparse] [--box x0 y0 z0 x1 y1 z1]
+//     pcr_decode <in.huffman> <out.ply> --normals R [MINCOUNT] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]
 //     pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1] [--rect x0 y0 x1 y1]
 //     pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]
@@ -20,7 +21,8 @@
 // read back (pcr_read_polygon). With --denoise the points come back without the isolated ones, or those alone (pcr_read_denoise).
 // With --components they come back without the connected components of voxels below a size, or those alone (pcr_read_components).
 // With --radius they come back without those that have fewer than a number of points within a radius, or those alone: the radius
-// outlier filter on actual point pairs (pcr_read_neighbors).
+// outlier filter on actual point pairs (pcr_read_neighbors). With --normals the points come back with the normal and the curvature
+// of their neighbourhood within a radius, as a PLY (pcr_read_local_moments).
 // With --dtm the lowest-point grid goes through the ground filter on the GPU (pcr_read_ground) and the terrain model is written;
 // with --height the points whose height above that model lies in a range are read back (pcr_read_height).
 #include <cerrno>
@@ -44,6 +46,7 @@ static const char *USAGE =
     "       pcr_decode <in.huffman> <out.las> --denoise CELL MAXCOUNT [--isolated] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --components CELL MINPOINTS [--conn 6|26] [--small] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --radius R MINCOUNT [--sparse] [--box x0 y0 z0 x1 y1 z1]\n"
+    "       pcr_decode <in.huffman> <out.ply> --normals R [MINCOUNT] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]\n"
     "       pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1]\n"
     "                                                [--rect x0 y0 x1 y1]\n"
@@ -77,6 +80,12 @@ static const char *USAGE =
     "  within R world units, the point itself and exact duplicates included, in the stream's order. --sparse: the other points\n"
     "  instead. Only the points inside --box count, as neighbours too, or inside the box of the file's header. No point to write\n"
     "  is an error.\n"
+    "  --normals R [MINCOUNT]: the points that have at least MINCOUNT points (a whole number >= 0, 3 if left out) within R world\n"
+    "  units, the point itself and exact duplicates included, with the unit normal of that neighbourhood (the eigenvector of the\n"
+    "  least eigenvalue of its covariance; z >= 0) and its curvature l0 / (l0 + l1 + l2), in the stream's order, as a binary\n"
+    "  little-endian PLY: double x y z, uchar red green blue, float nx ny nz, float curvature. R is at most 32767 lattice steps.\n"
+    "  Only the points inside --box count, as neighbours too, or inside the box of the file's header. No point to write is an\n"
+    "  error.\n"
     "  --polygon FILE: only the points inside a polygon, selected on the GPU, in the stream's order. FILE is text in world\n"
     "  coordinates: one vertex `x y` per line, a blank line starts the next ring (a ring inside another is a hole: the even-odd\n"
     "  rule); a ring has at least 3 vertices and is closed implicitly, all rings together at most 4096. A vertex goes to the\n"
@@ -255,6 +264,65 @@ static bool parse_radius(int argc, char **argv, int at, Radius &r)
         }
     }
     return true;
+}
+
+struct Normals {
+    double radius = 0.0;
+    long long min_count = 3;
+    bool has_box = false;
+    double lo[3], hi[3];
+};
+
+// the options behind --normals, every one well formed, or false
+static bool parse_normals(int argc, char **argv, int at, Normals &r)
+{
+    if (argc < at + 2 || std::strcmp(argv[at], "--normals") != 0) return false;
+    if (!parse_double(argv[at + 1], r.radius) || !(r.radius > 0.0)) return false;
+    int i = at + 2;
+    if (i < argc && std::strncmp(argv[i], "--", 2) != 0) {
+        char *end = nullptr;
+        errno = 0;
+        r.min_count = std::strtoll(argv[i], &end, 10);
+        if (end == argv[i] || *end != '\0' || errno == ERANGE || r.min_count < 0) return false;
+        ++i;
+    }
+    for (; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--box" && i + 6 < argc && !r.has_box) {
+            for (int k = 0; k < 6; ++k) if (!parse_double(argv[++i], k < 3 ? r.lo[k] : r.hi[k - 3])) return false;
+            r.has_box = true;
+        } else {
+            return false;
+        }
+    }
+    return true;
+}
+
+// A binary little-endian PLY of the points in world coordinates with their colours, normals and curvatures
+static void write_normals_ply(const std::string &path, const pcr_las_info &info, const std::vector<pcr_point> &points, const std::vector<pcr_eigen> &eigen)
+{
+    FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) throw std::runtime_error(path + ": cannot open for writing");
+    std::fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment pcr_decode --normals\nelement vertex %zu\n"
+                    "property double x\nproperty double y\nproperty double z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n"
+                    "property float nx\nproperty float ny\nproperty float nz\nproperty float curvature\nend_header\n", points.size());
+    std::vector<unsigned char> rec(3 * 8 + 3 + 4 * 4);
+    for (size_t i = 0; i < points.size(); ++i) {
+        const int32_t ints[3] = {points[i].x, points[i].y, points[i].z};
+        double w[3];
+        for (int k = 0; k < 3; ++k) {                       // (two roundings, as Python's x * scale + offset)
+            const double scaled = (double)ints[k] * info.scale[k];
+            w[k] = scaled + info.offset[k];
+        }
+        const pcr_eigen &e = eigen[i];
+        const double sum = e.value[0] + e.value[1] + e.value[2];
+        const float fl[4] = {(float)e.normal[0], (float)e.normal[1], (float)e.normal[2], (float)(sum != 0.0 ? e.value[0] / sum : 0.0)};
+        const unsigned char rgb[3] = {(unsigned char)(points[i].color & 255u), (unsigned char)((points[i].color >> 8) & 255u),
+                                      (unsigned char)((points[i].color >> 16) & 255u)};
+        std::memcpy(rec.data(), w, 24); std::memcpy(rec.data() + 24, rgb, 3); std::memcpy(rec.data() + 27, fl, 16);
+        if (std::fwrite(rec.data(), 1, rec.size(), f) != rec.size()) { std::fclose(f); throw std::runtime_error(path + ": write failed"); }
+    }
+    if (std::fclose(f) != 0) throw std::runtime_error(path + ": write failed");
 }
 
 struct Components {
@@ -528,11 +596,13 @@ int main(int argc, char **argv)
     const bool grounded = argc > 3 && (std::strcmp(argv[3], "--dtm") == 0 || std::strcmp(argv[3], "--height") == 0);
     Radius rad;
     const bool radiused = argc > 3 && std::strcmp(argv[3], "--radius") == 0;
-    const bool boxed = argc > 3 && !viewed && !orthoed && !thinned && !polygoned && !denoised && !componented && !grounded && !radiused;
+    Normals nrm;
+    const bool normaled = argc > 3 && std::strcmp(argv[3], "--normals") == 0;
+    const bool boxed = argc > 3 && !viewed && !orthoed && !thinned && !polygoned && !denoised && !componented && !grounded && !radiused && !normaled;
     if (argc < 3 || (polygoned && !parse_polygon(argc, argv, 3, poly)) || (boxed && !parse_box(argc, argv, 3, lo, hi)) || (viewed && !parse_view(argc, argv, 3, view)) ||
         (orthoed && !parse_ortho(argc, argv, 3, ortho)) || (thinned && !parse_thin(argc, argv, 3, thin)) || (denoised && !parse_denoise(argc, argv, 3, noise)) ||
         (componented && !parse_components(argc, argv, 3, comps)) || (grounded && !parse_ground(argc, argv, 3, ground)) ||
-        (radiused && !parse_radius(argc, argv, 3, rad))) { std::fputs(USAGE, stderr); return 2; }
+        (radiused && !parse_radius(argc, argv, 3, rad)) || (normaled && !parse_normals(argc, argv, 3, nrm))) { std::fputs(USAGE, stderr); return 2; }
     const std::string in = argv[1], out = argv[2];
     try {
         Renderer renderer(viewed ? view.w : 64, viewed ? view.h : 64, 0);
@@ -557,6 +627,20 @@ int main(int argc, char **argv)
         if (grounded && !ground.heights) {
             write_dtm(*las, info, ground, out);
             las->unload(&renderer);
+            return 0;
+        }
+        if (normaled) {
+            const int32_t r = radiusFromWorld(info, nrm.radius);
+            const pcr_box clip = boxFromWorld(info, nrm.has_box ? nrm.lo : info.min, nrm.has_box ? nrm.hi : info.max);
+            std::vector<pcr_eigen> eigen;
+            const pcr_neighbors_stats st = las->normals(r, &clip, nrm.min_count, points, eigen);
+            std::printf("normals: %d lattice steps, written %lld, considered %lld, below min count %lld, voxels %lld, pairs bound %lld\n", r,
+                        (long long)st.points_written, (long long)st.points_considered, (long long)st.points_sparse, (long long)st.voxels,
+                        (long long)st.pairs_bound);
+            las->unload(&renderer);
+            if (points.empty()) throw std::runtime_error("no points to write: nothing written");
+            write_normals_ply(out, info, points, eigen);
+            std::printf("points %lld (batches %lld) -> %s\n", (long long)points.size(), (long long)las->numBatches, out.c_str());
             return 0;
         }
         if (grounded) {

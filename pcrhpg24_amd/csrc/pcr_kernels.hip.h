@@ -22,6 +22,7 @@
 //   k_denoise_*     on request: the records whose 3 x 3 x 3 voxels hold few points (or the others), on k_thin_*'s frame
 //   k_components_*  on request: the connected components of the occupied voxels, the small ones dropped or extracted
 //   k_neighbors_*   on request: per point the points within a radius and the nearest one, from a copy bucketed by voxel
+//   k_moments_*     on request: per point the exact moments of the offsets to the points within a radius, eigenvalues and normal
 //   k_las_*         the 10-10-10 method (modules/compute_loop_las_cuda)
 //   k_resolve_*     framebuffer -> RGBA8 (resolve.cu:149-191, huffman_hqs/resolve.cu:2-47)
 //   k_merge_* / k_flip_sign  multi-GPU partial-framebuffer merges
@@ -3558,6 +3559,267 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_neighbors_write(StreamVi
             if (rows) rows[dst] = row0 + i;
             if (counts) counts[dst] = (int64_t)dense_n[row0 + i];
             if (nn2) nn2[dst] = dense_nn2[row0 + i];
+            ++dst;
+        }
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Local moments (pcr_local_moments / pcr_read_local_moments / pcr_moments_eigen): per candidate the count, the first and the
+// second moments of the offsets d = q - p to the candidates q within `radius` of p (p included), exact int64 sums, and from them
+// the eigenvalues of the covariance and the normal. The plan is pcr_neighbors' up to the filled buckets (k_neighbors_count /
+// _alloc / _fill above); then
+//   k_moments_pairs   k_neighbors_pairs' work distribution (a wave per work item, lane j holds centre j, lanes 0 .. 26 look up one
+//                     neighbour voxel each, the 27 buckets laid end to end, read in tiles of 64 and broadcast by lane reads; no
+//                     LDS, no barrier). Per lane and entry: three subtractions, d2 as there, the offsets masked to 0 where d2 >
+//                     r2, then N, three first moments and six products. radius <= 32767 keeps a masked offset within 16 bits, so
+//                     the products are exact 24-bit multiplies (v_mad_i32_i24, full rate, where the 32 x 32 -> 64 multiply-add
+//                     is not) into 32-bit partial sums: a product is below 2^30, so the squares (unsigned) are flushed into
+//                     the 64-bit sums every 4 entries and the mixed products (signed) every 2; N and the first moments fit 32
+//                     bits over a tile of 64 and are flushed per tile. No early exit: every pair contributes. A valid lane
+//                     sets its keep bit iff n >= min_count, stores its 80-byte record by row and runs moments_eigen in-lane.
+//   k_moments_eigen   moments_eigen over an array of records, a thread each.
+//   k_thin_totals (above) / k_moments_write   k_neighbors_write gathering the 80- and 48-byte records of the kept rows.
+// ------------------------------------------------------------------------------------------------
+static_assert(sizeof(pcr_moments) == 80 && sizeof(pcr_eigen) == 48, "the records k_moments_* store");
+
+// One Jacobi rotation in the (p, q) plane of a symmetric 3 x 3 matrix: app, aqq, apq and, with r the third axis, arp, arq; v holds
+// the eigenvectors as columns. Nothing happens for apq == 0. An overflowing theta * theta gives t = 0 and only clears apq.
+__device__ __forceinline__ void moments_rotate(double &app, double &aqq, double &apq, double &arp, double &arq, double (&v)[3][3], int p, int q)
+{
+#pragma clang fp contract(off)
+    if (apq == 0.0) return;
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
+    const double h = t * apq;
+    app = app - h; aqq = aqq + h; apq = 0.0;
+    const double g = arp, k = arq;
+    arp = g - s * (k + g * tau);
+    arq = k + s * (g - k * tau);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double vp = v[i][p], vq = v[i][q];
+        v[i][p] = vp - s * (vq + vp * tau);
+        v[i][q] = vq + s * (vp - vq * tau);
+    }
+}
+
+// pcr_eigen of a pcr_moments record (include/pcr_hip.h has the definition): out = value[0..2], normal[0..2]. f64, every operation
+// rounded once, only + - * / and sqrt; no NaN or Inf for finite input.
+__device__ __forceinline__ void moments_eigen(const pcr_moments &m, double (&out)[6])
+{
+#pragma clang fp contract(off)
+    if (m.n <= 0) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) out[i] = 0.0;
+        return;
+    }
+    const double nf = (double)m.n;
+    const double mx = (double)m.s[0] / nf, my = (double)m.s[1] / nf, mz = (double)m.s[2] / nf;
+    double a00 = (double)m.q[0] / nf - mx * mx, a01 = (double)m.q[1] / nf - mx * my, a02 = (double)m.q[2] / nf - mx * mz;
+    double a11 = (double)m.q[3] / nf - my * my, a12 = (double)m.q[4] / nf - my * mz, a22 = (double)m.q[5] / nf - mz * mz;
+    double v[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    for (int sweep = 0; sweep < 12 && (a01 != 0.0 || a02 != 0.0 || a12 != 0.0); ++sweep) {
+        moments_rotate(a00, a11, a01, a02, a12, v, 0, 1);
+        moments_rotate(a00, a22, a02, a01, a12, v, 0, 2);
+        moments_rotate(a11, a22, a12, a01, a02, v, 1, 2);
+    }
+    // the least eigenvalue's axis, the lower one at a tie; the values ascending
+    const int k = a22 < (a11 < a00 ? a11 : a00) ? 2 : (a11 < a00 ? 1 : 0);
+    double nx = k == 0 ? v[0][0] : k == 1 ? v[0][1] : v[0][2];
+    double ny = k == 0 ? v[1][0] : k == 1 ? v[1][1] : v[1][2];
+    double nz = k == 0 ? v[2][0] : k == 1 ? v[2][1] : v[2][2];
+    double e0 = a00, e1 = a11, e2 = a22, e;
+    if (e1 < e0) { e = e0; e0 = e1; e1 = e; }
+    if (e2 < e1) { e = e1; e1 = e2; e2 = e; }
+    if (e1 < e0) { e = e0; e0 = e1; e1 = e; }
+    // the sign: the first non-zero of nz, ny, nx is positive. (A chain of selects and an exact multiplication by +-1: as nested
+    // branches, `if (nz < 0 || (nz == 0 && (ny < 0 || ...))) negate`, hipcc -O3 for gfx950 left the lanes with nz == 0 unflipped.)
+    const double lead = nz != 0.0 ? nz : (ny != 0.0 ? ny : nx);
+    const double sign = lead < 0.0 ? -1.0 : 1.0;
+    nx = nx * sign; ny = ny * sign; nz = nz * sign;
+    // (+ 0.0: a negative zero leaves as a positive one, so that equal results are equal bytes)
+    out[0] = e0 + 0.0; out[1] = e1 + 0.0; out[2] = e2 + 0.0;
+    out[3] = nx + 0.0; out[4] = ny + 0.0; out[5] = nz + 0.0;
+}
+
+__device__ __forceinline__ uint4 moments_pack(int64_t a, int64_t b)
+{
+    return make_uint4((uint32_t)(thin_u64)a, (uint32_t)((thin_u64)a >> 32), (uint32_t)(thin_u64)b, (uint32_t)((thin_u64)b >> 32));
+}
+
+// out_m: [a.rows * 5] the pcr_moments records by row, or NULL; out_e: [a.rows * 3] the pcr_eigen records by row, or NULL
+__global__ void __launch_bounds__(256) k_moments_pairs(NeighborsArgs a, thin_u64 items, uint4 *out_m, uint4 *out_e)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    thin_u64 bound = 0, sparse_total = 0;                   // this wave's share of pairs_bound and of the sparse candidates
+    // (no barrier below: a wave is on its own; it takes every (waves of the grid)-th work item)
+    for (thin_u64 wi = neighbors_uniform((thin_u64)blockIdx.x * 4u + (threadIdx.x >> 6)); wi < items; wi += (thin_u64)gridDim.x * 4u) {
+    const thin_u64 item = neighbors_uniform(a.work[wi]);
+    const uint32_t slot = (uint32_t)(item >> 32), chunk = (uint32_t)item;
+    const ThinSlot *table = a.t.table;
+    const thin_u64 key = neighbors_uniform(table[slot].key), own = neighbors_uniform(table[slot].val);     // (k_neighbors_alloc's value)
+    const thin_u64 count = (own & 0xFFFFFFFFull) + 1ull, own_start = own >> 32;
+    const thin_u64 idx = (thin_u64)chunk * 64u + lane;
+    const bool valid = idx < count && own_start + idx < a.candidates;
+    const uint4 centre = valid ? a.bucket[own_start + idx] : make_uint4(0, 0, 0, 0);
+
+    // lane n < 27: the bucket of neighbour voxel n (13 is the chunk's own); lanes 27 .. 63 hold empty ones
+    uint32_t nb_start = 0;
+    thin_u64 nb_count = 0;
+    if (lane < 27u) {
+        uint32_t at = slot;
+        if (lane == 13u || components_lookup(table, a.t.log2_slots, neighbors_key(key, (int)lane), at)) {
+            const thin_u64 v = table[at].val;
+            nb_start = (uint32_t)(v >> 32);
+            nb_count = (v & 0xFFFFFFFFull) + 1ull;
+        }
+    }
+    thin_u64 nb_excl = nb_count;                            // the 27 buckets laid end to end, as in k_neighbors_pairs
+#pragma unroll
+    for (int d = 1; d < 32; d <<= 1) {
+        const thin_u64 up = __shfl_up(nb_excl, d, 64);
+        if (lane >= (uint32_t)d) nb_excl += up;
+    }
+    const thin_u64 total = neighbors_uniform(__shfl(nb_excl, 26, 64));
+    nb_excl -= nb_count;
+    const uint32_t excl_lo = (uint32_t)nb_excl, excl_hi = (uint32_t)(nb_excl >> 32), count_lo = (uint32_t)nb_count, count_hi = (uint32_t)(nb_count >> 32);
+
+    bound += (thin_u64)__popcll(__ballot(valid)) * total;
+
+    int64_t n_in = 0, sx = 0, sy = 0, sz = 0, qxy = 0, qxz = 0, qyz = 0;
+    thin_u64 qxx = 0, qyy = 0, qzz = 0;
+    for (thin_u64 t0 = 0; t0 < total; t0 += 64u) {
+        const int m = (int)min((thin_u64)64u, total - t0);
+        const thin_u64 g = t0 + lane;                       // this lane's entry of the tile
+        thin_u64 at = ~0ull;
+        for (int nb = 0; nb < 27; ++nb) {                   // (every value read here is wave-uniform)
+            const thin_u64 e = ((thin_u64)(uint32_t)__builtin_amdgcn_readlane((int)excl_hi, nb) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)excl_lo, nb);
+            const thin_u64 c = ((thin_u64)(uint32_t)__builtin_amdgcn_readlane((int)count_hi, nb) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)count_lo, nb);
+            if (c == 0ull || e >= t0 + 64u || e + c <= t0) continue;
+            const thin_u64 first = (uint32_t)__builtin_amdgcn_readlane((int)nb_start, nb);
+            if (g >= e && g - e < c) at = first + (g - e);
+        }
+        const bool have = lane < (uint32_t)m && at < a.candidates;
+        const uint4 tile = have ? a.bucket[at] : make_uint4(0, 0, 0, 0);
+        int32_t n32 = 0, sx32 = 0, sy32 = 0, sz32 = 0;      // a tile's share: at most 64, at most 64 * 32767
+        uint32_t xx32 = 0, yy32 = 0, zz32 = 0;              // at most 4 squares, each below 2^30
+        int32_t xy32 = 0, xz32 = 0, yz32 = 0;               // at most 2 products, each below 2^30 in magnitude
+        // entry k of the tile: offsets from the centre, masked to 0 outside the sphere (then every factor fits 16 bits)
+#define PCR_MOMENTS_ENTRY(k)                                                                                                              \
+        {                                                                                                                                 \
+            const int32_t ex = (int32_t)((uint32_t)__builtin_amdgcn_readlane((int)tile.x, (k)) - centre.x);                              \
+            const int32_t ey = (int32_t)((uint32_t)__builtin_amdgcn_readlane((int)tile.y, (k)) - centre.y);                              \
+            const int32_t ez = (int32_t)((uint32_t)__builtin_amdgcn_readlane((int)tile.z, (k)) - centre.z);                              \
+            const thin_u64 d2 = (thin_u64)((int64_t)ex * ex) + (thin_u64)((int64_t)ey * ey) + (thin_u64)((int64_t)ez * ez);             \
+            const bool in = d2 <= a.r2;                                                                                                   \
+            const int32_t dx = in ? ex : 0, dy = in ? ey : 0, dz = in ? ez : 0;                                                           \
+            n32 += in ? 1 : 0; sx32 += dx; sy32 += dy; sz32 += dz;                                                                        \
+            xx32 += (uint32_t)__mul24(dx, dx); yy32 += (uint32_t)__mul24(dy, dy); zz32 += (uint32_t)__mul24(dz, dz);                      \
+            xy32 += __mul24(dx, dy); xz32 += __mul24(dx, dz); yz32 += __mul24(dy, dz);                                                    \
+        }
+#define PCR_MOMENTS_FLUSH_MIXED() { qxy += xy32; qxz += xz32; qyz += yz32; xy32 = xz32 = yz32 = 0; }
+#define PCR_MOMENTS_FLUSH_SQUARES() { qxx += xx32; qyy += yy32; qzz += zz32; xx32 = yy32 = zz32 = 0u; }
+        int k = 0;
+        for (; k + 4 <= m; k += 4) {
+            PCR_MOMENTS_ENTRY(k) PCR_MOMENTS_ENTRY(k + 1) PCR_MOMENTS_FLUSH_MIXED()
+            PCR_MOMENTS_ENTRY(k + 2) PCR_MOMENTS_ENTRY(k + 3) PCR_MOMENTS_FLUSH_MIXED()
+            PCR_MOMENTS_FLUSH_SQUARES()
+        }
+        for (; k < m; ++k) {                                // (at most 3 entries)
+            PCR_MOMENTS_ENTRY(k) PCR_MOMENTS_FLUSH_MIXED()
+        }
+        PCR_MOMENTS_FLUSH_SQUARES()
+#undef PCR_MOMENTS_ENTRY
+#undef PCR_MOMENTS_FLUSH_MIXED
+#undef PCR_MOMENTS_FLUSH_SQUARES
+        n_in += n32; sx += sx32; sy += sy32; sz += sz32;
+    }
+    const bool sparse = valid && (thin_u64)n_in < a.min_count;
+    if (valid && centre.w < a.rows) {                       // (k_neighbors_fill wrote every entry: the row is one of the range)
+        const thin_u64 row = centre.w;
+        pcr_moments rec;
+        rec.n = n_in; rec.s[0] = sx; rec.s[1] = sy; rec.s[2] = sz;
+        rec.q[0] = (int64_t)qxx; rec.q[1] = qxy; rec.q[2] = qxz; rec.q[3] = (int64_t)qyy; rec.q[4] = qyz; rec.q[5] = (int64_t)qzz;
+        if (out_m) {
+            uint4 *dst = out_m + row * 5u;
+            dst[0] = moments_pack(rec.n, rec.s[0]); dst[1] = moments_pack(rec.s[1], rec.s[2]); dst[2] = moments_pack(rec.q[0], rec.q[1]);
+            dst[3] = moments_pack(rec.q[2], rec.q[3]); dst[4] = moments_pack(rec.q[4], rec.q[5]);
+        }
+        if (out_e) {
+            double e[6];
+            moments_eigen(rec, e);
+            uint4 *dst = out_e + row * 3u;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) dst[i] = moments_pack(__double_as_longlong(e[2 * i]), __double_as_longlong(e[2 * i + 1]));
+        }
+        if (!sparse) atomicOr(&a.keep[row >> 6], 1ull << (row & 63u));
+    }
+    sparse_total += (thin_u64)__popcll(__ballot(sparse));
+    }
+    if (lane == 0) {
+        if (bound) atomicAdd(&a.counters[NEIGHBORS_PAIRS_BOUND + (blockIdx.x & 63u)], bound);
+        if (sparse_total) atomicAdd(&a.counters[NEIGHBORS_SPARSE + (blockIdx.x & 63u)], sparse_total);
+    }
+}
+
+// moments: [n] pcr_moments, eigen: [n] pcr_eigen, both 8-byte aligned
+__global__ void __launch_bounds__(256) k_moments_eigen(const int64_t *moments, thin_u64 n, double *eigen)
+{
+    const thin_u64 i = (thin_u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t *src = moments + i * 10u;
+    pcr_moments rec;
+    rec.n = src[0];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) rec.s[k] = src[1 + k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) rec.q[k] = src[4 + k];
+    double e[6];
+    moments_eigen(rec, e);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) eigen[i * 6u + (thin_u64)k] = e[k];
+}
+
+// k_neighbors_write gathering the 80-byte and 48-byte records of the written rows from the dense arrays (any of the four outputs
+// may be NULL; moments and eigen are 8-byte aligned, so they are stored word by word)
+template <int LAYOUT, bool BC7>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_moments_write(StreamView s, const uint32_t *list, uint32_t first_batch, const thin_u64 *keep,
+                                                                      const int64_t *offsets, const thin_u64 *dense_m, const thin_u64 *dense_e,
+                                                                      uint4 *points, int64_t *rows, thin_u64 *moments, thin_u64 *eigen)
+{
+    const uint32_t b = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint32_t s_part[LWC_WAVES];
+    const thin_u64 word = keep[(size_t)(b - first_batch) * PCR_WORKGROUP_SIZE + tid];
+    const uint32_t mine = (uint32_t)__popcll(word);
+    uint32_t incl = mine;                                   // inclusive prefix inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += up;
+    }
+    if (lane == 63) s_part[wave] = incl;
+    load_packed_table(s, b, s_table);                       // (its barrier publishes s_part as well)
+    uint32_t before = incl - mine;
+    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    int64_t dst = offsets[blockIdx.x] + before;
+    const int64_t end = dst + mine;                         // never past the bits of this chain's word
+    const int64_t row0 = (int64_t)(b - first_batch) * PCR_POINTS_PER_BATCH + (int64_t)tid * PCR_POINTS_PER_THREAD;
+    decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        if (((word >> (uint32_t)i) & 1ull) && dst < end) {
+            if (points) points[dst] = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
+            if (rows) rows[dst] = row0 + i;
+            if (moments) {
+#pragma unroll
+                for (int k = 0; k < 10; ++k) moments[dst * 10 + k] = dense_m[(row0 + i) * 10 + k];
+            }
+            if (eigen) {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) eigen[dst * 6 + k] = dense_e[(row0 + i) * 6 + k];
+            }
             ++dst;
         }
     });

@@ -416,6 +416,27 @@ struct HuffmanLasData : Resource {
         return st;
     }
 
+    // The points inside `clip` (NULL: everywhere) that have at least min_count of them within `radius` lattice steps (1 ..
+    // PCR_MOMENTS_MAX_RADIUS), the point itself and exact duplicates included, with the eigenvalues of their neighbourhood's
+    // covariance and its unit normal, on the GPU straight from the compressed stream (pcr_read_local_moments: a counting call,
+    // then the read). moments (may be NULL): the exact moments the eigen records were made from. Not in the reference.
+    pcr_neighbors_stats normals(int32_t radius, const pcr_box *clip, int64_t min_count, std::vector<pcr_point> &out, std::vector<pcr_eigen> &eigen,
+                                std::vector<pcr_moments> *moments = nullptr)
+    {
+        if (!loadedOn) throw std::runtime_error("normals: the resource is not loaded");
+        const int64_t nB = pcr_batches_resident(loadedOn->ctx);
+        int64_t n = 0;
+        pcr_neighbors_stats st{};
+        loadedOn->check(pcr_read_local_moments(loadedOn->ctx, 0, nB, radius, clip, min_count, nullptr, nullptr, nullptr, nullptr, 0, &n, &st),
+                        "pcr_read_local_moments");
+        out.resize((size_t)n);
+        eigen.resize((size_t)n);
+        if (moments) moments->resize((size_t)n);
+        if (n) loadedOn->check(pcr_read_local_moments(loadedOn->ctx, 0, nB, radius, clip, min_count, out.data(), nullptr, moments ? moments->data() : nullptr,
+                                                      eigen.data(), out.size(), &n, &st), "pcr_read_local_moments");
+        return st;
+    }
+
     // The points a frame of camera `p` draws whose pixel lies in `rect` (NULL: the whole image), with where they land, selected on
     // the GPU (pcr_read_screen: a counting call, then the read). Either vector may be NULL. Not in the reference.
     pcr_screen_stats selectScreen(const pcr_render_params &p, const pcr_rect *rect, std::vector<pcr_point> *points, std::vector<pcr_screen_hit> *hits)

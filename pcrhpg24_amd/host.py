@@ -186,7 +186,9 @@ def read_las(path: str):
 POINT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("color", "<u4")])     # pcr_point
 
 HIT_DTYPE = np.dtype([("pixel", "<u4"), ("depth_bits", "<u4"), ("index", "<i8")])          # pcr_screen_hit
-ROW_DTYPE = np.dtype("<i8")                                                                  # a row of pcr_thin
+MOMENTS_DTYPE = np.dtype([("n", "<i8"), ("s", "<i8", (3,)), ("q", "<i8", (6,))])              # pcr_moments; q: xx, xy, xz, yy, yz, zz
+EIGEN_DTYPE = np.dtype([("value", "<f8", (3,)), ("normal", "<f8", (3,))])                   # pcr_eigen
+ROW_DTYPE = np.dtype("<i8")                                                                # a row of pcr_thin
 
 INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
 
@@ -473,6 +475,36 @@ def radius_from_world(las: LasInfo, radius: float) -> int:
     if r < 1 or r > N.NEIGHBORS_MAX_RADIUS:
         raise ValueError(f"a radius of {radius} is {r} lattice steps of {sx}: 1 .. {N.NEIGHBORS_MAX_RADIUS}")
     return r
+
+
+def covariance_from_moments(moments) -> np.ndarray:
+    """The covariance matrices [n, 3, 3] (float64) of pcr_moments records -- a MOMENTS_DTYPE array or an int [n, 10] array of n, s,
+    q (xx, xy, xz, yy, yz, zz) -- by pcr_moments_eigen's formula, every operation rounded once: nf = float(n), m_a = float(s_a) /
+    nf, C_ab = float(q_ab) / nf - m_a * m_b. Zero for n <= 0."""
+    m = np.asarray(moments)
+    if m.dtype == MOMENTS_DTYPE:
+        m = m.view("<i8").reshape(-1, 10)
+    m = m.reshape(-1, 10).astype(np.int64)
+    ok = m[:, 0] > 0
+    nf = np.where(ok, m[:, 0], 1).astype(np.float64)
+    mean = m[:, 1:4].astype(np.float64) / nf[:, None]
+    out = np.zeros((len(m), 3, 3), np.float64)
+    for k, (a, b) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+        out[:, a, b] = out[:, b, a] = m[:, 4 + k].astype(np.float64) / nf - mean[:, a] * mean[:, b]
+    out[~ok] = 0.0
+    return out
+
+
+def geometric_features(values) -> dict:
+    """From ascending eigenvalues l0 <= l1 <= l2 ([n, 3]; numpy, or a torch tensor that is brought to the host): float64 arrays of
+    curvature l0 / (l0 + l1 + l2), linearity (l2 - l1) / l2, planarity (l1 - l0) / l2 and scattering l0 / l2, each 0 where its
+    denominator is 0."""
+    v = np.asarray(values.cpu() if hasattr(values, "cpu") else values, np.float64).reshape(-1, 3)
+    l0, l1, l2 = v[:, 0], v[:, 1], v[:, 2]
+
+    def ratio(num, den):
+        return np.where(den != 0.0, num / np.where(den != 0.0, den, 1.0), 0.0)
+    return dict(curvature=ratio(l0, l0 + l1 + l2), linearity=ratio(l2 - l1, l2), planarity=ratio(l1 - l0, l2), scattering=ratio(l0, l2))
 
 
 def voxels_from_world(las: LasInfo, cell_size: float, origin=None) -> Voxels:
@@ -1243,6 +1275,80 @@ class Context:
         res = (pts,) + tuple(a for a in extra if a is not None)
         return res if len(res) > 1 else res[0]
 
+    # -- local moments (pcr_local_moments / pcr_read_local_moments / pcr_moments_eigen) ------------------------
+    def local_moments(self, radius: int, min_count: int = 1, clip=None, first: int = 0, count: Optional[int] = None, out=None,
+                      rows: bool = False, moments: bool = False, eigen: bool = False):
+        """The rows of batches [first, first + count) inside `clip` (as_box; None: everywhere) that have at least `min_count` rows of
+        the range and clip within `radius` lattice steps (1 .. MOMENTS_MAX_RADIUS), the row itself included, straight from the
+        compressed stream. Results, `out`, rows=True and stream ordering as Context.neighbors; moments=True appends an int64
+        tensor [n, 10] of the exact moments of the offsets to the rows within the radius (n, s x y z, q xx xy xz yy yz zz),
+        eigen=True a float64 tensor [n, 6] (the eigenvalues of the covariance, ascending, and the unit normal): points, then rows,
+        moments, eigen as asked for. What the last call did is in self.moments_stats."""
+        import torch
+        clip = None if clip is None else as_box(clip)
+        cp = None if clip is None else C.byref(clip)
+        dev = torch.device("cuda", self.device)
+        cnt, st, nb = c_i64(), NeighborsStats(), -1 if count is None else count
+        if out is None:
+            self._chk(self.lib.pcr_local_moments(self.h, first, nb, radius, cp, min_count, None, None, None, None, 0, C.byref(cnt), C.byref(st)),
+                      "pcr_local_moments")
+            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
+        cap = out.numel() // 4
+        extra = [torch.empty(shape, dtype=dt, device=dev) if want else None
+                 for want, shape, dt in ((rows, (cap,), torch.int64), (moments, (cap, 10), torch.int64), (eigen, (cap, 6), torch.float64))]
+        torch.cuda.current_stream(dev).synchronize()
+        ptrs = [C.c_void_p(t.data_ptr() if cap else None) if t is not None else None for t in extra]
+        rc = self.lib.pcr_local_moments(self.h, first, nb, radius, cp, min_count, C.c_void_p(out.data_ptr() if cap else None), ptrs[0], ptrs[1], ptrs[2],
+                                        cap, C.byref(cnt), C.byref(st))
+        self.moments_stats = st.as_dict()
+        if rc:
+            self.moments_stats["points_written"] = cnt.value
+        self._chk(rc, "pcr_local_moments")
+        res = (out.view(-1, 4)[:cnt.value],) + tuple(t[:cnt.value] for t in extra if t is not None)
+        return res if len(res) > 1 else res[0]
+
+    def read_local_moments(self, radius: int, min_count: int = 1, clip=None, first: int = 0, count: Optional[int] = None, rows: bool = False,
+                           moments: bool = False, eigen: bool = False):
+        """The same on the host, without torch: a numpy structured array of POINT_DTYPE, followed as asked for by an int64 array of
+        the rows, a MOMENTS_DTYPE array and an EIGEN_DTYPE array (pcr_read_local_moments: a counting call, then the read;
+        synchronises)."""
+        clip = None if clip is None else as_box(clip)
+        cp = None if clip is None else C.byref(clip)
+        cnt, st, nb = c_i64(), NeighborsStats(), -1 if count is None else count
+        self._chk(self.lib.pcr_read_local_moments(self.h, first, nb, radius, cp, min_count, None, None, None, None, 0, C.byref(cnt), C.byref(st)),
+                  "pcr_read_local_moments")
+        pts = np.empty(cnt.value, POINT_DTYPE)
+        extra = [np.empty(cnt.value, dt) if want else None for want, dt in ((rows, ROW_DTYPE), (moments, MOMENTS_DTYPE), (eigen, EIGEN_DTYPE))]
+        if cnt.value:
+            self._chk(self.lib.pcr_read_local_moments(self.h, first, nb, radius, cp, min_count, pts.ctypes.data,
+                                                      *[None if a is None else a.ctypes.data for a in extra], len(pts), C.byref(cnt), C.byref(st)),
+                      "pcr_read_local_moments")
+        self.moments_stats = st.as_dict()
+        res = (pts,) + tuple(a for a in extra if a is not None)
+        return res if len(res) > 1 else res[0]
+
+    def moments_eigen(self, moments):
+        """pcr_moments_eigen: the eigen records of moments records. An int64 torch tensor [n, 10] on this context's device gives a
+        float64 tensor [n, 6] there; a numpy array (MOMENTS_DTYPE, or int64 [n, 10]) is uploaded and gives an EIGEN_DTYPE array.
+        Needs no stream loaded; synchronises."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        on_host = not isinstance(moments, torch.Tensor)
+        if on_host:
+            m = np.ascontiguousarray(moments)
+            m = m.view("<i8") if m.dtype == MOMENTS_DTYPE else m.astype(np.int64, copy=False)
+            moments = torch.from_numpy(m.reshape(-1, 10).copy()).to(dev)
+        if moments.dtype != torch.int64 or moments.device != dev or not moments.is_contiguous() or moments.dim() != 2 or moments.shape[1] != 10:
+            raise ValueError(f"moments must be a contiguous int64 tensor [n, 10] on {dev}")
+        n = moments.shape[0]
+        out = torch.empty((n, 6), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        self._chk(self.lib.pcr_moments_eigen(self.h, C.c_void_p(moments.data_ptr() if n else None), n, C.c_void_p(out.data_ptr() if n else None)),
+                  "pcr_moments_eigen")
+        return out.cpu().numpy().reshape(-1).view(EIGEN_DTYPE) if on_host else out
+
     # -- screen selection and picking (pcr_select_screen / pcr_read_screen / pcr_pick) ---------------------
     def select_screen(self, p: RenderParams, rect=None):
         """The points a frame of camera `p` draws (render_basic's cull, level of detail, precision and inside test) whose pixel lies
@@ -1801,6 +1907,20 @@ class HuffmanLasData(Resource):
         scale = float(info.scale[0]) if world else 1.0
         spacing = torch.where(nn2 < 0, torch.full_like(nn2, float("inf"), dtype=torch.float64), torch.sqrt(nn2.to(torch.float64)) * scale)
         return pts, n, spacing
+
+    def normals(self, renderer: Renderer, radius: float, min_count: int = 3, lo=None, hi=None, world: bool = True):
+        """Per point of the loaded resource inside the clip that has at least `min_count` points within `radius` (itself and exact
+        duplicates included): (points, normals, curvature) -- the int32 records, the unit normal of the neighbourhood's covariance
+        (float64 [n, 3]; its sign is pcr_eigen's, not a viewpoint's) and the curvature l0 / (l0 + l1 + l2) (float64, 0 where the
+        sum is 0), on the GPU straight from the compressed stream (Context.local_moments). radius, lo, hi and world as for
+        radius_filtered(); radius_from_world refuses differing axis scales, so the normal of the lattice is the world's."""
+        import torch
+        info = self.las_info()
+        r, clip = self._neighbors_clip(info, radius, lo, hi, world)
+        pts, eig = renderer.ctx.local_moments(r, min_count, clip, eigen=True)
+        total = eig[:, 0] + eig[:, 1] + eig[:, 2]
+        curvature = torch.where(total != 0.0, eig[:, 0] / torch.where(total != 0.0, total, torch.ones_like(total)), torch.zeros_like(total))
+        return pts, eig[:, 3:6], curvature
 
     def las_info(self) -> LasInfo:
         """Scale, offset, min and max of the LAS file the stream was made from, as its first batch record carries them (the
