@@ -20,9 +20,13 @@ PPB = 65536
 
 
 def stream(name: str):
-    """The .huffman image of a named stream: those of tests/select_cases.py, and the scenes of tests/contention.py."""
+    """The .huffman image of a named stream: those of tests/select_cases.py and tests/decoder_cases.py, and the scenes of
+    tests/contention.py."""
     if name in ("synth", "clustered", "garbage_tail", "escape_heavy", "wide30"):
         return S.stream(name)
+    if name.startswith("decoder/"):                     # "decoder/<stream>-<padded|plain>[-bc7]": tests/decoder_cases.py
+        from tests import decoder_cases
+        return decoder_cases.stream_by_id(name[len("decoder/"):])
     return contention.stream(name)[0].view()
 
 

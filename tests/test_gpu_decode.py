@@ -174,6 +174,7 @@ def las_for(lo, hi, scale=0.001):
 
 @pytest.mark.parametrize("hop_bits", [30, 20])
 def test_wide_table_values(ctx, hop_bits):
+    """(The packed entry's real limit is 2^21, with -2^21 as its sentinel: the `limits` stream of tests/test_gpu_decoder.py sits on it.)"""
     rng = np.random.default_rng(21)
     n = 65536 * 2
     hop = np.where(np.arange(n) % 2 == 0, 0, 1 << hop_bits).astype(np.int64)
