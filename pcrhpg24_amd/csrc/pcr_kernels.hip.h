@@ -721,6 +721,8 @@ __device__ __forceinline__ uint32_t lod_prepass_batch(const RenderArgs &a, int64
 // BC1 block -> its four palette colours (render.cu:31-62, always 4-colour mode), one register per channel: byte k of
 // r / g / b is that channel of palette entry k. A point's colour 0x00BBGGRR is then two v_perm_b32 with selectors built from
 // its 2-bit index -- five instructions per point, no compare/select chain.
+// ("Always 4-colour mode", c0 <= c1 included, and every (e0, e1, selector) of every channel at every local position are held against
+// a numpy restatement of the rule by tests/test_gpu_colour.py, on the constructed blocks of tests/colour_cases.py.)
 struct Bc1Palette { uint32_t r, g, b, selectors; };
 
 __device__ __forceinline__ Bc1Palette bc1_palette(uint2 blk)
@@ -761,6 +763,8 @@ __device__ __forceinline__ void bc1_contribution(const Bc1Palette &p, uint32_t l
 // endpoints = 7 bits << 1 | p-bit, the 4-bit field at 4 * local of the high quadword as the index of EVERY pixel (so pixel 0
 // gets index << 1 | p1: reproduced), weight = round(idx * 64 / 15) = (idx * 64 + 7) / 15, channel = (e0 (64 - w) + e1 w + 32) >> 6.
 // Kept per 16-point block as: r | b << 16 of endpoint 0, of endpoint 1, g0 | g1 << 16, and the two index words.
+// (The mode bits are ignored. That, pixel 0's field and every (E0, E1, index) of every channel are held against a numpy restatement
+// of the rule by tests/test_gpu_colour.py, on the constructed blocks of tests/colour_cases.py.)
 struct Bc7Block { uint32_t rb0, rb1, g01, idx_lo, idx_hi; };
 __device__ __forceinline__ Bc7Block bc7_block(uint4 blk)
 {
