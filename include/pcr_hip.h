@@ -588,6 +588,39 @@ int pcr_read_local_moments(pcr_ctx *ctx, int64_t first_batch, int64_t count, int
                            size_t capacity_points, int64_t *out_count, pcr_neighbors_stats *stats);
 int pcr_moments_eigen(pcr_ctx *ctx, const void *dev_moments, int64_t n, void *dev_eigen);
 
+/* ---- k nearest neighbours: per point the k nearest other points within a radius, exact (no reference counterpart) ---------------
+ * Candidates are pcr_neighbors' own, padding duplicates and the tail artefact included. d2(p, q) is the squared distance of the
+ * integer coordinates in exact integer arithmetic. The neighbours of a candidate p are the candidates q of ANOTHER ROW with d2(p,
+ * q) <= radius * radius: an exact duplicate is a neighbour at d2 == 0, a point at exactly the radius is one. They are ordered by
+ * (d2, row) ascending, row being the row in pcr_decode_points order relative to first_batch; rows are distinct, so the order is
+ * total. knn(p) is the first found(p) = min(k, N(p) - 1) of them, N as pcr_neighbors defines it. CANONICAL: the result depends on
+ * no hash, table size, bucket order or order of lanes, workgroups and launches and is the same bytes from run to run.
+ * Limits: 1 <= k <= PCR_KNN_MAX_K, 1 <= radius <= PCR_KNN_MAX_RADIUS. With these d2 < 2^30, and a call has at most 2^32 rows, so a
+ * neighbour is one 64-bit word d2 << 32 | row whose unsigned order is the order above.
+ * A candidate is written iff found(p) >= min_found, 0 <= min_found <= k (0: all of them): its 16-byte record to dev_points (16-byte
+ * aligned), its row to dev_rows (int64) and its k words to dev_knn (uint64 [n * k], entry j of written record i at i * k + j,
+ * entries found .. k - 1 are PCR_KNN_NONE; each 8-byte aligned), all in increasing row order, packed. Any pointer may be NULL; all
+ * three NULL only counts. A capacity below the result is PCR_E_ARG with *out_count = the count needed and nothing written. stats
+ * are pcr_neighbors': points_sparse = the candidates with found < min_found, pairs_bound as there. PCR_E_ARG with a message,
+ * nothing written: pcr_neighbors' refusals word for word (range, alignment, more than 2^32 rows, the lattice rule with cell =
+ * radius and its advice to pass a clip or a larger radius), and k, radius or min_found outside their ranges. The call
+ * synchronises, touches no framebuffer, no prepass state, no render statistics; BC1 and BC7, either resident layout, before and
+ * after the first frame.
+ *   How: pcr_neighbors' plan up to the filled buckets; k_knn_pairs<K> (K = the least of 1, 2, 4, 8, 16 that holds k) has
+ *   k_neighbors_pairs' work distribution and keeps per lane the K least words in registers, sorted, by an insertion pass that runs
+ *   only where some lane of the wave has a word below its K-th; it stores the first k words by row; k_knn_write gathers the words
+ *   of the kept rows. No early exit, no pruning of voxels: the cost is pcr_neighbors' ALL call (stats.pairs_bound tests) plus the
+ *   insertions. With min_found == 0 and dev_knn == NULL the pair kernel decides nothing but runs all the same (pairs_bound comes
+ *   from it). Scratch: pcr_neighbors' plus k * 8 bytes per row of the range when dev_knn is asked for (PCR_E_NOMEM: pass a clip or
+ *   a shorter range).
+ * pcr_read_knn: the same into host memory (alignof(pcr_point) / alignof(int64_t)), in pieces through staging buffers as
+ * pcr_read_local_moments. */
+int pcr_knn(pcr_ctx *ctx, int64_t first_batch, int64_t count, int k, int32_t radius, const pcr_box *clip, int64_t min_found,
+            void *dev_points, void *dev_rows, void *dev_knn, size_t capacity_points, int64_t *out_count, pcr_neighbors_stats *stats);
+int pcr_read_knn(pcr_ctx *ctx, int64_t first_batch, int64_t count, int k, int32_t radius, const pcr_box *clip, int64_t min_found,
+                 pcr_point *host_points, int64_t *host_rows, uint64_t *host_knn, size_t capacity_points, int64_t *out_count,
+                 pcr_neighbors_stats *stats);
+
 /* What a collective library needs to merge partial frames in place (include/pcr_dist.h does it with RCCL): the HIP stream
  * the context enqueues on, its device ordinal and the length of each framebuffer in 64-bit words. */
 void *pcr_get_stream(pcr_ctx *ctx);

@@ -342,6 +342,13 @@ typedef struct pcr_eigen {
     double normal[3];
 } pcr_eigen;
 
+/* pcr_knn: a neighbour is one 64-bit word d2 << 32 | row -- the squared distance (below 2^30 with radius <= PCR_KNN_MAX_RADIUS) over
+ * the row relative to first_batch (a call has at most 2^32 rows); the unsigned order of the words is the order (d2, row).
+ * PCR_KNN_NONE fills the entries behind the last neighbour found. */
+#define PCR_KNN_MAX_K       16
+#define PCR_KNN_MAX_RADIUS  32767
+#define PCR_KNN_NONE        UINT64_MAX
+
 /* A rectangle of pixels (pcr_select_screen), bounds inclusive, clipped to the image by the call. x0 > x1 or y0 > y1: the
  * empty rect. */
 typedef struct pcr_rect {

@@ -175,6 +175,7 @@ class Eigen(C.Structure):                         # pcr_eigen: the eigenvalues o
 
 
 MOMENTS_MAX_RADIUS = 32767                                                                              # pcr_types.h
+KNN_MAX_K, KNN_MAX_RADIUS, KNN_NONE = 16, 32767, (1 << 64) - 1                                          # pcr_types.h
 
 
 class Rect(C.Structure):                          # pcr_rect: pixel bounds, inclusive; x0 > x1 or y0 > y1 = empty
@@ -243,6 +244,7 @@ HIP_SYMBOLS = [
     "pcr_components", "pcr_read_components",
     "pcr_neighbors", "pcr_read_neighbors",
     "pcr_local_moments", "pcr_read_local_moments", "pcr_moments_eigen",
+    "pcr_knn", "pcr_read_knn",
 ]
 
 HOST_SYMBOLS = [
@@ -389,6 +391,9 @@ def hip_lib() -> C.CDLL:
             getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, c_i32, C.POINTER(Box), c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_size_t, C.POINTER(c_i64), C.POINTER(NeighborsStats)]
         lib.pcr_moments_eigen.argtypes = [C.c_void_p, C.c_void_p, c_i64, C.c_void_p]
+        for n in ("pcr_knn", "pcr_read_knn"):
+            getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.c_int, c_i32, C.POINTER(Box), c_i64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.POINTER(c_i64), C.POINTER(NeighborsStats)]
         _hip = lib
     return _hip
 

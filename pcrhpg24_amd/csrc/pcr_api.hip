@@ -202,6 +202,11 @@ struct pcr_ctx {
     int64_t moments_stage_batches = 0;
     pcr_eigen *d_moments_eigen_stage = nullptr;         // [moments_eigen_stage_batches * 65536]
     int64_t moments_eigen_stage_batches = 0;
+    // k nearest neighbours (pcr_knn / pcr_read_knn) share pcr_neighbors' index; their own: the dense words and the stage
+    unsigned long long *d_knn_dense = nullptr;          // [knn_dense_words] k words by row, only once asked for
+    int64_t knn_dense_words = 0;
+    uint64_t *d_knn_stage = nullptr;                    // [knn_stage_words]
+    int64_t knn_stage_words = 0;
     int64_t components_labels_stage_batches = 0;
     int64_t prepass_batches = 0;
     static constexpr int FENCES = 8;
@@ -314,6 +319,7 @@ void free_stream_buffers(pcr_ctx *c)
     dfree(c->d_neighbors_counts_stage); c->neighbors_counts_stage_batches = 0; dfree(c->d_neighbors_nn2_stage); c->neighbors_nn2_stage_batches = 0;
     dfree(c->d_moments_dense); c->moments_dense_rows = 0; dfree(c->d_moments_eigen); c->moments_eigen_rows = 0;
     dfree(c->d_moments_stage); c->moments_stage_batches = 0; dfree(c->d_moments_eigen_stage); c->moments_eigen_stage_batches = 0;
+    dfree(c->d_knn_dense); c->knn_dense_words = 0; dfree(c->d_knn_stage); c->knn_stage_words = 0;
 
     if (c->any_generic_pending && c->any_generic_ev) (void)hipEventSynchronize(c->any_generic_ev);
     c->any_generic_pending = false;
@@ -3084,9 +3090,12 @@ namespace {
 // dense arrays a later neighbors_emit gathers from. Fills the plan neighbors_emit takes (p.st is not used) and st. Synchronises.
 // mom (pcr_local_moments): the same sequence with k_moments_pairs in k_neighbors_pairs' place, which keeps the rows with N >=
 // min_count and fills the dense pcr_moments / pcr_eigen records asked for; mode, want_n and want_nn2 are not used then.
+// knn (pcr_knn): the same sequence with k_knn_pairs<K> there, K the least of 1, 2, 4, 8, 16 that holds k, which keeps the rows with
+// found >= min_count (the call's min_found) and fills the dense words if asked for; mode, want_n and want_nn2 are not used then.
 struct MomentsWant { bool moments, eigen; };
+struct KnnWant { int k; bool words; };
 int neighbors_plan(pcr_ctx *c, int64_t first, int64_t n, int32_t radius, const pcr_box *clip, int64_t min_count, int mode, bool want_n, bool want_nn2,
-                   ThinPlan &p, pcr_neighbors_stats &st, const MomentsWant *mom = nullptr)
+                   ThinPlan &p, pcr_neighbors_stats &st, const MomentsWant *mom = nullptr, const KnnWant *knn = nullptr)
 {
     st = pcr_neighbors_stats{};
     VoxelPlan v;
@@ -3108,6 +3117,9 @@ int neighbors_plan(pcr_ctx *c, int64_t first, int64_t n, int32_t radius, const p
                 (mom->eigen && !thin_grow((void **)&c->d_moments_eigen, c->moments_eigen_rows, n * PCR_POINTS_PER_BATCH, sizeof(pcr_eigen)))))
         return set_err(c, PCR_E_NOMEM, "out of device memory for the moments of %lld rows (%d bytes each): pass a clip or a shorter range",
                        (long long)(n * PCR_POINTS_PER_BATCH), (int)((mom->moments ? sizeof(pcr_moments) : 0) + (mom->eigen ? sizeof(pcr_eigen) : 0)));
+    if (knn && knn->words && !thin_grow((void **)&c->d_knn_dense, c->knn_dense_words, n * PCR_POINTS_PER_BATCH * knn->k, 8))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the neighbours of %lld rows (%d bytes each): pass a clip or a shorter range",
+                       (long long)(n * PCR_POINTS_PER_BATCH), knn->k * 8);
     if (!c->d_neighbors_counters && hipMalloc((void **)&c->d_neighbors_counters, NEIGHBORS_COUNTERS * 8) != hipSuccess)
         return set_err(c, PCR_E_NOMEM, "out of device memory for the counters");
     st.table_slots = slots;
@@ -3142,7 +3154,13 @@ int neighbors_plan(pcr_ctx *c, int64_t first, int64_t n, int32_t radius, const p
     HIP_TRY(c, hipGetLastError());
     // (at most 16 384 workgroups: a wave walks the work list with the grid's stride and adds its statistics up in registers)
     const dim3 per_item((unsigned)std::min<int64_t>((items + 3) / 4, 16384));
-    if (mom) hipLaunchKernelGGL(k_moments_pairs, per_item, dim3(256), 0, c->stream, g, (unsigned long long)items, mom->moments ? c->d_moments_dense : nullptr,
+    if (knn) {
+        unsigned long long *const words = knn->words ? c->d_knn_dense : nullptr;
+#define PCR_LAUNCH(K) hipLaunchKernelGGL((k_knn_pairs<K>), per_item, dim3(256), 0, c->stream, g, (unsigned long long)items, knn->k, words)
+        if (knn->k <= 1) PCR_LAUNCH(1); else if (knn->k <= 2) PCR_LAUNCH(2); else if (knn->k <= 4) PCR_LAUNCH(4); else if (knn->k <= 8) PCR_LAUNCH(8); else PCR_LAUNCH(16);
+#undef PCR_LAUNCH
+    }
+    else if (mom) hipLaunchKernelGGL(k_moments_pairs, per_item, dim3(256), 0, c->stream, g, (unsigned long long)items, mom->moments ? c->d_moments_dense : nullptr,
                                 mom->eigen ? c->d_moments_eigen : nullptr);
     else     hipLaunchKernelGGL(k_neighbors_pairs, per_item, dim3(256), 0, c->stream, g, (unsigned long long)items);
     HIP_TRY(c, hipGetLastError());
@@ -3416,6 +3434,119 @@ int pcr_moments_eigen(pcr_ctx *c, const void *dev_moments, int64_t n, void *dev_
         HIP_TRY(c, hipGetLastError());
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+// ---- k nearest neighbours -----------------------------------------------------------------------
+namespace {
+// neighbors_emit with the k words per row: the writes of batches [i0, i1) of the plan's range, any of the three NULL. The caller
+// synchronises.
+int knn_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, int k, uint4 *points, int64_t *rows, uint64_t *knn)
+{
+    const size_t w0 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i0)) - p.writers.begin());
+    const size_t w1 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i1)) - p.writers.begin());
+    if (w0 == w1) return PCR_OK;
+    p.offsets.clear();
+    int64_t off = 0;
+    for (size_t w = w0; w < w1; ++w) { p.offsets.push_back(off); off += p.cnt[w]; }
+    HIP_TRY(c, hipMemcpyAsync(c->d_thin_wlist + w0, p.writers.data() + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_thin_offsets + w0, p.offsets.data(), (w1 - w0) * 8, hipMemcpyHostToDevice, c->stream));
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)(w1 - w0)), block(PCR_WORKGROUP_SIZE);
+    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
+#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_knn_write<L, B>), grid, block, 0, c->stream, s, c->d_thin_wlist + w0, (uint32_t)first, c->d_thin_keep, \
+                                            c->d_thin_offsets + w0, c->d_knn_dense, k, points, rows, reinterpret_cast<unsigned long long *>(knn))
+    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
+    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+#undef PCR_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    return PCR_OK;
+}
+
+// The checks and the plan shared by pcr_knn / pcr_read_knn: neighbors_prepare's, with the limits of the 64-bit word. With min_found
+// == 0 and no words asked for every candidate is kept whatever the pair kernel finds; it runs all the same, and pairs_bound comes
+// from it as in every other call. *done: nothing left to write (an error, a count-only call, no records).
+int knn_prepare(pcr_ctx *c, int64_t first, int64_t count, int k, int32_t radius, const pcr_box *clip, int64_t min_found, const void *points,
+                size_t points_align, const void *rows, const void *knn, size_t rows_align, size_t capacity, int64_t *out_count, pcr_neighbors_stats *stats,
+                int64_t *n, ThinPlan &p, bool *done)
+{
+    *done = true;
+    if (out_count) *out_count = 0;
+    int rc = select_range(c, first, count, n);
+    if (rc) return rc;
+    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
+    if (points && reinterpret_cast<uintptr_t>(points) % points_align != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
+    if (rows && reinterpret_cast<uintptr_t>(rows) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the rows is misaligned (%zu bytes)", rows_align);
+    if (knn && reinterpret_cast<uintptr_t>(knn) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the neighbours is misaligned (%zu bytes)", rows_align);
+    if (k < 1 || k > PCR_KNN_MAX_K) return set_err(c, PCR_E_ARG, "k of %d: 1 .. %d (PCR_KNN_MAX_K)", k, PCR_KNN_MAX_K);
+    if (radius < 1 || radius > PCR_KNN_MAX_RADIUS)
+        return set_err(c, PCR_E_ARG, "radius of %d: 1 .. %d stream units (PCR_KNN_MAX_RADIUS: a squared distance and a row share 64 bits)", radius, PCR_KNN_MAX_RADIUS);
+    if (min_found < 0 || min_found > k) return set_err(c, PCR_E_ARG, "min_found is %lld: 0 .. k = %d", (long long)min_found, k);
+    if (*n > ((int64_t)1 << 32) / PCR_POINTS_PER_BATCH)
+        return set_err(c, PCR_E_ARG, "a range of %lld batches has more than 2^32 rows (the index stores a 32-bit row)", (long long)*n);
+    pcr_neighbors_stats st{};
+    const KnnWant want{k, knn != nullptr};
+    if ((rc = neighbors_plan(c, first, *n, radius, clip, min_found, PCR_NEIGHBORS_ALL, false, false, p, st, nullptr, &want))) return rc;
+    *out_count = st.points_written;
+    if (stats) *stats = st;
+    if ((!points && !rows && !knn) || st.points_written == 0) return PCR_OK;
+    if (capacity < (size_t)st.points_written)
+        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld to write", capacity, (long long)st.points_written);
+    *done = false;
+    return PCR_OK;
+}
+} // namespace
+
+int pcr_knn(pcr_ctx *c, int64_t first_batch, int64_t count, int k, int32_t radius, const pcr_box *clip, int64_t min_found, void *dev_points, void *dev_rows,
+            void *dev_knn, size_t capacity_points, int64_t *out_count, pcr_neighbors_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = knn_prepare(c, first_batch, count, k, radius, clip, min_found, dev_points, 16, dev_rows, dev_knn, 8, capacity_points, out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    if ((rc = knn_emit(c, first_batch, 0, n, p, k, static_cast<uint4 *>(dev_points), static_cast<int64_t *>(dev_rows), static_cast<uint64_t *>(dev_knn)))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+int pcr_read_knn(pcr_ctx *c, int64_t first_batch, int64_t count, int k, int32_t radius, const pcr_box *clip, int64_t min_found, pcr_point *host_points,
+                 int64_t *host_rows, uint64_t *host_knn, size_t capacity_points, int64_t *out_count, pcr_neighbors_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = knn_prepare(c, first_batch, count, k, radius, clip, min_found, host_points, alignof(pcr_point), host_rows, host_knn, alignof(int64_t),
+                         capacity_points, out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    // pcr_read_local_moments' pieces: at most DECODE_STAGE_BATCHES batches at a time through the staging buffers
+    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
+    const size_t per_batch = (size_t)PCR_POINTS_PER_BATCH;
+    if ((host_points && !thin_grow((void **)&c->d_decode_stage, c->decode_stage_batches, piece, per_batch * sizeof(pcr_point))) ||
+        (host_rows && !thin_grow((void **)&c->d_thin_rows_stage, c->thin_rows_stage_batches, piece, per_batch * sizeof(int64_t))) ||
+        (host_knn && !thin_grow((void **)&c->d_knn_stage, c->knn_stage_words, piece * PCR_POINTS_PER_BATCH * k, sizeof(uint64_t))))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the staging buffers of %lld batches", (long long)piece);
+    uint4 *const d_points = host_points ? reinterpret_cast<uint4 *>(c->d_decode_stage) : nullptr;
+    int64_t *const d_rows = host_rows ? c->d_thin_rows_stage : nullptr;
+    uint64_t *const d_knn = host_knn ? c->d_knn_stage : nullptr;
+    int64_t written = 0;
+    size_t w = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += piece) {
+        const int64_t i1 = std::min(n, i0 + piece);
+        int64_t m = 0;
+        for (; w < p.writers.size() && p.writers[w] < (uint32_t)(first_batch + i1); ++w) m += p.cnt[w];
+        if (m == 0) continue;
+        if ((rc = knn_emit(c, first_batch, i0, i1, p, k, d_points, d_rows, d_knn))) return rc;
+        if (d_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
+        if (d_rows) HIP_TRY(c, hipMemcpyAsync(host_rows + written, d_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        if (d_knn) HIP_TRY(c, hipMemcpyAsync(host_knn + written * k, d_knn, (size_t)m * (size_t)k * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        written += m;
+    }
     return PCR_OK;
 }
 

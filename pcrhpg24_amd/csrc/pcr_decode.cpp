@@ -6,6 +6,7 @@
 //     pcr_decode <in.huffman> <out.las> --components CELL MINPOINTS [--conn 6|26] [--small] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --radius R MINCOUNT [--sparse] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.ply> --normals R [MINCOUNT] [--box x0 y0 z0 x1 y1 z1]
+//     pcr_decode <in.huffman> <out.las> --sor K MULT R [--outliers] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]
 //     pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1] [--rect x0 y0 x1 y1]
 //     pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]
@@ -22,7 +23,8 @@
 // With --components they come back without the connected components of voxels below a size, or those alone (pcr_read_components).
 // With --radius they come back without those that have fewer than a number of points within a radius, or those alone: the radius
 // outlier filter on actual point pairs (pcr_read_neighbors). With --normals the points come back with the normal and the curvature
-// of their neighbourhood within a radius, as a PLY (pcr_read_local_moments).
+// of their neighbourhood within a radius, as a PLY (pcr_read_local_moments). With --sor they come back without the statistical
+// outliers -- by the mean distance to their k nearest neighbours within a radius -- or those alone (pcr_read_knn).
 // With --dtm the lowest-point grid goes through the ground filter on the GPU (pcr_read_ground) and the terrain model is written;
 // with --height the points whose height above that model lies in a range are read back (pcr_read_height).
 #include <cerrno>
@@ -47,6 +49,7 @@ static const char *USAGE =
     "       pcr_decode <in.huffman> <out.las> --components CELL MINPOINTS [--conn 6|26] [--small] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --radius R MINCOUNT [--sparse] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.ply> --normals R [MINCOUNT] [--box x0 y0 z0 x1 y1 z1]\n"
+    "       pcr_decode <in.huffman> <out.las> --sor K MULT R [--outliers] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]\n"
     "       pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1]\n"
     "                                                [--rect x0 y0 x1 y1]\n"
@@ -86,6 +89,11 @@ static const char *USAGE =
     "  little-endian PLY: double x y z, uchar red green blue, float nx ny nz, float curvature. R is at most 32767 lattice steps.\n"
     "  Only the points inside --box count, as neighbours too, or inside the box of the file's header. No point to write is an\n"
     "  error.\n"
+    "  --sor K MULT R: the statistical outlier filter with the search capped at R world units (at most 32767 lattice steps): per\n"
+    "  point the mean distance to its K (1 .. 16) nearest other points within R, exact duplicates at distance 0; with mu and sigma\n"
+    "  the mean and the population standard deviation of those means, the points whose mean is at most mu + MULT * sigma, in the\n"
+    "  stream's order. A point with no other point within R is an outlier. --outliers: the outliers instead. Only the points\n"
+    "  inside --box count, as neighbours too, or inside the box of the file's header. No point to write is an error.\n"
     "  --polygon FILE: only the points inside a polygon, selected on the GPU, in the stream's order. FILE is text in world\n"
     "  coordinates: one vertex `x y` per line, a blank line starts the next ring (a ring inside another is a hole: the even-odd\n"
     "  rule); a ring has at least 3 vertices and is closed implicitly, all rings together at most 4096. A vertex goes to the\n"
@@ -291,6 +299,34 @@ static bool parse_normals(int argc, char **argv, int at, Normals &r)
         if (a == "--box" && i + 6 < argc && !r.has_box) {
             for (int k = 0; k < 6; ++k) if (!parse_double(argv[++i], k < 3 ? r.lo[k] : r.hi[k - 3])) return false;
             r.has_box = true;
+        } else {
+            return false;
+        }
+    }
+    return true;
+}
+
+struct Sor {
+    int k = 0;
+    double multiplier = 0.0, radius = 0.0;
+    bool outliers = false, has_box = false;
+    double lo[3], hi[3];
+};
+
+// the options behind --sor, every one well formed, or false
+static bool parse_sor(int argc, char **argv, int at, Sor &r)
+{
+    if (argc < at + 4 || std::strcmp(argv[at], "--sor") != 0) return false;
+    if (!parse_int(argv[at + 1], 1, PCR_KNN_MAX_K, r.k)) return false;
+    if (!parse_double(argv[at + 2], r.multiplier) || r.multiplier < 0.0) return false;
+    if (!parse_double(argv[at + 3], r.radius) || !(r.radius > 0.0)) return false;
+    for (int i = at + 4; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--box" && i + 6 < argc && !r.has_box) {
+            for (int k = 0; k < 6; ++k) if (!parse_double(argv[++i], k < 3 ? r.lo[k] : r.hi[k - 3])) return false;
+            r.has_box = true;
+        } else if (a == "--outliers" && !r.outliers) {
+            r.outliers = true;
         } else {
             return false;
         }
@@ -598,11 +634,14 @@ int main(int argc, char **argv)
     const bool radiused = argc > 3 && std::strcmp(argv[3], "--radius") == 0;
     Normals nrm;
     const bool normaled = argc > 3 && std::strcmp(argv[3], "--normals") == 0;
-    const bool boxed = argc > 3 && !viewed && !orthoed && !thinned && !polygoned && !denoised && !componented && !grounded && !radiused && !normaled;
+    Sor sor;
+    const bool sored = argc > 3 && std::strcmp(argv[3], "--sor") == 0;
+    const bool boxed = argc > 3 && !viewed && !orthoed && !thinned && !polygoned && !denoised && !componented && !grounded && !radiused && !normaled && !sored;
     if (argc < 3 || (polygoned && !parse_polygon(argc, argv, 3, poly)) || (boxed && !parse_box(argc, argv, 3, lo, hi)) || (viewed && !parse_view(argc, argv, 3, view)) ||
         (orthoed && !parse_ortho(argc, argv, 3, ortho)) || (thinned && !parse_thin(argc, argv, 3, thin)) || (denoised && !parse_denoise(argc, argv, 3, noise)) ||
         (componented && !parse_components(argc, argv, 3, comps)) || (grounded && !parse_ground(argc, argv, 3, ground)) ||
-        (radiused && !parse_radius(argc, argv, 3, rad)) || (normaled && !parse_normals(argc, argv, 3, nrm))) { std::fputs(USAGE, stderr); return 2; }
+        (radiused && !parse_radius(argc, argv, 3, rad)) || (normaled && !parse_normals(argc, argv, 3, nrm)) ||
+        (sored && !parse_sor(argc, argv, 3, sor))) { std::fputs(USAGE, stderr); return 2; }
     const std::string in = argv[1], out = argv[2];
     try {
         Renderer renderer(viewed ? view.w : 64, viewed ? view.h : 64, 0);
@@ -693,6 +732,14 @@ int main(int argc, char **argv)
             std::printf("radius: %d lattice steps, written %lld, considered %lld, sparse %lld, voxels %lld, table slots %lld, pairs bound %lld\n", r,
                         (long long)st.points_written, (long long)st.points_considered, (long long)st.points_sparse, (long long)st.voxels,
                         (long long)st.table_slots, (long long)st.pairs_bound);
+            if (points.empty()) throw std::runtime_error("no points to write: nothing written");
+        } else if (sored) {
+            const int32_t r = radiusFromWorld(info, sor.radius);
+            const pcr_box clip = boxFromWorld(info, sor.has_box ? sor.lo : info.min, sor.has_box ? sor.hi : info.max);
+            int64_t bad = 0;
+            const pcr_neighbors_stats st = las->statisticalOutliers(sor.k, sor.multiplier, r, &clip, info.scale[0], sor.outliers, points, &bad);
+            std::printf("sor: k %d, %d lattice steps, written %lld, considered %lld, outliers %lld, voxels %lld, pairs bound %lld\n", sor.k, r,
+                        (long long)points.size(), (long long)st.points_considered, (long long)bad, (long long)st.voxels, (long long)st.pairs_bound);
             if (points.empty()) throw std::runtime_error("no points to write: nothing written");
         } else if (componented) {
             const pcr_voxels vox = voxelsFromWorld(info, comps.cell, info.min);

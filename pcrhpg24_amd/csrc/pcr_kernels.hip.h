@@ -23,6 +23,7 @@
 //   k_components_*  on request: the connected components of the occupied voxels, the small ones dropped or extracted
 //   k_neighbors_*   on request: per point the points within a radius and the nearest one, from a copy bucketed by voxel
 //   k_moments_*     on request: per point the exact moments of the offsets to the points within a radius, eigenvalues and normal
+//   k_knn_*         on request: per point its k nearest other points within a radius, ordered by (distance, row), on k_neighbors_*'s index
 //   k_las_*         the 10-10-10 method (modules/compute_loop_las_cuda)
 //   k_resolve_*     framebuffer -> RGBA8 (resolve.cu:149-191, huffman_hqs/resolve.cu:2-47)
 //   k_merge_* / k_flip_sign  multi-GPU partial-framebuffer merges
@@ -3823,6 +3824,163 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_moments_write(StreamView
             if (eigen) {
 #pragma unroll
                 for (int k = 0; k < 6; ++k) eigen[dst * 6 + k] = dense_e[(row0 + i) * 6 + k];
+            }
+            ++dst;
+        }
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// k nearest neighbours (pcr_knn / pcr_read_knn): per candidate the first k, in the order (d2, row), of the candidates of another row
+// within `radius`, as words d2 << 32 | row (radius <= 32767: d2 < 2^30; a call has at most 2^32 rows), all ones behind the last one
+// found. The plan is pcr_neighbors' up to the filled buckets (k_neighbors_count / _alloc / _fill above); then
+//   k_knn_pairs<K>   k_neighbors_pairs' work distribution (a wave per work item, lane j holds centre j, lanes 0 .. 26 look up one
+//                    neighbour voxel each, the 27 buckets laid end to end, read in tiles of 64 and broadcast by lane reads; no LDS,
+//                    no barrier), for the least K of 1, 2, 4, 8, 16 that holds k. Per lane best[K], sorted ascending, all ones at
+//                    the start; per entry three subtractions, d2, the word, and, where one ballot finds a lane whose word is below
+//                    its best[K - 1], an insertion pass over best[] (min / max, unrolled: best[] is indexed with constants only and
+//                    stays in VGPRs). d2 is formed in 32 bits from exact 24-bit squares: coordinates of adjacent voxels differ by
+//                    at most 2 r - 1 = 65533, so each square is below 2^32 and exact, but the sum of three is not; an entry
+//                    counts iff the largest square and the sum are both <= r2 -- with every square <= r2 < 2^30 the sum cannot
+//                    wrap. (k_neighbors_pairs' 64-bit multiply-adds would do as well; the 24-bit multiply is the full-rate one.)
+//                    No early exit and no pruning of neighbour voxels. A valid lane stores its first k words by row into a dense
+//                    array (when asked for) and sets its keep bit iff found >= min_found.
+//   k_thin_totals (above) / k_knn_write   k_neighbors_write gathering the k words of the written rows.
+// The words of a centre are distinct (rows are), so the first k of them are the same whatever order the entries arrive in.
+// ------------------------------------------------------------------------------------------------
+#define KNN_NONE (~0ull)
+
+// a.min_count: min_found. out: [a.rows * k] by row, or NULL. 1 <= k <= K.
+template <int K>
+__global__ void __launch_bounds__(256) k_knn_pairs(NeighborsArgs a, thin_u64 items, int k, thin_u64 *out)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t r2 = (uint32_t)a.r2;
+    thin_u64 bound = 0, sparse_total = 0;                   // this wave's share of pairs_bound and of the sparse candidates
+    // (no barrier below: a wave is on its own; it takes every (waves of the grid)-th work item)
+    for (thin_u64 wi = neighbors_uniform((thin_u64)blockIdx.x * 4u + (threadIdx.x >> 6)); wi < items; wi += (thin_u64)gridDim.x * 4u) {
+    const thin_u64 item = neighbors_uniform(a.work[wi]);
+    const uint32_t slot = (uint32_t)(item >> 32), chunk = (uint32_t)item;
+    const ThinSlot *table = a.t.table;
+    const thin_u64 key = neighbors_uniform(table[slot].key), own = neighbors_uniform(table[slot].val);     // (k_neighbors_alloc's value)
+    const thin_u64 count = (own & 0xFFFFFFFFull) + 1ull, own_start = own >> 32;
+    const thin_u64 idx = (thin_u64)chunk * 64u + lane;
+    const bool valid = idx < count && own_start + idx < a.candidates;
+    const uint4 centre = valid ? a.bucket[own_start + idx] : make_uint4(0, 0, 0, 0);
+
+    // lane n < 27: the bucket of neighbour voxel n (13 is the chunk's own); lanes 27 .. 63 hold empty ones
+    uint32_t nb_start = 0;
+    thin_u64 nb_count = 0;
+    if (lane < 27u) {
+        uint32_t at = slot;
+        if (lane == 13u || components_lookup(table, a.t.log2_slots, neighbors_key(key, (int)lane), at)) {
+            const thin_u64 v = table[at].val;
+            nb_start = (uint32_t)(v >> 32);
+            nb_count = (v & 0xFFFFFFFFull) + 1ull;
+        }
+    }
+    thin_u64 nb_excl = nb_count;                            // the 27 buckets laid end to end, as in k_neighbors_pairs
+#pragma unroll
+    for (int d = 1; d < 32; d <<= 1) {
+        const thin_u64 up = __shfl_up(nb_excl, d, 64);
+        if (lane >= (uint32_t)d) nb_excl += up;
+    }
+    const thin_u64 total = neighbors_uniform(__shfl(nb_excl, 26, 64));
+    nb_excl -= nb_count;
+    const uint32_t excl_lo = (uint32_t)nb_excl, excl_hi = (uint32_t)(nb_excl >> 32), count_lo = (uint32_t)nb_count, count_hi = (uint32_t)(nb_count >> 32);
+
+    bound += (thin_u64)__popcll(__ballot(valid)) * total;
+
+    thin_u64 best[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) best[i] = KNN_NONE;
+    for (thin_u64 t0 = 0; t0 < total; t0 += 64u) {
+        const int m = (int)min((thin_u64)64u, total - t0);
+        const thin_u64 g = t0 + lane;                       // this lane's entry of the tile
+        thin_u64 at = ~0ull;
+        for (int nb = 0; nb < 27; ++nb) {                   // (every value read here is wave-uniform)
+            const thin_u64 e = ((thin_u64)(uint32_t)__builtin_amdgcn_readlane((int)excl_hi, nb) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)excl_lo, nb);
+            const thin_u64 c = ((thin_u64)(uint32_t)__builtin_amdgcn_readlane((int)count_hi, nb) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)count_lo, nb);
+            if (c == 0ull || e >= t0 + 64u || e + c <= t0) continue;
+            const thin_u64 first = (uint32_t)__builtin_amdgcn_readlane((int)nb_start, nb);
+            if (g >= e && g - e < c) at = first + (g - e);
+        }
+        const bool have = lane < (uint32_t)m && at < a.candidates;
+        const uint4 tile = have ? a.bucket[at] : make_uint4(0, 0, 0, 0);
+        for (int e = 0; e < m; ++e) {
+            const uint32_t row = (uint32_t)__builtin_amdgcn_readlane((int)tile.w, e);
+            const int32_t dx = (int32_t)(centre.x - (uint32_t)__builtin_amdgcn_readlane((int)tile.x, e));
+            const int32_t dy = (int32_t)(centre.y - (uint32_t)__builtin_amdgcn_readlane((int)tile.y, e));
+            const int32_t dz = (int32_t)(centre.z - (uint32_t)__builtin_amdgcn_readlane((int)tile.z, e));
+            // |d| <= 65533 fits 24 bits and its square 32: exact; the sum is exact wherever it is used (every square <= r2 < 2^30)
+            const uint32_t xx = (uint32_t)__mul24(dx, dx), yy = (uint32_t)__mul24(dy, dy), zz = (uint32_t)__mul24(dz, dz);
+            const uint32_t d2 = xx + yy + zz;
+            const bool in = valid && max(max(xx, yy), zz) <= r2 && d2 <= r2 && row != centre.w;
+            thin_u64 word = in ? ((thin_u64)d2 << 32) | row : KNN_NONE;
+            if (__ballot(word < best[K - 1]) != 0ull) {
+#pragma unroll
+                for (int i = 0; i < K; ++i) {               // lo = min(best[i], word); word = max(best[i], word): one compare for both
+                    const bool below = word < best[i];
+                    const thin_u64 lo = below ? word : best[i];
+                    word = below ? best[i] : word;
+                    best[i] = lo;
+                }
+            }
+        }
+    }
+    uint32_t found = 0;
+#pragma unroll
+    for (int i = 0; i < K; ++i) found += (i < k && best[i] != KNN_NONE) ? 1u : 0u;
+    const bool sparse = valid && (thin_u64)found < a.min_count;
+    if (valid && centre.w < a.rows) {                       // (k_neighbors_fill wrote every entry: the row is one of the range)
+        const thin_u64 row = centre.w;
+        if (out) {
+            thin_u64 *dst = out + row * (thin_u64)k;        // (row < a.rows: inside the array of a.rows * k words)
+#pragma unroll
+            for (int i = 0; i < K; ++i)
+                if (i < k) dst[i] = best[i];
+        }
+        if (!sparse) atomicOr(&a.keep[row >> 6], 1ull << (row & 63u));
+    }
+    sparse_total += (thin_u64)__popcll(__ballot(sparse));
+    }
+    if (lane == 0) {
+        if (bound) atomicAdd(&a.counters[NEIGHBORS_PAIRS_BOUND + (blockIdx.x & 63u)], bound);
+        if (sparse_total) atomicAdd(&a.counters[NEIGHBORS_SPARSE + (blockIdx.x & 63u)], sparse_total);
+    }
+}
+
+// k_neighbors_write gathering the k words of the written rows from the dense array (any of the three outputs may be NULL)
+template <int LAYOUT, bool BC7>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_knn_write(StreamView s, const uint32_t *list, uint32_t first_batch, const thin_u64 *keep,
+                                                                  const int64_t *offsets, const thin_u64 *dense, int k, uint4 *points, int64_t *rows,
+                                                                  thin_u64 *knn)
+{
+    const uint32_t b = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint32_t s_part[LWC_WAVES];
+    const thin_u64 word = keep[(size_t)(b - first_batch) * PCR_WORKGROUP_SIZE + tid];
+    const uint32_t mine = (uint32_t)__popcll(word);
+    uint32_t incl = mine;                                   // inclusive prefix inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += up;
+    }
+    if (lane == 63) s_part[wave] = incl;
+    load_packed_table(s, b, s_table);                       // (its barrier publishes s_part as well)
+    uint32_t before = incl - mine;
+    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    int64_t dst = offsets[blockIdx.x] + before;
+    const int64_t end = dst + mine;                         // never past the bits of this chain's word
+    const int64_t row0 = (int64_t)(b - first_batch) * PCR_POINTS_PER_BATCH + (int64_t)tid * PCR_POINTS_PER_THREAD;
+    decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        if (((word >> (uint32_t)i) & 1ull) && dst < end) {
+            if (points) points[dst] = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
+            if (rows) rows[dst] = row0 + i;
+            if (knn) {
+                for (int j = 0; j < k; ++j) knn[dst * k + j] = dense[(row0 + i) * k + j];
             }
             ++dst;
         }

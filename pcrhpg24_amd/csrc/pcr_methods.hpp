@@ -437,6 +437,67 @@ struct HuffmanLasData : Resource {
         return st;
     }
 
+    // Per point inside `clip` (NULL: everywhere) its k (1 .. PCR_KNN_MAX_K) nearest other points within `radius` lattice steps (1 ..
+    // PCR_KNN_MAX_RADIUS) in the order (squared distance, row), on the GPU straight from the compressed stream (pcr_read_knn: a
+    // counting call, then the read): knn holds k words d2 << 32 | row per point, PCR_KNN_NONE behind the last one found. Only the
+    // points with at least min_found (0 .. k) such neighbours come back. rows (may be NULL): the points' rows. Not in the reference.
+    pcr_neighbors_stats nearestNeighbors(int k, int32_t radius, const pcr_box *clip, int64_t min_found, std::vector<pcr_point> &out, std::vector<uint64_t> &knn,
+                                         std::vector<int64_t> *rows = nullptr)
+    {
+        if (!loadedOn) throw std::runtime_error("nearestNeighbors: the resource is not loaded");
+        const int64_t nB = pcr_batches_resident(loadedOn->ctx);
+        int64_t n = 0;
+        pcr_neighbors_stats st{};
+        loadedOn->check(pcr_read_knn(loadedOn->ctx, 0, nB, k, radius, clip, min_found, nullptr, nullptr, nullptr, 0, &n, &st), "pcr_read_knn");
+        out.resize((size_t)n);
+        knn.resize((size_t)n * (size_t)k);
+        if (rows) rows->resize((size_t)n);
+        if (n) loadedOn->check(pcr_read_knn(loadedOn->ctx, 0, nB, k, radius, clip, min_found, out.data(), rows ? rows->data() : nullptr, knn.data(), out.size(),
+                                            &n, &st), "pcr_read_knn");
+        return st;
+    }
+
+    // The statistical outlier filter with the search capped at `radius`: per point inside `clip` the mean of sqrt(d2) * scale over
+    // its k nearest other points within the radius (in entry order; infinite without one), mu and the population sigma of the finite
+    // means (summed in row order); a point is an outlier iff its mean is > mu + multiplier * sigma or infinite. out: the inliers, or
+    // with `outliers` the outliers; *num_outliers (may be NULL): how many there are. (PDAL's filters.outlier with method=statistical
+    // has no radius; this reading of its definition has not been checked against the tool.) Not in the reference.
+    pcr_neighbors_stats statisticalOutliers(int k, double multiplier, int32_t radius, const pcr_box *clip, double scale, bool outliers, std::vector<pcr_point> &out,
+                                            int64_t *num_outliers = nullptr)
+    {
+        std::vector<pcr_point> all;
+        std::vector<uint64_t> knn;
+        const pcr_neighbors_stats st = nearestNeighbors(k, radius, clip, 0, all, knn);
+        const double inf = std::numeric_limits<double>::infinity();
+        std::vector<double> mean(all.size(), inf);
+        double sum = 0.0;
+        size_t finite = 0;
+        for (size_t i = 0; i < all.size(); ++i) {
+            double total = 0.0;
+            int found = 0;
+            for (int j = 0; j < k; ++j) {
+                const uint64_t w = knn[i * (size_t)k + (size_t)j];
+                if (w == PCR_KNN_NONE) continue;
+                total += std::sqrt((double)(w >> 32)) * scale;
+                ++found;
+            }
+            if (found) { mean[i] = total / (double)found; sum += mean[i]; ++finite; }
+        }
+        const double mu = finite ? sum / (double)finite : 0.0;
+        double var = 0.0;
+        for (double m : mean) if (m != inf) var += (m - mu) * (m - mu);
+        const double limit = mu + multiplier * (finite ? std::sqrt(var / (double)finite) : 0.0);
+        out.clear();
+        int64_t bad = 0;
+        for (size_t i = 0; i < all.size(); ++i) {
+            const bool is_outlier = mean[i] == inf || mean[i] > limit;
+            bad += is_outlier;
+            if (is_outlier == outliers) out.push_back(all[i]);
+        }
+        if (num_outliers) *num_outliers = bad;
+        return st;
+    }
+
     // The points a frame of camera `p` draws whose pixel lies in `rect` (NULL: the whole image), with where they land, selected on
     // the GPU (pcr_read_screen: a counting call, then the read). Either vector may be NULL. Not in the reference.
     pcr_screen_stats selectScreen(const pcr_render_params &p, const pcr_rect *rect, std::vector<pcr_point> *points, std::vector<pcr_screen_hit> *hits)

@@ -495,6 +495,43 @@ def covariance_from_moments(moments) -> np.ndarray:
     return out
 
 
+def knn_split(words):
+    """A uint64 array of pcr_knn's words (d2 << 32 | row, KNN_NONE for none) as two int64 arrays of the same shape: the rows and
+    the squared distances, -1 where there is no neighbour."""
+    w = np.asarray(words, np.uint64)
+    none = w == np.uint64(N.KNN_NONE)
+    rows = np.where(none, -1, (w & np.uint64(0xFFFFFFFF)).astype(np.int64))
+    d2 = np.where(none, -1, (w >> np.uint64(32)).astype(np.int64))
+    return rows, d2
+
+
+def knn_mean_distance(knn_d2, scale: float = 1.0) -> np.ndarray:
+    """Per row of knn_d2 (int [n, k]: squared distances, -1 for no neighbour, as Context.read_knn returns them) the mean distance to
+    the neighbours found: float64 sqrt(d2) * scale summed over the found entries in entry order, divided by their number; inf
+    where none was found."""
+    d2 = np.asarray(knn_d2, np.int64)
+    d2 = d2.reshape(len(d2), d2.size // max(len(d2), 1)) if d2.ndim != 2 else d2
+    total = np.zeros(len(d2), np.float64)
+    found = np.zeros(len(d2), np.int64)
+    for j in range(d2.shape[1]):
+        have = d2[:, j] >= 0
+        total = total + np.where(have, np.sqrt(np.where(have, d2[:, j], 0).astype(np.float64)) * float(scale), 0.0)
+        found += have
+    return np.where(found > 0, total / np.where(found > 0, found, 1), np.inf)
+
+
+def statistical_outlier_mask(mean, multiplier: float) -> np.ndarray:
+    """The statistical outlier rule over per-point mean neighbour distances (knn_mean_distance): with mu and sigma the mean and the
+    population standard deviation of the finite entries, a point is an outlier iff its entry is > mu + multiplier * sigma or
+    infinite. A bool array."""
+    mean = np.asarray(mean, np.float64)
+    finite = np.isfinite(mean)
+    if not finite.any():
+        return ~finite
+    mu, sigma = float(mean[finite].mean()), float(mean[finite].std())
+    return ~finite | (mean > mu + float(multiplier) * sigma)
+
+
 def geometric_features(values) -> dict:
     """From ascending eigenvalues l0 <= l1 <= l2 ([n, 3]; numpy, or a torch tensor that is brought to the host): float64 arrays of
     curvature l0 / (l0 + l1 + l2), linearity (l2 - l1) / l2, planarity (l1 - l0) / l2 and scattering l0 / l2, each 0 where its
@@ -1329,6 +1366,61 @@ class Context:
         res = (pts,) + tuple(a for a in extra if a is not None)
         return res if len(res) > 1 else res[0]
 
+    # -- k nearest neighbours (pcr_knn / pcr_read_knn) --------------------------------------------------------
+    def knn(self, k: int, radius: int, min_found: int = 0, clip=None, first: int = 0, count: Optional[int] = None, out=None, rows: bool = False,
+            neighbors: bool = True):
+        """The rows of batches [first, first + count) inside `clip` (as_box; None: everywhere) that have at least `min_found` (0 ..
+        k) other rows of the range and clip within `radius` lattice steps (1 .. KNN_MAX_RADIUS), with their k (1 .. KNN_MAX_K)
+        nearest ones in the order (squared distance, row), straight from the compressed stream. Results, `out`, rows=True and stream
+        ordering as Context.neighbors; neighbors=True appends two int64 tensors [n, k], knn_rows (rows relative to `first`) and
+        knn_d2, both -1 where a row has fewer than k neighbours: points, then rows, knn_rows, knn_d2 as asked for. What the last
+        call did is in self.knn_stats."""
+        import torch
+        clip = None if clip is None else as_box(clip)
+        cp = None if clip is None else C.byref(clip)
+        dev = torch.device("cuda", self.device)
+        cnt, st, nb = c_i64(), NeighborsStats(), -1 if count is None else count
+        if out is None:
+            self._chk(self.lib.pcr_knn(self.h, first, nb, k, radius, cp, min_found, None, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_knn")
+            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
+        cap = out.numel() // 4
+        r = torch.empty(cap, dtype=torch.int64, device=dev) if rows else None
+        words = torch.empty((cap, k), dtype=torch.int64, device=dev) if neighbors else None
+        torch.cuda.current_stream(dev).synchronize()
+        ptrs = [C.c_void_p(t.data_ptr() if cap else None) if t is not None else None for t in (r, words)]
+        rc = self.lib.pcr_knn(self.h, first, nb, k, radius, cp, min_found, C.c_void_p(out.data_ptr() if cap else None), ptrs[0], ptrs[1], cap,
+                              C.byref(cnt), C.byref(st))
+        self.knn_stats = st.as_dict()
+        if rc:
+            self.knn_stats["points_written"] = cnt.value
+        self._chk(rc, "pcr_knn")
+        res = (out.view(-1, 4)[:cnt.value],) + ((r[:cnt.value],) if rows else ())
+        if neighbors:
+            w = words[:cnt.value]
+            none = w == -1                                  # (KNN_NONE's bits)
+            res += (torch.where(none, w, w & 0xFFFFFFFF), torch.where(none, w, w >> 32))
+        return res if len(res) > 1 else res[0]
+
+    def read_knn(self, k: int, radius: int, min_found: int = 0, clip=None, first: int = 0, count: Optional[int] = None, rows: bool = False,
+                 neighbors: bool = True):
+        """The same on the host, without torch: a numpy structured array of POINT_DTYPE, followed as asked for by an int64 array of
+        the rows and the int64 arrays [n, k] knn_rows and knn_d2 (pcr_read_knn: a counting call, then the read; synchronises)."""
+        clip = None if clip is None else as_box(clip)
+        cp = None if clip is None else C.byref(clip)
+        cnt, st, nb = c_i64(), NeighborsStats(), -1 if count is None else count
+        self._chk(self.lib.pcr_read_knn(self.h, first, nb, k, radius, cp, min_found, None, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_read_knn")
+        pts = np.empty(cnt.value, POINT_DTYPE)
+        r = np.empty(cnt.value, ROW_DTYPE) if rows else None
+        words = np.empty((cnt.value, k), np.uint64) if neighbors else None
+        if cnt.value:
+            self._chk(self.lib.pcr_read_knn(self.h, first, nb, k, radius, cp, min_found, pts.ctypes.data, None if r is None else r.ctypes.data,
+                                            None if words is None else words.ctypes.data, len(pts), C.byref(cnt), C.byref(st)), "pcr_read_knn")
+        self.knn_stats = st.as_dict()
+        res = (pts,) + ((r,) if rows else ()) + (knn_split(words) if neighbors else ())
+        return res if len(res) > 1 else res[0]
+
     def moments_eigen(self, moments):
         """pcr_moments_eigen: the eigen records of moments records. An int64 torch tensor [n, 10] on this context's device gives a
         float64 tensor [n, 6] there; a numpy array (MOMENTS_DTYPE, or int64 [n, 10]) is uploaded and gives an EIGEN_DTYPE array.
@@ -1921,6 +2013,35 @@ class HuffmanLasData(Resource):
         total = eig[:, 0] + eig[:, 1] + eig[:, 2]
         curvature = torch.where(total != 0.0, eig[:, 0] / torch.where(total != 0.0, total, torch.ones_like(total)), torch.zeros_like(total))
         return pts, eig[:, 3:6], curvature
+
+    def nearest_neighbors(self, renderer: Renderer, k: int, radius: float, lo=None, hi=None, world: bool = True):
+        """Per point of the loaded resource inside the clip: (points, rows, knn_rows, distances) -- the int32 records, their rows,
+        the rows of their k nearest other points within `radius` in the order (distance, row) (int64 [n, k], -1 for none; rows as
+        Context.knn counts them, over the whole resource) and the distances to them (float64 [n, k]: sqrt(d2) * scale in world
+        units, with world=False sqrt(d2) in lattice steps; inf for none), on the GPU straight from the compressed stream
+        (Context.knn). radius, lo, hi and world as for radius_filtered(); radius is at most KNN_MAX_RADIUS lattice steps."""
+        import torch
+        info = self.las_info()
+        r, clip = self._neighbors_clip(info, radius, lo, hi, world)
+        pts, rows, knn_rows, d2 = renderer.ctx.knn(k, r, 0, clip, rows=True)
+        scale = float(info.scale[0]) if world else 1.0
+        dist = torch.where(d2 < 0, torch.full_like(d2, float("inf"), dtype=torch.float64), torch.sqrt(d2.clamp(min=0).to(torch.float64)) * scale)
+        return pts, rows, knn_rows, dist
+
+    def statistical_outliers(self, renderer: Renderer, k: int, multiplier: float, radius: float, lo=None, hi=None, outliers: bool = False,
+                             world: bool = True):
+        """The statistical outlier filter with the search capped at `radius`: per point inside the clip the mean distance to its k
+        nearest other points within the radius (knn_mean_distance; Context.read_knn with min_found = 0), mu and the population
+        sigma of the finite means; a point is an outlier iff its mean is > mu + multiplier * sigma or it has no neighbour within
+        the radius. Returns (points, rows) of the inliers, or with outliers=True of the outliers: numpy arrays (POINT_DTYPE,
+        int64). radius, lo, hi and world as for radius_filtered(). (PDAL's filters.outlier with method=statistical has mean_k and
+        multiplier and no radius; this reading of its definition has not been checked against the tool.)"""
+        info = self.las_info()
+        r, clip = self._neighbors_clip(info, radius, lo, hi, world)
+        pts, rows, _, d2 = renderer.ctx.read_knn(k, r, 0, clip, rows=True)
+        out = statistical_outlier_mask(knn_mean_distance(d2, float(info.scale[0]) if world else 1.0), multiplier)
+        sel = out if outliers else ~out
+        return pts[sel], rows[sel]
 
     def las_info(self) -> LasInfo:
         """Scale, offset, min and max of the LAS file the stream was made from, as its first batch record carries them (the
