@@ -621,6 +621,51 @@ int pcr_read_knn(pcr_ctx *ctx, int64_t first_batch, int64_t count, int k, int32_
                  pcr_point *host_points, int64_t *host_rows, uint64_t *host_knn, size_t capacity_points, int64_t *out_count,
                  pcr_neighbors_stats *stats);
 
+/* ---- voxel means: centroid and mean colour per voxel, straight from the compressed stream (no reference counterpart) ------------
+ * Candidates, voxels and the lattice are pcr_thin's, word for word: the records pcr_decode_points writes for the range that lie
+ * inside *clip (bounds inclusive; NULL: all; padding duplicates and the tail artefact included), v = floor((p - origin) / cell) in
+ * exact integers, cell in 1 .. PCR_THIN_MAX_CELL. For a non-empty voxel V: n(V) = the number of its candidates; r(p) = p - origin -
+ * v * cell per axis, in [0, cell); S_a = the sum of r_a over the candidates; C_j = the sum of byte j (j = 0 .. 3) of the
+ * candidates' colour words; row(V) = the least row among the candidates.
+ * CONTRACT: one record per non-empty voxel, record i that of the voxel whose row(V) is the i-th smallest -- exactly the order and
+ * the count of pcr_thin with PCR_THIN_FIRST and the same arguments. dev_points[i] is a pcr_point: its position on axis a is
+ * origin_a + v_a * cell + (2 * S_a + n) / (2 * n), integer division of non-negative 64-bit values (the mean offset rounded half
+ * up); byte j of its colour is (2 * C_j + n) / (2 * n), every byte averaged on its own (a byte that is zero in every candidate
+ * stays zero). The mean offset lies in [min r_a, max r_a], inside [0, cell - 1]: the mean point lies in its own voxel and inside
+ * the coordinate range of its candidates, hence in int32 (the kernels form it modulo 2^32 from the shifted lattice, as for the
+ * key). dev_rows[i] = row(V) as int64, the rows pcr_thin FIRST returns; dev_counts[i] = n(V) as int64. A voxel whose candidates
+ * are identical (cell == 1 positions, padding duplicates) yields that record. Sums of integers commute: the result is exact,
+ * depends on no hash, table size or order of lanes, workgroups and launches and is the same bytes from run to run.
+ *
+ * pcr_voxel_mean: any of dev_points (16-byte aligned), dev_rows and dev_counts (8-byte aligned) may be NULL, with all three NULL
+ *   the call only counts (pcr_thin's count-only call: no sum is formed); capacity_points counts records of each. A capacity below
+ *   the result: PCR_E_ARG, *out_count = the count needed, nothing written. Range semantics, count < 0, the restriction under
+ *   pcr_set_async_upload, the empty clip / empty range / clip that misses every batch (0 records, PCR_OK, no kernel runs) and the
+ *   synchronisation are pcr_thin's. Touches no framebuffer, no prepass state, no render statistics; BC1 and BC7, either resident
+ *   layout, before and after the first frame. A voxel that spans two ranges is averaged once per range (the counts make a later
+ *   merge possible). stats (may be NULL) holds what pcr_thin FIRST reports for these arguments, table_slots included; points_kept
+ *   is the call's *out_count.
+ *   How: pcr_thin's FIRST plan runs unchanged (table of (voxel, least row), keep bitmap, records per batch). k_voxel_prefix scans
+ *   the popcounts of the keep words of every batch that keeps a row; k_voxel_index turns the least row in every occupied slot
+ *   into its record index and notes (key, row) per record; k_voxel_sum decodes the listed batches with colours, sums every run
+ *   of a chain in registers and adds it into the accumulator of the run's voxel -- eight 64-bit words indexed by record: S_x,
+ *   S_y, S_z, n, C_0 .. C_3 -- with atomic adds whose results are not used; k_voxel_finish does the roundings and the stores, a
+ *   thread per record. Scratch, grown on demand and released with the context: pcr_thin's (16 bytes per slot, 8 per chain), 8
+ *   bytes per chain of the range, and 80 bytes per voxel (64 the accumulator, 16 key and row).
+ *   With offsets below 2^30 and at most 2^32 rows a call (PCR_VOXEL_MEAN_MAX_ROWS) every S_a < 2^62, C_j < 2^40 and 2 * S_a + n <
+ *   2^64: the unsigned 64-bit sums and the rounding are exact.
+ * pcr_read_voxel_mean: the same into host memory (alignof(pcr_point) / alignof(int64_t)), in pieces of 64 * 65 536 records
+ *   through staging buffers as pcr_read_knn.
+ * PCR_E_ARG with a message, nothing written: pcr_thin's refusals without the PCR_THIN_CENTER limit (the lattice too large for
+ * the key included: pass a clip or a larger cell), a misaligned destination, and a range of more than PCR_VOXEL_MEAN_MAX_ROWS
+ * rows (65 536 batches): pass a shorter range. PCR_E_NOMEM: no device memory for the table or the sums -- pass a clip or a larger
+ * cell. */
+int pcr_voxel_mean(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, void *dev_points,
+                   void *dev_rows, void *dev_counts, size_t capacity_points, int64_t *out_count, pcr_thin_stats *stats);
+int pcr_read_voxel_mean(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip,
+                        pcr_point *host_points, int64_t *host_rows, int64_t *host_counts, size_t capacity_points, int64_t *out_count,
+                        pcr_thin_stats *stats);
+
 /* What a collective library needs to merge partial frames in place (include/pcr_dist.h does it with RCCL): the HIP stream
  * the context enqueues on, its device ordinal and the length of each framebuffer in 64-bit words. */
 void *pcr_get_stream(pcr_ctx *ctx);

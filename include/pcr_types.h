@@ -237,6 +237,7 @@ typedef struct pcr_height_stats {
 #define PCR_THIN_CENTER           1          /* mode: the one nearest to the voxel's centre, ties to the lowest row */
 #define PCR_THIN_MAX_CELL         (1 << 30)
 #define PCR_THIN_MAX_CENTER_CELL  2048       /* PCR_THIN_CENTER: 3 * (cell - 1)^2 < 2^24 */
+#define PCR_VOXEL_MEAN_MAX_ROWS   (1ll << 32) /* pcr_voxel_mean: rows of a call, so that n <= 2^32 and every sum S < 2^62 (offsets < 2^30) */
 typedef struct pcr_voxels {
     int32_t origin[3];           /* min corner of voxel (0, 0, 0) */
     int32_t cell;                /* edge length, 1 .. PCR_THIN_MAX_CELL */

@@ -131,6 +131,7 @@ class ThinStats(C.Structure):                     # pcr_thin_stats
 
 
 THIN_FIRST, THIN_CENTER, THIN_MAX_CELL, THIN_MAX_CENTER_CELL = 0, 1, 1 << 30, 2048                      # pcr_types.h
+VOXEL_MEAN_MAX_ROWS = 1 << 32                                                                           # pcr_types.h
 
 
 class DenoiseStats(C.Structure):                  # pcr_denoise_stats
@@ -245,6 +246,7 @@ HIP_SYMBOLS = [
     "pcr_neighbors", "pcr_read_neighbors",
     "pcr_local_moments", "pcr_read_local_moments", "pcr_moments_eigen",
     "pcr_knn", "pcr_read_knn",
+    "pcr_voxel_mean", "pcr_read_voxel_mean",
 ]
 
 HOST_SYMBOLS = [
@@ -394,6 +396,9 @@ def hip_lib() -> C.CDLL:
         for n in ("pcr_knn", "pcr_read_knn"):
             getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.c_int, c_i32, C.POINTER(Box), c_i64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_size_t, C.POINTER(c_i64), C.POINTER(NeighborsStats)]
+        for n in ("pcr_voxel_mean", "pcr_read_voxel_mean"):
+            getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Voxels), C.POINTER(Box), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.POINTER(c_i64), C.POINTER(ThinStats)]
         _hip = lib
     return _hip
 

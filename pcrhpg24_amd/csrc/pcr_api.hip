@@ -208,6 +208,16 @@ struct pcr_ctx {
     uint64_t *d_knn_stage = nullptr;                    // [knn_stage_words]
     int64_t knn_stage_words = 0;
     int64_t components_labels_stage_batches = 0;
+    // voxel means (pcr_voxel_mean / pcr_read_voxel_mean) share pcr_thin's scratch; their own: the record index of every chain's
+    // first kept row, the accumulator and (key, row) of every record, and pcr_read_voxel_mean's stage of the counts
+    unsigned long long *d_voxel_prefix = nullptr;       // [voxel_prefix_words] a word per chain of the call's range
+    int64_t voxel_prefix_words = 0;
+    unsigned long long *d_voxel_acc = nullptr;          // [voxel_acc_records * VOXEL_ACC_WORDS]
+    int64_t voxel_acc_records = 0;
+    VoxelRec *d_voxel_rec = nullptr;                    // [voxel_rec_records]
+    int64_t voxel_rec_records = 0;
+    int64_t *d_voxel_counts_stage = nullptr;            // [voxel_counts_stage_batches * 65536]
+    int64_t voxel_counts_stage_batches = 0;
     int64_t prepass_batches = 0;
     static constexpr int FENCES = 8;
     hipEvent_t fence[FENCES] = {};              // pcr_fence_record / pcr_fence_wait: device-scope ordering between streams
@@ -320,6 +330,8 @@ void free_stream_buffers(pcr_ctx *c)
     dfree(c->d_moments_dense); c->moments_dense_rows = 0; dfree(c->d_moments_eigen); c->moments_eigen_rows = 0;
     dfree(c->d_moments_stage); c->moments_stage_batches = 0; dfree(c->d_moments_eigen_stage); c->moments_eigen_stage_batches = 0;
     dfree(c->d_knn_dense); c->knn_dense_words = 0; dfree(c->d_knn_stage); c->knn_stage_words = 0;
+    dfree(c->d_voxel_prefix); c->voxel_prefix_words = 0; dfree(c->d_voxel_acc); c->voxel_acc_records = 0;
+    dfree(c->d_voxel_rec); c->voxel_rec_records = 0; dfree(c->d_voxel_counts_stage); c->voxel_counts_stage_batches = 0;
 
     if (c->any_generic_pending && c->any_generic_ev) (void)hipEventSynchronize(c->any_generic_ev);
     c->any_generic_pending = false;
@@ -2521,8 +2533,9 @@ struct ThinPlan {
     std::vector<int64_t> cnt;           // [writers.size()]
     std::vector<int64_t> offsets;       // staging of k_thin_write's offsets (alive until the stream has been synchronised)
     pcr_thin_stats st{};
-    ThinArgs args{};                    // pcr_components only: the lattice and the table of the plan, for k_components_labels,
-    const thin_u64 *label = nullptr;    // and the label of every slot
+    ThinArgs args{};                    // the clip, the lattice and the table of the plan (pcr_components: for k_components_labels;
+                                        // thin_plan: for pcr_voxel_mean's kernels)
+    const thin_u64 *label = nullptr;    // pcr_components only: the label of every slot
 };
 
 // *p holds at least `want` elements on return (a larger array replaces it, its content is not kept), or false
@@ -2620,6 +2633,7 @@ int thin_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const
                        (long long)p.st.runs);
     p.st.table_slots = slots;
     a.log2_slots = log2_slots; a.table = c->d_thin_table; a.error = c->d_thin_error;
+    p.args = a;
     HIP_TRY(c, hipMemsetAsync(c->d_thin_table, 0xFF, (size_t)slots * sizeof(ThinSlot), c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_thin_keep, 0, (size_t)n * PCR_WORKGROUP_SIZE * 8, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_thin_error, 0, 4, c->stream));
@@ -3548,6 +3562,143 @@ int pcr_read_knn(pcr_ctx *c, int64_t first_batch, int64_t count, int k, int32_t 
         written += m;
     }
     return PCR_OK;
+}
+
+// ---- voxel means -------------------------------------------------------------------------------
+namespace {
+// The checks and the plan shared by pcr_voxel_mean / pcr_read_voxel_mean: pcr_thin's FIRST plan, unchanged. *done: nothing left to
+// write (an error, a count-only call, no records).
+int voxel_mean_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_voxels *vox, const pcr_box *clip, const void *points, size_t points_align,
+                       const void *rows, const void *counts, size_t rows_align, size_t capacity, int64_t *out_count, pcr_thin_stats *stats, int64_t *n,
+                       ThinPlan &p, bool *done)
+{
+    *done = true;
+    if (out_count) *out_count = 0;
+    int rc = select_range(c, first, count, n);
+    if (rc) return rc;
+    if (!vox) return set_err(c, PCR_E_ARG, "the voxel lattice is NULL");
+    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
+    if (points && reinterpret_cast<uintptr_t>(points) % points_align != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
+    if (rows && reinterpret_cast<uintptr_t>(rows) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the rows is misaligned (%zu bytes)", rows_align);
+    if (counts && reinterpret_cast<uintptr_t>(counts) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the counts is misaligned (%zu bytes)", rows_align);
+    if (vox->cell < 1 || vox->cell > PCR_THIN_MAX_CELL)
+        return set_err(c, PCR_E_ARG, "voxel cell of %d: the edge length is 1 .. %d (PCR_THIN_MAX_CELL)", vox->cell, PCR_THIN_MAX_CELL);
+    if (*n > PCR_VOXEL_MEAN_MAX_ROWS / PCR_POINTS_PER_BATCH)
+        return set_err(c, PCR_E_ARG, "a range of %lld batches has more than 2^32 rows (the 64-bit sums of a voxel are exact up to there): pass a shorter range",
+                       (long long)*n);
+    if ((rc = thin_plan(c, first, *n, *vox, clip, PCR_THIN_FIRST, p))) return rc;
+    *out_count = p.st.points_kept;
+    if (stats) *stats = p.st;
+    if ((!points && !rows && !counts) || p.st.points_kept == 0) return PCR_OK;
+    if (capacity < (size_t)p.st.points_kept)
+        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld voxels", capacity, (long long)p.st.points_kept);
+    *done = false;
+    return PCR_OK;
+}
+
+// After thin_plan: the record index of every voxel into its slot, (key, row) of every record, and the sums of every voxel into
+// its accumulator. Enqueues only; the error word (zero after thin_plan) is read by voxel_mean_check.
+int voxel_mean_sums(pcr_ctx *c, int64_t first, int64_t n, ThinPlan &p)
+{
+    const int64_t records = p.st.points_kept, slots = p.st.table_slots;
+    const int64_t nL = (int64_t)p.listed.size(), nW = (int64_t)p.writers.size();
+    if (!thin_grow((void **)&c->d_voxel_prefix, c->voxel_prefix_words, n * PCR_WORKGROUP_SIZE, 8))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the record index of %lld batches: pass a shorter range", (long long)n);
+    if (!thin_grow((void **)&c->d_voxel_acc, c->voxel_acc_records, records, VOXEL_ACC_WORDS * 8) ||
+        !thin_grow((void **)&c->d_voxel_rec, c->voxel_rec_records, records, sizeof(VoxelRec)))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the sums of %lld voxels (80 bytes each): pass a clip or a larger cell", (long long)records);
+    p.offsets.clear();
+    int64_t off = 0;
+    for (int64_t w = 0; w < nW; ++w) { p.offsets.push_back(off); off += p.cnt[(size_t)w]; }
+    HIP_TRY(c, hipMemcpyAsync(c->d_thin_wlist, p.writers.data(), (size_t)nW * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_thin_offsets, p.offsets.data(), (size_t)nW * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_voxel_acc, 0, (size_t)records * VOXEL_ACC_WORDS * 8, c->stream));
+    hipLaunchKernelGGL(k_voxel_prefix, dim3((unsigned)nW), dim3(PCR_WORKGROUP_SIZE), 0, c->stream, c->d_thin_wlist, (uint32_t)first, c->d_thin_keep,
+                       c->d_thin_offsets, c->d_voxel_prefix);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(k_voxel_index, dim3((unsigned)std::min<int64_t>((slots + 255) / 256, 4096)), dim3(256), 0, c->stream, c->d_thin_table,
+                       (unsigned long long)slots, c->d_thin_keep, c->d_voxel_prefix, (unsigned long long)records, c->d_voxel_rec, c->d_thin_error);
+    HIP_TRY(c, hipGetLastError());
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)nL), block(PCR_WORKGROUP_SIZE);
+    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
+#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_voxel_sum<L, B>), grid, block, 0, c->stream, s, c->d_thin_list, p.args, (unsigned long long)records, c->d_voxel_acc)
+    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
+    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+#undef PCR_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    return PCR_OK;
+}
+
+// Enqueue the roundings and stores of records [i0, i1) (device destinations of i1 - i0 records, any may be NULL)
+int voxel_mean_emit(pcr_ctx *c, const ThinPlan &p, int64_t i0, int64_t i1, uint4 *points, int64_t *rows, int64_t *counts)
+{
+    hipLaunchKernelGGL(k_voxel_finish, dim3((unsigned)std::min<int64_t>((i1 - i0 + 255) / 256, 4096)), dim3(256), 0, c->stream, p.args.lat, c->d_voxel_acc,
+                       c->d_voxel_rec, (unsigned long long)i0, (unsigned long long)i1, points, rows, counts, c->d_thin_error);
+    HIP_TRY(c, hipGetLastError());
+    return PCR_OK;
+}
+
+// Synchronises; the error word of the call's kernels: the table, the bitmap and the accumulators disagree (cannot happen)
+int voxel_mean_check(pcr_ctx *c)
+{
+    uint32_t error = 0;
+    HIP_TRY(c, hipMemcpyAsync(&error, c->d_thin_error, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (error) return set_err(c, PCR_E_NOMEM, "voxel table and record index disagree");
+    return PCR_OK;
+}
+} // namespace
+
+int pcr_voxel_mean(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, void *dev_points, void *dev_rows,
+                   void *dev_counts, size_t capacity_points, int64_t *out_count, pcr_thin_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = voxel_mean_prepare(c, first_batch, count, vox, clip, dev_points, 16, dev_rows, dev_counts, 8, capacity_points, out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    if ((rc = voxel_mean_sums(c, first_batch, n, p))) return rc;
+    if ((rc = voxel_mean_emit(c, p, 0, p.st.points_kept, static_cast<uint4 *>(dev_points), static_cast<int64_t *>(dev_rows), static_cast<int64_t *>(dev_counts))))
+        return rc;
+    return voxel_mean_check(c);
+}
+
+int pcr_read_voxel_mean(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, pcr_point *host_points,
+                        int64_t *host_rows, int64_t *host_counts, size_t capacity_points, int64_t *out_count, pcr_thin_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = voxel_mean_prepare(c, first_batch, count, vox, clip, host_points, alignof(pcr_point), host_rows, host_counts, alignof(int64_t), capacity_points,
+                                out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    // pieces of at most DECODE_STAGE_BATCHES * 65 536 records through the staging buffers
+    const int64_t records = p.st.points_kept;
+    const int64_t piece_batches = std::min<int64_t>((records + PCR_POINTS_PER_BATCH - 1) / PCR_POINTS_PER_BATCH, DECODE_STAGE_BATCHES);
+    const int64_t piece = piece_batches * PCR_POINTS_PER_BATCH;
+    const size_t per_batch = (size_t)PCR_POINTS_PER_BATCH;
+    if ((host_points && !thin_grow((void **)&c->d_decode_stage, c->decode_stage_batches, piece_batches, per_batch * sizeof(pcr_point))) ||
+        (host_rows && !thin_grow((void **)&c->d_thin_rows_stage, c->thin_rows_stage_batches, piece_batches, per_batch * sizeof(int64_t))) ||
+        (host_counts && !thin_grow((void **)&c->d_voxel_counts_stage, c->voxel_counts_stage_batches, piece_batches, per_batch * sizeof(int64_t))))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the staging buffers of %lld records", (long long)piece);
+    uint4 *const d_points = host_points ? reinterpret_cast<uint4 *>(c->d_decode_stage) : nullptr;
+    int64_t *const d_rows = host_rows ? c->d_thin_rows_stage : nullptr;
+    int64_t *const d_counts = host_counts ? c->d_voxel_counts_stage : nullptr;
+    if ((rc = voxel_mean_sums(c, first_batch, n, p))) return rc;
+    for (int64_t i0 = 0; i0 < records; i0 += piece) {
+        const int64_t i1 = std::min(records, i0 + piece), m = i1 - i0;
+        if ((rc = voxel_mean_emit(c, p, i0, i1, d_points, d_rows, d_counts))) return rc;
+        if (d_points) HIP_TRY(c, hipMemcpyAsync(host_points + i0, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
+        if (d_rows) HIP_TRY(c, hipMemcpyAsync(host_rows + i0, d_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        if (d_counts) HIP_TRY(c, hipMemcpyAsync(host_counts + i0, d_counts, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return voxel_mean_check(c);
 }
 
 // ---- screen selection and picking --------------------------------------------------------------

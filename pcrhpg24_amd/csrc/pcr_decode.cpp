@@ -1,7 +1,7 @@
 // pcr_decode — a .huffman file back to a LAS file, decoded on the GPU (pcr_read_points). The reference has no such tool: its only
 // decoder outside the render kernels is the per-chain CPU one of include/huffman.h:433-477.
 //     pcr_decode <in.huffman> <out.las> [--box x0 y0 z0 x1 y1 z1]
-//     pcr_decode <in.huffman> <out.las> --thin CELL [--center] [--box x0 y0 z0 x1 y1 z1]
+//     pcr_decode <in.huffman> <out.las> --thin CELL [--center | --mean] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --denoise CELL MAXCOUNT [--isolated] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --components CELL MINPOINTS [--conn 6|26] [--small] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --radius R MINCOUNT [--sparse] [--box x0 y0 z0 x1 y1 z1]
@@ -44,7 +44,7 @@ using namespace pcr_host;
 
 static const char *USAGE =
     "usage: pcr_decode <in.huffman> <out.las> [--box x0 y0 z0 x1 y1 z1]\n"
-    "       pcr_decode <in.huffman> <out.las> --thin CELL [--center] [--box x0 y0 z0 x1 y1 z1]\n"
+    "       pcr_decode <in.huffman> <out.las> --thin CELL [--center | --mean] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --denoise CELL MAXCOUNT [--isolated] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --components CELL MINPOINTS [--conn 6|26] [--small] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --radius R MINCOUNT [--sparse] [--box x0 y0 z0 x1 y1 z1]\n"
@@ -68,7 +68,8 @@ static const char *USAGE =
     "  offset, in double precision), selected on the GPU, in the stream's order. A box that holds no point is an error.\n"
     "  --thin CELL: one point of every cubic voxel of CELL world units (a whole number of the stream's x, y and z lattice steps;\n"
     "  the lattice starts at the min corner of the header's box), thinned on the GPU, in the stream's order: the voxel's first\n"
-    "  point in that order, with --center the one nearest to the voxel's centre. Only the points inside --box count, or inside\n"
+    "  point in that order, with --center the one nearest to the voxel's centre, with --mean (not with --center) the mean of the\n"
+    "  voxel's points instead, position and colour, rounded to the lattice. Only the points inside --box count, or inside\n"
     "  the box of the file's header. No point there is an error.\n"
     "  --denoise CELL MAXCOUNT: the points without the isolated ones, in the stream's order. A point is isolated if the 3 x 3 x 3\n"
     "  cubic voxels of CELL world units around its own (the lattice of --thin) hold at most MAXCOUNT points (a whole number >= 0),\n"
@@ -191,7 +192,7 @@ static bool parse_box(int argc, char **argv, int at, double lo[3], double hi[3])
 
 struct Thin {
     double cell = 0.0;
-    bool center = false, has_box = false;
+    bool center = false, mean = false, has_box = false;
     double lo[3], hi[3];
 };
 
@@ -207,11 +208,13 @@ static bool parse_thin(int argc, char **argv, int at, Thin &t)
             t.has_box = true;
         } else if (a == "--center" && !t.center) {
             t.center = true;
+        } else if (a == "--mean" && !t.mean) {
+            t.mean = true;
         } else {
             return false;
         }
     }
-    return true;
+    return !(t.center && t.mean);
 }
 
 struct Denoise {
@@ -710,7 +713,9 @@ int main(int argc, char **argv)
         } else if (thinned) {
             const pcr_voxels vox = voxelsFromWorld(info, thin.cell, info.min);
             const pcr_box clip = boxFromWorld(info, thin.has_box ? thin.lo : info.min, thin.has_box ? thin.hi : info.max);
-            const pcr_thin_stats st = las->thin(vox, &clip, thin.center ? PCR_THIN_CENTER : PCR_THIN_FIRST, points);
+            std::vector<int64_t> counts;
+            const pcr_thin_stats st = thin.mean ? las->voxelMean(vox, &clip, points, counts)
+                                                : las->thin(vox, &clip, thin.center ? PCR_THIN_CENTER : PCR_THIN_FIRST, points);
             std::printf("thin: cell of %d lattice steps, batches outside %lld, decoded %lld, points considered %lld, runs %lld, kept %lld, table slots %lld\n",
                         vox.cell, (long long)st.batches_outside, (long long)st.batches_decoded, (long long)st.points_considered, (long long)st.runs,
                         (long long)st.points_kept, (long long)st.table_slots);

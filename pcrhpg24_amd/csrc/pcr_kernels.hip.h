@@ -24,6 +24,7 @@
 //   k_neighbors_*   on request: per point the points within a radius and the nearest one, from a copy bucketed by voxel
 //   k_moments_*     on request: per point the exact moments of the offsets to the points within a radius, eigenvalues and normal
 //   k_knn_*         on request: per point its k nearest other points within a radius, ordered by (distance, row), on k_neighbors_*'s index
+//   k_voxel_*       on request: the mean position and colour, the least row and the count of every voxel, on k_thin_*'s FIRST plan
 //   k_las_*         the 10-10-10 method (modules/compute_loop_las_cuda)
 //   k_resolve_*     framebuffer -> RGBA8 (resolve.cu:149-191, huffman_hqs/resolve.cu:2-47)
 //   k_merge_* / k_flip_sign  multi-GPU partial-framebuffer merges
@@ -3985,6 +3986,140 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_knn_write(StreamView s, 
             ++dst;
         }
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Voxel means (pcr_voxel_mean / pcr_read_voxel_mean): one computed record per non-empty voxel -- the mean position, rounded half
+// up inside the voxel, and the mean of each colour byte -- with the voxel's least row and its count. pcr_thin's FIRST plan runs
+// unchanged and leaves the table (key, least row), the keep bitmap and the records per batch; then
+//   k_voxel_prefix   a workgroup per batch that keeps a row: the exclusive prefix of the popcounts of its 1024 keep words, on top
+//                    of the batch's first record (from the host, as for k_thin_write): the record index of every chain's first bit.
+//   k_voxel_index    a thread per slot: the record index of the voxel's least row -- prefix plus the bits below the row's in its
+//                    word -- replaces the row in the slot's value; (key, row) go into the record's entry of `rec`.
+//   k_voxel_sum      decode with colours: a lane sums a run's offsets inside the voxel, its length and its colour bytes in
+//                    registers, looks the voxel's record up at the end of the run (denoise_lookup: the key is there) and adds the
+//                    run into the record's accumulator -- eight 64-bit words, one 64-byte line: S_x, S_y, S_z, n, C_0 .. C_3 --
+//                    with atomic adds whose results are not used (a zero byte sum is not added). Sums of integers commute: the
+//                    accumulators are exact and the same from run to run.
+//   k_voxel_finish   a thread per record of a range of records: the seven roundings (voxel_mean_round, pcr_lattice.h), the
+//                    position rebuilt modulo 2^32 from the key's three indices and the shifted lattice, and the stores.
+// Limits: an offset is below cell <= 2^30 and a call has at most 2^32 rows (PCR_VOXEL_MEAN_MAX_ROWS), so S < 2^62, C < 2^40 and
+// 2 S + n < 2^64. Within a run of at most 64 points an offset sum is below 2^36 and a byte sum below 2^14: two bytes share a
+// 32-bit register. No workgroup waits for another one; the probe loop makes at most `slots` steps.
+// ------------------------------------------------------------------------------------------------
+constexpr int VOXEL_ACC_WORDS = 8;                          // S_x, S_y, S_z, n, C_0, C_1, C_2, C_3
+struct VoxelRec { thin_u64 key, row; };
+
+// thin_key, and the point's offset inside its voxel on every axis (each in [0, cell))
+__device__ __forceinline__ thin_u64 voxel_mean_key(const ThinArgs &a, int32_t x, int32_t y, int32_t z, uint32_t (&r)[3])
+{
+    const uint32_t dx = (uint32_t)x - a.lat.origin[0], dy = (uint32_t)y - a.lat.origin[1], dz = (uint32_t)z - a.lat.origin[2];
+    const uint32_t vx = grid_div(a.lat.div, dx), vy = grid_div(a.lat.div, dy), vz = grid_div(a.lat.div, dz);
+    r[0] = dx - vx * a.lat.cell; r[1] = dy - vy * a.lat.cell; r[2] = dz - vz * a.lat.cell;
+    return (thin_u64)vx | ((thin_u64)vy << THIN_KEY_BITS) | ((thin_u64)vz << (2 * THIN_KEY_BITS));
+}
+
+// Workgroup x takes list[x], a batch that keeps a row: prefix[(b - first_batch) * 1024 + chain] = offsets[x] + the bits set in
+// the keep words of the batch's chains before `chain`
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_voxel_prefix(const uint32_t *list, uint32_t first_batch, const thin_u64 *keep, const int64_t *offsets,
+                                                                     thin_u64 *prefix)
+{
+    const uint32_t b = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ uint32_t s_part[LWC_WAVES];
+    const size_t at = (size_t)(b - first_batch) * PCR_WORKGROUP_SIZE + tid;
+    const uint32_t mine = (uint32_t)__popcll(keep[at]);
+    uint32_t incl = mine;                                   // inclusive prefix inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += up;
+    }
+    if (lane == 63) s_part[wave] = incl;
+    __syncthreads();
+    uint32_t before = incl - mine;
+    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    prefix[at] = (thin_u64)offsets[blockIdx.x] + before;
+}
+
+// The value of every taken slot: the row becomes the record index of the row's bit in the keep bitmap; rec[index] = (key, row).
+// An index that is no record of the call (the bitmap and the table disagree) sets the error word and leaves the slot alone.
+__global__ void __launch_bounds__(256) k_voxel_index(ThinSlot *table, thin_u64 slots, const thin_u64 *keep, const thin_u64 *prefix, thin_u64 records,
+                                                     VoxelRec *rec, uint32_t *error)
+{
+    for (thin_u64 i = (thin_u64)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (thin_u64)gridDim.x * blockDim.x) {
+        const thin_u64 key = table[i].key;
+        if (key == THIN_EMPTY) continue;
+        const thin_u64 row = table[i].val & THIN_ROW_MASK;
+        const thin_u64 index = prefix[row >> 6] + (thin_u64)__popcll(keep[row >> 6] & ((1ull << (row & 63u)) - 1ull));
+        if (index >= records) { *error = 1u; continue; }
+        table[i].val = index;
+        rec[index].key = key; rec[index].row = row;
+    }
+}
+
+__device__ __forceinline__ void voxel_add(thin_u64 *p, thin_u64 v)
+{
+    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                          // (the result is not used)
+}
+
+// Workgroup x takes list[x]: every run of its chains into the accumulator of the run's voxel (acc[index * 8 ..])
+template <int LAYOUT, bool BC7>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_voxel_sum(StreamView s, const uint32_t *list, ThinArgs a, thin_u64 records, thin_u64 *acc)
+{
+    const uint32_t b = list[blockIdx.x];
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    load_packed_table(s, b, s_table);
+    thin_u64 prev = THIN_EMPTY, sx = 0, sy = 0, sz = 0;
+    uint32_t len = 0, c02 = 0, c13 = 0;                     // colour bytes 0 and 2, 1 and 3: two 16-bit sums a register
+    auto flush = [&]() {
+        bool found;
+        const thin_u64 index = denoise_lookup(a.table, a.log2_slots, prev, found);
+        if (!found || index >= records) { *a.error = 1u; return; }                     // (k_thin_mark inserted every run's key)
+        thin_u64 *v = acc + index * VOXEL_ACC_WORDS;
+        voxel_add(v + 0, sx); voxel_add(v + 1, sy); voxel_add(v + 2, sz); voxel_add(v + 3, len);
+        if (c02 & 0xFFFFu) voxel_add(v + 4, c02 & 0xFFFFu);
+        if (c13 & 0xFFFFu) voxel_add(v + 5, c13 & 0xFFFFu);
+        if (c02 >> 16) voxel_add(v + 6, c02 >> 16);
+        if (c13 >> 16) voxel_add(v + 7, c13 >> 16);
+    };
+    decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        uint32_t r[3];
+        const thin_u64 key = in_box(a.q, x, y, z) ? voxel_mean_key(a, x, y, z, r) : THIN_EMPTY;
+        if (key != prev) {
+            if (prev != THIN_EMPTY) flush();
+            prev = key; sx = sy = sz = 0; len = 0; c02 = c13 = 0;
+        }
+        if (key != THIN_EMPTY) {
+            sx += r[0]; sy += r[1]; sz += r[2]; ++len;
+            c02 += colour & 0x00FF00FFu; c13 += (colour >> 8) & 0x00FF00FFu;
+        }
+    });
+    if (prev != THIN_EMPTY) flush();
+}
+
+// Records [i0, i1) of the call: points[i - i0], rows[i - i0], counts[i - i0] (each may be NULL) from acc and rec
+__global__ void __launch_bounds__(256) k_voxel_finish(ThinLattice lat, const thin_u64 *acc, const VoxelRec *rec, thin_u64 i0, thin_u64 i1, uint4 *points,
+                                                      int64_t *rows, int64_t *counts, uint32_t *error)
+{
+    for (thin_u64 i = i0 + (thin_u64)blockIdx.x * blockDim.x + threadIdx.x; i < i1; i += (thin_u64)gridDim.x * blockDim.x) {
+        const thin_u64 *v = acc + i * VOXEL_ACC_WORDS;
+        const thin_u64 n = v[3];
+        if (n == 0) { *error = 1u; continue; }              // (every record's voxel has a run)
+        if (points) {
+            const thin_u64 key = rec[i].key;
+            const uint32_t field = (1u << THIN_KEY_BITS) - 1u;
+            const uint32_t vx = (uint32_t)key & field, vy = (uint32_t)(key >> THIN_KEY_BITS) & field, vz = (uint32_t)(key >> (2 * THIN_KEY_BITS)) & field;
+            const uint32_t x = lat.origin[0] + vx * lat.cell + (uint32_t)voxel_mean_round(v[0], n);
+            const uint32_t y = lat.origin[1] + vy * lat.cell + (uint32_t)voxel_mean_round(v[1], n);
+            const uint32_t z = lat.origin[2] + vz * lat.cell + (uint32_t)voxel_mean_round(v[2], n);
+            const uint32_t colour = (uint32_t)voxel_mean_round(v[4], n) | ((uint32_t)voxel_mean_round(v[5], n) << 8) |
+                                    ((uint32_t)voxel_mean_round(v[6], n) << 16) | ((uint32_t)voxel_mean_round(v[7], n) << 24);
+            points[i - i0] = make_uint4(x, y, z, colour);
+        }
+        if (rows) rows[i - i0] = (int64_t)rec[i].row;
+        if (counts) counts[i - i0] = (int64_t)n;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -52,6 +52,15 @@ inline int thin_lattice(const int32_t origin[3], int32_t cell, const int32_t qmi
     return THIN_LATTICE_OK;
 }
 
+// The mean of n >= 1 non-negative integers with sum s, rounded half up: (2 s + n) / (2 n) in unsigned 64-bit integers. Exact for
+// n <= 2^32 (PCR_VOXEL_MEAN_MAX_ROWS) and s < 2^62: 2 s + n < 2^63 + 2^32 does not wrap. The result lies between the least and the
+// greatest of the integers (a mean does, and both are integers, so rounding cannot leave the interval). constexpr, so that the
+// kernels can call it as well.
+constexpr unsigned long long voxel_mean_round(unsigned long long s, unsigned long long n)
+{
+    return (2ull * s + n) / (2ull * n);
+}
+
 // The lattice of a denoising call: thin_lattice shifted by one whole cell more, origin'' = origin + (floor((q.min - origin) /
 // cell) - 1) * cell, so that q.min lies in voxel 1 on every axis. For a point p inside q, d = p - origin'' is in [cell, q.max -
 // q.min + 2 * cell) -- at most 2^32 - 1 for an extent below 2^31 and a cell of at most 2^30, so it still fits 32 unsigned bits --

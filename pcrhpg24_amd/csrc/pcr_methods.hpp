@@ -360,6 +360,23 @@ struct HuffmanLasData : Resource {
         return st;
     }
 
+    // One computed point per non-empty voxel of `vox` among the points inside `clip` (NULL: everywhere): the mean position, rounded
+    // half up inside the voxel, and the mean of each colour byte, in thin()'s PCR_THIN_FIRST order, with the points per voxel in
+    // `counts`, on the GPU straight from the compressed stream (pcr_read_voxel_mean: a counting call, then the read). Not in the
+    // reference.
+    pcr_thin_stats voxelMean(const pcr_voxels &vox, const pcr_box *clip, std::vector<pcr_point> &points, std::vector<int64_t> &counts)
+    {
+        if (!loadedOn) throw std::runtime_error("voxelMean: the resource is not loaded");
+        const int64_t nB = pcr_batches_resident(loadedOn->ctx);
+        int64_t n = 0;
+        pcr_thin_stats st{};
+        loadedOn->check(pcr_read_voxel_mean(loadedOn->ctx, 0, nB, &vox, clip, nullptr, nullptr, nullptr, 0, &n, &st), "pcr_read_voxel_mean");
+        points.resize((size_t)n); counts.resize((size_t)n);
+        if (n) loadedOn->check(pcr_read_voxel_mean(loadedOn->ctx, 0, nB, &vox, clip, points.data(), nullptr, counts.data(), points.size(), &n, &st),
+                               "pcr_read_voxel_mean");
+        return st;
+    }
+
     // The points inside `clip` (NULL: everywhere) without the isolated ones -- those whose 3 x 3 x 3 voxels of `vox` hold at most
     // max_count of them, the point itself included -- or with PCR_DENOISE_ISOLATED those alone, on the GPU straight from the
     // compressed stream (pcr_read_denoise: a counting call, then the read). Not in the reference.

@@ -1164,6 +1164,55 @@ class Context:
         self.thin_stats = st.as_dict()
         return (pts, r) if rows else pts
 
+    # -- voxel means (pcr_voxel_mean / pcr_read_voxel_mean) --------------------------------------------------
+    def voxel_mean(self, vox, clip=None, first: int = 0, count: Optional[int] = None, out=None, rows: bool = False, counts: bool = False):
+        """One computed point per non-empty voxel of `vox` (as_voxels) among the rows of batches [first, first + count) inside `clip`
+        (as_box; None: everywhere), straight from the compressed stream: the mean position of the voxel's points, rounded half up
+        inside the voxel, and the mean of each colour byte. A torch.int32 tensor [n, 4] on the context's device, in the order of
+        thin(vox, clip, "first"); rows=True appends a torch.int64 tensor [n] of each voxel's lowest row (the rows thin returns),
+        counts=True one of the points per voxel: points, then rows, then counts. `out` and the allocation behave as in thin.
+        Stream ordering as decode_points. What the last call did is in self.voxel_mean_stats (a ThinStats)."""
+        import torch
+        vox, clip = as_voxels(vox), None if clip is None else as_box(clip)
+        cp = None if clip is None else C.byref(clip)
+        dev = torch.device("cuda", self.device)
+        cnt, st, nb = c_i64(), ThinStats(), -1 if count is None else count
+        if out is None:
+            self._chk(self.lib.pcr_voxel_mean(self.h, first, nb, C.byref(vox), cp, None, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_voxel_mean")
+            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
+        cap = out.numel() // 4
+        r = torch.empty(cap, dtype=torch.int64, device=dev) if rows else None
+        n = torch.empty(cap, dtype=torch.int64, device=dev) if counts else None
+        torch.cuda.current_stream(dev).synchronize()
+        rc = self.lib.pcr_voxel_mean(self.h, first, nb, C.byref(vox), cp, C.c_void_p(out.data_ptr() if cap else None),
+                                     C.c_void_p(r.data_ptr() if cap else None) if rows else None,
+                                     C.c_void_p(n.data_ptr() if cap else None) if counts else None, cap, C.byref(cnt), C.byref(st))
+        self.voxel_mean_stats = st.as_dict()
+        if rc:
+            self.voxel_mean_stats["points_kept"] = cnt.value
+        self._chk(rc, "pcr_voxel_mean")
+        res = (out.view(-1, 4)[:cnt.value],) + ((r[:cnt.value],) if rows else ()) + ((n[:cnt.value],) if counts else ())
+        return res if len(res) > 1 else res[0]
+
+    def read_voxel_mean(self, vox, clip=None, first: int = 0, count: Optional[int] = None, rows: bool = False, counts: bool = False):
+        """The same on the host, without torch: a numpy structured array of POINT_DTYPE, then with rows=True an int64 array of the
+        lowest rows, with counts=True one of the points per voxel (pcr_read_voxel_mean: a counting call, then the read;
+        synchronises)."""
+        vox, clip = as_voxels(vox), None if clip is None else as_box(clip)
+        cp = None if clip is None else C.byref(clip)
+        cnt, st, nb = c_i64(), ThinStats(), -1 if count is None else count
+        self._chk(self.lib.pcr_read_voxel_mean(self.h, first, nb, C.byref(vox), cp, None, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_read_voxel_mean")
+        pts = np.empty(cnt.value, POINT_DTYPE)
+        r, n = np.empty(cnt.value if rows else 0, ROW_DTYPE), np.empty(cnt.value if counts else 0, ROW_DTYPE)
+        if cnt.value:
+            self._chk(self.lib.pcr_read_voxel_mean(self.h, first, nb, C.byref(vox), cp, pts.ctypes.data, r.ctypes.data if rows else None,
+                                                   n.ctypes.data if counts else None, len(pts), C.byref(cnt), C.byref(st)), "pcr_read_voxel_mean")
+        self.voxel_mean_stats = st.as_dict()
+        res = (pts,) + ((r,) if rows else ()) + ((n,) if counts else ())
+        return res if len(res) > 1 else res[0]
+
     # -- voxel denoising (pcr_denoise / pcr_read_denoise) ----------------------------------------------------
     def denoise(self, vox, max_count: int, clip=None, mode="keep", first: int = 0, count: Optional[int] = None, out=None, rows: bool = False):
         """The rows of batches [first, first + count) inside `clip` (as_box; None: everywhere) without the isolated ones (mode
@@ -1924,6 +1973,25 @@ class HuffmanLasData(Resource):
             return pts
         so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
         return pts[:, :3].to(torch.float64) * so[0] + so[1], pts
+
+    def voxel_centroids(self, renderer: Renderer, cell_size: float, lo=None, hi=None, world: bool = True):
+        """The loaded resource down-sampled to the centroid of every non-empty cubic voxel of `cell_size`, on the GPU and straight
+        from the compressed stream (Context.voxel_mean): the mean position, rounded to the stream's lattice inside the voxel, and
+        the mean colour of the voxel's points. cell_size, lo, hi and world are as for thinned(). world=True: (xyz, pts, counts) --
+        float64 world positions (i * scale + offset), the int32 records and the int64 points per voxel; world=False: (pts, counts)."""
+        import torch
+        info = self.las_info()
+        if world:
+            vox = voxels_from_world(info, cell_size)
+            clip = box_from_world(info, tuple(info.min) if lo is None else lo, tuple(info.max) if hi is None else hi)
+        else:
+            vox = as_voxels((0, 0, 0, cell_size))
+            clip = None if lo is None and hi is None else as_box(((INT32_MIN,) * 3 if lo is None else lo, (INT32_MAX,) * 3 if hi is None else hi))
+        pts, counts = renderer.ctx.voxel_mean(vox, clip, counts=True)
+        if not world:
+            return pts, counts
+        so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
+        return pts[:, :3].to(torch.float64) * so[0] + so[1], pts, counts
 
     def denoised(self, renderer: Renderer, cell_size: float, max_count: int, lo=None, hi=None, isolated: bool = False, world: bool = True):
         """The loaded resource without its isolated points -- those whose 3 x 3 x 3 cubic voxels of `cell_size` hold at most
