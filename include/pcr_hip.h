@@ -328,6 +328,39 @@ int pcr_grid_unpack(pcr_ctx *ctx, const pcr_grid *grid, const void *dev_words, i
 int pcr_read_grid(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_grid *grid, const pcr_box *clip,
                   uint64_t *host_top, uint64_t *host_bottom, uint32_t *host_count, uint32_t flags, pcr_grid_stats *stats);
 
+/* ---- height percentiles per grid cell: exact order statistics of z (no reference counterpart) --------------------------------
+ * CONTRACT: a record is a candidate of cell c iff it is one of the records pcr_decode_points writes for the range (padding
+ * duplicates and the tail artefact included), lies inside clip (NULL: all), falls into cell c of *grid by pcr_grid's cell rule
+ * exactly, and z >= floor[c] (dev_floor: int32[height * width], or NULL for no test; a floor of INT32_MIN admits every point of
+ * its cell). For a cell with n >= 1 candidates whose z sorted ascending are z_0 <= ... <= z_{n-1}, plane j holds z_k with
+ *   k = (q[j] * (n - 1) + PCR_QUANTILE_ONE / 2) / PCR_QUANTILE_ONE      (unsigned 64-bit integer division)
+ * -- the nearest rank, a half rounded up: q = 0 the lowest z, q = 10000 the highest, never an interpolated value. A cell with
+ * n == 0 holds INT32_MIN (PCR_GROUND_EMPTY, what pcr_grid_unpack writes; a real z == INT32_MIN cannot be told from empty, as
+ * there). An order statistic of a multiset does not depend on the order of its elements: the planes are exact, the same from
+ * run to run and for every layout and flag.
+ * dev_quantiles: int32[num_q][height * width], plane-major, every plane a raster with the layout of pcr_grid_unpack's height
+ *   plane (a low percentile can go to pcr_ground_filter as dev_lowest unchanged), or NULL: then no z is bucketed.
+ * dev_count: uint32[height * width], the candidates per cell (with a floor: the numerator of canopy cover), or NULL. With both
+ *   NULL the call still fills *stats (may be NULL itself).
+ * 1 <= num_q <= PCR_QUANTILES_MAX, every q[j] <= PCR_QUANTILE_ONE, in any order, repeats allowed. flags: 0 or
+ *   PCR_GRID_NO_WINDOW, as for pcr_grid_accumulate (the batch classes in *stats are that call's).
+ * Every cell of every plane asked for is written: no clear call is needed. The call synchronises (the host sizes the scratch
+ * from the candidate count). It touches no framebuffer, no prepass state and no render statistics, supports BC1 and BC7 and
+ * either resident layout, and works before and after the first frame. Scratch memory of the context, grown on demand and
+ * released with it: 12 to 16 bytes per cell and 4 bytes per candidate.
+ * Cost: count and fill are two colourless decode passes; the selection reads a cell of m candidates 1 + 3 * num_q times at most
+ * in a single workgroup, so a grid that puts the whole stream into one cell is slow, not wrong; stats->max_cell_points tells.
+ * pcr_read_grid_quantiles: the same with host memory for the floor and both outputs, through scratch memory of the context.
+ * PCR_E_ARG with a message, nothing written: pcr_grid_accumulate's refusals about range, grid and flags; num_q outside 1 ..
+ * PCR_QUANTILES_MAX; a q above PCR_QUANTILE_ONE; q == NULL; a destination or floor misaligned to 4 bytes; a range of more than
+ * PCR_QUANTILE_MAX_BATCHES batches (the counts and offsets are 32 bits). PCR_E_NOMEM names the scratch size. */
+int pcr_grid_quantiles(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_grid *grid, const pcr_box *clip,
+                       const void *dev_floor, const uint32_t *q, int32_t num_q, void *dev_quantiles, void *dev_count, uint32_t flags,
+                       pcr_quantile_stats *stats);
+int pcr_read_grid_quantiles(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_grid *grid, const pcr_box *clip,
+                            const int32_t *host_floor, const uint32_t *q, int32_t num_q, int32_t *host_quantiles, uint32_t *host_count,
+                            uint32_t flags, pcr_quantile_stats *stats);
+
 /* ---- ground model and heights above it: lasground + lasheight on the grid (no reference counterpart) ---------------------------
  * pcr_ground_filter turns a lowest-point height plane (pcr_grid's bottom plane through pcr_grid_unpack) into a ground plane;
  * pcr_select_height is pcr_select_box with a predicate that looks the record's cell up in such a plane. All integer, all exact.

@@ -192,6 +192,18 @@ typedef struct pcr_grid_stats {
     int64_t batches_outside, batches_windowed, batches_direct;
 } pcr_grid_stats;
 
+/* Height percentiles per cell (pcr_grid_quantiles). q is in basis points: 9500 = the 95th percentile. */
+#define PCR_QUANTILE_ONE       10000
+#define PCR_QUANTILES_MAX      8
+#define PCR_QUANTILE_MAX_BATCHES 65535   /* batches of a call: the counts and segment offsets are 32 bits */
+/* What pcr_grid_quantiles did: pcr_grid_stats' classes of the batches, the candidates (records inside grid and clip at or above
+ * their cell's floor), the cells with at least one, and the most candidates a single cell holds (the select kernels read a
+ * cell of m candidates up to 1 + 3 * num_q times in one workgroup: a very large value here explains a slow call). */
+typedef struct pcr_quantile_stats {
+    int64_t batches_outside, batches_windowed, batches_direct;
+    int64_t candidates, cells_occupied, max_cell_points;
+} pcr_quantile_stats;
+
 /* The ground filter over a lowest-point height plane of a grid (pcr_ground_filter): Zhang et al.'s progressive morphological
  * filter, step k an opening (minimum, then maximum) of the running surface over the square window of radius[k] cells around
  * each cell; a cell whose surface drops by more than threshold[k] in a step is not ground. pcr_hip.h has the exact definition.

@@ -97,6 +97,16 @@ class GridStats(C.Structure):                     # pcr_grid_stats
 GRID_MAX_CELLS, GRID_WINDOW_CELLS, GRID_NO_WINDOW, GRID_TOP, GRID_BOTTOM = 1 << 26, 4096, 1, 0, 1      # pcr_types.h
 
 
+class QuantileStats(C.Structure):                 # pcr_quantile_stats
+    _fields_ = [(n, c_i64) for n in ("batches_outside", "batches_windowed", "batches_direct", "candidates", "cells_occupied", "max_cell_points")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+QUANTILE_ONE, QUANTILES_MAX, QUANTILE_MAX_BATCHES = 10000, 8, 65535                                     # pcr_types.h
+
+
 class GroundParams(C.Structure):                  # pcr_ground_params: the steps of the ground filter and the rounds of its fill, 136 bytes
     _fields_ = [("num_steps", c_i32), ("fill_rounds", c_i32), ("radius", c_i32 * 16), ("threshold", c_i32 * 16)]
 
@@ -210,7 +220,7 @@ assert C.sizeof(Point) == 16 and C.sizeof(Box) == 24 and C.sizeof(SelectStats) =
 assert C.sizeof(Polygon) == 40 and C.sizeof(PolygonStats) == 48
 assert C.sizeof(Rect) == 16 and C.sizeof(ScreenHit) == 16 and C.sizeof(ScreenStats) == 32
 assert C.sizeof(DisplayOpts) == 16
-assert C.sizeof(Grid) == 24 and C.sizeof(GridStats) == 24
+assert C.sizeof(Grid) == 24 and C.sizeof(GridStats) == 24 and C.sizeof(QuantileStats) == 48
 assert C.sizeof(GroundParams) == 136 and C.sizeof(GroundStats) == 48 and C.sizeof(HeightStats) == 32
 assert C.sizeof(Voxels) == 16 and C.sizeof(ThinStats) == 48 and C.sizeof(DenoiseStats) == 72 and C.sizeof(ComponentsStats) == 88
 assert C.sizeof(NeighborsStats) == 80 and C.sizeof(Moments) == 80 and C.sizeof(Eigen) == 48
@@ -239,6 +249,7 @@ HIP_SYMBOLS = [
     "pcr_select_screen", "pcr_read_screen", "pcr_pick",
     "pcr_resolve_basic_display", "pcr_resolve_hqs_display", "pcr_resolve_las_display",
     "pcr_grid_clear", "pcr_grid_accumulate", "pcr_grid_unpack", "pcr_read_grid",
+    "pcr_grid_quantiles", "pcr_read_grid_quantiles",
     "pcr_ground_filter", "pcr_read_ground", "pcr_select_height", "pcr_read_height",
     "pcr_thin", "pcr_read_thin",
     "pcr_denoise", "pcr_read_denoise",
@@ -370,6 +381,9 @@ def hip_lib() -> C.CDLL:
         for n in ("pcr_grid_accumulate", "pcr_read_grid"):
             getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Grid), C.POINTER(Box), C.c_void_p, C.c_void_p, C.c_void_p, c_u32,
                                         C.POINTER(GridStats)]
+        for n in ("pcr_grid_quantiles", "pcr_read_grid_quantiles"):
+            getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Grid), C.POINTER(Box), C.c_void_p, C.POINTER(c_u32), c_i32, C.c_void_p,
+                                        C.c_void_p, c_u32, C.POINTER(QuantileStats)]
         lib.pcr_grid_unpack.argtypes = [C.c_void_p, C.POINTER(Grid), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.pcr_ground_filter.argtypes = [C.c_void_p, C.POINTER(Grid), C.POINTER(GroundParams), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GroundStats)]
         lib.pcr_read_ground.argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Grid), C.POINTER(Box), C.POINTER(GroundParams), C.c_void_p, C.c_void_p,

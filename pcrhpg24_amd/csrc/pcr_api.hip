@@ -157,6 +157,12 @@ struct pcr_ctx {
     bool grid_lds_ready = false;                // hipFuncSetAttribute done for the windowed k_grid launches
     unsigned char *d_grid_scratch = nullptr;    // pcr_read_grid: top, bottom, count planes back to back
     size_t grid_scratch_bytes = 0;
+    // height percentiles (pcr_grid_quantiles) share the list above; their own: the counters, per cell the segment, the work list and
+    // (when the caller takes no counts) the count plane, and the candidates' values bucketed by cell
+    unsigned char *d_quant_scratch = nullptr;
+    size_t quant_scratch_bytes = 0;
+    uint32_t *d_quant_values = nullptr;         // [quant_values_entries]
+    size_t quant_values_entries = 0;
     // voxel thinning (pcr_thin / pcr_read_thin): the lists of a call's batches, the voxel table, the keep bitmap, and
     // pcr_read_thin's staging of the rows (the records go through d_decode_stage)
     int64_t thin_capacity = 0;                  // batches the four arrays below hold
@@ -689,6 +695,8 @@ void pcr_destroy(pcr_ctx *c)
     dfree(c->d_stats);
     dfree(c->d_decode_stage);
     dfree(c->d_grid_scratch);
+    dfree(c->d_quant_scratch);
+    dfree(c->d_quant_values);
     for (int i = 0; i < 2; ++i) {
         if (c->arena[i]) (void)hipHostFree(c->arena[i]);
         if (c->arena_done[i]) (void)hipEventDestroy(c->arena_done[i]);
@@ -2060,6 +2068,55 @@ void grid_launch(pcr_ctx *c, bool windowed, int colour, unsigned nblocks, size_t
 #undef PCR_LAUNCH
 }
 
+// The batches [first, first + n) by their exact box against q (grid and clip intersected, not empty): those the box does not miss
+// into `list` with the rectangle of cells they can reach, the windowed ones (at most PCR_GRID_WINDOW_CELLS cells, and no
+// PCR_GRID_NO_WINDOW) first -- nW of them, the largest window win_cells -- then the direct ones. outside starts as n.
+int grid_classify(pcr_ctx *c, int64_t first, int64_t n, const pcr_grid &g, const pcr_box &q, uint32_t flags, std::vector<GridEntry> &list, size_t &nW,
+                  uint32_t &win_cells, int64_t &outside, int64_t &windowed, int64_t &direct)
+{
+    int rc;
+    if ((rc = ensure_point_bounds(c, first, n))) return rc;
+    const int64_t org[2] = {g.origin_x, g.origin_y};
+    std::vector<GridEntry> dir;
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t *bb = c->h_point_bounds.data() + (first + i) * 6;
+        bool disjoint = false;
+        for (int k = 0; k < 3; ++k) disjoint = disjoint || bb[3 + k] < q.min[k] || bb[k] > q.max[k];
+        if (disjoint) continue;
+        --outside;
+        uint32_t c0[2], c1[2];                              // the cells the batch's box reaches inside grid and clip
+        for (int k = 0; k < 2; ++k) {
+            c0[k] = (uint32_t)(((int64_t)std::max(bb[k], q.min[k]) - org[k]) / g.cell);
+            c1[k] = (uint32_t)(((int64_t)std::min(bb[3 + k], q.max[k]) - org[k]) / g.cell);
+        }
+        const GridEntry e{(uint32_t)(first + i), c0[0], c0[1], c1[0] - c0[0] + 1, c1[1] - c0[1] + 1};
+        const int64_t cells = (int64_t)e.ww * e.wh;
+        if (cells <= PCR_GRID_WINDOW_CELLS && !(flags & PCR_GRID_NO_WINDOW)) { list.push_back(e); win_cells = std::max(win_cells, (uint32_t)cells); ++windowed; }
+        else { dir.push_back(e); ++direct; }
+    }
+    nW = list.size();
+    list.insert(list.end(), dir.begin(), dir.end());
+    return PCR_OK;
+}
+
+// `list` (not empty) into d_grid_list (a call that repeats the last one's list finds it on the device)
+int grid_list_upload(pcr_ctx *c, const std::vector<GridEntry> &list)
+{
+    if (c->grid_capacity < (int64_t)list.size()) {
+        dfree(c->d_grid_list); c->grid_capacity = 0; c->h_grid_list.clear();
+        const int64_t cap = std::max<int64_t>((int64_t)list.size(), c->hdr.num_batches);
+        if (hipMalloc((void **)&c->d_grid_list, (size_t)cap * sizeof(GridEntry)) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for a list of %lld batches", (long long)cap);
+        c->grid_capacity = cap;
+    }
+    if (list.size() != c->h_grid_list.size() || std::memcmp(list.data(), c->h_grid_list.data(), list.size() * sizeof(GridEntry)) != 0) {
+        c->h_grid_list.clear();
+        HIP_TRY(c, hipMemcpyAsync(c->d_grid_list, list.data(), list.size() * sizeof(GridEntry), hipMemcpyHostToDevice, c->stream));
+        c->h_grid_list = list;
+    }
+    return PCR_OK;
+}
+
 // pcr_grid_accumulate behind its range check: n batches from `first`, the planes checked.
 int grid_accumulate(pcr_ctx *c, int64_t first, int64_t n, const pcr_grid &g, const pcr_box *clip, void *top, void *bottom, void *count,
                     uint32_t flags, pcr_grid_stats *stats)
@@ -2080,42 +2137,14 @@ int grid_accumulate(pcr_ctx *c, int64_t first, int64_t n, const pcr_grid &g, con
     }
     if (n == 0 || empty) { if (stats) *stats = st; return PCR_OK; }
     int rc;
-    if ((rc = ensure_point_bounds(c, first, n))) return rc;
-    std::vector<GridEntry> win, dir;
+    std::vector<GridEntry> win;
+    size_t nW = 0;
     uint32_t win_cells = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        const int32_t *bb = c->h_point_bounds.data() + (first + i) * 6;
-        bool disjoint = false;
-        for (int k = 0; k < 3; ++k) disjoint = disjoint || bb[3 + k] < a.q.min[k] || bb[k] > a.q.max[k];
-        if (disjoint) continue;
-        --st.batches_outside;
-        uint32_t c0[2], c1[2];                              // the cells the batch's box reaches inside grid and clip
-        for (int k = 0; k < 2; ++k) {
-            c0[k] = (uint32_t)(((int64_t)std::max(bb[k], a.q.min[k]) - org[k]) / g.cell);
-            c1[k] = (uint32_t)(((int64_t)std::min(bb[3 + k], a.q.max[k]) - org[k]) / g.cell);
-        }
-        const GridEntry e{(uint32_t)(first + i), c0[0], c0[1], c1[0] - c0[0] + 1, c1[1] - c0[1] + 1};
-        const int64_t cells = (int64_t)e.ww * e.wh;
-        if (cells <= PCR_GRID_WINDOW_CELLS && !(flags & PCR_GRID_NO_WINDOW)) { win.push_back(e); win_cells = std::max(win_cells, (uint32_t)cells); ++st.batches_windowed; }
-        else { dir.push_back(e); ++st.batches_direct; }
-    }
+    if ((rc = grid_classify(c, first, n, g, a.q, flags, win, nW, win_cells, st.batches_outside, st.batches_windowed, st.batches_direct))) return rc;
     if (stats) *stats = st;
-    const size_t nW = win.size(), nD = dir.size();
+    const size_t nD = win.size() - nW;
     if (nW + nD == 0) return PCR_OK;
-    win.insert(win.end(), dir.begin(), dir.end());
-    if (c->grid_capacity < (int64_t)win.size()) {
-        dfree(c->d_grid_list); c->grid_capacity = 0; c->h_grid_list.clear();
-        const int64_t cap = std::max<int64_t>((int64_t)win.size(), c->hdr.num_batches);
-        if (hipMalloc((void **)&c->d_grid_list, (size_t)cap * sizeof(GridEntry)) != hipSuccess)
-            return set_err(c, PCR_E_NOMEM, "out of device memory for a list of %lld batches", (long long)cap);
-        c->grid_capacity = cap;
-    }
-    // (a call that repeats the last one's list finds it on the device)
-    if (win.size() != c->h_grid_list.size() || std::memcmp(win.data(), c->h_grid_list.data(), win.size() * sizeof(GridEntry)) != 0) {
-        c->h_grid_list.clear();
-        HIP_TRY(c, hipMemcpyAsync(c->d_grid_list, win.data(), win.size() * sizeof(GridEntry), hipMemcpyHostToDevice, c->stream));
-        c->h_grid_list = win;
-    }
+    if ((rc = grid_list_upload(c, win))) return rc;
     if (!c->grid_lds_ready) {
         hipError_t e = hipSuccess;
 #define PCR_ALLOW(L, C) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_grid<L, C, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GRID_MAX_LDS_BYTES)
@@ -2520,6 +2549,157 @@ int pcr_read_height(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_gr
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         written += m;
     }
+    return PCR_OK;
+}
+
+// ---- height percentiles per grid cell ----------------------------------------------------------
+namespace {
+// The checks both entry points share behind the range check (dev: the floor and the outputs are device pointers, 4-byte aligned).
+int quantiles_check(pcr_ctx *c, int64_t n, const pcr_grid *grid, const void *floor, const uint32_t *q, int32_t num_q, const void *quantiles,
+                    const void *count, uint32_t flags)
+{
+    int rc;
+    if ((rc = grid_check(c, grid, nullptr, nullptr, count))) return rc;
+    if (flags & ~(uint32_t)PCR_GRID_NO_WINDOW) return set_err(c, PCR_E_ARG, "unknown flag bits 0x%x", flags & ~(uint32_t)PCR_GRID_NO_WINDOW);
+    if (!q) return set_err(c, PCR_E_ARG, "q is NULL");
+    if (num_q < 1 || num_q > PCR_QUANTILES_MAX) return set_err(c, PCR_E_ARG, "num_q of %d outside 1 .. %d", num_q, PCR_QUANTILES_MAX);
+    for (int32_t j = 0; j < num_q; ++j)
+        if (q[j] > PCR_QUANTILE_ONE) return set_err(c, PCR_E_ARG, "q[%d] of %u basis points: more than the %d of PCR_QUANTILE_ONE", j, q[j], PCR_QUANTILE_ONE);
+    if (reinterpret_cast<uintptr_t>(quantiles) % 4 != 0) return set_err(c, PCR_E_ARG, "the quantile planes are misaligned (4 bytes)");
+    if (reinterpret_cast<uintptr_t>(floor) % 4 != 0) return set_err(c, PCR_E_ARG, "the floor plane is misaligned (4 bytes)");
+    // the counts, the segment offsets and the candidate total are 32 bits: 65 535 batches hold less than 2^32 records
+    if (n > PCR_QUANTILE_MAX_BATCHES)
+        return set_err(c, PCR_E_ARG, "a range of %lld batches: more than the %d of PCR_QUANTILE_MAX_BATCHES", (long long)n, PCR_QUANTILE_MAX_BATCHES);
+    return PCR_OK;
+}
+
+void quantiles_launch(pcr_ctx *c, bool fill, bool windowed, unsigned nblocks, size_t lds, const GridEntry *list, const QuantArgs &a)
+{
+    const StreamView s = make_stream_view(c);
+    const dim3 grid(nblocks), block(PCR_WORKGROUP_SIZE);
+#define PCR_LAUNCH(L, W) do { if (fill) hipLaunchKernelGGL((k_quant_fill<L, W>), grid, block, lds, c->stream, s, list, a); \
+                              else      hipLaunchKernelGGL((k_quant_count<L, W>), grid, block, lds, c->stream, s, list, a); } while (0)
+    if (select_reads_windows(c)) { if (windowed) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
+    else                         { if (windowed) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+#undef PCR_LAUNCH
+}
+
+// pcr_grid_quantiles behind its checks: n batches from `first`; floor, planes and count are device pointers or NULL. Synchronises.
+int grid_quantiles(pcr_ctx *c, int64_t first, int64_t n, const pcr_grid &g, const pcr_box *clip, const int32_t *floor, const uint32_t *q, int32_t num_q,
+                   int32_t *planes, uint32_t *count, uint32_t flags, pcr_quantile_stats *stats)
+{
+    pcr_quantile_stats st{};
+    st.batches_outside = n;
+    QuantArgs a{};
+    std::vector<GridEntry> list;
+    size_t nW = 0;
+    int rc = PCR_OK;
+    if (n > 0 && grid_clip_box(g, clip, a.q) &&
+        (rc = grid_classify(c, first, n, g, a.q, flags, list, nW, a.win_cells, st.batches_outside, st.batches_windowed, st.batches_direct))) return rc;
+    const size_t nD = list.size() - nW;
+    if (!list.empty() && (rc = grid_list_upload(c, list))) return rc;
+    // the scratch: the counters, then per cell the segment (8 bytes), the work list (4 bytes per cell that can be occupied: no more
+    // than the records decoded) and, if the caller takes no counts, the count plane
+    const size_t cells = (size_t)g.width * (size_t)g.height;
+    const size_t list_capacity = planes ? std::min(cells, list.size() * (size_t)PCR_POINTS_PER_BATCH) : 0;
+    const size_t seg_at = QUANT_COUNTERS * 4, list_at = seg_at + (planes ? cells * 8 : 0), count_at = list_at + list_capacity * 4;
+    const size_t need = count_at + (count ? 0 : cells * 4);
+    if (c->quant_scratch_bytes < need) {
+        dfree(c->d_quant_scratch); c->quant_scratch_bytes = 0;
+        if (hipMalloc((void **)&c->d_quant_scratch, need) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for %zu bytes of scratch for a grid of %zu cells: pass a coarser grid", need, cells);
+        c->quant_scratch_bytes = need;
+    }
+    a.ox = g.origin_x; a.oy = g.origin_y; a.width = (uint32_t)g.width; a.cells = (uint32_t)cells;
+    a.div = make_cell_div((uint32_t)g.cell);
+    a.floor = floor;
+    a.counters = reinterpret_cast<uint32_t *>(c->d_quant_scratch);
+    a.seg = reinterpret_cast<uint2 *>(c->d_quant_scratch + seg_at);
+    a.list = reinterpret_cast<uint32_t *>(c->d_quant_scratch + list_at);
+    a.list_capacity = (uint32_t)list_capacity;
+    a.count = count ? count : reinterpret_cast<uint32_t *>(c->d_quant_scratch + count_at);
+    a.planes = planes;
+    a.num_q = (uint32_t)num_q;
+    for (int32_t j = 0; j < num_q; ++j) a.qv[j] = q[j];
+    const unsigned cell_blocks = (unsigned)std::min<size_t>((cells + 255) / 256, 2048);
+    HIP_TRY(c, hipMemsetAsync(a.counters, 0, QUANT_COUNTERS * 4, c->stream));
+    hipLaunchKernelGGL(k_grid_clear, dim3(cell_blocks), dim3(256), 0, c->stream, (unsigned long long *)nullptr, (unsigned long long *)nullptr, a.count, a.cells);
+    HIP_TRY(c, hipGetLastError());
+    // 1. count
+    if (nW) { quantiles_launch(c, false, true, (unsigned)nW, GRID_TABLE_BYTES + (size_t)a.win_cells * 4, c->d_grid_list, a); HIP_TRY(c, hipGetLastError()); }
+    if (nD) { quantiles_launch(c, false, false, (unsigned)nD, GRID_TABLE_BYTES, c->d_grid_list + nW, a); HIP_TRY(c, hipGetLastError()); }
+    // 2. allocate: segments, work lists, INT32_MIN into the empty cells, the statistics
+    const uint32_t chunk = (uint32_t)(((cells + cell_blocks - 1) / cell_blocks + 255) / 256 * 256);    // per workgroup: chunk * cell_blocks >= cells
+    hipLaunchKernelGGL(k_quant_alloc, dim3(cell_blocks), dim3(256), 0, c->stream, a, chunk);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t h[QUANT_COUNTERS] = {};
+    HIP_TRY(c, hipMemcpyAsync(h, a.counters, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    st.candidates = h[QUANT_VALUES]; st.cells_occupied = (int64_t)h[QUANT_SMALL] + h[QUANT_LARGE]; st.max_cell_points = h[QUANT_MAX_CELL];
+    if (stats) *stats = st;
+    if (h[QUANT_ERROR]) return set_err(c, PCR_E_NOMEM, "the work list of the quantile call is too short");    // (cannot happen)
+    if (!planes || st.candidates == 0) return PCR_OK;
+    if (c->quant_values_entries < (size_t)st.candidates) {
+        dfree(c->d_quant_values); c->quant_values_entries = 0;
+        if (hipMalloc((void **)&c->d_quant_values, (size_t)st.candidates * 4) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for %zu bytes of scratch (the z of %lld candidates): pass a clip or a shorter range",
+                           (size_t)st.candidates * 4, (long long)st.candidates);
+        c->quant_values_entries = (size_t)st.candidates;
+    }
+    a.values = c->d_quant_values; a.candidates = (uint32_t)st.candidates;
+    // 3. fill (the window holds the next slot and the end of every cell: 8 bytes a cell, 48 KiB with the table at most)
+    if (nW) { quantiles_launch(c, true, true, (unsigned)nW, GRID_TABLE_BYTES + (size_t)a.win_cells * 8, c->d_grid_list, a); HIP_TRY(c, hipGetLastError()); }
+    if (nD) { quantiles_launch(c, true, false, (unsigned)nD, GRID_TABLE_BYTES, c->d_grid_list + nW, a); HIP_TRY(c, hipGetLastError()); }
+    // 4. select: a wave per 64 small cells, a workgroup per large one, each list walked with the grid's stride
+    if (h[QUANT_SMALL]) {
+        hipLaunchKernelGGL(k_quant_select_small, dim3(std::min<uint32_t>((h[QUANT_SMALL] + 255) / 256, 8192)), dim3(256), 0, c->stream, a, h[QUANT_SMALL]);
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (h[QUANT_LARGE]) {
+        hipLaunchKernelGGL(k_quant_select_large, dim3(std::min<uint32_t>(h[QUANT_LARGE], 8192)), dim3(256), 0, c->stream, a, h[QUANT_LARGE]);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipMemcpyAsync(h, a.counters, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (h[QUANT_ERROR]) return set_err(c, PCR_E_NOMEM, "the counts and the segments of the quantile call disagree");   // (cannot happen)
+    return PCR_OK;
+}
+} // namespace
+
+int pcr_grid_quantiles(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_grid *grid, const pcr_box *clip, const void *dev_floor,
+                       const uint32_t *q, int32_t num_q, void *dev_quantiles, void *dev_count, uint32_t flags, pcr_quantile_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int64_t n = 0;
+    int rc = select_range(c, first_batch, count, &n);
+    if (rc) return rc;
+    if ((rc = quantiles_check(c, n, grid, dev_floor, q, num_q, dev_quantiles, dev_count, flags))) return rc;
+    return grid_quantiles(c, first_batch, n, *grid, clip, static_cast<const int32_t *>(dev_floor), q, num_q, static_cast<int32_t *>(dev_quantiles),
+                          static_cast<uint32_t *>(dev_count), flags, stats);
+}
+
+int pcr_read_grid_quantiles(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_grid *grid, const pcr_box *clip, const int32_t *host_floor,
+                            const uint32_t *q, int32_t num_q, int32_t *host_quantiles, uint32_t *host_count, uint32_t flags, pcr_quantile_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int64_t n = 0;
+    int rc = select_range(c, first_batch, count, &n);
+    if (rc) return rc;
+    if ((rc = quantiles_check(c, n, grid, host_floor, q, num_q, host_quantiles, host_count, flags))) return rc;
+    // the floor, the planes and the counts in the scratch memory pcr_read_grid uses
+    const size_t cells = (size_t)grid->width * (size_t)grid->height;
+    const size_t planes_at = host_floor ? cells * 4 : 0, count_at = planes_at + (host_quantiles ? cells * 4 * (size_t)num_q : 0);
+    if ((rc = grid_scratch_reserve(c, std::max<size_t>(count_at + (host_count ? cells * 4 : 0), 16)))) return rc;
+    int32_t *const d_floor = host_floor ? reinterpret_cast<int32_t *>(c->d_grid_scratch) : nullptr;
+    int32_t *const d_planes = host_quantiles ? reinterpret_cast<int32_t *>(c->d_grid_scratch + planes_at) : nullptr;
+    uint32_t *const d_count = host_count ? reinterpret_cast<uint32_t *>(c->d_grid_scratch + count_at) : nullptr;
+    if (d_floor) HIP_TRY(c, hipMemcpyAsync(d_floor, host_floor, cells * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = grid_quantiles(c, first_batch, n, *grid, clip, d_floor, q, num_q, d_planes, d_count, flags, stats))) return rc;
+    if (d_planes) HIP_TRY(c, hipMemcpyAsync(host_quantiles, d_planes, cells * 4 * (size_t)num_q, hipMemcpyDeviceToHost, c->stream));
+    if (d_count) HIP_TRY(c, hipMemcpyAsync(host_count, d_count, cells * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return PCR_OK;
 }
 

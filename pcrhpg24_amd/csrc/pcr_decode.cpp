@@ -10,6 +10,7 @@
 //     pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]
 //     pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1] [--rect x0 y0 x1 y1]
 //     pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]
+//     pcr_decode <in.huffman> <out.asc> --percentile P CELL [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.asc> --dtm CELL [--slope S] [--max-window W] [--initial D] [--max-distance D] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --height CELL LO HI [--normalize] [--slope S] [--max-window W] [--initial D] [--max-distance D] [--box ...]
 // Loads the file with the loader of the render tools (HuffmanLasData, csrc/pcr_methods.hpp), reads the points back in pieces of
@@ -26,7 +27,8 @@
 // of their neighbourhood within a radius, as a PLY (pcr_read_local_moments). With --sor they come back without the statistical
 // outliers -- by the mean distance to their k nearest neighbours within a radius -- or those alone (pcr_read_knn).
 // With --dtm the lowest-point grid goes through the ground filter on the GPU (pcr_read_ground) and the terrain model is written;
-// with --height the points whose height above that model lies in a range are read back (pcr_read_height).
+// with --height the points whose height above that model lies in a range are read back (pcr_read_height). With --percentile the
+// exact P-th percentile of z per cell is written like --dsm's surface model (pcr_read_grid_quantiles).
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -54,6 +56,7 @@ static const char *USAGE =
     "       pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1]\n"
     "                                                [--rect x0 y0 x1 y1]\n"
     "       pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]\n"
+    "       pcr_decode <in.huffman> <out.asc> --percentile P CELL [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.asc> --dtm CELL [--slope S] [--max-window W] [--initial D] [--max-distance D]\n"
     "                                                [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --height CELL LO HI [--normalize] [--slope S] [--max-window W] [--initial D]\n"
@@ -109,6 +112,11 @@ static const char *USAGE =
     "  PPM (empty cells black), rows from north to south. The cells cover the x and y range of --box, of which z0 and z1 clip the\n"
     "  points, or the box of the file's header. --dsm: the height of that point as an ESRI ASCII grid (ncols, nrows, xllcorner,\n"
     "  yllcorner, cellsize, NODATA_value -9999; world units, %.17g), the same rows. A grid no point falls into is an error.\n"
+    "  --percentile P CELL: no LAS file; the exact P-th percentile (0 .. 100, a whole number of hundredths) of the heights of every\n"
+    "  cell of CELL world units as an ESRI ASCII grid like --dsm's: the z of the point of rank round(P / 100 * (n - 1)) among the\n"
+    "  cell's n points sorted by z, a half rounded up, never interpolated. 95 or 99 is a surface model that one stray return does\n"
+    "  not set, 2 or 5 a robust lowest plane. The cells cover the x and y range of --box, of which z0 and z1 clip the points, or\n"
+    "  the box of the file's header. It combines with no other mode. A grid no point falls into is an error.\n"
     "  --dtm CELL: no LAS file; a terrain model as an ESRI ASCII grid like --dsm's. The lowest point of every cell of CELL world\n"
     "  units goes through a progressive morphological filter on the GPU: windows of 3, 5, 9, ... cells up to --max-window world\n"
     "  units (33), a cell being ground unless an opening lowers it by more than --initial (0.15) at the first window and\n"
@@ -478,6 +486,35 @@ static bool parse_ortho(int argc, char **argv, int at, Ortho &o)
     return true;
 }
 
+struct Percentile {
+    uint32_t q = 0;                     // basis points
+    double cell = 0.0;
+    bool has_box = false;
+    double lo[3], hi[3];
+};
+
+// the options behind --percentile, every one well formed, or false
+static bool parse_percentile(int argc, char **argv, int at, Percentile &p)
+{
+    if (argc < at + 3 || std::strcmp(argv[at], "--percentile") != 0) return false;
+    double pct = 0.0;
+    if (!parse_double(argv[at + 1], pct) || pct < 0.0 || pct > 100.0) return false;
+    const double bp = std::floor(pct * 100.0 + 0.5);
+    if (std::fabs(pct * 100.0 - bp) > 1e-6) return false;               // (not a whole basis point)
+    p.q = (uint32_t)bp;
+    if (!parse_double(argv[at + 2], p.cell) || !(p.cell > 0.0)) return false;
+    for (int i = at + 3; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--box" && i + 6 < argc && !p.has_box) {
+            for (int k = 0; k < 6; ++k) if (!parse_double(argv[++i], k < 3 ? p.lo[k] : p.hi[k - 3])) return false;
+            p.has_box = true;
+        } else {
+            return false;                                               // (--ortho, --dtm, --thin, ...: it combines with no other mode)
+        }
+    }
+    return true;
+}
+
 struct Ground {
     double cell = 0.0, h_lo = 0.0, h_hi = 0.0;
     double slope = 1.0, max_window = 33.0, initial = 0.15, max_distance = 2.5;
@@ -565,6 +602,43 @@ static void write_dtm(HuffmanLasData &las, const pcr_las_info &info, const Groun
     std::printf("cells %zu of %zu with a height -> %s\n", filled, ground.size(), asc.c_str());
 }
 
+// The percentile raster (ESRI ASCII grid) of the loaded resource, rows from north to south, as write_ortho writes the surface model.
+static void write_percentile(HuffmanLasData &las, const pcr_las_info &info, const Percentile &p, const std::string &asc)
+{
+    const double lo[2] = {p.has_box ? p.lo[0] : info.min[0], p.has_box ? p.lo[1] : info.min[1]};
+    const double hi[2] = {p.has_box ? p.hi[0] : info.max[0], p.has_box ? p.hi[1] : info.max[1]};
+    const pcr_grid grid = gridFromWorld(info, lo, hi, p.cell);
+    pcr_box clip{};
+    if (p.has_box) {
+        const double inf = std::numeric_limits<double>::infinity();
+        const double l3[3] = {-inf, -inf, p.lo[2]}, h3[3] = {inf, inf, p.hi[2]};
+        clip = boxFromWorld(info, l3, h3);
+    }
+    std::vector<int32_t> plane;
+    std::vector<uint32_t> count;
+    const pcr_quantile_stats st = las.heightQuantiles(grid, p.has_box ? &clip : nullptr, nullptr, std::vector<uint32_t>{p.q}, plane, &count);
+    std::printf("percentile: %u basis points, %d x %d cells of %d lattice steps, batches outside %lld, windowed %lld, direct %lld, cells occupied %lld, "
+                "candidates %lld, largest cell %lld\n", p.q, grid.width, grid.height, grid.cell, (long long)st.batches_outside, (long long)st.batches_windowed,
+                (long long)st.batches_direct, (long long)st.cells_occupied, (long long)st.candidates, (long long)st.max_cell_points);
+    if (!st.candidates) throw std::runtime_error("no points inside the grid: nothing written");
+    FILE *f = std::fopen(asc.c_str(), "w");
+    if (!f) throw std::runtime_error(asc + ": cannot open for writing");
+    const double px = (double)grid.origin_x * info.scale[0], py = (double)grid.origin_y * info.scale[1];
+    std::fprintf(f, "ncols %d\nnrows %d\nxllcorner %.17g\nyllcorner %.17g\ncellsize %.17g\nNODATA_value -9999\n", grid.width, grid.height,
+                 px + info.offset[0], py + info.offset[1], p.cell);
+    for (int cy = grid.height - 1; cy >= 0; --cy) {
+        for (int cx = 0; cx < grid.width; ++cx) {
+            const size_t g = (size_t)cy * grid.width + cx;
+            const double pz = (double)plane[g] * info.scale[2];
+            if (count[g]) std::fprintf(f, cx ? " %.17g" : "%.17g", pz + info.offset[2]);
+            else std::fputs(cx ? " -9999" : "-9999", f);
+        }
+        std::fputc('\n', f);
+    }
+    if (std::fclose(f) != 0) throw std::runtime_error(asc + ": write failed");
+    std::printf("cells %lld of %zu filled -> %s\n", (long long)st.cells_occupied, plane.size(), asc.c_str());
+}
+
 // The orthophoto (binary PPM) and, with a path, the surface model (ESRI ASCII grid) of the loaded resource, rows from north to south.
 static void write_ortho(HuffmanLasData &las, const pcr_las_info &info, const Ortho &o, const std::string &ppm)
 {
@@ -639,12 +713,14 @@ int main(int argc, char **argv)
     const bool normaled = argc > 3 && std::strcmp(argv[3], "--normals") == 0;
     Sor sor;
     const bool sored = argc > 3 && std::strcmp(argv[3], "--sor") == 0;
-    const bool boxed = argc > 3 && !viewed && !orthoed && !thinned && !polygoned && !denoised && !componented && !grounded && !radiused && !normaled && !sored;
+    Percentile pctl;
+    const bool percentiled = argc > 3 && std::strcmp(argv[3], "--percentile") == 0;
+    const bool boxed = argc > 3 && !percentiled && !viewed && !orthoed && !thinned && !polygoned && !denoised && !componented && !grounded && !radiused && !normaled && !sored;
     if (argc < 3 || (polygoned && !parse_polygon(argc, argv, 3, poly)) || (boxed && !parse_box(argc, argv, 3, lo, hi)) || (viewed && !parse_view(argc, argv, 3, view)) ||
         (orthoed && !parse_ortho(argc, argv, 3, ortho)) || (thinned && !parse_thin(argc, argv, 3, thin)) || (denoised && !parse_denoise(argc, argv, 3, noise)) ||
         (componented && !parse_components(argc, argv, 3, comps)) || (grounded && !parse_ground(argc, argv, 3, ground)) ||
         (radiused && !parse_radius(argc, argv, 3, rad)) || (normaled && !parse_normals(argc, argv, 3, nrm)) ||
-        (sored && !parse_sor(argc, argv, 3, sor))) { std::fputs(USAGE, stderr); return 2; }
+        (sored && !parse_sor(argc, argv, 3, sor)) || (percentiled && !parse_percentile(argc, argv, 3, pctl))) { std::fputs(USAGE, stderr); return 2; }
     const std::string in = argv[1], out = argv[2];
     try {
         Renderer renderer(viewed ? view.w : 64, viewed ? view.h : 64, 0);
@@ -663,6 +739,11 @@ int main(int argc, char **argv)
         const pcr_las_info info = las->lasInfo();
         if (orthoed) {
             write_ortho(*las, info, ortho, out);
+            las->unload(&renderer);
+            return 0;
+        }
+        if (percentiled) {
+            write_percentile(*las, info, pctl, out);
             las->unload(&renderer);
             return 0;
         }

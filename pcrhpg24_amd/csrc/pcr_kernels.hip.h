@@ -2452,6 +2452,352 @@ __global__ void __launch_bounds__(256) k_grid_unpack(const unsigned long long *w
 }
 
 // ------------------------------------------------------------------------------------------------
+// Height percentiles per cell (pcr_grid_quantiles): the z of every candidate bucketed by cell, then an exact selection per cell.
+// A candidate is a record inside grid and clip whose z is at least its cell's floor (no floor plane: every record). The host
+// lists the batches as for k_grid (GridEntry, windowed ones first). One launch each, windowed and direct batches apart:
+//   k_quant_count   colourless decode: count[cell] += 1 per candidate. Windowed: LDS adds in a window beside the table, then one
+//                   global add per non-empty cell; direct: one global add per candidate.
+//   k_quant_alloc   a thread per cell, k_neighbors_alloc's scheme with the cursors taken once per workgroup (a grid of 2^26 cells
+//                   has 2^20 waves: an atomic each on one word measured 11 ms per 10^7 cells): an occupied cell takes its
+//                   segment [start, start + n) of the value array from one cursor and its entry in the work list from another.
+//                   Cells of at most 64 candidates are listed from the front, larger ones from the back, so each select
+//                   launch is uniform. An empty cell gets INT32_MIN in every plane. The cursors are the call's statistics: candidates,
+//                   occupied cells (both lists), and the largest n by an atomic max.
+//   k_quant_fill    colourless decode again: (uint32)z ^ 0x80000000 of every candidate into its cell's segment. Windowed: the
+//                   workgroup decodes its batch twice. The first decode counts per window cell in LDS; after a barrier one
+//                   global atomic per non-empty window cell reserves the batch's share of the cell's segment and leaves its
+//                   base and end in LDS; after a second barrier the second decode takes a slot with an LDS add that returns.
+//                   One global atomic per cell and batch, not per candidate. Direct: one global atomic per candidate.
+//   k_quant_select_small   n <= 64: a wave per cell, lane i holds value i; its rank is the number of lanes j with v_j < v_i or
+//                   (v_j == v_i and j < i), taken with n wave-uniform lane reads -- no LDS, no barrier. The ranks are a
+//                   permutation of 0 .. n - 1, so for every q exactly one lane stores. Cells of at most 4 candidates (a fine
+//                   grid has little else) take a lane each instead: four values sorted in registers.
+//   k_quant_select_large   n > 64: a 256-thread workgroup per cell, an MSB-first radix select with 8-bit digits over a 256-bin
+//                   LDS histogram. The first pass's histogram serves every rank; the three later passes run per distinct
+//                   rank. A cell of m candidates is read 1 + 3 * (distinct ranks) <= 1 + 3 * num_q times by one workgroup: a
+//                   grid that puts the whole stream into one cell is slow, not wrong (max_cell_points tells).
+// An order statistic of a multiset does not depend on the order of its elements, so which segment lies where and which slot a
+// candidate takes is unobservable. No workgroup waits for another one; every loop is bounded by n, the cells or the list; every
+// store into the value array or the list is tested against the end of its segment and of the array (a miss sets the error
+// word, which the host reads).
+// ------------------------------------------------------------------------------------------------
+enum { QUANT_VALUES = 0, QUANT_SMALL, QUANT_LARGE, QUANT_MAX_CELL, QUANT_ERROR, QUANT_COUNTERS = 8 };
+constexpr uint32_t QUANT_SMALL_MAX = 64, QUANT_TINY_MAX = 4;
+struct QuantArgs {
+    pcr_box q;                      // grid and clip intersected, not empty (GridArgs::q)
+    int32_t ox, oy;
+    CellDiv div;
+    uint32_t width, cells;
+    uint32_t win_cells;             // cells of each LDS array of a windowed launch: the largest window listed
+    const int32_t *floor;           // [cells] or NULL: a candidate has z >= floor[cell]
+    uint32_t *count;                // [cells] candidates per cell
+    uint2 *seg;                     // [cells] x: the first entry of the cell's segment, y: entries reserved (k_quant_fill)
+    uint32_t *values;               // [candidates] (uint32)z ^ 0x80000000, bucketed by cell
+    uint32_t candidates;
+    uint32_t *list;                 // [list_capacity] cells with 1 .. 64 candidates from the front, larger ones from the back
+    uint32_t list_capacity;
+    int32_t *planes;                // [num_q][cells] or NULL (count only: nothing but count and the counters is written)
+    uint32_t num_q;
+    uint32_t qv[PCR_QUANTILES_MAX]; // basis points
+    uint32_t *counters;             // [QUANT_COUNTERS]
+};
+
+__device__ __forceinline__ bool quant_cell(const QuantArgs &a, int32_t x, int32_t y, int32_t z, uint32_t &cx, uint32_t &cy)
+{
+    if (!in_box(a.q, x, y, z)) return false;
+    cx = grid_div(a.div, (uint32_t)x - (uint32_t)a.ox); cy = grid_div(a.div, (uint32_t)y - (uint32_t)a.oy);
+    return !a.floor || z >= a.floor[(size_t)cy * a.width + cx];
+}
+
+template <int LAYOUT, bool WINDOWED>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_quant_count(StreamView s, const GridEntry *list, QuantArgs a)
+{
+    const GridEntry e = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x;
+    extern __shared__ __align__(16) unsigned char s_dyn[];                  // the table, then the window's counts
+    uint32_t *s_table = reinterpret_cast<uint32_t *>(s_dyn);
+    uint32_t *s_count = reinterpret_cast<uint32_t *>(s_dyn + GRID_TABLE_BYTES);
+    const uint32_t ncell = e.ww * e.wh;
+    if (WINDOWED) {
+        if (ncell > a.win_cells) return;                                    // (uniform; the host lists no such window)
+        for (uint32_t i = tid; i < ncell; i += PCR_WORKGROUP_SIZE) s_count[i] = 0u;
+    }
+    load_packed_table(s, e.b, s_table);                                     // (its barrier publishes the window as well)
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, e.b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t) {
+        uint32_t cx, cy;
+        if (!quant_cell(a, x, y, z, cx, cy)) return;
+        if (WINDOWED) {
+            const uint32_t lx = cx - e.wx0, ly = cy - e.wy0;
+            if (lx >= e.ww || ly >= e.wh) return;                           // (no point of the batch: the window is its exact box's)
+            __hip_atomic_fetch_add(&s_count[ly * e.ww + lx], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        } else {
+            atomicAdd(&a.count[(size_t)cy * a.width + cx], 1u);
+        }
+    });
+    if (WINDOWED) {
+        __syncthreads();
+        for (uint32_t i = tid; i < ncell; i += PCR_WORKGROUP_SIZE) {
+            const uint32_t ly = i / e.ww, lx = i - ly * e.ww;
+            const uint32_t v = s_count[i];
+            if (v) atomicAdd(&a.count[(size_t)(e.wy0 + ly) * a.width + e.wx0 + lx], v);
+        }
+    }
+}
+
+// Workgroup x takes the cells [x * chunk, (x + 1) * chunk) (chunk: a multiple of 256; chunk * gridDim.x >= cells): first their
+// totals, with one atomic per cursor and workgroup, then the cells in order with a running prefix -- a wave's prefix by
+// shuffles, the waves' totals through LDS.
+__global__ void __launch_bounds__(256) k_quant_alloc(QuantArgs a, uint32_t chunk)
+{
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ uint32_t s_wave[4][3], s_base[3];
+    const uint32_t c0 = blockIdx.x * chunk, c1 = min(a.cells, c0 + chunk);
+    if (c0 >= a.cells) return;                                              // (uniform)
+    uint32_t total[3] = {0, 0, 0}, largest = 0;
+    for (uint32_t i = c0 + tid; i < c1; i += 256u) {
+        const uint32_t n = a.count[i];
+        total[0] += n; total[1] += n >= 1u && n <= QUANT_SMALL_MAX ? 1u : 0u; total[2] += n > QUANT_SMALL_MAX ? 1u : 0u;
+        largest = max(largest, n);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) total[k] += __shfl_xor(total[k], d, 64);
+        largest = max(largest, (uint32_t)__shfl_xor(largest, d, 64));
+    }
+    if (lane == 0) {
+        for (int k = 0; k < 3; ++k) s_wave[wave][k] = total[k];
+        if (largest) atomicMax(&a.counters[QUANT_MAX_CELL], largest);
+    }
+    __syncthreads();
+    if (tid < 3u) {
+        const uint32_t t = s_wave[0][tid] + s_wave[1][tid] + s_wave[2][tid] + s_wave[3][tid];
+        s_base[tid] = t ? atomicAdd(&a.counters[QUANT_VALUES + tid], t) : 0u;   // (QUANT_VALUES, QUANT_SMALL, QUANT_LARGE are 0, 1, 2)
+    }
+    __syncthreads();
+    if (!a.planes) return;                                                  // (uniform) count only: the cursors and the maximum are all there is
+    uint32_t run[3] = {s_base[0], s_base[1], s_base[2]};
+    for (uint32_t base = c0; base < c1; base += 256u) {                     // (every thread makes the same rounds)
+        __syncthreads();                                                    // (the round before has read s_wave)
+        const uint32_t i = base + tid;
+        const uint32_t n = i < c1 ? a.count[i] : 0u;
+        const uint32_t own[3] = {n, n >= 1u && n <= QUANT_SMALL_MAX ? 1u : 0u, n > QUANT_SMALL_MAX ? 1u : 0u};
+        uint32_t incl[3] = {own[0], own[1], own[2]};                        // inclusive prefixes over the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const uint32_t u = __shfl_up(incl[k], d, 64);
+                if (lane >= (uint32_t)d) incl[k] += u;
+            }
+        }
+        if (lane == 63u) for (int k = 0; k < 3; ++k) s_wave[wave][k] = incl[k];
+        __syncthreads();
+        uint32_t at[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            uint32_t before = 0, all = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < 4u; ++w) { const uint32_t t = s_wave[w][k]; all += t; before += w < wave ? t : 0u; }
+            at[k] = run[k] + before + incl[k] - own[k];
+            run[k] += all;
+        }
+        if (i < c1) {
+            if (n == 0u) {
+                for (uint32_t j = 0; j < a.num_q; ++j) a.planes[(size_t)j * a.cells + i] = INT32_MIN;
+            } else {
+                a.seg[i] = make_uint2(at[0], 0u);
+                const uint32_t slot = own[1] ? at[1] : a.list_capacity - 1u - at[2];
+                if (slot < a.list_capacity) a.list[slot] = i;
+                else a.counters[QUANT_ERROR] = 1u;
+            }
+        }
+    }
+}
+
+template <int LAYOUT, bool WINDOWED>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_quant_fill(StreamView s, const GridEntry *list, QuantArgs a)
+{
+    const GridEntry e = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x;
+    extern __shared__ __align__(16) unsigned char s_dyn[];                  // the table, then per window cell the next slot and the end
+    uint32_t *s_table = reinterpret_cast<uint32_t *>(s_dyn);
+    uint32_t *s_next = reinterpret_cast<uint32_t *>(s_dyn + GRID_TABLE_BYTES);
+    uint32_t *s_end = s_next + a.win_cells;
+    const uint32_t ncell = e.ww * e.wh;
+    if (WINDOWED) {
+        if (ncell > a.win_cells) return;                                    // (uniform; the host lists no such window)
+        for (uint32_t i = tid; i < ncell; i += PCR_WORKGROUP_SIZE) s_next[i] = 0u;
+    }
+    load_packed_table(s, e.b, s_table);                                     // (its barrier publishes the window as well)
+    if (WINDOWED) {
+        decode_chain<LAYOUT, SEL_NO_COLOUR>(s, e.b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t) {
+            uint32_t cx, cy;
+            if (!quant_cell(a, x, y, z, cx, cy)) return;
+            const uint32_t lx = cx - e.wx0, ly = cy - e.wy0;
+            if (lx >= e.ww || ly >= e.wh) return;
+            __hip_atomic_fetch_add(&s_next[ly * e.ww + lx], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        });
+        __syncthreads();
+        // the batch's share of every cell it reaches: [first, first + n) of the cell's segment, never past what k_quant_count
+        // counted for the cell nor past the array
+        for (uint32_t i = tid; i < ncell; i += PCR_WORKGROUP_SIZE) {
+            const uint32_t n = s_next[i];
+            uint32_t first = 0, end = 0;
+            if (n) {
+                const uint32_t ly = i / e.ww, lx = i - ly * e.ww;
+                const size_t g = (size_t)(e.wy0 + ly) * a.width + e.wx0 + lx;
+                const unsigned long long taken = atomicAdd(&a.seg[g].y, n);
+                const unsigned long long at = (unsigned long long)a.seg[g].x + taken;
+                if (taken + n <= a.count[g] && at + n <= a.candidates) { first = (uint32_t)at; end = first + n; }
+                else a.counters[QUANT_ERROR] = 1u;
+            }
+            s_next[i] = first; s_end[i] = end;
+        }
+        __syncthreads();
+    }
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, e.b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t) {
+        uint32_t cx, cy;
+        if (!quant_cell(a, x, y, z, cx, cy)) return;
+        const uint32_t value = (uint32_t)z ^ 0x80000000u;
+        if (WINDOWED) {
+            const uint32_t lx = cx - e.wx0, ly = cy - e.wy0;
+            if (lx >= e.ww || ly >= e.wh) return;
+            const uint32_t i = ly * e.ww + lx;
+            const uint32_t at = __hip_atomic_fetch_add(&s_next[i], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (at < s_end[i]) a.values[at] = value;
+            else a.counters[QUANT_ERROR] = 1u;
+        } else {
+            const size_t g = (size_t)cy * a.width + cx;
+            const uint32_t taken = atomicAdd(&a.seg[g].y, 1u);
+            const unsigned long long at = (unsigned long long)a.seg[g].x + taken;
+            if (taken < a.count[g] && at < a.candidates) a.values[at] = value;
+            else a.counters[QUANT_ERROR] = 1u;
+        }
+    });
+}
+
+// The segment of listed cell `cell` (uniform over the caller's wave or workgroup): false, with the error word set, unless it is
+// full and inside the array
+__device__ __forceinline__ bool quant_segment(const QuantArgs &a, uint32_t cell, uint32_t &start, uint32_t &n)
+{
+    const uint2 sg = a.seg[cell];
+    start = sg.x; n = a.count[cell];
+    if (cell < a.cells && n >= 1u && sg.y == n && (unsigned long long)start + n <= a.candidates) return true;
+    a.counters[QUANT_ERROR] = 1u;
+    return false;
+}
+
+__device__ __forceinline__ void quant_order(uint32_t &lo, uint32_t &hi)
+{
+    const uint32_t a = min(lo, hi), b = max(lo, hi);
+    lo = a; hi = b;
+}
+
+// A wave takes 64 listed cells at a time. A cell of at most QUANT_TINY_MAX candidates is one lane's: its values sorted in
+// registers by a network. The others go one after the other through the whole wave, lane i holding value i.
+__global__ void __launch_bounds__(256) k_quant_select_small(QuantArgs a, uint32_t items)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6), waves = gridDim.x * (blockDim.x >> 6);
+    for (uint32_t w0 = wave * 64u; w0 < items; w0 += waves * 64u) {
+        uint32_t cell = 0, start = 0, n = 0;
+        if (w0 + lane < items) {
+            cell = min(a.list[w0 + lane], a.cells - 1u);
+            if (!quant_segment(a, cell, start, n)) n = 0u;
+            n = min(n, QUANT_SMALL_MAX);
+        }
+        if (n >= 1u && n <= QUANT_TINY_MAX) {
+            uint32_t v0 = a.values[start], v1 = n > 1u ? a.values[start + 1u] : 0xFFFFFFFFu;
+            uint32_t v2 = n > 2u ? a.values[start + 2u] : 0xFFFFFFFFu, v3 = n > 3u ? a.values[start + 3u] : 0xFFFFFFFFu;
+            quant_order(v0, v1); quant_order(v2, v3); quant_order(v0, v2); quant_order(v1, v3); quant_order(v1, v2);
+            for (uint32_t k = 0; k < a.num_q; ++k) {
+                const uint32_t r = (uint32_t)quantile_rank(a.qv[k], n);
+                a.planes[(size_t)k * a.cells + cell] = (int32_t)((r == 0u ? v0 : r == 1u ? v1 : r == 2u ? v2 : v3) ^ 0x80000000u);
+            }
+        }
+        unsigned long long todo = __ballot(n > QUANT_TINY_MAX);
+        while (todo) {                                                      // (uniform: at most 64 rounds)
+            const int l = __builtin_ctzll(todo);
+            todo &= todo - 1ull;
+            const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cell, l), first = (uint32_t)__builtin_amdgcn_readlane((int)start, l);
+            const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)n, l);
+            const uint32_t v = lane < m ? a.values[first + lane] : 0xFFFFFFFFu;
+            uint32_t rank = 0;
+            for (uint32_t j = 0; j < m; ++j) {
+                const uint32_t vj = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)j);
+                rank += vj < v || (vj == v && j < lane) ? 1u : 0u;
+            }
+            for (uint32_t k = 0; k < a.num_q; ++k)
+                if (lane < m && rank == (uint32_t)quantile_rank(a.qv[k], m)) a.planes[(size_t)k * a.cells + c] = (int32_t)(v ^ 0x80000000u);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_quant_select_large(QuantArgs a, uint32_t items)
+{
+    const uint32_t tid = threadIdx.x;
+    __shared__ uint32_t s_first[256], s_hist[256], s_pick[2], s_result[PCR_QUANTILES_MAX];
+    for (uint32_t w = blockIdx.x; w < items; w += gridDim.x) {
+        const uint32_t cell = min(a.list[a.list_capacity - 1u - w], a.cells - 1u);
+        uint32_t start, n;
+        if (!quant_segment(a, cell, start, n)) continue;                    // (uniform: every thread read the same words)
+        const uint32_t *v = a.values + start;
+        s_first[tid] = 0u;
+        __syncthreads();
+        for (uint32_t i = tid; i < n; i += 256u) __hip_atomic_fetch_add(&s_first[v[i] >> 24], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __syncthreads();
+        for (uint32_t j = 0; j < a.num_q; ++j) {
+            uint32_t k = (uint32_t)quantile_rank(a.qv[j], n);
+            int same = -1;                                                  // an earlier q with this rank: its result is this one's
+            for (uint32_t jj = 0; jj < j; ++jj) if ((uint32_t)quantile_rank(a.qv[jj], n) == k) same = (int)jj;
+            if (same >= 0) { if (tid == 0) s_result[j] = s_result[same]; continue; }
+            uint32_t prefix = 0;                                            // the digits found so far, in place
+            for (int pass = 0; pass < 4; ++pass) {
+                const uint32_t shift = 24u - 8u * (uint32_t)pass;
+                const uint32_t *hist = pass == 0 ? s_first : s_hist;
+                if (pass) {
+                    s_hist[tid] = 0u;
+                    __syncthreads();
+                    for (uint32_t i = tid; i < n; i += 256u) {
+                        const uint32_t x = v[i];
+                        if ((x >> (shift + 8u)) == (prefix >> (shift + 8u)))
+                            __hip_atomic_fetch_add(&s_hist[(x >> shift) & 255u], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                    __syncthreads();
+                }
+                // the bin that holds rank k among the values that share the prefix: the first wave, four bins a lane
+                if (tid < 64u) {
+                    uint32_t c[4], sum = 0;
+#pragma unroll
+                    for (int d = 0; d < 4; ++d) { c[d] = hist[tid * 4u + (uint32_t)d]; sum += c[d]; }
+                    uint32_t incl = sum;
+#pragma unroll
+                    for (int d = 1; d < 64; d <<= 1) {
+                        const uint32_t u = __shfl_up(incl, d, 64);
+                        if (tid >= (uint32_t)d) incl += u;
+                    }
+                    const uint32_t excl = incl - sum;
+                    if (excl <= k && k < incl) {
+                        uint32_t r = k - excl, d = 0;
+#pragma unroll
+                        for (uint32_t t = 0; t < 3u; ++t) if (d == t && r >= c[t]) { r -= c[t]; d = t + 1u; }   // (r < sum: d ends on a bin that holds it)
+                        s_pick[0] = tid * 4u + d; s_pick[1] = r;
+                    }
+                }
+                __syncthreads();
+                prefix |= s_pick[0] << shift; k = s_pick[1];
+                __syncthreads();                                            // (before the next pass overwrites s_pick and s_hist)
+            }
+            if (tid == 0) s_result[j] = prefix;
+        }
+        __syncthreads();
+        if (tid < a.num_q) a.planes[(size_t)tid * a.cells + cell] = (int32_t)(s_result[tid] ^ 0x80000000u);
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Ground filter (pcr_ground_filter): a progressive morphological filter over an int32 height plane, then a hole fill. The planes
 // in global memory are int32 with INT32_MIN for "empty"; no legal height has that value, and a minimum or maximum over non-empty
 // heights never produces it. Inside a kernel an empty cell is never compared as a height: k_ground_morph widens every cell to

@@ -61,6 +61,16 @@ constexpr unsigned long long voxel_mean_round(unsigned long long s, unsigned lon
     return (2ull * s + n) / (2ull * n);
 }
 
+// The rank pcr_grid_quantiles takes from a cell of n >= 1 candidates sorted ascending for q basis points (q <= 10000 =
+// PCR_QUANTILE_ONE): the nearest rank q * (n - 1) / 10000, a half rounded up, in unsigned 64-bit integers. n < 2^32, so the
+// product stays below 2^46. q = 0 gives 0, q = 10000 gives n - 1, and the rank never leaves [0, n - 1]. constexpr, so that the
+// kernels can call it as well.
+constexpr unsigned long long QUANTILE_ONE = 10000ull;
+constexpr unsigned long long quantile_rank(unsigned long long q, unsigned long long n)
+{
+    return (q * (n - 1ull) + QUANTILE_ONE / 2ull) / QUANTILE_ONE;
+}
+
 // The lattice of a denoising call: thin_lattice shifted by one whole cell more, origin'' = origin + (floor((q.min - origin) /
 // cell) - 1) * cell, so that q.min lies in voxel 1 on every axis. For a point p inside q, d = p - origin'' is in [cell, q.max -
 // q.min + 2 * cell) -- at most 2^32 - 1 for an extent below 2^31 and a cell of at most 2^30, so it still fits 32 unsigned bits --

@@ -555,6 +555,23 @@ struct HuffmanLasData : Resource {
         return st;
     }
 
+    // Exact percentiles of z per cell of `grid` over every batch the context holds right now (pcr_read_grid_quantiles): q in basis
+    // points (1 .. PCR_QUANTILES_MAX of them), planes[j * cells + cell] the z of the nearest rank, INT32_MIN for a cell without
+    // candidates; floor (the grid's cells, or NULL) admits only z >= floor[cell]; clip and count may be NULL. Not in the reference.
+    pcr_quantile_stats heightQuantiles(const pcr_grid &grid, const pcr_box *clip, const std::vector<int32_t> *floor, const std::vector<uint32_t> &q,
+                                       std::vector<int32_t> &planes, std::vector<uint32_t> *count)
+    {
+        if (!loadedOn) throw std::runtime_error("heightQuantiles: the resource is not loaded");
+        const size_t cells = (size_t)std::max(grid.width, 0) * (size_t)std::max(grid.height, 0);
+        if (floor && floor->size() != cells) throw std::runtime_error("heightQuantiles: the floor plane has not the grid's cells");
+        planes.resize(cells * q.size());
+        if (count) count->resize(cells);
+        pcr_quantile_stats st{};
+        loadedOn->check(pcr_read_grid_quantiles(loadedOn->ctx, 0, pcr_batches_resident(loadedOn->ctx), &grid, clip, floor ? floor->data() : nullptr, q.data(),
+                                                (int32_t)q.size(), planes.data(), count ? count->data() : nullptr, 0, &st), "pcr_read_grid_quantiles");
+        return st;
+    }
+
     // The lowest-point plane of `grid` over every batch the context holds right now, its ground plane (the progressive morphological
     // filter and hole fill of pcr_ground_filter) and the classes of its cells, on the GPU in one call (pcr_read_ground); clip may be
     // NULL, a vector NULL leaves its plane out. Not in the reference.

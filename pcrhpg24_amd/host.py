@@ -28,7 +28,7 @@ from typing import Iterator, Optional
 import numpy as np
 
 from . import _native as N
-from ._native import Box, DisplayOpts, EncodeStats, Grid, GridStats, GroundStats, HeightStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, ComponentsStats, DenoiseStats, NeighborsStats, ThinStats, Voxels, XyzBatch, c_i64, fb_elems
+from ._native import Box, DisplayOpts, EncodeStats, Grid, GridStats, QuantileStats, GroundStats, HeightStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, ComponentsStats, DenoiseStats, NeighborsStats, ThinStats, Voxels, XyzBatch, c_i64, fb_elems
 
 POINTS_PER_BATCH = 65536
 ENCODED_PAD_WORDS = 1024
@@ -407,6 +407,23 @@ def ground_params_from_world(las: LasInfo, cell_size: float, slope: float = 1.0,
         thresholds.append(min(INT32_MAX, max(0, int(round(dh / sz)))))
         prev = w
     return GroundParams(radii, thresholds, fill_rounds)
+
+
+def quantile_rank(q, n):
+    """The rank Context.grid_quantiles takes from a cell of n >= 1 candidates sorted ascending for q basis points (q <=
+    QUANTILE_ONE): (q * (n - 1) + QUANTILE_ONE // 2) // QUANTILE_ONE in unsigned 64-bit integers -- the nearest rank, a half
+    rounded up. q and n broadcast; numpy uint64."""
+    q, n = np.asarray(q, np.uint64), np.asarray(n, np.uint64)
+    one = np.uint64(N.QUANTILE_ONE)
+    return (q * (n - np.uint64(1)) + one // np.uint64(2)) // one
+
+
+def as_quantiles(q) -> np.ndarray:
+    """q (basis points, 0 .. QUANTILE_ONE, at most QUANTILES_MAX of them) as the uint32 array the C ABI takes."""
+    a = np.atleast_1d(np.asarray(q))
+    if a.ndim != 1 or a.dtype.kind not in "iu" or (a.size and (int(a.min()) < 0 or int(a.max()) >= 1 << 32)):
+        raise ValueError("q is a sequence of integers in basis points (0 .. 10000)")
+    return np.ascontiguousarray(a, np.uint32)
 
 
 def as_voxels(vox) -> Voxels:
@@ -1018,6 +1035,53 @@ class Context:
                                          top.ctypes.data, bottom.ctypes.data, cnt.ctypes.data, flags, C.byref(st)), "pcr_read_grid")
         self.grid_stats = st.as_dict()
         return top, bottom, cnt
+
+    # -- height percentiles per grid cell (pcr_grid_quantiles / pcr_read_grid_quantiles) ----------------------
+    def grid_quantiles(self, grid, q, clip=None, floor=None, first: int = 0, count: Optional[int] = None, flags: int = 0, counts: bool = False):
+        """Exact percentiles of z per cell of `grid` (as_grid) over batches [first, first + count) inside `clip` (as_box; None:
+        everywhere): a torch.int32 tensor [len(q), height, width], plane j the z of rank quantile_rank(q[j], n) among the cell's
+        n candidates sorted ascending, INT32_MIN for a cell without one. q: basis points (9500 = the 95th percentile), 1 ..
+        QUANTILES_MAX of them, any order, repeats allowed. floor: a torch.int32 tensor of the grid's cells, only records with
+        z >= floor[cell] are candidates (None: all). counts=True: (planes, counts) with the candidates per cell as a torch.int32
+        tensor [height, width] (the bits of the uint32). The statistics are in self.quantile_stats. Synchronises."""
+        import torch
+        grid = as_grid(grid)
+        qa = as_quantiles(q)
+        cells = grid.width * grid.height
+        dev = torch.device("cuda", self.device)
+        shape = (max(grid.height, 0), max(grid.width, 0))
+        planes = torch.empty((len(qa),) + shape, dtype=torch.int32, device=dev)
+        cnt = torch.empty(shape, dtype=torch.int32, device=dev) if counts else None
+        clip = None if clip is None else as_box(clip)
+        st = QuantileStats()
+        torch.cuda.current_stream(dev).synchronize()
+        self._chk(self.lib.pcr_grid_quantiles(self.h, first, -1 if count is None else count, C.byref(grid), None if clip is None else C.byref(clip),
+                                              None if floor is None else self._int32_plane(floor, cells, "floor"),
+                                              qa.ctypes.data_as(C.POINTER(N.c_u32)), len(qa), C.c_void_p(planes.data_ptr()),
+                                              None if cnt is None else C.c_void_p(cnt.data_ptr()), flags, C.byref(st)), "pcr_grid_quantiles")
+        self.quantile_stats = st.as_dict()
+        return (planes, cnt) if counts else planes
+
+    def read_grid_quantiles(self, grid, q, clip=None, floor=None, first: int = 0, count: Optional[int] = None, flags: int = 0, counts: bool = False):
+        """The same on the host, without torch (pcr_read_grid_quantiles; synchronises): numpy int32 [len(q), height, width], with
+        counts=True also the candidates per cell as uint32 [height, width]. floor: a numpy int32 array of the grid's cells or None."""
+        grid = as_grid(grid)
+        qa = as_quantiles(q)
+        shape = (max(grid.height, 0), max(grid.width, 0))
+        planes = np.empty((len(qa),) + shape, np.int32)
+        cnt = np.empty(shape, np.uint32) if counts else None
+        if floor is not None:
+            floor = np.ascontiguousarray(floor, np.int32)
+            if floor.size != shape[0] * shape[1]:
+                raise ValueError(f"floor must have the {shape[0]} x {shape[1]} cells of the grid")
+        clip = None if clip is None else as_box(clip)
+        st = QuantileStats()
+        self._chk(self.lib.pcr_read_grid_quantiles(self.h, first, -1 if count is None else count, C.byref(grid), None if clip is None else C.byref(clip),
+                                                   None if floor is None else floor.ctypes.data, qa.ctypes.data_as(C.POINTER(N.c_u32)), len(qa),
+                                                   planes.ctypes.data, None if cnt is None else cnt.ctypes.data, flags, C.byref(st)),
+                  "pcr_read_grid_quantiles")
+        self.quantile_stats = st.as_dict()
+        return (planes, cnt) if counts else planes
 
     # -- ground model and heights (pcr_ground_filter / pcr_read_ground / pcr_select_height / pcr_read_height) ----------
     def _int32_plane(self, t, cells: int, what: str, dtype=None):
@@ -1887,6 +1951,49 @@ class HuffmanLasData(Resource):
         height = z.to(torch.float64) * float(info.scale[2]) + float(info.offset[2])
         height[rgba == 0] = float("nan")
         return height, rgba.view(torch.uint8).view(grid.height, grid.width, 4), count, grid
+
+    def height_percentiles(self, renderer: Renderer, cell_size: float, percentiles, lo_xy=None, hi_xy=None, clip_z=None, ground=None,
+                           cutoff: float = 0.0):
+        """Exact height percentiles per cell of the loaded resource, in one call over the compressed stream (Context.
+        grid_quantiles): (heights, counts, grid) over the cells of grid_from_world(las_info(), lo_xy, hi_xy, cell_size).
+        percentiles: floats in 0 .. 100, each a whole number of basis points (95, 99.5, 2.25; not 33.333). heights is a float64
+        tensor [len(percentiles), h, w] in world units, the z of the nearest-rank point (no interpolation), NaN for a cell without
+        candidates; counts an int32 tensor [h, w] of candidates per cell. Row 0 is the southern edge. clip_z: (lo, hi) in world
+        units. ground: the int32 plane of the same grid that ground_model's filter gives (_ground_planes / Context.
+        ground_filter); then only points at least `cutoff` world units above their cell's ground are candidates (counts / all
+        points = canopy cover), the heights are above ground, and cells without ground come back NaN with count 0."""
+        import torch
+        bp = []
+        for p in np.atleast_1d(np.asarray(percentiles, np.float64)):
+            v = round(float(p) * 100.0)
+            if not 0.0 <= p <= 100.0 or abs(float(p) * 100.0 - v) > 1e-6:
+                raise ValueError(f"percentile {p}: a value in 0 .. 100 that is a whole number of basis points (hundredths)")
+            bp.append(int(v))
+        info = self.las_info()
+        lo_xy = (info.min[0], info.min[1]) if lo_xy is None else lo_xy
+        hi_xy = (info.max[0], info.max[1]) if hi_xy is None else hi_xy
+        grid = grid_from_world(info, lo_xy, hi_xy, cell_size)
+        inf = float("inf")
+        clip = None if clip_z is None else box_from_world(info, (-inf, -inf, clip_z[0]), (inf, inf, clip_z[1]))
+        ctx = renderer.ctx
+        floor = base = None
+        if ground is not None:
+            if tuple(ground.shape) != (grid.height, grid.width) or ground.dtype != torch.int32:
+                raise ValueError(f"ground must be an int32 tensor of the grid's {grid.height} x {grid.width} cells")
+            none = ground == INT32_MIN
+            lift = int(np.ceil(cutoff / float(info.scale[2]) - 1e-9))
+            floor = torch.clamp(ground.to(torch.int64) + lift, INT32_MIN + 1, INT32_MAX).to(torch.int32)
+            base = ground.to(torch.float64)
+        planes, counts = ctx.grid_quantiles(grid, bp, clip=clip, floor=None if floor is None else floor.contiguous(), counts=True)
+        empty = planes == INT32_MIN
+        if ground is None:
+            heights = planes.to(torch.float64) * float(info.scale[2]) + float(info.offset[2])
+        else:
+            heights = (planes.to(torch.float64) - base) * float(info.scale[2])
+            empty = empty | none
+            counts = torch.where(none, torch.zeros_like(counts), counts)
+        heights[empty] = float("nan")
+        return heights, counts, grid
 
     def _ground_planes(self, renderer: Renderer, cell_size: float, lo_xy, hi_xy, pmf: dict):
         """(grid, ground, classes): the ground filter over the lowest-point grid of the resource, int32 / uint8 tensors."""
