@@ -209,10 +209,10 @@ def decode_bc7(index: int, colors: np.ndarray) -> int:
 def decode_chain(words, separate, dt_values, dt_cwlen, n: int) -> np.ndarray:
     words = np.ascontiguousarray(words, np.uint32)
     separate = np.ascontiguousarray(np.concatenate([np.asarray(separate, np.int32), np.zeros(1, np.int32)]), np.int32)
+    dt_values, dt_cwlen = np.ascontiguousarray(dt_values, np.int32), np.ascontiguousarray(dt_cwlen, np.int32)   # alive over the call
     out = np.zeros(n, np.int32)
-    lib().pcr_oracle_decode_chain(words.ctypes.data, len(words), separate.ctypes.data,
-                                  np.ascontiguousarray(dt_values, np.int32).ctypes.data,
-                                  np.ascontiguousarray(dt_cwlen, np.int32).ctypes.data, n, out.ctypes.data)
+    lib().pcr_oracle_decode_chain(words.ctypes.data, len(words), separate.ctypes.data, dt_values.ctypes.data, dt_cwlen.ctypes.data, n,
+                                  out.ctypes.data)
     return out
 
 

@@ -56,11 +56,16 @@ def test_reference_library_reproduces_the_committed_blocks():
         pytest.skip("oracle/_ref not built (the reference checkout is absent)")
     d = np.load(os.path.join(G, "bc7_ref_blocks.npz"))
     ref = refpin.ref_lib()
-    for k in range(0, len(d["colors"]), 7):
+    # the arrays are read once and held: d["colors"] reads the file anew at every access, and a temporary's `.ctypes.data` is the
+    # address of memory that is freed before the call is made
+    colors, blocks, unpacked = (np.ascontiguousarray(d[n]) for n in ("colors", "blocks", "unpacked"))
+    assert colors.dtype == np.uint32 and colors.shape[1] == 16
+    for k in range(0, len(colors), 7):
         enc = np.zeros(16, np.uint8); unp = np.zeros(16, np.uint32)
-        ref.ref_bc7_encode(np.ascontiguousarray(d["colors"][k]).ctypes.data, enc.ctypes.data)
+        row = colors[k]
+        ref.ref_bc7_encode(row.ctypes.data, enc.ctypes.data)
         assert ref.ref_bc7_unpack(enc.ctypes.data, unp.ctypes.data) == 1
-        assert np.array_equal(enc, d["blocks"][k]) and np.array_equal(unp, d["unpacked"][k])
+        assert np.array_equal(enc, blocks[k]) and np.array_equal(unp, unpacked[k])
 
 
 def psnr(a: np.ndarray, b: np.ndarray) -> float:
