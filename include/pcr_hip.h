@@ -292,6 +292,39 @@ int pcr_read_screen(pcr_ctx *ctx, const pcr_render_params *params, const pcr_rec
 int pcr_pick(pcr_ctx *ctx, const pcr_render_params *params, int px, int py, int radius, pcr_point *out_point,
              pcr_screen_hit *out_hit, int *out_found);
 
+/* ---- visible selection: the points that make up the picture, occlusion-aware (no reference counterpart) -------------------------
+ * CONTRACT of pcr_select_visible, in terms of pcr_select_screen's hits (same kept batches, level of detail, precision, inside
+ * test, pixel and depth_bits). A pixel is a linear index p < width * height, column p % width, row p / width; hits of the
+ * framebuffer's extra row (pixel >= width * height) are never selected and never occlude.
+ *   D[p]   the least depth_bits over ALL hits of pixel p in the whole image, whatever the rect; 0xFFFFFFFF without a hit
+ *          (w > 0, so the order of the bits is the order of w)
+ *   Dr[p]  the least D over the pixels whose column and row both lie within `radius` of p's, inside the image;
+ *          radius 0 .. PCR_VISIBLE_MAX_RADIUS, and radius 0 gives Dr = D. A radius above 0 makes this hidden-point removal
+ *          for a cloud with gaps: the background seen through a hole between foreground points is occluded by their depths.
+ *   surface test  a hit passes iff (double)w <= (double)dr * 1.01, w and dr the floats of depth_bits and Dr[pixel]: the HQS
+ *          colour pass's rule, an f64 product
+ *   PCR_VISIBLE_SURFACE  every hit in the rect that passes the surface test. At radius 0 these are the points whose colours
+ *          pcr_render_hqs_color averages (where both LOD expressions agree).
+ *   PCR_VISIBLE_FRONT    of every pixel in the rect the one hit that is least by (depth_bits, colour, index) -- pcr_pick's
+ *          order, colour the record's 0x00BBGGRR -- if it passes the surface test (at radius 0 it always does). For a BC1
+ *          stream and radius 0 these are the points whose words pcr_render_basic leaves in the framebuffer.
+ * dev_points / dev_hits get the pcr_point and pcr_screen_hit records of the selected hits, in increasing index order, packed;
+ * dev_depth gets uint32[width * height], the plane Dr of the whole image whatever the rect. Any pointer may be NULL; all three
+ * NULL only counts. A capacity below the result with dev_points or dev_hits given: PCR_E_ARG, *out_count = the count needed,
+ * nothing written (the depth plane neither). stats may be NULL.
+ * An empty rect or no resident batch: 0 records, PCR_OK (the depth plane and the image's counts are still worked out).
+ * Synchronises. Touches no framebuffer, no render statistics and no pending pcr_frame_begin state. The per-pixel planes (24
+ * bytes a pixel) are scratch of the context, grown on demand.
+ * PCR_E_ARG with a message: what pcr_select_screen refuses, an unknown mode, a radius outside the range, a misaligned dev_depth
+ * (4 bytes).
+ * pcr_read_visible: the same into host memory. */
+int pcr_select_visible(pcr_ctx *ctx, const pcr_render_params *params, const pcr_rect *rect, int mode, int radius,
+                       void *dev_points, void *dev_hits, void *dev_depth, size_t capacity, int64_t *out_count,
+                       pcr_visible_stats *stats);
+int pcr_read_visible(pcr_ctx *ctx, const pcr_render_params *params, const pcr_rect *rect, int mode, int radius,
+                     pcr_point *host_points, pcr_screen_hit *host_hits, uint32_t *host_depth, size_t capacity,
+                     int64_t *out_count, pcr_visible_stats *stats);
+
 /* ---- top-down grid: the stream rasterized into height / colour / density planes (no reference counterpart) ------------------
  * CONTRACT: after pcr_grid_clear and pcr_grid_accumulate over a range, every cell of a plane holds the max / min / count
  * (pcr_grid in pcr_types.h) over exactly the records pcr_decode_points writes for that range that fall into the cell and into

@@ -386,6 +386,22 @@ typedef struct pcr_screen_stats {
     int64_t points_selected;
 } pcr_screen_stats;
 
+/* pcr_select_visible: which of a frame's hits are selected, and how far a pixel's front depth occludes its neighbours. */
+#define PCR_VISIBLE_FRONT       0   /* of every pixel the one hit that is least by (depth_bits, colour, index) */
+#define PCR_VISIBLE_SURFACE     1   /* every hit within 1 % of its pixel's (dilated) front depth */
+#define PCR_VISIBLE_MAX_RADIUS  8   /* the occluder window is (2 * radius + 1)^2 pixels */
+
+/* What a visible selection did (pcr_select_visible / pcr_read_visible): batches as pcr_screen_stats; the hits of the whole image
+ * (pixel < width * height) and the pixels that hold at least one; the hits in the rect; the records selected (*out_count). */
+typedef struct pcr_visible_stats {
+    int64_t batches_skipped;
+    int64_t batches_decoded;
+    int64_t hits;
+    int64_t pixels_covered;
+    int64_t candidates;
+    int64_t selected;
+} pcr_visible_stats;
+
 /* How a display resolve (pcr_resolve_*_display) turns the framebuffer into the image: the point size and eye-dome lighting of
  * the reference's GLSL 10-10-10 resolve (modules/compute_loop_las/resolve.cs:98-128 `window`, :41-62 and :143-185 `edlWindow`). */
 #define PCR_DISPLAY_MAX_WINDOW      4   /* point size 2*4+1 = 9 pixels */

@@ -204,6 +204,16 @@ class ScreenStats(C.Structure):                   # pcr_screen_stats
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+VISIBLE_FRONT, VISIBLE_SURFACE, VISIBLE_MAX_RADIUS = 0, 1, 8                                            # pcr_types.h
+
+
+class VisibleStats(C.Structure):                  # pcr_visible_stats
+    _fields_ = [(n, c_i64) for n in ("batches_skipped", "batches_decoded", "hits", "pixels_covered", "candidates", "selected")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class DisplayOpts(C.Structure):                   # pcr_display_opts: point size and eye-dome lighting of a display resolve, 16 bytes
     _fields_ = [("window", c_i32), ("edl_window", c_i32), ("edl_strength", c_f32), ("reserved", c_i32)]
 
@@ -218,7 +228,7 @@ class EncodeStats(C.Structure):                   # pcr_encode_stats
 
 assert C.sizeof(Point) == 16 and C.sizeof(Box) == 24 and C.sizeof(SelectStats) == 32
 assert C.sizeof(Polygon) == 40 and C.sizeof(PolygonStats) == 48
-assert C.sizeof(Rect) == 16 and C.sizeof(ScreenHit) == 16 and C.sizeof(ScreenStats) == 32
+assert C.sizeof(Rect) == 16 and C.sizeof(ScreenHit) == 16 and C.sizeof(ScreenStats) == 32 and C.sizeof(VisibleStats) == 48
 assert C.sizeof(DisplayOpts) == 16
 assert C.sizeof(Grid) == 24 and C.sizeof(GridStats) == 24 and C.sizeof(QuantileStats) == 48
 assert C.sizeof(GroundParams) == 136 and C.sizeof(GroundStats) == 48 and C.sizeof(HeightStats) == 32
@@ -247,6 +257,7 @@ HIP_SYMBOLS = [
     "pcr_batch_point_bounds", "pcr_select_box", "pcr_read_box",
     "pcr_select_polygon", "pcr_read_polygon",
     "pcr_select_screen", "pcr_read_screen", "pcr_pick",
+    "pcr_select_visible", "pcr_read_visible",
     "pcr_resolve_basic_display", "pcr_resolve_hqs_display", "pcr_resolve_las_display",
     "pcr_grid_clear", "pcr_grid_accumulate", "pcr_grid_unpack", "pcr_read_grid",
     "pcr_grid_quantiles", "pcr_read_grid_quantiles",
@@ -375,6 +386,9 @@ def hip_lib() -> C.CDLL:
             getattr(lib, n).argtypes = [C.c_void_p, C.POINTER(RenderParams), C.POINTER(Rect), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(c_i64),
                                         C.POINTER(ScreenStats)]
         lib.pcr_pick.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_int, C.c_int, C.c_int, C.POINTER(Point), C.POINTER(ScreenHit), C.POINTER(C.c_int)]
+        for n in ("pcr_select_visible", "pcr_read_visible"):
+            getattr(lib, n).argtypes = [C.c_void_p, C.POINTER(RenderParams), C.POINTER(Rect), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.POINTER(c_i64), C.POINTER(VisibleStats)]
         for n in ("pcr_resolve_basic_display", "pcr_resolve_hqs_display", "pcr_resolve_las_display"):
             getattr(lib, n).argtypes = [C.c_void_p, C.POINTER(RenderParams), C.POINTER(DisplayOpts)]
         lib.pcr_grid_clear.argtypes = [C.c_void_p, C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p]

@@ -150,6 +150,15 @@ struct pcr_ctx {
     uint32_t *d_scr_totals = nullptr;           // [scr_capacity] ... and per batch
     int64_t *d_scr_offsets = nullptr;           // [scr_capacity] first output record of each (k_screen_write)
     unsigned long long *d_pick = nullptr;       // [PICK_WORDS] pcr_pick: key, index, record, hit
+    // visible selection (pcr_select_visible): the per-pixel planes of the image and the per-batch totals; list, per-chain counts
+    // and offsets are the screen selection's arrays above
+    size_t vis_pixels = 0;                      // pixels the four planes below hold each
+    unsigned long long *d_vis_key = nullptr;    // [vis_pixels + 1] min of depth << 32 | colour per pixel (k_visible_key); then the covered-pixel counter
+    unsigned long long *d_vis_index = nullptr;  // [vis_pixels] FRONT: min record index among the hits that hold the key (k_visible_index)
+    uint32_t *d_vis_row = nullptr;              // [vis_pixels] the row pass of k_visible_dilate
+    uint32_t *d_vis_depth = nullptr;            // [vis_pixels] the dilated depth plane Dr
+    int64_t vis_capacity = 0;                   // kept batches d_vis_totals holds
+    uint32_t *d_vis_totals = nullptr;           // [vis_capacity * 3] per batch: hits in the image, then (selected, candidates) pairs
     // top-down grid (pcr_grid_accumulate / pcr_read_grid): the list of a call's batches with their windows, and pcr_read_grid's planes
     int64_t grid_capacity = 0;                  // entries d_grid_list holds
     GridEntry *d_grid_list = nullptr;           // [grid_capacity] the windowed batches of a call, then the direct ones
@@ -322,6 +331,7 @@ void free_stream_buffers(pcr_ctx *c)
     dfree(c->d_poly_batches); c->poly_capacity = 0; dfree(c->d_poly_edges); c->poly_edge_capacity = 0;
     dfree(c->d_screen_lod); dfree(c->d_scr_list); dfree(c->d_scr_counts); dfree(c->d_scr_totals); dfree(c->d_scr_offsets); c->scr_capacity = 0;
     dfree(c->d_pick);
+    dfree(c->d_vis_key); dfree(c->d_vis_index); dfree(c->d_vis_row); dfree(c->d_vis_depth); dfree(c->d_vis_totals); c->vis_pixels = 0; c->vis_capacity = 0;
     dfree(c->d_grid_list); c->grid_capacity = 0; c->h_grid_list.clear();
     dfree(c->d_thin_list); dfree(c->d_thin_totals); dfree(c->d_thin_wlist); dfree(c->d_thin_offsets); c->thin_capacity = 0;
     dfree(c->d_thin_table); c->thin_slots = 0; dfree(c->d_thin_keep); c->thin_keep_words = 0; dfree(c->d_thin_error);
@@ -4092,6 +4102,195 @@ int pcr_pick(pcr_ctx *c, const pcr_render_params *p, int px, int py, int radius,
     *out_found = 1;
     if (out_point) std::memcpy(out_point, &h[2], sizeof *out_point);
     if (out_hit) std::memcpy(out_hit, &h[4], sizeof *out_hit);
+    return PCR_OK;
+}
+
+// ---- visible selection ---------------------------------------------------------------------------
+namespace {
+// What pcr_select_visible / pcr_read_visible share: the screen selection's plan (kept batches, ScreenArgs; pl.cnt = the selected
+// hits per kept batch) and the call's mode. The depth plane of the call is in c->d_vis_depth.
+struct VisiblePlan {
+    ScreenPlan pl;
+    bool front = true;
+    pcr_visible_stats st{};
+};
+
+// The planes for an image of npix pixels, and the totals of nK kept batches
+int visible_scratch(pcr_ctx *c, size_t npix, int64_t nK)
+{
+    if (c->vis_pixels < npix) {
+        dfree(c->d_vis_key); dfree(c->d_vis_index); dfree(c->d_vis_row); dfree(c->d_vis_depth); c->vis_pixels = 0;
+        if (hipMalloc((void **)&c->d_vis_key, (npix + 1) * 8) != hipSuccess || hipMalloc((void **)&c->d_vis_index, npix * 8) != hipSuccess ||
+            hipMalloc((void **)&c->d_vis_row, npix * 4) != hipSuccess || hipMalloc((void **)&c->d_vis_depth, npix * 4) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for the planes of %zu pixels", npix);
+        c->vis_pixels = npix;
+    }
+    if (c->vis_capacity < nK) {
+        dfree(c->d_vis_totals); c->vis_capacity = 0;
+        if (hipMalloc((void **)&c->d_vis_totals, (size_t)nK * 3 * 4) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for the totals of %lld batches", (long long)nK);
+        c->vis_capacity = nK;
+    }
+    return PCR_OK;
+}
+
+// The checks, the planes and the counts. *done: nothing left to write (an error, a count-only call, no records). The depth
+// plane goes to `depth` (device or host memory) unless the call is refused.
+int visible_prepare(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect, int mode, int radius, const void *points, const void *hits, void *depth,
+                    size_t align_points, size_t align_hits, size_t capacity, int64_t *out_count, pcr_visible_stats *stats, VisiblePlan &vp, bool *done)
+{
+    *done = true;
+    if (out_count) *out_count = 0;
+    int rc = check_params(c, p);
+    if (rc) return rc;
+    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
+    if (mode != PCR_VISIBLE_FRONT && mode != PCR_VISIBLE_SURFACE) return set_err(c, PCR_E_ARG, "unknown mode %d (PCR_VISIBLE_FRONT or PCR_VISIBLE_SURFACE)", mode);
+    if (radius < 0 || radius > PCR_VISIBLE_MAX_RADIUS) return set_err(c, PCR_E_ARG, "radius must be 0 .. %d", PCR_VISIBLE_MAX_RADIUS);
+    if (points && reinterpret_cast<uintptr_t>(points) % align_points != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", align_points);
+    if (hits && reinterpret_cast<uintptr_t>(hits) % align_hits != 0) return set_err(c, PCR_E_ARG, "the destination of the hits is misaligned (%zu bytes)", align_hits);
+    if (depth && reinterpret_cast<uintptr_t>(depth) % alignof(uint32_t) != 0) return set_err(c, PCR_E_ARG, "the destination of the depth plane is misaligned (4 bytes)");
+    if (c->async_upload) poll_loader(c, false);
+    ScreenPlan &pl = vp.pl;
+    const int64_t nB = c->visible_batches();
+    const size_t npix = (size_t)p->width * (size_t)p->height;
+    vp.front = mode == PCR_VISIBLE_FRONT;
+    vp.st = pcr_visible_stats{nB, 0, 0, 0, 0, 0};
+    const bool some = rect ? screen_clip(p, rect->x0, rect->y0, rect->x1, rect->y1, pl.q) : screen_clip(p, 0, 0, p->width - 1, p->height - 1, pl.q);
+    if (nB > 0 && (rc = screen_list(c, p, nB, pl))) return rc;
+    const int64_t nK = (int64_t)pl.kept.size();
+    vp.st.batches_decoded = nK; vp.st.batches_skipped = nB - nK;
+    pl.cnt.assign((size_t)nK, 0);
+    if ((rc = visible_scratch(c, npix, nK))) return rc;
+    // the planes: empty, then the keys of every hit of the image, then the dilated depth
+    unsigned long long *const d_covered = c->d_vis_key + npix;
+    HIP_TRY(c, hipMemsetAsync(c->d_vis_key, 0xFF, npix * 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d_covered, 0, 8, c->stream));
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)nK), block(PCR_WORKGROUP_SIZE);
+    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7, windows = select_reads_windows(c);
+    uint32_t *const d_hit_totals = c->d_vis_totals, *const d_totals = c->d_vis_totals + nK;
+    if (nK > 0) {
+        // (SURFACE reads the keys' depth halves only: the colourless decode)
+#define PCR_LAUNCH(L, C) hipLaunchKernelGGL((k_visible_key<L, C>), grid, block, 0, c->stream, s, c->d_scr_list, pl.q, c->d_vis_key, d_hit_totals)
+#define PCR_LAUNCH_COLOUR(L) do { if (!vp.front) PCR_LAUNCH(L, SEL_NO_COLOUR); else if (bc7) PCR_LAUNCH(L, SEL_BC7); else PCR_LAUNCH(L, SEL_BC1); } while (0)
+        if (windows) PCR_LAUNCH_COLOUR(LAYOUT_POINT_WINDOWS); else PCR_LAUNCH_COLOUR(LAYOUT_WORDS);
+#undef PCR_LAUNCH_COLOUR
+#undef PCR_LAUNCH
+        HIP_TRY(c, hipGetLastError());
+    }
+    const dim3 dgrid((unsigned)std::min<size_t>((npix + VIS_DILATE_THREADS - 1) / VIS_DILATE_THREADS, 4096)), dblock(VIS_DILATE_THREADS);
+    hipLaunchKernelGGL((k_visible_dilate<true>), dgrid, dblock, 0, c->stream, c->d_vis_key, (const uint32_t *)nullptr, c->d_vis_row, p->width, p->height, radius, d_covered);
+    hipLaunchKernelGGL((k_visible_dilate<false>), dgrid, dblock, 0, c->stream, c->d_vis_key, c->d_vis_row, c->d_vis_depth, p->width, p->height, radius, d_covered);
+    HIP_TRY(c, hipGetLastError());
+    const bool count = some && nK > 0;
+    if (count) {
+        if (vp.front) {
+            HIP_TRY(c, hipMemsetAsync(c->d_vis_index, 0xFF, npix * 8, c->stream));
+#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_visible_index<L, B>), grid, block, 0, c->stream, s, c->d_scr_list, pl.q, c->d_vis_key, c->d_vis_index)
+            if (windows) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
+            else         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+#undef PCR_LAUNCH
+        }
+        if (windows) hipLaunchKernelGGL((k_visible_count<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_scr_list, pl.q, vp.front, c->d_vis_depth,
+                                        c->d_vis_index, c->d_scr_counts, d_totals);
+        else         hipLaunchKernelGGL((k_visible_count<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_scr_list, pl.q, vp.front, c->d_vis_depth,
+                                        c->d_vis_index, c->d_scr_counts, d_totals);
+        HIP_TRY(c, hipGetLastError());
+    }
+    std::vector<uint32_t> totals((size_t)nK * 3);
+    unsigned long long covered = 0;
+    if (nK > 0) HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_vis_totals, (size_t)nK * (count ? 3 : 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&covered, d_covered, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    vp.st.pixels_covered = (int64_t)covered;
+    for (int64_t k = 0; k < nK; ++k) {
+        vp.st.hits += totals[(size_t)k];
+        if (!count) continue;
+        pl.cnt[(size_t)k] = totals[(size_t)(nK + 2 * k)];
+        vp.st.selected += totals[(size_t)(nK + 2 * k)];
+        vp.st.candidates += totals[(size_t)(nK + 2 * k + 1)];
+    }
+    *out_count = vp.st.selected;
+    if (stats) *stats = vp.st;
+    if ((points || hits) && capacity < (size_t)vp.st.selected)
+        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld selected", capacity, (long long)vp.st.selected);
+    if (depth) {
+        HIP_TRY(c, hipMemcpyAsync(depth, c->d_vis_depth, npix * 4, hipMemcpyDefault, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    if ((!points && !hits) || vp.st.selected == 0) return PCR_OK;
+    *done = false;
+    return PCR_OK;
+}
+
+// screen_emit for the selected hits of kept batches [k0, k1). The caller synchronises.
+int visible_emit(pcr_ctx *c, VisiblePlan &vp, int64_t k0, int64_t k1, uint4 *points, uint4 *hits)
+{
+    ScreenPlan &pl = vp.pl;
+    pl.offsets.clear();
+    int64_t off = 0;
+    for (int64_t k = k0; k < k1; ++k) { pl.offsets.push_back(off); off += pl.cnt[(size_t)k]; }
+    if (off == 0) return PCR_OK;
+    HIP_TRY(c, hipMemcpyAsync(c->d_scr_offsets + k0, pl.offsets.data(), (size_t)(k1 - k0) * 8, hipMemcpyHostToDevice, c->stream));
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)(k1 - k0)), block(PCR_WORKGROUP_SIZE);
+    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
+#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_visible_write<L, B>), grid, block, 0, c->stream, s, c->d_scr_list + k0, pl.q, vp.front, c->d_vis_depth, \
+                                            c->d_vis_index, c->d_scr_counts + k0 * PCR_WORKGROUP_SIZE, c->d_scr_offsets + k0, points, hits)
+    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
+    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+#undef PCR_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    return PCR_OK;
+}
+} // namespace
+
+int pcr_select_visible(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect, int mode, int radius, void *dev_points, void *dev_hits, void *dev_depth,
+                       size_t capacity, int64_t *out_count, pcr_visible_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    VisiblePlan vp;
+    bool done = true;
+    int rc = visible_prepare(c, p, rect, mode, radius, dev_points, dev_hits, dev_depth, 16, 16, capacity, out_count, stats, vp, &done);
+    if (rc || done) return rc;
+    if ((rc = visible_emit(c, vp, 0, (int64_t)vp.pl.kept.size(), static_cast<uint4 *>(dev_points), static_cast<uint4 *>(dev_hits)))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+int pcr_read_visible(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect, int mode, int radius, pcr_point *host_points, pcr_screen_hit *host_hits,
+                     uint32_t *host_depth, size_t capacity, int64_t *out_count, pcr_visible_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    VisiblePlan vp;
+    bool done = true;
+    int rc = visible_prepare(c, p, rect, mode, radius, host_points, host_hits, host_depth, alignof(pcr_point), alignof(pcr_screen_hit), capacity, out_count,
+                             stats, vp, &done);
+    if (rc || done) return rc;
+    // pieces as pcr_read_screen's: a piece's points in the first half of the decode staging buffer, its hits in the second
+    const int64_t nK = (int64_t)vp.pl.kept.size();
+    const int64_t piece = std::min<int64_t>(nK, DECODE_STAGE_BATCHES / 2);
+    if (!c->d_decode_stage || c->decode_stage_batches < 2 * piece) {
+        dfree(c->d_decode_stage); c->decode_stage_batches = 0;
+        if (hipMalloc((void **)&c->d_decode_stage, (size_t)(2 * piece) * PCR_POINTS_PER_BATCH * sizeof(pcr_point)) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of points", (long long)(2 * piece));
+        c->decode_stage_batches = 2 * piece;
+    }
+    uint4 *const d_points = reinterpret_cast<uint4 *>(c->d_decode_stage), *const d_hits = d_points + (size_t)piece * PCR_POINTS_PER_BATCH;
+    int64_t written = 0;
+    for (int64_t k0 = 0; k0 < nK; k0 += piece) {
+        const int64_t k1 = std::min(nK, k0 + piece);
+        int64_t m = 0;
+        for (int64_t k = k0; k < k1; ++k) m += vp.pl.cnt[(size_t)k];
+        if (m == 0) continue;
+        if ((rc = visible_emit(c, vp, k0, k1, host_points ? d_points : nullptr, host_hits ? d_hits : nullptr))) return rc;
+        if (host_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
+        if (host_hits) HIP_TRY(c, hipMemcpyAsync(host_hits + written, d_hits, (size_t)m * sizeof(pcr_screen_hit), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        written += m;
+    }
     return PCR_OK;
 }
 

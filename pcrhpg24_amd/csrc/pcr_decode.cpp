@@ -9,6 +9,7 @@
 //     pcr_decode <in.huffman> <out.las> --sor K MULT R [--outliers] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]
 //     pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1] [--rect x0 y0 x1 y1]
+//                                                [--visible front|surface [--occluder R]]
 //     pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]
 //     pcr_decode <in.huffman> <out.asc> --percentile P CELL [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.asc> --dtm CELL [--slope S] [--max-window W] [--initial D] [--max-distance D] [--box x0 y0 z0 x1 y1 z1]
@@ -17,7 +18,7 @@
 // 64 batches and writes LAS 1.2 / point format 2 (pcr_write_las_points). With --box only the points inside a box of world
 // coordinates are read back (pcr_read_box: batches the box misses are not decoded). With --view only the points a frame of that
 // camera draws (pcr_render's camera arguments and defaults), and of those the ones inside --rect, a rectangle of pixels
-// (pcr_read_screen). With --ortho no points are read back at all: the stream is rasterized top-down on the GPU (pcr_read_grid) into
+// (pcr_read_screen); with --visible of those only the ones that make up the picture (pcr_read_visible). With --ortho no points are read back at all: the stream is rasterized top-down on the GPU (pcr_read_grid) into
 // an orthophoto and, with --dsm, a surface model. With --thin one point per cubic voxel is read back (pcr_read_thin): the cloud
 // decimated on the GPU without ever existing in full. With --polygon only the points inside a polygon prism of world coordinates are
 // read back (pcr_read_polygon). With --denoise the points come back without the isolated ones, or those alone (pcr_read_denoise).
@@ -54,7 +55,7 @@ static const char *USAGE =
     "       pcr_decode <in.huffman> <out.las> --sor K MULT R [--outliers] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]\n"
     "       pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1]\n"
-    "                                                [--rect x0 y0 x1 y1]\n"
+    "                                                [--rect x0 y0 x1 y1] [--visible front|surface [--occluder R]]\n"
     "       pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]\n"
     "       pcr_decode <in.huffman> <out.asc> --percentile P CELL [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.asc> --dtm CELL [--slope S] [--max-window W] [--initial D] [--max-distance D]\n"
@@ -107,6 +108,10 @@ static const char *USAGE =
     "  --view: only the points a frame of that camera draws (the basic method's cull and level of detail; the options and their\n"
     "  defaults are pcr_render's), in the stream's order; --rect: of those the ones whose pixel lies in the rectangle (pixels,\n"
     "  bounds inclusive, x0 <= x1 and y0 <= y1). A view that shows no point is an error.\n"
+    "  --visible: of those only the points that make up the picture, not what lies behind them. front: per pixel the one point\n"
+    "  the frame shows (the nearest; ties by colour, then by position in the stream); surface: every point within 1 % of its\n"
+    "  pixel's nearest depth. --occluder R (0 .. 8, default 0): a pixel's nearest depth is taken over the pixels within R columns\n"
+    "  and rows as well, so that a surface with gaps between its points still hides what is behind it.\n"
     "  --ortho CELL: no LAS file; the stream is rasterized top-down on the GPU into square cells of CELL world units (a whole\n"
     "  number of the stream's x and y lattice steps) and the colour of the highest point of every cell is written as a binary\n"
     "  PPM (empty cells black), rows from north to south. The cells cover the x and y range of --box, of which z0 and z1 clip the\n"
@@ -152,6 +157,8 @@ struct View {
     int cull = 1;
     bool has_rect = false;
     pcr_rect rect{};
+    int visible = -1;                           // PCR_VISIBLE_*, -1: --visible not given
+    int occluder = -1;                          // --occluder, -1: not given
 };
 
 // the options behind --view, every one well formed, or false
@@ -176,11 +183,18 @@ static bool parse_view(int argc, char **argv, int at, View &v)
             if (r[0] > r[2] || r[1] > r[3]) return false;
             v.rect = pcr_rect{r[0], r[1], r[2], r[3]};
             v.has_rect = true;
+        } else if (a == "--visible" && have(1) && v.visible < 0) {
+            const std::string m = argv[++i];
+            if (m == "front") v.visible = PCR_VISIBLE_FRONT;
+            else if (m == "surface") v.visible = PCR_VISIBLE_SURFACE;
+            else return false;
+        } else if (a == "--occluder" && have(1) && v.occluder < 0) {
+            if (!parse_int(argv[++i], 0, PCR_VISIBLE_MAX_RADIUS, v.occluder)) return false;
         } else {
             return false;
         }
     }
-    return true;
+    return v.occluder < 0 || v.visible >= 0;    // (--occluder belongs to --visible)
 }
 
 // six finite numbers behind --box, or false
@@ -842,9 +856,16 @@ int main(int argc, char **argv)
             for (int k = 0; k < 3; ++k) renderer.target[k] = view.cam[3 + k];
             Debug::LOD = (float)view.lod;
             Debug::frustumCullingEnabled = view.cull != 0;
-            const pcr_screen_stats st = las->selectScreen(renderer.params(), view.has_rect ? &view.rect : nullptr, &points, nullptr);
-            std::printf("view: batches skipped %lld, decoded %lld, points tested %lld\n", (long long)st.batches_skipped, (long long)st.batches_decoded,
-                        (long long)st.points_tested);
+            if (view.visible >= 0) {
+                const pcr_visible_stats st = las->selectVisible(renderer.params(), view.has_rect ? &view.rect : nullptr, view.visible, std::max(view.occluder, 0),
+                                                                &points, nullptr);
+                std::printf("view: batches skipped %lld, decoded %lld, hits %lld on %lld pixels, in the rect %lld, visible %lld\n", (long long)st.batches_skipped,
+                            (long long)st.batches_decoded, (long long)st.hits, (long long)st.pixels_covered, (long long)st.candidates, (long long)st.selected);
+            } else {
+                const pcr_screen_stats st = las->selectScreen(renderer.params(), view.has_rect ? &view.rect : nullptr, &points, nullptr);
+                std::printf("view: batches skipped %lld, decoded %lld, points tested %lld\n", (long long)st.batches_skipped, (long long)st.batches_decoded,
+                            (long long)st.points_tested);
+            }
             if (points.empty()) throw std::runtime_error("no points in the view: nothing written");
         } else {
             las->decodePoints(points);

@@ -16,6 +16,7 @@
 //                   MODE 3: the colour pass over BC7 mode-6 colours)
 //   k_decode_points on request: the same decode, every point of a range of batches written out as {x, y, z, colour} records
 //   k_screen_* / k_pick*  on request: the points a frame draws, selected by pixel (projection restated in screen_project)
+//   k_visible_*     on request: of those points the ones that make up the picture, by per-pixel planes of front depth and index
 //   k_grid*         on request: the stream rasterized top-down into max / min / count planes over its integer x and y
 //   k_polygon_*     on request: the records inside a polygon prism, each straddling batch against its own edge list in LDS
 //   k_thin_*        on request: one record per voxel of a cubic lattice, straight from the compressed stream
@@ -4680,6 +4681,197 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_pick_fetch(StreamView s,
             out[1] = make_uint4(pixel, depth, (uint32_t)winner, (uint32_t)(winner >> 32));
         }
     }, (int)(w & LOD_NPR_MASK));
+}
+
+// ------------------------------------------------------------------------------------------------
+// Visible selection (pcr_select_visible / pcr_read_visible): of pcr_select_screen's hits those that make up the picture. Per-pixel
+// planes over the image (width * height words each, scratch of the context) take the place of a sort of the hits by pixel:
+//   k_visible_key     per kept batch: 64-bit min of depth << 32 | colour of every hit into its pixel's word of the key plane
+//                     (every hit of the image, whatever the rect). A chain's consecutive hits of one pixel are merged in
+//                     registers, and the word is read before the atomic, which is skipped when it cannot lower the word.
+//   k_visible_dilate  rows, then columns: min of the keys' high halves over +-radius pixels, clipped to the image (the min over
+//                     a square window separates exactly) -- the depth plane Dr the surface test reads
+//   k_visible_index   FRONT only, per kept batch: min of the record index among the rect's hits that hold their pixel's key
+//   k_visible_count / k_visible_write   k_screen_count / k_screen_write with the extra predicate: the surface test
+//                     (double)w <= (double)dr * 1.01 (the HQS colour pass's rule), and for FRONT index == the pixel's index word
+// Hits of the framebuffer's extra row (pixel >= width * height, which screen_project admits) touch no plane and are in no rect.
+// No workgroup waits for another; every result is written with vector stores and vector atomics.
+// ------------------------------------------------------------------------------------------------
+constexpr uint64_t VIS_NONE = ~0ull;
+constexpr int VIS_DILATE_THREADS = 256;
+
+// *word = min(*word, v). The word only ever falls during a pass, so one read as <= v already makes the atomic a no-op: skipped.
+__device__ __forceinline__ void visible_min(unsigned long long *word, uint64_t v)
+{
+    if (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > v) atomicMin(word, (unsigned long long)v);
+}
+
+// The HQS colour pass's 1 % rule (k_render_color): an f64 product, not 1.01f. dr = 0xFFFFFFFF (no hit near) is a NaN: false.
+__device__ __forceinline__ bool visible_surface(uint32_t depth_bits, uint32_t dr_bits)
+{
+    return (double)__uint_as_float(depth_bits) <= (double)__uint_as_float(dr_bits) * 1.01;
+}
+
+// Workgroup x takes list[x]: the key of every hit into key_plane; hit_totals[x] = the batch's hits inside the image
+template <int LAYOUT, int COLOUR>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_visible_key(StreamView s, const ScreenEntry *list, ScreenArgs q, unsigned long long *key_plane,
+                                                                    uint32_t *hit_totals)
+{
+    const ScreenEntry e = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint32_t s_part[LWC_WAVES];
+    load_packed_table(s, e.b, s_table);
+    const ScreenBatch B = screen_batch(s, e.b, e.lod);
+    const uint32_t npix = (uint32_t)q.width * (uint32_t)q.height, no_pixel = ~0u;
+    uint32_t cnt = 0, run_pixel = no_pixel;                 // the run: the chain's latest hits, all of one pixel
+    uint64_t run_key = VIS_NONE;
+    decode_chain<LAYOUT, COLOUR>(s, e.b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        int ix, iy; uint32_t pixel, depth;
+        if (!screen_project(q, B, x, y, z, ix, iy, pixel, depth) || pixel >= npix) return;
+        ++cnt;
+        const uint64_t key = ((uint64_t)depth << 32) | colour;
+        if (pixel == run_pixel) { run_key = min(run_key, key); return; }
+        if (run_pixel != no_pixel) visible_min(key_plane + run_pixel, run_key);
+        run_pixel = pixel; run_key = key;
+    }, (int)(e.lod & LOD_NPR_MASK));
+    if (run_pixel != no_pixel) visible_min(key_plane + run_pixel, run_key);
+    uint32_t sum = cnt;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    if (lane == 0) s_part[wave] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < LWC_WAVES; ++w) t += s_part[w];
+        hit_totals[blockIdx.x] = t;
+    }
+}
+
+// ROW: out[p] = min of the high halves of key_plane over the columns within `radius` of p's, in p's row; *covered += the pixels
+// that hold a key. !ROW: out[p] = min of in[] over the rows within `radius` of p's, in p's column.
+template <bool ROW>
+__global__ void __launch_bounds__(VIS_DILATE_THREADS) k_visible_dilate(const unsigned long long *key_plane, const uint32_t *in, uint32_t *out, int32_t width,
+                                                                       int32_t height, int32_t radius, unsigned long long *covered)
+{
+    const int64_t npix = (int64_t)width * height;
+    uint32_t mine = 0;
+    for (int64_t p = (int64_t)blockIdx.x * VIS_DILATE_THREADS + threadIdx.x; p < npix; p += (int64_t)gridDim.x * VIS_DILATE_THREADS) {
+        const int32_t x = (int32_t)(p % width), y = (int32_t)(p / width);
+        uint32_t m = 0xFFFFFFFFu;
+        if (ROW) {
+            const int32_t c0 = max(x - radius, 0), c1 = min(x + radius, width - 1);
+            for (int32_t c = c0; c <= c1; ++c) m = min(m, (uint32_t)(key_plane[p - x + c] >> 32));
+            if (key_plane[p] != VIS_NONE) ++mine;
+        } else {
+            const int32_t r0 = max(y - radius, 0), r1 = min(y + radius, height - 1);
+            for (int32_t r = r0; r <= r1; ++r) m = min(m, in[(int64_t)r * width + x]);
+        }
+        out[p] = m;
+    }
+    if (ROW) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d, 64);
+        if ((threadIdx.x & 63u) == 0 && mine) atomicAdd(covered, (unsigned long long)mine);
+    }
+}
+
+// Workgroup x takes list[x]: index_plane[pixel] = min record index among the rect's hits whose key is the pixel's key word
+template <int LAYOUT, bool BC7>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_visible_index(StreamView s, const ScreenEntry *list, ScreenArgs q, const unsigned long long *key_plane,
+                                                                      unsigned long long *index_plane)
+{
+    const ScreenEntry e = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    load_packed_table(s, e.b, s_table);
+    const ScreenBatch B = screen_batch(s, e.b, e.lod);
+    const uint32_t npix = (uint32_t)q.width * (uint32_t)q.height;
+    const uint64_t index0 = (uint64_t)e.b * PCR_POINTS_PER_BATCH + (uint64_t)tid * PCR_POINTS_PER_THREAD;
+    decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, e.b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        int ix, iy; uint32_t pixel, depth;
+        if (!screen_project(q, B, x, y, z, ix, iy, pixel, depth) || !screen_in_rect(q, ix, iy) || pixel >= npix) return;
+        if (key_plane[pixel] == (((uint64_t)depth << 32) | colour)) visible_min(index_plane + pixel, index0 + (uint64_t)i);
+    }, (int)(e.lod & LOD_NPR_MASK));
+}
+
+// Is hit (pixel, depth) of record `index`, which lies in the rect, selected? front: PCR_VISIBLE_FRONT, else PCR_VISIBLE_SURFACE.
+__device__ __forceinline__ bool visible_selected(bool front, const uint32_t *depth_plane, const unsigned long long *index_plane, uint32_t pixel,
+                                                 uint32_t depth, uint64_t index)
+{
+    if (!visible_surface(depth, depth_plane[pixel])) return false;
+    return !front || index_plane[pixel] == index;
+}
+
+// Workgroup x takes list[x]: chain_counts[x * 1024 + chain] = the chain's selected hits, totals[2 x] = their sum, totals[2 x + 1]
+// = the batch's hits in the rect (the candidates)
+template <int LAYOUT>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_visible_count(StreamView s, const ScreenEntry *list, ScreenArgs q, bool front, const uint32_t *depth_plane,
+                                                                      const unsigned long long *index_plane, uint32_t *chain_counts, uint32_t *totals)
+{
+    const ScreenEntry e = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint32_t s_part[2][LWC_WAVES];
+    load_packed_table(s, e.b, s_table);
+    const ScreenBatch B = screen_batch(s, e.b, e.lod);
+    const uint32_t npix = (uint32_t)q.width * (uint32_t)q.height;
+    const uint64_t index0 = (uint64_t)e.b * PCR_POINTS_PER_BATCH + (uint64_t)tid * PCR_POINTS_PER_THREAD;
+    uint32_t cnt = 0, cand = 0;
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, e.b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t) {
+        int ix, iy; uint32_t pixel, depth;
+        if (!screen_project(q, B, x, y, z, ix, iy, pixel, depth) || !screen_in_rect(q, ix, iy) || pixel >= npix) return;
+        ++cand;
+        if (visible_selected(front, depth_plane, index_plane, pixel, depth, index0 + (uint64_t)i)) ++cnt;
+    }, (int)(e.lod & LOD_NPR_MASK));
+    chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid] = cnt;
+    uint32_t sum = cnt, sum_cand = cand;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { sum += __shfl_xor(sum, d, 64); sum_cand += __shfl_xor(sum_cand, d, 64); }
+    if (lane == 0) { s_part[0][wave] = sum; s_part[1][wave] = sum_cand; }
+    __syncthreads();
+    if (tid < 2) {
+        uint32_t t = 0;
+        for (int w = 0; w < LWC_WAVES; ++w) t += s_part[tid][w];
+        totals[2 * (size_t)blockIdx.x + tid] = t;
+    }
+}
+
+// Workgroup x takes list[x]: k_screen_write for the selected hits (chain_counts: k_visible_count's for the same arguments)
+template <int LAYOUT, bool BC7>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_visible_write(StreamView s, const ScreenEntry *list, ScreenArgs q, bool front, const uint32_t *depth_plane,
+                                                                      const unsigned long long *index_plane, const uint32_t *chain_counts, const int64_t *offsets,
+                                                                      uint4 *points, uint4 *hits)
+{
+    const ScreenEntry e = list[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint32_t s_part[LWC_WAVES];
+    const uint32_t mine = chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid];
+    uint32_t incl = mine;                                   // inclusive prefix inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += up;
+    }
+    if (lane == 63) s_part[wave] = incl;
+    load_packed_table(s, e.b, s_table);                     // (its barrier publishes s_part as well)
+    uint32_t before = incl - mine;
+    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    const ScreenBatch B = screen_batch(s, e.b, e.lod);
+    const uint32_t npix = (uint32_t)q.width * (uint32_t)q.height;
+    const int64_t first = offsets[blockIdx.x] + before;
+    const uint64_t index0 = (uint64_t)e.b * PCR_POINTS_PER_BATCH + (uint64_t)tid * PCR_POINTS_PER_THREAD;
+    uint32_t k = 0;                                         // never past what k_visible_count counted for this chain
+    decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, e.b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        int ix, iy; uint32_t pixel, depth;
+        if (!screen_project(q, B, x, y, z, ix, iy, pixel, depth) || !screen_in_rect(q, ix, iy) || pixel >= npix || k >= mine) return;
+        const uint64_t index = index0 + (uint64_t)i;
+        if (!visible_selected(front, depth_plane, index_plane, pixel, depth, index)) return;
+        if (points) points[first + k] = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
+        if (hits) hits[first + k] = make_uint4(pixel, depth, (uint32_t)index, (uint32_t)(index >> 32));
+        ++k;
+    }, (int)(e.lod & LOD_NPR_MASK));
 }
 
 // ------------------------------------------------------------------------------------------------

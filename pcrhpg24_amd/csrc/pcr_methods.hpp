@@ -531,6 +531,25 @@ struct HuffmanLasData : Resource {
         return st;
     }
 
+    // Of selectScreen's hits those that make up the picture (pcr_read_visible: a counting call, then the read): mode
+    // PCR_VISIBLE_FRONT / PCR_VISIBLE_SURFACE, radius = the occluder window. depth: the plane Dr of the whole image, width * height
+    // words. Any vector may be NULL. Not in the reference.
+    pcr_visible_stats selectVisible(const pcr_render_params &p, const pcr_rect *rect, int mode, int radius, std::vector<pcr_point> *points,
+                                    std::vector<pcr_screen_hit> *hits, std::vector<uint32_t> *depth = nullptr)
+    {
+        if (!loadedOn) throw std::runtime_error("selectVisible: the resource is not loaded");
+        int64_t n = 0;
+        pcr_visible_stats st{};
+        if (depth) depth->resize((size_t)p.width * (size_t)p.height);
+        loadedOn->check(pcr_read_visible(loadedOn->ctx, &p, rect, mode, radius, nullptr, nullptr, depth ? depth->data() : nullptr, 0, &n, &st), "pcr_read_visible");
+        if (points) points->resize((size_t)n);
+        if (hits) hits->resize((size_t)n);
+        if (n && (points || hits))
+            loadedOn->check(pcr_read_visible(loadedOn->ctx, &p, rect, mode, radius, points ? points->data() : nullptr, hits ? hits->data() : nullptr, nullptr,
+                                             (size_t)n, &n, &st), "pcr_read_visible");
+        return st;
+    }
+
     // The point under pixel (px, py) of a frame of camera `p`, within `radius` pixels (pcr_pick); false: none. Not in the reference.
     bool pick(const pcr_render_params &p, int px, int py, int radius, pcr_point &point, pcr_screen_hit &hit)
     {

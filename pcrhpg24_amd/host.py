@@ -1600,6 +1600,61 @@ class Context:
         self._chk(self.lib.pcr_pick(self.h, C.byref(p), int(px), int(py), int(radius), C.byref(pt), C.byref(hit), C.byref(found)), "pcr_pick")
         return (pt, hit) if found.value else None
 
+    # -- visible selection (pcr_select_visible / pcr_read_visible) -----------------------------------------
+    VISIBLE_FRONT, VISIBLE_SURFACE = N.VISIBLE_FRONT, N.VISIBLE_SURFACE
+    _VISIBLE_MODES = {"front": N.VISIBLE_FRONT, "surface": N.VISIBLE_SURFACE}
+
+    def _visible_mode(self, mode) -> int:
+        if isinstance(mode, str):
+            if mode not in self._VISIBLE_MODES:
+                raise ValueError(f"mode must be 'front' or 'surface', not {mode!r}")
+            return self._VISIBLE_MODES[mode]
+        return int(mode)
+
+    def select_visible(self, p: RenderParams, rect=None, mode="front", radius: int = 0, depth: bool = False):
+        """Of select_screen(p, rect)'s hits those that make up the picture, on the context's device: (points, hits), shaped as
+        select_screen's and in increasing index order, or (points, hits, depth) with depth=True. mode "front" (VISIBLE_FRONT):
+        per pixel of the rect the one hit that is least by (depth_bits, colour, index); "surface" (VISIBLE_SURFACE): every hit of
+        the rect within 1 % of its pixel's front depth, float64(w) <= float64(dr) * 1.01. The front depth of a pixel is taken
+        over all hits of the image, and with radius > 0 (up to VISIBLE_MAX_RADIUS) over the pixels within `radius` columns and
+        rows as well: hidden-point removal for a cloud with gaps; a front hit that fails the test is dropped. depth is that
+        plane of the whole image, a torch.int32 tensor [height, width] holding the uint32 float bits of w (0xFFFFFFFF = -1: no
+        hit within the radius; depth.view(torch.float32) gives w, NaN where empty). The call counts first and allocates
+        exactly; synchronises. The counts of the last call are in self.visible_stats."""
+        import torch
+        rect, mode, radius = as_rect(rect), self._visible_mode(mode), int(radius)
+        dev = torch.device("cuda", self.device)
+        cnt, st = c_i64(), N.VisibleStats()
+        rp = C.byref(rect) if rect is not None else None
+        plane = torch.empty((p.height, p.width), dtype=torch.int32, device=dev) if depth else None
+        torch.cuda.current_stream(dev).synchronize()
+        self._chk(self.lib.pcr_select_visible(self.h, C.byref(p), rp, mode, radius, None, None, C.c_void_p(plane.data_ptr()) if depth else None, 0,
+                                              C.byref(cnt), C.byref(st)), "pcr_select_visible")
+        pts = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
+        hits = torch.empty((cnt.value, 2), dtype=torch.int64, device=dev)
+        if cnt.value:
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self.lib.pcr_select_visible(self.h, C.byref(p), rp, mode, radius, C.c_void_p(pts.data_ptr()), C.c_void_p(hits.data_ptr()), None,
+                                                  cnt.value, C.byref(cnt), C.byref(st)), "pcr_select_visible")
+        self.visible_stats = st.as_dict()
+        return (pts, hits, plane) if depth else (pts, hits)
+
+    def read_visible(self, p: RenderParams, rect=None, mode="front", radius: int = 0, depth: bool = False):
+        """The same on the host, without torch: numpy structured arrays of POINT_DTYPE and HIT_DTYPE, and with depth=True the
+        plane as a uint32 array [height, width] (pcr_read_visible: a counting call, then the read; synchronises)."""
+        rect, mode, radius = as_rect(rect), self._visible_mode(mode), int(radius)
+        cnt, st = c_i64(), N.VisibleStats()
+        rp = C.byref(rect) if rect is not None else None
+        plane = np.empty((p.height, p.width), np.uint32) if depth else None
+        self._chk(self.lib.pcr_read_visible(self.h, C.byref(p), rp, mode, radius, None, None, plane.ctypes.data if depth else None, 0, C.byref(cnt),
+                                            C.byref(st)), "pcr_read_visible")
+        pts, hits = np.empty(cnt.value, POINT_DTYPE), np.empty(cnt.value, HIT_DTYPE)
+        if cnt.value:
+            self._chk(self.lib.pcr_read_visible(self.h, C.byref(p), rp, mode, radius, pts.ctypes.data, hits.ctypes.data, None, cnt.value, C.byref(cnt),
+                                                C.byref(st)), "pcr_read_visible")
+        self.visible_stats = st.as_dict()
+        return (pts, hits, plane) if depth else (pts, hits)
+
     def stats(self) -> dict:
         st = RenderStats()
         self._chk(self.lib.pcr_get_stats(self.h, C.byref(st)), "pcr_get_stats")
@@ -1917,6 +1972,18 @@ class HuffmanLasData(Resource):
         tensor [n, 3] = x * scale + offset from las_info()'s scale and offset, as points_in_box; world=False: (pts, hits)."""
         import torch
         pts, hits = renderer.ctx.select_screen(renderer.render_params() if params is None else params, rect)
+        if not world:
+            return pts, hits
+        info = self.las_info()
+        so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
+        return pts[:, :3].to(torch.float64) * so[0] + so[1], pts, hits
+
+    def visible_points(self, renderer: Renderer, params: Optional[RenderParams] = None, rect=None, mode="front", radius: int = 0, world: bool = True):
+        """The points of the loaded resource that make up the picture of `params` (None: renderer.render_params()) inside `rect`:
+        points_on_screen without what lies behind the surface (Context.select_visible: mode "front" / "surface", radius = the
+        occluder window). world=True: (xyz, pts, hits) as points_on_screen; world=False: (pts, hits)."""
+        import torch
+        pts, hits = renderer.ctx.select_visible(renderer.render_params() if params is None else params, rect, mode, radius)
         if not world:
             return pts, hits
         info = self.las_info()
