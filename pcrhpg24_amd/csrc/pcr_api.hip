@@ -15,6 +15,7 @@
 #include <cstring>
 #include <deque>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace pcr;
@@ -23,7 +24,8 @@ constexpr int PCR_STATS_PARTIALS = PCR_MAX_PREPASS_WORKGROUPS;   // one partial 
 #ifndef PCR_DEFAULT_PARTS
 #define PCR_DEFAULT_PARTS 2                     /* workgroups per batch of k_render unless pcr_set_workgroup_parts says otherwise */
 #endif
-constexpr int64_t DECODE_STAGE_BATCHES = 64;     // batches per piece of pcr_read_points: 64 MiB of records on the device
+constexpr int64_t DECODE_STAGE_BATCHES = 64;     // batches per piece of pcr_read_points and of the shared read loop of the kept-rows calls
+                                                 // (kept_write): 64 MiB of records on the device
 constexpr int64_t TRANSCODE_CHUNK = 128;        // batches per k_transcode launch when the lane-major words are scratch (40 MB)
 
 struct pcr_ctx {
@@ -172,8 +174,7 @@ struct pcr_ctx {
     size_t quant_scratch_bytes = 0;
     uint32_t *d_quant_values = nullptr;         // [quant_values_entries]
     size_t quant_values_entries = 0;
-    // voxel thinning (pcr_thin / pcr_read_thin): the lists of a call's batches, the voxel table, the keep bitmap, and
-    // pcr_read_thin's staging of the rows (the records go through d_decode_stage)
+    // voxel thinning (pcr_thin / pcr_read_thin): the lists of a call's batches, the voxel table and the keep bitmap
     int64_t thin_capacity = 0;                  // batches the four arrays below hold
     uint32_t *d_thin_list = nullptr;            // [thin_capacity] the batches the clip does not miss
     uint32_t *d_thin_totals = nullptr;          // [thin_capacity * 2] runs and candidates (k_thin_runs), then kept records (k_thin_totals)
@@ -184,8 +185,10 @@ struct pcr_ctx {
     unsigned long long *d_thin_keep = nullptr;  // [thin_keep_words] a word per chain of the call's range
     int64_t thin_keep_words = 0;
     uint32_t *d_thin_error = nullptr;           // [1] k_thin_mark found no slot
-    int64_t *d_thin_rows_stage = nullptr;       // [thin_rows_stage_batches * 65536]
-    int64_t thin_rows_stage_batches = 0;
+    // the host forms of the kept-rows calls (pcr_read_thin .. pcr_read_voxel_mean): the stage of column i of a call's outputs (the
+    // records go through d_decode_stage)
+    void *d_col_stage[3] = {};                  // [col_stage_bytes[i]]
+    int64_t col_stage_bytes[3] = {};
     // voxel denoising (pcr_denoise / pcr_read_denoise) shares all of the above; its own: the voxel counters of k_denoise_verdict
     unsigned long long *d_denoise_counters = nullptr;   // [2] occupied slots, isolated ones
     // connected components (pcr_components / pcr_read_components) share all of the above; their own: per slot of the table the
@@ -193,7 +196,6 @@ struct pcr_ctx {
     unsigned char *d_components_scratch = nullptr;      // [components_slots * 20]
     int64_t components_slots = 0;
     unsigned long long *d_components_counters = nullptr; // [5] occupied slots, components, small ones, their candidates, the largest
-    int64_t *d_components_labels_stage = nullptr;       // [components_labels_stage_batches * 65536]
     // radius neighbourhoods (pcr_neighbors / pcr_read_neighbors) share pcr_thin's scratch; their own: the index and the dense results
     uint2 *d_neighbors_cursor = nullptr;                // [neighbors_slots] per slot of the table: bucket start, entries filled
     int64_t neighbors_slots = 0;
@@ -206,33 +208,20 @@ struct pcr_ctx {
     unsigned long long *d_neighbors_n = nullptr, *d_neighbors_nn2 = nullptr;    // [.._rows] N and nn2 by row, each only once asked for
     int64_t neighbors_n_rows = 0, neighbors_nn2_rows = 0;
     unsigned long long *d_neighbors_counters = nullptr; // [NEIGHBORS_COUNTERS]
-    int64_t *d_neighbors_counts_stage = nullptr;        // [neighbors_counts_stage_batches * 65536]
-    int64_t neighbors_counts_stage_batches = 0;
-    uint64_t *d_neighbors_nn2_stage = nullptr;          // [neighbors_nn2_stage_batches * 65536]
-    int64_t neighbors_nn2_stage_batches = 0;
-    // local moments (pcr_local_moments / pcr_read_local_moments) share pcr_neighbors' index; their own: the dense records and the stages
+    // local moments (pcr_local_moments / pcr_read_local_moments) share pcr_neighbors' index; their own: the dense records
     uint4 *d_moments_dense = nullptr, *d_moments_eigen = nullptr;   // [.._rows * 5] pcr_moments and [.._rows * 3] pcr_eigen by row, each only once asked for
     int64_t moments_dense_rows = 0, moments_eigen_rows = 0;
-    pcr_moments *d_moments_stage = nullptr;             // [moments_stage_batches * 65536]
-    int64_t moments_stage_batches = 0;
-    pcr_eigen *d_moments_eigen_stage = nullptr;         // [moments_eigen_stage_batches * 65536]
-    int64_t moments_eigen_stage_batches = 0;
-    // k nearest neighbours (pcr_knn / pcr_read_knn) share pcr_neighbors' index; their own: the dense words and the stage
+    // k nearest neighbours (pcr_knn / pcr_read_knn) share pcr_neighbors' index; their own: the dense words
     unsigned long long *d_knn_dense = nullptr;          // [knn_dense_words] k words by row, only once asked for
     int64_t knn_dense_words = 0;
-    uint64_t *d_knn_stage = nullptr;                    // [knn_stage_words]
-    int64_t knn_stage_words = 0;
-    int64_t components_labels_stage_batches = 0;
     // voxel means (pcr_voxel_mean / pcr_read_voxel_mean) share pcr_thin's scratch; their own: the record index of every chain's
-    // first kept row, the accumulator and (key, row) of every record, and pcr_read_voxel_mean's stage of the counts
+    // first kept row, the accumulator and (key, row) of every record
     unsigned long long *d_voxel_prefix = nullptr;       // [voxel_prefix_words] a word per chain of the call's range
     int64_t voxel_prefix_words = 0;
     unsigned long long *d_voxel_acc = nullptr;          // [voxel_acc_records * VOXEL_ACC_WORDS]
     int64_t voxel_acc_records = 0;
     VoxelRec *d_voxel_rec = nullptr;                    // [voxel_rec_records]
     int64_t voxel_rec_records = 0;
-    int64_t *d_voxel_counts_stage = nullptr;            // [voxel_counts_stage_batches * 65536]
-    int64_t voxel_counts_stage_batches = 0;
     int64_t prepass_batches = 0;
     static constexpr int FENCES = 8;
     hipEvent_t fence[FENCES] = {};              // pcr_fence_record / pcr_fence_wait: device-scope ordering between streams
@@ -335,19 +324,16 @@ void free_stream_buffers(pcr_ctx *c)
     dfree(c->d_grid_list); c->grid_capacity = 0; c->h_grid_list.clear();
     dfree(c->d_thin_list); dfree(c->d_thin_totals); dfree(c->d_thin_wlist); dfree(c->d_thin_offsets); c->thin_capacity = 0;
     dfree(c->d_thin_table); c->thin_slots = 0; dfree(c->d_thin_keep); c->thin_keep_words = 0; dfree(c->d_thin_error);
-    dfree(c->d_thin_rows_stage); c->thin_rows_stage_batches = 0;
+    for (int i = 0; i < 3; ++i) { dfree(c->d_col_stage[i]); c->col_stage_bytes[i] = 0; }
     dfree(c->d_denoise_counters);
     dfree(c->d_components_scratch); c->components_slots = 0; dfree(c->d_components_counters);
-    dfree(c->d_components_labels_stage); c->components_labels_stage_batches = 0;
     dfree(c->d_neighbors_cursor); c->neighbors_slots = 0; dfree(c->d_neighbors_starts); c->neighbors_chains = 0;
     dfree(c->d_neighbors_bucket); c->neighbors_candidates = 0; dfree(c->d_neighbors_work); c->neighbors_work = 0;
     dfree(c->d_neighbors_n); c->neighbors_n_rows = 0; dfree(c->d_neighbors_nn2); c->neighbors_nn2_rows = 0; dfree(c->d_neighbors_counters);
-    dfree(c->d_neighbors_counts_stage); c->neighbors_counts_stage_batches = 0; dfree(c->d_neighbors_nn2_stage); c->neighbors_nn2_stage_batches = 0;
     dfree(c->d_moments_dense); c->moments_dense_rows = 0; dfree(c->d_moments_eigen); c->moments_eigen_rows = 0;
-    dfree(c->d_moments_stage); c->moments_stage_batches = 0; dfree(c->d_moments_eigen_stage); c->moments_eigen_stage_batches = 0;
-    dfree(c->d_knn_dense); c->knn_dense_words = 0; dfree(c->d_knn_stage); c->knn_stage_words = 0;
+    dfree(c->d_knn_dense); c->knn_dense_words = 0;
     dfree(c->d_voxel_prefix); c->voxel_prefix_words = 0; dfree(c->d_voxel_acc); c->voxel_acc_records = 0;
-    dfree(c->d_voxel_rec); c->voxel_rec_records = 0; dfree(c->d_voxel_counts_stage); c->voxel_counts_stage_batches = 0;
+    dfree(c->d_voxel_rec); c->voxel_rec_records = 0;
 
     if (c->any_generic_pending && c->any_generic_ev) (void)hipEventSynchronize(c->any_generic_ev);
     c->any_generic_pending = false;
@@ -2713,16 +2699,20 @@ int pcr_read_grid_quantiles(pcr_ctx *c, int64_t first_batch, int64_t count, cons
     return PCR_OK;
 }
 
-// ---- voxel thinning ----------------------------------------------------------------------------
+// ---- kept rows: the host path of pcr_thin, _denoise, _components, _neighbors, _local_moments, _knn and _voxel_mean ----------
+// Each of these calls classifies batches against a clip, builds a voxel table, sets bits in the keep bitmap c->d_thin_keep, counts
+// them per batch and writes the kept records with a few columns per row; the device form (pcr_X) and the host form (pcr_read_X)
+// differ in where the destinations live. What they share is here; the sections below hold each call's checks, plan and kernels.
+extern "C++" {                          // (templates among them)
 namespace {
-// What a thinning call over batches [first, first + n) has to write: the batches the clip does not miss, of those the ones that
-// keep a record (their keep words sit in c->d_thin_keep) and each one's record count.
+// What a call over batches [first, first + n) has to write: the batches the clip does not miss, of those the ones that keep a
+// record (their keep words sit in c->d_thin_keep) and each one's record count.
 struct ThinPlan {
     std::vector<uint32_t> listed;       // ascending
     std::vector<uint32_t> writers;      // ascending
     std::vector<int64_t> cnt;           // [writers.size()]
-    std::vector<int64_t> offsets;       // staging of k_thin_write's offsets (alive until the stream has been synchronised)
-    pcr_thin_stats st{};
+    std::vector<int64_t> offsets;       // staging of the write kernels' offsets (alive until the stream has been synchronised)
+    pcr_thin_stats st{};                // thin_plan only
     ThinArgs args{};                    // the clip, the lattice and the table of the plan (pcr_components: for k_components_labels;
                                         // thin_plan: for pcr_voxel_mean's kernels)
     const thin_u64 *label = nullptr;    // pcr_components only: the label of every slot
@@ -2774,226 +2764,30 @@ int thin_reserve(pcr_ctx *c, int64_t nL, int64_t n)
     return PCR_OK;
 }
 
-// Phases one to three: classify (host, from the cached exact boxes), count the runs, fill the voxel table, flag the kept rows and
-// count them per batch. Synchronises.
-int thin_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const pcr_box *clip, int mode, ThinPlan &p)
-{
-    p.listed.clear(); p.writers.clear(); p.cnt.clear();
-    p.st = pcr_thin_stats{n, 0, 0, 0, 0, 0};
-    ThinArgs a{};
-    for (int k = 0; k < 3; ++k) { a.q.min[k] = clip ? clip->min[k] : INT32_MIN; a.q.max[k] = clip ? clip->max[k] : INT32_MAX; }
-    if (n == 0 || box_empty(a.q)) return PCR_OK;
-    int rc;
-    pcr_box q{};                                    // the union of the listed batches' boxes, inside the clip
-    if ((rc = thin_list_batches(c, first, n, a, p.listed, q))) return rc;
-    const int64_t nL = (int64_t)p.listed.size();
-    if (nL == 0) return PCR_OK;
-    int axis = 0;
-    switch (thin_lattice(vox.origin, vox.cell, q.min, q.max, &a.lat, &axis)) {
-    case THIN_LATTICE_EXTENT:
-        return set_err(c, PCR_E_ARG, "the points to thin span %lld on axis %d, 2^31 or more: pass a clip or a larger cell (a tail artefact far outside the cloud?)",
-                       (long long)q.max[axis] - (long long)q.min[axis], axis);
-    case THIN_LATTICE_VOXELS:
-        return set_err(c, PCR_E_ARG, "the points to thin span %lld on axis %d, more than 2^21 voxels of %d: pass a clip or a larger cell (a tail artefact far outside the cloud?)",
-                       (long long)q.max[axis] - (long long)q.min[axis], axis, vox.cell);
-    default: break;
-    }
-    p.st.batches_outside = n - nL; p.st.batches_decoded = nL;
-    if ((rc = thin_reserve(c, nL, n))) return rc;
-
-    a.first_batch = (uint32_t)first;
-    const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)nL), block(PCR_WORKGROUP_SIZE);
-    const bool windows = select_reads_windows(c);
-    HIP_TRY(c, hipMemcpyAsync(c->d_thin_list, p.listed.data(), (size_t)nL * 4, hipMemcpyHostToDevice, c->stream));
-    if (windows) hipLaunchKernelGGL((k_thin_runs<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_thin_list, a, c->d_thin_totals);
-    else         hipLaunchKernelGGL((k_thin_runs<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_thin_list, a, c->d_thin_totals);
-    HIP_TRY(c, hipGetLastError());
-    std::vector<uint32_t> totals((size_t)nL * 2 + 1);
-    HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_thin_totals, (size_t)nL * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (int64_t k = 0; k < nL; ++k) { p.st.runs += totals[(size_t)k * 2]; p.st.points_considered += totals[(size_t)k * 2 + 1]; }
-    if (p.st.runs == 0) return PCR_OK;
-
-    uint32_t log2_slots = 10;
-    while (((int64_t)1 << log2_slots) < 2 * p.st.runs) ++log2_slots;
-    const int64_t slots = (int64_t)1 << log2_slots;
-    if (!thin_grow((void **)&c->d_thin_table, c->thin_slots, slots, sizeof(ThinSlot)))
-        return set_err(c, PCR_E_NOMEM, "out of device memory for a voxel table of %lld slots (%lld runs): pass a clip or a larger cell", (long long)slots,
-                       (long long)p.st.runs);
-    p.st.table_slots = slots;
-    a.log2_slots = log2_slots; a.table = c->d_thin_table; a.error = c->d_thin_error;
-    p.args = a;
-    HIP_TRY(c, hipMemsetAsync(c->d_thin_table, 0xFF, (size_t)slots * sizeof(ThinSlot), c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_thin_keep, 0, (size_t)n * PCR_WORKGROUP_SIZE * 8, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_thin_error, 0, 4, c->stream));
-#define PCR_LAUNCH(L, M) hipLaunchKernelGGL((k_thin_mark<L, M>), grid, block, 0, c->stream, s, c->d_thin_list, a)
-    if (windows) { if (mode == PCR_THIN_CENTER) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, PCR_THIN_CENTER); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, PCR_THIN_FIRST); }
-    else         { if (mode == PCR_THIN_CENTER) PCR_LAUNCH(LAYOUT_WORDS, PCR_THIN_CENTER); else PCR_LAUNCH(LAYOUT_WORDS, PCR_THIN_FIRST); }
-#undef PCR_LAUNCH
-    HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(k_thin_flag, dim3((unsigned)std::min<int64_t>((slots + 255) / 256, 4096)), dim3(256), 0, c->stream, c->d_thin_table,
-                       (unsigned long long)slots, (unsigned long long)n * PCR_POINTS_PER_BATCH, c->d_thin_keep);
-    HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(k_thin_totals, grid, dim3(256), 0, c->stream, c->d_thin_list, (uint32_t)first, c->d_thin_keep, c->d_thin_totals);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_thin_totals, (size_t)nL * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(totals.data() + nL * 2, c->d_thin_error, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (totals[(size_t)nL * 2]) return set_err(c, PCR_E_NOMEM, "voxel table overflow: %lld slots for %lld runs", (long long)slots, (long long)p.st.runs);
-    for (int64_t k = 0; k < nL; ++k) {
-        if (!totals[(size_t)k]) continue;
-        p.writers.push_back(p.listed[(size_t)k]); p.cnt.push_back(totals[(size_t)k]);
-        p.st.points_kept += totals[(size_t)k];
-    }
-    return PCR_OK;
-}
-
-// Enqueue the writes of batches [i0, i1) of the plan's range: their kept records to `points`, the rows to `rows` (device, either
-// may be NULL, each holds the records of those batches); for a plan of pcr_components the labels of the rows to `labels` as well
-// (NULL: not). The caller synchronises.
-int thin_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, uint4 *points, int64_t *rows, int64_t *labels = nullptr)
-{
-    const size_t w0 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i0)) - p.writers.begin());
-    const size_t w1 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i1)) - p.writers.begin());
-    if (w0 == w1) return PCR_OK;
-    p.offsets.clear();
-    int64_t off = 0;
-    for (size_t w = w0; w < w1; ++w) { p.offsets.push_back(off); off += p.cnt[w]; }
-    HIP_TRY(c, hipMemcpyAsync(c->d_thin_wlist + w0, p.writers.data() + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_thin_offsets + w0, p.offsets.data(), (w1 - w0) * 8, hipMemcpyHostToDevice, c->stream));
-    const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)(w1 - w0)), block(PCR_WORKGROUP_SIZE);
-    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
-#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_thin_write<L, B>), grid, block, 0, c->stream, s, c->d_thin_wlist + w0, (uint32_t)first, c->d_thin_keep, \
-                                            c->d_thin_offsets + w0, points, rows)
-    if (points || rows) {
-        if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
-        else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
-        HIP_TRY(c, hipGetLastError());
-    }
-#undef PCR_LAUNCH
-    if (labels) {
-        if (select_reads_windows(c))
-            hipLaunchKernelGGL((k_components_labels<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_thin_wlist + w0, p.args, c->d_thin_keep,
-                               c->d_thin_offsets + w0, p.label, labels);
-        else
-            hipLaunchKernelGGL((k_components_labels<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_thin_wlist + w0, p.args, c->d_thin_keep,
-                               c->d_thin_offsets + w0, p.label, labels);
-        HIP_TRY(c, hipGetLastError());
-    }
-    return PCR_OK;
-}
-
-// The checks and the plan shared by pcr_thin / pcr_read_thin. *done: nothing left to write (an error, a count-only call, no records).
-int thin_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int mode, const void *points, size_t points_align,
-                 const void *rows, size_t rows_align, size_t capacity, int64_t *out_count, pcr_thin_stats *stats, int64_t *n, ThinPlan &p, bool *done)
-{
-    *done = true;
-    if (out_count) *out_count = 0;
-    int rc = select_range(c, first, count, n);
-    if (rc) return rc;
-    if (!vox) return set_err(c, PCR_E_ARG, "the voxel lattice is NULL");
-    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
-    if (points && reinterpret_cast<uintptr_t>(points) % points_align != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
-    if (rows && reinterpret_cast<uintptr_t>(rows) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the rows is misaligned (%zu bytes)", rows_align);
-    if (vox->cell < 1 || vox->cell > PCR_THIN_MAX_CELL)
-        return set_err(c, PCR_E_ARG, "voxel cell of %d: the edge length is 1 .. %d (PCR_THIN_MAX_CELL)", vox->cell, PCR_THIN_MAX_CELL);
-    if (mode != PCR_THIN_FIRST && mode != PCR_THIN_CENTER) return set_err(c, PCR_E_ARG, "mode is %d, not PCR_THIN_FIRST or PCR_THIN_CENTER", mode);
-    if (mode == PCR_THIN_CENTER && vox->cell > PCR_THIN_MAX_CENTER_CELL)
-        return set_err(c, PCR_E_ARG, "voxel cell of %d with PCR_THIN_CENTER: at most %d (PCR_THIN_MAX_CENTER_CELL)", vox->cell, PCR_THIN_MAX_CENTER_CELL);
-    if (*n > ((int64_t)1 << 40) / PCR_POINTS_PER_BATCH) return set_err(c, PCR_E_ARG, "a range of %lld batches has more than 2^40 rows", (long long)*n);
-    if ((rc = thin_plan(c, first, *n, *vox, clip, mode, p))) return rc;
-    *out_count = p.st.points_kept;
-    if (stats) *stats = p.st;
-    if ((!points && !rows) || p.st.points_kept == 0) return PCR_OK;
-    if (capacity < (size_t)p.st.points_kept)
-        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld kept", capacity, (long long)p.st.points_kept);
-    *done = false;
-    return PCR_OK;
-}
-
-// The plan's records and / or rows (either may be NULL), for a plan of pcr_components the labels too (NULL: not), into host memory
-// through the staging buffers. Synchronises.
-int thin_read_pieces(pcr_ctx *c, int64_t first_batch, int64_t n, ThinPlan &p, pcr_point *host_points, int64_t *host_rows, int64_t *host_labels = nullptr)
-{
-    int rc;
-    // pieces of at most DECODE_STAGE_BATCHES batches: a batch keeps at most 65 536 records, so a piece fits the staging buffers
-    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
-    if (host_points && !thin_grow((void **)&c->d_decode_stage, c->decode_stage_batches, piece, (size_t)PCR_POINTS_PER_BATCH * sizeof(pcr_point)))
-        return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of points", (long long)piece);
-    if (host_rows && !thin_grow((void **)&c->d_thin_rows_stage, c->thin_rows_stage_batches, piece, (size_t)PCR_POINTS_PER_BATCH * sizeof(int64_t)))
-        return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of rows", (long long)piece);
-    if (host_labels && !thin_grow((void **)&c->d_components_labels_stage, c->components_labels_stage_batches, piece, (size_t)PCR_POINTS_PER_BATCH * sizeof(int64_t)))
-        return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of labels", (long long)piece);
-    uint4 *const d_points = host_points ? reinterpret_cast<uint4 *>(c->d_decode_stage) : nullptr;
-    int64_t *const d_rows = host_rows ? c->d_thin_rows_stage : nullptr;
-    int64_t *const d_labels = host_labels ? c->d_components_labels_stage : nullptr;
-    int64_t written = 0;
-    size_t w = 0;
-    for (int64_t i0 = 0; i0 < n; i0 += piece) {
-        const int64_t i1 = std::min(n, i0 + piece);
-        int64_t m = 0;
-        for (; w < p.writers.size() && p.writers[w] < (uint32_t)(first_batch + i1); ++w) m += p.cnt[w];
-        if (m == 0) continue;
-        if ((rc = thin_emit(c, first_batch, i0, i1, p, d_points, d_rows, d_labels))) return rc;
-        if (d_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
-        if (d_rows) HIP_TRY(c, hipMemcpyAsync(host_rows + written, d_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        if (d_labels) HIP_TRY(c, hipMemcpyAsync(host_labels + written, d_labels, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        written += m;
-    }
-    return PCR_OK;
-}
-} // namespace
-
-int pcr_thin(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int mode, void *dev_points, void *dev_rows,
-             size_t capacity_points, int64_t *out_count, pcr_thin_stats *stats)
-{
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ThinPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = thin_prepare(c, first_batch, count, vox, clip, mode, dev_points, 16, dev_rows, 8, capacity_points, out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    if ((rc = thin_emit(c, first_batch, 0, n, p, static_cast<uint4 *>(dev_points), static_cast<int64_t *>(dev_rows)))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PCR_OK;
-}
-
-int pcr_read_thin(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int mode, pcr_point *host_points,
-                  int64_t *host_rows, size_t capacity_points, int64_t *out_count, pcr_thin_stats *stats)
-{
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ThinPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = thin_prepare(c, first_batch, count, vox, clip, mode, host_points, alignof(pcr_point), host_rows, alignof(int64_t), capacity_points, out_count,
-                          stats, &n, p, &done);
-    if (rc || done) return rc;
-    return thin_read_pieces(c, first_batch, n, p, host_points, host_rows);
-}
-
-// ---- voxel denoising ---------------------------------------------------------------------------
-namespace {
-// What the calls on pcr_denoise's frame (pcr_denoise, pcr_components) share: the statistics common to both, and what the first half
-// of the plan hands to the call's own kernels and to the second half.
+// What the plans share: the statistics common to all, and what the first half hands to the call's own kernels and to the tail.
 struct VoxelPlan {
     int64_t batches_outside = 0, batches_decoded = 0, points_considered = 0, runs = 0, table_slots = 0, points_written = 0;
     int64_t nL = 0;                     // the listed batches
     bool windows = false;               // the layout the kernels read
-    ThinArgs a{};                       // the clip, the lattice of noise_lattice, the first batch, the table and the error word
+    ThinArgs a{};                       // the clip, the lattice, the first batch, the table and the error word
     std::vector<uint32_t> totals;       // staging of d_thin_totals and the error word
 };
 
-// The first half: classify (host, from the cached exact boxes), the lattice, the scratch, the runs (k_thin_runs), the table sized
-// from them, key = all ones and value = 0 in every slot, the error word cleared. v.runs == 0 on return: nothing to do, no kernel
-// has touched the table. `verb` names the call in the messages; a table of more than 2^max_log2_slots slots is refused.
-// Synchronises.
-int voxel_plan_begin(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const pcr_box *clip, const char *verb, uint32_t max_log2_slots, ThinPlan &p,
-                     VoxelPlan &v, const char *cell = "cell")
+// The two kinds of voxel table: the lattice (pcr_lattice.h), its voxel limit as the messages put it, and how the table starts.
+// ones: every byte of the table 0xFF and the keep bitmap zeroed, for k_thin_mark's minima and k_thin_flag's bits; otherwise
+// k_denoise_clear: key = all ones and value = 0 in every slot (every lane of a listed batch stores its keep word later).
+struct VoxelTable {
+    int (*lattice)(const int32_t origin[3], int32_t cell, const int32_t qmin[3], const int32_t qmax[3], ThinLattice *out, int *axis);
+    const char *max_voxels;
+    bool ones;
+};
+constexpr VoxelTable THIN_TABLE{thin_lattice, "2^21", true}, NOISE_TABLE{noise_lattice, "2^21 - 2", false};
+
+// The first half of every plan: classify (host, from the cached exact boxes), the lattice, the scratch, the runs (k_thin_runs), the
+// table sized from them and started as `table` says, the error word cleared. v.runs == 0 on return: nothing to do, no kernel has
+// touched the table. `verb` names the call in the messages; a table of more than 2^max_log2_slots slots is refused. Synchronises.
+int voxel_plan_begin(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const pcr_box *clip, const char *verb, const VoxelTable &table,
+                     uint32_t max_log2_slots, ThinPlan &p, VoxelPlan &v, const char *cell = "cell")
 {
     p.listed.clear(); p.writers.clear(); p.cnt.clear();
     v = VoxelPlan{};
@@ -3007,13 +2801,13 @@ int voxel_plan_begin(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox
     const int64_t nL = (int64_t)p.listed.size();
     if (nL == 0) return PCR_OK;
     int axis = 0;
-    switch (noise_lattice(vox.origin, vox.cell, q.min, q.max, &a.lat, &axis)) {
+    switch (table.lattice(vox.origin, vox.cell, q.min, q.max, &a.lat, &axis)) {
     case THIN_LATTICE_EXTENT:
         return set_err(c, PCR_E_ARG, "the points to %s span %lld on axis %d, 2^31 or more: pass a clip or a larger %s (a tail artefact far outside the cloud?)",
                        verb, (long long)q.max[axis] - (long long)q.min[axis], axis, cell);
     case THIN_LATTICE_VOXELS:
-        return set_err(c, PCR_E_ARG, "the points to %s span %lld on axis %d, more than 2^21 - 2 voxels of %d: pass a clip or a larger %s (a tail artefact far outside the cloud?)",
-                       verb, (long long)q.max[axis] - (long long)q.min[axis], axis, vox.cell, cell);
+        return set_err(c, PCR_E_ARG, "the points to %s span %lld on axis %d, more than %s voxels of %d: pass a clip or a larger %s (a tail artefact far outside the cloud?)",
+                       verb, (long long)q.max[axis] - (long long)q.min[axis], axis, table.max_voxels, vox.cell, cell);
     default: break;
     }
     v.batches_outside = n - nL; v.batches_decoded = nL; v.nL = nL;
@@ -3044,33 +2838,29 @@ int voxel_plan_begin(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox
                        (long long)v.runs, cell);
     v.table_slots = slots;
     a.log2_slots = log2_slots; a.table = c->d_thin_table; a.error = c->d_thin_error;
-    hipLaunchKernelGGL(k_denoise_clear, dim3((unsigned)std::min<int64_t>((slots + 255) / 256, 4096)), dim3(256), 0, c->stream, c->d_thin_table,
-                       (unsigned long long)slots);
-    HIP_TRY(c, hipGetLastError());
+    if (table.ones) {
+        HIP_TRY(c, hipMemsetAsync(c->d_thin_table, 0xFF, (size_t)slots * sizeof(ThinSlot), c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_thin_keep, 0, (size_t)n * PCR_WORKGROUP_SIZE * 8, c->stream));
+    } else {
+        hipLaunchKernelGGL(k_denoise_clear, dim3((unsigned)std::min<int64_t>((slots + 255) / 256, 4096)), dim3(256), 0, c->stream, c->d_thin_table,
+                           (unsigned long long)slots);
+        HIP_TRY(c, hipGetLastError());
+    }
     HIP_TRY(c, hipMemsetAsync(c->d_thin_error, 0, 4, c->stream));
     return PCR_OK;
 }
 
-// The second half, after the call's own kernels have left their verdict in bit 63 of every occupied slot's value: flag the rows
-// on `mode`'s side of it (PCR_DENOISE_KEEP: bit clear), count them per batch, fill the plan thin_emit takes (p.st is not used) and
-// v.points_written, and copy `bytes` of the call's device counters `src` to `dst` on the way. Synchronises.
-int voxel_plan_finish(pcr_ctx *c, int64_t first, int mode, ThinPlan &p, VoxelPlan &v, void *dst, const void *src, size_t bytes)
+// The tail of every plan, once the keep bitmap is set: count the kept rows per batch (k_thin_totals), read the totals and the error
+// word back, refuse an overflow of the table, and collect the plan an emit takes (p.writers, p.cnt) and v.points_written. `bytes` of
+// the call's device counters `src` go to `dst` on the way. Synchronises.
+int voxel_plan_collect(pcr_ctx *c, int64_t first, ThinPlan &p, VoxelPlan &v, void *dst = nullptr, const void *src = nullptr, size_t bytes = 0)
 {
     const int64_t nL = v.nL;
-    const ThinArgs &a = v.a;
-    const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)nL), block(PCR_WORKGROUP_SIZE);
-    // (every lane of a listed batch stores its keep word, and only listed batches are read: the bitmap needs no clearing)
-#define PCR_LAUNCH(L, M) hipLaunchKernelGGL((k_denoise_flag<L, M>), grid, block, 0, c->stream, s, c->d_thin_list, a, c->d_thin_keep)
-    if (v.windows) { if (mode == PCR_DENOISE_ISOLATED) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, PCR_DENOISE_ISOLATED); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, PCR_DENOISE_KEEP); }
-    else           { if (mode == PCR_DENOISE_ISOLATED) PCR_LAUNCH(LAYOUT_WORDS, PCR_DENOISE_ISOLATED); else PCR_LAUNCH(LAYOUT_WORDS, PCR_DENOISE_KEEP); }
-#undef PCR_LAUNCH
-    HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(k_thin_totals, grid, dim3(256), 0, c->stream, c->d_thin_list, (uint32_t)first, c->d_thin_keep, c->d_thin_totals);
+    hipLaunchKernelGGL(k_thin_totals, dim3((unsigned)nL), dim3(256), 0, c->stream, c->d_thin_list, (uint32_t)first, c->d_thin_keep, c->d_thin_totals);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(v.totals.data(), c->d_thin_totals, (size_t)nL * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(v.totals.data() + nL * 2, c->d_thin_error, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (bytes) HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (v.totals[(size_t)nL * 2]) return set_err(c, PCR_E_NOMEM, "voxel table overflow: %lld slots for %lld runs", (long long)v.table_slots, (long long)v.runs);
     for (int64_t k = 0; k < nL; ++k) {
@@ -3081,6 +2871,286 @@ int voxel_plan_finish(pcr_ctx *c, int64_t first, int mode, ThinPlan &p, VoxelPla
     return PCR_OK;
 }
 
+// What a call writes per kept row: the record to `points` and up to three columns, `name` as the messages call them. Any
+// destination may be NULL, each holds `capacity` rows. host: the destinations are host memory (the pcr_read_ form).
+struct KeptColumn { const char *name; void *dst; size_t row_bytes; };
+struct KeptOut {
+    bool host;
+    void *points;
+    size_t capacity;
+    KeptColumn col[3];
+};
+
+// The checks every call starts with: the range into *n, the lattice where the call has one (has_lattice), out_count and the
+// alignment of the destinations: 16 / 8 bytes on the device, the types' own on the host. *out_count is 0 from here on.
+int kept_begin(pcr_ctx *c, int64_t first, int64_t count, const KeptOut &o, int64_t *out_count, int64_t *n, bool has_lattice = false,
+               const pcr_voxels *vox = nullptr)
+{
+    if (out_count) *out_count = 0;
+    int rc = select_range(c, first, count, n);
+    if (rc) return rc;
+    if (has_lattice && !vox) return set_err(c, PCR_E_ARG, "the voxel lattice is NULL");
+    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
+    const size_t points_align = o.host ? alignof(pcr_point) : 16, col_align = o.host ? alignof(int64_t) : 8;
+    if (o.points && reinterpret_cast<uintptr_t>(o.points) % points_align != 0)
+        return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
+    for (const KeptColumn &k : o.col)
+        if (k.dst && reinterpret_cast<uintptr_t>(k.dst) % col_align != 0)
+            return set_err(c, PCR_E_ARG, "the destination of the %s is misaligned (%zu bytes)", k.name, col_align);
+    if (vox && (vox->cell < 1 || vox->cell > PCR_THIN_MAX_CELL))
+        return set_err(c, PCR_E_ARG, "voxel cell of %d: the edge length is 1 .. %d (PCR_THIN_MAX_CELL)", vox->cell, PCR_THIN_MAX_CELL);
+    return PCR_OK;
+}
+
+// The last of a call's checks: a range of n batches holds at most max_rows rows (`limit` words it: 2^40 where rows are 64-bit, 2^32
+// where an index or a sum holds a 32-bit row)
+constexpr const char *ROWS_2_40 = "2^40 rows", *ROWS_2_32_INDEX = "2^32 rows (the index stores a 32-bit row)";
+int kept_row_limit(pcr_ctx *c, int64_t n, int64_t max_rows, const char *limit)
+{
+    if (n > max_rows / PCR_POINTS_PER_BATCH) return set_err(c, PCR_E_ARG, "a range of %lld batches has more than %s", (long long)n, limit);
+    return PCR_OK;
+}
+
+// After the plan: the count and the statistics out; *done unless something is left to write, which is not so for a count-only
+// call, without rows, or where `kept` rows (`noun` in the message) do not fit the capacity
+template <class Stats>
+int kept_finish(pcr_ctx *c, const KeptOut &o, int64_t kept, const char *noun, const Stats &st, int64_t *out_count, Stats *stats, bool *done)
+{
+    *done = true;
+    *out_count = kept;
+    if (stats) *stats = st;
+    if ((!o.points && !o.col[0].dst && !o.col[1].dst && !o.col[2].dst) || kept == 0) return PCR_OK;
+    if (o.capacity < (size_t)kept) return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld %s", o.capacity, (long long)kept, noun);
+    *done = false;
+    return PCR_OK;
+}
+
+// Where the write of some batches of a plan launches: a workgroup per writer among them, list[x] its batch and offsets[x] its
+// first output record
+struct EmitAt {
+    StreamView s;
+    dim3 grid, block;
+    const uint32_t *list;
+    const int64_t *offsets;
+};
+
+// The writers among batches [i0, i1) of the plan's range and the first output record of each, counted from the first of them, on
+// their way to the device. e.grid.x == 0: there is none.
+int emit_offsets(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, EmitAt &e)
+{
+    const size_t w0 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i0)) - p.writers.begin());
+    const size_t w1 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i1)) - p.writers.begin());
+    e = EmitAt{make_stream_view(c), dim3((unsigned)(w1 - w0)), dim3(PCR_WORKGROUP_SIZE), c->d_thin_wlist + w0, c->d_thin_offsets + w0};
+    if (w0 == w1) return PCR_OK;
+    p.offsets.clear();
+    int64_t off = 0;
+    for (size_t w = w0; w < w1; ++w) { p.offsets.push_back(off); off += p.cnt[w]; }
+    HIP_TRY(c, hipMemcpyAsync(c->d_thin_wlist + w0, p.writers.data() + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_thin_offsets + w0, p.offsets.data(), (w1 - w0) * 8, hipMemcpyHostToDevice, c->stream));
+    return PCR_OK;
+}
+
+// launch(layout, bc7) with the layout the selections read and the stream's colour format, each a std::integral_constant: the
+// template arguments of a kernel that decodes with colour
+template <class Launch>
+void for_layout_bc7(const pcr_ctx *c, Launch launch)
+{
+    using Windows = std::integral_constant<int, LAYOUT_POINT_WINDOWS>;
+    using Words = std::integral_constant<int, LAYOUT_WORDS>;
+    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
+    if (select_reads_windows(c)) { if (bc7) launch(Windows{}, std::true_type{}); else launch(Windows{}, std::false_type{}); }
+    else                         { if (bc7) launch(Words{}, std::true_type{}); else launch(Words{}, std::false_type{}); }
+}
+
+// Enqueue the writes of batches [i0, i1) of the plan's range: launch(layout, bc7, e) starts the call's write kernel at e. The
+// caller synchronises.
+template <class Launch>
+int kept_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, Launch launch)
+{
+    EmitAt e;
+    const int rc = emit_offsets(c, first, i0, i1, p, e);
+    if (rc || e.grid.x == 0) return rc;
+    for_layout_bc7(c, [&](auto layout, auto bc7) { launch(layout, bc7, e); });
+    HIP_TRY(c, hipGetLastError());
+    return PCR_OK;
+}
+
+// The device twin of a host description for `batches` batches of 65 536 rows: the points through d_decode_stage, column i through
+// d_col_stage[i], NULL where the host takes none. The name of the buffer there is no memory for, or NULL.
+const char *stage_reserve(pcr_ctx *c, const KeptOut &o, int64_t batches, KeptOut &d)
+{
+    d = o;
+    d.host = false;
+    if (o.points) {
+        if (!thin_grow((void **)&c->d_decode_stage, c->decode_stage_batches, batches, (size_t)PCR_POINTS_PER_BATCH * sizeof(pcr_point))) return "points";
+        d.points = c->d_decode_stage;
+    }
+    for (int i = 0; i < 3; ++i) {
+        if (!o.col[i].dst) continue;
+        if (!thin_grow(&c->d_col_stage[i], c->col_stage_bytes[i], batches * PCR_POINTS_PER_BATCH * (int64_t)o.col[i].row_bytes, 1)) return o.col[i].name;
+        d.col[i].dst = c->d_col_stage[i];
+    }
+    return nullptr;
+}
+
+// The first m rows of the stages d to rows [at, at + m) of the host destinations o. Synchronises.
+int stage_copy(pcr_ctx *c, const KeptOut &o, const KeptOut &d, int64_t at, int64_t m)
+{
+    if (d.points) HIP_TRY(c, hipMemcpyAsync(static_cast<pcr_point *>(o.points) + at, d.points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
+    for (int i = 0; i < 3; ++i) {
+        const size_t row_bytes = o.col[i].row_bytes;
+        if (d.col[i].dst)
+            HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(o.col[i].dst) + (size_t)at * row_bytes, d.col[i].dst, (size_t)m * row_bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+// The plan's rows to the destinations: emit(i0, i1, d) enqueues the writes of batches [i0, i1) to the device destinations d, each
+// holding the rows of those batches. On the device one emit into o itself; to the host in pieces through the stages. stage_named:
+// a stage that does not fit is reported by name. Synchronises.
+template <class Emit>
+int kept_write(pcr_ctx *c, int64_t first, int64_t n, const ThinPlan &p, const KeptOut &o, Emit emit, bool stage_named = false)
+{
+    int rc;
+    if (!o.host) {
+        if ((rc = emit(0, n, o))) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return PCR_OK;
+    }
+    // pieces of at most DECODE_STAGE_BATCHES batches: a batch keeps at most 65 536 records, so a piece fits the stages
+    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
+    KeptOut d;
+    if (const char *what = stage_reserve(c, o, piece, d))
+        return stage_named ? set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of %s", (long long)piece, what)
+                           : set_err(c, PCR_E_NOMEM, "out of device memory for the staging buffers of %lld batches", (long long)piece);
+    int64_t written = 0;
+    size_t w = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += piece) {
+        const int64_t i1 = std::min(n, i0 + piece);
+        int64_t m = 0;
+        for (; w < p.writers.size() && p.writers[w] < (uint32_t)(first + i1); ++w) m += p.cnt[w];
+        if (m == 0) continue;
+        if ((rc = emit(i0, i1, d)) || (rc = stage_copy(c, o, d, written, m))) return rc;
+        written += m;
+    }
+    return PCR_OK;
+}
+} // namespace
+} // extern "C++"
+
+// ---- voxel thinning ----------------------------------------------------------------------------
+namespace {
+// Phases one to three: the plan's first half, then fill the voxel table (k_thin_mark), flag the kept rows and count them per batch.
+// Synchronises.
+int thin_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const pcr_box *clip, int mode, ThinPlan &p)
+{
+    VoxelPlan v;
+    int rc = voxel_plan_begin(c, first, n, vox, clip, "thin", THIN_TABLE, 62, p, v);    // (2^40 rows: never more than 2^41 slots)
+    p.st = pcr_thin_stats{v.batches_outside, v.batches_decoded, v.points_considered, v.runs, 0, v.table_slots};
+    if (rc || v.runs == 0) return rc;
+    p.args = v.a;
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)v.nL), block(PCR_WORKGROUP_SIZE);
+#define PCR_LAUNCH(L, M) hipLaunchKernelGGL((k_thin_mark<L, M>), grid, block, 0, c->stream, s, c->d_thin_list, v.a)
+    if (v.windows) { if (mode == PCR_THIN_CENTER) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, PCR_THIN_CENTER); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, PCR_THIN_FIRST); }
+    else           { if (mode == PCR_THIN_CENTER) PCR_LAUNCH(LAYOUT_WORDS, PCR_THIN_CENTER); else PCR_LAUNCH(LAYOUT_WORDS, PCR_THIN_FIRST); }
+#undef PCR_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(k_thin_flag, dim3((unsigned)std::min<int64_t>((v.table_slots + 255) / 256, 4096)), dim3(256), 0, c->stream, c->d_thin_table,
+                       (unsigned long long)v.table_slots, (unsigned long long)n * PCR_POINTS_PER_BATCH, c->d_thin_keep);
+    HIP_TRY(c, hipGetLastError());
+    rc = voxel_plan_collect(c, first, p, v);
+    p.st.points_kept = v.points_written;
+    return rc;
+}
+
+// Enqueue the writes of batches [i0, i1) of the plan's range: their kept records to d.points, the rows to column 0 (device, either
+// may be NULL, each holds the records of those batches); for a plan of pcr_components the labels of the rows to column 1 as well
+// (NULL: not). The caller synchronises.
+int thin_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, const KeptOut &d)
+{
+    uint4 *const points = static_cast<uint4 *>(d.points);
+    int64_t *const rows = static_cast<int64_t *>(d.col[0].dst), *const labels = static_cast<int64_t *>(d.col[1].dst);
+    EmitAt e;
+    const int rc = emit_offsets(c, first, i0, i1, p, e);
+    if (rc || e.grid.x == 0) return rc;
+    if (points || rows) {
+        for_layout_bc7(c, [&](auto layout, auto bc7) {
+            hipLaunchKernelGGL((k_thin_write<layout.value, bc7.value>), e.grid, e.block, 0, c->stream, e.s, e.list, (uint32_t)first, c->d_thin_keep, e.offsets,
+                               points, rows);
+        });
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (labels) {
+        if (select_reads_windows(c))
+            hipLaunchKernelGGL((k_components_labels<LAYOUT_POINT_WINDOWS>), e.grid, e.block, 0, c->stream, e.s, e.list, p.args, c->d_thin_keep, e.offsets,
+                               p.label, labels);
+        else
+            hipLaunchKernelGGL((k_components_labels<LAYOUT_WORDS>), e.grid, e.block, 0, c->stream, e.s, e.list, p.args, c->d_thin_keep, e.offsets, p.label,
+                               labels);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return PCR_OK;
+}
+
+// kept_write for the three calls that write with thin_emit
+int thin_write(pcr_ctx *c, int64_t first, int64_t n, ThinPlan &p, const KeptOut &o)
+{
+    return kept_write(c, first, n, p, o, [&](int64_t i0, int64_t i1, const KeptOut &d) { return thin_emit(c, first, i0, i1, p, d); }, true);
+}
+
+// pcr_thin / pcr_read_thin
+int thin_call(pcr_ctx *c, int64_t first, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int mode, const KeptOut &o, int64_t *out_count,
+              pcr_thin_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = kept_begin(c, first, count, o, out_count, &n, true, vox);
+    if (rc) return rc;
+    if (mode != PCR_THIN_FIRST && mode != PCR_THIN_CENTER) return set_err(c, PCR_E_ARG, "mode is %d, not PCR_THIN_FIRST or PCR_THIN_CENTER", mode);
+    if (mode == PCR_THIN_CENTER && vox->cell > PCR_THIN_MAX_CENTER_CELL)
+        return set_err(c, PCR_E_ARG, "voxel cell of %d with PCR_THIN_CENTER: at most %d (PCR_THIN_MAX_CENTER_CELL)", vox->cell, PCR_THIN_MAX_CENTER_CELL);
+    if ((rc = kept_row_limit(c, n, (int64_t)1 << 40, ROWS_2_40)) || (rc = thin_plan(c, first, n, *vox, clip, mode, p))) return rc;
+    if ((rc = kept_finish(c, o, p.st.points_kept, "kept", p.st, out_count, stats, &done)) || done) return rc;
+    return thin_write(c, first, n, p, o);
+}
+} // namespace
+
+int pcr_thin(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int mode, void *dev_points, void *dev_rows,
+             size_t capacity_points, int64_t *out_count, pcr_thin_stats *stats)
+{
+    return thin_call(c, first_batch, count, vox, clip, mode, KeptOut{false, dev_points, capacity_points, {{"rows", dev_rows, 8}}}, out_count, stats);
+}
+
+int pcr_read_thin(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int mode, pcr_point *host_points,
+                  int64_t *host_rows, size_t capacity_points, int64_t *out_count, pcr_thin_stats *stats)
+{
+    return thin_call(c, first_batch, count, vox, clip, mode, KeptOut{true, host_points, capacity_points, {{"rows", host_rows, 8}}}, out_count, stats);
+}
+
+// ---- voxel denoising ---------------------------------------------------------------------------
+namespace {
+// The second half of a plan on the lattice of noise_lattice, after the call's own kernels have left their verdict in bit 63 of every
+// occupied slot's value: flag the rows on `mode`'s side of it (PCR_DENOISE_KEEP: bit clear), then the tail (voxel_plan_collect,
+// which copies the call's counters). Synchronises.
+int voxel_plan_finish(pcr_ctx *c, int64_t first, int mode, ThinPlan &p, VoxelPlan &v, void *dst, const void *src, size_t bytes)
+{
+    const ThinArgs &a = v.a;
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)v.nL), block(PCR_WORKGROUP_SIZE);
+    // (every lane of a listed batch stores its keep word, and only listed batches are read: the bitmap needs no clearing)
+#define PCR_LAUNCH(L, M) hipLaunchKernelGGL((k_denoise_flag<L, M>), grid, block, 0, c->stream, s, c->d_thin_list, a, c->d_thin_keep)
+    if (v.windows) { if (mode == PCR_DENOISE_ISOLATED) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, PCR_DENOISE_ISOLATED); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, PCR_DENOISE_KEEP); }
+    else           { if (mode == PCR_DENOISE_ISOLATED) PCR_LAUNCH(LAYOUT_WORDS, PCR_DENOISE_ISOLATED); else PCR_LAUNCH(LAYOUT_WORDS, PCR_DENOISE_KEEP); }
+#undef PCR_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    return voxel_plan_collect(c, first, p, v, dst, src, bytes);
+}
+
 // pcr_thin's phases with a sum in the table: classify, count the runs, count the candidates per voxel, decide per voxel, flag the
 // rows to write and count them per batch. Fills the plan thin_emit takes (p.st is not used) and st. Synchronises.
 int denoise_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, const pcr_box *clip, int64_t max_count, int mode, ThinPlan &p,
@@ -3088,7 +3158,7 @@ int denoise_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, co
 {
     st = pcr_denoise_stats{};
     VoxelPlan v;
-    int rc = voxel_plan_begin(c, first, n, vox, clip, "denoise", 62, p, v);
+    int rc = voxel_plan_begin(c, first, n, vox, clip, "denoise", NOISE_TABLE, 62, p, v);
     st.batches_outside = v.batches_outside; st.batches_decoded = v.batches_decoded; st.points_considered = v.points_considered; st.runs = v.runs;
     if (rc || v.runs == 0) return rc;
     if (!c->d_denoise_counters && hipMalloc((void **)&c->d_denoise_counters, 16) != hipSuccess)
@@ -3113,63 +3183,36 @@ int denoise_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox, co
     return PCR_OK;
 }
 
-// The checks and the plan shared by pcr_denoise / pcr_read_denoise. *done: nothing left to write (an error, a count-only call, no records).
-int denoise_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int64_t max_count, int mode, const void *points,
-                    size_t points_align, const void *rows, size_t rows_align, size_t capacity, int64_t *out_count, pcr_denoise_stats *stats, int64_t *n,
-                    ThinPlan &p, bool *done)
+// pcr_denoise / pcr_read_denoise
+int denoise_call(pcr_ctx *c, int64_t first, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int64_t max_count, int mode, const KeptOut &o,
+                 int64_t *out_count, pcr_denoise_stats *stats)
 {
-    *done = true;
-    if (out_count) *out_count = 0;
-    int rc = select_range(c, first, count, n);
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    pcr_denoise_stats st{};
+    int64_t n = 0;
+    bool done = true;
+    int rc = kept_begin(c, first, count, o, out_count, &n, true, vox);
     if (rc) return rc;
-    if (!vox) return set_err(c, PCR_E_ARG, "the voxel lattice is NULL");
-    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
-    if (points && reinterpret_cast<uintptr_t>(points) % points_align != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
-    if (rows && reinterpret_cast<uintptr_t>(rows) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the rows is misaligned (%zu bytes)", rows_align);
-    if (vox->cell < 1 || vox->cell > PCR_THIN_MAX_CELL)
-        return set_err(c, PCR_E_ARG, "voxel cell of %d: the edge length is 1 .. %d (PCR_THIN_MAX_CELL)", vox->cell, PCR_THIN_MAX_CELL);
     if (max_count < 0) return set_err(c, PCR_E_ARG, "max_count is %lld: 0 or more", (long long)max_count);
     if (mode != PCR_DENOISE_KEEP && mode != PCR_DENOISE_ISOLATED) return set_err(c, PCR_E_ARG, "mode is %d, not PCR_DENOISE_KEEP or PCR_DENOISE_ISOLATED", mode);
-    if (*n > ((int64_t)1 << 40) / PCR_POINTS_PER_BATCH) return set_err(c, PCR_E_ARG, "a range of %lld batches has more than 2^40 rows", (long long)*n);
-    pcr_denoise_stats st{};
-    if ((rc = denoise_plan(c, first, *n, *vox, clip, max_count, mode, p, st))) return rc;
-    *out_count = st.points_written;
-    if (stats) *stats = st;
-    if ((!points && !rows) || st.points_written == 0) return PCR_OK;
-    if (capacity < (size_t)st.points_written)
-        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld to write", capacity, (long long)st.points_written);
-    *done = false;
-    return PCR_OK;
+    if ((rc = kept_row_limit(c, n, (int64_t)1 << 40, ROWS_2_40)) || (rc = denoise_plan(c, first, n, *vox, clip, max_count, mode, p, st))) return rc;
+    if ((rc = kept_finish(c, o, st.points_written, "to write", st, out_count, stats, &done)) || done) return rc;
+    return thin_write(c, first, n, p, o);
 }
 } // namespace
 
 int pcr_denoise(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int64_t max_count, int mode, void *dev_points,
                 void *dev_rows, size_t capacity_points, int64_t *out_count, pcr_denoise_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ThinPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = denoise_prepare(c, first_batch, count, vox, clip, max_count, mode, dev_points, 16, dev_rows, 8, capacity_points, out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    if ((rc = thin_emit(c, first_batch, 0, n, p, static_cast<uint4 *>(dev_points), static_cast<int64_t *>(dev_rows)))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PCR_OK;
+    return denoise_call(c, first_batch, count, vox, clip, max_count, mode, KeptOut{false, dev_points, capacity_points, {{"rows", dev_rows, 8}}}, out_count, stats);
 }
 
 int pcr_read_denoise(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int64_t max_count, int mode,
                      pcr_point *host_points, int64_t *host_rows, size_t capacity_points, int64_t *out_count, pcr_denoise_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ThinPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = denoise_prepare(c, first_batch, count, vox, clip, max_count, mode, host_points, alignof(pcr_point), host_rows, alignof(int64_t), capacity_points,
-                             out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    return thin_read_pieces(c, first_batch, n, p, host_points, host_rows);
+    return denoise_call(c, first_batch, count, vox, clip, max_count, mode, KeptOut{true, host_points, capacity_points, {{"rows", host_rows, 8}}}, out_count, stats);
 }
 
 // ---- connected components -----------------------------------------------------------------------
@@ -3182,7 +3225,7 @@ int components_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox,
 {
     st = pcr_components_stats{};
     VoxelPlan v;
-    int rc = voxel_plan_begin(c, first, n, vox, clip, "label", 32, p, v);       // (the parent words are 32-bit)
+    int rc = voxel_plan_begin(c, first, n, vox, clip, "label", NOISE_TABLE, 32, p, v);       // (the parent words are 32-bit)
     st.batches_outside = v.batches_outside; st.batches_decoded = v.batches_decoded; st.points_considered = v.points_considered; st.runs = v.runs;
     if (rc || v.runs == 0) return rc;
     const int64_t slots = v.table_slots;
@@ -3223,68 +3266,41 @@ int components_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox,
     return PCR_OK;
 }
 
-// The checks and the plan shared by pcr_components / pcr_read_components. *done: nothing left to write (an error, a count-only call, no records).
-int components_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int connectivity, int64_t min_points, int mode,
-                       const void *points, size_t points_align, const void *rows, const void *labels, size_t rows_align, size_t capacity, int64_t *out_count,
-                       pcr_components_stats *stats, int64_t *n, ThinPlan &p, bool *done)
+// pcr_components / pcr_read_components
+int components_call(pcr_ctx *c, int64_t first, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int connectivity, int64_t min_points, int mode,
+                    const KeptOut &o, int64_t *out_count, pcr_components_stats *stats)
 {
-    *done = true;
-    if (out_count) *out_count = 0;
-    int rc = select_range(c, first, count, n);
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    pcr_components_stats st{};
+    int64_t n = 0;
+    bool done = true;
+    int rc = kept_begin(c, first, count, o, out_count, &n, true, vox);
     if (rc) return rc;
-    if (!vox) return set_err(c, PCR_E_ARG, "the voxel lattice is NULL");
-    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
-    if (points && reinterpret_cast<uintptr_t>(points) % points_align != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
-    if (rows && reinterpret_cast<uintptr_t>(rows) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the rows is misaligned (%zu bytes)", rows_align);
-    if (labels && reinterpret_cast<uintptr_t>(labels) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the labels is misaligned (%zu bytes)", rows_align);
-    if (vox->cell < 1 || vox->cell > PCR_THIN_MAX_CELL)
-        return set_err(c, PCR_E_ARG, "voxel cell of %d: the edge length is 1 .. %d (PCR_THIN_MAX_CELL)", vox->cell, PCR_THIN_MAX_CELL);
     if (connectivity != 6 && connectivity != 26) return set_err(c, PCR_E_ARG, "connectivity is %d, not 6 or 26", connectivity);
     if (min_points < 0) return set_err(c, PCR_E_ARG, "min_points is %lld: 0 or more", (long long)min_points);
     if (mode != PCR_COMPONENTS_KEEP && mode != PCR_COMPONENTS_SMALL) return set_err(c, PCR_E_ARG, "mode is %d, not PCR_COMPONENTS_KEEP or PCR_COMPONENTS_SMALL", mode);
-    if (*n > ((int64_t)1 << 40) / PCR_POINTS_PER_BATCH) return set_err(c, PCR_E_ARG, "a range of %lld batches has more than 2^40 rows", (long long)*n);
-    pcr_components_stats st{};
-    if ((rc = components_plan(c, first, *n, *vox, clip, connectivity, min_points, mode, p, st))) return rc;
-    *out_count = st.points_written;
-    if (stats) *stats = st;
-    if ((!points && !rows && !labels) || st.points_written == 0) return PCR_OK;
-    if (capacity < (size_t)st.points_written)
-        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld to write", capacity, (long long)st.points_written);
-    *done = false;
-    return PCR_OK;
+    if ((rc = kept_row_limit(c, n, (int64_t)1 << 40, ROWS_2_40)) || (rc = components_plan(c, first, n, *vox, clip, connectivity, min_points, mode, p, st)))
+        return rc;
+    if ((rc = kept_finish(c, o, st.points_written, "to write", st, out_count, stats, &done)) || done) return rc;
+    return thin_write(c, first, n, p, o);
 }
 } // namespace
 
 int pcr_components(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int connectivity, int64_t min_points, int mode,
                    void *dev_points, void *dev_rows, void *dev_labels, size_t capacity_points, int64_t *out_count, pcr_components_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ThinPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = components_prepare(c, first_batch, count, vox, clip, connectivity, min_points, mode, dev_points, 16, dev_rows, dev_labels, 8, capacity_points,
-                                out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    if ((rc = thin_emit(c, first_batch, 0, n, p, static_cast<uint4 *>(dev_points), static_cast<int64_t *>(dev_rows), static_cast<int64_t *>(dev_labels))))
-        return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PCR_OK;
+    return components_call(c, first_batch, count, vox, clip, connectivity, min_points, mode,
+                           KeptOut{false, dev_points, capacity_points, {{"rows", dev_rows, 8}, {"labels", dev_labels, 8}}}, out_count, stats);
 }
 
 int pcr_read_components(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, int connectivity, int64_t min_points,
                         int mode, pcr_point *host_points, int64_t *host_rows, int64_t *host_labels, size_t capacity_points, int64_t *out_count,
                         pcr_components_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ThinPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = components_prepare(c, first_batch, count, vox, clip, connectivity, min_points, mode, host_points, alignof(pcr_point), host_rows, host_labels,
-                                alignof(int64_t), capacity_points, out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    return thin_read_pieces(c, first_batch, n, p, host_points, host_rows, host_labels);
+    return components_call(c, first_batch, count, vox, clip, connectivity, min_points, mode,
+                           KeptOut{true, host_points, capacity_points, {{"rows", host_rows, 8}, {"labels", host_labels, 8}}}, out_count, stats);
 }
 
 // ---- radius neighbourhoods ----------------------------------------------------------------------
@@ -3304,7 +3320,7 @@ int neighbors_plan(pcr_ctx *c, int64_t first, int64_t n, int32_t radius, const p
     st = pcr_neighbors_stats{};
     VoxelPlan v;
     const pcr_voxels vox{{0, 0, 0}, radius};
-    int rc = voxel_plan_begin(c, first, n, vox, clip, "search", 32, p, v, "radius");      // (a work item holds a 32-bit slot)
+    int rc = voxel_plan_begin(c, first, n, vox, clip, "search", NOISE_TABLE, 32, p, v, "radius");      // (a work item holds a 32-bit slot)
     st.batches_outside = v.batches_outside; st.batches_decoded = v.batches_decoded; st.points_considered = v.points_considered; st.runs = v.runs;
     if (rc || v.runs == 0) return rc;
     const int64_t slots = v.table_slots, nL = v.nL;
@@ -3368,257 +3384,121 @@ int neighbors_plan(pcr_ctx *c, int64_t first, int64_t n, int32_t radius, const p
                                 mom->eigen ? c->d_moments_eigen : nullptr);
     else     hipLaunchKernelGGL(k_neighbors_pairs, per_item, dim3(256), 0, c->stream, g, (unsigned long long)items);
     HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(k_thin_totals, grid, dim3(256), 0, c->stream, c->d_thin_list, (uint32_t)first, c->d_thin_keep, c->d_thin_totals);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(v.totals.data(), c->d_thin_totals, (size_t)nL * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(v.totals.data() + nL * 2, c->d_thin_error, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(counters, c->d_neighbors_counters, sizeof counters, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (v.totals[(size_t)nL * 2]) return set_err(c, PCR_E_NOMEM, "voxel table overflow: %lld slots for %lld runs", (long long)slots, (long long)v.runs);
-    for (int64_t k = 0; k < nL; ++k) {
-        if (!v.totals[(size_t)k]) continue;
-        p.writers.push_back(p.listed[(size_t)k]); p.cnt.push_back(v.totals[(size_t)k]);
-        st.points_written += v.totals[(size_t)k];
-    }
+    if ((rc = voxel_plan_collect(c, first, p, v, counters, c->d_neighbors_counters, sizeof counters))) return rc;
+    st.points_written = v.points_written;
     st.voxels = (int64_t)counters[NEIGHBORS_VOXELS]; st.max_voxel_points = (int64_t)counters[NEIGHBORS_MAX_VOXEL];
     for (int k = 0; k < 64; ++k) { st.pairs_bound += (int64_t)counters[NEIGHBORS_PAIRS_BOUND + k]; st.points_sparse += (int64_t)counters[NEIGHBORS_SPARSE + k]; }
     return PCR_OK;
 }
 
-// thin_emit with two more outputs: the writes of batches [i0, i1) of the plan's range, any of the four NULL. The caller synchronises.
-int neighbors_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, uint4 *points, int64_t *rows, int64_t *counts, uint64_t *nn2)
+// The write of pcr_neighbors: the records, the rows (column 0) and, gathered from the dense arrays, N (1) and nn2 (2)
+int neighbors_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, const KeptOut &d)
 {
-    const size_t w0 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i0)) - p.writers.begin());
-    const size_t w1 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i1)) - p.writers.begin());
-    if (w0 == w1) return PCR_OK;
-    p.offsets.clear();
-    int64_t off = 0;
-    for (size_t w = w0; w < w1; ++w) { p.offsets.push_back(off); off += p.cnt[w]; }
-    HIP_TRY(c, hipMemcpyAsync(c->d_thin_wlist + w0, p.writers.data() + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_thin_offsets + w0, p.offsets.data(), (w1 - w0) * 8, hipMemcpyHostToDevice, c->stream));
-    const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)(w1 - w0)), block(PCR_WORKGROUP_SIZE);
-    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
-#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_neighbors_write<L, B>), grid, block, 0, c->stream, s, c->d_thin_wlist + w0, (uint32_t)first, c->d_thin_keep, \
-                                            c->d_thin_offsets + w0, c->d_neighbors_n, c->d_neighbors_nn2, points, rows, counts,                          \
-                                            reinterpret_cast<unsigned long long *>(nn2))
-    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
-    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
-#undef PCR_LAUNCH
-    HIP_TRY(c, hipGetLastError());
-    return PCR_OK;
+    return kept_emit(c, first, i0, i1, p, [&](auto layout, auto bc7, const EmitAt &e) {
+        hipLaunchKernelGGL((k_neighbors_write<layout.value, bc7.value>), e.grid, e.block, 0, c->stream, e.s, e.list, (uint32_t)first, c->d_thin_keep, e.offsets,
+                           c->d_neighbors_n, c->d_neighbors_nn2, static_cast<uint4 *>(d.points), static_cast<int64_t *>(d.col[0].dst),
+                           static_cast<int64_t *>(d.col[1].dst), static_cast<unsigned long long *>(d.col[2].dst));
+    });
 }
 
-// The checks and the plan shared by pcr_neighbors / pcr_read_neighbors. *done: nothing left to write (an error, a count-only call, no records).
-int neighbors_prepare(pcr_ctx *c, int64_t first, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count, int mode, const void *points,
-                      size_t points_align, const void *rows, const void *counts, const void *nn2, size_t rows_align, size_t capacity, int64_t *out_count,
-                      pcr_neighbors_stats *stats, int64_t *n, ThinPlan &p, bool *done)
+// pcr_neighbors / pcr_read_neighbors
+int neighbors_call(pcr_ctx *c, int64_t first, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count, int mode, const KeptOut &o,
+                   int64_t *out_count, pcr_neighbors_stats *stats)
 {
-    *done = true;
-    if (out_count) *out_count = 0;
-    int rc = select_range(c, first, count, n);
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    pcr_neighbors_stats st{};
+    int64_t n = 0;
+    bool done = true;
+    int rc = kept_begin(c, first, count, o, out_count, &n);
     if (rc) return rc;
-    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
-    if (points && reinterpret_cast<uintptr_t>(points) % points_align != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
-    if (rows && reinterpret_cast<uintptr_t>(rows) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the rows is misaligned (%zu bytes)", rows_align);
-    if (counts && reinterpret_cast<uintptr_t>(counts) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the counts is misaligned (%zu bytes)", rows_align);
-    if (nn2 && reinterpret_cast<uintptr_t>(nn2) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the nearest distances is misaligned (%zu bytes)", rows_align);
     if (radius < 1 || radius > PCR_NEIGHBORS_MAX_RADIUS)
         return set_err(c, PCR_E_ARG, "radius of %d: 1 .. %d stream units (PCR_NEIGHBORS_MAX_RADIUS)", radius, PCR_NEIGHBORS_MAX_RADIUS);
     if (min_count < 0) return set_err(c, PCR_E_ARG, "min_count is %lld: 0 or more", (long long)min_count);
     if (mode != PCR_NEIGHBORS_ALL && mode != PCR_NEIGHBORS_KEEP && mode != PCR_NEIGHBORS_SPARSE)
         return set_err(c, PCR_E_ARG, "mode is %d, not PCR_NEIGHBORS_ALL, PCR_NEIGHBORS_KEEP or PCR_NEIGHBORS_SPARSE", mode);
-    if (*n > ((int64_t)1 << 32) / PCR_POINTS_PER_BATCH)
-        return set_err(c, PCR_E_ARG, "a range of %lld batches has more than 2^32 rows (the index stores a 32-bit row)", (long long)*n);
-    pcr_neighbors_stats st{};
-    if ((rc = neighbors_plan(c, first, *n, radius, clip, min_count, mode, counts != nullptr, nn2 != nullptr, p, st))) return rc;
-    *out_count = st.points_written;
-    if (stats) *stats = st;
-    if ((!points && !rows && !counts && !nn2) || st.points_written == 0) return PCR_OK;
-    if (capacity < (size_t)st.points_written)
-        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld to write", capacity, (long long)st.points_written);
-    *done = false;
-    return PCR_OK;
+    if ((rc = kept_row_limit(c, n, (int64_t)1 << 32, ROWS_2_32_INDEX)) ||
+        (rc = neighbors_plan(c, first, n, radius, clip, min_count, mode, o.col[1].dst != nullptr, o.col[2].dst != nullptr, p, st)))
+        return rc;
+    if ((rc = kept_finish(c, o, st.points_written, "to write", st, out_count, stats, &done)) || done) return rc;
+    return kept_write(c, first, n, p, o, [&](int64_t i0, int64_t i1, const KeptOut &d) { return neighbors_emit(c, first, i0, i1, p, d); });
 }
 } // namespace
 
 int pcr_neighbors(pcr_ctx *c, int64_t first_batch, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count, int mode, void *dev_points,
                   void *dev_rows, void *dev_counts, void *dev_nn2, size_t capacity_points, int64_t *out_count, pcr_neighbors_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ThinPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = neighbors_prepare(c, first_batch, count, radius, clip, min_count, mode, dev_points, 16, dev_rows, dev_counts, dev_nn2, 8, capacity_points,
-                               out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    if ((rc = neighbors_emit(c, first_batch, 0, n, p, static_cast<uint4 *>(dev_points), static_cast<int64_t *>(dev_rows), static_cast<int64_t *>(dev_counts),
-                             static_cast<uint64_t *>(dev_nn2))))
-        return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PCR_OK;
+    return neighbors_call(c, first_batch, count, radius, clip, min_count, mode,
+                          KeptOut{false, dev_points, capacity_points, {{"rows", dev_rows, 8}, {"counts", dev_counts, 8}, {"nearest distances", dev_nn2, 8}}},
+                          out_count, stats);
 }
 
 int pcr_read_neighbors(pcr_ctx *c, int64_t first_batch, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count, int mode,
                        pcr_point *host_points, int64_t *host_rows, int64_t *host_counts, uint64_t *host_nn2, size_t capacity_points, int64_t *out_count,
                        pcr_neighbors_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ThinPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = neighbors_prepare(c, first_batch, count, radius, clip, min_count, mode, host_points, alignof(pcr_point), host_rows, host_counts, host_nn2,
-                               alignof(int64_t), capacity_points, out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    // thin_read_pieces with two more outputs: pieces of at most DECODE_STAGE_BATCHES batches through the staging buffers
-    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
-    const size_t per_batch = (size_t)PCR_POINTS_PER_BATCH;
-    if ((host_points && !thin_grow((void **)&c->d_decode_stage, c->decode_stage_batches, piece, per_batch * sizeof(pcr_point))) ||
-        (host_rows && !thin_grow((void **)&c->d_thin_rows_stage, c->thin_rows_stage_batches, piece, per_batch * sizeof(int64_t))) ||
-        (host_counts && !thin_grow((void **)&c->d_neighbors_counts_stage, c->neighbors_counts_stage_batches, piece, per_batch * sizeof(int64_t))) ||
-        (host_nn2 && !thin_grow((void **)&c->d_neighbors_nn2_stage, c->neighbors_nn2_stage_batches, piece, per_batch * sizeof(uint64_t))))
-        return set_err(c, PCR_E_NOMEM, "out of device memory for the staging buffers of %lld batches", (long long)piece);
-    uint4 *const d_points = host_points ? reinterpret_cast<uint4 *>(c->d_decode_stage) : nullptr;
-    int64_t *const d_rows = host_rows ? c->d_thin_rows_stage : nullptr;
-    int64_t *const d_counts = host_counts ? c->d_neighbors_counts_stage : nullptr;
-    uint64_t *const d_nn2 = host_nn2 ? c->d_neighbors_nn2_stage : nullptr;
-    int64_t written = 0;
-    size_t w = 0;
-    for (int64_t i0 = 0; i0 < n; i0 += piece) {
-        const int64_t i1 = std::min(n, i0 + piece);
-        int64_t m = 0;
-        for (; w < p.writers.size() && p.writers[w] < (uint32_t)(first_batch + i1); ++w) m += p.cnt[w];
-        if (m == 0) continue;
-        if ((rc = neighbors_emit(c, first_batch, i0, i1, p, d_points, d_rows, d_counts, d_nn2))) return rc;
-        if (d_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
-        if (d_rows) HIP_TRY(c, hipMemcpyAsync(host_rows + written, d_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        if (d_counts) HIP_TRY(c, hipMemcpyAsync(host_counts + written, d_counts, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        if (d_nn2) HIP_TRY(c, hipMemcpyAsync(host_nn2 + written, d_nn2, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        written += m;
-    }
-    return PCR_OK;
+    return neighbors_call(c, first_batch, count, radius, clip, min_count, mode,
+                          KeptOut{true, host_points, capacity_points, {{"rows", host_rows, 8}, {"counts", host_counts, 8}, {"nearest distances", host_nn2, 8}}},
+                          out_count, stats);
 }
 
 // ---- local moments ------------------------------------------------------------------------------
 namespace {
-// neighbors_emit with the 80- and 48-byte records: the writes of batches [i0, i1) of the plan's range, any of the four NULL. The
-// caller synchronises.
-int moments_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, uint4 *points, int64_t *rows, void *moments, void *eigen)
+// The write of pcr_local_moments: the records, the rows (column 0) and, gathered from the dense arrays, the 80-byte pcr_moments (1)
+// and the 48-byte pcr_eigen (2)
+int moments_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, const KeptOut &d)
 {
-    const size_t w0 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i0)) - p.writers.begin());
-    const size_t w1 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i1)) - p.writers.begin());
-    if (w0 == w1) return PCR_OK;
-    p.offsets.clear();
-    int64_t off = 0;
-    for (size_t w = w0; w < w1; ++w) { p.offsets.push_back(off); off += p.cnt[w]; }
-    HIP_TRY(c, hipMemcpyAsync(c->d_thin_wlist + w0, p.writers.data() + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_thin_offsets + w0, p.offsets.data(), (w1 - w0) * 8, hipMemcpyHostToDevice, c->stream));
-    const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)(w1 - w0)), block(PCR_WORKGROUP_SIZE);
-    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
-#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_moments_write<L, B>), grid, block, 0, c->stream, s, c->d_thin_wlist + w0, (uint32_t)first, c->d_thin_keep, \
-                                            c->d_thin_offsets + w0, reinterpret_cast<const unsigned long long *>(c->d_moments_dense),                     \
-                                            reinterpret_cast<const unsigned long long *>(c->d_moments_eigen), points, rows,                               \
-                                            static_cast<unsigned long long *>(moments), static_cast<unsigned long long *>(eigen))
-    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
-    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
-#undef PCR_LAUNCH
-    HIP_TRY(c, hipGetLastError());
-    return PCR_OK;
+    return kept_emit(c, first, i0, i1, p, [&](auto layout, auto bc7, const EmitAt &e) {
+        hipLaunchKernelGGL((k_moments_write<layout.value, bc7.value>), e.grid, e.block, 0, c->stream, e.s, e.list, (uint32_t)first, c->d_thin_keep, e.offsets,
+                           reinterpret_cast<const unsigned long long *>(c->d_moments_dense), reinterpret_cast<const unsigned long long *>(c->d_moments_eigen),
+                           static_cast<uint4 *>(d.points), static_cast<int64_t *>(d.col[0].dst), static_cast<unsigned long long *>(d.col[1].dst),
+                           static_cast<unsigned long long *>(d.col[2].dst));
+    });
 }
 
-// The checks and the plan shared by pcr_local_moments / pcr_read_local_moments: neighbors_prepare's, with the radius limit of the
-// exact sums. *done: nothing left to write (an error, a count-only call, no records).
-int moments_prepare(pcr_ctx *c, int64_t first, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count, const void *points,
-                    size_t points_align, const void *rows, const void *moments, const void *eigen, size_t rows_align, size_t capacity, int64_t *out_count,
-                    pcr_neighbors_stats *stats, int64_t *n, ThinPlan &p, bool *done)
+// pcr_local_moments / pcr_read_local_moments: pcr_neighbors' checks with the radius limit of the exact sums, its plan with
+// k_moments_pairs
+int moments_call(pcr_ctx *c, int64_t first, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count, const KeptOut &o, int64_t *out_count,
+                 pcr_neighbors_stats *stats)
 {
-    *done = true;
-    if (out_count) *out_count = 0;
-    int rc = select_range(c, first, count, n);
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    pcr_neighbors_stats st{};
+    int64_t n = 0;
+    bool done = true;
+    int rc = kept_begin(c, first, count, o, out_count, &n);
     if (rc) return rc;
-    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
-    if (points && reinterpret_cast<uintptr_t>(points) % points_align != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
-    if (rows && reinterpret_cast<uintptr_t>(rows) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the rows is misaligned (%zu bytes)", rows_align);
-    if (moments && reinterpret_cast<uintptr_t>(moments) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the moments is misaligned (%zu bytes)", rows_align);
-    if (eigen && reinterpret_cast<uintptr_t>(eigen) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the eigen records is misaligned (%zu bytes)", rows_align);
     if (radius < 1 || radius > PCR_MOMENTS_MAX_RADIUS)
         return set_err(c, PCR_E_ARG, "radius of %d: 1 .. %d stream units (PCR_MOMENTS_MAX_RADIUS: the sums stay exact in 64 bits)", radius, PCR_MOMENTS_MAX_RADIUS);
     if (min_count < 0) return set_err(c, PCR_E_ARG, "min_count is %lld: 0 or more", (long long)min_count);
-    if (*n > ((int64_t)1 << 32) / PCR_POINTS_PER_BATCH)
-        return set_err(c, PCR_E_ARG, "a range of %lld batches has more than 2^32 rows (the index stores a 32-bit row)", (long long)*n);
-    pcr_neighbors_stats st{};
-    const MomentsWant want{moments != nullptr, eigen != nullptr};
-    if ((rc = neighbors_plan(c, first, *n, radius, clip, min_count, PCR_NEIGHBORS_ALL, false, false, p, st, &want))) return rc;
-    *out_count = st.points_written;
-    if (stats) *stats = st;
-    if ((!points && !rows && !moments && !eigen) || st.points_written == 0) return PCR_OK;
-    if (capacity < (size_t)st.points_written)
-        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld to write", capacity, (long long)st.points_written);
-    *done = false;
-    return PCR_OK;
+    const MomentsWant want{o.col[1].dst != nullptr, o.col[2].dst != nullptr};
+    if ((rc = kept_row_limit(c, n, (int64_t)1 << 32, ROWS_2_32_INDEX)) ||
+        (rc = neighbors_plan(c, first, n, radius, clip, min_count, PCR_NEIGHBORS_ALL, false, false, p, st, &want)))
+        return rc;
+    if ((rc = kept_finish(c, o, st.points_written, "to write", st, out_count, stats, &done)) || done) return rc;
+    return kept_write(c, first, n, p, o, [&](int64_t i0, int64_t i1, const KeptOut &d) { return moments_emit(c, first, i0, i1, p, d); });
 }
 } // namespace
 
 int pcr_local_moments(pcr_ctx *c, int64_t first_batch, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count, void *dev_points,
                       void *dev_rows, void *dev_moments, void *dev_eigen, size_t capacity_points, int64_t *out_count, pcr_neighbors_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ThinPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = moments_prepare(c, first_batch, count, radius, clip, min_count, dev_points, 16, dev_rows, dev_moments, dev_eigen, 8, capacity_points, out_count,
-                             stats, &n, p, &done);
-    if (rc || done) return rc;
-    if ((rc = moments_emit(c, first_batch, 0, n, p, static_cast<uint4 *>(dev_points), static_cast<int64_t *>(dev_rows), dev_moments, dev_eigen))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PCR_OK;
+    return moments_call(c, first_batch, count, radius, clip, min_count,
+                        KeptOut{false, dev_points, capacity_points,
+                                {{"rows", dev_rows, 8}, {"moments", dev_moments, sizeof(pcr_moments)}, {"eigen records", dev_eigen, sizeof(pcr_eigen)}}},
+                        out_count, stats);
 }
 
 int pcr_read_local_moments(pcr_ctx *c, int64_t first_batch, int64_t count, int32_t radius, const pcr_box *clip, int64_t min_count, pcr_point *host_points,
                            int64_t *host_rows, pcr_moments *host_moments, pcr_eigen *host_eigen, size_t capacity_points, int64_t *out_count,
                            pcr_neighbors_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ThinPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = moments_prepare(c, first_batch, count, radius, clip, min_count, host_points, alignof(pcr_point), host_rows, host_moments, host_eigen,
-                             alignof(int64_t), capacity_points, out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    // pcr_read_neighbors' pieces: at most DECODE_STAGE_BATCHES batches at a time through the staging buffers
-    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
-    const size_t per_batch = (size_t)PCR_POINTS_PER_BATCH;
-    if ((host_points && !thin_grow((void **)&c->d_decode_stage, c->decode_stage_batches, piece, per_batch * sizeof(pcr_point))) ||
-        (host_rows && !thin_grow((void **)&c->d_thin_rows_stage, c->thin_rows_stage_batches, piece, per_batch * sizeof(int64_t))) ||
-        (host_moments && !thin_grow((void **)&c->d_moments_stage, c->moments_stage_batches, piece, per_batch * sizeof(pcr_moments))) ||
-        (host_eigen && !thin_grow((void **)&c->d_moments_eigen_stage, c->moments_eigen_stage_batches, piece, per_batch * sizeof(pcr_eigen))))
-        return set_err(c, PCR_E_NOMEM, "out of device memory for the staging buffers of %lld batches", (long long)piece);
-    uint4 *const d_points = host_points ? reinterpret_cast<uint4 *>(c->d_decode_stage) : nullptr;
-    int64_t *const d_rows = host_rows ? c->d_thin_rows_stage : nullptr;
-    pcr_moments *const d_moments = host_moments ? c->d_moments_stage : nullptr;
-    pcr_eigen *const d_eigen = host_eigen ? c->d_moments_eigen_stage : nullptr;
-    int64_t written = 0;
-    size_t w = 0;
-    for (int64_t i0 = 0; i0 < n; i0 += piece) {
-        const int64_t i1 = std::min(n, i0 + piece);
-        int64_t m = 0;
-        for (; w < p.writers.size() && p.writers[w] < (uint32_t)(first_batch + i1); ++w) m += p.cnt[w];
-        if (m == 0) continue;
-        if ((rc = moments_emit(c, first_batch, i0, i1, p, d_points, d_rows, d_moments, d_eigen))) return rc;
-        if (d_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
-        if (d_rows) HIP_TRY(c, hipMemcpyAsync(host_rows + written, d_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        if (d_moments) HIP_TRY(c, hipMemcpyAsync(host_moments + written, d_moments, (size_t)m * sizeof(pcr_moments), hipMemcpyDeviceToHost, c->stream));
-        if (d_eigen) HIP_TRY(c, hipMemcpyAsync(host_eigen + written, d_eigen, (size_t)m * sizeof(pcr_eigen), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        written += m;
-    }
-    return PCR_OK;
+    return moments_call(c, first_batch, count, radius, clip, min_count,
+                        KeptOut{true, host_points, capacity_points,
+                                {{"rows", host_rows, 8}, {"moments", host_moments, sizeof(pcr_moments)}, {"eigen records", host_eigen, sizeof(pcr_eigen)}}},
+                        out_count, stats);
 }
 
 int pcr_moments_eigen(pcr_ctx *c, const void *dev_moments, int64_t n, void *dev_eigen)
@@ -3643,188 +3523,95 @@ int pcr_moments_eigen(pcr_ctx *c, const void *dev_moments, int64_t n, void *dev_
 
 // ---- k nearest neighbours -----------------------------------------------------------------------
 namespace {
-// neighbors_emit with the k words per row: the writes of batches [i0, i1) of the plan's range, any of the three NULL. The caller
-// synchronises.
-int knn_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, int k, uint4 *points, int64_t *rows, uint64_t *knn)
+// The write of pcr_knn: the records, the rows (column 0) and, gathered from the dense array, the k words of every row (1)
+int knn_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, int k, const KeptOut &d)
 {
-    const size_t w0 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i0)) - p.writers.begin());
-    const size_t w1 = (size_t)(std::lower_bound(p.writers.begin(), p.writers.end(), (uint32_t)(first + i1)) - p.writers.begin());
-    if (w0 == w1) return PCR_OK;
-    p.offsets.clear();
-    int64_t off = 0;
-    for (size_t w = w0; w < w1; ++w) { p.offsets.push_back(off); off += p.cnt[w]; }
-    HIP_TRY(c, hipMemcpyAsync(c->d_thin_wlist + w0, p.writers.data() + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_thin_offsets + w0, p.offsets.data(), (w1 - w0) * 8, hipMemcpyHostToDevice, c->stream));
-    const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)(w1 - w0)), block(PCR_WORKGROUP_SIZE);
-    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
-#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_knn_write<L, B>), grid, block, 0, c->stream, s, c->d_thin_wlist + w0, (uint32_t)first, c->d_thin_keep, \
-                                            c->d_thin_offsets + w0, c->d_knn_dense, k, points, rows, reinterpret_cast<unsigned long long *>(knn))
-    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
-    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
-#undef PCR_LAUNCH
-    HIP_TRY(c, hipGetLastError());
-    return PCR_OK;
+    return kept_emit(c, first, i0, i1, p, [&](auto layout, auto bc7, const EmitAt &e) {
+        hipLaunchKernelGGL((k_knn_write<layout.value, bc7.value>), e.grid, e.block, 0, c->stream, e.s, e.list, (uint32_t)first, c->d_thin_keep, e.offsets,
+                           c->d_knn_dense, k, static_cast<uint4 *>(d.points), static_cast<int64_t *>(d.col[0].dst),
+                           static_cast<unsigned long long *>(d.col[1].dst));
+    });
 }
 
-// The checks and the plan shared by pcr_knn / pcr_read_knn: neighbors_prepare's, with the limits of the 64-bit word. With min_found
+// pcr_knn / pcr_read_knn: pcr_neighbors' checks with the limits of the 64-bit word, its plan with k_knn_pairs<K>. With min_found
 // == 0 and no words asked for every candidate is kept whatever the pair kernel finds; it runs all the same, and pairs_bound comes
-// from it as in every other call. *done: nothing left to write (an error, a count-only call, no records).
-int knn_prepare(pcr_ctx *c, int64_t first, int64_t count, int k, int32_t radius, const pcr_box *clip, int64_t min_found, const void *points,
-                size_t points_align, const void *rows, const void *knn, size_t rows_align, size_t capacity, int64_t *out_count, pcr_neighbors_stats *stats,
-                int64_t *n, ThinPlan &p, bool *done)
-{
-    *done = true;
-    if (out_count) *out_count = 0;
-    int rc = select_range(c, first, count, n);
-    if (rc) return rc;
-    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
-    if (points && reinterpret_cast<uintptr_t>(points) % points_align != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
-    if (rows && reinterpret_cast<uintptr_t>(rows) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the rows is misaligned (%zu bytes)", rows_align);
-    if (knn && reinterpret_cast<uintptr_t>(knn) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the neighbours is misaligned (%zu bytes)", rows_align);
-    if (k < 1 || k > PCR_KNN_MAX_K) return set_err(c, PCR_E_ARG, "k of %d: 1 .. %d (PCR_KNN_MAX_K)", k, PCR_KNN_MAX_K);
-    if (radius < 1 || radius > PCR_KNN_MAX_RADIUS)
-        return set_err(c, PCR_E_ARG, "radius of %d: 1 .. %d stream units (PCR_KNN_MAX_RADIUS: a squared distance and a row share 64 bits)", radius, PCR_KNN_MAX_RADIUS);
-    if (min_found < 0 || min_found > k) return set_err(c, PCR_E_ARG, "min_found is %lld: 0 .. k = %d", (long long)min_found, k);
-    if (*n > ((int64_t)1 << 32) / PCR_POINTS_PER_BATCH)
-        return set_err(c, PCR_E_ARG, "a range of %lld batches has more than 2^32 rows (the index stores a 32-bit row)", (long long)*n);
-    pcr_neighbors_stats st{};
-    const KnnWant want{k, knn != nullptr};
-    if ((rc = neighbors_plan(c, first, *n, radius, clip, min_found, PCR_NEIGHBORS_ALL, false, false, p, st, nullptr, &want))) return rc;
-    *out_count = st.points_written;
-    if (stats) *stats = st;
-    if ((!points && !rows && !knn) || st.points_written == 0) return PCR_OK;
-    if (capacity < (size_t)st.points_written)
-        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld to write", capacity, (long long)st.points_written);
-    *done = false;
-    return PCR_OK;
-}
-} // namespace
-
-int pcr_knn(pcr_ctx *c, int64_t first_batch, int64_t count, int k, int32_t radius, const pcr_box *clip, int64_t min_found, void *dev_points, void *dev_rows,
-            void *dev_knn, size_t capacity_points, int64_t *out_count, pcr_neighbors_stats *stats)
+// from it as in every other call.
+int knn_call(pcr_ctx *c, int64_t first, int64_t count, int k, int32_t radius, const pcr_box *clip, int64_t min_found, const KeptOut &o, int64_t *out_count,
+             pcr_neighbors_stats *stats)
 {
     if (!c) return PCR_E_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     ThinPlan p;
+    pcr_neighbors_stats st{};
     int64_t n = 0;
     bool done = true;
-    int rc = knn_prepare(c, first_batch, count, k, radius, clip, min_found, dev_points, 16, dev_rows, dev_knn, 8, capacity_points, out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    if ((rc = knn_emit(c, first_batch, 0, n, p, k, static_cast<uint4 *>(dev_points), static_cast<int64_t *>(dev_rows), static_cast<uint64_t *>(dev_knn)))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PCR_OK;
+    int rc = kept_begin(c, first, count, o, out_count, &n);
+    if (rc) return rc;
+    if (k < 1 || k > PCR_KNN_MAX_K) return set_err(c, PCR_E_ARG, "k of %d: 1 .. %d (PCR_KNN_MAX_K)", k, PCR_KNN_MAX_K);
+    if (radius < 1 || radius > PCR_KNN_MAX_RADIUS)
+        return set_err(c, PCR_E_ARG, "radius of %d: 1 .. %d stream units (PCR_KNN_MAX_RADIUS: a squared distance and a row share 64 bits)", radius, PCR_KNN_MAX_RADIUS);
+    if (min_found < 0 || min_found > k) return set_err(c, PCR_E_ARG, "min_found is %lld: 0 .. k = %d", (long long)min_found, k);
+    const KnnWant want{k, o.col[1].dst != nullptr};
+    if ((rc = kept_row_limit(c, n, (int64_t)1 << 32, ROWS_2_32_INDEX)) ||
+        (rc = neighbors_plan(c, first, n, radius, clip, min_found, PCR_NEIGHBORS_ALL, false, false, p, st, nullptr, &want)))
+        return rc;
+    if ((rc = kept_finish(c, o, st.points_written, "to write", st, out_count, stats, &done)) || done) return rc;
+    return kept_write(c, first, n, p, o, [&](int64_t i0, int64_t i1, const KeptOut &d) { return knn_emit(c, first, i0, i1, p, k, d); });
+}
+} // namespace
+
+// (a row of the words column is k words: only a k that knn_call accepts reaches the stages)
+int pcr_knn(pcr_ctx *c, int64_t first_batch, int64_t count, int k, int32_t radius, const pcr_box *clip, int64_t min_found, void *dev_points, void *dev_rows,
+            void *dev_knn, size_t capacity_points, int64_t *out_count, pcr_neighbors_stats *stats)
+{
+    return knn_call(c, first_batch, count, k, radius, clip, min_found,
+                    KeptOut{false, dev_points, capacity_points, {{"rows", dev_rows, 8}, {"neighbours", dev_knn, (size_t)k * 8}}}, out_count, stats);
 }
 
 int pcr_read_knn(pcr_ctx *c, int64_t first_batch, int64_t count, int k, int32_t radius, const pcr_box *clip, int64_t min_found, pcr_point *host_points,
                  int64_t *host_rows, uint64_t *host_knn, size_t capacity_points, int64_t *out_count, pcr_neighbors_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ThinPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = knn_prepare(c, first_batch, count, k, radius, clip, min_found, host_points, alignof(pcr_point), host_rows, host_knn, alignof(int64_t),
-                         capacity_points, out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    // pcr_read_local_moments' pieces: at most DECODE_STAGE_BATCHES batches at a time through the staging buffers
-    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
-    const size_t per_batch = (size_t)PCR_POINTS_PER_BATCH;
-    if ((host_points && !thin_grow((void **)&c->d_decode_stage, c->decode_stage_batches, piece, per_batch * sizeof(pcr_point))) ||
-        (host_rows && !thin_grow((void **)&c->d_thin_rows_stage, c->thin_rows_stage_batches, piece, per_batch * sizeof(int64_t))) ||
-        (host_knn && !thin_grow((void **)&c->d_knn_stage, c->knn_stage_words, piece * PCR_POINTS_PER_BATCH * k, sizeof(uint64_t))))
-        return set_err(c, PCR_E_NOMEM, "out of device memory for the staging buffers of %lld batches", (long long)piece);
-    uint4 *const d_points = host_points ? reinterpret_cast<uint4 *>(c->d_decode_stage) : nullptr;
-    int64_t *const d_rows = host_rows ? c->d_thin_rows_stage : nullptr;
-    uint64_t *const d_knn = host_knn ? c->d_knn_stage : nullptr;
-    int64_t written = 0;
-    size_t w = 0;
-    for (int64_t i0 = 0; i0 < n; i0 += piece) {
-        const int64_t i1 = std::min(n, i0 + piece);
-        int64_t m = 0;
-        for (; w < p.writers.size() && p.writers[w] < (uint32_t)(first_batch + i1); ++w) m += p.cnt[w];
-        if (m == 0) continue;
-        if ((rc = knn_emit(c, first_batch, i0, i1, p, k, d_points, d_rows, d_knn))) return rc;
-        if (d_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
-        if (d_rows) HIP_TRY(c, hipMemcpyAsync(host_rows + written, d_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        if (d_knn) HIP_TRY(c, hipMemcpyAsync(host_knn + written * k, d_knn, (size_t)m * (size_t)k * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        written += m;
-    }
-    return PCR_OK;
+    return knn_call(c, first_batch, count, k, radius, clip, min_found,
+                    KeptOut{true, host_points, capacity_points, {{"rows", host_rows, 8}, {"neighbours", host_knn, (size_t)k * 8}}}, out_count, stats);
 }
 
 // ---- voxel means -------------------------------------------------------------------------------
 namespace {
-// The checks and the plan shared by pcr_voxel_mean / pcr_read_voxel_mean: pcr_thin's FIRST plan, unchanged. *done: nothing left to
-// write (an error, a count-only call, no records).
-int voxel_mean_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_voxels *vox, const pcr_box *clip, const void *points, size_t points_align,
-                       const void *rows, const void *counts, size_t rows_align, size_t capacity, int64_t *out_count, pcr_thin_stats *stats, int64_t *n,
-                       ThinPlan &p, bool *done)
-{
-    *done = true;
-    if (out_count) *out_count = 0;
-    int rc = select_range(c, first, count, n);
-    if (rc) return rc;
-    if (!vox) return set_err(c, PCR_E_ARG, "the voxel lattice is NULL");
-    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
-    if (points && reinterpret_cast<uintptr_t>(points) % points_align != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
-    if (rows && reinterpret_cast<uintptr_t>(rows) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the rows is misaligned (%zu bytes)", rows_align);
-    if (counts && reinterpret_cast<uintptr_t>(counts) % rows_align != 0) return set_err(c, PCR_E_ARG, "the destination of the counts is misaligned (%zu bytes)", rows_align);
-    if (vox->cell < 1 || vox->cell > PCR_THIN_MAX_CELL)
-        return set_err(c, PCR_E_ARG, "voxel cell of %d: the edge length is 1 .. %d (PCR_THIN_MAX_CELL)", vox->cell, PCR_THIN_MAX_CELL);
-    if (*n > PCR_VOXEL_MEAN_MAX_ROWS / PCR_POINTS_PER_BATCH)
-        return set_err(c, PCR_E_ARG, "a range of %lld batches has more than 2^32 rows (the 64-bit sums of a voxel are exact up to there): pass a shorter range",
-                       (long long)*n);
-    if ((rc = thin_plan(c, first, *n, *vox, clip, PCR_THIN_FIRST, p))) return rc;
-    *out_count = p.st.points_kept;
-    if (stats) *stats = p.st;
-    if ((!points && !rows && !counts) || p.st.points_kept == 0) return PCR_OK;
-    if (capacity < (size_t)p.st.points_kept)
-        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld voxels", capacity, (long long)p.st.points_kept);
-    *done = false;
-    return PCR_OK;
-}
-
 // After thin_plan: the record index of every voxel into its slot, (key, row) of every record, and the sums of every voxel into
 // its accumulator. Enqueues only; the error word (zero after thin_plan) is read by voxel_mean_check.
 int voxel_mean_sums(pcr_ctx *c, int64_t first, int64_t n, ThinPlan &p)
 {
     const int64_t records = p.st.points_kept, slots = p.st.table_slots;
-    const int64_t nL = (int64_t)p.listed.size(), nW = (int64_t)p.writers.size();
     if (!thin_grow((void **)&c->d_voxel_prefix, c->voxel_prefix_words, n * PCR_WORKGROUP_SIZE, 8))
         return set_err(c, PCR_E_NOMEM, "out of device memory for the record index of %lld batches: pass a shorter range", (long long)n);
     if (!thin_grow((void **)&c->d_voxel_acc, c->voxel_acc_records, records, VOXEL_ACC_WORDS * 8) ||
         !thin_grow((void **)&c->d_voxel_rec, c->voxel_rec_records, records, sizeof(VoxelRec)))
         return set_err(c, PCR_E_NOMEM, "out of device memory for the sums of %lld voxels (80 bytes each): pass a clip or a larger cell", (long long)records);
-    p.offsets.clear();
-    int64_t off = 0;
-    for (int64_t w = 0; w < nW; ++w) { p.offsets.push_back(off); off += p.cnt[(size_t)w]; }
-    HIP_TRY(c, hipMemcpyAsync(c->d_thin_wlist, p.writers.data(), (size_t)nW * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_thin_offsets, p.offsets.data(), (size_t)nW * 8, hipMemcpyHostToDevice, c->stream));
+    EmitAt e;                                       // every writer of the range: there is one, records > 0
+    const int rc = emit_offsets(c, first, 0, n, p, e);
+    if (rc) return rc;
     HIP_TRY(c, hipMemsetAsync(c->d_voxel_acc, 0, (size_t)records * VOXEL_ACC_WORDS * 8, c->stream));
-    hipLaunchKernelGGL(k_voxel_prefix, dim3((unsigned)nW), dim3(PCR_WORKGROUP_SIZE), 0, c->stream, c->d_thin_wlist, (uint32_t)first, c->d_thin_keep,
-                       c->d_thin_offsets, c->d_voxel_prefix);
+    hipLaunchKernelGGL(k_voxel_prefix, e.grid, e.block, 0, c->stream, e.list, (uint32_t)first, c->d_thin_keep, e.offsets, c->d_voxel_prefix);
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(k_voxel_index, dim3((unsigned)std::min<int64_t>((slots + 255) / 256, 4096)), dim3(256), 0, c->stream, c->d_thin_table,
                        (unsigned long long)slots, c->d_thin_keep, c->d_voxel_prefix, (unsigned long long)records, c->d_voxel_rec, c->d_thin_error);
     HIP_TRY(c, hipGetLastError());
-    const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)nL), block(PCR_WORKGROUP_SIZE);
-    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
-#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_voxel_sum<L, B>), grid, block, 0, c->stream, s, c->d_thin_list, p.args, (unsigned long long)records, c->d_voxel_acc)
-    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
-    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
-#undef PCR_LAUNCH
+    const dim3 grid((unsigned)p.listed.size());
+    for_layout_bc7(c, [&](auto layout, auto bc7) {
+        hipLaunchKernelGGL((k_voxel_sum<layout.value, bc7.value>), grid, e.block, 0, c->stream, e.s, c->d_thin_list, p.args, (unsigned long long)records,
+                           c->d_voxel_acc);
+    });
     HIP_TRY(c, hipGetLastError());
     return PCR_OK;
 }
 
-// Enqueue the roundings and stores of records [i0, i1) (device destinations of i1 - i0 records, any may be NULL)
-int voxel_mean_emit(pcr_ctx *c, const ThinPlan &p, int64_t i0, int64_t i1, uint4 *points, int64_t *rows, int64_t *counts)
+// Enqueue the roundings and stores of records [i0, i1): the points, the rows (column 0) and the counts (1) to device destinations
+// of i1 - i0 records, any may be NULL
+int voxel_mean_emit(pcr_ctx *c, const ThinPlan &p, int64_t i0, int64_t i1, const KeptOut &d)
 {
     hipLaunchKernelGGL(k_voxel_finish, dim3((unsigned)std::min<int64_t>((i1 - i0 + 255) / 256, 4096)), dim3(256), 0, c->stream, p.args.lat, c->d_voxel_acc,
-                       c->d_voxel_rec, (unsigned long long)i0, (unsigned long long)i1, points, rows, counts, c->d_thin_error);
+                       c->d_voxel_rec, (unsigned long long)i0, (unsigned long long)i1, static_cast<uint4 *>(d.points), static_cast<int64_t *>(d.col[0].dst),
+                       static_cast<int64_t *>(d.col[1].dst), c->d_thin_error);
     HIP_TRY(c, hipGetLastError());
     return PCR_OK;
 }
@@ -3838,57 +3625,53 @@ int voxel_mean_check(pcr_ctx *c)
     if (error) return set_err(c, PCR_E_NOMEM, "voxel table and record index disagree");
     return PCR_OK;
 }
+
+// pcr_voxel_mean / pcr_read_voxel_mean: pcr_thin's FIRST plan, unchanged, then the sums and one computed record per voxel. The
+// records are not rows of batches, so the host form walks them in pieces of its own, through the same stages.
+int voxel_mean_call(pcr_ctx *c, int64_t first, int64_t count, const pcr_voxels *vox, const pcr_box *clip, const KeptOut &o, int64_t *out_count,
+                    pcr_thin_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ThinPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = kept_begin(c, first, count, o, out_count, &n, true, vox);
+    if (rc) return rc;
+    if ((rc = kept_row_limit(c, n, PCR_VOXEL_MEAN_MAX_ROWS, "2^32 rows (the 64-bit sums of a voxel are exact up to there): pass a shorter range")) ||
+        (rc = thin_plan(c, first, n, *vox, clip, PCR_THIN_FIRST, p)))
+        return rc;
+    if ((rc = kept_finish(c, o, p.st.points_kept, "voxels", p.st, out_count, stats, &done)) || done) return rc;
+    const int64_t records = p.st.points_kept;
+    KeptOut d = o;
+    int64_t piece = records;                        // on the device: all at once
+    if (o.host) {
+        // pieces of at most DECODE_STAGE_BATCHES * 65 536 records through the stages
+        const int64_t piece_batches = std::min<int64_t>((records + PCR_POINTS_PER_BATCH - 1) / PCR_POINTS_PER_BATCH, DECODE_STAGE_BATCHES);
+        piece = piece_batches * PCR_POINTS_PER_BATCH;
+        if (stage_reserve(c, o, piece_batches, d)) return set_err(c, PCR_E_NOMEM, "out of device memory for the staging buffers of %lld records", (long long)piece);
+    }
+    if ((rc = voxel_mean_sums(c, first, n, p))) return rc;
+    for (int64_t i0 = 0; i0 < records; i0 += piece) {
+        const int64_t i1 = std::min(records, i0 + piece);
+        if ((rc = voxel_mean_emit(c, p, i0, i1, d)) || (o.host && (rc = stage_copy(c, o, d, i0, i1 - i0)))) return rc;
+    }
+    return voxel_mean_check(c);
+}
 } // namespace
 
 int pcr_voxel_mean(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, void *dev_points, void *dev_rows,
                    void *dev_counts, size_t capacity_points, int64_t *out_count, pcr_thin_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ThinPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = voxel_mean_prepare(c, first_batch, count, vox, clip, dev_points, 16, dev_rows, dev_counts, 8, capacity_points, out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    if ((rc = voxel_mean_sums(c, first_batch, n, p))) return rc;
-    if ((rc = voxel_mean_emit(c, p, 0, p.st.points_kept, static_cast<uint4 *>(dev_points), static_cast<int64_t *>(dev_rows), static_cast<int64_t *>(dev_counts))))
-        return rc;
-    return voxel_mean_check(c);
+    return voxel_mean_call(c, first_batch, count, vox, clip, KeptOut{false, dev_points, capacity_points, {{"rows", dev_rows, 8}, {"counts", dev_counts, 8}}},
+                           out_count, stats);
 }
 
 int pcr_read_voxel_mean(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxels *vox, const pcr_box *clip, pcr_point *host_points,
                         int64_t *host_rows, int64_t *host_counts, size_t capacity_points, int64_t *out_count, pcr_thin_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ThinPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = voxel_mean_prepare(c, first_batch, count, vox, clip, host_points, alignof(pcr_point), host_rows, host_counts, alignof(int64_t), capacity_points,
-                                out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    // pieces of at most DECODE_STAGE_BATCHES * 65 536 records through the staging buffers
-    const int64_t records = p.st.points_kept;
-    const int64_t piece_batches = std::min<int64_t>((records + PCR_POINTS_PER_BATCH - 1) / PCR_POINTS_PER_BATCH, DECODE_STAGE_BATCHES);
-    const int64_t piece = piece_batches * PCR_POINTS_PER_BATCH;
-    const size_t per_batch = (size_t)PCR_POINTS_PER_BATCH;
-    if ((host_points && !thin_grow((void **)&c->d_decode_stage, c->decode_stage_batches, piece_batches, per_batch * sizeof(pcr_point))) ||
-        (host_rows && !thin_grow((void **)&c->d_thin_rows_stage, c->thin_rows_stage_batches, piece_batches, per_batch * sizeof(int64_t))) ||
-        (host_counts && !thin_grow((void **)&c->d_voxel_counts_stage, c->voxel_counts_stage_batches, piece_batches, per_batch * sizeof(int64_t))))
-        return set_err(c, PCR_E_NOMEM, "out of device memory for the staging buffers of %lld records", (long long)piece);
-    uint4 *const d_points = host_points ? reinterpret_cast<uint4 *>(c->d_decode_stage) : nullptr;
-    int64_t *const d_rows = host_rows ? c->d_thin_rows_stage : nullptr;
-    int64_t *const d_counts = host_counts ? c->d_voxel_counts_stage : nullptr;
-    if ((rc = voxel_mean_sums(c, first_batch, n, p))) return rc;
-    for (int64_t i0 = 0; i0 < records; i0 += piece) {
-        const int64_t i1 = std::min(records, i0 + piece), m = i1 - i0;
-        if ((rc = voxel_mean_emit(c, p, i0, i1, d_points, d_rows, d_counts))) return rc;
-        if (d_points) HIP_TRY(c, hipMemcpyAsync(host_points + i0, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
-        if (d_rows) HIP_TRY(c, hipMemcpyAsync(host_rows + i0, d_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        if (d_counts) HIP_TRY(c, hipMemcpyAsync(host_counts + i0, d_counts, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return voxel_mean_check(c);
+    return voxel_mean_call(c, first_batch, count, vox, clip, KeptOut{true, host_points, capacity_points, {{"rows", host_rows, 8}, {"counts", host_counts, 8}}},
+                           out_count, stats);
 }
 
 // ---- screen selection and picking --------------------------------------------------------------

@@ -3199,11 +3199,14 @@ __global__ void __launch_bounds__(256) k_thin_totals(const uint32_t *list, uint3
     if (threadIdx.x == 0) totals[blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
 }
 
-// Workgroup x takes list[x], a batch that keeps a record: the flagged records go to points[offsets[x] ..] and their rows to
-// rows[offsets[x] ..] (either may be NULL), chain after chain, each chain's in point order. A lane's keep word is its chain's.
-template <int LAYOUT, bool BC7>
-__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_thin_write(StreamView s, const uint32_t *list, uint32_t first_batch, const thin_u64 *keep,
-                                                                   const int64_t *offsets, uint4 *points, int64_t *rows)
+// The body of the write kernels. Workgroup x takes list[x], a batch that keeps a record: the flagged records go to
+// points[offsets[x] ..] and their rows to rows[offsets[x] ..] (either may be NULL), chain after chain, each chain's in point order;
+// extra(dst, row) stores the call's other columns of that record. A lane's keep word is its chain's. k_thin_write and k_knn_write
+// are this body; k_neighbors_write and k_moments_write spell it out once more: built on it they come out with other register
+// counts and another block order, and these kernels are kept as measured.
+template <int LAYOUT, bool BC7, class Extra>
+__device__ __forceinline__ void write_kept_rows(const StreamView &s, const uint32_t *list, uint32_t first_batch, const thin_u64 *keep, const int64_t *offsets,
+                                                uint4 *points, int64_t *rows, Extra extra)
 {
     const uint32_t b = list[blockIdx.x];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -3228,9 +3231,17 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_thin_write(StreamView s,
         if (((word >> (uint32_t)i) & 1ull) && dst < end) {
             if (points) points[dst] = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
             if (rows) rows[dst] = row0 + i;
+            extra(dst, row0 + i);
             ++dst;
         }
     });
+}
+
+template <int LAYOUT, bool BC7>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_thin_write(StreamView s, const uint32_t *list, uint32_t first_batch, const thin_u64 *keep,
+                                                                   const int64_t *offsets, uint4 *points, int64_t *rows)
+{
+    write_kept_rows<LAYOUT, BC7>(s, list, first_batch, keep, offsets, points, rows, [](int64_t, int64_t) {});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3881,7 +3892,8 @@ __global__ void __launch_bounds__(256) k_neighbors_pairs(NeighborsArgs a, thin_u
     }
 }
 
-// k_thin_write that also gathers N and nn2 of the written rows from the dense arrays (any of the four outputs may be NULL)
+// k_thin_write that also gathers N and nn2 of the written rows from the dense arrays (any of the four outputs may be NULL);
+// write_kept_rows' body written out, see there
 template <int LAYOUT, bool BC7>
 __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_neighbors_write(StreamView s, const uint32_t *list, uint32_t first_batch, const thin_u64 *keep,
                                                                         const int64_t *offsets, const thin_u64 *dense_n, const thin_u64 *dense_nn2,
@@ -4136,7 +4148,7 @@ __global__ void __launch_bounds__(256) k_moments_eigen(const int64_t *moments, t
 }
 
 // k_neighbors_write gathering the 80-byte and 48-byte records of the written rows from the dense arrays (any of the four outputs
-// may be NULL; moments and eigen are 8-byte aligned, so they are stored word by word)
+// may be NULL; moments and eigen are 8-byte aligned, so they are stored word by word); write_kept_rows' body written out, see there
 template <int LAYOUT, bool BC7>
 __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_moments_write(StreamView s, const uint32_t *list, uint32_t first_batch, const thin_u64 *keep,
                                                                       const int64_t *offsets, const thin_u64 *dense_m, const thin_u64 *dense_e,
@@ -4304,33 +4316,9 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_knn_write(StreamView s, 
                                                                   const int64_t *offsets, const thin_u64 *dense, int k, uint4 *points, int64_t *rows,
                                                                   thin_u64 *knn)
 {
-    const uint32_t b = list[blockIdx.x];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
-    __shared__ uint32_t s_part[LWC_WAVES];
-    const thin_u64 word = keep[(size_t)(b - first_batch) * PCR_WORKGROUP_SIZE + tid];
-    const uint32_t mine = (uint32_t)__popcll(word);
-    uint32_t incl = mine;                                   // inclusive prefix inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d) incl += up;
-    }
-    if (lane == 63) s_part[wave] = incl;
-    load_packed_table(s, b, s_table);                       // (its barrier publishes s_part as well)
-    uint32_t before = incl - mine;
-    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
-    int64_t dst = offsets[blockIdx.x] + before;
-    const int64_t end = dst + mine;                         // never past the bits of this chain's word
-    const int64_t row0 = (int64_t)(b - first_batch) * PCR_POINTS_PER_BATCH + (int64_t)tid * PCR_POINTS_PER_THREAD;
-    decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t colour) {
-        if (((word >> (uint32_t)i) & 1ull) && dst < end) {
-            if (points) points[dst] = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
-            if (rows) rows[dst] = row0 + i;
-            if (knn) {
-                for (int j = 0; j < k; ++j) knn[dst * k + j] = dense[(row0 + i) * k + j];
-            }
-            ++dst;
+    write_kept_rows<LAYOUT, BC7>(s, list, first_batch, keep, offsets, points, rows, [&](int64_t dst, int64_t row) {
+        if (knn) {
+            for (int j = 0; j < k; ++j) knn[dst * k + j] = dense[row * k + j];
         }
     });
 }

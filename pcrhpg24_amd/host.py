@@ -1183,6 +1183,45 @@ class Context:
         self.height_stats = st.as_dict()
         return (pts, hts) if heights else pts
 
+    # -- the calls that write kept rows: the records and a few columns per row (pcr_thin .. pcr_knn) -------------
+    def _kept_device(self, fn, args, stats, attr: str, key: str, out, extra):
+        """The device form of such a call: `fn` with `args` between the context and the destinations, `stats` its statistics
+        structure, left as a dict in self.<attr> (its `key` is the count). `out` as Context.thin takes it: without it a counting
+        call, then the exact allocation. `extra`: (asked for, torch dtype name, shape of one row) per column the call can write.
+        The records, followed by the columns asked for; the records alone if there is none."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        name, cnt, st, none = fn.__name__, c_i64(), stats(), (None,) * len(extra)
+        if out is None:
+            self._chk(fn(self.h, *args, None, *none, 0, C.byref(cnt), C.byref(st)), name)
+            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
+        cap = out.numel() // 4
+        cols = [torch.empty((cap,) + tuple(row), dtype=getattr(torch, dt), device=dev) if want else None for want, dt, row in extra]
+        torch.cuda.current_stream(dev).synchronize()
+        ptrs = [C.c_void_p(t.data_ptr() if cap else None) if t is not None else None for t in cols]
+        rc = fn(self.h, *args, C.c_void_p(out.data_ptr() if cap else None), *ptrs, cap, C.byref(cnt), C.byref(st))
+        setattr(self, attr, st.as_dict())
+        if rc:
+            getattr(self, attr)[key] = cnt.value
+        self._chk(rc, name)
+        res = (out.view(-1, 4)[:cnt.value],) + tuple(t[:cnt.value] for t in cols if t is not None)
+        return res if len(res) > 1 else res[0]
+
+    def _kept_host(self, fn, args, stats, attr: str, extra):
+        """The host form: a counting call, then the read into numpy arrays. `extra`: (asked for, numpy dtype, shape of one row) per
+        column. The records (POINT_DTYPE), followed by the columns asked for; the records alone if there is none."""
+        name, cnt, st, none = fn.__name__, c_i64(), stats(), (None,) * len(extra)
+        self._chk(fn(self.h, *args, None, *none, 0, C.byref(cnt), C.byref(st)), name)
+        pts = np.empty(cnt.value, POINT_DTYPE)
+        cols = [np.empty((cnt.value,) + tuple(row), dt) if want else None for want, dt, row in extra]
+        if cnt.value:
+            self._chk(fn(self.h, *args, pts.ctypes.data, *[None if a is None else a.ctypes.data for a in cols], len(pts), C.byref(cnt), C.byref(st)), name)
+        setattr(self, attr, st.as_dict())
+        res = (pts,) + tuple(a for a in cols if a is not None)
+        return res if len(res) > 1 else res[0]
+
     # -- voxel thinning (pcr_thin / pcr_read_thin) ----------------------------------------------------------
     def thin(self, vox, clip=None, mode="first", first: int = 0, count: Optional[int] = None, out=None, rows: bool = False):
         """One point per voxel of `vox` (as_voxels: a Voxels or origin x, y, z, cell) among the rows of batches [first, first + count)
@@ -1192,41 +1231,16 @@ class Context:
         of their row numbers there. `out`: a contiguous int32 CUDA tensor to fill; it has to hold the result (PcrError if not;
         thin_stats then tells the count). Without it the call counts first and allocates exactly. Stream ordering as
         decode_points. What the last call did is in self.thin_stats."""
-        import torch
         vox, clip, mode = as_voxels(vox), None if clip is None else as_box(clip), thin_mode(mode)
-        cp = None if clip is None else C.byref(clip)
-        dev = torch.device("cuda", self.device)
-        cnt, st, nb = c_i64(), ThinStats(), -1 if count is None else count
-        if out is None:
-            self._chk(self.lib.pcr_thin(self.h, first, nb, C.byref(vox), cp, mode, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_thin")
-            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
-        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
-        cap = out.numel() // 4
-        r = torch.empty(cap, dtype=torch.int64, device=dev) if rows else None
-        torch.cuda.current_stream(dev).synchronize()
-        rc = self.lib.pcr_thin(self.h, first, nb, C.byref(vox), cp, mode, C.c_void_p(out.data_ptr() if cap else None),
-                               C.c_void_p(r.data_ptr() if cap else None) if rows else None, cap, C.byref(cnt), C.byref(st))
-        self.thin_stats = st.as_dict()
-        if rc:
-            self.thin_stats["points_kept"] = cnt.value
-        self._chk(rc, "pcr_thin")
-        pts = out.view(-1, 4)[:cnt.value]
-        return (pts, r[:cnt.value]) if rows else pts
+        args = (first, -1 if count is None else count, C.byref(vox), None if clip is None else C.byref(clip), mode)
+        return self._kept_device(self.lib.pcr_thin, args, ThinStats, "thin_stats", "points_kept", out, [(rows, "int64", ())])
 
     def read_thin(self, vox, clip=None, mode="first", first: int = 0, count: Optional[int] = None, rows: bool = False):
         """The same on the host, without torch: a numpy structured array of POINT_DTYPE, with rows=True (points, rows), rows an
         int64 array (pcr_read_thin: a counting call, then the read; synchronises)."""
         vox, clip, mode = as_voxels(vox), None if clip is None else as_box(clip), thin_mode(mode)
-        cp = None if clip is None else C.byref(clip)
-        cnt, st, nb = c_i64(), ThinStats(), -1 if count is None else count
-        self._chk(self.lib.pcr_read_thin(self.h, first, nb, C.byref(vox), cp, mode, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_read_thin")
-        pts, r = np.empty(cnt.value, POINT_DTYPE), np.empty(cnt.value if rows else 0, ROW_DTYPE)
-        if cnt.value:
-            self._chk(self.lib.pcr_read_thin(self.h, first, nb, C.byref(vox), cp, mode, pts.ctypes.data, r.ctypes.data if rows else None, len(pts),
-                                             C.byref(cnt), C.byref(st)), "pcr_read_thin")
-        self.thin_stats = st.as_dict()
-        return (pts, r) if rows else pts
+        args = (first, -1 if count is None else count, C.byref(vox), None if clip is None else C.byref(clip), mode)
+        return self._kept_host(self.lib.pcr_read_thin, args, ThinStats, "thin_stats", [(rows, ROW_DTYPE, ())])
 
     # -- voxel means (pcr_voxel_mean / pcr_read_voxel_mean) --------------------------------------------------
     def voxel_mean(self, vox, clip=None, first: int = 0, count: Optional[int] = None, out=None, rows: bool = False, counts: bool = False):
@@ -1236,46 +1250,18 @@ class Context:
         thin(vox, clip, "first"); rows=True appends a torch.int64 tensor [n] of each voxel's lowest row (the rows thin returns),
         counts=True one of the points per voxel: points, then rows, then counts. `out` and the allocation behave as in thin.
         Stream ordering as decode_points. What the last call did is in self.voxel_mean_stats (a ThinStats)."""
-        import torch
         vox, clip = as_voxels(vox), None if clip is None else as_box(clip)
-        cp = None if clip is None else C.byref(clip)
-        dev = torch.device("cuda", self.device)
-        cnt, st, nb = c_i64(), ThinStats(), -1 if count is None else count
-        if out is None:
-            self._chk(self.lib.pcr_voxel_mean(self.h, first, nb, C.byref(vox), cp, None, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_voxel_mean")
-            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
-        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
-        cap = out.numel() // 4
-        r = torch.empty(cap, dtype=torch.int64, device=dev) if rows else None
-        n = torch.empty(cap, dtype=torch.int64, device=dev) if counts else None
-        torch.cuda.current_stream(dev).synchronize()
-        rc = self.lib.pcr_voxel_mean(self.h, first, nb, C.byref(vox), cp, C.c_void_p(out.data_ptr() if cap else None),
-                                     C.c_void_p(r.data_ptr() if cap else None) if rows else None,
-                                     C.c_void_p(n.data_ptr() if cap else None) if counts else None, cap, C.byref(cnt), C.byref(st))
-        self.voxel_mean_stats = st.as_dict()
-        if rc:
-            self.voxel_mean_stats["points_kept"] = cnt.value
-        self._chk(rc, "pcr_voxel_mean")
-        res = (out.view(-1, 4)[:cnt.value],) + ((r[:cnt.value],) if rows else ()) + ((n[:cnt.value],) if counts else ())
-        return res if len(res) > 1 else res[0]
+        args = (first, -1 if count is None else count, C.byref(vox), None if clip is None else C.byref(clip))
+        return self._kept_device(self.lib.pcr_voxel_mean, args, ThinStats, "voxel_mean_stats", "points_kept", out,
+                                 [(rows, "int64", ()), (counts, "int64", ())])
 
     def read_voxel_mean(self, vox, clip=None, first: int = 0, count: Optional[int] = None, rows: bool = False, counts: bool = False):
         """The same on the host, without torch: a numpy structured array of POINT_DTYPE, then with rows=True an int64 array of the
         lowest rows, with counts=True one of the points per voxel (pcr_read_voxel_mean: a counting call, then the read;
         synchronises)."""
         vox, clip = as_voxels(vox), None if clip is None else as_box(clip)
-        cp = None if clip is None else C.byref(clip)
-        cnt, st, nb = c_i64(), ThinStats(), -1 if count is None else count
-        self._chk(self.lib.pcr_read_voxel_mean(self.h, first, nb, C.byref(vox), cp, None, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_read_voxel_mean")
-        pts = np.empty(cnt.value, POINT_DTYPE)
-        r, n = np.empty(cnt.value if rows else 0, ROW_DTYPE), np.empty(cnt.value if counts else 0, ROW_DTYPE)
-        if cnt.value:
-            self._chk(self.lib.pcr_read_voxel_mean(self.h, first, nb, C.byref(vox), cp, pts.ctypes.data, r.ctypes.data if rows else None,
-                                                   n.ctypes.data if counts else None, len(pts), C.byref(cnt), C.byref(st)), "pcr_read_voxel_mean")
-        self.voxel_mean_stats = st.as_dict()
-        res = (pts,) + ((r,) if rows else ()) + ((n,) if counts else ())
-        return res if len(res) > 1 else res[0]
+        args = (first, -1 if count is None else count, C.byref(vox), None if clip is None else C.byref(clip))
+        return self._kept_host(self.lib.pcr_read_voxel_mean, args, ThinStats, "voxel_mean_stats", [(rows, ROW_DTYPE, ()), (counts, ROW_DTYPE, ())])
 
     # -- voxel denoising (pcr_denoise / pcr_read_denoise) ----------------------------------------------------
     def denoise(self, vox, max_count: int, clip=None, mode="keep", first: int = 0, count: Optional[int] = None, out=None, rows: bool = False):
@@ -1283,41 +1269,16 @@ class Context:
         "keep") or the isolated ones alone (mode "isolated"), straight from the compressed stream. A row is isolated iff the 27
         voxels of `vox` (as_voxels) around its own hold at most `max_count` rows of the range inside the clip, itself included.
         Results, `out`, rows=True and stream ordering as Context.thin. What the last call did is in self.denoise_stats."""
-        import torch
         vox, clip, mode = as_voxels(vox), None if clip is None else as_box(clip), denoise_mode(mode)
-        cp = None if clip is None else C.byref(clip)
-        dev = torch.device("cuda", self.device)
-        cnt, st, nb = c_i64(), DenoiseStats(), -1 if count is None else count
-        if out is None:
-            self._chk(self.lib.pcr_denoise(self.h, first, nb, C.byref(vox), cp, max_count, mode, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_denoise")
-            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
-        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
-        cap = out.numel() // 4
-        r = torch.empty(cap, dtype=torch.int64, device=dev) if rows else None
-        torch.cuda.current_stream(dev).synchronize()
-        rc = self.lib.pcr_denoise(self.h, first, nb, C.byref(vox), cp, max_count, mode, C.c_void_p(out.data_ptr() if cap else None),
-                                  C.c_void_p(r.data_ptr() if cap else None) if rows else None, cap, C.byref(cnt), C.byref(st))
-        self.denoise_stats = st.as_dict()
-        if rc:
-            self.denoise_stats["points_written"] = cnt.value
-        self._chk(rc, "pcr_denoise")
-        pts = out.view(-1, 4)[:cnt.value]
-        return (pts, r[:cnt.value]) if rows else pts
+        args = (first, -1 if count is None else count, C.byref(vox), None if clip is None else C.byref(clip), max_count, mode)
+        return self._kept_device(self.lib.pcr_denoise, args, DenoiseStats, "denoise_stats", "points_written", out, [(rows, "int64", ())])
 
     def read_denoise(self, vox, max_count: int, clip=None, mode="keep", first: int = 0, count: Optional[int] = None, rows: bool = False):
         """The same on the host, without torch: a numpy structured array of POINT_DTYPE, with rows=True (points, rows), rows an
         int64 array (pcr_read_denoise: a counting call, then the read; synchronises)."""
         vox, clip, mode = as_voxels(vox), None if clip is None else as_box(clip), denoise_mode(mode)
-        cp = None if clip is None else C.byref(clip)
-        cnt, st, nb = c_i64(), DenoiseStats(), -1 if count is None else count
-        self._chk(self.lib.pcr_read_denoise(self.h, first, nb, C.byref(vox), cp, max_count, mode, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_read_denoise")
-        pts, r = np.empty(cnt.value, POINT_DTYPE), np.empty(cnt.value if rows else 0, ROW_DTYPE)
-        if cnt.value:
-            self._chk(self.lib.pcr_read_denoise(self.h, first, nb, C.byref(vox), cp, max_count, mode, pts.ctypes.data, r.ctypes.data if rows else None,
-                                                len(pts), C.byref(cnt), C.byref(st)), "pcr_read_denoise")
-        self.denoise_stats = st.as_dict()
-        return (pts, r) if rows else pts
+        args = (first, -1 if count is None else count, C.byref(vox), None if clip is None else C.byref(clip), max_count, mode)
+        return self._kept_host(self.lib.pcr_read_denoise, args, DenoiseStats, "denoise_stats", [(rows, ROW_DTYPE, ())])
 
     # -- connected components (pcr_components / pcr_read_components) -----------------------------------------
     def components(self, vox, min_points: int = 1, connectivity: int = 26, clip=None, mode="keep", first: int = 0, count: Optional[int] = None, out=None,
@@ -1329,48 +1290,18 @@ class Context:
         is the least of its rows. Results, `out`, rows=True and stream ordering as Context.denoise; labels=True appends an int64
         tensor of the labels: points, (points, rows), (points, labels) or (points, rows, labels). What the last call did is in
         self.components_stats."""
-        import torch
         vox, clip, mode = as_voxels(vox), None if clip is None else as_box(clip), components_mode(mode)
-        cp = None if clip is None else C.byref(clip)
-        dev = torch.device("cuda", self.device)
-        cnt, st, nb = c_i64(), ComponentsStats(), -1 if count is None else count
-        if out is None:
-            self._chk(self.lib.pcr_components(self.h, first, nb, C.byref(vox), cp, connectivity, min_points, mode, None, None, None, 0, C.byref(cnt),
-                                              C.byref(st)), "pcr_components")
-            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
-        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
-        cap = out.numel() // 4
-        r = torch.empty(cap, dtype=torch.int64, device=dev) if rows else None
-        lab = torch.empty(cap, dtype=torch.int64, device=dev) if labels else None
-        torch.cuda.current_stream(dev).synchronize()
-        rc = self.lib.pcr_components(self.h, first, nb, C.byref(vox), cp, connectivity, min_points, mode, C.c_void_p(out.data_ptr() if cap else None),
-                                     C.c_void_p(r.data_ptr() if cap else None) if rows else None,
-                                     C.c_void_p(lab.data_ptr() if cap else None) if labels else None, cap, C.byref(cnt), C.byref(st))
-        self.components_stats = st.as_dict()
-        if rc:
-            self.components_stats["points_written"] = cnt.value
-        self._chk(rc, "pcr_components")
-        res = (out.view(-1, 4)[:cnt.value],) + ((r[:cnt.value],) if rows else ()) + ((lab[:cnt.value],) if labels else ())
-        return res if len(res) > 1 else res[0]
+        args = (first, -1 if count is None else count, C.byref(vox), None if clip is None else C.byref(clip), connectivity, min_points, mode)
+        return self._kept_device(self.lib.pcr_components, args, ComponentsStats, "components_stats", "points_written", out,
+                                 [(rows, "int64", ()), (labels, "int64", ())])
 
     def read_components(self, vox, min_points: int = 1, connectivity: int = 26, clip=None, mode="keep", first: int = 0, count: Optional[int] = None,
                         rows: bool = False, labels: bool = False):
         """The same on the host, without torch: a numpy structured array of POINT_DTYPE, with rows=True / labels=True followed by
         int64 arrays of the rows / the labels (pcr_read_components: a counting call, then the read; synchronises)."""
         vox, clip, mode = as_voxels(vox), None if clip is None else as_box(clip), components_mode(mode)
-        cp = None if clip is None else C.byref(clip)
-        cnt, st, nb = c_i64(), ComponentsStats(), -1 if count is None else count
-        self._chk(self.lib.pcr_read_components(self.h, first, nb, C.byref(vox), cp, connectivity, min_points, mode, None, None, None, 0, C.byref(cnt),
-                                               C.byref(st)), "pcr_read_components")
-        pts, r, lab = np.empty(cnt.value, POINT_DTYPE), np.empty(cnt.value if rows else 0, ROW_DTYPE), np.empty(cnt.value if labels else 0, ROW_DTYPE)
-        if cnt.value:
-            self._chk(self.lib.pcr_read_components(self.h, first, nb, C.byref(vox), cp, connectivity, min_points, mode, pts.ctypes.data,
-                                                   r.ctypes.data if rows else None, lab.ctypes.data if labels else None, len(pts), C.byref(cnt),
-                                                   C.byref(st)), "pcr_read_components")
-        self.components_stats = st.as_dict()
-        res = (pts,) + ((r,) if rows else ()) + ((lab,) if labels else ())
-        return res if len(res) > 1 else res[0]
+        args = (first, -1 if count is None else count, C.byref(vox), None if clip is None else C.byref(clip), connectivity, min_points, mode)
+        return self._kept_host(self.lib.pcr_read_components, args, ComponentsStats, "components_stats", [(rows, ROW_DTYPE, ()), (labels, ROW_DTYPE, ())])
 
     # -- radius neighbourhoods (pcr_neighbors / pcr_read_neighbors) ------------------------------------------
     def neighbors(self, radius: int, min_count: int = 1, clip=None, mode="all", first: int = 0, count: Optional[int] = None, out=None,
@@ -1381,29 +1312,10 @@ class Context:
         Context.denoise; counts=True appends an int64 tensor of N (the rows within the radius), nn2=True an int64 tensor holding
         the squared distance to the nearest other row within the radius (-1, the bits of NN2_NONE, for none): points, then rows,
         counts, nn2 as asked for. What the last call did is in self.neighbors_stats."""
-        import torch
         clip, mode = None if clip is None else as_box(clip), neighbors_mode(mode)
-        cp = None if clip is None else C.byref(clip)
-        dev = torch.device("cuda", self.device)
-        cnt, st, nb = c_i64(), NeighborsStats(), -1 if count is None else count
-        if out is None:
-            self._chk(self.lib.pcr_neighbors(self.h, first, nb, radius, cp, min_count, mode, None, None, None, None, 0, C.byref(cnt), C.byref(st)),
-                      "pcr_neighbors")
-            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
-        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
-        cap = out.numel() // 4
-        extra = [torch.empty(cap, dtype=torch.int64, device=dev) if want else None for want in (rows, counts, nn2)]
-        torch.cuda.current_stream(dev).synchronize()
-        ptrs = [C.c_void_p(t.data_ptr() if cap else None) if t is not None else None for t in extra]
-        rc = self.lib.pcr_neighbors(self.h, first, nb, radius, cp, min_count, mode, C.c_void_p(out.data_ptr() if cap else None), ptrs[0], ptrs[1], ptrs[2],
-                                    cap, C.byref(cnt), C.byref(st))
-        self.neighbors_stats = st.as_dict()
-        if rc:
-            self.neighbors_stats["points_written"] = cnt.value
-        self._chk(rc, "pcr_neighbors")
-        res = (out.view(-1, 4)[:cnt.value],) + tuple(t[:cnt.value] for t in extra if t is not None)
-        return res if len(res) > 1 else res[0]
+        args = (first, -1 if count is None else count, radius, None if clip is None else C.byref(clip), min_count, mode)
+        return self._kept_device(self.lib.pcr_neighbors, args, NeighborsStats, "neighbors_stats", "points_written", out,
+                                 [(rows, "int64", ()), (counts, "int64", ()), (nn2, "int64", ())])
 
     def read_neighbors(self, radius: int, min_count: int = 1, clip=None, mode="all", first: int = 0, count: Optional[int] = None, rows: bool = False,
                        counts: bool = False, nn2: bool = False):
@@ -1411,19 +1323,9 @@ class Context:
         the rows and of N and a uint64 array of nn2 (NN2_NONE for none) (pcr_read_neighbors: a counting call, then the read;
         synchronises)."""
         clip, mode = None if clip is None else as_box(clip), neighbors_mode(mode)
-        cp = None if clip is None else C.byref(clip)
-        cnt, st, nb = c_i64(), NeighborsStats(), -1 if count is None else count
-        self._chk(self.lib.pcr_read_neighbors(self.h, first, nb, radius, cp, min_count, mode, None, None, None, None, 0, C.byref(cnt), C.byref(st)),
-                  "pcr_read_neighbors")
-        pts = np.empty(cnt.value, POINT_DTYPE)
-        extra = [np.empty(cnt.value, dt) if want else None for want, dt in ((rows, ROW_DTYPE), (counts, np.int64), (nn2, np.uint64))]
-        if cnt.value:
-            self._chk(self.lib.pcr_read_neighbors(self.h, first, nb, radius, cp, min_count, mode, pts.ctypes.data,
-                                                  *[None if a is None else a.ctypes.data for a in extra], len(pts), C.byref(cnt), C.byref(st)),
-                      "pcr_read_neighbors")
-        self.neighbors_stats = st.as_dict()
-        res = (pts,) + tuple(a for a in extra if a is not None)
-        return res if len(res) > 1 else res[0]
+        args = (first, -1 if count is None else count, radius, None if clip is None else C.byref(clip), min_count, mode)
+        return self._kept_host(self.lib.pcr_read_neighbors, args, NeighborsStats, "neighbors_stats",
+                               [(rows, ROW_DTYPE, ()), (counts, np.int64, ()), (nn2, np.uint64, ())])
 
     # -- local moments (pcr_local_moments / pcr_read_local_moments / pcr_moments_eigen) ------------------------
     def local_moments(self, radius: int, min_count: int = 1, clip=None, first: int = 0, count: Optional[int] = None, out=None,
@@ -1434,30 +1336,10 @@ class Context:
         tensor [n, 10] of the exact moments of the offsets to the rows within the radius (n, s x y z, q xx xy xz yy yz zz),
         eigen=True a float64 tensor [n, 6] (the eigenvalues of the covariance, ascending, and the unit normal): points, then rows,
         moments, eigen as asked for. What the last call did is in self.moments_stats."""
-        import torch
         clip = None if clip is None else as_box(clip)
-        cp = None if clip is None else C.byref(clip)
-        dev = torch.device("cuda", self.device)
-        cnt, st, nb = c_i64(), NeighborsStats(), -1 if count is None else count
-        if out is None:
-            self._chk(self.lib.pcr_local_moments(self.h, first, nb, radius, cp, min_count, None, None, None, None, 0, C.byref(cnt), C.byref(st)),
-                      "pcr_local_moments")
-            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
-        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
-        cap = out.numel() // 4
-        extra = [torch.empty(shape, dtype=dt, device=dev) if want else None
-                 for want, shape, dt in ((rows, (cap,), torch.int64), (moments, (cap, 10), torch.int64), (eigen, (cap, 6), torch.float64))]
-        torch.cuda.current_stream(dev).synchronize()
-        ptrs = [C.c_void_p(t.data_ptr() if cap else None) if t is not None else None for t in extra]
-        rc = self.lib.pcr_local_moments(self.h, first, nb, radius, cp, min_count, C.c_void_p(out.data_ptr() if cap else None), ptrs[0], ptrs[1], ptrs[2],
-                                        cap, C.byref(cnt), C.byref(st))
-        self.moments_stats = st.as_dict()
-        if rc:
-            self.moments_stats["points_written"] = cnt.value
-        self._chk(rc, "pcr_local_moments")
-        res = (out.view(-1, 4)[:cnt.value],) + tuple(t[:cnt.value] for t in extra if t is not None)
-        return res if len(res) > 1 else res[0]
+        args = (first, -1 if count is None else count, radius, None if clip is None else C.byref(clip), min_count)
+        return self._kept_device(self.lib.pcr_local_moments, args, NeighborsStats, "moments_stats", "points_written", out,
+                                 [(rows, "int64", ()), (moments, "int64", (10,)), (eigen, "float64", (6,))])
 
     def read_local_moments(self, radius: int, min_count: int = 1, clip=None, first: int = 0, count: Optional[int] = None, rows: bool = False,
                            moments: bool = False, eigen: bool = False):
@@ -1465,19 +1347,9 @@ class Context:
         the rows, a MOMENTS_DTYPE array and an EIGEN_DTYPE array (pcr_read_local_moments: a counting call, then the read;
         synchronises)."""
         clip = None if clip is None else as_box(clip)
-        cp = None if clip is None else C.byref(clip)
-        cnt, st, nb = c_i64(), NeighborsStats(), -1 if count is None else count
-        self._chk(self.lib.pcr_read_local_moments(self.h, first, nb, radius, cp, min_count, None, None, None, None, 0, C.byref(cnt), C.byref(st)),
-                  "pcr_read_local_moments")
-        pts = np.empty(cnt.value, POINT_DTYPE)
-        extra = [np.empty(cnt.value, dt) if want else None for want, dt in ((rows, ROW_DTYPE), (moments, MOMENTS_DTYPE), (eigen, EIGEN_DTYPE))]
-        if cnt.value:
-            self._chk(self.lib.pcr_read_local_moments(self.h, first, nb, radius, cp, min_count, pts.ctypes.data,
-                                                      *[None if a is None else a.ctypes.data for a in extra], len(pts), C.byref(cnt), C.byref(st)),
-                      "pcr_read_local_moments")
-        self.moments_stats = st.as_dict()
-        res = (pts,) + tuple(a for a in extra if a is not None)
-        return res if len(res) > 1 else res[0]
+        args = (first, -1 if count is None else count, radius, None if clip is None else C.byref(clip), min_count)
+        return self._kept_host(self.lib.pcr_read_local_moments, args, NeighborsStats, "moments_stats",
+                               [(rows, ROW_DTYPE, ()), (moments, MOMENTS_DTYPE, ()), (eigen, EIGEN_DTYPE, ())])
 
     # -- k nearest neighbours (pcr_knn / pcr_read_knn) --------------------------------------------------------
     def knn(self, k: int, radius: int, min_found: int = 0, clip=None, first: int = 0, count: Optional[int] = None, out=None, rows: bool = False,
@@ -1490,49 +1362,22 @@ class Context:
         call did is in self.knn_stats."""
         import torch
         clip = None if clip is None else as_box(clip)
-        cp = None if clip is None else C.byref(clip)
-        dev = torch.device("cuda", self.device)
-        cnt, st, nb = c_i64(), NeighborsStats(), -1 if count is None else count
-        if out is None:
-            self._chk(self.lib.pcr_knn(self.h, first, nb, k, radius, cp, min_found, None, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_knn")
-            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
-        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
-        cap = out.numel() // 4
-        r = torch.empty(cap, dtype=torch.int64, device=dev) if rows else None
-        words = torch.empty((cap, k), dtype=torch.int64, device=dev) if neighbors else None
-        torch.cuda.current_stream(dev).synchronize()
-        ptrs = [C.c_void_p(t.data_ptr() if cap else None) if t is not None else None for t in (r, words)]
-        rc = self.lib.pcr_knn(self.h, first, nb, k, radius, cp, min_found, C.c_void_p(out.data_ptr() if cap else None), ptrs[0], ptrs[1], cap,
-                              C.byref(cnt), C.byref(st))
-        self.knn_stats = st.as_dict()
-        if rc:
-            self.knn_stats["points_written"] = cnt.value
-        self._chk(rc, "pcr_knn")
-        res = (out.view(-1, 4)[:cnt.value],) + ((r[:cnt.value],) if rows else ())
+        args = (first, -1 if count is None else count, k, radius, None if clip is None else C.byref(clip), min_found)
+        res = self._kept_device(self.lib.pcr_knn, args, NeighborsStats, "knn_stats", "points_written", out, [(rows, "int64", ()), (neighbors, "int64", (k,))])
         if neighbors:
-            w = words[:cnt.value]
+            w = res[-1]
             none = w == -1                                  # (KNN_NONE's bits)
-            res += (torch.where(none, w, w & 0xFFFFFFFF), torch.where(none, w, w >> 32))
-        return res if len(res) > 1 else res[0]
+            res = res[:-1] + (torch.where(none, w, w & 0xFFFFFFFF), torch.where(none, w, w >> 32))
+        return res
 
     def read_knn(self, k: int, radius: int, min_found: int = 0, clip=None, first: int = 0, count: Optional[int] = None, rows: bool = False,
                  neighbors: bool = True):
         """The same on the host, without torch: a numpy structured array of POINT_DTYPE, followed as asked for by an int64 array of
         the rows and the int64 arrays [n, k] knn_rows and knn_d2 (pcr_read_knn: a counting call, then the read; synchronises)."""
         clip = None if clip is None else as_box(clip)
-        cp = None if clip is None else C.byref(clip)
-        cnt, st, nb = c_i64(), NeighborsStats(), -1 if count is None else count
-        self._chk(self.lib.pcr_read_knn(self.h, first, nb, k, radius, cp, min_found, None, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_read_knn")
-        pts = np.empty(cnt.value, POINT_DTYPE)
-        r = np.empty(cnt.value, ROW_DTYPE) if rows else None
-        words = np.empty((cnt.value, k), np.uint64) if neighbors else None
-        if cnt.value:
-            self._chk(self.lib.pcr_read_knn(self.h, first, nb, k, radius, cp, min_found, pts.ctypes.data, None if r is None else r.ctypes.data,
-                                            None if words is None else words.ctypes.data, len(pts), C.byref(cnt), C.byref(st)), "pcr_read_knn")
-        self.knn_stats = st.as_dict()
-        res = (pts,) + ((r,) if rows else ()) + (knn_split(words) if neighbors else ())
-        return res if len(res) > 1 else res[0]
+        args = (first, -1 if count is None else count, k, radius, None if clip is None else C.byref(clip), min_found)
+        res = self._kept_host(self.lib.pcr_read_knn, args, NeighborsStats, "knn_stats", [(rows, ROW_DTYPE, ()), (neighbors, np.uint64, (k,))])
+        return res[:-1] + knn_split(res[-1]) if neighbors else res
 
     def moments_eigen(self, moments):
         """pcr_moments_eigen: the eigen records of moments records. An int64 torch tensor [n, 10] on this context's device gives a

@@ -420,6 +420,27 @@ def test_twenty_million_points(ctx):
     # the host read goes through the 64-batch staging buffers in five pieces
     got, got_rows = ctx.read_thin((*origin, cell), None, T.CENTER, rows=True)
     assert np.array_equal(got_rows, want_rows.cpu().numpy()) and got.tobytes() == ref[want_rows].cpu().numpy().tobytes()
+    # The other host reads of the family go through the same loop, with their own columns (k words a row for read_knn): each
+    # against its device form, which writes in one emit and not through the loop. The clip is a slab 4 m thick through the whole
+    # cloud: on the host-decoded stream 76 000 candidates in 31 batches, in each of the five pieces -- which the stats and
+    # the returned rows have to confirm.
+    slab = ((500_000, -(1 << 31), -(1 << 31)), (503_999, (1 << 31) - 1, (1 << 31) - 1))
+    reads = (("components", "components_stats", 3, dict(vox=(0, 0, 0, 500), min_points=10, connectivity=6, rows=True, labels=True)),
+             ("voxel_mean", "voxel_mean_stats", 3, dict(vox=(-12345, 777, -1, 1000), rows=True, counts=True)),
+             ("neighbors", "neighbors_stats", 4, dict(radius=1000, min_count=1, rows=True, counts=True, nn2=True)),
+             ("local_moments", "moments_stats", 4, dict(radius=1000, min_count=3, rows=True, moments=True, eigen=True)),
+             ("knn", "knn_stats", 4, dict(k=3, radius=1000, rows=True, neighbors=True)))
+    for name, stats, outputs, kw in reads:
+        host = getattr(ctx, "read_" + name)(clip=slab, **kw)
+        host_stats = dict(getattr(ctx, stats))
+        dev = getattr(ctx, name)(clip=slab, **kw)
+        assert dict(getattr(ctx, stats)) == host_stats
+        assert 0 < host_stats["points_considered"] <= 300_000, name
+        assert len(host) == len(dev) == outputs, name
+        for k, (h, d) in enumerate(zip(host, dev)):
+            assert h.tobytes() == d.cpu().numpy().tobytes(), f"{name}: output {k}"
+        assert len(np.unique(host[1] // (64 * PPB))) >= 3, name
+        print(f"{name}: {len(host[1])} rows of {host_stats['points_considered']} candidates")
 
 
 # ---- 9. the resource and the CLI ----------------------------------------------------------------------------------------------------
