@@ -732,6 +732,52 @@ int pcr_read_voxel_mean(pcr_ctx *ctx, int64_t first_batch, int64_t count, const 
                         pcr_point *host_points, int64_t *host_rows, int64_t *host_counts, size_t capacity_points, int64_t *out_count,
                         pcr_thin_stats *stats);
 
+/* ---- levels of detail: the stream ordered by nested voxel lattices, straight from the compressed stream (no reference counterpart)
+ * Candidates and rows are pcr_thin's, word for word: the records pcr_decode_points writes for the range that lie inside *clip
+ * (bounds inclusive; NULL: all; padding duplicates and the tail artefact included), rows counted from first_batch. Level l of
+ * *lod (0 = coarsest, L - 1 = finest, L = lod->levels) is pcr_thin's lattice {origin, cell << (L - 1 - l)}.
+ * CONTRACT: level(p) of a candidate is the least l such that p has the lowest row of all candidates in its level-l voxel, and L
+ * ("the rest") if it has the lowest row at no level. The lattices are nested (floor(floor(d / c) / 2) == floor(d / 2c)), so the
+ * lowest row of a coarse voxel is also the lowest row of the finer voxel it lies in: the candidates with level <= l are exactly
+ * the rows pcr_thin(PCR_THIN_FIRST) keeps with {origin, cell << (L - 1 - l)} and the same clip, the levels are disjoint, and
+ * levels == 1 is pcr_thin FIRST plus a rest. The records written are all candidates, with PCR_LOD_DROP_REST those with level <
+ * L, each byte for byte pcr_decode_points' record. They come in increasing (level, row): records [0, level_count[0]) are level 0,
+ * the next level_count[1] level 1, and so on -- every prefix that ends at a level boundary is a uniformly thinned cloud. With
+ * PCR_LOD_ROW_ORDER they come in increasing row order instead (the level as a per-point attribute). dev_rows[i] is the row of
+ * record i as int64, dev_levels[i] its level as uint8 (0 .. L). Minima commute: the result is exact, depends on no hash, table
+ * size or order of lanes, workgroups and launches, and is the same bytes from run to run.
+ *
+ * pcr_lod_order: any of dev_points (16-byte aligned), dev_rows and dev_levels (8-byte aligned) may be NULL, with all three NULL
+ *   the call only counts; capacity_points counts records of each. A capacity below the result: PCR_E_ARG, *out_count = the count
+ *   needed, nothing written. Range semantics, count < 0, the restriction under pcr_set_async_upload, the empty clip / empty range /
+ *   clip that misses every batch (0 records, PCR_OK, no kernel runs), the limit of 2^40 rows and the synchronisation are
+ *   pcr_thin's. Touches no framebuffer, no prepass state, no render statistics and no pending pcr_frame_begin; BC1 and BC7,
+ *   either resident layout, before and after the first frame. stats may be NULL.
+ *   How: pcr_thin's FIRST plan fills the finest table with (voxel, lowest row) on the lattice of lod_lattice (pcr_lattice.h:
+ *   shifted by whole coarsest cells, so that the shifted lattices stay nested). k_lod_coarsen, a thread per slot, inserts
+ *   (parent voxel, row) of every occupied slot of level l + 1 into the table of level l -- compare-and-swap on the key, unsigned
+ *   minimum on the row; the parent key is every 21-bit field shifted right by one. k_lod_mark, a thread per slot of the new
+ *   table, stores l into the level byte of the slot's row and counts the occupied slots, from which the host sizes the next
+ *   table; going from fine to coarse the last store of a row is its least level. k_lod_count, a workgroup per listed batch,
+ *   makes the bytes final (a candidate without a level gets L), counts the batch's records per level and sets the keep words;
+ *   it decodes only a batch that the clip cuts. k_lod_write decodes with colours and stores every written record at the
+ *   running index of its level: a stable partition by level, the offsets per (batch, level) a prefix sum on the host. In row
+ *   order the keep words go through pcr_thin's write. No workgroup waits for another one; every probe loop is bounded by the
+ *   slot count. Scratch, grown on demand and released with the context: pcr_thin's, two tables for the coarser levels (each at
+ *   most the slots of twice the occupied finest voxels), 1 byte per row of the range and 8 (L + 1) bytes per listed batch.
+ * pcr_read_lod_order: the same into host memory (alignof(pcr_point) / alignof(int64_t) / 1), in pieces of 64 * 65 536 rows
+ *   through staging buffers; a piece is written in (level, row) order and copied to the L + 1 regions of the result.
+ * PCR_E_ARG with a message, nothing written: no stream loaded, a range outside the resident batches, a NULL lod or out_count, a
+ * misaligned destination, cell < 1, levels outside 1 .. PCR_LOD_MAX_LEVELS, cell << (levels - 1) > PCR_THIN_MAX_CELL, reserved !=
+ * 0, an unknown flag bit, and a lattice too large for the key: with q = the union of the exact boxes of the batches the clip
+ * does not miss, intersected with the clip, the call is refused if on any axis q.max - q.min >= 2^31 or (q.max - q.min) / cell +
+ * 2^(L - 1) + 1 > 2^21 -- pass a clip or a larger cell. PCR_E_NOMEM: no device memory for the tables or the level bytes. */
+int pcr_lod_order(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_lod *lod, const pcr_box *clip, uint32_t flags,
+                  void *dev_points, void *dev_rows, void *dev_levels, size_t capacity_points, int64_t *out_count, pcr_lod_stats *stats);
+int pcr_read_lod_order(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_lod *lod, const pcr_box *clip, uint32_t flags,
+                       pcr_point *host_points, int64_t *host_rows, uint8_t *host_levels, size_t capacity_points, int64_t *out_count,
+                       pcr_lod_stats *stats);
+
 /* What a collective library needs to merge partial frames in place (include/pcr_dist.h does it with RCCL): the HIP stream
  * the context enqueues on, its device ordinal and the length of each framebuffer in 64-bit words. */
 void *pcr_get_stream(pcr_ctx *ctx);

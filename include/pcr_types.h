@@ -268,6 +268,31 @@ typedef struct pcr_thin_stats {
     int64_t table_slots;
 } pcr_thin_stats;
 
+/* pcr_lod_order: `levels` nested lattices of pcr_thin over one origin. Level l (0 = coarsest, levels - 1 = finest) has the cell
+ * cell << (levels - 1 - l); the coarsest cell is at most PCR_THIN_MAX_CELL. 24 bytes. */
+#define PCR_LOD_MAX_LEVELS        16
+#define PCR_LOD_DROP_REST         1u         /* flag: do not write the candidates that are first in no voxel of any level */
+#define PCR_LOD_ROW_ORDER         2u         /* flag: the records in increasing row order, not in increasing (level, row) */
+typedef struct pcr_lod {
+    int32_t origin[3];           /* min corner of voxel (0, 0, 0) of every level */
+    int32_t cell;                /* edge length of the finest level, >= 1 */
+    int32_t levels;              /* L, 1 .. PCR_LOD_MAX_LEVELS */
+    int32_t reserved;            /* 0 */
+} pcr_lod;
+
+/* What pcr_lod_order did: pcr_thin_stats' batches, candidates and runs, the slots of the finest level's table, the records
+ * written, and the candidates of every level: level_count[l] for l < levels, level_count[levels] those of no level ("the rest",
+ * counted also when PCR_LOD_DROP_REST keeps them out of the result); the entries above are 0. */
+typedef struct pcr_lod_stats {
+    int64_t batches_outside;
+    int64_t batches_decoded;
+    int64_t points_considered;
+    int64_t runs;
+    int64_t table_slots;
+    int64_t points_written;
+    int64_t level_count[PCR_LOD_MAX_LEVELS + 1];
+} pcr_lod_stats;
+
 /* pcr_denoise: a candidate is isolated iff the 27 voxels around its own hold at most max_count candidates, itself included. */
 #define PCR_DENOISE_KEEP          0          /* mode: write the candidates that are not isolated */
 #define PCR_DENOISE_ISOLATED      1          /* mode: write the isolated ones */

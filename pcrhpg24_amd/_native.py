@@ -142,6 +142,21 @@ class ThinStats(C.Structure):                     # pcr_thin_stats
 
 THIN_FIRST, THIN_CENTER, THIN_MAX_CELL, THIN_MAX_CENTER_CELL = 0, 1, 1 << 30, 2048                      # pcr_types.h
 VOXEL_MEAN_MAX_ROWS = 1 << 32                                                                           # pcr_types.h
+LOD_MAX_LEVELS, LOD_DROP_REST, LOD_ROW_ORDER = 16, 1, 2                                                 # pcr_types.h
+
+
+class Lod(C.Structure):                           # pcr_lod: nested lattices, level l with the cell cell << (levels - 1 - l), 24 bytes
+    _fields_ = [("origin", c_i32 * 3), ("cell", c_i32), ("levels", c_i32), ("reserved", c_i32)]
+
+
+class LodStats(C.Structure):                      # pcr_lod_stats
+    _fields_ = [(n, c_i64) for n in ("batches_outside", "batches_decoded", "points_considered", "runs", "table_slots", "points_written")] + [
+        ("level_count", c_i64 * (LOD_MAX_LEVELS + 1))]
+
+    def as_dict(self) -> dict:
+        d = {n: int(getattr(self, n)) for n, _ in self._fields_[:-1]}
+        d["level_count"] = [int(v) for v in self.level_count]
+        return d
 
 
 class DenoiseStats(C.Structure):                  # pcr_denoise_stats
@@ -233,6 +248,7 @@ assert C.sizeof(DisplayOpts) == 16
 assert C.sizeof(Grid) == 24 and C.sizeof(GridStats) == 24 and C.sizeof(QuantileStats) == 48
 assert C.sizeof(GroundParams) == 136 and C.sizeof(GroundStats) == 48 and C.sizeof(HeightStats) == 32
 assert C.sizeof(Voxels) == 16 and C.sizeof(ThinStats) == 48 and C.sizeof(DenoiseStats) == 72 and C.sizeof(ComponentsStats) == 88
+assert C.sizeof(Lod) == 24 and C.sizeof(LodStats) == 48 + 8 * (LOD_MAX_LEVELS + 1)
 assert C.sizeof(NeighborsStats) == 80 and C.sizeof(Moments) == 80 and C.sizeof(Eigen) == 48
 assert C.sizeof(XyzBatch) == 64 and C.sizeof(GpuBatch) == 160 and C.sizeof(FileHeader) == 40 and C.sizeof(RenderParams) == 224
 
@@ -269,6 +285,7 @@ HIP_SYMBOLS = [
     "pcr_local_moments", "pcr_read_local_moments", "pcr_moments_eigen",
     "pcr_knn", "pcr_read_knn",
     "pcr_voxel_mean", "pcr_read_voxel_mean",
+    "pcr_lod_order", "pcr_read_lod_order",
 ]
 
 HOST_SYMBOLS = [
@@ -427,6 +444,9 @@ def hip_lib() -> C.CDLL:
         for n in ("pcr_voxel_mean", "pcr_read_voxel_mean"):
             getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Voxels), C.POINTER(Box), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.POINTER(c_i64), C.POINTER(ThinStats)]
+        for n in ("pcr_lod_order", "pcr_read_lod_order"):
+            getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Lod), C.POINTER(Box), c_u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.POINTER(c_i64), C.POINTER(LodStats)]
         _hip = lib
     return _hip
 

@@ -222,6 +222,18 @@ struct pcr_ctx {
     int64_t voxel_acc_records = 0;
     VoxelRec *d_voxel_rec = nullptr;                    // [voxel_rec_records]
     int64_t voxel_rec_records = 0;
+    // levels of detail (pcr_lod_order / pcr_read_lod_order) share pcr_thin's scratch; their own: the tables of the coarser levels
+    // (two, used in turn), the level byte of every row, the batches with their "the clip cuts it" bit, the counts and then the
+    // offsets per (batch, level), and the occupied slots of every level
+    ThinSlot *d_lod_tables = nullptr;                   // [lod_slots]
+    int64_t lod_slots = 0;
+    uint8_t *d_lod_level = nullptr;                     // [lod_level_rows] a byte per row of the call's range
+    int64_t lod_level_rows = 0;
+    uint32_t *d_lod_list = nullptr;                     // [lod_list_batches]
+    int64_t lod_list_batches = 0;
+    int64_t *d_lod_batch = nullptr;                     // [lod_batch_words] (levels + 1) words per listed batch
+    int64_t lod_batch_words = 0;
+    unsigned long long *d_lod_occupied = nullptr;       // [PCR_LOD_MAX_LEVELS]
     int64_t prepass_batches = 0;
     static constexpr int FENCES = 8;
     hipEvent_t fence[FENCES] = {};              // pcr_fence_record / pcr_fence_wait: device-scope ordering between streams
@@ -334,6 +346,8 @@ void free_stream_buffers(pcr_ctx *c)
     dfree(c->d_knn_dense); c->knn_dense_words = 0;
     dfree(c->d_voxel_prefix); c->voxel_prefix_words = 0; dfree(c->d_voxel_acc); c->voxel_acc_records = 0;
     dfree(c->d_voxel_rec); c->voxel_rec_records = 0;
+    dfree(c->d_lod_tables); c->lod_slots = 0; dfree(c->d_lod_level); c->lod_level_rows = 0; dfree(c->d_lod_list); c->lod_list_batches = 0;
+    dfree(c->d_lod_batch); c->lod_batch_words = 0; dfree(c->d_lod_occupied);
 
     if (c->any_generic_pending && c->any_generic_ev) (void)hipEventSynchronize(c->any_generic_ev);
     c->any_generic_pending = false;
@@ -2776,10 +2790,12 @@ struct VoxelPlan {
 // The two kinds of voxel table: the lattice (pcr_lattice.h), its voxel limit as the messages put it, and how the table starts.
 // ones: every byte of the table 0xFF and the keep bitmap zeroed, for k_thin_mark's minima and k_thin_flag's bits; otherwise
 // k_denoise_clear: key = all ones and value = 0 in every slot (every lane of a listed batch stores its keep word later).
+// levels > 0: the lattice is lod_lattice with that many levels (`lattice` is not called).
 struct VoxelTable {
     int (*lattice)(const int32_t origin[3], int32_t cell, const int32_t qmin[3], const int32_t qmax[3], ThinLattice *out, int *axis);
     const char *max_voxels;
     bool ones;
+    int32_t levels = 0;
 };
 constexpr VoxelTable THIN_TABLE{thin_lattice, "2^21", true}, NOISE_TABLE{noise_lattice, "2^21 - 2", false};
 
@@ -2801,7 +2817,8 @@ int voxel_plan_begin(pcr_ctx *c, int64_t first, int64_t n, const pcr_voxels &vox
     const int64_t nL = (int64_t)p.listed.size();
     if (nL == 0) return PCR_OK;
     int axis = 0;
-    switch (table.lattice(vox.origin, vox.cell, q.min, q.max, &a.lat, &axis)) {
+    switch (table.levels > 0 ? lod_lattice(vox.origin, vox.cell, table.levels, q.min, q.max, &a.lat, &axis)
+                             : table.lattice(vox.origin, vox.cell, q.min, q.max, &a.lat, &axis)) {
     case THIN_LATTICE_EXTENT:
         return set_err(c, PCR_E_ARG, "the points to %s span %lld on axis %d, 2^31 or more: pass a clip or a larger %s (a tail artefact far outside the cloud?)",
                        verb, (long long)q.max[axis] - (long long)q.min[axis], axis, cell);
@@ -3130,6 +3147,259 @@ int pcr_read_thin(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_voxe
                   int64_t *host_rows, size_t capacity_points, int64_t *out_count, pcr_thin_stats *stats)
 {
     return thin_call(c, first_batch, count, vox, clip, mode, KeptOut{true, host_points, capacity_points, {{"rows", host_rows, 8}}}, out_count, stats);
+}
+
+// ---- levels of detail --------------------------------------------------------------------------
+namespace {
+// What lod_plan leaves for the writes: the counts per (listed batch, level) and the kernels' arguments
+struct LodPlan {
+    ThinPlan p;
+    pcr_lod_stats st{};
+    LodArgs a{};
+    int64_t nL = 0;
+    int classes = 0;                    // the levels written: L + 1, or L where the rest is dropped
+    std::vector<int64_t> counts;        // [nL * (L + 1)]
+    std::vector<int64_t> offsets;       // staging of the write kernel's offsets (alive until the stream has been synchronised)
+};
+
+// pcr_thin's FIRST plan on the lattice of lod_lattice, then the tables of the coarser levels, one after the other from the
+// finest, each sized from the occupied slots of the one below, and the level byte of every winning row. Fills st up to
+// level_count; st.runs == 0: nothing to do, no kernel has touched a table. Synchronises.
+int lod_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_lod &lod, const pcr_box *clip, LodPlan &lp)
+{
+    const int L = lod.levels;
+    VoxelPlan v;
+    char limit[32];
+    snprintf(limit, sizeof limit, "2^21 - %d", 1 << (L - 1));
+    const VoxelTable table{nullptr, L == 1 ? "2^21" : limit, true, L};
+    const pcr_voxels vox{{lod.origin[0], lod.origin[1], lod.origin[2]}, lod.cell};
+    int rc = voxel_plan_begin(c, first, n, vox, clip, "order", table, 62, lp.p, v);      // (2^40 rows: never more than 2^41 slots)
+    lp.st = pcr_lod_stats{v.batches_outside, v.batches_decoded, v.points_considered, v.runs, v.table_slots, 0, {}};
+    lp.nL = v.nL;
+    if (rc || v.runs == 0) return rc;
+    const int64_t rows = n * PCR_POINTS_PER_BATCH;
+    if (!thin_grow((void **)&c->d_lod_level, c->lod_level_rows, rows, 1))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the level bytes of %lld batches", (long long)n);
+    if (!c->d_lod_occupied && hipMalloc((void **)&c->d_lod_occupied, PCR_LOD_MAX_LEVELS * 8) != hipSuccess)
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the counters of the levels");
+    HIP_TRY(c, hipMemsetAsync(c->d_lod_level, 0xFF, (size_t)rows, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_lod_occupied, 0, PCR_LOD_MAX_LEVELS * 8, c->stream));
+
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)v.nL), block(PCR_WORKGROUP_SIZE);
+    if (v.windows) hipLaunchKernelGGL((k_thin_mark<LAYOUT_POINT_WINDOWS, PCR_THIN_FIRST>), grid, block, 0, c->stream, s, c->d_thin_list, v.a);
+    else           hipLaunchKernelGGL((k_thin_mark<LAYOUT_WORDS, PCR_THIN_FIRST>), grid, block, 0, c->stream, s, c->d_thin_list, v.a);
+    HIP_TRY(c, hipGetLastError());
+
+    // occupied[l]: the voxels of level l. The error word travels with every counter: an overflow ends the call at its level.
+    unsigned long long occupied[PCR_LOD_MAX_LEVELS] = {};
+    uint32_t error = 0;
+    auto mark = [&](const ThinSlot *t, int64_t slots, int l) -> int {
+        hipLaunchKernelGGL(k_lod_mark, dim3((unsigned)std::min<int64_t>((slots + 255) / 256, 4096)), dim3(256), 0, c->stream, t, (unsigned long long)slots,
+                           (unsigned long long)rows, (uint32_t)l, c->d_lod_level, c->d_lod_occupied + l);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(&occupied[l], c->d_lod_occupied + l, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(&error, c->d_thin_error, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (error) return set_err(c, PCR_E_NOMEM, "voxel table overflow at level %d: %lld slots", l, (long long)slots);
+        return PCR_OK;
+    };
+    if ((rc = mark(c->d_thin_table, v.table_slots, L - 1))) return rc;
+    // The tables of levels L - 2 .. 0 take turns in two halves of one allocation: a level has at most the voxels of the level
+    // below it, so no table is larger than the first of them.
+    const ThinSlot *src = c->d_thin_table;
+    int64_t src_slots = v.table_slots, half = 0;
+    for (int l = L - 2; l >= 0; --l) {
+        uint32_t log2_slots = 10;
+        while (((int64_t)1 << log2_slots) < 2 * (int64_t)occupied[l + 1]) ++log2_slots;
+        const int64_t slots = (int64_t)1 << log2_slots;
+        if (l == L - 2) {
+            half = slots;
+            if (!thin_grow((void **)&c->d_lod_tables, c->lod_slots, L > 2 ? 2 * half : half, sizeof(ThinSlot)))
+                return set_err(c, PCR_E_NOMEM, "out of device memory for the voxel tables of the coarser levels (%lld slots): pass a clip or a larger cell",
+                               (long long)(L > 2 ? 2 * half : half));
+        }
+        ThinSlot *dst = c->d_lod_tables + (((L - 2 - l) & 1) ? half : 0);
+        HIP_TRY(c, hipMemsetAsync(dst, 0xFF, (size_t)slots * sizeof(ThinSlot), c->stream));
+        ThinArgs a = v.a;
+        a.log2_slots = log2_slots; a.table = dst;
+        hipLaunchKernelGGL(k_lod_coarsen, dim3((unsigned)std::min<int64_t>((src_slots + 255) / 256, 4096)), dim3(256), 0, c->stream, src,
+                           (unsigned long long)src_slots, a);
+        HIP_TRY(c, hipGetLastError());
+        if ((rc = mark(dst, slots, l))) return rc;
+        src = dst; src_slots = slots;
+    }
+    lp.st.level_count[0] = (int64_t)occupied[0];
+    for (int l = 1; l < L; ++l) lp.st.level_count[l] = (int64_t)occupied[l] - (int64_t)occupied[l - 1];
+    lp.st.level_count[L] = v.points_considered - (int64_t)occupied[L - 1];
+    lp.a.q = v.a.q; lp.a.first_batch = (uint32_t)first; lp.a.levels = (uint32_t)L; lp.a.level = c->d_lod_level;
+    return PCR_OK;
+}
+
+// After lod_plan, for a call that writes: the final level bytes, the keep words and the counts per (listed batch, level); for
+// PCR_LOD_ROW_ORDER the plan kept_write takes as well. A batch whose box lies inside the clip is not decoded. Synchronises.
+int lod_count(pcr_ctx *c, int64_t first, const pcr_box *clip, bool row_order, LodPlan &lp)
+{
+    const int64_t nL = lp.nL, per = (int64_t)lp.a.levels + 1;
+    std::vector<uint32_t> list(lp.p.listed);
+    for (int64_t k = 0; clip && k < nL; ++k) {
+        const int32_t *bb = c->h_point_bounds.data() + (int64_t)list[(size_t)k] * 6;
+        bool within = true;
+        for (int d = 0; d < 3; ++d) within = within && bb[d] >= clip->min[d] && bb[3 + d] <= clip->max[d];
+        if (!within) list[(size_t)k] |= LOD_CUT;
+    }
+    if (!thin_grow((void **)&c->d_lod_list, c->lod_list_batches, nL, 4) || !thin_grow((void **)&c->d_lod_batch, c->lod_batch_words, nL * per, 8))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for the lists of %lld batches", (long long)nL);
+    HIP_TRY(c, hipMemcpyAsync(c->d_lod_list, list.data(), (size_t)nL * 4, hipMemcpyHostToDevice, c->stream));
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)nL), block(PCR_WORKGROUP_SIZE);
+    if (select_reads_windows(c)) hipLaunchKernelGGL((k_lod_count<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_lod_list, lp.a, c->d_thin_keep, c->d_lod_batch);
+    else                         hipLaunchKernelGGL((k_lod_count<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_lod_list, lp.a, c->d_thin_keep, c->d_lod_batch);
+    HIP_TRY(c, hipGetLastError());
+    lp.counts.assign((size_t)(nL * per), 0);
+    HIP_TRY(c, hipMemcpyAsync(lp.counts.data(), c->d_lod_batch, (size_t)(nL * per) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // the two ways of counting a level agree, or nothing is written: the offsets below rest on these counts
+    for (int64_t l = 0; l < per; ++l) {
+        int64_t sum = 0;
+        for (int64_t k = 0; k < nL; ++k) sum += lp.counts[(size_t)(k * per + l)];
+        if (sum != lp.st.level_count[l])
+            return set_err(c, PCR_E_HIP, "level %lld holds %lld records by batch and %lld by table", (long long)l, (long long)sum, (long long)lp.st.level_count[l]);
+    }
+    if (row_order)
+        for (int64_t k = 0; k < nL; ++k) {
+            int64_t m = 0;
+            for (int l = 0; l < lp.classes; ++l) m += lp.counts[(size_t)(k * per + l)];
+            if (m) { lp.p.writers.push_back(lp.p.listed[(size_t)k]); lp.p.cnt.push_back(m); }
+        }
+    (void)first;
+    return PCR_OK;
+}
+
+// Enqueue the level-ordered write of listed batches [k0, k1): level l of them starts at record base[l] of the destinations d and
+// takes room[l] records there; d holds `total` records. The caller synchronises.
+int lod_emit(pcr_ctx *c, int64_t k0, int64_t k1, LodPlan &lp, const int64_t *base, int64_t total, const KeptOut &d)
+{
+    const int64_t per = (int64_t)lp.a.levels + 1;
+    if (k0 == k1) return PCR_OK;
+    lp.offsets.assign((size_t)((k1 - k0) * per), 0);
+    int64_t at[LOD_CLASSES];
+    for (int l = 0; l < LOD_CLASSES; ++l) at[l] = base[l];
+    for (int64_t k = k0; k < k1; ++k)
+        for (int l = 0; l < lp.classes; ++l) { lp.offsets[(size_t)((k - k0) * per + l)] = at[l]; at[l] += lp.counts[(size_t)(k * per + l)]; }
+    HIP_TRY(c, hipMemcpyAsync(c->d_lod_batch + k0 * per, lp.offsets.data(), (size_t)((k1 - k0) * per) * 8, hipMemcpyHostToDevice, c->stream));
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)(k1 - k0)), block(PCR_WORKGROUP_SIZE);
+    for_layout_bc7(c, [&](auto layout, auto bc7) {
+        hipLaunchKernelGGL((k_lod_write<layout.value, bc7.value>), grid, block, 0, c->stream, s, c->d_lod_list + k0, lp.a, c->d_lod_batch + k0 * per,
+                           (unsigned long long)total, static_cast<uint4 *>(d.points), static_cast<int64_t *>(d.col[0].dst), static_cast<uint8_t *>(d.col[1].dst));
+    });
+    HIP_TRY(c, hipGetLastError());
+    return PCR_OK;
+}
+
+// The records in (level, row) order. On the device one launch over every listed batch; to the host in pieces of at most
+// DECODE_STAGE_BATCHES batches of the range: a piece goes into the stages in its own (level, row) order, then each of its levels
+// to the place behind the earlier pieces' records of that level. Synchronises.
+int lod_write_levels(pcr_ctx *c, int64_t first, int64_t n, LodPlan &lp, const KeptOut &o)
+{
+    const int64_t per = (int64_t)lp.a.levels + 1, nL = lp.nL;
+    int rc;
+    int64_t base[LOD_CLASSES] = {};                 // where every level starts in the result
+    for (int l = 1; l < lp.classes; ++l) base[l] = base[l - 1] + lp.st.level_count[l - 1];
+    if (!o.host) {
+        if ((rc = lod_emit(c, 0, nL, lp, base, lp.st.points_written, o))) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return PCR_OK;
+    }
+    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
+    KeptOut d;
+    if (const char *what = stage_reserve(c, o, piece, d))
+        return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of %s", (long long)piece, what);
+    int64_t k0 = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += piece) {
+        const int64_t i1 = std::min(n, i0 + piece);
+        int64_t k1 = k0;
+        int64_t room[LOD_CLASSES] = {}, start[LOD_CLASSES] = {}, m = 0;
+        for (; k1 < nL && lp.p.listed[(size_t)k1] < (uint32_t)(first + i1); ++k1)
+            for (int l = 0; l < lp.classes; ++l) room[l] += lp.counts[(size_t)(k1 * per + l)];
+        for (int l = 0; l < lp.classes; ++l) { start[l] = m; m += room[l]; }
+        if (m) {
+            if ((rc = lod_emit(c, k0, k1, lp, start, m, d))) return rc;
+            for (int l = 0; l < lp.classes; ++l) {
+                if (!room[l]) continue;
+                if (d.points)
+                    HIP_TRY(c, hipMemcpyAsync(static_cast<pcr_point *>(o.points) + base[l], static_cast<pcr_point *>(d.points) + start[l],
+                                              (size_t)room[l] * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
+                for (int i = 0; i < 2; ++i) {
+                    const size_t row_bytes = o.col[i].row_bytes;
+                    if (d.col[i].dst)
+                        HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(o.col[i].dst) + (size_t)base[l] * row_bytes,
+                                                  static_cast<char *>(d.col[i].dst) + (size_t)start[l] * row_bytes, (size_t)room[l] * row_bytes,
+                                                  hipMemcpyDeviceToHost, c->stream));
+                }
+                base[l] += room[l];
+            }
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+        }
+        k0 = k1;
+    }
+    return PCR_OK;
+}
+
+// pcr_lod_order / pcr_read_lod_order
+int lod_call(pcr_ctx *c, int64_t first, int64_t count, const pcr_lod *lod, const pcr_box *clip, uint32_t flags, const KeptOut &o, int64_t *out_count,
+             pcr_lod_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int64_t n = 0;
+    bool done = true;
+    KeptOut checked = o;
+    checked.col[1].dst = nullptr;                   // (the levels are bytes: on the host any address will do)
+    int rc = kept_begin(c, first, count, checked, out_count, &n);
+    if (rc) return rc;
+    if (!lod) return set_err(c, PCR_E_ARG, "the level-of-detail lattice is NULL");
+    if (!o.host && o.col[1].dst && reinterpret_cast<uintptr_t>(o.col[1].dst) % 8 != 0)
+        return set_err(c, PCR_E_ARG, "the destination of the levels is misaligned (8 bytes)");
+    if (flags & ~(PCR_LOD_DROP_REST | PCR_LOD_ROW_ORDER)) return set_err(c, PCR_E_ARG, "flags 0x%x: only PCR_LOD_DROP_REST and PCR_LOD_ROW_ORDER are known", flags);
+    if (lod->reserved != 0) return set_err(c, PCR_E_ARG, "pcr_lod::reserved is %d, not 0", lod->reserved);
+    if (lod->levels < 1 || lod->levels > PCR_LOD_MAX_LEVELS)
+        return set_err(c, PCR_E_ARG, "%d levels: the number of levels is 1 .. %d (PCR_LOD_MAX_LEVELS)", lod->levels, PCR_LOD_MAX_LEVELS);
+    if (lod->cell < 1 || ((int64_t)lod->cell << (lod->levels - 1)) > PCR_THIN_MAX_CELL)
+        return set_err(c, PCR_E_ARG, "finest cell of %d with %d levels: the coarsest edge length, cell << (levels - 1), is 1 .. %d (PCR_THIN_MAX_CELL)",
+                       lod->cell, lod->levels, PCR_THIN_MAX_CELL);
+    if ((rc = kept_row_limit(c, n, (int64_t)1 << 40, ROWS_2_40))) return rc;
+    LodPlan lp;
+    const bool drop = (flags & PCR_LOD_DROP_REST) != 0, row_order = (flags & PCR_LOD_ROW_ORDER) != 0;
+    lp.classes = lod->levels + (drop ? 0 : 1);
+    if ((rc = lod_plan(c, first, n, *lod, clip, lp))) return rc;
+    lp.a.classes = (uint32_t)lp.classes;
+    lp.st.points_written = lp.st.points_considered - (drop ? lp.st.level_count[lod->levels] : 0);
+    if ((rc = kept_finish(c, o, lp.st.points_written, "to write", lp.st, out_count, stats, &done)) || done) return rc;
+    if ((rc = lod_count(c, first, clip, row_order, lp))) return rc;
+    if (!row_order) return lod_write_levels(c, first, n, lp, o);
+    return kept_write(c, first, n, lp.p, o, [&](int64_t i0, int64_t i1, const KeptOut &d) {
+        return kept_emit(c, first, i0, i1, lp.p, [&](auto layout, auto bc7, const EmitAt &e) {
+            hipLaunchKernelGGL((k_lod_rows<layout.value, bc7.value>), e.grid, e.block, 0, c->stream, e.s, e.list, (uint32_t)first, c->d_thin_keep, e.offsets,
+                               static_cast<uint4 *>(d.points), static_cast<int64_t *>(d.col[0].dst), c->d_lod_level, static_cast<uint8_t *>(d.col[1].dst));
+        });
+    }, true);
+}
+} // namespace
+
+int pcr_lod_order(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_lod *lod, const pcr_box *clip, uint32_t flags, void *dev_points, void *dev_rows,
+                  void *dev_levels, size_t capacity_points, int64_t *out_count, pcr_lod_stats *stats)
+{
+    return lod_call(c, first_batch, count, lod, clip, flags, KeptOut{false, dev_points, capacity_points, {{"rows", dev_rows, 8}, {"levels", dev_levels, 1}}},
+                    out_count, stats);
+}
+
+int pcr_read_lod_order(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_lod *lod, const pcr_box *clip, uint32_t flags, pcr_point *host_points,
+                       int64_t *host_rows, uint8_t *host_levels, size_t capacity_points, int64_t *out_count, pcr_lod_stats *stats)
+{
+    return lod_call(c, first_batch, count, lod, clip, flags, KeptOut{true, host_points, capacity_points, {{"rows", host_rows, 8}, {"levels", host_levels, 1}}},
+                    out_count, stats);
 }
 
 // ---- voxel denoising ---------------------------------------------------------------------------

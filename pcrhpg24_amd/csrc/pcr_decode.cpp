@@ -2,6 +2,7 @@
 // decoder outside the render kernels is the per-chain CPU one of include/huffman.h:433-477.
 //     pcr_decode <in.huffman> <out.las> [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --thin CELL [--center | --mean] [--box x0 y0 z0 x1 y1 z1]
+//     pcr_decode <in.huffman> <out.las> --lod CELL LEVELS [--drop-rest] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --denoise CELL MAXCOUNT [--isolated] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --components CELL MINPOINTS [--conn 6|26] [--small] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --radius R MINCOUNT [--sparse] [--box x0 y0 z0 x1 y1 z1]
@@ -20,7 +21,8 @@
 // camera draws (pcr_render's camera arguments and defaults), and of those the ones inside --rect, a rectangle of pixels
 // (pcr_read_screen); with --visible of those only the ones that make up the picture (pcr_read_visible). With --ortho no points are read back at all: the stream is rasterized top-down on the GPU (pcr_read_grid) into
 // an orthophoto and, with --dsm, a surface model. With --thin one point per cubic voxel is read back (pcr_read_thin): the cloud
-// decimated on the GPU without ever existing in full. With --polygon only the points inside a polygon prism of world coordinates are
+// decimated on the GPU without ever existing in full. With --lod the points come back ordered by nested voxel lattices, coarse
+// to fine (pcr_read_lod_order): a file whose every prefix up to a level boundary is a thinned cloud. With --polygon only the points inside a polygon prism of world coordinates are
 // read back (pcr_read_polygon). With --denoise the points come back without the isolated ones, or those alone (pcr_read_denoise).
 // With --components they come back without the connected components of voxels below a size, or those alone (pcr_read_components).
 // With --radius they come back without those that have fewer than a number of points within a radius, or those alone: the radius
@@ -48,6 +50,7 @@ using namespace pcr_host;
 static const char *USAGE =
     "usage: pcr_decode <in.huffman> <out.las> [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --thin CELL [--center | --mean] [--box x0 y0 z0 x1 y1 z1]\n"
+    "       pcr_decode <in.huffman> <out.las> --lod CELL LEVELS [--drop-rest] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --denoise CELL MAXCOUNT [--isolated] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --components CELL MINPOINTS [--conn 6|26] [--small] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --radius R MINCOUNT [--sparse] [--box x0 y0 z0 x1 y1 z1]\n"
@@ -75,6 +78,12 @@ static const char *USAGE =
     "  point in that order, with --center the one nearest to the voxel's centre, with --mean (not with --center) the mean of the\n"
     "  voxel's points instead, position and colour, rounded to the lattice. Only the points inside --box count, or inside\n"
     "  the box of the file's header. No point there is an error.\n"
+    "  --lod CELL LEVELS: the points in level-of-detail order. LEVELS (1 .. 16) nested lattices of cubic voxels, the finest of\n"
+    "  CELL world units (the lattice of --thin), every coarser one of twice the edge: first the points that are the first of their\n"
+    "  voxel of the coarsest lattice, then those of the next finer one, and so on, last the points that are first in no voxel\n"
+    "  (--drop-rest: without them); inside a level in the stream's order. The point records of the file cut off where a level\n"
+    "  ends (the `level k: n` lines tell the counts) are --thin with that level's cell. Only the points inside --box count, or\n"
+    "  inside the box of the file's header. No point there is an error. It combines with no other selecting option.\n"
     "  --denoise CELL MAXCOUNT: the points without the isolated ones, in the stream's order. A point is isolated if the 3 x 3 x 3\n"
     "  cubic voxels of CELL world units around its own (the lattice of --thin) hold at most MAXCOUNT points (a whole number >= 0),\n"
     "  the point itself and exact duplicates included. --isolated: the isolated points instead. Only the points inside --box\n"
@@ -237,6 +246,37 @@ static bool parse_thin(int argc, char **argv, int at, Thin &t)
         }
     }
     return !(t.center && t.mean);
+}
+
+struct Lod {
+    double cell = 0.0;
+    int levels = 0;
+    bool drop_rest = false, has_box = false;
+    double lo[3], hi[3];
+};
+
+// the options behind --lod, every one well formed, or false
+static bool parse_lod(int argc, char **argv, int at, Lod &l)
+{
+    if (argc < at + 3 || std::strcmp(argv[at], "--lod") != 0) return false;
+    if (!parse_double(argv[at + 1], l.cell) || !(l.cell > 0.0)) return false;
+    char *end = nullptr;
+    errno = 0;
+    const long long levels = std::strtoll(argv[at + 2], &end, 10);
+    if (end == argv[at + 2] || *end != '\0' || errno == ERANGE || levels < 1 || levels > PCR_LOD_MAX_LEVELS) return false;
+    l.levels = (int)levels;
+    for (int i = at + 3; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--box" && i + 6 < argc && !l.has_box) {
+            for (int k = 0; k < 6; ++k) if (!parse_double(argv[++i], k < 3 ? l.lo[k] : l.hi[k - 3])) return false;
+            l.has_box = true;
+        } else if (a == "--drop-rest" && !l.drop_rest) {
+            l.drop_rest = true;
+        } else {
+            return false;                                               // (--thin, --denoise, ...: it combines with no other mode)
+        }
+    }
+    return true;
 }
 
 struct Denoise {
@@ -713,6 +753,8 @@ int main(int argc, char **argv)
     const bool viewed = argc > 3 && std::strcmp(argv[3], "--view") == 0, orthoed = argc > 3 && std::strcmp(argv[3], "--ortho") == 0;
     Thin thin;
     const bool thinned = argc > 3 && std::strcmp(argv[3], "--thin") == 0;
+    Lod lod;
+    const bool lodded = argc > 3 && std::strcmp(argv[3], "--lod") == 0;
     Poly poly;
     const bool polygoned = argc > 3 && std::strcmp(argv[3], "--polygon") == 0;
     Denoise noise;
@@ -729,9 +771,9 @@ int main(int argc, char **argv)
     const bool sored = argc > 3 && std::strcmp(argv[3], "--sor") == 0;
     Percentile pctl;
     const bool percentiled = argc > 3 && std::strcmp(argv[3], "--percentile") == 0;
-    const bool boxed = argc > 3 && !percentiled && !viewed && !orthoed && !thinned && !polygoned && !denoised && !componented && !grounded && !radiused && !normaled && !sored;
+    const bool boxed = argc > 3 && !percentiled && !viewed && !orthoed && !thinned && !lodded && !polygoned && !denoised && !componented && !grounded && !radiused && !normaled && !sored;
     if (argc < 3 || (polygoned && !parse_polygon(argc, argv, 3, poly)) || (boxed && !parse_box(argc, argv, 3, lo, hi)) || (viewed && !parse_view(argc, argv, 3, view)) ||
-        (orthoed && !parse_ortho(argc, argv, 3, ortho)) || (thinned && !parse_thin(argc, argv, 3, thin)) || (denoised && !parse_denoise(argc, argv, 3, noise)) ||
+        (orthoed && !parse_ortho(argc, argv, 3, ortho)) || (thinned && !parse_thin(argc, argv, 3, thin)) || (lodded && !parse_lod(argc, argv, 3, lod)) || (denoised && !parse_denoise(argc, argv, 3, noise)) ||
         (componented && !parse_components(argc, argv, 3, comps)) || (grounded && !parse_ground(argc, argv, 3, ground)) ||
         (radiused && !parse_radius(argc, argv, 3, rad)) || (normaled && !parse_normals(argc, argv, 3, nrm)) ||
         (sored && !parse_sor(argc, argv, 3, sor)) || (percentiled && !parse_percentile(argc, argv, 3, pctl))) { std::fputs(USAGE, stderr); return 2; }
@@ -814,6 +856,16 @@ int main(int argc, char **argv)
             std::printf("thin: cell of %d lattice steps, batches outside %lld, decoded %lld, points considered %lld, runs %lld, kept %lld, table slots %lld\n",
                         vox.cell, (long long)st.batches_outside, (long long)st.batches_decoded, (long long)st.points_considered, (long long)st.runs,
                         (long long)st.points_kept, (long long)st.table_slots);
+            if (points.empty()) throw std::runtime_error("no points inside the box: nothing written");
+        } else if (lodded) {
+            const pcr_lod nested = lodFromWorld(info, lod.cell, lod.levels, info.min);
+            const pcr_box clip = boxFromWorld(info, lod.has_box ? lod.lo : info.min, lod.has_box ? lod.hi : info.max);
+            const pcr_lod_stats st = las->lodOrdered(nested, &clip, lod.drop_rest ? PCR_LOD_DROP_REST : 0u, points);
+            std::printf("lod: finest cell of %d lattice steps, %d levels, batches outside %lld, decoded %lld, written %lld / considered %lld / runs %lld / "
+                        "table slots %lld\n", nested.cell, nested.levels, (long long)st.batches_outside, (long long)st.batches_decoded,
+                        (long long)st.points_written, (long long)st.points_considered, (long long)st.runs, (long long)st.table_slots);
+            for (int l = 0; l < nested.levels; ++l) std::printf("level %d: %lld\n", l, (long long)st.level_count[l]);
+            std::printf("rest: %lld%s\n", (long long)st.level_count[nested.levels], lod.drop_rest ? " (dropped)" : "");
             if (points.empty()) throw std::runtime_error("no points inside the box: nothing written");
         } else if (denoised) {
             const pcr_voxels vox = voxelsFromWorld(info, noise.cell, info.min);

@@ -3245,6 +3245,188 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_thin_write(StreamView s,
 }
 
 // ------------------------------------------------------------------------------------------------
+// Levels of detail (pcr_lod_order / pcr_read_lod_order): the candidates of pcr_thin ordered by `levels` nested lattices, level l
+// (0 = coarsest) with the cell cell << (levels - 1 - l). level(p) = the least l at which p has the lowest row of its voxel,
+// `levels` ("the rest") if at none. k_thin_runs and k_thin_mark<FIRST> (above) fill the finest table on the lattice of lod_lattice
+// (pcr_lattice.h); then, the sizes in between computed by the host:
+//   k_lod_coarsen  a thread per slot of level l + 1: (parent key, row) of an occupied slot into the table of level l with
+//                  thin_insert. The minimum over the children's lowest rows is the lowest row of the parent voxel.
+//   k_lod_mark     a thread per slot of a level's table: l into the level byte of the slot's row, and the occupied slots counted
+//                  (the host sizes the next table from them; their differences are the level counts). Launched from the finest
+//                  level to the coarsest, in stream order: the last store into a row's byte is its least level. The lattices are
+//                  nested, so a row that is the lowest of a voxel of level l is the lowest of its voxel of every finer level: the
+//                  levels between its least one and the finest stored before it, none is missing.
+//   k_lod_count    a workgroup per listed batch: the bytes made final (a candidate whose byte was never stored gets `levels`; a
+//                  row outside the clip keeps LOD_NO_LEVEL), the keep word of every chain and the batch's records per level. Only
+//                  a batch the clip cuts is decoded (colourless); in any other every row is a candidate.
+//   k_lod_write    a workgroup per listed batch, decode with colour: a stable partition of the batch's written records by level.
+//                  Per level an exclusive prefix over the 1024 chains' counts (wave shuffles, then the 16 wave sums through LDS)
+//                  gives every (chain, level) its first index; the running indices live in LDS as 16-bit words, a column per
+//                  lane -- the greatest value a prefix takes is 1023 * 64, the greatest index stored to 65 535 -- and are picked by
+//                  the record's level at run time; a register array indexed that way would go to scratch. The chain's 64 level
+//                  bytes sit in eight 64-bit registers that move down one place every eight points, so no register is indexed
+//                  at run time either.
+//   k_lod_rows     PCR_LOD_ROW_ORDER: write_kept_rows with the level byte as the extra column.
+// No workgroup waits for another one; the probe loops are thin_insert's.
+// ------------------------------------------------------------------------------------------------
+struct LodArgs {
+    pcr_box q;                      // the clip (every int32 point if the call has none)
+    uint32_t first_batch;           // row = (b - first_batch) * 65536 + chain * 64 + i
+    uint32_t levels;                // L
+    uint32_t classes;               // the levels a call writes: L + 1, or L with PCR_LOD_DROP_REST
+    uint8_t *level;                 // [rows of the range]
+};
+constexpr uint32_t LOD_CUT = 1u << 31;                      // in a list entry: the clip cuts the batch's box
+constexpr int LOD_CLASSES = PCR_LOD_MAX_LEVELS + 1;
+
+__global__ void __launch_bounds__(256) k_lod_coarsen(const ThinSlot *src, thin_u64 src_slots, ThinArgs dst)
+{
+    for (thin_u64 i = (thin_u64)blockIdx.x * blockDim.x + threadIdx.x; i < src_slots; i += (thin_u64)gridDim.x * blockDim.x) {
+        const thin_u64 key = src[i].key;
+        if (key != THIN_EMPTY) thin_insert(dst, lod_parent_key(key), src[i].val);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_lod_mark(const ThinSlot *table, thin_u64 slots, thin_u64 rows, uint32_t l, uint8_t *level, thin_u64 *occupied)
+{
+    uint32_t n = 0;
+    for (thin_u64 i = (thin_u64)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (thin_u64)gridDim.x * blockDim.x) {
+        if (table[i].key == THIN_EMPTY) continue;
+        ++n;
+        const thin_u64 row = table[i].val & THIN_ROW_MASK;
+        if (row < rows) level[row] = (uint8_t)l;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d, 64);
+    if ((threadIdx.x & 63u) == 0 && n) atomicAdd(occupied, (thin_u64)n);
+}
+
+// The 64 level bytes of chain `tid` of the batch at `row0`, eight to a word
+__device__ __forceinline__ void lod_load_bytes(const uint8_t *level, thin_u64 row0, thin_u64 (&w)[8])
+{
+    const uint4 *src = reinterpret_cast<const uint4 *>(level + row0);           // (row0 is a multiple of 64, the array 256-byte aligned)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint4 v = src[k];
+        w[2 * k] = (thin_u64)v.x | ((thin_u64)v.y << 32);
+        w[2 * k + 1] = (thin_u64)v.z | ((thin_u64)v.w << 32);
+    }
+}
+
+__device__ __forceinline__ uint32_t lod_count_level(const thin_u64 (&w)[8], uint32_t level)
+{
+    uint32_t n = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) n += (uint32_t)__popcll(lod_bytes_equal(w[k], level));
+    return n;
+}
+
+// Workgroup x takes list[x]: counts[x * (levels + 1) + l] = its records of level l (the rest included, dropped or not)
+template <int LAYOUT>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_lod_count(StreamView s, const uint32_t *list, LodArgs a, thin_u64 *keep, int64_t *counts)
+{
+    const uint32_t entry = list[blockIdx.x], b = entry & ~LOD_CUT;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint32_t s_part[LOD_CLASSES][LWC_WAVES];
+    thin_u64 cand = ~0ull;
+    if (entry & LOD_CUT) {                                  // (uniform over the workgroup)
+        load_packed_table(s, b, s_table);
+        cand = 0;
+        decode_chain<LAYOUT, SEL_NO_COLOUR>(s, b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t) {
+            cand |= (thin_u64)(in_box(a.q, x, y, z) ? 1u : 0u) << (uint32_t)i;
+        });
+    }
+    const thin_u64 chain = (thin_u64)(b - a.first_batch) * PCR_WORKGROUP_SIZE + tid;
+    thin_u64 w[8];
+    lod_load_bytes(a.level, chain * PCR_POINTS_PER_THREAD, w);
+    thin_u64 word = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        w[k] = lod_bytes_final(w[k], (uint32_t)(cand >> (8 * k)) & 0xFFu, a.levels);
+        word |= (thin_u64)lod_bits_of_flags(lod_bytes_written(w[k], a.levels, a.classes)) << (8 * k);
+    }
+    uint4 *dst = reinterpret_cast<uint4 *>(a.level + chain * PCR_POINTS_PER_THREAD);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        dst[k] = make_uint4((uint32_t)w[2 * k], (uint32_t)(w[2 * k] >> 32), (uint32_t)w[2 * k + 1], (uint32_t)(w[2 * k + 1] >> 32));
+    keep[chain] = word;
+    for (uint32_t l = 0; l <= a.levels; ++l) {
+        uint32_t n = lod_count_level(w, l);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d, 64);
+        if (lane == 0) s_part[l][wave] = n;
+    }
+    __syncthreads();
+    if (tid <= a.levels) {
+        uint32_t t = 0;
+        for (int k = 0; k < LWC_WAVES; ++k) t += s_part[tid][k];
+        counts[(size_t)blockIdx.x * (a.levels + 1) + tid] = t;
+    }
+}
+
+// Workgroup x takes list[x]: its record of level l with the lowest row goes to index offsets[x * (levels + 1) + l] of points, rows
+// and levels (each may be NULL), the others of that level behind it in row order. Nothing is stored at or beyond index `total`.
+template <int LAYOUT, bool BC7>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_lod_write(StreamView s, const uint32_t *list, LodArgs a, const int64_t *offsets, thin_u64 total,
+                                                                  uint4 *points, int64_t *rows, uint8_t *levels)
+{
+    const uint32_t b = list[blockIdx.x] & ~LOD_CUT;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
+    __shared__ uint16_t s_index[LOD_CLASSES][PCR_WORKGROUP_SIZE];
+    __shared__ uint32_t s_wave[LOD_CLASSES][LWC_WAVES];
+    __shared__ int64_t s_first[LOD_CLASSES];
+    const int64_t row0 = (int64_t)(b - a.first_batch) * PCR_POINTS_PER_BATCH + (int64_t)tid * PCR_POINTS_PER_THREAD;
+    thin_u64 w[8];
+    lod_load_bytes(a.level, (thin_u64)row0, w);
+    for (uint32_t l = 0; l < a.classes; ++l) {
+        const uint32_t mine = lod_count_level(w, l);
+        uint32_t incl = mine;                               // inclusive prefix inside the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d, 64);
+            if (lane >= (uint32_t)d) incl += up;
+        }
+        if (lane == 63) s_wave[l][wave] = incl;
+        s_index[l][tid] = (uint16_t)(incl - mine);
+    }
+    if (tid < a.classes) s_first[tid] = offsets[(size_t)blockIdx.x * (a.levels + 1) + tid];
+    load_packed_table(s, b, s_table);                       // (its barrier publishes s_wave and s_first as well)
+    for (uint32_t l = 0; l < a.classes; ++l) {
+        uint32_t before = 0;
+        for (uint32_t k = 0; k < wave; ++k) before += s_wave[l][k];
+        s_index[l][tid] = (uint16_t)(s_index[l][tid] + before);                // (a lane reads and writes its own column only)
+    }
+    decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, b, s_table, [&](int i, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        const uint32_t l = (uint32_t)(w[0] >> (8u * ((uint32_t)i & 7u))) & 0xFFu;
+        if (((uint32_t)i & 7u) == 7u) {
+#pragma unroll
+            for (int k = 0; k < 7; ++k) w[k] = w[k + 1];
+        }
+        if (l < a.classes) {
+            const uint32_t at = s_index[l][tid];
+            s_index[l][tid] = (uint16_t)(at + 1u);
+            const int64_t dst = s_first[l] + at;
+            if ((thin_u64)dst < total) {
+                if (points) points[dst] = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
+                if (rows) rows[dst] = row0 + i;
+                if (levels) levels[dst] = (uint8_t)l;
+            }
+        }
+    });
+}
+
+template <int LAYOUT, bool BC7>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_lod_rows(StreamView s, const uint32_t *list, uint32_t first_batch, const thin_u64 *keep,
+                                                                 const int64_t *offsets, uint4 *points, int64_t *rows, const uint8_t *level, uint8_t *levels)
+{
+    write_kept_rows<LAYOUT, BC7>(s, list, first_batch, keep, offsets, points, rows, [&](int64_t dst, int64_t row) {
+        if (levels) levels[dst] = level[row];
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
 // Voxel denoising (pcr_denoise / pcr_read_denoise): a candidate is isolated iff the 27 voxels around its own hold at most
 // max_count candidates of the call (itself included). pcr_thin's frame with a sum in the table instead of a minimum, on the
 // lattice of noise_lattice (pcr_lattice.h: every voxel index in 1 .. 2^21 - 2, so a neighbour's key is the voxel's key plus or

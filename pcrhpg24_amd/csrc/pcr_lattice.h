@@ -1,5 +1,6 @@
-// Integer lattice arithmetic shared by the top-down grid, the voxel thinning and the voxel denoising: the exact division of a
-// 32-bit difference by a cell, and the lattices pcr_thin and pcr_denoise hand to their kernels. Plain C++ without a HIP dependency, so a host-only build can call it.
+// Integer lattice arithmetic shared by the top-down grid, the voxel thinning, the voxel denoising and the levels of detail: the
+// exact division of a 32-bit difference by a cell, the lattices pcr_thin, pcr_denoise and pcr_lod_order hand to their kernels, and
+// the level-byte arithmetic of pcr_lod_order. Plain C++ without a HIP dependency, so a host-only build can call it.
 #pragma once
 #include <cstdint>
 
@@ -50,6 +51,71 @@ inline int thin_lattice(const int32_t origin[3], int32_t cell, const int32_t qmi
     out->cell = (uint32_t)cell;
     out->div = make_cell_div((uint32_t)cell);
     return THIN_LATTICE_OK;
+}
+
+// The lattice of a level-of-detail call (pcr_lod_order): `levels` nested lattices over one origin, level l (0 = coarsest) with
+// the cell cell << (levels - 1 - l). The shift of the origin is by whole COARSEST cells C = cell << (levels - 1): origin' = origin +
+// floor((q.min - origin) / C) * C in 64 bits. A shift by whole cells of a level changes neither which points share a voxel of
+// that level nor the nesting floor(floor(d / c) / 2) == floor(d / 2c), which holds for d >= 0 counted from one origin; C is a
+// whole number of cells of every level, a finer cell would not be one of the coarser levels. For a point p inside q, d = p -
+// origin' is in [0, q.max - q.min + C): q.min - origin' is in [0, C - 1]. With an extent below 2^31 and C <= 2^30 that is less
+// than 2^32, so d fits 32 unsigned bits. The finest index is d / cell <= (q.max - q.min + C - 1) / cell <= (q.max - q.min) / cell
+// + 2^(levels - 1), because C / cell = 2^(levels - 1) is whole; the call is refused when (q.max - q.min) / cell + 2^(levels - 1) + 1
+// > 2^21, so every finest index fits its 21-bit field of the key. The level-l index is the finest one shifted right by levels - 1
+// - l (lod_parent_key, one level at a time). levels == 1 is thin_lattice. Same result codes as thin_lattice. cell >= 1, 1 <=
+// levels, cell << (levels - 1) <= 2^30.
+inline int lod_lattice(const int32_t origin[3], int32_t cell, int32_t levels, const int32_t qmin[3], const int32_t qmax[3], ThinLattice *out, int *axis)
+{
+    const int64_t coarsest = (int64_t)cell << (levels - 1);
+    for (int k = 0; k < 3; ++k) {
+        const int64_t extent = (int64_t)qmax[k] - (int64_t)qmin[k];
+        *axis = k;
+        if (extent >= (int64_t)1 << 31) return THIN_LATTICE_EXTENT;
+        if (extent / cell + ((int64_t)1 << (levels - 1)) + 1 > (int64_t)1 << THIN_KEY_BITS) return THIN_LATTICE_VOXELS;
+        const int64_t shifted = (int64_t)origin[k] + floor_div64((int64_t)qmin[k] - (int64_t)origin[k], coarsest) * coarsest;
+        out->origin[k] = (uint32_t)(uint64_t)shifted;
+    }
+    out->cell = (uint32_t)cell;
+    out->div = make_cell_div((uint32_t)cell);
+    return THIN_LATTICE_OK;
+}
+
+// The key of the voxel one level up: every 21-bit field of the key shifted right by one (the bit that leaves a field is dropped)
+constexpr unsigned long long lod_parent_key(unsigned long long key)
+{
+    return (key >> 1) & ~((1ull << (THIN_KEY_BITS - 1)) | (1ull << (2 * THIN_KEY_BITS - 1)) | (1ull << (3 * THIN_KEY_BITS - 1)));
+}
+
+// Eight level bytes in a 64-bit word, byte j that of point j (little endian). A byte is a level 0 .. levels, or LOD_NO_LEVEL.
+// Flags are 0x80 in the byte they speak of. constexpr, so that the kernels can call them as well.
+constexpr uint32_t LOD_NO_LEVEL = 0xFFu;
+constexpr unsigned long long LOD_BYTE_LOW7 = 0x7F7F7F7F7F7F7F7Full, LOD_BYTE_FLAGS = 0x8080808080808080ull, LOD_BYTE_ONES = 0x0101010101010101ull;
+constexpr unsigned long long lod_bytes_nonzero(unsigned long long w)            // (a sum of two 7-bit values never leaves its byte)
+{
+    return (((w & LOD_BYTE_LOW7) + LOD_BYTE_LOW7) | w) & LOD_BYTE_FLAGS;
+}
+constexpr unsigned long long lod_bytes_equal(unsigned long long w, uint32_t v)  // v < 256
+{
+    return ~lod_bytes_nonzero(w ^ (LOD_BYTE_ONES * v)) & LOD_BYTE_FLAGS;
+}
+constexpr unsigned long long lod_flags_of_bits(uint32_t bits)                   // bit j of bits -> the flag of byte j
+{
+    return lod_bytes_nonzero((LOD_BYTE_ONES * (bits & 0xFFu)) & 0x8040201008040201ull);
+}
+constexpr uint32_t lod_bits_of_flags(unsigned long long flags)                  // the flag of byte j -> bit j (the partial products meet in no bit)
+{
+    return (uint32_t)(((flags >> 7) * 0x0102040810204080ull) >> 56);
+}
+// The final bytes: a candidate (bit j of cand) that won at no level (LOD_NO_LEVEL) gets `levels`, the rest; others stay.
+constexpr unsigned long long lod_bytes_final(unsigned long long w, uint32_t cand, uint32_t levels)
+{
+    const unsigned long long full = ((lod_bytes_equal(w, LOD_NO_LEVEL) & lod_flags_of_bits(cand)) >> 7) * 0xFFull;
+    return (w & ~full) | (full & (LOD_BYTE_ONES * levels));
+}
+// The flags of the final bytes a call writes: every level below `classes` (levels + 1, or levels where the rest is dropped)
+constexpr unsigned long long lod_bytes_written(unsigned long long w, uint32_t levels, uint32_t classes)
+{
+    return ~lod_bytes_equal(w, LOD_NO_LEVEL) & (classes > levels ? LOD_BYTE_FLAGS : ~lod_bytes_equal(w, levels)) & LOD_BYTE_FLAGS;
 }
 
 // The mean of n >= 1 non-negative integers with sum s, rounded half up: (2 s + n) / (2 n) in unsigned 64-bit integers. Exact for

@@ -360,6 +360,25 @@ struct HuffmanLasData : Resource {
         return st;
     }
 
+    // The points inside `clip` (NULL: everywhere) in level-of-detail order: by the least level of `lod`'s nested lattices at which a
+    // point is the first of its voxel in the stream's order (0 = coarsest), inside a level in the stream's order, last the points
+    // that are first at no level (left out with PCR_LOD_DROP_REST; PCR_LOD_ROW_ORDER: the stream's order throughout), on the GPU
+    // straight from the compressed stream (pcr_read_lod_order: a counting call, then the read). `levels` (may be NULL) gets the level
+    // of every point; the returned level_count tells where every level ends. Not in the reference.
+    pcr_lod_stats lodOrdered(const pcr_lod &lod, const pcr_box *clip, uint32_t flags, std::vector<pcr_point> &out, std::vector<uint8_t> *levels = nullptr)
+    {
+        if (!loadedOn) throw std::runtime_error("lodOrdered: the resource is not loaded");
+        const int64_t nB = pcr_batches_resident(loadedOn->ctx);
+        int64_t n = 0;
+        pcr_lod_stats st{};
+        loadedOn->check(pcr_read_lod_order(loadedOn->ctx, 0, nB, &lod, clip, flags, nullptr, nullptr, nullptr, 0, &n, &st), "pcr_read_lod_order");
+        out.resize((size_t)n);
+        if (levels) levels->resize((size_t)n);
+        if (n) loadedOn->check(pcr_read_lod_order(loadedOn->ctx, 0, nB, &lod, clip, flags, out.data(), nullptr, levels ? levels->data() : nullptr, out.size(), &n, &st),
+                               "pcr_read_lod_order");
+        return st;
+    }
+
     // One computed point per non-empty voxel of `vox` among the points inside `clip` (NULL: everywhere): the mean position, rounded
     // half up inside the voxel, and the mean of each colour byte, in thin()'s PCR_THIN_FIRST order, with the points per voxel in
     // `counts`, on the GPU straight from the compressed stream (pcr_read_voxel_mean: a counting call, then the read). Not in the
@@ -828,6 +847,17 @@ inline pcr_voxels voxelsFromWorld(const pcr_las_info &las, double cell_size, con
     const pcr_box b = boxFromWorld(las, origin, h3);
     for (int k = 0; k < 3; ++k) if (b.min[k] > b.max[k]) throw std::runtime_error("voxelsFromWorld: the origin lies beyond every int32 coordinate");
     return pcr_voxels{{b.min[0], b.min[1], b.min[2]}, (int32_t)cells[0]};
+}
+
+// The nested lattices pcr_lod_order takes for a finest cell of `cell_size` world units and `levels` levels, each coarser level with
+// cells twice as large: voxelsFromWorld's lattice as the finest. levels in 1 .. PCR_LOD_MAX_LEVELS, the coarsest cell at most
+// PCR_THIN_MAX_CELL lattice steps. The Python twin is host.lod_from_world.
+inline pcr_lod lodFromWorld(const pcr_las_info &las, double cell_size, int levels, const double origin[3])
+{
+    if (levels < 1 || levels > PCR_LOD_MAX_LEVELS) throw std::runtime_error("lodFromWorld: the number of levels is 1 .. 16");
+    const pcr_voxels vox = voxelsFromWorld(las, cell_size, origin);
+    if (((int64_t)vox.cell << (levels - 1)) > PCR_THIN_MAX_CELL) throw std::runtime_error("lodFromWorld: the coarsest cell is more than 2^30 lattice steps");
+    return pcr_lod{{vox.origin[0], vox.origin[1], vox.origin[2]}, vox.cell, levels, 0};
 }
 
 // The largest whole number r of lattice steps with r * scale <= radius (as doubles): the radius pcr_neighbors takes for `radius`

@@ -28,7 +28,7 @@ from typing import Iterator, Optional
 import numpy as np
 
 from . import _native as N
-from ._native import Box, DisplayOpts, EncodeStats, Grid, GridStats, QuantileStats, GroundStats, HeightStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, ComponentsStats, DenoiseStats, NeighborsStats, ThinStats, Voxels, XyzBatch, c_i64, fb_elems
+from ._native import Box, DisplayOpts, EncodeStats, Grid, GridStats, QuantileStats, GroundStats, HeightStats, FileHeader, LasInfo, RenderParams, RenderStats, SelectStats, ComponentsStats, DenoiseStats, NeighborsStats, ThinStats, Lod, LodStats, Voxels, XyzBatch, c_i64, fb_elems
 
 POINTS_PER_BATCH = 65536
 ENCODED_PAD_WORDS = 1024
@@ -438,6 +438,22 @@ def as_voxels(vox) -> Voxels:
     return out
 
 
+def as_lod(lod) -> Lod:
+    """A pcr_lod from a Lod or five numbers origin x, y, z, the finest cell, levels (the stream's int32 coordinates)."""
+    if isinstance(lod, Lod):
+        return lod
+    v = [int(a) for a in np.asarray(lod, dtype=np.int64).reshape(5)]
+    if any(a < INT32_MIN or a > INT32_MAX for a in v):
+        raise ValueError("level-of-detail fields are int32")
+    out = Lod()
+    out.origin[:], out.cell, out.levels, out.reserved = v[:3], v[3], v[4], 0
+    return out
+
+
+def lod_flags(drop_rest: bool, row_order: bool) -> int:
+    return (N.LOD_DROP_REST if drop_rest else 0) | (N.LOD_ROW_ORDER if row_order else 0)
+
+
 def thin_mode(mode) -> int:
     """PCR_THIN_FIRST / PCR_THIN_CENTER from "first" / "center" (an integer passes through: the library checks it)."""
     if isinstance(mode, str):
@@ -583,6 +599,19 @@ def voxels_from_world(las: LasInfo, cell_size: float, origin=None) -> Voxels:
     if any(box.min[k] > box.max[k] for k in range(3)):
         raise ValueError("the origin lies beyond every int32 coordinate")
     return as_voxels((box.min[0], box.min[1], box.min[2], cells[0]))
+
+
+def lod_from_world(las: LasInfo, cell_size: float, levels: int, origin=None) -> Lod:
+    """The nested lattices of Context.lod_order whose finest level is voxels_from_world(las, cell_size, origin) and whose level l
+    (0 = coarsest) has cells of cell_size * 2 ** (levels - 1 - l). ValueError for what voxels_from_world refuses, for levels
+    outside 1 .. LOD_MAX_LEVELS and for a coarsest cell of more than THIN_MAX_CELL lattice steps."""
+    levels = int(levels)
+    if levels < 1 or levels > N.LOD_MAX_LEVELS:
+        raise ValueError(f"levels is 1 .. {N.LOD_MAX_LEVELS}, not {levels}")
+    vox = voxels_from_world(las, cell_size, origin)
+    if vox.cell << (levels - 1) > N.THIN_MAX_CELL:
+        raise ValueError(f"a finest cell of {vox.cell} lattice steps with {levels} levels: the coarsest cell is more than {N.THIN_MAX_CELL} steps")
+    return as_lod((vox.origin[0], vox.origin[1], vox.origin[2], vox.cell, levels))
 
 
 def write_las(path, x=None, y=None, z=None, color=None, las: Optional[LasInfo] = None, points=None) -> None:
@@ -1241,6 +1270,29 @@ class Context:
         vox, clip, mode = as_voxels(vox), None if clip is None else as_box(clip), thin_mode(mode)
         args = (first, -1 if count is None else count, C.byref(vox), None if clip is None else C.byref(clip), mode)
         return self._kept_host(self.lib.pcr_read_thin, args, ThinStats, "thin_stats", [(rows, ROW_DTYPE, ())])
+
+    # -- levels of detail (pcr_lod_order / pcr_read_lod_order) ---------------------------------------------
+    def lod_order(self, lod, clip=None, first: int = 0, count: Optional[int] = None, drop_rest: bool = False, row_order: bool = False, out=None,
+                  rows: bool = False, levels: bool = False):
+        """The rows of batches [first, first + count) inside `clip` (as_box; None: everywhere) ordered by the nested lattices of `lod`
+        (as_lod: a Lod or origin x, y, z, finest cell, levels), straight from the compressed stream: a row's level is the least l
+        (0 = coarsest) at which it is the lowest row of its voxel, `levels` ("the rest") if at none, so the rows of level <= l
+        are thin() "first" with the cell of level l. A torch.int32 tensor [n, 4] on the context's device, rows of decode_points of
+        the range in increasing (level, row): the first lod_stats["level_count"][0] records are level 0, and so on. drop_rest=True
+        leaves the rest out; row_order=True gives increasing row order instead. rows=True appends a torch.int64 tensor [n] of
+        the row numbers, levels=True a torch.uint8 tensor [n] of the levels: points, then rows, then levels. `out` and the
+        allocation behave as in thin. Stream ordering as decode_points. What the last call did is in self.lod_stats."""
+        lod, clip = as_lod(lod), None if clip is None else as_box(clip)
+        args = (first, -1 if count is None else count, C.byref(lod), None if clip is None else C.byref(clip), lod_flags(drop_rest, row_order))
+        return self._kept_device(self.lib.pcr_lod_order, args, LodStats, "lod_stats", "points_written", out, [(rows, "int64", ()), (levels, "uint8", ())])
+
+    def read_lod_order(self, lod, clip=None, first: int = 0, count: Optional[int] = None, drop_rest: bool = False, row_order: bool = False,
+                       rows: bool = False, levels: bool = False):
+        """The same on the host, without torch: a numpy structured array of POINT_DTYPE, then with rows=True an int64 array of the
+        rows and with levels=True a uint8 array of the levels (pcr_read_lod_order: a counting call, then the read; synchronises)."""
+        lod, clip = as_lod(lod), None if clip is None else as_box(clip)
+        args = (first, -1 if count is None else count, C.byref(lod), None if clip is None else C.byref(clip), lod_flags(drop_rest, row_order))
+        return self._kept_host(self.lib.pcr_read_lod_order, args, LodStats, "lod_stats", [(rows, ROW_DTYPE, ()), (levels, np.dtype("u1"), ())])
 
     # -- voxel means (pcr_voxel_mean / pcr_read_voxel_mean) --------------------------------------------------
     def voxel_mean(self, vox, clip=None, first: int = 0, count: Optional[int] = None, out=None, rows: bool = False, counts: bool = False):
@@ -1992,6 +2044,28 @@ class HuffmanLasData(Resource):
             return pts
         so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
         return pts[:, :3].to(torch.float64) * so[0] + so[1], pts
+
+    def lod_ordered(self, renderer: Renderer, cell_size: float, levels: int, lo=None, hi=None, drop_rest: bool = False, world: bool = True):
+        """The loaded resource in level-of-detail order, on the GPU and straight from the compressed stream (Context.lod_order):
+        `levels` nested voxel lattices, the finest with cells of `cell_size`, every coarser one with cells twice as large; the
+        points that are first in a voxel of the coarsest lattice come first, then those of the next level, and so on, last the rest
+        (left out with drop_rest=True). Every prefix that ends at a level boundary is thinned() "first" with that level's cell.
+        cell_size, lo, hi and world are as for thinned(). world=True: (xyz, pts, level_counts) -- level_counts a list of levels + 1
+        numbers, the last one the rest (counted also when it is dropped); world=False: (pts, level_counts)."""
+        import torch
+        info = self.las_info()
+        if world:
+            lod = lod_from_world(info, cell_size, levels)
+            clip = box_from_world(info, tuple(info.min) if lo is None else lo, tuple(info.max) if hi is None else hi)
+        else:
+            lod = as_lod((0, 0, 0, cell_size, levels))
+            clip = None if lo is None and hi is None else as_box(((INT32_MIN,) * 3 if lo is None else lo, (INT32_MAX,) * 3 if hi is None else hi))
+        pts = renderer.ctx.lod_order(lod, clip, drop_rest=drop_rest)
+        counts = renderer.ctx.lod_stats["level_count"][:int(levels) + 1]
+        if not world:
+            return pts, counts
+        so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
+        return pts[:, :3].to(torch.float64) * so[0] + so[1], pts, counts
 
     def voxel_centroids(self, renderer: Renderer, cell_size: float, lo=None, hi=None, world: bool = True):
         """The loaded resource down-sampled to the centroid of every non-empty cubic voxel of `cell_size`, on the GPU and straight
