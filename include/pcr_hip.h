@@ -252,6 +252,41 @@ int pcr_select_polygon(pcr_ctx *ctx, int64_t first_batch, int64_t count, const p
 int pcr_read_polygon(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_polygon *poly, pcr_point *host, size_t capacity_points,
                      int64_t *out_count, pcr_polygon_stats *stats);
 
+/* ---- slabs: plane hypotheses and oriented selections (no reference counterpart) ------------------------------------------------
+ * A pcr_slab (pcr_types.h) is one linear form with two bounds, lo <= n.p <= hi, taken in exact 64-bit integers: a plane with a
+ * tolerance, with one bound at the limit a half-space, several together an oriented box, a frustum, a tilted cross-section.
+ *
+ * CONTRACT of pcr_plane_support: the candidates are the records pcr_decode_points writes for the range (padding duplicates and
+ * the tail artefact included) that lie inside clip (NULL: all) and are in NO slab of exclude; host_counts[j] = the number of
+ * candidates in hyp[j]. 1 <= num_hyp <= PCR_PLANE_MAX_HYPOTHESES, 0 <= num_exclude <= PCR_SLAB_MAX_EXCLUDE. Sums commute: the
+ * result is exact, the same from run to run, for both layouts, for BC1 and BC7 (no colour is decoded), before and after the
+ * first frame. Synchronises. Touches no framebuffer, no prepass state, no render statistics. stats may be NULL. An empty clip
+ * or an empty range gives all zeros.
+ * The host plan, per batch from its exact box (pcr_batch_point_bounds): a box disjoint from the clip, or an exclusion of class
+ * ALL: skipped. The exclusions of class CUT form the batch's exclusion slice. The batch is open iff its box lies within the clip
+ * and that slice is empty: every record of an open batch is a candidate. A hypothesis of class MISS adds nothing; one of class
+ * ALL adds the batch's candidate count (65 536 for an open batch, else what the kernel reports for the batch); those of class
+ * CUT form the batch's hypothesis slice. A batch is decoded (one workgroup of k_plane_support, its slices in LDS) iff that slice
+ * is not empty, or it is not open and has an ALL hypothesis; a batch neither skipped nor decoded is whole.
+ * PCR_E_ARG with a message: NULL hyp or host_counts; counts out of range; exclude == NULL with num_exclude > 0; reserved != 0;
+ * a normal component or a bound beyond its limit; whatever pcr_select_box refuses about the range. */
+int pcr_plane_support(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_slab *hyp, int num_hyp, const pcr_box *clip,
+                      const pcr_slab *exclude, int num_exclude, int64_t *host_counts, pcr_plane_stats *stats);
+
+/* CONTRACT: pcr_select_slabs / pcr_read_slabs are pcr_select_polygon / pcr_read_polygon with another predicate: a record is
+ * selected iff it lies inside clip (NULL: all) and (it is in ALL of slabs[0 .. num_slabs)) != (flags & PCR_SLAB_INVERT), with
+ * 1 <= num_slabs <= PCR_SLAB_MAX_SELECT. Output, order, counting call, capacity rule, layouts, colour formats and what is left
+ * alone are pcr_select_box's. A batch is outside (not decoded) if the clip or any slab misses its box, inside (decoded whole) if
+ * its box lies within the clip and every slab is ALL, else straddling (k_slab_count, then k_slab_write, against the batch's CUT
+ * slabs in LDS). With PCR_SLAB_INVERT the slab classes swap: a slab that misses the box selects all of it, slabs that are all
+ * ALL none of it.
+ * PCR_E_ARG with a message, nothing written: what pcr_plane_support refuses about a slab list; unknown flag bits; a NULL
+ * out_count; a misaligned destination; whatever pcr_select_box refuses about the range. */
+int pcr_select_slabs(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_slab *slabs, int num_slabs, const pcr_box *clip,
+                     uint32_t flags, void *dev_points, size_t capacity_points, int64_t *out_count, pcr_slab_stats *stats);
+int pcr_read_slabs(pcr_ctx *ctx, int64_t first_batch, int64_t count, const pcr_slab *slabs, int num_slabs, const pcr_box *clip,
+                   uint32_t flags, pcr_point *host, size_t capacity_points, int64_t *out_count, pcr_slab_stats *stats);
+
 /* ---- screen selection and picking: which points does a frame show, and where (no reference counterpart) -----------------------
  * CONTRACT of pcr_select_screen: the selected points are exactly those pcr_render_basic(params) scatters -- the batches its
  * cull/LOD prepass keeps, of each chain the first points by the prepass's level of detail, each batch dequantised in the

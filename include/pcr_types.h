@@ -166,6 +166,50 @@ typedef struct pcr_polygon_stats {
     int64_t edges_max;
 } pcr_polygon_stats;
 
+/* A slab in the stream's int32 coordinates (pcr_plane_support, pcr_select_slabs), 32 bytes: one linear form with two bounds.
+ * s(S, p) = n[0]*x + n[1]*y + n[2]*z in exact 64-bit integers: with |n[a]| <= PCR_SLAB_MAX_NORMAL every product is below 2^51
+ * and the sum below 2^53 for any int32 point. p is in S iff lo <= s(S, p) <= hi. lo > hi: legal and empty. A bound at
+ * -/+PCR_SLAB_MAX_BOUND: a half-space. n = (0, 0, 0): legal, in iff lo <= 0 <= hi.
+ * The class of a slab against an exact batch box bb: smin = sum over a of min(n[a]*bb.min[a], n[a]*bb.max[a]), smax likewise
+ * with max (a linear form takes its extremes at the corners, so both are attained); MISS iff lo > hi || smax < lo || smin > hi;
+ * ALL iff not MISS and lo <= smin && smax <= hi; CUT otherwise. */
+#define PCR_SLAB_MAX_NORMAL (1 << 20)            /* |n[a]| <= this */
+#define PCR_SLAB_MAX_BOUND ((int64_t)1 << 61)    /* |lo|, |hi| <= this */
+#define PCR_PLANE_MAX_HYPOTHESES 1024
+#define PCR_SLAB_MAX_EXCLUDE 16
+#define PCR_SLAB_MAX_SELECT 16
+#define PCR_SLAB_INVERT 1u                       /* pcr_select_slabs flags: keep the points NOT in all of the slabs (the clip still applies) */
+typedef struct pcr_slab {
+    int32_t n[3];
+    int32_t reserved;            /* 0 */
+    int64_t lo, hi;              /* inclusive */
+} pcr_slab;
+
+/* What pcr_plane_support did: the batches of the range by the host plan (pcr_hip.h has the rule) -- skipped (no candidate),
+ * whole (neither skipped nor decoded: every contribution known from the box), decoded (one workgroup of k_plane_support) --
+ * the sum and the largest of the decoded batches' hypothesis slices, the sum of their exclusion slices, and the sum of the
+ * kernel's per-batch candidate counts. */
+typedef struct pcr_plane_stats {
+    int64_t batches_skipped;
+    int64_t batches_whole;
+    int64_t batches_decoded;
+    int64_t hypotheses_listed;
+    int64_t hypotheses_max;
+    int64_t exclusions_listed;
+    int64_t candidates_decoded;
+    int64_t reserved;
+} pcr_plane_stats;
+
+/* What pcr_select_slabs / pcr_read_slabs did: pcr_polygon_stats with the slab lists in place of the edge lists. */
+typedef struct pcr_slab_stats {
+    int64_t batches_outside;
+    int64_t batches_inside;
+    int64_t batches_straddling;
+    int64_t points_selected;
+    int64_t slabs_listed;
+    int64_t slabs_max;
+} pcr_slab_stats;
+
 /* A top-down grid over the stream's int32 x and y (pcr_grid_accumulate), 24 bytes. A point (x, y, z, colour) belongs to cell
  * (cx, cy) iff x >= origin_x, y >= origin_y, cx = (uint32)(x - origin_x) / cell < width and cy = (uint32)(y - origin_y) / cell
  * < height (the differences fit 32 unsigned bits for every int32 input); the cell's index in a plane is cx + cy * width.

@@ -83,6 +83,28 @@ class PolygonStats(C.Structure):                  # pcr_polygon_stats
 POLY_MAX_VERTICES, POLY_INVERT = 4096, 1                                                                # pcr_types.h
 
 
+class Slab(C.Structure):                          # pcr_slab: lo <= n.p <= hi in exact integers, 32 bytes (host.Slab fills one)
+    _fields_ = [("n", c_i32 * 3), ("reserved", c_i32), ("lo", c_i64), ("hi", c_i64)]
+
+
+class PlaneStats(C.Structure):                    # pcr_plane_stats
+    _fields_ = [(n, c_i64) for n in ("batches_skipped", "batches_whole", "batches_decoded", "hypotheses_listed", "hypotheses_max", "exclusions_listed",
+                                     "candidates_decoded", "reserved")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_[:-1]}
+
+
+class SlabStats(C.Structure):                     # pcr_slab_stats
+    _fields_ = [(n, c_i64) for n in ("batches_outside", "batches_inside", "batches_straddling", "points_selected", "slabs_listed", "slabs_max")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+SLAB_MAX_NORMAL, SLAB_MAX_BOUND, PLANE_MAX_HYPOTHESES, SLAB_MAX_EXCLUDE, SLAB_MAX_SELECT, SLAB_INVERT = 1 << 20, 1 << 61, 1024, 16, 16, 1    # pcr_types.h
+
+
 class Grid(C.Structure):                          # pcr_grid: a top-down grid over the stream's int32 x and y, 24 bytes
     _fields_ = [(n, c_i32) for n in ("origin_x", "origin_y", "cell", "width", "height", "reserved")]
 
@@ -243,6 +265,7 @@ class EncodeStats(C.Structure):                   # pcr_encode_stats
 
 assert C.sizeof(Point) == 16 and C.sizeof(Box) == 24 and C.sizeof(SelectStats) == 32
 assert C.sizeof(Polygon) == 40 and C.sizeof(PolygonStats) == 48
+assert C.sizeof(Slab) == 32 and C.sizeof(PlaneStats) == 64 and C.sizeof(SlabStats) == 48
 assert C.sizeof(Rect) == 16 and C.sizeof(ScreenHit) == 16 and C.sizeof(ScreenStats) == 32 and C.sizeof(VisibleStats) == 48
 assert C.sizeof(DisplayOpts) == 16
 assert C.sizeof(Grid) == 24 and C.sizeof(GridStats) == 24 and C.sizeof(QuantileStats) == 48
@@ -272,6 +295,7 @@ HIP_SYMBOLS = [
     "pcr_decode_points", "pcr_read_points",
     "pcr_batch_point_bounds", "pcr_select_box", "pcr_read_box",
     "pcr_select_polygon", "pcr_read_polygon",
+    "pcr_plane_support", "pcr_select_slabs", "pcr_read_slabs",
     "pcr_select_screen", "pcr_read_screen", "pcr_pick",
     "pcr_select_visible", "pcr_read_visible",
     "pcr_resolve_basic_display", "pcr_resolve_hqs_display", "pcr_resolve_las_display",
@@ -399,6 +423,11 @@ def hip_lib() -> C.CDLL:
             getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Box), C.c_void_p, C.c_size_t, C.POINTER(c_i64), C.POINTER(SelectStats)]
         for n in ("pcr_select_polygon", "pcr_read_polygon"):
             getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Polygon), C.c_void_p, C.c_size_t, C.POINTER(c_i64), C.POINTER(PolygonStats)]
+        lib.pcr_plane_support.argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Slab), C.c_int, C.POINTER(Box), C.POINTER(Slab), C.c_int, C.POINTER(c_i64),
+                                          C.POINTER(PlaneStats)]
+        for n in ("pcr_select_slabs", "pcr_read_slabs"):
+            getattr(lib, n).argtypes = [C.c_void_p, c_i64, c_i64, C.POINTER(Slab), C.c_int, C.POINTER(Box), c_u32, C.c_void_p, C.c_size_t, C.POINTER(c_i64),
+                                        C.POINTER(SlabStats)]
         for n in ("pcr_select_screen", "pcr_read_screen"):
             getattr(lib, n).argtypes = [C.c_void_p, C.POINTER(RenderParams), C.POINTER(Rect), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(c_i64),
                                         C.POINTER(ScreenStats)]

@@ -1,7 +1,7 @@
 """In-tree builds of the native libraries (no JIT cache, no pip): the .so files land next to this
 file so they travel to the GPU box with the repository snapshot.
 
-    libpcr_hip.so   hipcc --offload-arch=gfx950   csrc/pcr_api.hip (+ pcr_kernels.hip.h, pcr_gpu_encoder.hip.h, pcr_lattice.h, pcr_polygon.h)   hot path + GPU encoder
+    libpcr_hip.so   hipcc --offload-arch=gfx950   csrc/pcr_api.hip (+ pcr_kernels.hip.h, pcr_gpu_encoder.hip.h, pcr_lattice.h, pcr_polygon.h, pcr_plane.h)   hot path + GPU encoder
     libpcr_host.so  g++                           csrc/pcr_encoder.cpp                     CPU encoder / generator / camera
 """
 from __future__ import annotations
@@ -49,7 +49,7 @@ def _hipcc() -> str:
 
 def build_hip(force: bool = False) -> str:
     srcs = [os.path.join(CSRC, "pcr_api.hip"), os.path.join(CSRC, "pcr_kernels.hip.h"), os.path.join(CSRC, "pcr_gpu_encoder.hip.h"),
-            os.path.join(CSRC, "pcr_codec_common.h"), os.path.join(CSRC, "pcr_lattice.h"), os.path.join(CSRC, "pcr_polygon.h"),
+            os.path.join(CSRC, "pcr_codec_common.h"), os.path.join(CSRC, "pcr_lattice.h"), os.path.join(CSRC, "pcr_polygon.h"), os.path.join(CSRC, "pcr_plane.h"),
             os.path.join(INCLUDE, "pcr_hip.h"),
             os.path.join(INCLUDE, "pcr_types.h"), os.path.join(INCLUDE, "pcr_encode.h"), os.path.join(INCLUDE, "pcr_gpu_encode.h")]
     if force or _stale(HIP_LIB, srcs):

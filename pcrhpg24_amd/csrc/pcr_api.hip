@@ -143,6 +143,20 @@ struct pcr_ctx {
     int64_t poly_edge_capacity = 0;             // edges d_poly_edges holds
     PolyEdge *d_poly_edges = nullptr;           // [poly_edge_capacity] the batches' edge lists, back to back
     bool poly_lds_ready = false;                // hipFuncSetAttribute done for the k_polygon_* launches
+    // slabs (pcr_select_slabs, pcr_plane_support): the listed batches of a call with their slices of the slab arrays, the arrays,
+    // and pcr_plane_support's counters (pcr_select_slabs' per-chain counts, totals and offsets are the box selection's)
+    int64_t slab_capacity = 0;                  // entries d_slab_batches holds
+    SlabBatch *d_slab_batches = nullptr;        // [slab_capacity]
+    int64_t slab_entry_capacity = 0;            // slabs d_slab_entries holds
+    pcr_slab *d_slab_entries = nullptr;         // [slab_entry_capacity] the batches' slab lists, back to back
+    int64_t plane_capacity = 0;                 // entries d_plane_batches holds
+    PlaneBatch *d_plane_batches = nullptr;      // [plane_capacity]
+    int64_t plane_cand_capacity = 0;            // entries d_plane_candidates holds
+    uint32_t *d_plane_candidates = nullptr;     // [plane_cand_capacity] candidates per decoded batch
+    int64_t plane_entry_capacity = 0;           // slabs d_plane_entries holds: the exclusion slices, then the hypothesis slices
+    pcr_slab *d_plane_entries = nullptr;        // [plane_entry_capacity]
+    unsigned long long *d_plane_counts = nullptr;   // [PCR_PLANE_MAX_HYPOTHESES]
+    bool slab_lds_ready = false;                // hipFuncSetAttribute done for the k_slab_* and k_plane_support launches
     // screen selection and picking (pcr_select_screen / pcr_pick): the cull/LOD words of the call's camera in an array of their own
     // (k_screen_lod; the frame's d_lod, lists and plans are not touched), and the scratch of the kept batches
     uint32_t *d_screen_lod = nullptr;           // [hdr.num_batches]
@@ -330,6 +344,9 @@ void free_stream_buffers(pcr_ctx *c)
     dfree(c->d_point_bounds); c->h_point_bounds.clear(); c->h_point_bounds_ok.clear();
     dfree(c->d_sel_list); dfree(c->d_sel_counts); dfree(c->d_sel_totals); dfree(c->d_sel_offsets); c->sel_capacity = 0;
     dfree(c->d_poly_batches); c->poly_capacity = 0; dfree(c->d_poly_edges); c->poly_edge_capacity = 0;
+    dfree(c->d_slab_batches); c->slab_capacity = 0; dfree(c->d_slab_entries); c->slab_entry_capacity = 0;
+    dfree(c->d_plane_batches); c->plane_capacity = 0; dfree(c->d_plane_candidates); c->plane_cand_capacity = 0; dfree(c->d_plane_entries); c->plane_entry_capacity = 0;
+    dfree(c->d_plane_counts);
     dfree(c->d_screen_lod); dfree(c->d_scr_list); dfree(c->d_scr_counts); dfree(c->d_scr_totals); dfree(c->d_scr_offsets); c->scr_capacity = 0;
     dfree(c->d_pick);
     dfree(c->d_vis_key); dfree(c->d_vis_index); dfree(c->d_vis_row); dfree(c->d_vis_depth); dfree(c->d_vis_totals); c->vis_pixels = 0; c->vis_capacity = 0;
@@ -2045,6 +2062,255 @@ int pcr_read_polygon(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_p
     int rc = polygon_prepare(c, first_batch, count, poly, host, alignof(pcr_point), capacity_points, out_count, stats, &n, p, &done);
     if (rc || done) return rc;
     return select_read(c, first_batch, n, p.sel, host, [&](size_t s0, size_t nS, uint4 *out) { polygon_write(c, p, s0, nS, out); });
+}
+
+// ---- slabs: pcr_select_slabs / pcr_read_slabs / pcr_plane_support ------------------------------------
+namespace {
+constexpr size_t SLAB_MAX_LDS_BYTES = SLAB_TABLE_BYTES + (size_t)PCR_SLAB_MAX_SELECT * sizeof(pcr_slab);
+constexpr size_t PLANE_MAX_LDS_BYTES = SLAB_TABLE_BYTES + (size_t)PCR_SLAB_MAX_EXCLUDE * sizeof(pcr_slab) +
+                                       (size_t)PCR_PLANE_MAX_HYPOTHESES * (sizeof(pcr_slab) + LWC_WAVES * sizeof(uint32_t));
+static_assert(sizeof(pcr_slab) == 32 && sizeof(pcr_plane_stats) == 64 && sizeof(pcr_slab_stats) == 48, "the slab structs of pcr_types.h");
+
+// *p holds at least `need` elements on return (scratch of the context: grown on demand, contents not kept)
+extern "C++" template <class T>
+int slab_reserve(pcr_ctx *c, T *&p, int64_t &capacity, int64_t need, const char *what)
+{
+    if (capacity >= need) return PCR_OK;
+    dfree(p); capacity = 0;
+    if (hipMalloc((void **)&p, (size_t)need * sizeof(T)) != hipSuccess) return set_err(c, PCR_E_NOMEM, "out of device memory for %lld %s", (long long)need, what);
+    capacity = need;
+    return PCR_OK;
+}
+
+int slab_lds_allow(pcr_ctx *c)
+{
+    if (c->slab_lds_ready) return PCR_OK;
+    hipError_t e = hipSuccess;
+#define PCR_ALLOW(K, BYTES) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES))
+    PCR_ALLOW(k_slab_count<LAYOUT_WORDS>, SLAB_MAX_LDS_BYTES); PCR_ALLOW(k_slab_count<LAYOUT_POINT_WINDOWS>, SLAB_MAX_LDS_BYTES);
+    PCR_ALLOW((k_slab_write<LAYOUT_WORDS, false>), SLAB_MAX_LDS_BYTES); PCR_ALLOW((k_slab_write<LAYOUT_WORDS, true>), SLAB_MAX_LDS_BYTES);
+    PCR_ALLOW((k_slab_write<LAYOUT_POINT_WINDOWS, false>), SLAB_MAX_LDS_BYTES); PCR_ALLOW((k_slab_write<LAYOUT_POINT_WINDOWS, true>), SLAB_MAX_LDS_BYTES);
+    PCR_ALLOW(k_plane_support<LAYOUT_WORDS>, PLANE_MAX_LDS_BYTES); PCR_ALLOW(k_plane_support<LAYOUT_POINT_WINDOWS>, PLANE_MAX_LDS_BYTES);
+#undef PCR_ALLOW
+    if (e != hipSuccess) return set_err(c, PCR_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
+    c->slab_lds_ready = true;
+    return PCR_OK;
+}
+
+// The checks on a list of slabs shared by the three entry points.
+int slab_list_check(pcr_ctx *c, const pcr_slab *slabs, int n, int n_min, int n_max, const char *what)
+{
+    if (n < n_min || n > n_max) return set_err(c, PCR_E_ARG, "%d %s: %d to %d are taken", n, what, n_min, n_max);
+    if (n > 0 && !slabs) return set_err(c, PCR_E_ARG, "the list of %s is NULL", what);
+    for (int k = 0; k < n; ++k)
+        if (const char *why = slab_check(slabs[k])) return set_err(c, PCR_E_ARG, "%s (entry %d of the %s)", why, k, what);
+    return PCR_OK;
+}
+
+const pcr_box FULL_BOX = {{INT32_MIN, INT32_MIN, INT32_MIN}, {INT32_MAX, INT32_MAX, INT32_MAX}};
+
+// What a slab selection adds to a SelectPlan: the straddling batches with their slices, the slab array.
+struct SlabsPlan {
+    SelectPlan sel;
+    std::vector<SlabBatch> batches;     // the straddling batches, ascending (alive until the stream has been synchronised)
+    std::vector<pcr_slab> slabs;
+    SlabArgs args{};
+    size_t lds = 0;                     // dynamic LDS of the k_slab_* launches
+    pcr_slab_stats st{};
+};
+
+// Classify (host, pcr_plane.h), upload the straddling batches' slab lists and count them (k_slab_count). Synchronises.
+int slabs_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_slab *slabs, int num_slabs, const pcr_box *clip, uint32_t invert, SlabsPlan &p)
+{
+    p.sel.cls.assign((size_t)n, SEL_OUTSIDE); p.sel.cnt.assign((size_t)n, 0); p.sel.strad.clear();
+    p.batches.clear(); p.slabs.clear();
+    p.st = pcr_slab_stats{n, 0, 0, 0, 0, 0};
+    if (n == 0 || (clip && plane_box_empty(*clip))) return PCR_OK;
+    int rc;
+    if ((rc = ensure_point_bounds(c, first, n))) return rc;
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t e0 = p.slabs.size();
+        uint32_t inv = 0;
+        const int cls = slabs_plan_batch(slabs, num_slabs, clip, invert, c->h_point_bounds.data() + (first + i) * 6, p.slabs, &inv);
+        if (cls == SLABS_OUTSIDE) continue;
+        --p.st.batches_outside;
+        if (cls == SLABS_INSIDE) { p.sel.cls[(size_t)i] = SEL_INSIDE; p.sel.cnt[(size_t)i] = PCR_POINTS_PER_BATCH; ++p.st.batches_inside; continue; }
+        const size_t ne = p.slabs.size() - e0;
+        p.sel.cls[(size_t)i] = SEL_STRADDLING; p.sel.strad.push_back((uint32_t)(first + i)); ++p.st.batches_straddling;
+        p.batches.push_back(SlabBatch{(uint32_t)(first + i), (uint32_t)e0, (uint32_t)ne, inv});
+        p.st.slabs_listed += (int64_t)ne;
+        p.st.slabs_max = std::max(p.st.slabs_max, (int64_t)ne);
+    }
+    const int64_t nS = (int64_t)p.batches.size(), nE = (int64_t)p.slabs.size();
+    if (nS) {
+        if ((rc = select_reserve(c, nS))) return rc;
+        if ((rc = slab_reserve(c, c->d_slab_batches, c->slab_capacity, nS, "straddling batches"))) return rc;
+        if ((rc = slab_reserve(c, c->d_slab_entries, c->slab_entry_capacity, std::max<int64_t>(nE, 1), "slabs"))) return rc;
+        if ((rc = slab_lds_allow(c))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->d_slab_batches, p.batches.data(), (size_t)nS * sizeof(SlabBatch), hipMemcpyHostToDevice, c->stream));
+        if (nE) HIP_TRY(c, hipMemcpyAsync(c->d_slab_entries, p.slabs.data(), (size_t)nE * sizeof(pcr_slab), hipMemcpyHostToDevice, c->stream));
+        p.args = SlabArgs{clip ? *clip : FULL_BOX, (uint32_t)p.st.slabs_max, c->d_slab_batches, c->d_slab_entries};
+        p.lds = SLAB_TABLE_BYTES + (size_t)p.st.slabs_max * sizeof(pcr_slab);
+        const StreamView s = make_stream_view(c);
+        const dim3 grid((unsigned)nS), block(PCR_WORKGROUP_SIZE);
+        if (select_reads_windows(c)) hipLaunchKernelGGL((k_slab_count<LAYOUT_POINT_WINDOWS>), grid, block, p.lds, c->stream, s, p.args, c->d_sel_counts, c->d_sel_totals);
+        else                         hipLaunchKernelGGL((k_slab_count<LAYOUT_WORDS>), grid, block, p.lds, c->stream, s, p.args, c->d_sel_counts, c->d_sel_totals);
+        HIP_TRY(c, hipGetLastError());
+        std::vector<uint32_t> totals((size_t)nS);
+        HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_sel_totals, (size_t)nS * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (int64_t k = 0; k < nS; ++k) p.sel.cnt[(size_t)(p.batches[(size_t)k].b - first)] = totals[(size_t)k];
+    }
+    for (int64_t i = 0; i < n; ++i) p.st.points_selected += p.sel.cnt[(size_t)i];
+    return PCR_OK;
+}
+
+// k_slab_write over the straddling batches [s0, s0 + nS) of the plan
+void slabs_write(pcr_ctx *c, const SlabsPlan &p, size_t s0, size_t nS, uint4 *out)
+{
+    const StreamView s = make_stream_view(c);
+    const dim3 grid((unsigned)nS), block(PCR_WORKGROUP_SIZE);
+    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
+    SlabArgs a = p.args;
+    a.batches += s0;
+#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_slab_write<L, B>), grid, block, p.lds, c->stream, s, a, c->d_sel_counts + s0 * PCR_WORKGROUP_SIZE, \
+                                            c->d_sel_offsets + s0, out)
+    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
+    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
+#undef PCR_LAUNCH
+}
+
+// The checks and the plan shared by pcr_select_slabs / pcr_read_slabs (select_prepare with the slabs' checks).
+int slabs_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_slab *slabs, int num_slabs, const pcr_box *clip, uint32_t flags, const void *dst,
+                  size_t dst_align, size_t capacity, int64_t *out_count, pcr_slab_stats *stats, int64_t *n, SlabsPlan &p, bool *done)
+{
+    *done = true;
+    if (out_count) *out_count = 0;
+    int rc = select_range(c, first, count, n);
+    if (rc) return rc;
+    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
+    if ((rc = slab_list_check(c, slabs, num_slabs, 1, PCR_SLAB_MAX_SELECT, "slabs"))) return rc;
+    if (flags & ~PCR_SLAB_INVERT) return set_err(c, PCR_E_ARG, "unknown flag bits 0x%x", flags);
+    if (dst && reinterpret_cast<uintptr_t>(dst) % dst_align != 0) return set_err(c, PCR_E_ARG, "the destination is misaligned (%zu bytes)", dst_align);
+    if ((rc = slabs_plan(c, first, *n, slabs, num_slabs, clip, flags & PCR_SLAB_INVERT, p))) return rc;
+    *out_count = p.st.points_selected;
+    if (stats) *stats = p.st;
+    if (!dst || p.st.points_selected == 0) return PCR_OK;
+    if (capacity < (size_t)p.st.points_selected)
+        return set_err(c, PCR_E_ARG, "capacity of %zu points is below the %lld selected", capacity, (long long)p.st.points_selected);
+    *done = false;
+    return PCR_OK;
+}
+} // namespace
+
+int pcr_select_slabs(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_slab *slabs, int num_slabs, const pcr_box *clip, uint32_t flags,
+                     void *dev_points, size_t capacity_points, int64_t *out_count, pcr_slab_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    SlabsPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = slabs_prepare(c, first_batch, count, slabs, num_slabs, clip, flags, dev_points, 16, capacity_points, out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    if ((rc = select_emit(c, first_batch, 0, n, p.sel, static_cast<uint4 *>(dev_points),
+                          [&](size_t s0, size_t nS, uint4 *out) { slabs_write(c, p, s0, nS, out); }))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+int pcr_read_slabs(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_slab *slabs, int num_slabs, const pcr_box *clip, uint32_t flags,
+                   pcr_point *host, size_t capacity_points, int64_t *out_count, pcr_slab_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    SlabsPlan p;
+    int64_t n = 0;
+    bool done = true;
+    int rc = slabs_prepare(c, first_batch, count, slabs, num_slabs, clip, flags, host, alignof(pcr_point), capacity_points, out_count, stats, &n, p, &done);
+    if (rc || done) return rc;
+    return select_read(c, first_batch, n, p.sel, host, [&](size_t s0, size_t nS, uint4 *out) { slabs_write(c, p, s0, nS, out); });
+}
+
+int pcr_plane_support(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_slab *hyp, int num_hyp, const pcr_box *clip, const pcr_slab *exclude,
+                      int num_exclude, int64_t *host_counts, pcr_plane_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int64_t n = 0;
+    int rc = select_range(c, first_batch, count, &n);
+    if (rc) return rc;
+    if (!host_counts) return set_err(c, PCR_E_ARG, "host_counts is NULL");
+    if ((rc = slab_list_check(c, hyp, num_hyp, 1, PCR_PLANE_MAX_HYPOTHESES, "hypotheses"))) return rc;
+    if (!hyp) return set_err(c, PCR_E_ARG, "the list of hypotheses is NULL");
+    if ((rc = slab_list_check(c, exclude, num_exclude, 0, PCR_SLAB_MAX_EXCLUDE, "exclusions"))) return rc;
+    std::fill(host_counts, host_counts + num_hyp, (int64_t)0);
+    pcr_plane_stats st{};
+    st.batches_skipped = n;
+    if (stats) *stats = st;
+    if (n == 0 || (clip && plane_box_empty(*clip))) return PCR_OK;
+    if ((rc = ensure_point_bounds(c, first_batch, n))) return rc;
+
+    // the plan: per decoded batch its slices and, for a batch that is not open, the hypotheses that take its candidate count
+    std::vector<PlaneBatch> batches;
+    std::vector<pcr_slab> excl, cut;
+    std::vector<int32_t> all, later;                        // `later`: per decoded batch that is not open: count, then the indices
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t e0 = excl.size(), c0 = cut.size();
+        bool open = false;
+        all.clear();
+        const int cls = plane_plan_batch(hyp, num_hyp, clip, exclude, num_exclude, c->h_point_bounds.data() + (first_batch + i) * 6, excl, cut, all, &open);
+        if (cls == PLANE_SKIPPED) continue;
+        --st.batches_skipped;
+        if (open) for (int32_t j : all) host_counts[j] += PCR_POINTS_PER_BATCH;
+        if (cls == PLANE_WHOLE) { ++st.batches_whole; continue; }
+        ++st.batches_decoded;
+        const size_t ne = excl.size() - e0, nc = cut.size() - c0;
+        batches.push_back(PlaneBatch{(uint32_t)(first_batch + i), (uint32_t)e0, (uint32_t)ne, (uint32_t)c0, (uint32_t)nc});
+        st.hypotheses_listed += (int64_t)nc;
+        st.hypotheses_max = std::max(st.hypotheses_max, (int64_t)nc);
+        st.exclusions_listed += (int64_t)ne;
+        later.push_back(open ? 0 : (int32_t)all.size());
+        if (!open) later.insert(later.end(), all.begin(), all.end());
+    }
+    const int64_t nD = (int64_t)batches.size();
+    if (nD) {
+        size_t excl_max = 0;
+        for (const PlaneBatch &b : batches) excl_max = std::max(excl_max, (size_t)b.excl_count);
+        const int64_t nX = (int64_t)excl.size(), nH = (int64_t)cut.size();
+        if ((rc = slab_reserve(c, c->d_plane_batches, c->plane_capacity, nD, "decoded batches"))) return rc;
+        if ((rc = slab_reserve(c, c->d_plane_candidates, c->plane_cand_capacity, nD, "candidate counts"))) return rc;
+        if ((rc = slab_reserve(c, c->d_plane_entries, c->plane_entry_capacity, std::max<int64_t>(nX + nH, 1), "slabs"))) return rc;
+        if (!c->d_plane_counts && hipMalloc((void **)&c->d_plane_counts, PCR_PLANE_MAX_HYPOTHESES * sizeof(unsigned long long)) != hipSuccess)
+            return set_err(c, PCR_E_NOMEM, "out of device memory for the hypothesis counters");
+        if ((rc = slab_lds_allow(c))) return rc;
+        HIP_TRY(c, hipMemsetAsync(c->d_plane_counts, 0, (size_t)num_hyp * sizeof(unsigned long long), c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_plane_batches, batches.data(), (size_t)nD * sizeof(PlaneBatch), hipMemcpyHostToDevice, c->stream));
+        if (nX) HIP_TRY(c, hipMemcpyAsync(c->d_plane_entries, excl.data(), (size_t)nX * sizeof(pcr_slab), hipMemcpyHostToDevice, c->stream));
+        if (nH) HIP_TRY(c, hipMemcpyAsync(c->d_plane_entries + nX, cut.data(), (size_t)nH * sizeof(pcr_slab), hipMemcpyHostToDevice, c->stream));
+        const PlaneArgs a{clip ? *clip : FULL_BOX, (uint32_t)excl_max, (uint32_t)st.hypotheses_max, c->d_plane_batches, c->d_plane_entries,
+                          c->d_plane_entries + nX, c->d_plane_counts, c->d_plane_candidates};
+        const size_t lds = SLAB_TABLE_BYTES + excl_max * sizeof(pcr_slab) + (size_t)st.hypotheses_max * (sizeof(pcr_slab) + LWC_WAVES * sizeof(uint32_t));
+        const StreamView s = make_stream_view(c);
+        const dim3 grid((unsigned)nD), block(PCR_WORKGROUP_SIZE);
+        if (select_reads_windows(c)) hipLaunchKernelGGL((k_plane_support<LAYOUT_POINT_WINDOWS>), grid, block, lds, c->stream, s, a);
+        else                         hipLaunchKernelGGL((k_plane_support<LAYOUT_WORDS>), grid, block, lds, c->stream, s, a);
+        HIP_TRY(c, hipGetLastError());
+        std::vector<unsigned long long> counts((size_t)num_hyp);
+        std::vector<uint32_t> cand((size_t)nD);
+        HIP_TRY(c, hipMemcpyAsync(counts.data(), c->d_plane_counts, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(cand.data(), c->d_plane_candidates, cand.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (int j = 0; j < num_hyp; ++j) host_counts[j] += (int64_t)counts[(size_t)j];
+        size_t at = 0;
+        for (int64_t k = 0; k < nD; ++k) {
+            st.candidates_decoded += cand[(size_t)k];
+            const int32_t m = later[at++];
+            for (int32_t q = 0; q < m; ++q) host_counts[later[at++]] += cand[(size_t)k];
+        }
+    }
+    if (stats) *stats = st;
+    return PCR_OK;
 }
 
 // ---- top-down grid -----------------------------------------------------------------------------

@@ -9,6 +9,7 @@
 //     pcr_decode <in.huffman> <out.ply> --normals R [MINCOUNT] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --sor K MULT R [--outliers] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]
+//     pcr_decode <in.huffman> <out.las> --slab px py pz nx ny nz DIST [--outside] [--box x0 y0 z0 x1 y1 z1]
 //     pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1] [--rect x0 y0 x1 y1]
 //                                                [--visible front|surface [--occluder R]]
 //     pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]
@@ -57,6 +58,7 @@ static const char *USAGE =
     "       pcr_decode <in.huffman> <out.ply> --normals R [MINCOUNT] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --sor K MULT R [--outliers] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --polygon FILE [--z LO HI] [--outside]\n"
+    "       pcr_decode <in.huffman> <out.las> --slab px py pz nx ny nz DIST [--outside] [--box x0 y0 z0 x1 y1 z1]\n"
     "       pcr_decode <in.huffman> <out.las> --view [--size WxH] [--camera yaw pitch radius tx ty tz] [--lod f] [--cull 0|1]\n"
     "                                                [--rect x0 y0 x1 y1] [--visible front|surface [--occluder R]]\n"
     "       pcr_decode <in.huffman> <out.ppm> --ortho CELL [--box x0 y0 z0 x1 y1 z1] [--dsm out.asc]\n"
@@ -114,6 +116,10 @@ static const char *USAGE =
     "  nearest lattice step of the stream. The boundary is half-open: of two polygons that share an edge exactly one takes a\n"
     "  point on it. --z: of those the points with LO <= p.z <= HI; --outside: the points NOT inside the polygon (--z still\n"
     "  applies). A polygon that holds no point is an error.\n"
+    "  --slab: only the points within DIST of the plane through (px, py, pz) with the normal (nx, ny, nz), world units, selected\n"
+    "  on the GPU in the stream's order; the normal may have any length but zero. --outside: the other points. Only the points\n"
+    "  inside --box count, or inside the box of the file's header. No point to write is an error. It combines with no other\n"
+    "  selecting option.\n"
     "  --view: only the points a frame of that camera draws (the basic method's cull and level of detail; the options and their\n"
     "  defaults are pcr_render's), in the stream's order; --rect: of those the ones whose pixel lies in the rectangle (pixels,\n"
     "  bounds inclusive, x0 <= x1 and y0 <= y1). A view that shows no point is an error.\n"
@@ -514,6 +520,33 @@ static bool parse_polygon(int argc, char **argv, int at, Poly &p)
     return true;
 }
 
+struct SlabOpt {
+    double point[3], normal[3], dist = 0.0;
+    bool outside = false, has_box = false;
+    double lo[3], hi[3];
+};
+
+// the options behind --slab, every one well formed, or false
+static bool parse_slab(int argc, char **argv, int at, SlabOpt &o)
+{
+    if (argc < at + 8 || std::strcmp(argv[at], "--slab") != 0) return false;
+    for (int k = 0; k < 7; ++k)
+        if (!parse_double(argv[at + 1 + k], k < 3 ? o.point[k] : k < 6 ? o.normal[k - 3] : o.dist)) return false;
+    if (!(o.dist >= 0.0) || (o.normal[0] == 0.0 && o.normal[1] == 0.0 && o.normal[2] == 0.0)) return false;
+    for (int i = at + 8; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--box" && i + 6 < argc && !o.has_box) {
+            for (int k = 0; k < 6; ++k) if (!parse_double(argv[++i], k < 3 ? o.lo[k] : o.hi[k - 3])) return false;
+            o.has_box = true;
+        } else if (a == "--outside" && !o.outside) {
+            o.outside = true;
+        } else {
+            return false;
+        }
+    }
+    return true;
+}
+
 struct Ortho {
     double cell = 0.0;
     bool has_box = false;
@@ -757,6 +790,8 @@ int main(int argc, char **argv)
     const bool lodded = argc > 3 && std::strcmp(argv[3], "--lod") == 0;
     Poly poly;
     const bool polygoned = argc > 3 && std::strcmp(argv[3], "--polygon") == 0;
+    SlabOpt slab;
+    const bool slabbed = argc > 3 && std::strcmp(argv[3], "--slab") == 0;
     Denoise noise;
     const bool denoised = argc > 3 && std::strcmp(argv[3], "--denoise") == 0;
     Components comps;
@@ -771,8 +806,8 @@ int main(int argc, char **argv)
     const bool sored = argc > 3 && std::strcmp(argv[3], "--sor") == 0;
     Percentile pctl;
     const bool percentiled = argc > 3 && std::strcmp(argv[3], "--percentile") == 0;
-    const bool boxed = argc > 3 && !percentiled && !viewed && !orthoed && !thinned && !lodded && !polygoned && !denoised && !componented && !grounded && !radiused && !normaled && !sored;
-    if (argc < 3 || (polygoned && !parse_polygon(argc, argv, 3, poly)) || (boxed && !parse_box(argc, argv, 3, lo, hi)) || (viewed && !parse_view(argc, argv, 3, view)) ||
+    const bool boxed = argc > 3 && !percentiled && !viewed && !orthoed && !thinned && !lodded && !polygoned && !slabbed && !denoised && !componented && !grounded && !radiused && !normaled && !sored;
+    if (argc < 3 || (polygoned && !parse_polygon(argc, argv, 3, poly)) || (slabbed && !parse_slab(argc, argv, 3, slab)) || (boxed && !parse_box(argc, argv, 3, lo, hi)) || (viewed && !parse_view(argc, argv, 3, view)) ||
         (orthoed && !parse_ortho(argc, argv, 3, ortho)) || (thinned && !parse_thin(argc, argv, 3, thin)) || (lodded && !parse_lod(argc, argv, 3, lod)) || (denoised && !parse_denoise(argc, argv, 3, noise)) ||
         (componented && !parse_components(argc, argv, 3, comps)) || (grounded && !parse_ground(argc, argv, 3, ground)) ||
         (radiused && !parse_radius(argc, argv, 3, rad)) || (normaled && !parse_normals(argc, argv, 3, nrm)) ||
@@ -847,6 +882,14 @@ int main(int argc, char **argv)
             std::printf("polygon: batches outside %lld, inside %lld, straddling %lld, edges listed %lld, largest list %lld\n", (long long)st.batches_outside,
                         (long long)st.batches_inside, (long long)st.batches_straddling, (long long)st.edges_listed, (long long)st.edges_max);
             if (points.empty()) throw std::runtime_error("no points inside the polygon: nothing written");
+        } else if (slabbed) {
+            const std::vector<pcr_slab> slabs{slabFromWorld(info, slab.point, slab.normal, slab.dist)};
+            const pcr_box clip = boxFromWorld(info, slab.has_box ? slab.lo : info.min, slab.has_box ? slab.hi : info.max);
+            const pcr_slab_stats st = las->selectSlabs(slabs, &clip, slab.outside ? PCR_SLAB_INVERT : 0u, points);
+            std::printf("slab: normal %d %d %d, %lld .. %lld, written %lld, batches outside %lld, inside %lld, straddling %lld\n", slabs[0].n[0], slabs[0].n[1],
+                        slabs[0].n[2], (long long)slabs[0].lo, (long long)slabs[0].hi, (long long)st.points_selected, (long long)st.batches_outside,
+                        (long long)st.batches_inside, (long long)st.batches_straddling);
+            if (points.empty()) throw std::runtime_error("no points to write: nothing written");
         } else if (thinned) {
             const pcr_voxels vox = voxelsFromWorld(info, thin.cell, info.min);
             const pcr_box clip = boxFromWorld(info, thin.has_box ? thin.lo : info.min, thin.has_box ? thin.hi : info.max);

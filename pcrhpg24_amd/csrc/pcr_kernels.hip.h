@@ -19,6 +19,7 @@
 //   k_visible_*     on request: of those points the ones that make up the picture, by per-pixel planes of front depth and index
 //   k_grid*         on request: the stream rasterized top-down into max / min / count planes over its integer x and y
 //   k_polygon_*     on request: the records inside a polygon prism, each straddling batch against its own edge list in LDS
+//   k_slab_* / k_plane_support  on request: the records in a set of slabs lo <= n.p <= hi; the support of plane hypotheses
 //   k_thin_*        on request: one record per voxel of a cubic lattice, straight from the compressed stream
 //   k_denoise_*     on request: the records whose 3 x 3 x 3 voxels hold few points (or the others), on k_thin_*'s frame
 //   k_components_*  on request: the connected components of the occupied voxels, the small ones dropped or extracted
@@ -36,6 +37,7 @@
 #include "pcr_types.h"
 #include "pcr_lattice.h"
 #include "pcr_polygon.h"
+#include "pcr_plane.h"
 
 namespace pcr {
 
@@ -2345,6 +2347,169 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_polygon_write(StreamView
     decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, pb.b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t colour) {
         if (in_polygon(a, s_edges, pb.edge_count, pb.base_parity, x, y, z) && dst < end) *dst++ = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Slabs (pcr_plane_support, pcr_select_slabs): lo <= n.p <= hi in exact 64-bit integers, for the batches whose exact box a slab
+// cuts. The host (pcr_plane.h) gives every such batch its own slices of slab arrays; the workgroup copies them into LDS beside
+// the table as 32-byte entries (n[3], a word, lo, hi), launch-sized to the largest slices listed. Per point and entry all lanes
+// read the same entry (two ds_read_b128 that broadcast), three 32 x 32 -> 64 multiply-adds, two 64-bit compares.
+//   k_slab_count / k_slab_write   k_select_count / k_select_write with "inside the clip and in all of the slice" as the test
+//   k_plane_support               counts, per hypothesis of the batch's slice, the candidates in it: a wave-wide vote per
+//                                 hypothesis, its population count added by one lane into the wave's own row of 32-bit LDS
+//                                 counters (a zero vote adds nothing; a wave without a candidate skips the slice); after the
+//                                 chain the rows are summed, one 64-bit global atomic add per non-zero hypothesis. Sums commute,
+//                                 so the counts do not depend on the order of lanes, workgroups or launches.
+// ------------------------------------------------------------------------------------------------
+struct SlabBatch { uint32_t b, first, count, invert; };             // a straddling batch and its slice of the slab array
+struct SlabArgs {
+    pcr_box clip;
+    uint32_t lds_slabs;             // slabs the launch's dynamic LDS holds behind the table: the largest slice listed
+    const SlabBatch *batches;
+    const pcr_slab *slabs;
+};
+struct PlaneBatch { uint32_t b, excl_first, excl_count, hyp_first, hyp_count; };    // a decoded batch and its two slices
+struct PlaneArgs {
+    pcr_box clip;
+    uint32_t lds_excl, lds_hyp;     // entries the launch's dynamic LDS holds: table, lds_excl slabs, lds_hyp slabs, LWC_WAVES rows of lds_hyp counters
+    const PlaneBatch *batches;
+    const pcr_slab *excl, *hyp;     // the slices, back to back; a hypothesis carries its index in `reserved`
+    unsigned long long *counts;     // [num_hyp], cleared by the host
+    uint32_t *candidates;           // [decoded batches]
+};
+constexpr uint32_t SLAB_TABLE_BYTES = PCR_HUFFMAN_TABLE_SIZE * 4;
+
+// entry k of a slice in LDS against one point
+__device__ __forceinline__ bool in_slab(const int4 *s_slabs, uint32_t k, int32_t x, int32_t y, int32_t z)
+{
+    const int4 n = s_slabs[2 * k], w = s_slabs[2 * k + 1];                  // n0 n1 n2 word, lo, hi
+    const int64_t v = (int64_t)n.x * x + (int64_t)n.y * y + (int64_t)n.z * z;
+    const int64_t lo = (int64_t)(((uint64_t)(uint32_t)w.y << 32) | (uint32_t)w.x), hi = (int64_t)(((uint64_t)(uint32_t)w.w << 32) | (uint32_t)w.z);
+    return v >= lo && v <= hi;
+}
+
+// `count` slabs from src[first ..] into LDS (no barrier)
+__device__ __forceinline__ void load_slab_slice(const pcr_slab *src, uint32_t first, uint32_t count, int4 *s_slabs)
+{
+    const int4 *from = reinterpret_cast<const int4 *>(src + first);
+    for (uint32_t i = threadIdx.x; i < 2u * count; i += PCR_WORKGROUP_SIZE) s_slabs[i] = from[i];
+}
+
+__device__ __forceinline__ bool in_slabs(const SlabArgs &a, const int4 *s_slabs, uint32_t count, uint32_t invert, int32_t x, int32_t y, int32_t z)
+{
+    if (!in_box(a.clip, x, y, z)) return false;
+    bool all = true;
+    for (uint32_t k = 0; k < count; ++k) all = all && in_slab(s_slabs, k, x, y, z);
+    return all != (invert != 0u);
+}
+
+// Workgroup x takes the straddling batch a.batches[x]: chain_counts[x * 1024 + chain] = its points selected, totals[x] = their sum
+template <int LAYOUT>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_slab_count(StreamView s, SlabArgs a, uint32_t *chain_counts, uint32_t *totals)
+{
+    const SlabBatch sb = a.batches[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    extern __shared__ __align__(16) unsigned char s_dyn[];                  // the table, then a.lds_slabs slabs
+    __shared__ uint32_t s_part[LWC_WAVES];
+    uint32_t *s_table = reinterpret_cast<uint32_t *>(s_dyn);
+    int4 *s_slabs = reinterpret_cast<int4 *>(s_dyn + SLAB_TABLE_BYTES);
+    if (sb.count > a.lds_slabs) return;                                     // (uniform; the host never lists such a slice)
+    load_slab_slice(a.slabs, sb.first, sb.count, s_slabs);
+    load_packed_table(s, sb.b, s_table);
+    uint32_t cnt = 0;
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, sb.b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t) {
+        cnt += in_slabs(a, s_slabs, sb.count, sb.invert, x, y, z) ? 1u : 0u;
+    });
+    chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid] = cnt;
+    uint32_t sum = cnt;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    if (lane == 0) s_part[wave] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < LWC_WAVES; ++w) t += s_part[w];
+        totals[blockIdx.x] = t;
+    }
+}
+
+// Workgroup x takes the straddling batch a.batches[x]: its selected records go to out[offsets[x] ..] as k_select_write's do.
+// chain_counts is k_slab_count's, for the same batches, slabs and arguments.
+template <int LAYOUT, bool BC7>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_slab_write(StreamView s, SlabArgs a, const uint32_t *chain_counts, const int64_t *offsets, uint4 *out)
+{
+    const SlabBatch sb = a.batches[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    extern __shared__ __align__(16) unsigned char s_dyn[];                  // the table, then a.lds_slabs slabs
+    __shared__ uint32_t s_part[LWC_WAVES];
+    uint32_t *s_table = reinterpret_cast<uint32_t *>(s_dyn);
+    int4 *s_slabs = reinterpret_cast<int4 *>(s_dyn + SLAB_TABLE_BYTES);
+    if (sb.count > a.lds_slabs) return;
+    const uint32_t mine = chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid];
+    uint32_t incl = mine;                                   // inclusive prefix inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += up;
+    }
+    if (lane == 63) s_part[wave] = incl;
+    load_slab_slice(a.slabs, sb.first, sb.count, s_slabs);
+    load_packed_table(s, sb.b, s_table);                    // (its barrier publishes s_part and the slice as well)
+    uint32_t before = incl - mine;
+    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    uint4 *dst = out + offsets[blockIdx.x] + before;
+    uint4 *const end = dst + mine;                          // never past what k_slab_count counted for this chain
+    decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, sb.b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t colour) {
+        if (in_slabs(a, s_slabs, sb.count, sb.invert, x, y, z) && dst < end) *dst++ = make_uint4((uint32_t)x, (uint32_t)y, (uint32_t)z, colour);
+    });
+}
+
+// Workgroup x takes the decoded batch a.batches[x]: a.candidates[x] = its records inside the clip and in no slab of its exclusion
+// slice; a.counts[j] += those of them in hypothesis j, for every j of its hypothesis slice. decode_chain calls the sink uniformly
+// over the workgroup, so the votes see whole waves.
+template <int LAYOUT>
+__global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_plane_support(StreamView s, PlaneArgs a)
+{
+    const PlaneBatch pb = a.batches[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    __shared__ uint32_t s_part[LWC_WAVES];
+    uint32_t *s_table = reinterpret_cast<uint32_t *>(s_dyn);
+    int4 *s_excl = reinterpret_cast<int4 *>(s_dyn + SLAB_TABLE_BYTES);
+    int4 *s_hyp = s_excl + 2u * a.lds_excl;
+    uint32_t *s_rows = reinterpret_cast<uint32_t *>(s_hyp + 2u * a.lds_hyp);    // [LWC_WAVES][a.lds_hyp]
+    if (pb.excl_count > a.lds_excl || pb.hyp_count > a.lds_hyp) return;         // (uniform; the host never lists such slices)
+    load_slab_slice(a.excl, pb.excl_first, pb.excl_count, s_excl);
+    load_slab_slice(a.hyp, pb.hyp_first, pb.hyp_count, s_hyp);
+    for (uint32_t i = tid; i < (uint32_t)LWC_WAVES * a.lds_hyp; i += PCR_WORKGROUP_SIZE) s_rows[i] = 0u;
+    load_packed_table(s, pb.b, s_table);                    // (its barrier publishes the slices and the cleared rows as well)
+    uint32_t *const row = s_rows + wave * a.lds_hyp;
+    uint32_t cand = 0;
+    decode_chain<LAYOUT, SEL_NO_COLOUR>(s, pb.b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t) {
+        bool c = in_box(a.clip, x, y, z);
+        for (uint32_t k = 0; k < pb.excl_count; ++k) c = c && !in_slab(s_excl, k, x, y, z);
+        cand += c ? 1u : 0u;
+        if (__ballot(c) == 0ull) return;
+        for (uint32_t k = 0; k < pb.hyp_count; ++k) {
+            const uint64_t vote = __ballot(c && in_slab(s_hyp, k, x, y, z));
+            if (vote != 0ull && lane == 0u) row[k] += (uint32_t)__popcll(vote);     // the wave's own row: no other wave touches it
+        }
+    });
+    uint32_t sum = cand;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    if (lane == 0) s_part[wave] = sum;
+    __syncthreads();
+    for (uint32_t k = tid; k < pb.hyp_count; k += PCR_WORKGROUP_SIZE) {
+        uint32_t t = 0;
+        for (int w = 0; w < LWC_WAVES; ++w) t += s_rows[(uint32_t)w * a.lds_hyp + k];
+        if (t) atomicAdd(&a.counts[(uint32_t)s_hyp[2 * k].w], (unsigned long long)t);
+    }
+    if (tid == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < LWC_WAVES; ++w) t += s_part[w];
+        a.candidates[blockIdx.x] = t;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -346,6 +346,35 @@ struct HuffmanLasData : Resource {
         return st;
     }
 
+    // The support of plane hypotheses (pcr_plane_support): counts[j] = the points inside `clip` (NULL: everywhere) and in no slab of
+    // `exclude` that are in hyp[j], of every batch the context holds right now, counted on the GPU straight from the compressed
+    // stream. Not in the reference.
+    pcr_plane_stats planeSupport(const std::vector<pcr_slab> &hyp, const pcr_box *clip, const std::vector<pcr_slab> &exclude, std::vector<int64_t> &counts)
+    {
+        if (!loadedOn) throw std::runtime_error("planeSupport: the resource is not loaded");
+        const int64_t nB = pcr_batches_resident(loadedOn->ctx);
+        counts.assign(hyp.size(), 0);
+        pcr_plane_stats st{};
+        loadedOn->check(pcr_plane_support(loadedOn->ctx, 0, nB, hyp.data(), (int)hyp.size(), clip, exclude.empty() ? nullptr : exclude.data(),
+                                          (int)exclude.size(), counts.data(), &st), "pcr_plane_support");
+        return st;
+    }
+
+    // The points inside `clip` (NULL: everywhere) that are in all of `slabs`, with PCR_SLAB_INVERT in `flags` those that are not, of
+    // every batch the context holds right now, selected on the GPU (pcr_read_slabs: batches a slab misses are not decoded). Not in
+    // the reference.
+    pcr_slab_stats selectSlabs(const std::vector<pcr_slab> &slabs, const pcr_box *clip, uint32_t flags, std::vector<pcr_point> &out)
+    {
+        if (!loadedOn) throw std::runtime_error("selectSlabs: the resource is not loaded");
+        const int64_t nB = pcr_batches_resident(loadedOn->ctx);
+        int64_t n = 0;
+        pcr_slab_stats st{};
+        loadedOn->check(pcr_read_slabs(loadedOn->ctx, 0, nB, slabs.data(), (int)slabs.size(), clip, flags, nullptr, 0, &n, &st), "pcr_read_slabs");
+        out.resize((size_t)n);
+        if (n) loadedOn->check(pcr_read_slabs(loadedOn->ctx, 0, nB, slabs.data(), (int)slabs.size(), clip, flags, out.data(), out.size(), &n, &st), "pcr_read_slabs");
+        return st;
+    }
+
     // One point per voxel of `vox` among the points inside `clip` (NULL: everywhere), thinned on the GPU straight from the compressed
     // stream (pcr_read_thin: a counting call, then the read). Not in the reference.
     pcr_thin_stats thin(const pcr_voxels &vox, const pcr_box *clip, int mode, std::vector<pcr_point> &out)
@@ -858,6 +887,38 @@ inline pcr_lod lodFromWorld(const pcr_las_info &las, double cell_size, int level
     const pcr_voxels vox = voxelsFromWorld(las, cell_size, origin);
     if (((int64_t)vox.cell << (levels - 1)) > PCR_THIN_MAX_CELL) throw std::runtime_error("lodFromWorld: the coarsest cell is more than 2^30 lattice steps");
     return pcr_lod{{vox.origin[0], vox.origin[1], vox.origin[2]}, vox.cell, levels, 0};
+}
+
+// The slab of the points within `distance` world units of the plane through `point` with the normal `normal` (world coordinates, any
+// length). In lattice coordinates the form is (nw_a * scale_a) . p: n_a = rint(nw_a * scale_a * k) with k = 2^20 / max |nw_a * scale_a|,
+// p = rint((point - offset) / scale), d = n . p exactly, the tolerance floor(distance * |nw| * k) in double. The Python twin is
+// host.slab_from_world.
+inline pcr_slab slabFromWorld(const pcr_las_info &las, const double point[3], const double normal[3], double distance)
+{
+    double w[3], m = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        if (!(las.scale[k] > 0.0) || !std::isfinite(point[k]) || !std::isfinite(las.offset[k])) throw std::runtime_error("slabFromWorld: needs a positive scale and a finite point");
+        w[k] = normal[k] * las.scale[k];
+        if (!std::isfinite(w[k])) throw std::runtime_error("slabFromWorld: the normal is not finite");
+        m = std::max(m, std::fabs(w[k]));
+    }
+    if (!(m > 0.0)) throw std::runtime_error("slabFromWorld: the normal is zero");
+    if (!(distance >= 0.0) || !std::isfinite(distance)) throw std::runtime_error("slabFromWorld: needs a finite distance that is not negative");
+    const double k = (double)PCR_SLAB_MAX_NORMAL / m;
+    pcr_slab s{};
+    int64_t d = 0;
+    for (int a = 0; a < 3; ++a) {
+        s.n[a] = (int32_t)std::nearbyint(w[a] * k);
+        const double p = std::nearbyint((point[a] - las.offset[a]) / las.scale[a]);
+        if (!(p >= (double)INT32_MIN && p <= (double)INT32_MAX)) throw std::runtime_error("slabFromWorld: the point lies beyond the int32 lattice of the stream");
+        d += (int64_t)s.n[a] * (int64_t)p;
+    }
+    const double len = std::sqrt(normal[0] * normal[0] + normal[1] * normal[1] + normal[2] * normal[2]);
+    const double t = std::floor(distance * len * k);
+    if (!(t <= (double)PCR_SLAB_MAX_BOUND / 2)) throw std::runtime_error("slabFromWorld: the distance is beyond the bounds of a slab");
+    s.lo = d - (int64_t)t;
+    s.hi = d + (int64_t)t;
+    return s;
 }
 
 // The largest whole number r of lattice steps with r * scale <= radius (as doubles): the radius pcr_neighbors takes for `radius`

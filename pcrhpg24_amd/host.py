@@ -326,6 +326,170 @@ def polygon_from_world(las: LasInfo, rings, z_lo=None, z_hi=None, invert: bool =
     return Polygon(out, zb.min[2], zb.max[2], invert)
 
 
+class Slab:
+    """A slab in the stream's int32 coordinates (pcr_slab): the points p with lo <= normal . p <= hi, the form taken in exact
+    integers. lo > hi is legal and empty; a bound at -/+SLAB_MAX_BOUND makes a half-space; the zero normal holds every point or
+    none. ValueError for a value that is not a whole number, a normal component beyond SLAB_MAX_NORMAL or a bound beyond
+    SLAB_MAX_BOUND (nothing is rounded or wrapped here)."""
+
+    def __init__(self, normal, lo, hi):
+        try:
+            n = tuple(int(v) for v in normal)
+            b = (int(lo), int(hi))
+            if len(n) != 3 or any(float(a) != float(v) for a, v in zip(n + b, tuple(normal) + (lo, hi))):
+                raise ValueError
+        except (ValueError, TypeError, OverflowError):
+            raise ValueError("a slab is three whole numbers (the normal) and two whole bounds") from None
+        if any(abs(v) > N.SLAB_MAX_NORMAL for v in n):
+            raise ValueError(f"a normal component beyond {N.SLAB_MAX_NORMAL}")
+        if any(abs(v) > N.SLAB_MAX_BOUND for v in b):
+            raise ValueError("a bound beyond 2^61")
+        self.normal, self.lo, self.hi = n, b[0], b[1]
+        self.c = N.Slab((N.c_i32 * 3)(*n), 0, b[0], b[1])
+
+    def __repr__(self):
+        return f"Slab({self.normal}, {self.lo}, {self.hi})"
+
+
+def slab_from_plane(normal, d, tol) -> Slab:
+    """The slab |normal . p - d| <= tol: lo = d - tol, hi = d + tol."""
+    return Slab(normal, int(d) - int(tol), int(d) + int(tol))
+
+
+def as_slabs(slabs):
+    """A ctypes array of pcr_slab from a sequence of Slab (or one Slab); such an array is passed through."""
+    if isinstance(slabs, C.Array) and slabs._type_ is N.Slab:
+        return slabs
+    if isinstance(slabs, (Slab, N.Slab)):
+        slabs = [slabs]
+    slabs = list(slabs)
+    out = (N.Slab * len(slabs))()
+    for k, sl in enumerate(slabs):
+        if isinstance(sl, Slab):
+            sl = sl.c
+        elif not isinstance(sl, N.Slab):
+            sl = Slab(*sl).c
+        out[k] = sl
+    return out
+
+
+def plane_through(p0, p1, p2):
+    """The plane through three integer points as (normal, d) with normal . p = d on it, in Python integers: the cross product of
+    the differences divided by its gcd; if a component then exceeds M = SLAB_MAX_NORMAL, every component becomes
+    floor((2 * n_a * M + m) / (2 * m)) with m = max |n_a| (the nearest multiple, floor division); the sign such that the first
+    non-zero of n[2], n[1], n[0] is positive (pcr_eigen's convention); d = normal . p0 exactly. None for collinear points."""
+    import math
+    p0, p1, p2 = (tuple(int(v) for v in p) for p in (p0, p1, p2))
+    u, v = [p1[k] - p0[k] for k in range(3)], [p2[k] - p0[k] for k in range(3)]
+    n = [u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]]
+    g = math.gcd(*n)
+    if g == 0:
+        return None
+    n = [a // g for a in n]
+    m, M = max(abs(a) for a in n), N.SLAB_MAX_NORMAL
+    if m > M:
+        n = [(2 * a * M + m) // (2 * m) for a in n]
+    lead = next(a for a in (n[2], n[1], n[0]) if a != 0)
+    if lead < 0:
+        n = [-a for a in n]
+    return tuple(n), sum(a * b for a, b in zip(n, p0))
+
+
+def slab_tolerance(normal, dist) -> int:
+    """isqrt(dist^2 * (normal . normal)): the largest whole t with t <= dist * |normal|, so that |normal . p - d| <= t iff the
+    point lies within `dist` stream units of the plane (dist a whole number of lattice steps)."""
+    import math
+    dist = int(dist)
+    if dist < 0:
+        raise ValueError("a distance is not negative")
+    return math.isqrt(dist * dist * sum(int(a) * int(a) for a in normal))
+
+
+PLANE_REDRAWS = 8
+
+
+def plane_hypotheses(xyz, count: int, rng):
+    """`count` plane hypotheses through triples of the integer points xyz -- one [n, 3] array, or a sequence of them (one per
+    batch): the three points of a hypothesis come from the same array, hence from one neighbourhood of the Morton order. Per
+    hypothesis: an array (rng.integers), three rows of it (rng.integers), redrawn at most PLANE_REDRAWS times while the points are
+    collinear; a hypothesis that stays collinear is left out, so fewer than `count` may come back. Returns (normals int64 [m, 3],
+    d int64 [m]) as plane_through gives them. Pure numpy and Python integers; the same rng state gives the same list."""
+    groups = [np.asarray(xyz)] if isinstance(xyz, np.ndarray) else [np.asarray(g) for g in xyz]
+    groups = [g.reshape(-1, 3) for g in groups if g.size >= 9]
+    normals, ds = [], []
+    for _ in range(int(count) if groups else 0):
+        g = groups[int(rng.integers(0, len(groups)))]
+        for _ in range(1 + PLANE_REDRAWS):
+            i, j, k = (int(v) for v in rng.integers(0, len(g), 3))
+            plane = plane_through(g[i], g[j], g[k])
+            if plane is not None:
+                normals.append(plane[0]); ds.append(plane[1])
+                break
+    return np.array(normals, np.int64).reshape(-1, 3), np.array(ds, np.int64)
+
+
+def slab_from_world(las: LasInfo, point, normal, distance: float) -> Slab:
+    """The slab of the points within `distance` world units of the plane through `point` with the normal `normal` (world
+    coordinates; any length). In lattice coordinates the form is (nw_a * scale_a) . p: n_a = rint(nw_a * scale_a * k) with
+    k = SLAB_MAX_NORMAL / max |nw_a * scale_a|, p = rint((point - offset) / scale), d = n . p exactly, and the tolerance
+    floor(distance * |nw| * k) in float64. ValueError for a zero or non-finite normal, a point beyond int32 or a negative distance."""
+    import math
+    sc, off = [float(v) for v in las.scale], [float(v) for v in las.offset]
+    nw, pw = [float(v) for v in normal], [float(v) for v in point]
+    w = [a * b for a, b in zip(nw, sc)]
+    m = max(abs(a) for a in w)
+    if len(nw) != 3 or len(pw) != 3 or not all(math.isfinite(a) for a in w + pw) or not m > 0.0 or not all(a > 0.0 for a in sc):
+        raise ValueError("slab_from_world needs a positive scale, a finite point and a finite normal that is not zero")
+    distance = float(distance)
+    if not distance >= 0.0 or math.isinf(distance):
+        raise ValueError("slab_from_world needs a finite distance that is not negative")
+    k = float(N.SLAB_MAX_NORMAL) / m
+    n = [int(np.rint(a * k)) for a in w]
+    p = [float(np.rint((a - o) / s)) for a, o, s in zip(pw, off, sc)]
+    if any(a < INT32_MIN or a > INT32_MAX for a in p):
+        raise ValueError("the point lies beyond the int32 lattice of the stream")
+    d = sum(a * int(b) for a, b in zip(n, p))
+    tol = int(math.floor(distance * math.sqrt(sum(a * a for a in nw)) * k))
+    return slab_from_plane(n, d, tol)
+
+
+def fit_planes_rounds(read_batch, support, num_batches: int, tolerance_steps: int, num_planes: int = 1, hypotheses: int = 256, seed: int = 0,
+                      min_support: int = 3, clip=None, sample_batches: int = 4):
+    """The RANSAC rounds of HuffmanLasData.fit_planes over two callables: read_batch(b) -> integer [65536, 3] points of batch b,
+    support(hyp, exclude) -> the number of candidates in every Slab of hyp, the candidates being the points inside the clip and
+    in no Slab of exclude. Per round: `sample_batches` batches chosen by numpy.random.default_rng(seed) (rng.choice without
+    replacement, sorted), their points that are still candidates (inside `clip`, in no plane found so far), `hypotheses` planes
+    through them (plane_hypotheses) with the tolerance slab_tolerance(normal, tolerance_steps), one support call with a
+    zero-normal slab appended (it counts every candidate), the hypothesis of greatest support (ties: the lowest index). Stops after
+    num_planes planes, when the best support is below min_support or when no hypothesis can be drawn. Returns (slabs, supports,
+    candidates): the planes found, their supports and the candidate count of every round made."""
+    rng = np.random.default_rng(seed)
+    found, supports, candidates = [], [], []
+    for _ in range(int(num_planes)):
+        pick = np.sort(rng.choice(num_batches, size=min(int(sample_batches), num_batches), replace=False))
+        groups = []
+        for b in pick:
+            g = np.asarray(read_batch(int(b)), np.int64).reshape(-1, 3)
+            keep = np.ones(len(g), bool)
+            if clip is not None:
+                keep &= ((g >= np.array(tuple(clip.min), np.int64)) & (g <= np.array(tuple(clip.max), np.int64))).all(axis=1)
+            for sl in found:
+                v = g @ np.array(sl.normal, np.int64)
+                keep &= ~((v >= sl.lo) & (v <= sl.hi))
+            groups.append(g[keep])
+        normals, d = plane_hypotheses(groups, hypotheses, rng)
+        if len(d) == 0:
+            break
+        hyp = [slab_from_plane(n, int(dk), slab_tolerance(n, tolerance_steps)) for n, dk in zip(normals.tolist(), d.tolist())]
+        counts = np.asarray(support(hyp + [Slab((0, 0, 0), 0, 0)], list(found)), np.int64)
+        candidates.append(int(counts[-1]))
+        best = int(np.argmax(counts[:-1]))
+        if int(counts[best]) < int(min_support):
+            break
+        found.append(hyp[best]); supports.append(int(counts[best]))
+    return found, supports, candidates
+
+
 def as_grid(grid) -> Grid:
     """A pcr_grid from a Grid or five numbers origin_x, origin_y, cell, width, height (the stream's int32 coordinates, cells)."""
     if isinstance(grid, Grid):
@@ -991,6 +1155,62 @@ class Context:
         if cnt.value:
             self._chk(self.lib.pcr_read_polygon(self.h, first, nb, C.byref(poly.c), out.ctypes.data, len(out), C.byref(cnt), C.byref(st)), "pcr_read_polygon")
         self.polygon_stats = st.as_dict()
+        return out
+
+    # -- slabs (pcr_plane_support / pcr_select_slabs / pcr_read_slabs) -----------------------------------------
+    def plane_support(self, hyp, clip=None, exclude=(), first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The support of plane hypotheses: numpy int64 [num_hyp], entry j the number of candidates in hyp[j] -- the records of
+        batches [first, first + count) inside `clip` (as_box; None: all) and in no slab of `exclude` (the planes found already).
+        hyp and exclude are sequences of Slab (as_slabs). Counted on the GPU from the compressed stream; no record is written
+        (pcr_plane_support; synchronises). What the host plan did is in self.plane_stats."""
+        h, x = as_slabs(hyp), as_slabs(exclude)
+        box = None if clip is None else as_box(clip)
+        out = np.zeros(len(h), np.int64)
+        st = N.PlaneStats()
+        self._chk(self.lib.pcr_plane_support(self.h, first, -1 if count is None else count, h, len(h), None if box is None else C.byref(box),
+                                             x if len(x) else None, len(x), out.ctypes.data_as(C.POINTER(c_i64)), C.byref(st)), "pcr_plane_support")
+        self.plane_stats = st.as_dict()
+        return out
+
+    def select_slabs(self, slabs, clip=None, invert: bool = False, first: int = 0, count: Optional[int] = None, out=None):
+        """The points of batches [first, first + count) inside `clip` (as_box; None: all) that are in all of `slabs` (a sequence of
+        1 to 16 Slab) -- with invert=True those inside the clip that are not -- as a torch.int32 tensor [n, 4] on the context's
+        device: select_box with another predicate, `out` and the stream ordering as there. The batch classes, the count and the
+        slab-list sizes of the last call are in self.slab_stats."""
+        import torch
+        s = as_slabs(slabs)
+        box = None if clip is None else as_box(clip)
+        pbox = None if box is None else C.byref(box)
+        flags = N.SLAB_INVERT if invert else 0
+        dev = torch.device("cuda", self.device)
+        cnt, st, nb = c_i64(), N.SlabStats(), -1 if count is None else count
+        if out is None:
+            self._chk(self.lib.pcr_select_slabs(self.h, first, nb, s, len(s), pbox, flags, None, 0, C.byref(cnt), C.byref(st)), "pcr_select_slabs")
+            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
+        torch.cuda.current_stream(dev).synchronize()
+        rc = self.lib.pcr_select_slabs(self.h, first, nb, s, len(s), pbox, flags, C.c_void_p(out.data_ptr() if out.numel() else None), out.numel() // 4,
+                                       C.byref(cnt), C.byref(st))
+        self.slab_stats = st.as_dict()
+        if rc:
+            self.slab_stats["points_selected"] = cnt.value
+        self._chk(rc, "pcr_select_slabs")
+        return out.view(-1, 4)[:cnt.value]
+
+    def read_slabs(self, slabs, clip=None, invert: bool = False, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The same on the host, without torch: a numpy structured array of POINT_DTYPE (pcr_read_slabs: a counting call, then
+        the read; synchronises)."""
+        s = as_slabs(slabs)
+        box = None if clip is None else as_box(clip)
+        pbox = None if box is None else C.byref(box)
+        flags = N.SLAB_INVERT if invert else 0
+        cnt, st, nb = c_i64(), N.SlabStats(), -1 if count is None else count
+        self._chk(self.lib.pcr_read_slabs(self.h, first, nb, s, len(s), pbox, flags, None, 0, C.byref(cnt), C.byref(st)), "pcr_read_slabs")
+        out = np.empty(cnt.value, POINT_DTYPE)
+        if cnt.value:
+            self._chk(self.lib.pcr_read_slabs(self.h, first, nb, s, len(s), pbox, flags, out.ctypes.data, len(out), C.byref(cnt), C.byref(st)), "pcr_read_slabs")
+        self.slab_stats = st.as_dict()
         return out
 
     # -- top-down grid (pcr_grid_clear / pcr_grid_accumulate / pcr_grid_unpack / pcr_read_grid) --------------
@@ -1862,6 +2082,42 @@ class HuffmanLasData(Resource):
             return pts
         so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
         return pts[:, :3].to(torch.float64) * so[0] + so[1], pts
+
+    def points_in_slabs(self, renderer: Renderer, slabs, lo=None, hi=None, invert: bool = False, world: bool = True):
+        """The points of the loaded resource in all of `slabs` (Slab objects in the stream's coordinates: slab_from_world makes them
+        from a world plane), or with invert=True the others, selected on the GPU (Context.select_slabs). world=True: lo / hi are
+        world coordinates of a clip box (None: the header's min / max) and the result is (xyz, pts) as points(world=True) returns
+        it. world=False: lo / hi are the stream's int32 coordinates (None: no clip), the result the int32 tensor alone."""
+        import torch
+        info = self.las_info()
+        if world:
+            clip = box_from_world(info, tuple(info.min) if lo is None else lo, tuple(info.max) if hi is None else hi)
+        else:
+            clip = None if lo is None and hi is None else as_box(((INT32_MIN,) * 3 if lo is None else lo, (INT32_MAX,) * 3 if hi is None else hi))
+        pts = renderer.ctx.select_slabs(slabs, clip, invert)
+        if not world:
+            return pts
+        so = torch.tensor([tuple(info.scale), tuple(info.offset)], dtype=torch.float64, device=pts.device)
+        return pts[:, :3].to(torch.float64) * so[0] + so[1], pts
+
+    def fit_planes(self, renderer: Renderer, distance: float, num_planes: int = 1, hypotheses: int = 256, seed: int = 0, lo=None, hi=None,
+                   min_support: int = 3):
+        """The dominant planes of the loaded resource by sequential RANSAC (fit_planes_rounds has the rounds): per round a few
+        batches are read back to draw `hypotheses` planes from, and one Context.plane_support call counts, for all of them at once
+        and straight from the compressed stream, the points within `distance` world units (radius_from_world + slab_tolerance)
+        that no plane found earlier holds. lo / hi: a clip box in world coordinates (None: the header's min / max). Returns
+        (slabs, supports, candidates): the planes as Slab objects in the stream's coordinates, their supports, and the number of
+        points each round had left. No refinement: a plane is the best hypothesis as drawn."""
+        info = self.las_info()
+        clip = box_from_world(info, tuple(info.min) if lo is None else lo, tuple(info.max) if hi is None else hi)
+        ctx = renderer.ctx
+
+        def read_batch(b):
+            pts = ctx.read_points(b, 1)
+            return np.stack([pts["x"], pts["y"], pts["z"]], axis=1)
+
+        return fit_planes_rounds(read_batch, lambda hyp, exclude: ctx.plane_support(hyp, clip, exclude), ctx.batches_resident,
+                                 radius_from_world(info, distance), num_planes, hypotheses, seed, min_support, clip)
 
     def points_on_screen(self, renderer: Renderer, params: Optional[RenderParams] = None, rect=None, world: bool = True):
         """The points of the loaded resource a frame of `params` (None: renderer.render_params()) draws inside `rect` (pixels,
