@@ -28,6 +28,15 @@ constexpr int64_t DECODE_STAGE_BATCHES = 64;     // batches per piece of pcr_rea
                                                  // (kept_write): 64 MiB of records on the device
 constexpr int64_t TRANSCODE_CHUNK = 128;        // batches per k_transcode launch when the lane-major words are scratch (40 MB)
 
+// Scratch of the batches a selection decodes twice (counted, then written), grown on demand (scratch_reserve)
+template <class Entry> struct BatchScratch {
+    int64_t capacity = 0;                       // batches the four arrays below hold
+    Entry *list = nullptr;                      // [capacity] the batches, ascending
+    uint32_t *counts = nullptr;                 // [capacity * 1024] selected points per chain (the count kernel)
+    uint32_t *totals = nullptr;                 // [capacity] ... and per batch
+    int64_t *offsets = nullptr;                 // [capacity] first output record of each (the write kernel)
+};
+
 struct pcr_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -131,11 +140,7 @@ struct pcr_ctx {
     std::vector<int32_t> h_point_bounds;        // [hdr.num_batches * 6]
     std::vector<uint8_t> h_point_bounds_ok;     // [hdr.num_batches]
     int32_t *d_point_bounds = nullptr;          // [hdr.num_batches * 6]
-    int64_t sel_capacity = 0;                   // straddling batches the four arrays below hold
-    uint32_t *d_sel_list = nullptr;             // [sel_capacity] their batch indices
-    uint32_t *d_sel_counts = nullptr;           // [sel_capacity * 1024] selected points per chain (k_select_count)
-    uint32_t *d_sel_totals = nullptr;           // [sel_capacity] ... and per batch
-    int64_t *d_sel_offsets = nullptr;           // [sel_capacity] first output record of each (k_select_write)
+    BatchScratch<uint32_t> sel;                 // the straddling batches by their indices
     // polygon selection (pcr_select_polygon): the straddling batches of a call with their slices of the edge array, and the array
     // (the per-chain counts, totals and offsets are the box selection's four arrays above)
     int64_t poly_capacity = 0;                  // entries d_poly_batches holds
@@ -160,11 +165,7 @@ struct pcr_ctx {
     // screen selection and picking (pcr_select_screen / pcr_pick): the cull/LOD words of the call's camera in an array of their own
     // (k_screen_lod; the frame's d_lod, lists and plans are not touched), and the scratch of the kept batches
     uint32_t *d_screen_lod = nullptr;           // [hdr.num_batches]
-    int64_t scr_capacity = 0;                   // kept batches the four arrays below hold
-    ScreenEntry *d_scr_list = nullptr;          // [scr_capacity] batch and LOD word
-    uint32_t *d_scr_counts = nullptr;           // [scr_capacity * 1024] selected points per chain (k_screen_count)
-    uint32_t *d_scr_totals = nullptr;           // [scr_capacity] ... and per batch
-    int64_t *d_scr_offsets = nullptr;           // [scr_capacity] first output record of each (k_screen_write)
+    BatchScratch<ScreenEntry> scr;              // the kept batches: batch and LOD word
     unsigned long long *d_pick = nullptr;       // [PICK_WORDS] pcr_pick: key, index, record, hit
     // visible selection (pcr_select_visible): the per-pixel planes of the image and the per-batch totals; list, per-chain counts
     // and offsets are the screen selection's arrays above
@@ -173,8 +174,8 @@ struct pcr_ctx {
     unsigned long long *d_vis_index = nullptr;  // [vis_pixels] FRONT: min record index among the hits that hold the key (k_visible_index)
     uint32_t *d_vis_row = nullptr;              // [vis_pixels] the row pass of k_visible_dilate
     uint32_t *d_vis_depth = nullptr;            // [vis_pixels] the dilated depth plane Dr
-    int64_t vis_capacity = 0;                   // kept batches d_vis_totals holds
-    uint32_t *d_vis_totals = nullptr;           // [vis_capacity * 3] per batch: hits in the image, then (selected, candidates) pairs
+    int64_t vis_capacity = 0;                   // words d_vis_totals holds
+    uint32_t *d_vis_totals = nullptr;           // [3 per kept batch] per batch: hits in the image, then (selected, candidates) pairs
     // top-down grid (pcr_grid_accumulate / pcr_read_grid): the list of a call's batches with their windows, and pcr_read_grid's planes
     int64_t grid_capacity = 0;                  // entries d_grid_list holds
     GridEntry *d_grid_list = nullptr;           // [grid_capacity] the windowed batches of a call, then the direct ones
@@ -316,6 +317,7 @@ int set_err(pcr_ctx *c, int code, const char *fmt, ...)
     } while (0)
 
 template <class T> void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
+template <class E> void dfree(BatchScratch<E> &b) { dfree(b.list); dfree(b.counts); dfree(b.totals); dfree(b.offsets); b.capacity = 0; }
 
 // Async loader: retire the tasks whose event has fired (or, with wait, all of them).
 void poll_loader(pcr_ctx *c, bool wait)
@@ -342,12 +344,12 @@ void free_stream_buffers(pcr_ctx *c)
     dfree(c->d_lane_words); dfree(c->d_batch_flags); dfree(c->d_packed_table); dfree(c->d_point_windows); dfree(c->d_batch_runs); c->transcoded = 0;
     dfree(c->d_order); dfree(c->d_chunk_count); dfree(c->d_any_generic); c->order_stride = 0;
     dfree(c->d_point_bounds); c->h_point_bounds.clear(); c->h_point_bounds_ok.clear();
-    dfree(c->d_sel_list); dfree(c->d_sel_counts); dfree(c->d_sel_totals); dfree(c->d_sel_offsets); c->sel_capacity = 0;
+    dfree(c->sel);
     dfree(c->d_poly_batches); c->poly_capacity = 0; dfree(c->d_poly_edges); c->poly_edge_capacity = 0;
     dfree(c->d_slab_batches); c->slab_capacity = 0; dfree(c->d_slab_entries); c->slab_entry_capacity = 0;
     dfree(c->d_plane_batches); c->plane_capacity = 0; dfree(c->d_plane_candidates); c->plane_cand_capacity = 0; dfree(c->d_plane_entries); c->plane_entry_capacity = 0;
     dfree(c->d_plane_counts);
-    dfree(c->d_screen_lod); dfree(c->d_scr_list); dfree(c->d_scr_counts); dfree(c->d_scr_totals); dfree(c->d_scr_offsets); c->scr_capacity = 0;
+    dfree(c->d_screen_lod); dfree(c->scr);
     dfree(c->d_pick);
     dfree(c->d_vis_key); dfree(c->d_vis_index); dfree(c->d_vis_row); dfree(c->d_vis_depth); dfree(c->d_vis_totals); c->vis_pixels = 0; c->vis_capacity = 0;
     dfree(c->d_grid_list); c->grid_capacity = 0; c->h_grid_list.clear();
@@ -1583,10 +1585,92 @@ int pcr_read_rgba(pcr_ctx *c, uint32_t *host, size_t n)
     return PCR_OK;
 }
 
-// ---- decode ------------------------------------------------------------------------------------
-// Range check shared by pcr_decode_points / pcr_read_points: [first, first + count) inside the batches the next frame would
-// draw; count < 0 = up to the last of them. Returns the count through *n.
-static int decode_range(pcr_ctx *c, int64_t first, int64_t count, const void *dst, size_t capacity, int64_t *n)
+// ---- shared by the decode, selection and kept-rows calls -----------------------------------------
+extern "C++" {                          // (templates among them)
+namespace {
+// A stream that holds both layouts follows pcr_set_render_variant (AUTO: point windows); either decodes to the same points.
+bool select_reads_windows(const pcr_ctx *c)
+{
+    const bool have_windows = c->layout != PCR_LAYOUT_WORDS, have_words = c->layout != PCR_LAYOUT_POINT_WINDOWS;
+    return have_windows && (c->variant != PCR_VARIANT_WORDS || !have_words);
+}
+
+// launch(layout) with the layout the calls read as a std::integral_constant: the template argument of a kernel that decodes
+// positions only
+template <class Launch>
+void for_layout(const pcr_ctx *c, Launch launch)
+{
+    if (select_reads_windows(c)) launch(std::integral_constant<int, LAYOUT_POINT_WINDOWS>{});
+    else                         launch(std::integral_constant<int, LAYOUT_WORDS>{});
+}
+
+// launch(layout, bc7) with the stream's colour format as well: the template arguments of a kernel that decodes with colour
+template <class Launch>
+void for_layout_bc7(const pcr_ctx *c, Launch launch)
+{
+    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
+    for_layout(c, [&](auto layout) { if (bc7) launch(layout, std::true_type{}); else launch(layout, std::false_type{}); });
+}
+
+// launch(layout, colour) for the kernels that can leave the colour out: SEL_NO_COLOUR unless `coloured`, else the stream's format
+template <class Launch>
+void for_layout_colour(const pcr_ctx *c, bool coloured, Launch launch)
+{
+    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
+    for_layout(c, [&](auto layout) {
+        if (!coloured) launch(layout, std::integral_constant<int, SEL_NO_COLOUR>{});
+        else if (bc7)  launch(layout, std::integral_constant<int, SEL_BC7>{});
+        else           launch(layout, std::integral_constant<int, SEL_BC1>{});
+    });
+}
+
+// Let each of `kernels` launch with `bytes` of dynamic LDS (the callers do it once per context)
+template <class... Kernels>
+int lds_allow(pcr_ctx *c, size_t bytes, Kernels... kernels)
+{
+    for (const void *k : {reinterpret_cast<const void *>(kernels)...}) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return set_err(c, PCR_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
+    }
+    return PCR_OK;
+}
+
+// *p holds at least `want` elements on return (a larger array replaces it, its content is not kept), or false
+bool thin_grow(void **p, int64_t &have, int64_t want, size_t elem_bytes)
+{
+    if (*p && have >= want) return true;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; have = 0;
+    if (hipMalloc(p, (size_t)want * elem_bytes) != hipSuccess) { *p = nullptr; return false; }
+    have = want;
+    return true;
+}
+
+// thin_grow for the scratch of the selections, with the refusal
+template <class T>
+int reserve(pcr_ctx *c, T *&p, int64_t &capacity, int64_t need, const char *what)
+{
+    if (thin_grow((void **)&p, capacity, need, sizeof(T))) return PCR_OK;
+    return set_err(c, PCR_E_NOMEM, "out of device memory for %lld %s", (long long)need, what);
+}
+
+// Room for the list, counts, totals and offsets of `need` batches
+template <class Entry>
+int scratch_reserve(pcr_ctx *c, BatchScratch<Entry> &b, int64_t need, const char *what)
+{
+    if (b.capacity >= need) return PCR_OK;
+    int64_t list = 0, totals = 0, offsets = 0, counts = 0;          // (nothing is kept: every array is replaced)
+    b.capacity = 0;
+    int rc;
+    if ((rc = reserve(c, b.list, list, need, what)) || (rc = reserve(c, b.totals, totals, need, what)) || (rc = reserve(c, b.offsets, offsets, need, what)) ||
+        (rc = reserve(c, b.counts, counts, need * PCR_WORKGROUP_SIZE, what))) return rc;
+    b.capacity = need;
+    return PCR_OK;
+}
+
+// Range check of the calls over batches: [first, first + count) inside the batches the next frame would draw; count < 0 = up to
+// the last of them. Returns the count through *n.
+int select_range(pcr_ctx *c, int64_t first, int64_t count, int64_t *n)
 {
     if (!c->stream_open) return set_err(c, PCR_E_ARG, "no stream loaded (call pcr_stream_begin / pcr_upload_batch)");
     if (c->async_upload) poll_loader(c, false);
@@ -1596,11 +1680,130 @@ static int decode_range(pcr_ctx *c, int64_t first, int64_t count, const void *ds
     if (count > nB - first)
         return set_err(c, PCR_E_ARG, "batches [%lld, %lld) reach past the %lld resident batches", (long long)first, (long long)(first + count), (long long)nB);
     *n = count;
-    if (count == 0) return PCR_OK;
+    return PCR_OK;
+}
+
+// What a call writes per row: the record to `points` and up to three columns, `name` as the messages call them, aligned to
+// dev_align bytes on the device and host_align on the host. Any destination may be NULL, each holds `capacity` rows. host: the
+// destinations are host memory (the pcr_read_ form).
+struct KeptColumn { const char *name; void *dst; size_t row_bytes; size_t dev_align = 8, host_align = alignof(int64_t); };
+struct KeptOut {
+    bool host;
+    void *points;
+    size_t capacity;
+    KeptColumn col[3];
+};
+// (the columns of the selections)
+KeptColumn heights_column(void *dst) { return KeptColumn{"heights", dst, 4, 4, alignof(int32_t)}; }
+KeptColumn hits_column(void *dst) { return KeptColumn{"hits", dst, sizeof(pcr_screen_hit), 16, alignof(pcr_screen_hit)}; }
+
+// The checks every call starts with: the range into *n, the lattice where the call has one (has_lattice), out_count and the
+// alignment of the destinations: 16 bytes for the points on the device, the type's own on the host. *out_count is 0 from here on.
+int kept_begin(pcr_ctx *c, int64_t first, int64_t count, const KeptOut &o, int64_t *out_count, int64_t *n, bool has_lattice = false,
+               const pcr_voxels *vox = nullptr)
+{
+    if (out_count) *out_count = 0;
+    int rc = select_range(c, first, count, n);
+    if (rc) return rc;
+    if (has_lattice && !vox) return set_err(c, PCR_E_ARG, "the voxel lattice is NULL");
+    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
+    const size_t points_align = o.host ? alignof(pcr_point) : 16;
+    if (o.points && reinterpret_cast<uintptr_t>(o.points) % points_align != 0)
+        return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
+    for (const KeptColumn &k : o.col)
+        if (k.dst && reinterpret_cast<uintptr_t>(k.dst) % (o.host ? k.host_align : k.dev_align) != 0)
+            return set_err(c, PCR_E_ARG, "the destination of the %s is misaligned (%zu bytes)", k.name, o.host ? k.host_align : k.dev_align);
+    if (vox && (vox->cell < 1 || vox->cell > PCR_THIN_MAX_CELL))
+        return set_err(c, PCR_E_ARG, "voxel cell of %d: the edge length is 1 .. %d (PCR_THIN_MAX_CELL)", vox->cell, PCR_THIN_MAX_CELL);
+    return PCR_OK;
+}
+
+// After the plan: the count and the statistics out; *done unless something is left to write, which is not so for a count-only
+// call, without rows, or where `kept` rows (`noun` in the message) do not fit the capacity
+template <class Stats>
+int kept_finish(pcr_ctx *c, const KeptOut &o, int64_t kept, const char *noun, const Stats &st, int64_t *out_count, Stats *stats, bool *done)
+{
+    *done = true;
+    *out_count = kept;
+    if (stats) *stats = st;
+    if ((!o.points && !o.col[0].dst && !o.col[1].dst && !o.col[2].dst) || kept == 0) return PCR_OK;
+    if (o.capacity < (size_t)kept) return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld %s", o.capacity, (long long)kept, noun);
+    *done = false;
+    return PCR_OK;
+}
+
+// The device twin of a host description for `batches` batches of 65 536 rows: the points through d_decode_stage, column i through
+// d_col_stage[i], NULL where the host takes none. The name of the buffer there is no memory for, or NULL.
+const char *stage_reserve(pcr_ctx *c, const KeptOut &o, int64_t batches, KeptOut &d)
+{
+    d = o;
+    d.host = false;
+    if (o.points) {
+        if (!thin_grow((void **)&c->d_decode_stage, c->decode_stage_batches, batches, (size_t)PCR_POINTS_PER_BATCH * sizeof(pcr_point))) return "points";
+        d.points = c->d_decode_stage;
+    }
+    for (int i = 0; i < 3; ++i) {
+        if (!o.col[i].dst) continue;
+        if (!thin_grow(&c->d_col_stage[i], c->col_stage_bytes[i], batches * PCR_POINTS_PER_BATCH * (int64_t)o.col[i].row_bytes, 1)) return o.col[i].name;
+        d.col[i].dst = c->d_col_stage[i];
+    }
+    return nullptr;
+}
+
+// The first m rows of the stages d to rows [at, at + m) of the host destinations o. Synchronises.
+int stage_copy(pcr_ctx *c, const KeptOut &o, const KeptOut &d, int64_t at, int64_t m)
+{
+    if (d.points) HIP_TRY(c, hipMemcpyAsync(static_cast<pcr_point *>(o.points) + at, d.points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
+    for (int i = 0; i < 3; ++i) {
+        const size_t row_bytes = o.col[i].row_bytes;
+        if (d.col[i].dst)
+            HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(o.col[i].dst) + (size_t)at * row_bytes, d.col[i].dst, (size_t)m * row_bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PCR_OK;
+}
+
+// A plan's rows to the destinations. The plan has n units (the batches of its range, or the batches it lists); rows(i0, i1) is the
+// number of rows of units [i0, i1), asked for ascending pieces; emit(i0, i1, d) enqueues their writes to the device destinations
+// d, each holding those rows. On the device one emit into o itself; to the host in pieces through the stages. stage_named: a
+// stage that does not fit is reported by name. Synchronises.
+template <class Rows, class Emit>
+int kept_write(pcr_ctx *c, int64_t n, const KeptOut &o, Rows rows, Emit emit, bool stage_named = false)
+{
+    int rc;
+    if (!o.host) {
+        if ((rc = emit(0, n, o))) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return PCR_OK;
+    }
+    // pieces of at most DECODE_STAGE_BATCHES batches: a batch writes at most 65 536 rows, so a piece fits the stages
+    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
+    KeptOut d;
+    if (const char *what = stage_reserve(c, o, piece, d))
+        return stage_named ? set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of %s", (long long)piece, what)
+                           : set_err(c, PCR_E_NOMEM, "out of device memory for the staging buffers of %lld batches", (long long)piece);
+    int64_t written = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += piece) {
+        const int64_t i1 = std::min(n, i0 + piece), m = rows(i0, i1);
+        if (m == 0) continue;
+        if ((rc = emit(i0, i1, d)) || (rc = stage_copy(c, o, d, written, m))) return rc;
+        written += m;
+    }
+    return PCR_OK;
+}
+} // namespace
+} // extern "C++"
+
+// ---- decode ------------------------------------------------------------------------------------
+// Range check shared by pcr_decode_points / pcr_read_points: select_range, and a destination that holds every record of the range.
+static int decode_range(pcr_ctx *c, int64_t first, int64_t count, const void *dst, size_t capacity, int64_t *n)
+{
+    const int rc = select_range(c, first, count, n);
+    if (rc || *n == 0) return rc;
     if (!dst) return set_err(c, PCR_E_ARG, "the destination is NULL");
     if (reinterpret_cast<uintptr_t>(dst) % alignof(pcr_point) != 0) return set_err(c, PCR_E_ARG, "the destination is misaligned");
-    if (capacity < (size_t)count * PCR_POINTS_PER_BATCH)
-        return set_err(c, PCR_E_ARG, "capacity of %zu points is below the %lld x %d of the range", capacity, (long long)count, PCR_POINTS_PER_BATCH);
+    if (capacity < (size_t)*n * PCR_POINTS_PER_BATCH)
+        return set_err(c, PCR_E_ARG, "capacity of %zu points is below the %lld x %d of the range", capacity, (long long)*n, PCR_POINTS_PER_BATCH);
     return PCR_OK;
 }
 
@@ -1610,24 +1813,15 @@ static int launch_decode(pcr_ctx *c, int64_t first, int64_t count, void *dev_poi
     // (as a frame: the provisional last batch of a stream that is still loading is walked here if no frame has done so)
     if (!c->async_upload && (rc = enqueue_transcode(c, true, c->stream))) return rc;
     if (!c->decode_lds_ready) {
-        hipError_t e = hipSuccess;
-#define PCR_ALLOW(L, B) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode_points<L, B>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEC_LDS_BYTES)
-        PCR_ALLOW(LAYOUT_WORDS, false); PCR_ALLOW(LAYOUT_WORDS, true); PCR_ALLOW(LAYOUT_POINT_WINDOWS, false); PCR_ALLOW(LAYOUT_POINT_WINDOWS, true);
-#undef PCR_ALLOW
-        if (e != hipSuccess) return set_err(c, PCR_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
+        if ((rc = lds_allow(c, DEC_LDS_BYTES, &k_decode_points<LAYOUT_WORDS, false>, &k_decode_points<LAYOUT_WORDS, true>,
+                            &k_decode_points<LAYOUT_POINT_WINDOWS, false>, &k_decode_points<LAYOUT_POINT_WINDOWS, true>))) return rc;
         c->decode_lds_ready = true;
     }
-    // either layout decodes to the same points; a stream that holds both follows pcr_set_render_variant (AUTO: point windows)
-    const bool have_windows = c->layout != PCR_LAYOUT_WORDS, have_words = c->layout != PCR_LAYOUT_POINT_WINDOWS;
-    const bool windows = have_windows && (c->variant != PCR_VARIANT_WORDS || !have_words);
-    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
     const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)count), block(PCR_WORKGROUP_SIZE);
-    uint4 *out = static_cast<uint4 *>(dev_points);
-#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_decode_points<L, B>), grid, block, DEC_LDS_BYTES, c->stream, s, out, (uint32_t)first)
-    if (windows) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
-    else         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
-#undef PCR_LAUNCH
+    for_layout_bc7(c, [&](auto layout, auto bc7) {
+        hipLaunchKernelGGL((k_decode_points<layout.value, bc7.value>), dim3((unsigned)count), dim3(PCR_WORKGROUP_SIZE), DEC_LDS_BYTES, c->stream, s,
+                           static_cast<uint4 *>(dev_points), (uint32_t)first);
+    });
     HIP_TRY(c, hipGetLastError());
     return PCR_OK;
 }
@@ -1669,27 +1863,6 @@ int pcr_read_points(pcr_ctx *c, int64_t first_batch, int64_t count, pcr_point *h
 }
 
 // ---- box selection -----------------------------------------------------------------------------
-// (as launch_decode: a stream that holds both layouts follows pcr_set_render_variant, AUTO: point windows)
-static bool select_reads_windows(const pcr_ctx *c)
-{
-    const bool have_windows = c->layout != PCR_LAYOUT_WORDS, have_words = c->layout != PCR_LAYOUT_POINT_WINDOWS;
-    return have_windows && (c->variant != PCR_VARIANT_WORDS || !have_words);
-}
-
-// Range check shared by the three entry points: decode_range's without the destination (it may be NULL here).
-static int select_range(pcr_ctx *c, int64_t first, int64_t count, int64_t *n)
-{
-    if (!c->stream_open) return set_err(c, PCR_E_ARG, "no stream loaded (call pcr_stream_begin / pcr_upload_batch)");
-    if (c->async_upload) poll_loader(c, false);
-    const int64_t nB = c->visible_batches();
-    if (first < 0 || first > nB) return set_err(c, PCR_E_ARG, "first batch %lld outside the %lld resident batches", (long long)first, (long long)nB);
-    if (count < 0) count = nB - first;
-    if (count > nB - first)
-        return set_err(c, PCR_E_ARG, "batches [%lld, %lld) reach past the %lld resident batches", (long long)first, (long long)(first + count), (long long)nB);
-    *n = count;
-    return PCR_OK;
-}
-
 // c->h_point_bounds holds the exact boxes of batches [first, first + n) on return: one k_point_bounds launch over the span of the
 // batches not cached yet, read back. Synchronises if it launches.
 static int ensure_point_bounds(pcr_ctx *c, int64_t first, int64_t n)
@@ -1705,9 +1878,9 @@ static int ensure_point_bounds(pcr_ctx *c, int64_t first, int64_t n)
     if (lo < 0) return PCR_OK;
     if (!c->d_point_bounds) HIP_TRY(c, hipMalloc((void **)&c->d_point_bounds, nB * 6 * sizeof(int32_t)));
     const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)(hi - lo)), block(PCR_WORKGROUP_SIZE);
-    if (select_reads_windows(c)) hipLaunchKernelGGL((k_point_bounds<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_point_bounds, (uint32_t)lo);
-    else                         hipLaunchKernelGGL((k_point_bounds<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_point_bounds, (uint32_t)lo);
+    for_layout(c, [&](auto layout) {
+        hipLaunchKernelGGL((k_point_bounds<layout.value>), dim3((unsigned)(hi - lo)), dim3(PCR_WORKGROUP_SIZE), 0, c->stream, s, c->d_point_bounds, (uint32_t)lo);
+    });
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(c->h_point_bounds.data() + lo * 6, c->d_point_bounds + lo * 6, (size_t)(hi - lo) * 6 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1728,76 +1901,70 @@ int pcr_batch_point_bounds(pcr_ctx *c, int64_t first_batch, int64_t count, int32
     return PCR_OK;
 }
 
+// ---- the host path of the selection calls --------------------------------------------------------
+// Six predicates (box, polygon, slabs, height, screen, visible), each in a device form pcr_select_X and a host form pcr_read_X that
+// are one function X_call behind two descriptions of the outputs (KeptOut), on the kept-rows calls' begin, finish and write. Box,
+// polygon and slabs class the batches of a range by their exact boxes (select_plan, select_write); height, screen and visible list
+// the batches they decode (listed_write).
+extern "C++" {                          // (templates among them)
 namespace {
 enum : int8_t { SEL_OUTSIDE = 0, SEL_INSIDE = 1, SEL_STRADDLING = 2 };
+static_assert((int)POLY_OUTSIDE == SEL_OUTSIDE && (int)POLY_INSIDE == SEL_INSIDE && (int)POLY_STRADDLING == SEL_STRADDLING, "poly_plan_batch returns a SEL_ class");
+static_assert((int)SLABS_OUTSIDE == SEL_OUTSIDE && (int)SLABS_INSIDE == SEL_INSIDE && (int)SLABS_STRADDLING == SEL_STRADDLING, "slabs_plan_batch returns a SEL_ class");
 
 // What a selection over batches [first, first + n) has to write: the class of every batch, its record count, and for the
-// straddling ones (slot = position among them; their per-chain counts sit in c->d_sel_counts) the batch index.
+// straddling ones (slot = position among them; their per-chain counts sit in c->sel.counts) the batch index.
 struct SelectPlan {
     std::vector<int8_t> cls;
     std::vector<int64_t> cnt;
     std::vector<uint32_t> strad;        // batch indices of the straddling batches, ascending
-    std::vector<int64_t> offsets;       // staging of k_select_write's offsets (alive until the stream has been synchronised)
-    pcr_select_stats st{};
+    std::vector<int64_t> offsets;       // staging of the write kernel's offsets (alive until the stream has been synchronised)
 };
 
-bool box_empty(const pcr_box &q) { return q.min[0] > q.max[0] || q.min[1] > q.max[1] || q.min[2] > q.max[2]; }
-
-// Room for the list, counts, totals and offsets of nS straddling batches.
-int select_reserve(pcr_ctx *c, int64_t nS)
+// rows(i0, i1) of kept_write for a plan that holds the rows of every unit
+auto rows_of(const std::vector<int64_t> &cnt)
 {
-    if (c->sel_capacity >= nS) return PCR_OK;
-    dfree(c->d_sel_list); dfree(c->d_sel_counts); dfree(c->d_sel_totals); dfree(c->d_sel_offsets); c->sel_capacity = 0;
-    if (hipMalloc((void **)&c->d_sel_list, (size_t)nS * 4) != hipSuccess || hipMalloc((void **)&c->d_sel_totals, (size_t)nS * 4) != hipSuccess ||
-        hipMalloc((void **)&c->d_sel_offsets, (size_t)nS * 8) != hipSuccess ||
-        hipMalloc((void **)&c->d_sel_counts, (size_t)nS * PCR_WORKGROUP_SIZE * 4) != hipSuccess)
-        return set_err(c, PCR_E_NOMEM, "out of device memory for the counts of %lld straddling batches", (long long)nS);
-    c->sel_capacity = nS;
-    return PCR_OK;
+    return [&cnt](int64_t i0, int64_t i1) { int64_t m = 0; for (int64_t i = i0; i < i1; ++i) m += cnt[(size_t)i]; return m; };
 }
 
-// Classify (host, from the cached exact boxes) and count the straddling batches (k_select_count). Synchronises.
-int select_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_box &q, SelectPlan &p)
+// The plan of a box-classified selection: classify(b, bb) classes batch b from its exact box bb (host) and notes what the
+// predicate keeps per straddling batch; count(nS) uploads that and enqueues the predicate's count kernel over the nS straddling
+// batches into c->sel.counts / c->sel.totals. st: the call's statistics, whose first four fields are pcr_select_stats'.
+// nothing: the predicate selects no point at all. Synchronises.
+template <class Stats, class Classify, class Count>
+int select_plan(pcr_ctx *c, int64_t first, int64_t n, bool nothing, SelectPlan &p, Stats &st, Classify classify, Count count)
 {
     p.cls.assign((size_t)n, SEL_OUTSIDE); p.cnt.assign((size_t)n, 0); p.strad.clear();
-    p.st = pcr_select_stats{n, 0, 0, 0};
-    if (n == 0 || box_empty(q)) return PCR_OK;
+    st = Stats{};
+    st.batches_outside = n;
+    if (n == 0 || nothing) return PCR_OK;
     int rc;
     if ((rc = ensure_point_bounds(c, first, n))) return rc;
     for (int64_t i = 0; i < n; ++i) {
-        const int32_t *bb = c->h_point_bounds.data() + (first + i) * 6;
-        bool disjoint = false, within = true;
-        for (int k = 0; k < 3; ++k) {
-            disjoint = disjoint || bb[3 + k] < q.min[k] || bb[k] > q.max[k];
-            within = within && bb[k] >= q.min[k] && bb[3 + k] <= q.max[k];
-        }
-        if (disjoint) continue;
-        --p.st.batches_outside;
-        if (within) { p.cls[(size_t)i] = SEL_INSIDE; p.cnt[(size_t)i] = PCR_POINTS_PER_BATCH; ++p.st.batches_inside; }
-        else { p.cls[(size_t)i] = SEL_STRADDLING; p.strad.push_back((uint32_t)(first + i)); ++p.st.batches_straddling; }
+        const int cls = classify((uint32_t)(first + i), c->h_point_bounds.data() + (first + i) * 6);
+        if (cls == SEL_OUTSIDE) continue;
+        --st.batches_outside;
+        p.cls[(size_t)i] = (int8_t)cls;
+        if (cls == SEL_INSIDE) { p.cnt[(size_t)i] = PCR_POINTS_PER_BATCH; ++st.batches_inside; }
+        else { p.strad.push_back((uint32_t)(first + i)); ++st.batches_straddling; }
     }
     const int64_t nS = (int64_t)p.strad.size();
     if (nS) {
-        if ((rc = select_reserve(c, nS))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(c->d_sel_list, p.strad.data(), (size_t)nS * 4, hipMemcpyHostToDevice, c->stream));
-        const StreamView s = make_stream_view(c);
-        const dim3 grid((unsigned)nS), block(PCR_WORKGROUP_SIZE);
-        if (select_reads_windows(c)) hipLaunchKernelGGL((k_select_count<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_sel_list, q, c->d_sel_counts, c->d_sel_totals);
-        else                         hipLaunchKernelGGL((k_select_count<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_sel_list, q, c->d_sel_counts, c->d_sel_totals);
+        if ((rc = scratch_reserve(c, c->sel, nS, "straddling batches (their counts)")) || (rc = count(nS))) return rc;
         HIP_TRY(c, hipGetLastError());
         std::vector<uint32_t> totals((size_t)nS);
-        HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_sel_totals, (size_t)nS * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(totals.data(), c->sel.totals, (size_t)nS * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         for (int64_t k = 0; k < nS; ++k) p.cnt[(size_t)(p.strad[(size_t)k] - first)] = totals[(size_t)k];
     }
-    for (int64_t i = 0; i < n; ++i) p.st.points_selected += p.cnt[(size_t)i];
+    for (int64_t i = 0; i < n; ++i) st.points_selected += p.cnt[(size_t)i];
     return PCR_OK;
 }
 
 // Enqueue the writes of batches [i0, i1) of the plan's range to `out` (device, holds their records): runs of inside batches
-// through k_decode_points, the straddling ones through one launch of write(s0, nS, out): the kernel that writes the straddling
-// batches [s0, s0 + nS) of the plan from d_sel_offsets + s0. The caller synchronises.
-extern "C++" template <class Write>
+// through k_decode_points, the straddling ones through one launch of write(s0, grid, out): the kernel that writes the straddling
+// batches [s0, s0 + grid.x) of the plan from c->sel.offsets + s0. The caller synchronises.
+template <class Write>
 int select_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, SelectPlan &p, uint4 *out, Write &&write)
 {
     int rc;
@@ -1818,281 +1985,187 @@ int select_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, SelectPlan &p
     }
     const size_t nS = p.offsets.size();
     if (nS) {
-        HIP_TRY(c, hipMemcpyAsync(c->d_sel_offsets + s0, p.offsets.data(), nS * 8, hipMemcpyHostToDevice, c->stream));
-        write(s0, nS, out);
+        HIP_TRY(c, hipMemcpyAsync(c->sel.offsets + s0, p.offsets.data(), nS * 8, hipMemcpyHostToDevice, c->stream));
+        write(s0, dim3((unsigned)nS), out);
         HIP_TRY(c, hipGetLastError());
     }
     return PCR_OK;
 }
 
-// k_select_write over the straddling batches [s0, s0 + nS) of a box selection's plan
-void box_write(pcr_ctx *c, const pcr_box &q, size_t s0, size_t nS, uint4 *out)
+// kept_write for a box-classified plan: the selected records to o.points (the range in pieces of whole batches on the host form)
+template <class Write>
+int select_write(pcr_ctx *c, int64_t first, int64_t n, SelectPlan &p, const KeptOut &o, Write write)
 {
-    const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)nS), block(PCR_WORKGROUP_SIZE);
-    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
-#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_select_write<L, B>), grid, block, 0, c->stream, s, c->d_sel_list + s0, q, \
-                                            c->d_sel_counts + s0 * PCR_WORKGROUP_SIZE, c->d_sel_offsets + s0, out)
-    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
-    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
-#undef PCR_LAUNCH
+    return kept_write(c, n, o, rows_of(p.cnt), [&](int64_t i0, int64_t i1, const KeptOut &d) {
+        return select_emit(c, first, i0, i1, p, static_cast<uint4 *>(d.points), write);
+    }, true);
 }
 
-// The selected records of the plan's n batches into host memory, through the context's decode staging buffer in pieces of at
-// most DECODE_STAGE_BATCHES batches: a batch selects at most 65 536 records, so a piece fits the buffer. Synchronises.
-extern "C++" template <class Write>
-int select_read(pcr_ctx *c, int64_t first, int64_t n, SelectPlan &p, pcr_point *host, Write &&write)
+// kept_write for a plan that lists the batches it decodes, cnt[k] records from the k-th: launch(k0, grid, d) starts the call's
+// write kernel over the listed batches [k0, k0 + grid.x), which finds the first output record of each at d_offsets + k0
+template <class Launch>
+int listed_write(pcr_ctx *c, const std::vector<int64_t> &cnt, std::vector<int64_t> &offsets, int64_t *d_offsets, const KeptOut &o, Launch launch)
 {
-    int rc;
-    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
-    if (!c->d_decode_stage || c->decode_stage_batches < piece) {
-        dfree(c->d_decode_stage); c->decode_stage_batches = 0;
-        if (hipMalloc((void **)&c->d_decode_stage, (size_t)piece * PCR_POINTS_PER_BATCH * sizeof(pcr_point)) != hipSuccess)
-            return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of points", (long long)piece);
-        c->decode_stage_batches = piece;
-    }
-    int64_t written = 0;
-    for (int64_t i0 = 0; i0 < n; i0 += piece) {
-        const int64_t i1 = std::min(n, i0 + piece);
-        int64_t m = 0;
-        for (int64_t i = i0; i < i1; ++i) m += p.cnt[(size_t)i];
-        if (m == 0) continue;
-        if ((rc = select_emit(c, first, i0, i1, p, reinterpret_cast<uint4 *>(c->d_decode_stage), write))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(host + written, c->d_decode_stage, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        written += m;
-    }
-    return PCR_OK;
+    return kept_write(c, (int64_t)cnt.size(), o, rows_of(cnt), [&](int64_t k0, int64_t k1, const KeptOut &d) {
+        offsets.clear();                                                        // (alive until the stream has been synchronised)
+        int64_t off = 0;
+        for (int64_t k = k0; k < k1; ++k) { offsets.push_back(off); off += cnt[(size_t)k]; }
+        if (off == 0) return (int)PCR_OK;
+        HIP_TRY(c, hipMemcpyAsync(d_offsets + k0, offsets.data(), (size_t)(k1 - k0) * 8, hipMemcpyHostToDevice, c->stream));
+        launch(k0, dim3((unsigned)(k1 - k0)), d);
+        HIP_TRY(c, hipGetLastError());
+        return (int)PCR_OK;
+    }, true);
 }
 
-// The checks and the plan shared by pcr_select_box / pcr_read_box. *done: nothing left to write (an error, a count-only call,
-// no records).
-int select_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_box *box, const void *dst, size_t dst_align, size_t capacity,
-                   int64_t *out_count, pcr_select_stats *stats, int64_t *n, SelectPlan &p, bool *done)
-{
-    *done = true;
-    if (out_count) *out_count = 0;
-    int rc = select_range(c, first, count, n);
-    if (rc) return rc;
-    if (!box) return set_err(c, PCR_E_ARG, "the box is NULL");
-    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
-    if (dst && reinterpret_cast<uintptr_t>(dst) % dst_align != 0) return set_err(c, PCR_E_ARG, "the destination is misaligned (%zu bytes)", dst_align);
-    if ((rc = select_plan(c, first, *n, *box, p))) return rc;
-    *out_count = p.st.points_selected;
-    if (stats) *stats = p.st;
-    if (!dst || p.st.points_selected == 0) return PCR_OK;
-    if (capacity < (size_t)p.st.points_selected)
-        return set_err(c, PCR_E_ARG, "capacity of %zu points is below the %lld selected", capacity, (long long)p.st.points_selected);
-    *done = false;
-    return PCR_OK;
-}
-} // namespace
+bool box_empty(const pcr_box &q) { return q.min[0] > q.max[0] || q.min[1] > q.max[1] || q.min[2] > q.max[2]; }
 
-int pcr_select_box(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_box *box, void *dev_points, size_t capacity_points,
-                   int64_t *out_count, pcr_select_stats *stats)
+// pcr_select_box / pcr_read_box
+int box_call(pcr_ctx *c, int64_t first, int64_t count, const pcr_box *box, const KeptOut &o, int64_t *out_count, pcr_select_stats *stats)
 {
     if (!c) return PCR_E_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     SelectPlan p;
+    pcr_select_stats st;
     int64_t n = 0;
     bool done = true;
-    int rc = select_prepare(c, first_batch, count, box, dev_points, 16, capacity_points, out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    if ((rc = select_emit(c, first_batch, 0, n, p, static_cast<uint4 *>(dev_points),
-                          [&](size_t s0, size_t nS, uint4 *out) { box_write(c, *box, s0, nS, out); }))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PCR_OK;
+    int rc = kept_begin(c, first, count, o, out_count, &n);
+    if (rc) return rc;
+    if (!box) return set_err(c, PCR_E_ARG, "the box is NULL");
+    const pcr_box q = *box;
+    const dim3 block(PCR_WORKGROUP_SIZE);
+    rc = select_plan(c, first, n, box_empty(q), p, st, [&](uint32_t, const int32_t *bb) {
+        bool disjoint = false, within = true;
+        for (int k = 0; k < 3; ++k) {
+            disjoint = disjoint || bb[3 + k] < q.min[k] || bb[k] > q.max[k];
+            within = within && bb[k] >= q.min[k] && bb[3 + k] <= q.max[k];
+        }
+        return disjoint ? SEL_OUTSIDE : within ? SEL_INSIDE : SEL_STRADDLING;
+    }, [&](int64_t nS) {
+        HIP_TRY(c, hipMemcpyAsync(c->sel.list, p.strad.data(), (size_t)nS * 4, hipMemcpyHostToDevice, c->stream));
+        for_layout(c, [&](auto layout) {
+            hipLaunchKernelGGL((k_select_count<layout.value>), dim3((unsigned)nS), block, 0, c->stream, make_stream_view(c), c->sel.list, q, c->sel.counts, c->sel.totals);
+        });
+        return (int)PCR_OK;
+    });
+    if (rc || (rc = kept_finish(c, o, st.points_selected, "selected", st, out_count, stats, &done)) || done) return rc;
+    return select_write(c, first, n, p, o, [&](size_t s0, dim3 grid, uint4 *out) {
+        for_layout_bc7(c, [&](auto layout, auto bc7) {
+            hipLaunchKernelGGL((k_select_write<layout.value, bc7.value>), grid, block, 0, c->stream, make_stream_view(c), c->sel.list + s0, q,
+                               c->sel.counts + s0 * PCR_WORKGROUP_SIZE, c->sel.offsets + s0, out);
+        });
+    });
+}
+} // namespace
+} // extern "C++"
+
+int pcr_select_box(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_box *box, void *dev_points, size_t capacity_points,
+                   int64_t *out_count, pcr_select_stats *stats)
+{
+    return box_call(c, first_batch, count, box, KeptOut{false, dev_points, capacity_points, {}}, out_count, stats);
 }
 
 int pcr_read_box(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_box *box, pcr_point *host, size_t capacity_points,
                  int64_t *out_count, pcr_select_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    SelectPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = select_prepare(c, first_batch, count, box, host, alignof(pcr_point), capacity_points, out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    return select_read(c, first_batch, n, p, host, [&](size_t s0, size_t nS, uint4 *out) { box_write(c, *box, s0, nS, out); });
+    return box_call(c, first_batch, count, box, KeptOut{true, host, capacity_points, {}}, out_count, stats);
 }
 
 // ---- polygon selection -------------------------------------------------------------------------
+extern "C++" {
 namespace {
 constexpr size_t POLY_MAX_LDS_BYTES = POLY_TABLE_BYTES + (size_t)PCR_POLY_MAX_VERTICES * sizeof(PolyEdge);
 
-// What a polygon selection adds to a SelectPlan: the checked polygon, the straddling batches with their slices, the edge array.
-struct PolygonPlan {
-    SelectPlan sel;
+// pcr_select_polygon / pcr_read_polygon: what the polygon adds to select_plan is the straddling batches with their slices of the
+// edge array (both alive until the stream has been synchronised)
+int polygon_call(pcr_ctx *c, int64_t first, int64_t count, const pcr_polygon *poly, const KeptOut &o, int64_t *out_count, pcr_polygon_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    SelectPlan p;
     PolyShape shape;
-    std::vector<PolyBatch> batches;     // the straddling batches, ascending (alive until the stream has been synchronised)
+    std::vector<PolyBatch> batches;
     std::vector<PolyEdge> edges;
     PolyArgs args{};
     size_t lds = 0;                     // dynamic LDS of the k_polygon_* launches
-    pcr_polygon_stats st{};
-};
-
-// Classify (host, pcr_polygon.h), upload the straddling batches' edge lists and count them (k_polygon_count). Synchronises.
-int polygon_plan(pcr_ctx *c, int64_t first, int64_t n, PolygonPlan &p)
-{
-    p.sel.cls.assign((size_t)n, SEL_OUTSIDE); p.sel.cnt.assign((size_t)n, 0); p.sel.strad.clear();
-    p.batches.clear(); p.edges.clear();
-    p.st = pcr_polygon_stats{n, 0, 0, 0, 0, 0};
-    if (n == 0 || p.shape.z_min > p.shape.z_max) return PCR_OK;
-    int rc;
-    if ((rc = ensure_point_bounds(c, first, n))) return rc;
-    for (int64_t i = 0; i < n; ++i) {
-        const size_t e0 = p.edges.size();
+    pcr_polygon_stats st;
+    int64_t n = 0;
+    bool done = true;
+    int rc = kept_begin(c, first, count, o, out_count, &n);
+    if (rc) return rc;
+    if (const char *why = poly_shape(poly, &shape)) return set_err(c, PCR_E_ARG, "%s", why);
+    const dim3 block(PCR_WORKGROUP_SIZE);
+    rc = select_plan(c, first, n, shape.z_min > shape.z_max, p, st, [&](uint32_t b, const int32_t *bb) {
+        const size_t e0 = edges.size();
         uint32_t base = 0;
-        const int cls = poly_plan_batch(p.shape, c->h_point_bounds.data() + (first + i) * 6, p.edges, &base);
-        if (cls == POLY_OUTSIDE) continue;
-        --p.st.batches_outside;
-        if (cls == POLY_INSIDE) { p.sel.cls[(size_t)i] = SEL_INSIDE; p.sel.cnt[(size_t)i] = PCR_POINTS_PER_BATCH; ++p.st.batches_inside; continue; }
-        const size_t ne = p.edges.size() - e0;
-        p.sel.cls[(size_t)i] = SEL_STRADDLING; p.sel.strad.push_back((uint32_t)(first + i)); ++p.st.batches_straddling;
-        p.batches.push_back(PolyBatch{(uint32_t)(first + i), (uint32_t)e0, (uint32_t)ne, base});
-        p.st.edges_listed += (int64_t)ne;
-        p.st.edges_max = std::max(p.st.edges_max, (int64_t)ne);
-    }
-    const int64_t nS = (int64_t)p.batches.size(), nE = (int64_t)p.edges.size();
-    if (nS) {
-        if ((rc = select_reserve(c, nS))) return rc;
-        if (c->poly_capacity < nS) {
-            dfree(c->d_poly_batches); c->poly_capacity = 0;
-            if (hipMalloc((void **)&c->d_poly_batches, (size_t)nS * sizeof(PolyBatch)) != hipSuccess)
-                return set_err(c, PCR_E_NOMEM, "out of device memory for a list of %lld straddling batches", (long long)nS);
-            c->poly_capacity = nS;
-        }
-        if (c->poly_edge_capacity < nE) {
-            dfree(c->d_poly_edges); c->poly_edge_capacity = 0;
-            if (hipMalloc((void **)&c->d_poly_edges, (size_t)nE * sizeof(PolyEdge)) != hipSuccess)
-                return set_err(c, PCR_E_NOMEM, "out of device memory for %lld polygon edges", (long long)nE);
-            c->poly_edge_capacity = nE;
-        }
+        const int cls = poly_plan_batch(shape, bb, edges, &base);
+        if (cls != POLY_STRADDLING) return cls;
+        const size_t ne = edges.size() - e0;
+        batches.push_back(PolyBatch{b, (uint32_t)e0, (uint32_t)ne, base});
+        st.edges_listed += (int64_t)ne;
+        st.edges_max = std::max(st.edges_max, (int64_t)ne);
+        return cls;
+    }, [&](int64_t nS) {
+        const int64_t nE = (int64_t)edges.size();
+        int rc;
+        if ((rc = reserve(c, c->d_poly_batches, c->poly_capacity, nS, "straddling batches")) ||
+            (rc = reserve(c, c->d_poly_edges, c->poly_edge_capacity, std::max<int64_t>(nE, 1), "polygon edges"))) return rc;
         if (!c->poly_lds_ready) {
-            hipError_t e = hipSuccess;
-#define PCR_ALLOW(K) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)POLY_MAX_LDS_BYTES)
-            PCR_ALLOW(k_polygon_count<LAYOUT_WORDS>); PCR_ALLOW(k_polygon_count<LAYOUT_POINT_WINDOWS>);
-            PCR_ALLOW((k_polygon_write<LAYOUT_WORDS, false>)); PCR_ALLOW((k_polygon_write<LAYOUT_WORDS, true>));
-            PCR_ALLOW((k_polygon_write<LAYOUT_POINT_WINDOWS, false>)); PCR_ALLOW((k_polygon_write<LAYOUT_POINT_WINDOWS, true>));
-#undef PCR_ALLOW
-            if (e != hipSuccess) return set_err(c, PCR_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
+            if ((rc = lds_allow(c, POLY_MAX_LDS_BYTES, &k_polygon_count<LAYOUT_WORDS>, &k_polygon_count<LAYOUT_POINT_WINDOWS>,
+                                &k_polygon_write<LAYOUT_WORDS, false>, &k_polygon_write<LAYOUT_WORDS, true>,
+                                &k_polygon_write<LAYOUT_POINT_WINDOWS, false>, &k_polygon_write<LAYOUT_POINT_WINDOWS, true>))) return rc;
             c->poly_lds_ready = true;
         }
-        HIP_TRY(c, hipMemcpyAsync(c->d_poly_batches, p.batches.data(), (size_t)nS * sizeof(PolyBatch), hipMemcpyHostToDevice, c->stream));
-        if (nE) HIP_TRY(c, hipMemcpyAsync(c->d_poly_edges, p.edges.data(), (size_t)nE * sizeof(PolyEdge), hipMemcpyHostToDevice, c->stream));
-        p.args = PolyArgs{p.shape.x0, p.shape.y0, p.shape.x1, p.shape.y1, p.shape.z_min, p.shape.z_max, p.shape.invert ? 1u : 0u,
-                          (uint32_t)p.st.edges_max, c->d_poly_batches, c->d_poly_edges};
-        p.lds = POLY_TABLE_BYTES + (size_t)p.st.edges_max * sizeof(PolyEdge);
-        const StreamView s = make_stream_view(c);
-        const dim3 grid((unsigned)nS), block(PCR_WORKGROUP_SIZE);
-        if (select_reads_windows(c)) hipLaunchKernelGGL((k_polygon_count<LAYOUT_POINT_WINDOWS>), grid, block, p.lds, c->stream, s, p.args, c->d_sel_counts, c->d_sel_totals);
-        else                         hipLaunchKernelGGL((k_polygon_count<LAYOUT_WORDS>), grid, block, p.lds, c->stream, s, p.args, c->d_sel_counts, c->d_sel_totals);
-        HIP_TRY(c, hipGetLastError());
-        std::vector<uint32_t> totals((size_t)nS);
-        HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_sel_totals, (size_t)nS * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (int64_t k = 0; k < nS; ++k) p.sel.cnt[(size_t)(p.batches[(size_t)k].b - first)] = totals[(size_t)k];
-    }
-    for (int64_t i = 0; i < n; ++i) p.st.points_selected += p.sel.cnt[(size_t)i];
-    return PCR_OK;
-}
-
-// k_polygon_write over the straddling batches [s0, s0 + nS) of the plan
-void polygon_write(pcr_ctx *c, const PolygonPlan &p, size_t s0, size_t nS, uint4 *out)
-{
-    const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)nS), block(PCR_WORKGROUP_SIZE);
-    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
-    PolyArgs a = p.args;
-    a.batches += s0;
-#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_polygon_write<L, B>), grid, block, p.lds, c->stream, s, a, c->d_sel_counts + s0 * PCR_WORKGROUP_SIZE, \
-                                            c->d_sel_offsets + s0, out)
-    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
-    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
-#undef PCR_LAUNCH
-}
-
-// The checks and the plan shared by pcr_select_polygon / pcr_read_polygon (select_prepare with the polygon's checks).
-int polygon_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_polygon *poly, const void *dst, size_t dst_align, size_t capacity,
-                    int64_t *out_count, pcr_polygon_stats *stats, int64_t *n, PolygonPlan &p, bool *done)
-{
-    *done = true;
-    if (out_count) *out_count = 0;
-    int rc = select_range(c, first, count, n);
-    if (rc) return rc;
-    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
-    if (const char *why = poly_shape(poly, &p.shape)) return set_err(c, PCR_E_ARG, "%s", why);
-    if (dst && reinterpret_cast<uintptr_t>(dst) % dst_align != 0) return set_err(c, PCR_E_ARG, "the destination is misaligned (%zu bytes)", dst_align);
-    if ((rc = polygon_plan(c, first, *n, p))) return rc;
-    *out_count = p.st.points_selected;
-    if (stats) *stats = p.st;
-    if (!dst || p.st.points_selected == 0) return PCR_OK;
-    if (capacity < (size_t)p.st.points_selected)
-        return set_err(c, PCR_E_ARG, "capacity of %zu points is below the %lld selected", capacity, (long long)p.st.points_selected);
-    *done = false;
-    return PCR_OK;
+        HIP_TRY(c, hipMemcpyAsync(c->d_poly_batches, batches.data(), (size_t)nS * sizeof(PolyBatch), hipMemcpyHostToDevice, c->stream));
+        if (nE) HIP_TRY(c, hipMemcpyAsync(c->d_poly_edges, edges.data(), (size_t)nE * sizeof(PolyEdge), hipMemcpyHostToDevice, c->stream));
+        args = PolyArgs{shape.x0, shape.y0, shape.x1, shape.y1, shape.z_min, shape.z_max, shape.invert ? 1u : 0u, (uint32_t)st.edges_max, c->d_poly_batches,
+                        c->d_poly_edges};
+        lds = POLY_TABLE_BYTES + (size_t)st.edges_max * sizeof(PolyEdge);
+        for_layout(c, [&](auto layout) {
+            hipLaunchKernelGGL((k_polygon_count<layout.value>), dim3((unsigned)nS), block, lds, c->stream, make_stream_view(c), args, c->sel.counts, c->sel.totals);
+        });
+        return (int)PCR_OK;
+    });
+    if (rc || (rc = kept_finish(c, o, st.points_selected, "selected", st, out_count, stats, &done)) || done) return rc;
+    return select_write(c, first, n, p, o, [&](size_t s0, dim3 grid, uint4 *out) {
+        PolyArgs a = args;
+        a.batches += s0;
+        for_layout_bc7(c, [&](auto layout, auto bc7) {
+            hipLaunchKernelGGL((k_polygon_write<layout.value, bc7.value>), grid, block, lds, c->stream, make_stream_view(c), a,
+                               c->sel.counts + s0 * PCR_WORKGROUP_SIZE, c->sel.offsets + s0, out);
+        });
+    });
 }
 } // namespace
+} // extern "C++"
 
 int pcr_select_polygon(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_polygon *poly, void *dev_points, size_t capacity_points,
                        int64_t *out_count, pcr_polygon_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    PolygonPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = polygon_prepare(c, first_batch, count, poly, dev_points, 16, capacity_points, out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    if ((rc = select_emit(c, first_batch, 0, n, p.sel, static_cast<uint4 *>(dev_points),
-                          [&](size_t s0, size_t nS, uint4 *out) { polygon_write(c, p, s0, nS, out); }))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PCR_OK;
+    return polygon_call(c, first_batch, count, poly, KeptOut{false, dev_points, capacity_points, {}}, out_count, stats);
 }
 
 int pcr_read_polygon(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_polygon *poly, pcr_point *host, size_t capacity_points,
                      int64_t *out_count, pcr_polygon_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    PolygonPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = polygon_prepare(c, first_batch, count, poly, host, alignof(pcr_point), capacity_points, out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    return select_read(c, first_batch, n, p.sel, host, [&](size_t s0, size_t nS, uint4 *out) { polygon_write(c, p, s0, nS, out); });
+    return polygon_call(c, first_batch, count, poly, KeptOut{true, host, capacity_points, {}}, out_count, stats);
 }
 
 // ---- slabs: pcr_select_slabs / pcr_read_slabs / pcr_plane_support ------------------------------------
+extern "C++" {
 namespace {
 constexpr size_t SLAB_MAX_LDS_BYTES = SLAB_TABLE_BYTES + (size_t)PCR_SLAB_MAX_SELECT * sizeof(pcr_slab);
 constexpr size_t PLANE_MAX_LDS_BYTES = SLAB_TABLE_BYTES + (size_t)PCR_SLAB_MAX_EXCLUDE * sizeof(pcr_slab) +
                                        (size_t)PCR_PLANE_MAX_HYPOTHESES * (sizeof(pcr_slab) + LWC_WAVES * sizeof(uint32_t));
 static_assert(sizeof(pcr_slab) == 32 && sizeof(pcr_plane_stats) == 64 && sizeof(pcr_slab_stats) == 48, "the slab structs of pcr_types.h");
 
-// *p holds at least `need` elements on return (scratch of the context: grown on demand, contents not kept)
-extern "C++" template <class T>
-int slab_reserve(pcr_ctx *c, T *&p, int64_t &capacity, int64_t need, const char *what)
-{
-    if (capacity >= need) return PCR_OK;
-    dfree(p); capacity = 0;
-    if (hipMalloc((void **)&p, (size_t)need * sizeof(T)) != hipSuccess) return set_err(c, PCR_E_NOMEM, "out of device memory for %lld %s", (long long)need, what);
-    capacity = need;
-    return PCR_OK;
-}
-
 int slab_lds_allow(pcr_ctx *c)
 {
     if (c->slab_lds_ready) return PCR_OK;
-    hipError_t e = hipSuccess;
-#define PCR_ALLOW(K, BYTES) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES))
-    PCR_ALLOW(k_slab_count<LAYOUT_WORDS>, SLAB_MAX_LDS_BYTES); PCR_ALLOW(k_slab_count<LAYOUT_POINT_WINDOWS>, SLAB_MAX_LDS_BYTES);
-    PCR_ALLOW((k_slab_write<LAYOUT_WORDS, false>), SLAB_MAX_LDS_BYTES); PCR_ALLOW((k_slab_write<LAYOUT_WORDS, true>), SLAB_MAX_LDS_BYTES);
-    PCR_ALLOW((k_slab_write<LAYOUT_POINT_WINDOWS, false>), SLAB_MAX_LDS_BYTES); PCR_ALLOW((k_slab_write<LAYOUT_POINT_WINDOWS, true>), SLAB_MAX_LDS_BYTES);
-    PCR_ALLOW(k_plane_support<LAYOUT_WORDS>, PLANE_MAX_LDS_BYTES); PCR_ALLOW(k_plane_support<LAYOUT_POINT_WINDOWS>, PLANE_MAX_LDS_BYTES);
-#undef PCR_ALLOW
-    if (e != hipSuccess) return set_err(c, PCR_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
+    int rc;
+    if ((rc = lds_allow(c, SLAB_MAX_LDS_BYTES, &k_slab_count<LAYOUT_WORDS>, &k_slab_count<LAYOUT_POINT_WINDOWS>, &k_slab_write<LAYOUT_WORDS, false>,
+                        &k_slab_write<LAYOUT_WORDS, true>, &k_slab_write<LAYOUT_POINT_WINDOWS, false>, &k_slab_write<LAYOUT_POINT_WINDOWS, true>)) ||
+        (rc = lds_allow(c, PLANE_MAX_LDS_BYTES, &k_plane_support<LAYOUT_WORDS>, &k_plane_support<LAYOUT_POINT_WINDOWS>))) return rc;
     c->slab_lds_ready = true;
     return PCR_OK;
 }
@@ -2109,127 +2182,72 @@ int slab_list_check(pcr_ctx *c, const pcr_slab *slabs, int n, int n_min, int n_m
 
 const pcr_box FULL_BOX = {{INT32_MIN, INT32_MIN, INT32_MIN}, {INT32_MAX, INT32_MAX, INT32_MAX}};
 
-// What a slab selection adds to a SelectPlan: the straddling batches with their slices, the slab array.
-struct SlabsPlan {
-    SelectPlan sel;
-    std::vector<SlabBatch> batches;     // the straddling batches, ascending (alive until the stream has been synchronised)
-    std::vector<pcr_slab> slabs;
+// pcr_select_slabs / pcr_read_slabs: what the slabs add to select_plan is the straddling batches with their slices of the slab
+// array (both alive until the stream has been synchronised)
+int slabs_call(pcr_ctx *c, int64_t first, int64_t count, const pcr_slab *slabs, int num_slabs, const pcr_box *clip, uint32_t flags, const KeptOut &o,
+               int64_t *out_count, pcr_slab_stats *stats)
+{
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    SelectPlan p;
+    std::vector<SlabBatch> batches;
+    std::vector<pcr_slab> listed;
     SlabArgs args{};
     size_t lds = 0;                     // dynamic LDS of the k_slab_* launches
-    pcr_slab_stats st{};
-};
-
-// Classify (host, pcr_plane.h), upload the straddling batches' slab lists and count them (k_slab_count). Synchronises.
-int slabs_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_slab *slabs, int num_slabs, const pcr_box *clip, uint32_t invert, SlabsPlan &p)
-{
-    p.sel.cls.assign((size_t)n, SEL_OUTSIDE); p.sel.cnt.assign((size_t)n, 0); p.sel.strad.clear();
-    p.batches.clear(); p.slabs.clear();
-    p.st = pcr_slab_stats{n, 0, 0, 0, 0, 0};
-    if (n == 0 || (clip && plane_box_empty(*clip))) return PCR_OK;
-    int rc;
-    if ((rc = ensure_point_bounds(c, first, n))) return rc;
-    for (int64_t i = 0; i < n; ++i) {
-        const size_t e0 = p.slabs.size();
-        uint32_t inv = 0;
-        const int cls = slabs_plan_batch(slabs, num_slabs, clip, invert, c->h_point_bounds.data() + (first + i) * 6, p.slabs, &inv);
-        if (cls == SLABS_OUTSIDE) continue;
-        --p.st.batches_outside;
-        if (cls == SLABS_INSIDE) { p.sel.cls[(size_t)i] = SEL_INSIDE; p.sel.cnt[(size_t)i] = PCR_POINTS_PER_BATCH; ++p.st.batches_inside; continue; }
-        const size_t ne = p.slabs.size() - e0;
-        p.sel.cls[(size_t)i] = SEL_STRADDLING; p.sel.strad.push_back((uint32_t)(first + i)); ++p.st.batches_straddling;
-        p.batches.push_back(SlabBatch{(uint32_t)(first + i), (uint32_t)e0, (uint32_t)ne, inv});
-        p.st.slabs_listed += (int64_t)ne;
-        p.st.slabs_max = std::max(p.st.slabs_max, (int64_t)ne);
-    }
-    const int64_t nS = (int64_t)p.batches.size(), nE = (int64_t)p.slabs.size();
-    if (nS) {
-        if ((rc = select_reserve(c, nS))) return rc;
-        if ((rc = slab_reserve(c, c->d_slab_batches, c->slab_capacity, nS, "straddling batches"))) return rc;
-        if ((rc = slab_reserve(c, c->d_slab_entries, c->slab_entry_capacity, std::max<int64_t>(nE, 1), "slabs"))) return rc;
-        if ((rc = slab_lds_allow(c))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(c->d_slab_batches, p.batches.data(), (size_t)nS * sizeof(SlabBatch), hipMemcpyHostToDevice, c->stream));
-        if (nE) HIP_TRY(c, hipMemcpyAsync(c->d_slab_entries, p.slabs.data(), (size_t)nE * sizeof(pcr_slab), hipMemcpyHostToDevice, c->stream));
-        p.args = SlabArgs{clip ? *clip : FULL_BOX, (uint32_t)p.st.slabs_max, c->d_slab_batches, c->d_slab_entries};
-        p.lds = SLAB_TABLE_BYTES + (size_t)p.st.slabs_max * sizeof(pcr_slab);
-        const StreamView s = make_stream_view(c);
-        const dim3 grid((unsigned)nS), block(PCR_WORKGROUP_SIZE);
-        if (select_reads_windows(c)) hipLaunchKernelGGL((k_slab_count<LAYOUT_POINT_WINDOWS>), grid, block, p.lds, c->stream, s, p.args, c->d_sel_counts, c->d_sel_totals);
-        else                         hipLaunchKernelGGL((k_slab_count<LAYOUT_WORDS>), grid, block, p.lds, c->stream, s, p.args, c->d_sel_counts, c->d_sel_totals);
-        HIP_TRY(c, hipGetLastError());
-        std::vector<uint32_t> totals((size_t)nS);
-        HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_sel_totals, (size_t)nS * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (int64_t k = 0; k < nS; ++k) p.sel.cnt[(size_t)(p.batches[(size_t)k].b - first)] = totals[(size_t)k];
-    }
-    for (int64_t i = 0; i < n; ++i) p.st.points_selected += p.sel.cnt[(size_t)i];
-    return PCR_OK;
-}
-
-// k_slab_write over the straddling batches [s0, s0 + nS) of the plan
-void slabs_write(pcr_ctx *c, const SlabsPlan &p, size_t s0, size_t nS, uint4 *out)
-{
-    const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)nS), block(PCR_WORKGROUP_SIZE);
-    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
-    SlabArgs a = p.args;
-    a.batches += s0;
-#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_slab_write<L, B>), grid, block, p.lds, c->stream, s, a, c->d_sel_counts + s0 * PCR_WORKGROUP_SIZE, \
-                                            c->d_sel_offsets + s0, out)
-    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
-    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
-#undef PCR_LAUNCH
-}
-
-// The checks and the plan shared by pcr_select_slabs / pcr_read_slabs (select_prepare with the slabs' checks).
-int slabs_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_slab *slabs, int num_slabs, const pcr_box *clip, uint32_t flags, const void *dst,
-                  size_t dst_align, size_t capacity, int64_t *out_count, pcr_slab_stats *stats, int64_t *n, SlabsPlan &p, bool *done)
-{
-    *done = true;
-    if (out_count) *out_count = 0;
-    int rc = select_range(c, first, count, n);
-    if (rc) return rc;
-    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
-    if ((rc = slab_list_check(c, slabs, num_slabs, 1, PCR_SLAB_MAX_SELECT, "slabs"))) return rc;
+    pcr_slab_stats st;
+    int64_t n = 0;
+    bool done = true;
+    int rc = kept_begin(c, first, count, o, out_count, &n);
+    if (rc || (rc = slab_list_check(c, slabs, num_slabs, 1, PCR_SLAB_MAX_SELECT, "slabs"))) return rc;
     if (flags & ~PCR_SLAB_INVERT) return set_err(c, PCR_E_ARG, "unknown flag bits 0x%x", flags);
-    if (dst && reinterpret_cast<uintptr_t>(dst) % dst_align != 0) return set_err(c, PCR_E_ARG, "the destination is misaligned (%zu bytes)", dst_align);
-    if ((rc = slabs_plan(c, first, *n, slabs, num_slabs, clip, flags & PCR_SLAB_INVERT, p))) return rc;
-    *out_count = p.st.points_selected;
-    if (stats) *stats = p.st;
-    if (!dst || p.st.points_selected == 0) return PCR_OK;
-    if (capacity < (size_t)p.st.points_selected)
-        return set_err(c, PCR_E_ARG, "capacity of %zu points is below the %lld selected", capacity, (long long)p.st.points_selected);
-    *done = false;
-    return PCR_OK;
+    const dim3 block(PCR_WORKGROUP_SIZE);
+    rc = select_plan(c, first, n, clip && plane_box_empty(*clip), p, st, [&](uint32_t b, const int32_t *bb) {
+        const size_t e0 = listed.size();
+        uint32_t inv = 0;
+        const int cls = slabs_plan_batch(slabs, num_slabs, clip, flags & PCR_SLAB_INVERT, bb, listed, &inv);
+        if (cls != SLABS_STRADDLING) return cls;
+        const size_t ne = listed.size() - e0;
+        batches.push_back(SlabBatch{b, (uint32_t)e0, (uint32_t)ne, inv});
+        st.slabs_listed += (int64_t)ne;
+        st.slabs_max = std::max(st.slabs_max, (int64_t)ne);
+        return cls;
+    }, [&](int64_t nS) {
+        const int64_t nE = (int64_t)listed.size();
+        int rc;
+        if ((rc = reserve(c, c->d_slab_batches, c->slab_capacity, nS, "straddling batches")) ||
+            (rc = reserve(c, c->d_slab_entries, c->slab_entry_capacity, std::max<int64_t>(nE, 1), "slabs")) || (rc = slab_lds_allow(c))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->d_slab_batches, batches.data(), (size_t)nS * sizeof(SlabBatch), hipMemcpyHostToDevice, c->stream));
+        if (nE) HIP_TRY(c, hipMemcpyAsync(c->d_slab_entries, listed.data(), (size_t)nE * sizeof(pcr_slab), hipMemcpyHostToDevice, c->stream));
+        args = SlabArgs{clip ? *clip : FULL_BOX, (uint32_t)st.slabs_max, c->d_slab_batches, c->d_slab_entries};
+        lds = SLAB_TABLE_BYTES + (size_t)st.slabs_max * sizeof(pcr_slab);
+        for_layout(c, [&](auto layout) {
+            hipLaunchKernelGGL((k_slab_count<layout.value>), dim3((unsigned)nS), block, lds, c->stream, make_stream_view(c), args, c->sel.counts, c->sel.totals);
+        });
+        return (int)PCR_OK;
+    });
+    if (rc || (rc = kept_finish(c, o, st.points_selected, "selected", st, out_count, stats, &done)) || done) return rc;
+    return select_write(c, first, n, p, o, [&](size_t s0, dim3 grid, uint4 *out) {
+        SlabArgs a = args;
+        a.batches += s0;
+        for_layout_bc7(c, [&](auto layout, auto bc7) {
+            hipLaunchKernelGGL((k_slab_write<layout.value, bc7.value>), grid, block, lds, c->stream, make_stream_view(c), a,
+                               c->sel.counts + s0 * PCR_WORKGROUP_SIZE, c->sel.offsets + s0, out);
+        });
+    });
 }
 } // namespace
+} // extern "C++"
 
 int pcr_select_slabs(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_slab *slabs, int num_slabs, const pcr_box *clip, uint32_t flags,
                      void *dev_points, size_t capacity_points, int64_t *out_count, pcr_slab_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    SlabsPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = slabs_prepare(c, first_batch, count, slabs, num_slabs, clip, flags, dev_points, 16, capacity_points, out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    if ((rc = select_emit(c, first_batch, 0, n, p.sel, static_cast<uint4 *>(dev_points),
-                          [&](size_t s0, size_t nS, uint4 *out) { slabs_write(c, p, s0, nS, out); }))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PCR_OK;
+    return slabs_call(c, first_batch, count, slabs, num_slabs, clip, flags, KeptOut{false, dev_points, capacity_points, {}}, out_count, stats);
 }
 
 int pcr_read_slabs(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_slab *slabs, int num_slabs, const pcr_box *clip, uint32_t flags,
                    pcr_point *host, size_t capacity_points, int64_t *out_count, pcr_slab_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    SlabsPlan p;
-    int64_t n = 0;
-    bool done = true;
-    int rc = slabs_prepare(c, first_batch, count, slabs, num_slabs, clip, flags, host, alignof(pcr_point), capacity_points, out_count, stats, &n, p, &done);
-    if (rc || done) return rc;
-    return select_read(c, first_batch, n, p.sel, host, [&](size_t s0, size_t nS, uint4 *out) { slabs_write(c, p, s0, nS, out); });
+    return slabs_call(c, first_batch, count, slabs, num_slabs, clip, flags, KeptOut{true, host, capacity_points, {}}, out_count, stats);
 }
 
 int pcr_plane_support(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_slab *hyp, int num_hyp, const pcr_box *clip, const pcr_slab *exclude,
@@ -2278,9 +2296,9 @@ int pcr_plane_support(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_
         size_t excl_max = 0;
         for (const PlaneBatch &b : batches) excl_max = std::max(excl_max, (size_t)b.excl_count);
         const int64_t nX = (int64_t)excl.size(), nH = (int64_t)cut.size();
-        if ((rc = slab_reserve(c, c->d_plane_batches, c->plane_capacity, nD, "decoded batches"))) return rc;
-        if ((rc = slab_reserve(c, c->d_plane_candidates, c->plane_cand_capacity, nD, "candidate counts"))) return rc;
-        if ((rc = slab_reserve(c, c->d_plane_entries, c->plane_entry_capacity, std::max<int64_t>(nX + nH, 1), "slabs"))) return rc;
+        if ((rc = reserve(c, c->d_plane_batches, c->plane_capacity, nD, "decoded batches"))) return rc;
+        if ((rc = reserve(c, c->d_plane_candidates, c->plane_cand_capacity, nD, "candidate counts"))) return rc;
+        if ((rc = reserve(c, c->d_plane_entries, c->plane_entry_capacity, std::max<int64_t>(nX + nH, 1), "slabs"))) return rc;
         if (!c->d_plane_counts && hipMalloc((void **)&c->d_plane_counts, PCR_PLANE_MAX_HYPOTHESES * sizeof(unsigned long long)) != hipSuccess)
             return set_err(c, PCR_E_NOMEM, "out of device memory for the hypothesis counters");
         if ((rc = slab_lds_allow(c))) return rc;
@@ -2332,16 +2350,14 @@ int grid_check(pcr_ctx *c, const pcr_grid *g, const void *top, const void *botto
     return PCR_OK;
 }
 
-void grid_launch(pcr_ctx *c, bool windowed, int colour, unsigned nblocks, size_t lds, const GridEntry *list, const GridArgs &a)
+void grid_launch(pcr_ctx *c, bool windowed, bool coloured, unsigned nblocks, size_t lds, const GridEntry *list, const GridArgs &a)
 {
     const StreamView s = make_stream_view(c);
     const dim3 grid(nblocks), block(PCR_WORKGROUP_SIZE);
-#define PCR_LAUNCH(L, C, W) hipLaunchKernelGGL((k_grid<L, C, W>), grid, block, lds, c->stream, s, list, a)
-#define PCR_LAUNCH_COLOUR(L, W) do { if (colour == SEL_BC7) PCR_LAUNCH(L, SEL_BC7, W); else if (colour == SEL_BC1) PCR_LAUNCH(L, SEL_BC1, W); else PCR_LAUNCH(L, SEL_NO_COLOUR, W); } while (0)
-    if (select_reads_windows(c)) { if (windowed) PCR_LAUNCH_COLOUR(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH_COLOUR(LAYOUT_POINT_WINDOWS, false); }
-    else                         { if (windowed) PCR_LAUNCH_COLOUR(LAYOUT_WORDS, true); else PCR_LAUNCH_COLOUR(LAYOUT_WORDS, false); }
-#undef PCR_LAUNCH_COLOUR
-#undef PCR_LAUNCH
+    for_layout_colour(c, coloured, [&](auto layout, auto colour) {
+        if (windowed) hipLaunchKernelGGL((k_grid<layout.value, colour.value, true>), grid, block, lds, c->stream, s, list, a);
+        else          hipLaunchKernelGGL((k_grid<layout.value, colour.value, false>), grid, block, lds, c->stream, s, list, a);
+    });
 }
 
 // The batches [first, first + n) by their exact box against q (grid and clip intersected, not empty): those the box does not miss
@@ -2422,19 +2438,16 @@ int grid_accumulate(pcr_ctx *c, int64_t first, int64_t n, const pcr_grid &g, con
     if (nW + nD == 0) return PCR_OK;
     if ((rc = grid_list_upload(c, win))) return rc;
     if (!c->grid_lds_ready) {
-        hipError_t e = hipSuccess;
-#define PCR_ALLOW(L, C) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_grid<L, C, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GRID_MAX_LDS_BYTES)
-        PCR_ALLOW(LAYOUT_WORDS, SEL_NO_COLOUR); PCR_ALLOW(LAYOUT_WORDS, SEL_BC1); PCR_ALLOW(LAYOUT_WORDS, SEL_BC7);
-        PCR_ALLOW(LAYOUT_POINT_WINDOWS, SEL_NO_COLOUR); PCR_ALLOW(LAYOUT_POINT_WINDOWS, SEL_BC1); PCR_ALLOW(LAYOUT_POINT_WINDOWS, SEL_BC7);
-#undef PCR_ALLOW
-        if (e != hipSuccess) return set_err(c, PCR_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
+        if ((rc = lds_allow(c, GRID_MAX_LDS_BYTES, &k_grid<LAYOUT_WORDS, SEL_NO_COLOUR, true>, &k_grid<LAYOUT_WORDS, SEL_BC1, true>,
+                            &k_grid<LAYOUT_WORDS, SEL_BC7, true>, &k_grid<LAYOUT_POINT_WINDOWS, SEL_NO_COLOUR, true>,
+                            &k_grid<LAYOUT_POINT_WINDOWS, SEL_BC1, true>, &k_grid<LAYOUT_POINT_WINDOWS, SEL_BC7, true>))) return rc;
         c->grid_lds_ready = true;
     }
     a.ox = g.origin_x; a.oy = g.origin_y; a.width = (uint32_t)g.width;
     a.div = make_cell_div((uint32_t)g.cell);
     a.top = static_cast<unsigned long long *>(top); a.bottom = static_cast<unsigned long long *>(bottom); a.count = static_cast<uint32_t *>(count);
     a.win_cells = win_cells;
-    const int colour = !top && !bottom ? SEL_NO_COLOUR : c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7 ? SEL_BC7 : SEL_BC1;
+    const bool colour = top || bottom;
     if (nW) {
         const size_t lds = GRID_TABLE_BYTES + (size_t)win_cells * ((top ? 8 : 0) + (bottom ? 8 : 0) + (count ? 4 : 0));
         grid_launch(c, true, colour, (unsigned)nW, lds, c->d_grid_list, a);
@@ -2632,11 +2645,11 @@ bool grid_clip_box(const pcr_grid &g, const pcr_box *clip, pcr_box &q)
 }
 
 // What a height selection over batches [first, first + n) has to write: the batches that are not outside (ascending; their
-// per-chain counts sit in c->d_sel_counts in the same order) and each one's record count.
+// per-chain counts sit in c->sel.counts in the same order) and each one's record count.
 struct HeightPlan {
     std::vector<uint32_t> listed;
     std::vector<int64_t> cnt;
-    std::vector<int64_t> offsets;       // staging of k_height_write's offsets (alive until the stream has been synchronised)
+    std::vector<int64_t> offsets;       // listed_write's
     HeightArgs a{};
     pcr_height_stats st{};
 };
@@ -2659,17 +2672,17 @@ int height_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_grid &g, const p
     p.st.batches_outside = n - nL; p.st.batches_decoded = nL;
     p.cnt.assign((size_t)nL, 0);
     if (nL == 0) return PCR_OK;
-    if ((rc = select_reserve(c, 2 * nL))) return rc;                            // (two totals per batch)
-    HIP_TRY(c, hipMemcpyAsync(c->d_sel_list, p.listed.data(), (size_t)nL * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = scratch_reserve(c, c->sel, 2 * nL, "totals of the listed batches (two each)"))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->sel.list, p.listed.data(), (size_t)nL * 4, hipMemcpyHostToDevice, c->stream));
     p.a.ox = g.origin_x; p.a.oy = g.origin_y; p.a.width = (uint32_t)g.width;
     p.a.div = make_cell_div((uint32_t)g.cell);
-    const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)nL), block(PCR_WORKGROUP_SIZE);
-    if (select_reads_windows(c)) hipLaunchKernelGGL((k_height_count<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_sel_list, p.a, c->d_sel_counts, c->d_sel_totals);
-    else                         hipLaunchKernelGGL((k_height_count<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_sel_list, p.a, c->d_sel_counts, c->d_sel_totals);
+    for_layout(c, [&](auto layout) {
+        hipLaunchKernelGGL((k_height_count<layout.value>), dim3((unsigned)nL), dim3(PCR_WORKGROUP_SIZE), 0, c->stream, make_stream_view(c), c->sel.list, p.a,
+                           c->sel.counts, c->sel.totals);
+    });
     HIP_TRY(c, hipGetLastError());
     std::vector<uint32_t> totals((size_t)nL * 2);
-    HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_sel_totals, (size_t)nL * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(totals.data(), c->sel.totals, (size_t)nL * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int64_t k = 0; k < nL; ++k) {
         p.cnt[(size_t)k] = totals[(size_t)k * 2];
@@ -2678,54 +2691,28 @@ int height_plan(pcr_ctx *c, int64_t first, int64_t n, const pcr_grid &g, const p
     return PCR_OK;
 }
 
-// Enqueue the writes of listed batches [k0, k1) to points / heights (device, either may be NULL; record 0 = the first of batch k0).
-// The caller synchronises.
-int height_emit(pcr_ctx *c, HeightPlan &p, int64_t k0, int64_t k1, uint4 *points, int32_t *heights)
+// pcr_select_height / pcr_read_height: the records to o.points, their heights to column 0
+int height_call(pcr_ctx *c, int64_t first, int64_t count, const pcr_grid *grid, const void *dev_ground, const pcr_box *clip, int32_t h_min, int32_t h_max,
+                uint32_t flags, const KeptOut &o, int64_t *out_count, pcr_height_stats *stats)
 {
-    p.offsets.clear();
-    int64_t off = 0;
-    for (int64_t k = k0; k < k1; ++k) { p.offsets.push_back(off); off += p.cnt[(size_t)k]; }
-    if (off == 0) return PCR_OK;
-    HIP_TRY(c, hipMemcpyAsync(c->d_sel_offsets + k0, p.offsets.data(), (size_t)(k1 - k0) * 8, hipMemcpyHostToDevice, c->stream));
-    const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)(k1 - k0)), block(PCR_WORKGROUP_SIZE);
-    const int colour = !points ? SEL_NO_COLOUR : c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7 ? SEL_BC7 : SEL_BC1;
-#define PCR_LAUNCH(L, C) hipLaunchKernelGGL((k_height_write<L, C>), grid, block, 0, c->stream, s, c->d_sel_list + k0, p.a, \
-                                            c->d_sel_counts + k0 * PCR_WORKGROUP_SIZE, c->d_sel_offsets + k0, points, heights)
-#define PCR_LAUNCH_COLOUR(L) do { if (colour == SEL_BC7) PCR_LAUNCH(L, SEL_BC7); else if (colour == SEL_BC1) PCR_LAUNCH(L, SEL_BC1); else PCR_LAUNCH(L, SEL_NO_COLOUR); } while (0)
-    if (select_reads_windows(c)) PCR_LAUNCH_COLOUR(LAYOUT_POINT_WINDOWS); else PCR_LAUNCH_COLOUR(LAYOUT_WORDS);
-#undef PCR_LAUNCH_COLOUR
-#undef PCR_LAUNCH
-    HIP_TRY(c, hipGetLastError());
-    return PCR_OK;
-}
-
-// The checks and the plan shared by pcr_select_height / pcr_read_height. *done: nothing left to write.
-int height_prepare(pcr_ctx *c, int64_t first, int64_t count, const pcr_grid *grid, const void *dev_ground, const pcr_box *clip, int32_t h_min,
-                   int32_t h_max, uint32_t flags, const void *points, const void *heights, size_t align_points, size_t capacity,
-                   int64_t *out_count, pcr_height_stats *stats, HeightPlan &p, bool *done)
-{
-    *done = true;
-    if (out_count) *out_count = 0;
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HeightPlan p;
     int64_t n = 0;
-    int rc = select_range(c, first, count, &n);
-    if (rc) return rc;
-    if ((rc = grid_check(c, grid, nullptr, nullptr, nullptr))) return rc;
+    bool done = true;
+    int rc = kept_begin(c, first, count, o, out_count, &n);
+    if (rc || (rc = grid_check(c, grid, nullptr, nullptr, nullptr))) return rc;
     if (!dev_ground) return set_err(c, PCR_E_ARG, "the ground plane is NULL");
     if (reinterpret_cast<uintptr_t>(dev_ground) % 4 != 0) return set_err(c, PCR_E_ARG, "the ground plane is misaligned (4 bytes)");
     if (flags & ~(uint32_t)PCR_HEIGHT_REPLACE_Z) return set_err(c, PCR_E_ARG, "unknown flag bits 0x%x", flags & ~(uint32_t)PCR_HEIGHT_REPLACE_Z);
-    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
-    if (points && reinterpret_cast<uintptr_t>(points) % align_points != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", align_points);
-    if (heights && reinterpret_cast<uintptr_t>(heights) % 4 != 0) return set_err(c, PCR_E_ARG, "the destination of the heights is misaligned (4 bytes)");
     p.a.ground = static_cast<const int32_t *>(dev_ground); p.a.h_min = h_min; p.a.h_max = h_max; p.a.replace_z = flags & PCR_HEIGHT_REPLACE_Z;
-    if ((rc = height_plan(c, first, n, *grid, clip, p))) return rc;
-    *out_count = p.st.points_selected;
-    if (stats) *stats = p.st;
-    if ((!points && !heights) || p.st.points_selected == 0) return PCR_OK;
-    if (capacity < (size_t)p.st.points_selected)
-        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld selected", capacity, (long long)p.st.points_selected);
-    *done = false;
-    return PCR_OK;
+    if ((rc = height_plan(c, first, n, *grid, clip, p)) || (rc = kept_finish(c, o, p.st.points_selected, "selected", p.st, out_count, stats, &done)) || done) return rc;
+    return listed_write(c, p.cnt, p.offsets, c->sel.offsets, o, [&](int64_t k0, dim3 grid, const KeptOut &d) {
+        for_layout_colour(c, d.points != nullptr, [&](auto layout, auto colour) {
+            hipLaunchKernelGGL((k_height_write<layout.value, colour.value>), grid, dim3(PCR_WORKGROUP_SIZE), 0, c->stream, make_stream_view(c), c->sel.list + k0, p.a,
+                               c->sel.counts + k0 * PCR_WORKGROUP_SIZE, c->sel.offsets + k0, static_cast<uint4 *>(d.points), static_cast<int32_t *>(d.col[0].dst));
+        });
+    });
 }
 } // namespace
 
@@ -2779,53 +2766,16 @@ int pcr_select_height(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_
                       int32_t h_min, int32_t h_max, uint32_t flags, void *dev_points, void *dev_heights, size_t capacity, int64_t *out_count,
                       pcr_height_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HeightPlan p;
-    bool done = true;
-    int rc = height_prepare(c, first_batch, count, grid, dev_ground, clip, h_min, h_max, flags, dev_points, dev_heights, 16, capacity, out_count, stats, p, &done);
-    if (rc || done) return rc;
-    if ((rc = height_emit(c, p, 0, (int64_t)p.listed.size(), static_cast<uint4 *>(dev_points), static_cast<int32_t *>(dev_heights)))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PCR_OK;
+    return height_call(c, first_batch, count, grid, dev_ground, clip, h_min, h_max, flags, KeptOut{false, dev_points, capacity, {heights_column(dev_heights)}},
+                       out_count, stats);
 }
 
 int pcr_read_height(pcr_ctx *c, int64_t first_batch, int64_t count, const pcr_grid *grid, const void *dev_ground, const pcr_box *clip,
                     int32_t h_min, int32_t h_max, uint32_t flags, pcr_point *host_points, int32_t *host_heights, size_t capacity,
                     int64_t *out_count, pcr_height_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HeightPlan p;
-    bool done = true;
-    int rc = height_prepare(c, first_batch, count, grid, dev_ground, clip, h_min, h_max, flags, host_points, host_heights, alignof(pcr_point), capacity,
-                            out_count, stats, p, &done);
-    if (rc || done) return rc;
-    // pieces of at most DECODE_STAGE_BATCHES / 2 listed batches: a piece's points fit the first half of the staging buffer, its
-    // heights the second (pcr_read_screen's scheme)
-    const int64_t nL = (int64_t)p.listed.size();
-    const int64_t piece = std::min<int64_t>(nL, DECODE_STAGE_BATCHES / 2);
-    if (!c->d_decode_stage || c->decode_stage_batches < 2 * piece) {
-        dfree(c->d_decode_stage); c->decode_stage_batches = 0;
-        if (hipMalloc((void **)&c->d_decode_stage, (size_t)(2 * piece) * PCR_POINTS_PER_BATCH * sizeof(pcr_point)) != hipSuccess)
-            return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of points", (long long)(2 * piece));
-        c->decode_stage_batches = 2 * piece;
-    }
-    uint4 *const d_points = reinterpret_cast<uint4 *>(c->d_decode_stage);
-    int32_t *const d_heights = reinterpret_cast<int32_t *>(d_points + (size_t)piece * PCR_POINTS_PER_BATCH);
-    int64_t written = 0;
-    for (int64_t k0 = 0; k0 < nL; k0 += piece) {
-        const int64_t k1 = std::min(nL, k0 + piece);
-        int64_t m = 0;
-        for (int64_t k = k0; k < k1; ++k) m += p.cnt[(size_t)k];
-        if (m == 0) continue;
-        if ((rc = height_emit(c, p, k0, k1, host_points ? d_points : nullptr, host_heights ? d_heights : nullptr))) return rc;
-        if (host_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
-        if (host_heights) HIP_TRY(c, hipMemcpyAsync(host_heights + written, d_heights, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        written += m;
-    }
-    return PCR_OK;
+    return height_call(c, first_batch, count, grid, dev_ground, clip, h_min, h_max, flags, KeptOut{true, host_points, capacity, {heights_column(host_heights)}},
+                       out_count, stats);
 }
 
 // ---- height percentiles per grid cell ----------------------------------------------------------
@@ -2853,11 +2803,11 @@ void quantiles_launch(pcr_ctx *c, bool fill, bool windowed, unsigned nblocks, si
 {
     const StreamView s = make_stream_view(c);
     const dim3 grid(nblocks), block(PCR_WORKGROUP_SIZE);
-#define PCR_LAUNCH(L, W) do { if (fill) hipLaunchKernelGGL((k_quant_fill<L, W>), grid, block, lds, c->stream, s, list, a); \
-                              else      hipLaunchKernelGGL((k_quant_count<L, W>), grid, block, lds, c->stream, s, list, a); } while (0)
-    if (select_reads_windows(c)) { if (windowed) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
-    else                         { if (windowed) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
-#undef PCR_LAUNCH
+    auto both = [&](auto layout, auto win) {
+        if (fill) hipLaunchKernelGGL((k_quant_fill<layout.value, win.value>), grid, block, lds, c->stream, s, list, a);
+        else      hipLaunchKernelGGL((k_quant_count<layout.value, win.value>), grid, block, lds, c->stream, s, list, a);
+    };
+    for_layout(c, [&](auto layout) { if (windowed) both(layout, std::true_type{}); else both(layout, std::false_type{}); });
 }
 
 // pcr_grid_quantiles behind its checks: n batches from `first`; floor, planes and count are device pointers or NULL. Synchronises.
@@ -2997,17 +2947,6 @@ struct ThinPlan {
                                         // thin_plan: for pcr_voxel_mean's kernels)
     const thin_u64 *label = nullptr;    // pcr_components only: the label of every slot
 };
-
-// *p holds at least `want` elements on return (a larger array replaces it, its content is not kept), or false
-bool thin_grow(void **p, int64_t &have, int64_t want, size_t elem_bytes)
-{
-    if (*p && have >= want) return true;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; have = 0;
-    if (hipMalloc(p, (size_t)want * elem_bytes) != hipSuccess) { *p = nullptr; return false; }
-    have = want;
-    return true;
-}
 
 // The batches of [first, first + n) whose exact box the clip a.q does not miss into `listed` (ascending), and into q the union of
 // their boxes intersected with the clip. a.q is not empty.
@@ -3154,57 +3093,12 @@ int voxel_plan_collect(pcr_ctx *c, int64_t first, ThinPlan &p, VoxelPlan &v, voi
     return PCR_OK;
 }
 
-// What a call writes per kept row: the record to `points` and up to three columns, `name` as the messages call them. Any
-// destination may be NULL, each holds `capacity` rows. host: the destinations are host memory (the pcr_read_ form).
-struct KeptColumn { const char *name; void *dst; size_t row_bytes; };
-struct KeptOut {
-    bool host;
-    void *points;
-    size_t capacity;
-    KeptColumn col[3];
-};
-
-// The checks every call starts with: the range into *n, the lattice where the call has one (has_lattice), out_count and the
-// alignment of the destinations: 16 / 8 bytes on the device, the types' own on the host. *out_count is 0 from here on.
-int kept_begin(pcr_ctx *c, int64_t first, int64_t count, const KeptOut &o, int64_t *out_count, int64_t *n, bool has_lattice = false,
-               const pcr_voxels *vox = nullptr)
-{
-    if (out_count) *out_count = 0;
-    int rc = select_range(c, first, count, n);
-    if (rc) return rc;
-    if (has_lattice && !vox) return set_err(c, PCR_E_ARG, "the voxel lattice is NULL");
-    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
-    const size_t points_align = o.host ? alignof(pcr_point) : 16, col_align = o.host ? alignof(int64_t) : 8;
-    if (o.points && reinterpret_cast<uintptr_t>(o.points) % points_align != 0)
-        return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", points_align);
-    for (const KeptColumn &k : o.col)
-        if (k.dst && reinterpret_cast<uintptr_t>(k.dst) % col_align != 0)
-            return set_err(c, PCR_E_ARG, "the destination of the %s is misaligned (%zu bytes)", k.name, col_align);
-    if (vox && (vox->cell < 1 || vox->cell > PCR_THIN_MAX_CELL))
-        return set_err(c, PCR_E_ARG, "voxel cell of %d: the edge length is 1 .. %d (PCR_THIN_MAX_CELL)", vox->cell, PCR_THIN_MAX_CELL);
-    return PCR_OK;
-}
-
 // The last of a call's checks: a range of n batches holds at most max_rows rows (`limit` words it: 2^40 where rows are 64-bit, 2^32
 // where an index or a sum holds a 32-bit row)
 constexpr const char *ROWS_2_40 = "2^40 rows", *ROWS_2_32_INDEX = "2^32 rows (the index stores a 32-bit row)";
 int kept_row_limit(pcr_ctx *c, int64_t n, int64_t max_rows, const char *limit)
 {
     if (n > max_rows / PCR_POINTS_PER_BATCH) return set_err(c, PCR_E_ARG, "a range of %lld batches has more than %s", (long long)n, limit);
-    return PCR_OK;
-}
-
-// After the plan: the count and the statistics out; *done unless something is left to write, which is not so for a count-only
-// call, without rows, or where `kept` rows (`noun` in the message) do not fit the capacity
-template <class Stats>
-int kept_finish(pcr_ctx *c, const KeptOut &o, int64_t kept, const char *noun, const Stats &st, int64_t *out_count, Stats *stats, bool *done)
-{
-    *done = true;
-    *out_count = kept;
-    if (stats) *stats = st;
-    if ((!o.points && !o.col[0].dst && !o.col[1].dst && !o.col[2].dst) || kept == 0) return PCR_OK;
-    if (o.capacity < (size_t)kept) return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld %s", o.capacity, (long long)kept, noun);
-    *done = false;
     return PCR_OK;
 }
 
@@ -3233,18 +3127,6 @@ int emit_offsets(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p,
     return PCR_OK;
 }
 
-// launch(layout, bc7) with the layout the selections read and the stream's colour format, each a std::integral_constant: the
-// template arguments of a kernel that decodes with colour
-template <class Launch>
-void for_layout_bc7(const pcr_ctx *c, Launch launch)
-{
-    using Windows = std::integral_constant<int, LAYOUT_POINT_WINDOWS>;
-    using Words = std::integral_constant<int, LAYOUT_WORDS>;
-    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
-    if (select_reads_windows(c)) { if (bc7) launch(Windows{}, std::true_type{}); else launch(Windows{}, std::false_type{}); }
-    else                         { if (bc7) launch(Words{}, std::true_type{}); else launch(Words{}, std::false_type{}); }
-}
-
 // Enqueue the writes of batches [i0, i1) of the plan's range: launch(layout, bc7, e) starts the call's write kernel at e. The
 // caller synchronises.
 template <class Launch>
@@ -3258,66 +3140,16 @@ int kept_emit(pcr_ctx *c, int64_t first, int64_t i0, int64_t i1, ThinPlan &p, La
     return PCR_OK;
 }
 
-// The device twin of a host description for `batches` batches of 65 536 rows: the points through d_decode_stage, column i through
-// d_col_stage[i], NULL where the host takes none. The name of the buffer there is no memory for, or NULL.
-const char *stage_reserve(pcr_ctx *c, const KeptOut &o, int64_t batches, KeptOut &d)
-{
-    d = o;
-    d.host = false;
-    if (o.points) {
-        if (!thin_grow((void **)&c->d_decode_stage, c->decode_stage_batches, batches, (size_t)PCR_POINTS_PER_BATCH * sizeof(pcr_point))) return "points";
-        d.points = c->d_decode_stage;
-    }
-    for (int i = 0; i < 3; ++i) {
-        if (!o.col[i].dst) continue;
-        if (!thin_grow(&c->d_col_stage[i], c->col_stage_bytes[i], batches * PCR_POINTS_PER_BATCH * (int64_t)o.col[i].row_bytes, 1)) return o.col[i].name;
-        d.col[i].dst = c->d_col_stage[i];
-    }
-    return nullptr;
-}
-
-// The first m rows of the stages d to rows [at, at + m) of the host destinations o. Synchronises.
-int stage_copy(pcr_ctx *c, const KeptOut &o, const KeptOut &d, int64_t at, int64_t m)
-{
-    if (d.points) HIP_TRY(c, hipMemcpyAsync(static_cast<pcr_point *>(o.points) + at, d.points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
-    for (int i = 0; i < 3; ++i) {
-        const size_t row_bytes = o.col[i].row_bytes;
-        if (d.col[i].dst)
-            HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(o.col[i].dst) + (size_t)at * row_bytes, d.col[i].dst, (size_t)m * row_bytes, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PCR_OK;
-}
-
-// The plan's rows to the destinations: emit(i0, i1, d) enqueues the writes of batches [i0, i1) to the device destinations d, each
-// holding the rows of those batches. On the device one emit into o itself; to the host in pieces through the stages. stage_named:
-// a stage that does not fit is reported by name. Synchronises.
+// kept_write for a plan of the kept-rows calls: its units are the n batches of the range, their rows are the writers' counts
 template <class Emit>
 int kept_write(pcr_ctx *c, int64_t first, int64_t n, const ThinPlan &p, const KeptOut &o, Emit emit, bool stage_named = false)
 {
-    int rc;
-    if (!o.host) {
-        if ((rc = emit(0, n, o))) return rc;
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return PCR_OK;
-    }
-    // pieces of at most DECODE_STAGE_BATCHES batches: a batch keeps at most 65 536 records, so a piece fits the stages
-    const int64_t piece = std::min<int64_t>(n, DECODE_STAGE_BATCHES);
-    KeptOut d;
-    if (const char *what = stage_reserve(c, o, piece, d))
-        return stage_named ? set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of %s", (long long)piece, what)
-                           : set_err(c, PCR_E_NOMEM, "out of device memory for the staging buffers of %lld batches", (long long)piece);
-    int64_t written = 0;
     size_t w = 0;
-    for (int64_t i0 = 0; i0 < n; i0 += piece) {
-        const int64_t i1 = std::min(n, i0 + piece);
+    return kept_write(c, n, o, [&](int64_t, int64_t i1) {
         int64_t m = 0;
         for (; w < p.writers.size() && p.writers[w] < (uint32_t)(first + i1); ++w) m += p.cnt[w];
-        if (m == 0) continue;
-        if ((rc = emit(i0, i1, d)) || (rc = stage_copy(c, o, d, written, m))) return rc;
-        written += m;
-    }
-    return PCR_OK;
+        return m;
+    }, emit, stage_named);
 }
 } // namespace
 } // extern "C++"
@@ -4213,11 +4045,11 @@ int pcr_read_voxel_mean(pcr_ctx *c, int64_t first_batch, int64_t count, const pc
 // ---- screen selection and picking --------------------------------------------------------------
 namespace {
 // What a screen selection has to write: the batches the prepass keeps for the camera (ascending, with their LOD words; their
-// per-chain counts sit in c->d_scr_counts in the same order) and each one's record count.
+// per-chain counts sit in c->scr.counts in the same order) and each one's record count.
 struct ScreenPlan {
     std::vector<ScreenEntry> kept;
     std::vector<int64_t> cnt;
-    std::vector<int64_t> offsets;       // staging of k_screen_write's offsets (alive until the stream has been synchronised)
+    std::vector<int64_t> offsets;       // listed_write's
     ScreenArgs q{};
     pcr_screen_stats st{};
 };
@@ -4257,15 +4089,8 @@ int screen_list(pcr_ctx *c, const pcr_render_params *p, int64_t nB, ScreenPlan &
     const int64_t nK = (int64_t)pl.kept.size();
     pl.st.batches_decoded = nK; pl.st.batches_skipped = nB - nK;
     if (nK == 0) return PCR_OK;
-    if (c->scr_capacity < nK) {
-        dfree(c->d_scr_list); dfree(c->d_scr_counts); dfree(c->d_scr_totals); dfree(c->d_scr_offsets); c->scr_capacity = 0;
-        if (hipMalloc((void **)&c->d_scr_list, (size_t)nK * sizeof(ScreenEntry)) != hipSuccess || hipMalloc((void **)&c->d_scr_totals, (size_t)nK * 4) != hipSuccess ||
-            hipMalloc((void **)&c->d_scr_offsets, (size_t)nK * 8) != hipSuccess ||
-            hipMalloc((void **)&c->d_scr_counts, (size_t)nK * PCR_WORKGROUP_SIZE * 4) != hipSuccess)
-            return set_err(c, PCR_E_NOMEM, "out of device memory for the counts of %lld batches", (long long)nK);
-        c->scr_capacity = nK;
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->d_scr_list, pl.kept.data(), (size_t)nK * sizeof(ScreenEntry), hipMemcpyHostToDevice, c->stream));
+    if ((rc = scratch_reserve(c, c->scr, nK, "kept batches (their counts)"))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->scr.list, pl.kept.data(), (size_t)nK * sizeof(ScreenEntry), hipMemcpyHostToDevice, c->stream));
     return PCR_OK;
 }
 
@@ -4275,115 +4100,56 @@ int screen_count(pcr_ctx *c, ScreenPlan &pl)
     const int64_t nK = (int64_t)pl.kept.size();
     pl.cnt.assign((size_t)nK, 0);
     if (nK == 0) return PCR_OK;
-    const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)nK), block(PCR_WORKGROUP_SIZE);
-    if (select_reads_windows(c)) hipLaunchKernelGGL((k_screen_count<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_scr_list, pl.q, c->d_scr_counts, c->d_scr_totals);
-    else                         hipLaunchKernelGGL((k_screen_count<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_scr_list, pl.q, c->d_scr_counts, c->d_scr_totals);
+    for_layout(c, [&](auto layout) {
+        hipLaunchKernelGGL((k_screen_count<layout.value>), dim3((unsigned)nK), dim3(PCR_WORKGROUP_SIZE), 0, c->stream, make_stream_view(c), c->scr.list, pl.q,
+                           c->scr.counts, c->scr.totals);
+    });
     HIP_TRY(c, hipGetLastError());
     std::vector<uint32_t> totals((size_t)nK);
-    HIP_TRY(c, hipMemcpyAsync(totals.data(), c->d_scr_totals, (size_t)nK * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(totals.data(), c->scr.totals, (size_t)nK * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int64_t k = 0; k < nK; ++k) { pl.cnt[(size_t)k] = totals[(size_t)k]; pl.st.points_selected += totals[(size_t)k]; }
     return PCR_OK;
 }
 
-// Enqueue the writes of kept batches [k0, k1) to points / hits (device, either may be NULL; record 0 = the first of batch k0).
-// The caller synchronises.
-int screen_emit(pcr_ctx *c, ScreenPlan &pl, int64_t k0, int64_t k1, uint4 *points, uint4 *hits)
+// The rect of a call (NULL: the image) clipped to the image into q; false: nothing is left of it.
+bool screen_rect(const pcr_render_params *p, const pcr_rect *rect, ScreenArgs &q)
 {
-    pl.offsets.clear();
-    int64_t off = 0;
-    for (int64_t k = k0; k < k1; ++k) { pl.offsets.push_back(off); off += pl.cnt[(size_t)k]; }
-    if (off == 0) return PCR_OK;
-    HIP_TRY(c, hipMemcpyAsync(c->d_scr_offsets + k0, pl.offsets.data(), (size_t)(k1 - k0) * 8, hipMemcpyHostToDevice, c->stream));
-    const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)(k1 - k0)), block(PCR_WORKGROUP_SIZE);
-    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
-#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_screen_write<L, B>), grid, block, 0, c->stream, s, c->d_scr_list + k0, pl.q, \
-                                            c->d_scr_counts + k0 * PCR_WORKGROUP_SIZE, c->d_scr_offsets + k0, points, hits)
-    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
-    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
-#undef PCR_LAUNCH
-    HIP_TRY(c, hipGetLastError());
-    return PCR_OK;
+    return rect ? screen_clip(p, rect->x0, rect->y0, rect->x1, rect->y1, q) : screen_clip(p, 0, 0, p->width - 1, p->height - 1, q);
 }
 
-// The checks and the plan shared by pcr_select_screen / pcr_read_screen. *done: nothing left to write (an error, a count-only
-// call, no records).
-int screen_prepare(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect, const void *points, const void *hits, size_t align_points,
-                   size_t align_hits, size_t capacity, int64_t *out_count, pcr_screen_stats *stats, ScreenPlan &pl, bool *done)
+// pcr_select_screen / pcr_read_screen: the records to o.points, their hits to column 0
+int screen_call(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect, const KeptOut &o, int64_t *out_count, pcr_screen_stats *stats)
 {
-    *done = true;
-    if (out_count) *out_count = 0;
-    int rc = check_params(c, p);
-    if (rc) return rc;
-    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
-    if (points && reinterpret_cast<uintptr_t>(points) % align_points != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", align_points);
-    if (hits && reinterpret_cast<uintptr_t>(hits) % align_hits != 0) return set_err(c, PCR_E_ARG, "the destination of the hits is misaligned (%zu bytes)", align_hits);
-    if (c->async_upload) poll_loader(c, false);
-    const int64_t nB = c->visible_batches();
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ScreenPlan pl;
+    int64_t nB = 0;
+    bool done = true;
+    int rc = kept_begin(c, 0, -1, o, out_count, &nB);                           // (the range: every resident batch)
+    if (rc || (rc = check_params(c, p))) return rc;
     pl.st = pcr_screen_stats{nB, 0, 0, 0};
-    const bool some = rect ? screen_clip(p, rect->x0, rect->y0, rect->x1, rect->y1, pl.q) : screen_clip(p, 0, 0, p->width - 1, p->height - 1, pl.q);
-    if (some && nB > 0) {
-        if ((rc = screen_list(c, p, nB, pl)) || (rc = screen_count(c, pl))) return rc;
-    }
-    *out_count = pl.st.points_selected;
-    if (stats) *stats = pl.st;
-    if ((!points && !hits) || pl.st.points_selected == 0) return PCR_OK;
-    if (capacity < (size_t)pl.st.points_selected)
-        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld selected", capacity, (long long)pl.st.points_selected);
-    *done = false;
-    return PCR_OK;
+    if (screen_rect(p, rect, pl.q) && nB > 0 && ((rc = screen_list(c, p, nB, pl)) || (rc = screen_count(c, pl)))) return rc;
+    if ((rc = kept_finish(c, o, pl.st.points_selected, "selected", pl.st, out_count, stats, &done)) || done) return rc;
+    return listed_write(c, pl.cnt, pl.offsets, c->scr.offsets, o, [&](int64_t k0, dim3 grid, const KeptOut &d) {
+        for_layout_bc7(c, [&](auto layout, auto bc7) {
+            hipLaunchKernelGGL((k_screen_write<layout.value, bc7.value>), grid, dim3(PCR_WORKGROUP_SIZE), 0, c->stream, make_stream_view(c), c->scr.list + k0, pl.q,
+                               c->scr.counts + k0 * PCR_WORKGROUP_SIZE, c->scr.offsets + k0, static_cast<uint4 *>(d.points), static_cast<uint4 *>(d.col[0].dst));
+        });
+    });
 }
 } // namespace
 
 int pcr_select_screen(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect, void *dev_points, void *dev_hits, size_t capacity,
                       int64_t *out_count, pcr_screen_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ScreenPlan pl;
-    bool done = true;
-    int rc = screen_prepare(c, p, rect, dev_points, dev_hits, 16, 16, capacity, out_count, stats, pl, &done);
-    if (rc || done) return rc;
-    if ((rc = screen_emit(c, pl, 0, (int64_t)pl.kept.size(), static_cast<uint4 *>(dev_points), static_cast<uint4 *>(dev_hits)))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PCR_OK;
+    return screen_call(c, p, rect, KeptOut{false, dev_points, capacity, {hits_column(dev_hits)}}, out_count, stats);
 }
 
 int pcr_read_screen(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect, pcr_point *host_points, pcr_screen_hit *host_hits,
                     size_t capacity, int64_t *out_count, pcr_screen_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    ScreenPlan pl;
-    bool done = true;
-    int rc = screen_prepare(c, p, rect, host_points, host_hits, alignof(pcr_point), alignof(pcr_screen_hit), capacity, out_count, stats, pl, &done);
-    if (rc || done) return rc;
-    // pieces of at most DECODE_STAGE_BATCHES / 2 kept batches: a batch selects at most 65 536 records, so a piece's points fit the
-    // first half of the staging buffer and its hits the second
-    const int64_t nK = (int64_t)pl.kept.size();
-    const int64_t piece = std::min<int64_t>(nK, DECODE_STAGE_BATCHES / 2);
-    if (!c->d_decode_stage || c->decode_stage_batches < 2 * piece) {
-        dfree(c->d_decode_stage); c->decode_stage_batches = 0;
-        if (hipMalloc((void **)&c->d_decode_stage, (size_t)(2 * piece) * PCR_POINTS_PER_BATCH * sizeof(pcr_point)) != hipSuccess)
-            return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of points", (long long)(2 * piece));
-        c->decode_stage_batches = 2 * piece;
-    }
-    uint4 *const d_points = reinterpret_cast<uint4 *>(c->d_decode_stage), *const d_hits = d_points + (size_t)piece * PCR_POINTS_PER_BATCH;
-    int64_t written = 0;
-    for (int64_t k0 = 0; k0 < nK; k0 += piece) {
-        const int64_t k1 = std::min(nK, k0 + piece);
-        int64_t m = 0;
-        for (int64_t k = k0; k < k1; ++k) m += pl.cnt[(size_t)k];
-        if (m == 0) continue;
-        if ((rc = screen_emit(c, pl, k0, k1, host_points ? d_points : nullptr, host_hits ? d_hits : nullptr))) return rc;
-        if (host_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
-        if (host_hits) HIP_TRY(c, hipMemcpyAsync(host_hits + written, d_hits, (size_t)m * sizeof(pcr_screen_hit), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        written += m;
-    }
-    return PCR_OK;
+    return screen_call(c, p, rect, KeptOut{true, host_points, capacity, {hits_column(host_hits)}}, out_count, stats);
 }
 
 int pcr_pick(pcr_ctx *c, const pcr_render_params *p, int px, int py, int radius, pcr_point *out_point, pcr_screen_hit *out_hit, int *out_found)
@@ -4406,13 +4172,11 @@ int pcr_pick(pcr_ctx *c, const pcr_render_params *p, int px, int py, int radius,
     HIP_TRY(c, hipMemsetAsync(c->d_pick, 0xFF, PICK_WORDS * sizeof(unsigned long long), c->stream));
     const StreamView s = make_stream_view(c);
     const dim3 grid((unsigned)nK), block(PCR_WORKGROUP_SIZE);
-    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
-#define PCR_LAUNCH(L, B) do { hipLaunchKernelGGL((k_pick<L, B, false>), grid, block, 0, c->stream, s, c->d_scr_list, pl.q, c->d_pick); \
-                              hipLaunchKernelGGL((k_pick<L, B, true>), grid, block, 0, c->stream, s, c->d_scr_list, pl.q, c->d_pick); \
-                              hipLaunchKernelGGL((k_pick_fetch<L, B>), dim3(1), block, 0, c->stream, s, c->d_screen_lod, pl.q, c->d_pick); } while (0)
-    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
-    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
-#undef PCR_LAUNCH
+    for_layout_bc7(c, [&](auto layout, auto bc7) {
+        hipLaunchKernelGGL((k_pick<layout.value, bc7.value, false>), grid, block, 0, c->stream, s, c->scr.list, pl.q, c->d_pick);
+        hipLaunchKernelGGL((k_pick<layout.value, bc7.value, true>), grid, block, 0, c->stream, s, c->scr.list, pl.q, c->d_pick);
+        hipLaunchKernelGGL((k_pick_fetch<layout.value, bc7.value>), dim3(1), block, 0, c->stream, s, c->d_screen_lod, pl.q, c->d_pick);
+    });
     HIP_TRY(c, hipGetLastError());
     unsigned long long h[PICK_WORDS];
     HIP_TRY(c, hipMemcpyAsync(h, c->d_pick, sizeof h, hipMemcpyDeviceToHost, c->stream));
@@ -4444,37 +4208,29 @@ int visible_scratch(pcr_ctx *c, size_t npix, int64_t nK)
             return set_err(c, PCR_E_NOMEM, "out of device memory for the planes of %zu pixels", npix);
         c->vis_pixels = npix;
     }
-    if (c->vis_capacity < nK) {
-        dfree(c->d_vis_totals); c->vis_capacity = 0;
-        if (hipMalloc((void **)&c->d_vis_totals, (size_t)nK * 3 * 4) != hipSuccess)
-            return set_err(c, PCR_E_NOMEM, "out of device memory for the totals of %lld batches", (long long)nK);
-        c->vis_capacity = nK;
-    }
-    return PCR_OK;
+    return nK ? reserve(c, c->d_vis_totals, c->vis_capacity, nK * 3, "totals of the kept batches (three each)") : (int)PCR_OK;
 }
 
-// The checks, the planes and the counts. *done: nothing left to write (an error, a count-only call, no records). The depth
-// plane goes to `depth` (device or host memory) unless the call is refused.
-int visible_prepare(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect, int mode, int radius, const void *points, const void *hits, void *depth,
-                    size_t align_points, size_t align_hits, size_t capacity, int64_t *out_count, pcr_visible_stats *stats, VisiblePlan &vp, bool *done)
+// pcr_select_visible / pcr_read_visible: the planes, the counts, then the records to o.points and their hits to column 0. The
+// depth plane goes to `depth` (memory of the form's side) unless the call is refused.
+int visible_call(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect, int mode, int radius, const KeptOut &o, void *depth, int64_t *out_count,
+                 pcr_visible_stats *stats)
 {
-    *done = true;
-    if (out_count) *out_count = 0;
-    int rc = check_params(c, p);
-    if (rc) return rc;
-    if (!out_count) return set_err(c, PCR_E_ARG, "out_count is NULL");
+    if (!c) return PCR_E_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    VisiblePlan vp;
+    ScreenPlan &pl = vp.pl;
+    int64_t nB = 0;
+    bool done = true;
+    int rc = kept_begin(c, 0, -1, o, out_count, &nB);                           // (the range: every resident batch)
+    if (rc || (rc = check_params(c, p))) return rc;
     if (mode != PCR_VISIBLE_FRONT && mode != PCR_VISIBLE_SURFACE) return set_err(c, PCR_E_ARG, "unknown mode %d (PCR_VISIBLE_FRONT or PCR_VISIBLE_SURFACE)", mode);
     if (radius < 0 || radius > PCR_VISIBLE_MAX_RADIUS) return set_err(c, PCR_E_ARG, "radius must be 0 .. %d", PCR_VISIBLE_MAX_RADIUS);
-    if (points && reinterpret_cast<uintptr_t>(points) % align_points != 0) return set_err(c, PCR_E_ARG, "the destination of the points is misaligned (%zu bytes)", align_points);
-    if (hits && reinterpret_cast<uintptr_t>(hits) % align_hits != 0) return set_err(c, PCR_E_ARG, "the destination of the hits is misaligned (%zu bytes)", align_hits);
     if (depth && reinterpret_cast<uintptr_t>(depth) % alignof(uint32_t) != 0) return set_err(c, PCR_E_ARG, "the destination of the depth plane is misaligned (4 bytes)");
-    if (c->async_upload) poll_loader(c, false);
-    ScreenPlan &pl = vp.pl;
-    const int64_t nB = c->visible_batches();
     const size_t npix = (size_t)p->width * (size_t)p->height;
     vp.front = mode == PCR_VISIBLE_FRONT;
     vp.st = pcr_visible_stats{nB, 0, 0, 0, 0, 0};
-    const bool some = rect ? screen_clip(p, rect->x0, rect->y0, rect->x1, rect->y1, pl.q) : screen_clip(p, 0, 0, p->width - 1, p->height - 1, pl.q);
+    const bool some = screen_rect(p, rect, pl.q);
     if (nB > 0 && (rc = screen_list(c, p, nB, pl))) return rc;
     const int64_t nK = (int64_t)pl.kept.size();
     vp.st.batches_decoded = nK; vp.st.batches_skipped = nB - nK;
@@ -4486,15 +4242,12 @@ int visible_prepare(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect
     HIP_TRY(c, hipMemsetAsync(d_covered, 0, 8, c->stream));
     const StreamView s = make_stream_view(c);
     const dim3 grid((unsigned)nK), block(PCR_WORKGROUP_SIZE);
-    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7, windows = select_reads_windows(c);
     uint32_t *const d_hit_totals = c->d_vis_totals, *const d_totals = c->d_vis_totals + nK;
     if (nK > 0) {
         // (SURFACE reads the keys' depth halves only: the colourless decode)
-#define PCR_LAUNCH(L, C) hipLaunchKernelGGL((k_visible_key<L, C>), grid, block, 0, c->stream, s, c->d_scr_list, pl.q, c->d_vis_key, d_hit_totals)
-#define PCR_LAUNCH_COLOUR(L) do { if (!vp.front) PCR_LAUNCH(L, SEL_NO_COLOUR); else if (bc7) PCR_LAUNCH(L, SEL_BC7); else PCR_LAUNCH(L, SEL_BC1); } while (0)
-        if (windows) PCR_LAUNCH_COLOUR(LAYOUT_POINT_WINDOWS); else PCR_LAUNCH_COLOUR(LAYOUT_WORDS);
-#undef PCR_LAUNCH_COLOUR
-#undef PCR_LAUNCH
+        for_layout_colour(c, vp.front, [&](auto layout, auto colour) {
+            hipLaunchKernelGGL((k_visible_key<layout.value, colour.value>), grid, block, 0, c->stream, s, c->scr.list, pl.q, c->d_vis_key, d_hit_totals);
+        });
         HIP_TRY(c, hipGetLastError());
     }
     const dim3 dgrid((unsigned)std::min<size_t>((npix + VIS_DILATE_THREADS - 1) / VIS_DILATE_THREADS, 4096)), dblock(VIS_DILATE_THREADS);
@@ -4505,15 +4258,14 @@ int visible_prepare(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect
     if (count) {
         if (vp.front) {
             HIP_TRY(c, hipMemsetAsync(c->d_vis_index, 0xFF, npix * 8, c->stream));
-#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_visible_index<L, B>), grid, block, 0, c->stream, s, c->d_scr_list, pl.q, c->d_vis_key, c->d_vis_index)
-            if (windows) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
-            else         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
-#undef PCR_LAUNCH
+            for_layout_bc7(c, [&](auto layout, auto bc7) {
+                hipLaunchKernelGGL((k_visible_index<layout.value, bc7.value>), grid, block, 0, c->stream, s, c->scr.list, pl.q, c->d_vis_key, c->d_vis_index);
+            });
         }
-        if (windows) hipLaunchKernelGGL((k_visible_count<LAYOUT_POINT_WINDOWS>), grid, block, 0, c->stream, s, c->d_scr_list, pl.q, vp.front, c->d_vis_depth,
-                                        c->d_vis_index, c->d_scr_counts, d_totals);
-        else         hipLaunchKernelGGL((k_visible_count<LAYOUT_WORDS>), grid, block, 0, c->stream, s, c->d_scr_list, pl.q, vp.front, c->d_vis_depth,
-                                        c->d_vis_index, c->d_scr_counts, d_totals);
+        for_layout(c, [&](auto layout) {
+            hipLaunchKernelGGL((k_visible_count<layout.value>), grid, block, 0, c->stream, s, c->scr.list, pl.q, vp.front, c->d_vis_depth, c->d_vis_index,
+                               c->scr.counts, d_totals);
+        });
         HIP_TRY(c, hipGetLastError());
     }
     std::vector<uint32_t> totals((size_t)nK * 3);
@@ -4529,88 +4281,32 @@ int visible_prepare(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect
         vp.st.selected += totals[(size_t)(nK + 2 * k)];
         vp.st.candidates += totals[(size_t)(nK + 2 * k + 1)];
     }
-    *out_count = vp.st.selected;
-    if (stats) *stats = vp.st;
-    if ((points || hits) && capacity < (size_t)vp.st.selected)
-        return set_err(c, PCR_E_ARG, "capacity of %zu records is below the %lld selected", capacity, (long long)vp.st.selected);
+    if ((rc = kept_finish(c, o, vp.st.selected, "selected", vp.st, out_count, stats, &done))) return rc;
     if (depth) {
         HIP_TRY(c, hipMemcpyAsync(depth, c->d_vis_depth, npix * 4, hipMemcpyDefault, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
-    if ((!points && !hits) || vp.st.selected == 0) return PCR_OK;
-    *done = false;
-    return PCR_OK;
-}
-
-// screen_emit for the selected hits of kept batches [k0, k1). The caller synchronises.
-int visible_emit(pcr_ctx *c, VisiblePlan &vp, int64_t k0, int64_t k1, uint4 *points, uint4 *hits)
-{
-    ScreenPlan &pl = vp.pl;
-    pl.offsets.clear();
-    int64_t off = 0;
-    for (int64_t k = k0; k < k1; ++k) { pl.offsets.push_back(off); off += pl.cnt[(size_t)k]; }
-    if (off == 0) return PCR_OK;
-    HIP_TRY(c, hipMemcpyAsync(c->d_scr_offsets + k0, pl.offsets.data(), (size_t)(k1 - k0) * 8, hipMemcpyHostToDevice, c->stream));
-    const StreamView s = make_stream_view(c);
-    const dim3 grid((unsigned)(k1 - k0)), block(PCR_WORKGROUP_SIZE);
-    const bool bc7 = c->color_bytes == PCR_COLOR_BYTES_PER_BATCH_BC7;
-#define PCR_LAUNCH(L, B) hipLaunchKernelGGL((k_visible_write<L, B>), grid, block, 0, c->stream, s, c->d_scr_list + k0, pl.q, vp.front, c->d_vis_depth, \
-                                            c->d_vis_index, c->d_scr_counts + k0 * PCR_WORKGROUP_SIZE, c->d_scr_offsets + k0, points, hits)
-    if (select_reads_windows(c)) { if (bc7) PCR_LAUNCH(LAYOUT_POINT_WINDOWS, true); else PCR_LAUNCH(LAYOUT_POINT_WINDOWS, false); }
-    else                         { if (bc7) PCR_LAUNCH(LAYOUT_WORDS, true); else PCR_LAUNCH(LAYOUT_WORDS, false); }
-#undef PCR_LAUNCH
-    HIP_TRY(c, hipGetLastError());
-    return PCR_OK;
+    if (done) return PCR_OK;
+    return listed_write(c, pl.cnt, pl.offsets, c->scr.offsets, o, [&](int64_t k0, dim3 wgrid, const KeptOut &d) {
+        for_layout_bc7(c, [&](auto layout, auto bc7) {
+            hipLaunchKernelGGL((k_visible_write<layout.value, bc7.value>), wgrid, block, 0, c->stream, s, c->scr.list + k0, pl.q, vp.front, c->d_vis_depth,
+                               c->d_vis_index, c->scr.counts + k0 * PCR_WORKGROUP_SIZE, c->scr.offsets + k0, static_cast<uint4 *>(d.points),
+                               static_cast<uint4 *>(d.col[0].dst));
+        });
+    });
 }
 } // namespace
 
 int pcr_select_visible(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect, int mode, int radius, void *dev_points, void *dev_hits, void *dev_depth,
                        size_t capacity, int64_t *out_count, pcr_visible_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    VisiblePlan vp;
-    bool done = true;
-    int rc = visible_prepare(c, p, rect, mode, radius, dev_points, dev_hits, dev_depth, 16, 16, capacity, out_count, stats, vp, &done);
-    if (rc || done) return rc;
-    if ((rc = visible_emit(c, vp, 0, (int64_t)vp.pl.kept.size(), static_cast<uint4 *>(dev_points), static_cast<uint4 *>(dev_hits)))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PCR_OK;
+    return visible_call(c, p, rect, mode, radius, KeptOut{false, dev_points, capacity, {hits_column(dev_hits)}}, dev_depth, out_count, stats);
 }
 
 int pcr_read_visible(pcr_ctx *c, const pcr_render_params *p, const pcr_rect *rect, int mode, int radius, pcr_point *host_points, pcr_screen_hit *host_hits,
                      uint32_t *host_depth, size_t capacity, int64_t *out_count, pcr_visible_stats *stats)
 {
-    if (!c) return PCR_E_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    VisiblePlan vp;
-    bool done = true;
-    int rc = visible_prepare(c, p, rect, mode, radius, host_points, host_hits, host_depth, alignof(pcr_point), alignof(pcr_screen_hit), capacity, out_count,
-                             stats, vp, &done);
-    if (rc || done) return rc;
-    // pieces as pcr_read_screen's: a piece's points in the first half of the decode staging buffer, its hits in the second
-    const int64_t nK = (int64_t)vp.pl.kept.size();
-    const int64_t piece = std::min<int64_t>(nK, DECODE_STAGE_BATCHES / 2);
-    if (!c->d_decode_stage || c->decode_stage_batches < 2 * piece) {
-        dfree(c->d_decode_stage); c->decode_stage_batches = 0;
-        if (hipMalloc((void **)&c->d_decode_stage, (size_t)(2 * piece) * PCR_POINTS_PER_BATCH * sizeof(pcr_point)) != hipSuccess)
-            return set_err(c, PCR_E_NOMEM, "out of device memory for a staging buffer of %lld batches of points", (long long)(2 * piece));
-        c->decode_stage_batches = 2 * piece;
-    }
-    uint4 *const d_points = reinterpret_cast<uint4 *>(c->d_decode_stage), *const d_hits = d_points + (size_t)piece * PCR_POINTS_PER_BATCH;
-    int64_t written = 0;
-    for (int64_t k0 = 0; k0 < nK; k0 += piece) {
-        const int64_t k1 = std::min(nK, k0 + piece);
-        int64_t m = 0;
-        for (int64_t k = k0; k < k1; ++k) m += vp.pl.cnt[(size_t)k];
-        if (m == 0) continue;
-        if ((rc = visible_emit(c, vp, k0, k1, host_points ? d_points : nullptr, host_hits ? d_hits : nullptr))) return rc;
-        if (host_points) HIP_TRY(c, hipMemcpyAsync(host_points + written, d_points, (size_t)m * sizeof(pcr_point), hipMemcpyDeviceToHost, c->stream));
-        if (host_hits) HIP_TRY(c, hipMemcpyAsync(host_hits + written, d_hits, (size_t)m * sizeof(pcr_screen_hit), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        written += m;
-    }
-    return PCR_OK;
+    return visible_call(c, p, rect, mode, radius, KeptOut{true, host_points, capacity, {hits_column(host_hits)}}, host_depth, out_count, stats);
 }
 
 // ---- multi-GPU plumbing ------------------------------------------------------------------------

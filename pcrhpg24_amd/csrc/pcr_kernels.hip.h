@@ -2190,6 +2190,27 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_point_bounds(StreamView 
     }
 }
 
+// The write kernels' place of a chain among the chains of its workgroup, from each chain's count `mine`: the inclusive prefix inside
+// the wave, whose last lane leaves the wave's sum in s_part; then, once a barrier has published s_part, the count of every chain
+// before this one
+__device__ __forceinline__ uint32_t chain_prefix_in_wave(uint32_t mine, uint32_t lane, uint32_t wave, uint32_t *s_part)
+{
+    uint32_t incl = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += up;
+    }
+    if (lane == 63) s_part[wave] = incl;
+    return incl;
+}
+__device__ __forceinline__ uint32_t chain_prefix_before(uint32_t incl, uint32_t mine, uint32_t wave, const uint32_t *s_part)
+{
+    uint32_t before = incl - mine;
+    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    return before;
+}
+
 // Workgroup x takes the straddling batch list[x]: chain_counts[x * 1024 + chain] = its points inside q, totals[x] = their sum
 template <int LAYOUT>
 __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_select_count(StreamView s, const uint32_t *list, pcr_box q, uint32_t *chain_counts, uint32_t *totals)
@@ -2226,16 +2247,9 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_select_write(StreamView 
     __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
     __shared__ uint32_t s_part[LWC_WAVES];
     const uint32_t mine = chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid];
-    uint32_t incl = mine;                                   // inclusive prefix inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d) incl += up;
-    }
-    if (lane == 63) s_part[wave] = incl;
+    const uint32_t incl = chain_prefix_in_wave(mine, lane, wave, s_part);
     load_packed_table(s, b, s_table);                       // (its barrier publishes s_part as well)
-    uint32_t before = incl - mine;
-    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    const uint32_t before = chain_prefix_before(incl, mine, wave, s_part);
     uint4 *dst = out + offsets[blockIdx.x] + before;
     uint4 *const end = dst + mine;                          // never past what k_select_count counted for this chain
     decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t colour) {
@@ -2332,16 +2346,9 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_polygon_write(StreamView
     uint32_t *s_table = reinterpret_cast<uint32_t *>(s_dyn);
     int4 *s_edges = reinterpret_cast<int4 *>(s_dyn + POLY_TABLE_BYTES);
     const uint32_t mine = chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid];
-    uint32_t incl = mine;                                   // inclusive prefix inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d) incl += up;
-    }
-    if (lane == 63) s_part[wave] = incl;
+    const uint32_t incl = chain_prefix_in_wave(mine, lane, wave, s_part);
     if (!load_polygon_batch(s, a, pb, s_table, s_edges)) return;            // (its barrier publishes s_part as well)
-    uint32_t before = incl - mine;
-    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    const uint32_t before = chain_prefix_before(incl, mine, wave, s_part);
     uint4 *dst = out + offsets[blockIdx.x] + before;
     uint4 *const end = dst + mine;                          // never past what k_polygon_count counted for this chain
     decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, pb.b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t colour) {
@@ -2446,17 +2453,10 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_slab_write(StreamView s,
     int4 *s_slabs = reinterpret_cast<int4 *>(s_dyn + SLAB_TABLE_BYTES);
     if (sb.count > a.lds_slabs) return;
     const uint32_t mine = chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid];
-    uint32_t incl = mine;                                   // inclusive prefix inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d) incl += up;
-    }
-    if (lane == 63) s_part[wave] = incl;
+    const uint32_t incl = chain_prefix_in_wave(mine, lane, wave, s_part);
     load_slab_slice(a.slabs, sb.first, sb.count, s_slabs);
     load_packed_table(s, sb.b, s_table);                    // (its barrier publishes s_part and the slice as well)
-    uint32_t before = incl - mine;
-    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    const uint32_t before = chain_prefix_before(incl, mine, wave, s_part);
     uint4 *dst = out + offsets[blockIdx.x] + before;
     uint4 *const end = dst + mine;                          // never past what k_slab_count counted for this chain
     decode_chain<LAYOUT, BC7 ? SEL_BC7 : SEL_BC1>(s, sb.b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t colour) {
@@ -3206,16 +3206,9 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_height_write(StreamView 
     __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
     __shared__ uint32_t s_part[LWC_WAVES];
     const uint32_t mine = chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid];
-    uint32_t incl = mine;                                   // inclusive prefix inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d) incl += up;
-    }
-    if (lane == 63) s_part[wave] = incl;
+    const uint32_t incl = chain_prefix_in_wave(mine, lane, wave, s_part);
     load_packed_table(s, b, s_table);                       // (its barrier publishes s_part as well)
-    uint32_t before = incl - mine;
-    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    const uint32_t before = chain_prefix_before(incl, mine, wave, s_part);
     const int64_t first = offsets[blockIdx.x] + before;
     uint32_t k = 0;                                         // never past what k_height_count counted for this chain
     decode_chain<LAYOUT, COLOUR>(s, b, s_table, [&](int, int32_t x, int32_t y, int32_t z, uint32_t colour) {
@@ -3379,16 +3372,9 @@ __device__ __forceinline__ void write_kept_rows(const StreamView &s, const uint3
     __shared__ uint32_t s_part[LWC_WAVES];
     const thin_u64 word = keep[(size_t)(b - first_batch) * PCR_WORKGROUP_SIZE + tid];
     const uint32_t mine = (uint32_t)__popcll(word);
-    uint32_t incl = mine;                                   // inclusive prefix inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d) incl += up;
-    }
-    if (lane == 63) s_part[wave] = incl;
+    const uint32_t incl = chain_prefix_in_wave(mine, lane, wave, s_part);
     load_packed_table(s, b, s_table);                       // (its barrier publishes s_part as well)
-    uint32_t before = incl - mine;
-    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    const uint32_t before = chain_prefix_before(incl, mine, wave, s_part);
     int64_t dst = offsets[blockIdx.x] + before;
     const int64_t end = dst + mine;                         // never past the bits of this chain's word
     const int64_t row0 = (int64_t)(b - first_batch) * PCR_POINTS_PER_BATCH + (int64_t)tid * PCR_POINTS_PER_THREAD;
@@ -3547,7 +3533,7 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_lod_write(StreamView s, 
     lod_load_bytes(a.level, (thin_u64)row0, w);
     for (uint32_t l = 0; l < a.classes; ++l) {
         const uint32_t mine = lod_count_level(w, l);
-        uint32_t incl = mine;                               // inclusive prefix inside the wave
+        uint32_t incl = mine;                               // chain_prefix_in_wave spelled out: on it every instantiation compiles to another stream
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
             const uint32_t up = __shfl_up(incl, d, 64);
@@ -3969,16 +3955,9 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_components_labels(Stream
     __shared__ uint32_t s_part[LWC_WAVES];
     const thin_u64 word = keep[(size_t)(b - a.first_batch) * PCR_WORKGROUP_SIZE + tid];
     const uint32_t mine = (uint32_t)__popcll(word);
-    uint32_t incl = mine;                                   // inclusive prefix inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d) incl += up;
-    }
-    if (lane == 63) s_part[wave] = incl;
+    const uint32_t incl = chain_prefix_in_wave(mine, lane, wave, s_part);
     load_packed_table(s, b, s_table);                       // (its barrier publishes s_part as well)
-    uint32_t before = incl - mine;
-    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    const uint32_t before = chain_prefix_before(incl, mine, wave, s_part);
     int64_t dst = offsets[blockIdx.x] + before;
     const int64_t end = dst + mine;                         // never past the bits of this chain's word
     thin_u64 prev = THIN_EMPTY;
@@ -4252,16 +4231,9 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_neighbors_write(StreamVi
     __shared__ uint32_t s_part[LWC_WAVES];
     const thin_u64 word = keep[(size_t)(b - first_batch) * PCR_WORKGROUP_SIZE + tid];
     const uint32_t mine = (uint32_t)__popcll(word);
-    uint32_t incl = mine;                                   // inclusive prefix inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d) incl += up;
-    }
-    if (lane == 63) s_part[wave] = incl;
+    const uint32_t incl = chain_prefix_in_wave(mine, lane, wave, s_part);
     load_packed_table(s, b, s_table);                       // (its barrier publishes s_part as well)
-    uint32_t before = incl - mine;
-    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    const uint32_t before = chain_prefix_before(incl, mine, wave, s_part);
     int64_t dst = offsets[blockIdx.x] + before;
     const int64_t end = dst + mine;                         // never past the bits of this chain's word
     const int64_t row0 = (int64_t)(b - first_batch) * PCR_POINTS_PER_BATCH + (int64_t)tid * PCR_POINTS_PER_THREAD;
@@ -4507,16 +4479,9 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_moments_write(StreamView
     __shared__ uint32_t s_part[LWC_WAVES];
     const thin_u64 word = keep[(size_t)(b - first_batch) * PCR_WORKGROUP_SIZE + tid];
     const uint32_t mine = (uint32_t)__popcll(word);
-    uint32_t incl = mine;                                   // inclusive prefix inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d) incl += up;
-    }
-    if (lane == 63) s_part[wave] = incl;
+    const uint32_t incl = chain_prefix_in_wave(mine, lane, wave, s_part);
     load_packed_table(s, b, s_table);                       // (its barrier publishes s_part as well)
-    uint32_t before = incl - mine;
-    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    const uint32_t before = chain_prefix_before(incl, mine, wave, s_part);
     int64_t dst = offsets[blockIdx.x] + before;
     const int64_t end = dst + mine;                         // never past the bits of this chain's word
     const int64_t row0 = (int64_t)(b - first_batch) * PCR_POINTS_PER_BATCH + (int64_t)tid * PCR_POINTS_PER_THREAD;
@@ -4711,16 +4676,9 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_voxel_prefix(const uint3
     __shared__ uint32_t s_part[LWC_WAVES];
     const size_t at = (size_t)(b - first_batch) * PCR_WORKGROUP_SIZE + tid;
     const uint32_t mine = (uint32_t)__popcll(keep[at]);
-    uint32_t incl = mine;                                   // inclusive prefix inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d) incl += up;
-    }
-    if (lane == 63) s_part[wave] = incl;
+    const uint32_t incl = chain_prefix_in_wave(mine, lane, wave, s_part);
     __syncthreads();
-    uint32_t before = incl - mine;
-    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    const uint32_t before = chain_prefix_before(incl, mine, wave, s_part);
     prefix[at] = (thin_u64)offsets[blockIdx.x] + before;
 }
 
@@ -4938,16 +4896,9 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_screen_write(StreamView 
     __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
     __shared__ uint32_t s_part[LWC_WAVES];
     const uint32_t mine = chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid];
-    uint32_t incl = mine;                                   // inclusive prefix inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d) incl += up;
-    }
-    if (lane == 63) s_part[wave] = incl;
+    const uint32_t incl = chain_prefix_in_wave(mine, lane, wave, s_part);
     load_packed_table(s, e.b, s_table);                     // (its barrier publishes s_part as well)
-    uint32_t before = incl - mine;
-    for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
+    const uint32_t before = chain_prefix_before(incl, mine, wave, s_part);
     const ScreenBatch B = screen_batch(s, e.b, e.lod);
     const int64_t first = offsets[blockIdx.x] + before;
     const uint64_t index0 = (uint64_t)e.b * PCR_POINTS_PER_BATCH + (uint64_t)tid * PCR_POINTS_PER_THREAD;
@@ -5183,7 +5134,7 @@ __global__ void __launch_bounds__(PCR_WORKGROUP_SIZE) k_visible_write(StreamView
     __shared__ __align__(16) uint32_t s_table[PCR_HUFFMAN_TABLE_SIZE];
     __shared__ uint32_t s_part[LWC_WAVES];
     const uint32_t mine = chain_counts[(size_t)blockIdx.x * PCR_WORKGROUP_SIZE + tid];
-    uint32_t incl = mine;                                   // inclusive prefix inside the wave
+    uint32_t incl = mine;                                   // chain_prefix_in_wave spelled out: on it <POINT_WINDOWS, false> compiles to another stream
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const uint32_t up = __shfl_up(incl, d, 64);

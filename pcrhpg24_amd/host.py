@@ -1094,68 +1094,28 @@ class Context:
         `out`: a contiguous int32 CUDA tensor to fill; it has to hold the result (PcrError if not; select_stats then tells
         the count). Without it the call counts first and allocates exactly. Stream ordering as decode_points. The batch
         classes and the count of the last call are in self.select_stats."""
-        import torch
-        box = as_box(box)
-        dev = torch.device("cuda", self.device)
-        cnt, st, nb = c_i64(), N.SelectStats(), -1 if count is None else count
-        if out is None:
-            self._chk(self.lib.pcr_select_box(self.h, first, nb, C.byref(box), None, 0, C.byref(cnt), C.byref(st)), "pcr_select_box")
-            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
-        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
-        torch.cuda.current_stream(dev).synchronize()
-        rc = self.lib.pcr_select_box(self.h, first, nb, C.byref(box), C.c_void_p(out.data_ptr() if out.numel() else None), out.numel() // 4,
-                                     C.byref(cnt), C.byref(st))
-        self.select_stats = st.as_dict()
-        if rc:
-            self.select_stats["points_selected"] = cnt.value
-        self._chk(rc, "pcr_select_box")
-        return out.view(-1, 4)[:cnt.value]
+        args = (first, -1 if count is None else count, C.byref(as_box(box)))
+        return self._kept_device(self.lib.pcr_select_box, args, N.SelectStats, "select_stats", "points_selected", out, [])
 
     def read_box(self, box, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """The same on the host, without torch: a numpy structured array of POINT_DTYPE (pcr_read_box: a counting call, then
         the read; synchronises)."""
-        box = as_box(box)
-        cnt, st, nb = c_i64(), N.SelectStats(), -1 if count is None else count
-        self._chk(self.lib.pcr_read_box(self.h, first, nb, C.byref(box), None, 0, C.byref(cnt), C.byref(st)), "pcr_read_box")
-        out = np.empty(cnt.value, POINT_DTYPE)
-        if cnt.value:
-            self._chk(self.lib.pcr_read_box(self.h, first, nb, C.byref(box), out.ctypes.data, len(out), C.byref(cnt), C.byref(st)), "pcr_read_box")
-        self.select_stats = st.as_dict()
-        return out
+        args = (first, -1 if count is None else count, C.byref(as_box(box)))
+        return self._kept_host(self.lib.pcr_read_box, args, N.SelectStats, "select_stats", [])
 
     # -- polygon selection (pcr_select_polygon / pcr_read_polygon) ------------------------------------------
     def select_polygon(self, poly: Polygon, first: int = 0, count: Optional[int] = None, out=None):
         """The points of batches [first, first + count) inside the prism `poly` (a Polygon) as a torch.int32 tensor [n, 4] on the
         context's device: select_box with the polygon's predicate, `out` and the stream ordering as there. The batch classes,
         the count and the edge-list sizes of the last call are in self.polygon_stats."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        cnt, st, nb = c_i64(), N.PolygonStats(), -1 if count is None else count
-        if out is None:
-            self._chk(self.lib.pcr_select_polygon(self.h, first, nb, C.byref(poly.c), None, 0, C.byref(cnt), C.byref(st)), "pcr_select_polygon")
-            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
-        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
-        torch.cuda.current_stream(dev).synchronize()
-        rc = self.lib.pcr_select_polygon(self.h, first, nb, C.byref(poly.c), C.c_void_p(out.data_ptr() if out.numel() else None), out.numel() // 4,
-                                         C.byref(cnt), C.byref(st))
-        self.polygon_stats = st.as_dict()
-        if rc:
-            self.polygon_stats["points_selected"] = cnt.value
-        self._chk(rc, "pcr_select_polygon")
-        return out.view(-1, 4)[:cnt.value]
+        args = (first, -1 if count is None else count, C.byref(poly.c))
+        return self._kept_device(self.lib.pcr_select_polygon, args, N.PolygonStats, "polygon_stats", "points_selected", out, [])
 
     def read_polygon(self, poly: Polygon, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """The same on the host, without torch: a numpy structured array of POINT_DTYPE (pcr_read_polygon: a counting call, then
         the read; synchronises)."""
-        cnt, st, nb = c_i64(), N.PolygonStats(), -1 if count is None else count
-        self._chk(self.lib.pcr_read_polygon(self.h, first, nb, C.byref(poly.c), None, 0, C.byref(cnt), C.byref(st)), "pcr_read_polygon")
-        out = np.empty(cnt.value, POINT_DTYPE)
-        if cnt.value:
-            self._chk(self.lib.pcr_read_polygon(self.h, first, nb, C.byref(poly.c), out.ctypes.data, len(out), C.byref(cnt), C.byref(st)), "pcr_read_polygon")
-        self.polygon_stats = st.as_dict()
-        return out
+        args = (first, -1 if count is None else count, C.byref(poly.c))
+        return self._kept_host(self.lib.pcr_read_polygon, args, N.PolygonStats, "polygon_stats", [])
 
     # -- slabs (pcr_plane_support / pcr_select_slabs / pcr_read_slabs) -----------------------------------------
     def plane_support(self, hyp, clip=None, exclude=(), first: int = 0, count: Optional[int] = None) -> np.ndarray:
@@ -1172,46 +1132,26 @@ class Context:
         self.plane_stats = st.as_dict()
         return out
 
+    @staticmethod
+    def _slab_args(slabs, clip, invert: bool, first: int, count: Optional[int]):
+        """What pcr_select_slabs / pcr_read_slabs take between the context and the destination."""
+        s = as_slabs(slabs)
+        box = None if clip is None else as_box(clip)
+        return (first, -1 if count is None else count, s, len(s), None if box is None else C.byref(box), N.SLAB_INVERT if invert else 0)
+
     def select_slabs(self, slabs, clip=None, invert: bool = False, first: int = 0, count: Optional[int] = None, out=None):
         """The points of batches [first, first + count) inside `clip` (as_box; None: all) that are in all of `slabs` (a sequence of
         1 to 16 Slab) -- with invert=True those inside the clip that are not -- as a torch.int32 tensor [n, 4] on the context's
         device: select_box with another predicate, `out` and the stream ordering as there. The batch classes, the count and the
         slab-list sizes of the last call are in self.slab_stats."""
-        import torch
-        s = as_slabs(slabs)
-        box = None if clip is None else as_box(clip)
-        pbox = None if box is None else C.byref(box)
-        flags = N.SLAB_INVERT if invert else 0
-        dev = torch.device("cuda", self.device)
-        cnt, st, nb = c_i64(), N.SlabStats(), -1 if count is None else count
-        if out is None:
-            self._chk(self.lib.pcr_select_slabs(self.h, first, nb, s, len(s), pbox, flags, None, 0, C.byref(cnt), C.byref(st)), "pcr_select_slabs")
-            out = torch.empty((cnt.value, 4), dtype=torch.int32, device=dev)
-        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out must be a contiguous int32 tensor on {dev}")
-        torch.cuda.current_stream(dev).synchronize()
-        rc = self.lib.pcr_select_slabs(self.h, first, nb, s, len(s), pbox, flags, C.c_void_p(out.data_ptr() if out.numel() else None), out.numel() // 4,
-                                       C.byref(cnt), C.byref(st))
-        self.slab_stats = st.as_dict()
-        if rc:
-            self.slab_stats["points_selected"] = cnt.value
-        self._chk(rc, "pcr_select_slabs")
-        return out.view(-1, 4)[:cnt.value]
+        args = self._slab_args(slabs, clip, invert, first, count)
+        return self._kept_device(self.lib.pcr_select_slabs, args, N.SlabStats, "slab_stats", "points_selected", out, [])
 
     def read_slabs(self, slabs, clip=None, invert: bool = False, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """The same on the host, without torch: a numpy structured array of POINT_DTYPE (pcr_read_slabs: a counting call, then
         the read; synchronises)."""
-        s = as_slabs(slabs)
-        box = None if clip is None else as_box(clip)
-        pbox = None if box is None else C.byref(box)
-        flags = N.SLAB_INVERT if invert else 0
-        cnt, st, nb = c_i64(), N.SlabStats(), -1 if count is None else count
-        self._chk(self.lib.pcr_read_slabs(self.h, first, nb, s, len(s), pbox, flags, None, 0, C.byref(cnt), C.byref(st)), "pcr_read_slabs")
-        out = np.empty(cnt.value, POINT_DTYPE)
-        if cnt.value:
-            self._chk(self.lib.pcr_read_slabs(self.h, first, nb, s, len(s), pbox, flags, out.ctypes.data, len(out), C.byref(cnt), C.byref(st)), "pcr_read_slabs")
-        self.slab_stats = st.as_dict()
-        return out
+        args = self._slab_args(slabs, clip, invert, first, count)
+        return self._kept_host(self.lib.pcr_read_slabs, args, N.SlabStats, "slab_stats", [])
 
     # -- top-down grid (pcr_grid_clear / pcr_grid_accumulate / pcr_grid_unpack / pcr_read_grid) --------------
     def _grid_plane(self, t, bits: int, cells: int, what: str):
@@ -1432,7 +1372,8 @@ class Context:
         self.height_stats = st.as_dict()
         return (pts, hts) if heights else pts
 
-    # -- the calls that write kept rows: the records and a few columns per row (pcr_thin .. pcr_knn) -------------
+    # -- the calls that write kept rows: the records and a few columns per row (pcr_thin .. pcr_knn; without columns the
+    # selections by box, polygon and slabs above) -------------------------------------------------------------
     def _kept_device(self, fn, args, stats, attr: str, key: str, out, extra):
         """The device form of such a call: `fn` with `args` between the context and the destinations, `stats` its statistics
         structure, left as a dict in self.<attr> (its `key` is the count). `out` as Context.thin takes it: without it a counting
@@ -1699,15 +1640,8 @@ class Context:
         """The same on the host, without torch: (points, hits), numpy structured arrays of POINT_DTYPE and HIT_DTYPE
         (pcr_read_screen: a counting call, then the read; synchronises)."""
         rect = as_rect(rect)
-        cnt, st = c_i64(), N.ScreenStats()
-        rp = C.byref(rect) if rect is not None else None
-        self._chk(self.lib.pcr_read_screen(self.h, C.byref(p), rp, None, None, 0, C.byref(cnt), C.byref(st)), "pcr_read_screen")
-        pts, hits = np.empty(cnt.value, POINT_DTYPE), np.empty(cnt.value, HIT_DTYPE)
-        if cnt.value:
-            self._chk(self.lib.pcr_read_screen(self.h, C.byref(p), rp, pts.ctypes.data, hits.ctypes.data, cnt.value, C.byref(cnt), C.byref(st)),
-                      "pcr_read_screen")
-        self.screen_stats = st.as_dict()
-        return pts, hits
+        args = (C.byref(p), C.byref(rect) if rect is not None else None)
+        return self._kept_host(self.lib.pcr_read_screen, args, N.ScreenStats, "screen_stats", [(True, HIT_DTYPE, ())])
 
     def pick(self, p: RenderParams, px: int, py: int, radius: int = 0):
         """The point under pixel (px, py) of a frame of camera `p`: among the select_screen hits within `radius` pixels (a square
